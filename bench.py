@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MI355X subword-tokenizer hot path, one JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--workload headline|bpe_encode|wp_encode|bpe_train|wp_train|bpe_train_1g|mixed_encode]
+
+A plain run sets up, warms up, times K steps, writes its outputs when asked and prints the line, nothing more.  `--full` adds,
+after the timed steps, everything else a workload measures and checks (the legs below: roofline, cpu_baseline, encode_detail,
+parity with the C oracle, and on the headline the wp_encode / mixed_encode / train blocks).  `--dump-outputs DIR` writes what
+the timed path returned in its last step (token ids, offsets, statuses; merges for the training workloads) as DIR/<name>.npy,
+float32 or float64, 64 MB at most (past that a fixed, seeded sample); the inputs are seeded, so two builds compare output for output.
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (one process per GPU; RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment).  Encode shards the corpus
 by sentence: every rank encodes its own S85k-shaped shard with a replicated table and there is NO data-path
 collective (weak scaling); torch.distributed/RCCL is only the barrier and the MAX over ranks of the time.
 
-Default workload `headline` = BOTH halves of BASELINE.json's metric in one line:
+Default workload `headline` = BOTH halves of BASELINE.json's metric in one line (the second half, "train", with --full):
 
   value / unit   FastBPE encode (configs[1]) MB/s of input text (UTF-8, 1 MB = 1e6 B), inputs resident in HBM, first 8,000
                  pretrained merges, measured on TWO seeded stand-ins for the absent data/train-85k.json -- S85k-lex (closed
@@ -105,6 +111,40 @@ def host_cores():
         return os.cpu_count() or 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20261016
+
+
+def merge_arrays(merges):
+    """a merges list [(left, right), ...] of strings as arrays: the two lengths per merge and all code points in order"""
+    cps = "".join(a + b for a, b in merges).encode("utf-32-le", "surrogatepass")
+    return {"merge_left_len": np.array([len(a) for a, _ in merges], dtype=np.int64),
+            "merge_right_len": np.array([len(b) for _, b in merges], dtype=np.int64),
+            "merge_codepoints": np.frombuffer(cps, dtype=np.uint32)}
+
+
+def write_outputs(out_dir, outputs):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 where that holds every value exactly, else float64.  Past
+    DUMP_LIMIT_BYTES in all, the arrays are cut down to the same fixed, seeded sample of their elements (sorted positions)."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a).ravel()
+        exact32 = a.dtype.kind in "biu" and (a.size == 0 or (int(a.min()) > -(1 << 24) and int(a.max()) < (1 << 24)))
+        arrays[name] = a.astype(np.float32 if exact32 or a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # room for the .npy headers
+    if total > budget:
+        keep = budget / total
+        for name, a in arrays.items():
+            k = int(a.size * keep)
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+            arrays[name] = a[pos]
+        log("bench: outputs sampled to %.3f of their elements (seed %d) to stay within %d MB" % (keep, DUMP_SEED, DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def check_frac(roof):
     """a roofline fraction above 1 means the bytes were not moved in that time: refuse to print it"""
     if roof is not None and roof.get("frac") is not None and roof["frac"] > 1.0:
@@ -143,7 +183,9 @@ def encode_corpus_bench(args, torch, dist, rank, N, bpe, sents, merges, name, cp
     total_bytes = sum_over_ranks(torch, dist, float(n_bytes))
     res = {"corpus": name, "mb_s": total_bytes * args.steps / 1e6 / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
            "n_bytes": n_bytes, "n_sent": n_sent, "n_tok": n_tok, "roofline": None, "cpu": None, "detail": None}
-    if args.lean:  # profiling runs (tools/gpu_profile_r02.sh): only the launches of the timed path reach the counters
+    if args.dump_outputs:  # what the last timed step left for its caller (the legs below run the call again)
+        res["outputs"] = {"ids": d_out[:int(d_ntok.item())].cpu().numpy().view(np.uint32), "offsets": d_out_off.cpu().numpy().view(np.uint64)}
+    if args.lean:  # plain runs, and profiling runs (tools/gpu_profile_r02.sh): only the launches of the timed path reach the counters
         N.profile_enable(False)
         return res
     # ---- outside the timed region ----
@@ -309,9 +351,22 @@ def train_bench(args, torch, dist, rank, world, N, sents, max_vocab, name, repea
     N.profile_enable(False)
     if rank != 0:
         return None
+    n_merges = max(len(merges), 1)
+    loop_s = sum(loops) / len(loops)
+    per_merge_s = loop_s / n_merges
+    wall = sum(times) / len(times)
+    parallelism = ("single GPU" if world == 1 and not os.environ.get("SWT_BENCH_FORCE_SHARDED") else
+                   "corpus-sharded x%d over RCCL: per step one tie-message all-gather + one record-block all-gather (%s form)"
+                   % (world, "generic one-merge-per-step" if os.environ.get("SWT_DIST_GENERIC", "0") not in ("", "0") else "fast"))
+    res = {"metric": "BPE train seconds per 1k merges", "s_per_1k_merges": round(wall / n_merges * 1000, 5), "train_wall_s": round(wall, 4),
+           "merge_loop_s": round(loop_s, 4), "us_per_merge_device": round(per_merge_s * 1e6, 2), "n_merges": len(merges),
+           "workload": "FastBPE.train on %s to max_vocab=%d: %d merges" % (name, max_vocab, len(merges)), "parallelism": parallelism}
+    if args.dump_outputs:
+        res["outputs"] = merge_arrays(merges)
+    if args.lean:  # plain runs: no oracle, no roofline
+        return res
     from oracle import oracle as O
 
-    n_merges = max(len(merges), 1)
     orc = O.OracleBPETrainer(sents)
     n0, w0 = orc.n_symbols, orc.n_words
     t1 = time.perf_counter()
@@ -320,21 +375,14 @@ def train_bench(args, torch, dist, rank, world, N, sents, max_vocab, name, repea
     if orc.merges_list != merges[:cpu_sample]:
         raise SystemExit("PARITY FAILURE: device merges differ from the oracle on the first %d merges (%s)" % (cpu_sample, name))
     n_final = int(info["n_symbols"])
-    loop_s = sum(loops) / len(loops)
-    per_merge_s = loop_s / n_merges
-    wall = sum(times) / len(times)
     roof = train_roofline(trace, stats if stats is not None else info, n0, w0, n_final, n_merges, per_merge_s, n_merges * len(loops),
                           12.0 * (n0 + n_final) / 2.0 + 8.0 * w0, world=world, traffic=traffic_from_profile("bpe_train"))
-    return {"metric": "BPE train seconds per 1k merges", "s_per_1k_merges": round(wall / n_merges * 1000, 5), "train_wall_s": round(wall, 4),
-            "merge_loop_s": round(loop_s, 4), "us_per_merge_device": round(per_merge_s * 1e6, 2), "n_merges": len(merges),
-            "workload": "FastBPE.train on %s to max_vocab=%d: %d merges, %d unique words, %d -> %d symbols" % (name, max_vocab, len(merges), w0, n0, n_final),
-            "parallelism": ("single GPU" if world == 1 and not os.environ.get("SWT_BENCH_FORCE_SHARDED") else
-                            "corpus-sharded x%d over RCCL: per step one tie-message all-gather + one record-block all-gather (%s form)"
-                            % (world, "generic one-merge-per-step" if os.environ.get("SWT_DIST_GENERIC", "0") not in ("", "0") else "fast")),
-            "roofline": roof,
-            "cpu_baseline": {"value": round(cpu_s / cpu_sample * 1000, 3), "unit": "s/1k-merges", "cores": 1, "kind": "port",
-                             "sample": "first %d merges of the same run through oracle/swt_oracle.c orc_train_run (the reference's "
-                                       "full recount per merge; its cost per merge falls slowly with N_t)" % cpu_sample}}
+    res["workload"] += ", %d unique words, %d -> %d symbols" % (w0, n0, n_final)
+    res["roofline"] = roof
+    res["cpu_baseline"] = {"value": round(cpu_s / cpu_sample * 1000, 3), "unit": "s/1k-merges", "cores": 1, "kind": "port",
+                           "sample": "first %d merges of the same run through oracle/swt_oracle.c orc_train_run (the reference's "
+                                     "full recount per merge; its cost per merge falls slowly with N_t)" % cpu_sample}
+    return res
 
 
 EMIT = None  # main() installs the function that formats a result as THE JSON line and writes it (rank 0)
@@ -382,9 +430,6 @@ def bench_headline(args, torch, dist, rank, world, local):
     corpora = [("S85k-lex", synth.sentences(85000, 85000 + rank) if rank else synth.s85k()),
                ("S85k-open", synth.sentences_open(85000, 85000 + rank) if rank else synth.s85k_open())]
     runs = [encode_corpus_bench(args, torch, dist, rank, N, bpe, sents, merges, name, cpu_leg=True) for name, sents in corpora]
-    # encode: every rank has its own shard-shaped corpus; training: ONE corpus, which the sharded runner cuts into the ranks'
-    # sentence ranges (train_sharded) -- so every rank must hold the same sentences, rank 0's
-    train_sents = corpora[1][1] if rank == 0 else synth.s85k_open()
     head, other = sorted(runs, key=lambda r: r["mb_s"])
     out = {
         "metric": "FastBPE encode MB/s (value; tokens bit-exact) + BPE train s/1k-merges (train.s_per_1k_merges)",
@@ -399,6 +444,17 @@ def bench_headline(args, torch, dist, rank, world, local):
                          "bytes_per_gpu": other["n_bytes"], "tokens_per_gpu": other["n_tok"], "roofline": other["roofline"],
                          "cpu_baseline": other["cpu"]},
     }
+    if args.dump_outputs:
+        out["outputs"] = {"bpe_%s_%s" % (r["corpus"][5:], k): a for r in runs for k, a in r.pop("outputs").items()}
+    if args.lean:  # a plain run: the two timed encodes and nothing else
+        for k in ("roofline", "cpu_baseline", "encode_detail"):
+            del out[k]
+        for k in ("roofline", "cpu_baseline"):
+            del out["other_corpus"][k]
+        return out
+    # encode: every rank has its own shard-shaped corpus; training: ONE corpus, which the sharded runner cuts into the ranks'
+    # sentence ranges (train_sharded) -- so every rank must hold the same sentences, rank 0's
+    train_sents = corpora[1][1] if rank == 0 else synth.s85k_open()
     # the other half of the north star's encode path, and the mixed shard of configs[4]: blocks of their own beside `train`
     # (their own timed regions, same bracket: barrier + synchronize on both sides, MAX over ranks)
     wp = tokenizers.FastWP()
@@ -406,9 +462,13 @@ def bench_headline(args, torch, dist, rank, world, local):
     wp._build_trie()
     out["wp_encode"] = wp_encode_block(args, torch, dist, rank, N, wp, args.sentences or 1000000, max(args.steps // 5, 5), 3)
     out["mixed_encode"] = mixed_encode_block(args, torch, dist, rank, N, bpe, wp, 625000, max(args.steps // 10, 3), 2)
+    for blk in ("wp_encode", "mixed_encode"):  # the line's outputs are those of its own timed path, the two encodes above
+        out[blk].pop("outputs", None)
     if out.get("cpu_baseline") is not None:
         out["cpu_baseline"]["reference_python"] = reference_python_baseline("bpe_encode")
     out["train"] = train_bench_guarded(out, args, torch, dist, rank, world, N, train_sents, args.max_vocab or 8000, "S85k-open")
+    if isinstance(out["train"], dict):
+        out["train"].pop("outputs", None)
     if isinstance(out["train"], dict) and out["train"].get("cpu_baseline") is not None:
         out["train"]["cpu_baseline"]["reference_python"] = reference_python_baseline("train_extrapolated")
     return out
@@ -436,7 +496,7 @@ def bench_bpe_encode(args, torch, dist, rank, world, local):
                                % (name, r["n_bytes"] / 1e6),
                    "sentences_per_gpu": r["n_sent"], "bytes_per_gpu": r["n_bytes"], "tokens_per_gpu": r["n_tok"],
                    "parallelism": "corpus-sharded x%d, no collective" % world},
-        "roofline": r["roofline"], "cpu_baseline": r["cpu"], "encode_detail": {name: r["detail"]},
+        "roofline": r["roofline"], "cpu_baseline": r["cpu"], "encode_detail": {name: r["detail"]}, "outputs": r.get("outputs"),
     }
 
 
@@ -493,7 +553,10 @@ def wp_encode_block(args, torch, dist, rank, N, wp, n_sent, steps, warmup, cpu_s
     res = {"value": round(total_bytes * steps / 1e6 / elapsed, 1), "unit": "MB/s", "ms_per_step": round(elapsed / steps * 1e3, 4), "steps": steps,
            "workload": "configs[2]: FastWP failure-link trie encode, V30k vocab, %d synthetic sentences (%.1f MB/GPU)" % (n_sent, n_bytes / 1e6),
            "sentences_per_gpu": n_sent, "bytes_per_gpu": n_bytes, "tokens_per_gpu": n_tok, "roofline": None, "cpu_baseline": None}
-    if args.lean:  # counter passes: only the launches of the timed path
+    if args.dump_outputs:
+        res["outputs"] = {"wp_ids": d_out[:int(d_ntok.item())].cpu().numpy().view(np.uint32),
+                          "wp_offsets": d_out_off.cpu().numpy().view(np.uint64), "wp_status": d_status[:n_sent].cpu().numpy()}
+    if args.lean:  # plain runs and counter passes: only the launches of the timed path
         N.profile_enable(False)
         return res
     # outside the timed region: one event pair around ALL kernels of a call (level 2), then around the split + lookup
@@ -586,7 +649,7 @@ def bench_wp_encode(args, torch, dist, rank, world, local):
         "unit": "MB/s", "ms_per_step": r["ms_per_step"], "dtype": "u32",
         "config": {"workload": r["workload"], "sentences_per_gpu": r["sentences_per_gpu"], "bytes_per_gpu": r["bytes_per_gpu"],
                    "tokens_per_gpu": r["tokens_per_gpu"], "parallelism": "corpus-sharded x%d, no collective" % world},
-        "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"], "end_to_end_mb_s": r.get("end_to_end_mb_s"),
+        "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"], "end_to_end_mb_s": r.get("end_to_end_mb_s"), "outputs": r.get("outputs"),
     }
 
 
@@ -604,8 +667,8 @@ def bench_bpe_train(args, torch, dist, rank, world, local):
     return {"metric": tr["metric"], "value": tr["s_per_1k_merges"], "unit": "s/1k-merges", "higher_is_better": False,
             "ms_per_step": round(tr["train_wall_s"] * 1e3, 3), "dtype": "u32", "scaling": "strong",
             "config": {"workload": tr["workload"], "parallelism": tr["parallelism"]},
-            "roofline": tr["roofline"], "cpu_baseline": tr["cpu_baseline"], "us_per_merge_device": tr["us_per_merge_device"],
-            "merge_loop_s": tr["merge_loop_s"]}
+            "roofline": tr.get("roofline"), "cpu_baseline": tr.get("cpu_baseline"), "us_per_merge_device": tr["us_per_merge_device"],
+            "merge_loop_s": tr["merge_loop_s"], "outputs": tr.get("outputs")}
 
 
 def mixed_encode_block(args, torch, dist, rank, N, bpe, wp, n_each, steps, warmup, cpu_sents=100000):
@@ -648,6 +711,12 @@ def mixed_encode_block(args, torch, dist, rank, N, bpe, wp, n_each, steps, warmu
            "workload": "configs[4] per GPU: %d sentences through FastBPE (8,000 merges, %.1f MB) + %d through FastWP (V30k, %.1f MB)"
                        % (n_each, bufs[0][5] / 1e6, n_each, bufs[1][5] / 1e6),
            "sentences_per_gpu": 2 * n_each, "bytes_per_gpu": n_bytes, "roofline": None, "cpu_baseline": None}
+    if args.dump_outputs:
+        res["outputs"] = {}
+        for half, (t, o, out, oo, nt, nb) in zip(("bpe", "wp"), bufs):
+            res["outputs"][half + "_ids"] = out[:int(nt.item())].cpu().numpy().view(np.uint32)
+            res["outputs"][half + "_offsets"] = oo.cpu().numpy().view(np.uint64)
+        res["outputs"]["wp_status"] = d_status[:n_each].cpu().numpy()
     if args.lean:
         return res
     N.profile_enable(2)
@@ -722,7 +791,7 @@ def bench_mixed_encode(args, torch, dist, rank, world, local):
         "value": r["value"], "unit": "MB/s", "ms_per_step": r["ms_per_step"], "dtype": "u32",
         "config": {"workload": r["workload"], "sentences_per_gpu": r["sentences_per_gpu"], "bytes_per_gpu": r["bytes_per_gpu"],
                    "parallelism": "corpus-sharded x%d, no collective" % world},
-        "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"],
+        "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"], "outputs": r.get("outputs"),
     }
 
 
@@ -757,6 +826,15 @@ def bench_bpe_train_words(args, torch, dist, rank, world, local):
             times.append(time.perf_counter() - t0)
     kernel_ms, launches = N.profile_read()
     N.profile_enable(False)
+    elapsed = sum(times)
+    outputs = {"merge_left": lefts, "merge_right": rights, "merge_count": counts} if args.dump_outputs else None
+    if args.lean:  # plain runs: no oracle, no roofline
+        return {"metric": "BPE train seconds per 1k merges", "value": round(elapsed / len(times) / max(len(lefts), 1) * 1000, 4),
+                "unit": "s/1k-merges", "higher_is_better": False, "ms_per_step": round(elapsed / len(times) * 1e3, 3), "dtype": "u32",
+                "config": {"workload": "configs[3] shape: BPE train of %d word types / %d tokens (~%.2f GB of text) to %d merges, "
+                                       "deduplicated-words-with-frequencies form" % (freq.size, int(freq.sum()), corpus_bytes / 1e9, len(lefts)),
+                           "parallelism": "single GPU"},
+                "scaling": "strong", "final_symbols": info["n_symbols"], "outputs": outputs}
     from oracle import oracle as O
 
     sample = args.parity_merges or 200
@@ -772,7 +850,6 @@ def bench_bpe_train_words(args, torch, dist, rank, world, local):
         raise SystemExit("PARITY FAILURE: device merges differ from the oracle on the first %d merges" % sample)
     n_final = int(info["n_symbols"])
     per_merge_s = kernel_ms / 1e3 / max(len(times), 1) / max(len(lefts), 1)  # the event brackets span whole batches of merge steps
-    elapsed = sum(times)
     return {
         "metric": "BPE train seconds per 1k merges", "value": round(elapsed / len(times) / max(len(lefts), 1) * 1000, 4),
         "unit": "s/1k-merges", "higher_is_better": False, "ms_per_step": round(elapsed / len(times) * 1e3, 3), "dtype": "u32",
@@ -784,7 +861,7 @@ def bench_bpe_train_words(args, torch, dist, rank, world, local):
                                    12.0 * (n0 + n_final) / 2.0 + 8.0 * w0),  # rescan: N_t averaged over the run (trapezoid)
         "cpu_baseline": {"value": round(cpu_s / sample * 1000, 3), "unit": "s/1k-merges", "cores": 1, "kind": "port",
                          "sample": "first %d merges of the same run through oracle/swt_oracle.c (full recount per merge)" % sample},
-        "final_symbols": info["n_symbols"], "parity_merges_checked": sample,
+        "final_symbols": info["n_symbols"], "parity_merges_checked": sample, "outputs": outputs,
     }
 
 
@@ -821,6 +898,14 @@ def bench_wp_train(args, torch, dist, rank, world, local):
             times.append(time.perf_counter() - t0)
     kernel_ms, launches = N.profile_read()
     N.profile_enable(False)
+    elapsed = sum(times)
+    outputs = merge_arrays(order) if args.dump_outputs else None
+    if args.lean:  # plain runs: no oracle, no roofline
+        return {"metric": "WordPiece train seconds per 1k merges", "value": round(elapsed / len(times) / max(len(order), 1) * 1000, 4),
+                "unit": "s/1k-merges", "higher_is_better": False, "ms_per_step": round(elapsed / len(times) * 1e3, 3), "dtype": "u32+f64 score",
+                "config": {"workload": "NaiveWP.train on S85k to max_vocab=%d: %d initial symbols, %d merges" % (max_vocab, base, len(order)),
+                           "parallelism": "single GPU"},
+                "scaling": "strong", "final_symbols": info["n_symbols"], "outputs": outputs}
     from oracle import oracle as O
 
     sample = 60
@@ -833,7 +918,6 @@ def bench_wp_train(args, torch, dist, rank, world, local):
         raise SystemExit("PARITY FAILURE: device merges differ from the oracle on the first %d merges" % sample)
     n_final = int(info["n_symbols"])
     per_merge_s = kernel_ms / 1e3 / max(len(times), 1) / max(len(order), 1)
-    elapsed = sum(times)
     return {
         "metric": "WordPiece train seconds per 1k merges", "value": round(elapsed / len(times) / max(len(order), 1) * 1000, 4),
         "unit": "s/1k-merges", "higher_is_better": False, "ms_per_step": round(elapsed / len(times) * 1e3, 3), "dtype": "u32+f64 score",
@@ -845,7 +929,7 @@ def bench_wp_train(args, torch, dist, rank, world, local):
                                    16.0 * (n0 + n_final) / 2.0 + 8.0 * w0, whole_table=stats["theta"] == 0),  # theta 1: the list of live pairs
         "cpu_baseline": {"value": round(cpu_s / sample * 1000, 3), "unit": "s/1k-merges", "cores": 1, "kind": "port",
                          "sample": "first %d merges of the same run through oracle/swt_oracle.c (orc_wptrain_new + orc_train_run)" % sample},
-        "final_symbols": info["n_symbols"],
+        "final_symbols": info["n_symbols"], "outputs": outputs,
     }
 
 
@@ -860,7 +944,10 @@ def main():
     ap.add_argument("--types", type=int, default=None, help="bpe_train_1g: word types (default 2,000,000)")
     ap.add_argument("--merges", type=int, default=None, help="bpe_train_1g: merges (default 32,000)")
     ap.add_argument("--parity-merges", type=int, default=None, help="bpe_train_1g: merges compared with the oracle (default 200)")
-    ap.add_argument("--lean", action="store_true", help="bpe_encode / wp_encode / mixed_encode: timed steps only (no extra legs, no parity check): for counter passes")
+    ap.add_argument("--lean", action="store_true", help="timed steps only, also with --full (no extra legs, no parity check): for counter passes")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the workload measures and checks: roofline, "
+                    "CPU baselines, parity with the oracle, end-to-end rates and, on the headline, the wp_encode / mixed_encode / train blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--corpus", default="open", choices=["open", "lex"], help="bpe_train / bpe_encode: S85k-open (default) or S85k-lex")
     args = ap.parse_args()
     defaults = {"headline": (100, 10), "bpe_encode": (200, 20), "wp_encode": (20, 3), "bpe_train": (2, 1), "wp_train": (2, 1), "bpe_train_1g": (1, 0), "mixed_encode": (10, 2)}[args.workload]
@@ -868,6 +955,8 @@ def main():
         args.steps = defaults[0]
     if args.warmup is None:
         args.warmup = defaults[1]
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the line
+        args.lean = True
 
     # ONE line on stdout, whatever the libraries print (RCCL writes a version banner to fd 1 when a communicator is made):
     # everything else goes to stderr, the JSON line to the stdout this process was given
@@ -880,6 +969,11 @@ def main():
           "wp_train": bench_wp_train, "bpe_train_1g": bench_bpe_train_words, "mixed_encode": bench_mixed_encode}[args.workload]
     def emit(res):
         res = dict(res)
+        outputs = res.pop("outputs", None)
+        if args.dump_outputs:
+            if not outputs:
+                raise SystemExit("--dump-outputs: workload %s returned no outputs" % args.workload)
+            write_outputs(args.dump_outputs, outputs)
         line = {"metric": res.pop("metric"), "value": res.pop("value"), "unit": res.pop("unit"), "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": res.pop("ms_per_step"),
                 "higher_is_better": res.pop("higher_is_better", True), "scaling": res.pop("scaling", "weak"), "vs_baseline": None,

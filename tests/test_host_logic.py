@@ -489,6 +489,29 @@ def test_bench_watchdog_emits_the_line_without_the_train_block(monkeypatch):
     assert emitted == [] and fired == []
 
 
+def test_bench_dump_outputs_exact_and_bounded(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: float32 only where it holds every value exactly, float64 otherwise; past the size limit, the
+    same seeded sample of positions on every run, and the files within the limit"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    ids = np.arange(1 << 16, dtype=np.uint32) * 7
+    big = np.array([0, (1 << 24) + 1, 1 << 40], dtype=np.uint64)
+    bench.write_outputs(str(tmp_path / "a"), dict(ids=ids, big=big, **bench.merge_arrays([("ab", "c"), ("é", "##x")])))
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(tmp_path / "a")}
+    assert got["ids"].dtype == np.float32 and np.array_equal(got["ids"], ids)
+    assert got["big"].dtype == np.float64 and np.array_equal(got["big"].astype(np.uint64), big)
+    assert got["merge_left_len"].tolist() == [2, 1] and got["merge_right_len"].tolist() == [1, 3]
+    assert "".join(map(chr, got["merge_codepoints"].astype(int))) == "abcé##x"
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), {"ids": ids, "off": np.arange(1 << 14, dtype=np.uint64)})
+    for f in ("ids.npy", "off.npy"):
+        b, c = np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f))
+        assert 0 < b.size < (1 << 16) and np.array_equal(b, c) and np.all(np.diff(b) > 0)
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(tmp_path / "b")) <= 64 << 10
+
+
 def test_merge_strings_helper_is_the_python_loop(native):
     """csrc/swt_pyhost.c swt_py_bpe_merge_strings against the per-merge loop of NaiveBPE.train it stands in for (bpe.py:102-104):
     same strings / index / vocab / merges afterwards, same stop at the first merge whose id is not the expected one"""
