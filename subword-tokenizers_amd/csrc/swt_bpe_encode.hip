@@ -6,24 +6,14 @@
 //   FastBPE.encode_word / _pairs     /root/reference/source/bpe.py:202-243
 //   the rank dict                    /root/reference/source/bpe.py:200,257
 //
-// One 64-lane wavefront per tile (workgroup = one wave, so every barrier is a wave-local fence):
+// One kernel, bpe_lane_kernel: one 64-lane wavefront per tile (workgroup = one wave, so every barrier is a wave-local fence):
 //   tile   = the sentences whose first byte lies in one window of the text (whole sentences, no data-path atomics between
 //            workgroups, a tile's tokens are contiguous in the output)
 //   chunk  = the part of the tile's span staged in LDS at a time; longer spans are cut at word boundaries
-// Two kernels share that skeleton and the two-choice rank table (slot_value):
-//   bpe_lane_kernel   (the default, round 3; described where it stands, below): the split stays byte-parallel and looks every
-//                     adjacent pair up on the way, then ONE LANE OWNS ONE WORD through the merge rounds (live-slot mask, a lane takes
-//                     the next word when its own is finished, four lanes a word once few words are left)
-//   bpe_encode_kernel (rounds 1-2, SWT_BPE_KERNEL=bytes: the comparison form): one lane per BYTE POSITION in every phase --
-//     B/C  64 bytes per step: decode the code point at each UTF-8 lead byte, class from an LDS copy of the table,
-//          then everything structural (word starts, next symbol of the word, head of the word) comes from 64-bit
-//          ballot masks and scalar bit arithmetic
-//     C2/D the table value of every adjacent pair, then merge rounds over the list of symbols that still belong to an
-//          unfinished word: per-word minimum by LDS atomicMin, the winners merge in place (symbols are linked by a
-//          next-pointer, nothing is shifted), and only symbols next to a merge look the table up again
-//     E/F  order-preserving ballot compaction to the tile's output run, per-sentence offsets
+// The split stays byte-parallel and looks every adjacent pair up in the two-choice rank table (slot_value) on the way, then
+// ONE LANE OWNS ONE WORD through the merge rounds (live-slot mask, a lane takes the next word when its own is finished, four
+// lanes a word once few words are left); the phases are described where the kernel stands, below.
 // A word longer than a chunk falls to a one-lane global-memory path (correct, slow, pathological inputs only).
-#include <cstdlib>
 #include <cstring>
 #include <unordered_map>
 #include <utility>
@@ -42,20 +32,6 @@ struct alignas(16) BpeSlot {
 
 constexpr uint8_t kClsWs = 1, kClsPunct = 2;
 constexpr uint32_t kNoRank = 0xFFFFFFFFu;
-#ifndef SWT_CLS_LDS
-#define SWT_CLS_LDS 1024
-#endif
-constexpr int kClsLds = SWT_CLS_LDS;    // code points whose class is served from LDS (16 B a lane)
-
-#ifndef SWT_BPE_TILE
-#define SWT_BPE_TILE 192
-#endif
-#ifndef SWT_BPE_CAP
-#define SWT_BPE_CAP 256
-#endif
-constexpr int kBpeTile = SWT_BPE_TILE;   // bytes of sentence starts per tile.  Measured on S85k-open with 256-byte chunks (tools/gpu_enc_sweep.sh):
-                                         // 96: 489 us, 128: 481, 160: 467, 192: 453, 224: 456, 256: 460; 512-byte chunks: 558 (fewer resident waves)
-constexpr int kBpeCap = SWT_BPE_CAP;    // staged bytes per chunk
 #ifndef SWT_LANE_TILE
 #define SWT_LANE_TILE 384
 #endif
@@ -67,7 +43,6 @@ constexpr int kBpeCap = SWT_BPE_CAP;    // staged bytes per chunk
 constexpr int kLaneTile = SWT_LANE_TILE;  // the word-lane kernel (bpe_lane_kernel): bytes of sentence starts per tile ...
 constexpr int kLaneCap = SWT_LANE_CAP;    // ... and staged bytes per chunk (a batch of 64 word lanes wants ~350 bytes of text)
 constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one workgroup and one launch do the whole call
-constexpr uint32_t kNoPos = 0xFFFFu;
 
 // The rank table is a two-choice cuckoo table (built once on the host, swt_bpe_table_create): a pair lives in slot h1 or in
 // slot h2, so a lookup is two independent 16-byte loads and two compares -- no probe loop, and a wave never goes round
@@ -157,488 +132,13 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
   return r;
 }
 
-template <int Cap>
-struct BpeLds {
-  static constexpr int Blocks = Cap / 64;
-  __attribute__((aligned(16))) uint8_t txt[Cap + 16];
-  uint32_t sym[Cap];           // per byte position: symbol id (token id at the end) or kInvalidTok
-  uint16_t nxt[Cap];           // per byte position: next live symbol of the same word, kNoPos for the last one
-  uint32_t act[Cap];           // symbols of unfinished words: position | head position << 16
-  uint32_t aval[Cap];          // per list entry: table value of (this symbol, next symbol); kNoRank when none
-  uint32_t wm[2][Cap / 2];     // per word (indexed by head >> 1): minimum table value, this round / next round
-  unsigned long long sbits[Blocks + 1];  // sentence-start bit per byte
-  unsigned long long mark[Blocks + 1];   // "my predecessor is a candidate of a twin pair (a,a)"
-  unsigned long long tk[Blocks + 1];     // taken: this symbol merges with its next one this round
-  unsigned long long dead[Blocks + 1];   // consumed by the symbol before it this round
-  unsigned long long vmask[Blocks + 1];  // phase E
-  uint32_t blkpre[Blocks + 1];
-  __attribute__((aligned(16))) uint8_t cls_lo[kClsLds];  // classes of U+0000..U+03FF
-  GiantResult giant;
-};
-
-__device__ __forceinline__ bool bit_at(const unsigned long long *m, uint32_t p) { return (m[p >> 6] >> (p & 63)) & 1ull; }
-
-// Packed = true: the table value of a pair is rank << 16 | (merged - SWT_SYM_BASE), so a merge round learns the
-// merged symbol without touching memory (tables below 65,534 merges); false: the value is the rank and the merged
-// symbol is read from merged_of_rank[].
-// Mode: 0 = tiles of running text (plan, sent_local / tile_tok for the scan + gather), 1 = the unique-word pass of the dedup
-// path (every "sentence" is a unique word: rec / drec / uslot), 2 = one workgroup writing the caller's arrays (DirectOut).  A
-// template parameter, not a run-time test: each form keeps only its own arguments in scalar registers (one kernel for all
-// three spilled 44 of them).
-template <bool Packed, int Cap, int Mode>
-__global__ __launch_bounds__(64) void bpe_encode_kernel(
-    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
-    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots,
-    uint32_t sh, const uint32_t *__restrict__ merged_of_rank, uint32_t *__restrict__ scratch,
-    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, const uint32_t *__restrict__ uslot,
-    unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec, DirectOut direct, uint32_t dbg_arg) {
-#ifdef SWT_ABLATION
-  const uint32_t dbg = dbg_arg;
-#else
-  constexpr uint32_t dbg = 0;  // the ablation switches exist in -DSWT_ABLATION builds only
-  (void)dbg_arg;
-#endif
-  constexpr bool kDirect = Mode == 2, kRec = Mode == 1;
-  // uslot/rec/drec (dedup path, every "sentence" s is unique word s): the word's token run -- its place in scratch and its
-  // length -- goes straight to drec[s] (dense: stays in L2 for the last pass) and length | s to the word's table slot, and
-  // nobody needs a scan or a gather of this launch's output.
-  constexpr int Blocks = Cap / 64;
-  __shared__ BpeLds<Cap> L;
-  const int lane = threadIdx.x;
-  const unsigned long long lt = (1ull << lane) - 1ull;  // lanes below me
-  const unsigned long long le = (2ull << lane) - 1ull;  // me and below
-  const uint64_t t = blockIdx.x;
-  const uint64_t s_lo = kDirect ? 0 : plan[t], s_hi = kDirect ? direct.n_sent : plan[t + 1];
-  if (s_lo == s_hi) {
-    if (Mode == 0 && lane == 0) tile_tok[t] = 0;
-    return;
-  }
-  {
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (lane < kClsLds / 16) {
-      if (cls_tab) v = reinterpret_cast<const uint4 *>(cls_tab)[lane];
-      reinterpret_cast<uint4 *>(L.cls_lo)[lane] = v;
-    }
-  }
-  const uint64_t span_base = sent_off[s_lo], span_end = sent_off[s_hi];
-  uint32_t *const tile_out = scratch + span_base;
-  uint32_t run = 0;        // tokens emitted by this tile so far
-  uint64_t s_next = s_lo;  // first sentence whose local offset is not recorded yet
-  uint64_t cb = span_base;
-
-  for (;;) {
-    const uint64_t abase = cb & ~15ull;
-    const uint32_t off0 = (uint32_t)(cb - abase);
-    const uint64_t avail = span_end - abase;
-    const bool last = avail <= (uint64_t)Cap;
-    const uint32_t staged = last ? (uint32_t)avail : (uint32_t)Cap;
-    const uint32_t nblk = (staged + 63) >> 6;
-
-    // ---- A. stage [abase, abase+staged): one dwordx4 per lane
-    for (uint32_t c = lane * 16; c < staged; c += 64 * 16) {
-      const uint64_t g = abase + c;
-      if (g + 16 <= n_bytes && ((reinterpret_cast<uintptr_t>(text + g) & 15) == 0)) {
-        *reinterpret_cast<uint4 *>(&L.txt[c]) = *reinterpret_cast<const uint4 *>(text + g);
-      } else {
-        for (int i = 0; i < 16; i++) L.txt[c + i] = (g + i < n_bytes) ? text[g + i] : (uint8_t)' ';
-      }
-    }
-    if (lane <= Blocks) { L.sbits[lane] = 0ull; L.mark[lane] = 0ull; L.tk[lane] = 0ull; L.dead[lane] = 0ull; }
-    __syncthreads();
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t o = sent_off[s];
-      if (o >= abase + staged) break;
-      if (o >= cb) atomicOr(&L.sbits[(o - abase) >> 6], 1ull << ((o - abase) & 63));
-    }
-    __syncthreads();
-    if (dbg & 1) { if (last) break; cb = abase + staged; continue; }  // ablation: staging only
-
-    // ---- B/C. 64 bytes per step.  Scalars carried from block to block:
-    uint32_t na = 0;          // active-list length
-    bool prev_wb = true;      // the byte before this block belongs to a whitespace/punctuation char (or chunk start)
-    uint32_t pend = kNoPos;   // last symbol of the previous block whose word may continue, and its data
-    uint32_t pend_head = 0;
-    bool pend_listed = false;
-    int cut = -1;             // last word boundary (for a span longer than the chunk)
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-      const uint32_t p = blk * 64 + lane;
-      const bool inr = p >= off0 && p < staged;
-      const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
-      const bool lead = !utf8_is_cont(b);
-      uint32_t cp = b;
-      if (b >= 0xC0) {
-        int len = utf8_len(b);
-        if (p + len > staged) len = (int)(staged - p);
-        if (len > 1) {
-          cp = b & (0xFF >> (len + 1));
-          for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
-        }
-      }
-      uint8_t c = kClsWs;  // bytes outside the chunk behave as whitespace
-      if (inr && lead) c = cp < (uint32_t)kClsLds ? L.cls_lo[cp] : ((cls_tab && cp < kNumCodePoints) ? cls_tab[cp] : (uint8_t)0);
-      const unsigned long long INR = __ballot(inr);
-      const unsigned long long LEAD = __ballot(lead);
-      const unsigned long long WSm = __ballot(lead && (c & kClsWs));
-      const unsigned long long PNm = __ballot(lead && (c & kClsPunct));
-      const unsigned long long CONT = ~LEAD;
-      // bytes that belong to a whitespace/punctuation char (continuation bytes inherit from their lead byte)
-      unsigned long long WB = WSm | PNm | ((prev_wb && (CONT & 1ull)) ? 1ull : 0ull);
-      WB |= (WB << 1) & CONT;
-      WB |= (WB << 1) & CONT;
-      WB |= (WB << 1) & CONT;
-      const unsigned long long SS = L.sbits[blk];
-      const unsigned long long first_bit = blk == 0 ? (1ull << off0) : 0ull;  // off0 < 16
-      const unsigned long long before = (WB << 1) | (prev_wb ? 1ull : 0ull) | SS | first_bit;
-      const unsigned long long SYM = LEAD & ~WSm & INR;
-      const unsigned long long WSTART = SYM & (PNm | before);
-      // chunk cut candidates: word boundaries strictly inside, with room for a whole UTF-8 char behind them
-      {
-        const unsigned long long CUT = LEAD & (WSm | PNm | SS) & __ballot(inr && p > off0 && p + 4 <= staged);
-        if (CUT) cut = (int)(blk * 64 + 63 - __builtin_clzll(CUT));
-      }
-      const bool is_sym = (SYM >> lane) & 1ull;
-      const bool wstart = (WSTART >> lane) & 1ull;
-      const unsigned long long hm = WSTART & le;
-      const uint32_t head = hm ? blk * 64 + 63 - __builtin_clzll(hm) : pend_head;
-      const unsigned long long after = SYM & ~le;
-      const uint32_t q = after ? (uint32_t)__builtin_ctzll(after) : 64u;
-      const bool hasnext = is_sym && q < 64 && !((WSTART >> (q & 63)) & 1ull);
-      // does the symbol left pending by the previous block continue into this one?
-      const uint32_t f = SYM ? (uint32_t)__builtin_ctzll(SYM) : 64u;
-      const bool joins = pend != kNoPos && f < 64 && !((WSTART >> (f & 63)) & 1ull);
-      const bool i_join = joins && lane == (int)f;
-      if (i_join) L.nxt[pend] = (uint16_t)p;
-      L.sym[p] = is_sym ? cp : kInvalidTok;
-      L.nxt[p] = hasnext ? (uint16_t)(blk * 64 + q) : (uint16_t)kNoPos;
-      // active list: symbols of words with at least two symbols (a lone word start waits for its successor)
-      const bool active = is_sym && (!wstart || hasnext);
-      const unsigned long long ACT = __ballot(active);
-      const uint32_t extra = (joins && !pend_listed) ? 1u : 0u;  // the pending word start now has a successor
-      if (i_join && extra) { L.act[na] = pend | (pend_head << 16); L.wm[0][pend_head >> 1] = kNoRank; }
-      if (active) {
-        L.act[na + extra + __popcll(ACT & lt)] = p | (head << 16);
-        if (p == head) L.wm[0][head >> 1] = kNoRank;
-      }
-      na += extra + __popcll(ACT);
-      // carries
-      if (SYM) {
-        const int li = 63 - __builtin_clzll(SYM);
-        const unsigned long long tail = li == 63 ? 0ull : ~((2ull << li) - 1ull);
-        const bool open = ((WSm | PNm | SS) & tail) == 0ull && !((PNm >> li) & 1ull);
-        pend = open ? blk * 64 + li : kNoPos;
-        pend_head = __shfl(head, li);
-        pend_listed = ((ACT >> li) & 1ull) != 0ull;
-      } else {
-        pend = kNoPos;  // a block without symbols holds whitespace: every word ended
-      }
-      prev_wb = (WB >> 63) & 1ull;
-    }
-    __syncthreads();
-
-    // ---- chunk end
-    uint32_t ce = staged;
-    if (!last) {
-      if (cut < 0) {
-        // a single word longer than the LDS chunk: one lane, global memory
-        if (lane == 0) {
-          uint64_t s = s_next;
-          while (s < s_hi && sent_off[s] <= cb) s++;
-          const uint64_t send = sent_off[s];  // s <= s_hi and sent_off[s_hi] = span_end > cb
-          L.giant = giant_word(text, cb, send, cls_tab, slots, sh, tile_out + run);
-        }
-        __syncthreads();
-        const GiantResult g = L.giant;
-        uint32_t mine = 0;
-        for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-          if (sent_off[s] >= g.end) break;
-          if (kDirect) direct.off[s] = run; else if (Mode == 0) sent_local[s] = run;
-          if (kRec) {
-            drec[s] = (unsigned long long)(span_base + run) | ((unsigned long long)g.ntok << 32);
-            rec[uslot[s]] = (unsigned long long)s | ((unsigned long long)g.ntok << 32);
-          }
-          mine++;
-        }
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        s_next += mine;
-        run += g.ntok;
-        cb = g.end;
-        __syncthreads();
-        continue;
-      }
-      ce = (uint32_t)cut;
-      // drop list entries at or beyond the cut (the next chunk stages them again)
-      uint32_t keep = 0;
-      for (uint32_t k0 = 0; k0 < na; k0 += 64) {
-        const uint32_t k = k0 + lane;
-        const uint32_t e = k < na ? L.act[k] : 0u;
-        const bool ok = k < na && (e & 0xFFFFu) < ce;
-        const unsigned long long M = __ballot(ok);
-        __syncthreads();
-        if (ok) L.act[keep + __popcll(M & lt)] = e;
-        keep += __popcll(M);
-        __syncthreads();
-      }
-      na = keep;
-    }
-
-    // ---- C2. the table value of every adjacent pair of every listed symbol: the whole first merge round
-    // (bpe.py:211-219), four independent probes in flight per lane; each value also goes into its word's minimum
-    for (uint32_t k0 = 0; k0 < na; k0 += 256) {
-      uint32_t pl[4], pr[4], hd[4];
-      bool want[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t k = k0 + u * 64 + lane;
-        want[u] = false;
-        pl[u] = pr[u] = hd[u] = 0;
-        if (k < na && !(dbg & 4)) {
-          const uint32_t e = L.act[k];
-          const uint32_t p = e & 0xFFFFu;
-          const uint32_t qn = L.nxt[p];
-          hd[u] = e >> 17;
-          if (qn != kNoPos) {
-            want[u] = true;
-            pl[u] = L.sym[p];
-            pr[u] = L.sym[qn];
-          }
-        }
-      }
-      uint32_t vv[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) vv[u] = slot_value(slots, sh, pl[u], pr[u]);
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t k = k0 + u * 64 + lane;
-        const uint32_t v = want[u] ? vv[u] : kNoRank;
-        if (v != kNoRank && !(dbg & 8)) atomicMin(&L.wm[0][hd[u]], v);
-        if (k < na) L.aval[k] = v;
-      }
-    }
-    __syncthreads();
-
-    // ---- D. merge rounds (bpe.py:210-238), all lanes on the symbols of unfinished words.  Two passes per round:
-    //   X  candidates = left symbols of their word's best pair; they publish "taken" (tk) and "consumed" (dead) bits.
-    //      A pair of two different symbols cannot overlap itself, so such a candidate always merges; a twin pair
-    //      (a,a) in a run like "aaaa" merges left to right, non-overlapping (bpe.py:225-235): every second member,
-    //      decided by the run's first member.
-    //   Y  every listed symbol updates itself from those bits (merged symbol, next pointer), re-probes the table only
-    //      if its pair changed, feeds the next round's per-word minimum, and the list is compacted.
-    uint32_t cur = 0, round_no = 0;
-    while (na > 0 && !(dbg & 16)) {
-      if (na <= 64 && dbg == 0) {
-        // ---- register rounds: once the symbols of the unfinished words fit one wave (always, after a few rounds; from the
-        // start for the short tiles of the unique-word pass) every entry lives in a lane.  The entries of a word are
-        // consecutive lanes in text order, so "my next symbol" is the lane above me, a round is ballots and shuffles, and
-        // the dependent LDS chain of the list form (~30 accesses per round) shrinks to the word minimum and the compaction.
-        bool valid = (uint32_t)lane < na;
-        uint32_t e = valid ? L.act[lane] : 0u, v = valid ? L.aval[lane] : kNoRank;
-        uint32_t p = e & 0xFFFFu, head = e >> 16;
-        uint32_t sy = valid ? L.sym[p] : 0u;
-        for (;;) {
-          const unsigned long long VALID = __ballot(valid);
-          if (!VALID) break;
-          const uint32_t hw = head >> 1;
-          const uint32_t m = valid ? L.wm[cur][hw] : kNoRank;
-          __syncthreads();
-          if (valid && p == head) L.wm[cur ^ 1][hw] = kNoRank;
-          const uint32_t head1 = __shfl_down(head, 1), head2 = __shfl_down(head, 2);
-          const uint32_t sy1 = __shfl_down(sy, 1), sy2 = __shfl_down(sy, 2);
-          const bool same1 = lane < 63 && ((VALID >> (lane + 1)) & 1ull) && head1 == head;
-          const bool same2 = same1 && lane < 62 && ((VALID >> (lane + 2)) & 1ull) && head2 == head;
-          const bool cand = valid && m != kNoRank && v == m;  // v is the value of (me, lane above me): that lane exists
-          const bool twin = cand && sy1 == sy;
-          const unsigned long long TW = __ballot(twin);
-          bool taken = cand;
-          if (twin) {
-            // a run of twin pairs ("aaaa") merges left to right, non-overlapping (bpe.py:225-235): every second member,
-            // counted from the run's first lane (runs of different words never touch: a word's last symbol is no candidate)
-            const unsigned long long low = ~TW & lt;
-            const int start = low ? 64 - __builtin_clzll(low) : 0;
-            taken = ((lane - start) & 1) == 0;
-          }
-          const unsigned long long TK = __ballot(taken);
-          const bool dead = lane > 0 && ((TK >> (lane - 1)) & 1ull);  // the lane below me merged me in
-          const bool tk1 = same1 && ((TK >> (lane + 1)) & 1ull), tk2 = same2 && ((TK >> (lane + 2)) & 1ull);
-          uint32_t mg = 0;
-          if (valid && m != kNoRank) mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
-          const bool keep = valid && m != kNoRank && !dead;
-          if (valid && !keep) L.sym[p] = dead ? kInvalidTok : (p != head ? (sy | SWT_BPE_CONT) : sy);  // consumed, or word finished
-          // my symbol and the symbol above me after this round
-          const uint32_t sn = taken ? mg : sy;
-          const bool has_r = taken ? same2 : same1;
-          const uint32_t sr = taken ? (tk2 ? mg : sy2) : (tk1 ? mg : sy1);
-          uint32_t vn = v;
-          if (!has_r) vn = kNoRank;
-          else if (taken || tk1) vn = slot_value(slots, sh, sn, sr);
-          __syncthreads();  // the reset of the next round's minima (above) comes before the lanes feed them
-          if (keep && vn != kNoRank) atomicMin(&L.wm[cur ^ 1][hw], vn);
-          const unsigned long long KEEP = __ballot(keep);
-          if (keep) {
-            const uint32_t d = (uint32_t)__popcll(KEEP & lt);
-            L.act[d] = e;
-            L.aval[d] = vn;
-            L.sym[p] = sn;
-          }
-          __syncthreads();
-          valid = (uint32_t)lane < (uint32_t)__popcll(KEEP);
-          if (valid) {
-            e = L.act[lane];
-            v = L.aval[lane];
-            p = e & 0xFFFFu;
-            head = e >> 16;
-            sy = L.sym[p];
-          }
-          cur ^= 1;
-        }
-        na = 0;
-        break;
-      }
-      round_no++;
-      const bool stop_now = (dbg >> 8) && round_no > (dbg >> 8);  // ablation: bounded rounds
-      bool twin = false;
-      for (uint32_t k = lane; k < na; k += 64) {
-        const uint32_t e = L.act[k];
-        const uint32_t v = L.aval[k];
-        const uint32_t p = e & 0xFFFFu, w = e >> 17;
-        const uint32_t m = stop_now ? kNoRank : L.wm[cur][w];
-        if (p == (e >> 16)) L.wm[cur ^ 1][w] = kNoRank;
-        if (m != kNoRank && v == m) {
-          const uint32_t qn = L.nxt[p];
-          if (L.sym[p] == L.sym[qn]) {
-            atomicOr(&L.mark[qn >> 6], 1ull << (qn & 63));
-            twin = true;
-          } else {
-            atomicOr(&L.tk[p >> 6], 1ull << (p & 63));
-            atomicOr(&L.dead[qn >> 6], 1ull << (qn & 63));
-          }
-        }
-      }
-      twin = __any(twin);
-      __syncthreads();
-      if (twin) {
-        for (uint32_t k = lane; k < na; k += 64) {
-          const uint32_t e = L.act[k];
-          uint32_t p = e & 0xFFFFu;
-          const uint32_t m = L.wm[cur][e >> 17];
-          if (m != kNoRank && L.aval[k] == m && L.sym[p] == L.sym[L.nxt[p]] && !bit_at(L.mark, p)) {
-            // first member of a run of twins: take, skip, take, ...  (a member's pair value equals m iff the symbol
-            // after it is the same symbol again)
-            const uint32_t a = L.sym[p];
-            for (;;) {
-              const uint32_t qn = L.nxt[p];
-              if (qn == kNoPos || L.sym[qn] != a) break;
-              atomicOr(&L.tk[p >> 6], 1ull << (p & 63));
-              atomicOr(&L.dead[qn >> 6], 1ull << (qn & 63));
-              p = L.nxt[qn];
-              if (p == kNoPos || L.sym[p] != a) break;
-            }
-          }
-        }
-        __syncthreads();
-      }
-      uint32_t keep = 0;
-      for (uint32_t k0 = 0; k0 < na; k0 += 64) {
-        const uint32_t k = k0 + lane;
-        uint32_t e = 0, v = kNoRank;
-        bool stay = false;
-        if (k < na) {
-          e = L.act[k];
-          v = L.aval[k];
-          const uint32_t p = e & 0xFFFFu, h = e >> 16;
-          const uint32_t m = stop_now ? kNoRank : L.wm[cur][h >> 1];
-          if (bit_at(L.dead, p)) {
-            L.sym[p] = kInvalidTok;  // consumed by the symbol before it; nobody reads a consumed symbol again
-          } else {
-            uint32_t sp = L.sym[p];
-            if (m == kNoRank) {
-              if (p != h) L.sym[p] = sp | SWT_BPE_CONT;  // word finished: '##' on all but its first token (bpe.py:240-241)
-            } else {
-              stay = true;
-              const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
-              uint32_t nq = L.nxt[p];
-              bool dirty;
-              if (bit_at(L.tk, p)) {
-                nq = L.nxt[nq];  // my partner is consumed; its successor becomes mine
-                sp = mg;
-                L.sym[p] = mg;
-                L.nxt[p] = (uint16_t)nq;
-                dirty = true;
-              } else {
-                dirty = nq != kNoPos && bit_at(L.tk, nq);
-              }
-              if (nq == kNoPos) v = kNoRank;
-              else if (dirty) v = slot_value(slots, sh, sp, bit_at(L.tk, nq) ? mg : L.sym[nq]);
-              if (v != kNoRank) atomicMin(&L.wm[cur ^ 1][h >> 1], v);
-            }
-          }
-        }
-        const unsigned long long M = __ballot(stay);
-        __syncthreads();
-        if (stay) {
-          const uint32_t d = keep + __popcll(M & lt);
-          L.act[d] = e;
-          L.aval[d] = v;
-        }
-        keep += __popcll(M);
-        __syncthreads();
-      }
-      na = keep;
-      if (lane <= Blocks) { L.tk[lane] = 0ull; L.mark[lane] = 0ull; L.dead[lane] = 0ull; }
-      cur ^= 1;
-      __syncthreads();
-    }
-
-    // ---- E. order-preserving compaction of the valid positions into the tile's output run
-    if (dbg & 32) { if (last) break; cb = abase + ce; continue; }
-    uint32_t total = 0;
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-      const uint32_t p = blk * 64 + lane;
-      const uint32_t sv = (p >= off0 && p < ce) ? L.sym[p] : kInvalidTok;
-      const unsigned long long m = __ballot(sv != kInvalidTok);
-      if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
-      if (sv != kInvalidTok) tile_out[run + total + __popcll(m & lt)] = sv;
-      total += __popcll(m);
-    }
-    __syncthreads();
-    // ---- F. tile-local token offset of every sentence starting in [cb, ce) (and == ce on the last chunk)
-    uint32_t mine = 0;
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t rel = sent_off[s] - abase;
-      if (rel > ce || (rel == ce && !last)) break;
-      uint32_t e = total;
-      if (rel < ce && (rel >> 6) < nblk) e = L.blkpre[rel >> 6] + __popcll(L.vmask[rel >> 6] & ((1ull << (rel & 63)) - 1ull));
-      if (kDirect) direct.off[s] = run + e; else if (Mode == 0) sent_local[s] = run + e;
-      if (kRec && rel < ce) {  // a word never straddles the cut, so its end lies in this chunk too
-        const uint64_t rel2 = sent_off[s + 1] - abase;
-        uint32_t e2 = total;
-        if (rel2 < ce && (rel2 >> 6) < nblk) e2 = L.blkpre[rel2 >> 6] + __popcll(L.vmask[rel2 >> 6] & ((1ull << (rel2 & 63)) - 1ull));
-        drec[s] = (unsigned long long)(span_base + run + e) | ((unsigned long long)(e2 - e) << 32);
-        rec[uslot[s]] = (unsigned long long)s | ((unsigned long long)(e2 - e) << 32);
-      }
-      mine++;
-    }
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-    s_next += mine;
-    run += total;
-    if (last) break;
-    cb = abase + ce;
-    __syncthreads();
-  }
-  if (lane == 0) {
-    if (kDirect) { direct.off[s_hi] = run; *direct.n_tokens = run; }
-    else if (Mode == 0) tile_tok[t] = run;
-  }
-}
-
-
 // ======================================================================================================================
-// The word-lane form of the same call (round 3; the default): bpe_lane_kernel.
-//
-// The kernel above keeps one lane per BYTE through the merge rounds: a round costs the wave the same ~170 instructions
-// whether 64 symbols take part or three, and a tile goes through as many rounds as its longest word has merges (the SQ
-// counters of round 2: 19.7 scalar + 14 vector instructions per input byte, the scalar pipe bound).  Here the split stays
-// byte-parallel (ballots), but it leaves the symbols DENSE (indexed by symbol, not by byte) together with the table value of
-// every adjacent pair (probed right there, all lanes at once), and then one lane owns one WORD:
+// bpe_lane_kernel, phase by phase (one chunk of a tile at a time):
+//   A    stage the chunk's bytes in LDS (one dwordx4 per lane) and mark the sentence starts in it
+//   B/C  64 bytes per step: decode the code point at each UTF-8 lead byte, class from a two-bit LDS copy of the table, then
+//        everything structural (word starts, symbols, the cut for a span longer than the chunk) comes from 64-bit ballot
+//        masks.  The symbols are left DENSE (indexed by symbol, not by byte) together with the table value of every adjacent
+//        pair (probed right there, all lanes at once).
 //   W    the multi-symbol words of the chunk, longest class first (9+, 5-8, 2-4 symbols)
 //   D    lane = word.  The word's slots stay where the split put them; a 32-bit mask says which are still live.  A round =
 //        leftmost minimum over the live slots' cached pair values (four slots per step) -> the pair merges in place, its
@@ -648,11 +148,21 @@ __global__ __launch_bounds__(64) void bpe_encode_kernel(
 //        pair, left to right" (bpe.py:221-235) -- what is left of the pair is still the minimum and is found leftmost-first
 //        in the next round.  Tables without that property, and words beyond 32 symbols, take slow_word(): the same loop in
 //        its literal form (all occurrences per round, compaction), one lane per word.
-//   E/F  ballot compaction over the SYMBOL space, sentence offsets through the split's symbol masks.
+//   E/F  order-preserving ballot compaction over the SYMBOL space to the tile's output run; the tile-local token offset of
+//        every sentence, through the split's symbol masks.
+// Template parameters:
+//   Packed = true: the table value of a pair is rank << 16 | (merged - SWT_SYM_BASE), so a merge round learns the merged
+//            symbol without touching memory (tables below 65,534 merges); false: the value is the rank and the merged symbol
+//            is read from merged_of_rank[].
+//   Proper: the table is proper (above), so the one-occurrence rounds of D apply.
+//   Mode:  0 = tiles of running text (plan, sent_local / tile_tok for the scan + gather), 1 = the unique-word pass of the
+//          dedup path (every "sentence" is a unique word: its token run -- place in scratch and length -- goes straight to
+//          drec[s], and length | s to the word's table slot, rec[uslot[s]]; nobody needs a scan or a gather of that launch's
+//          output), 2 = one workgroup writing the caller's arrays (DirectOut).  A template parameter, not a run-time test:
+//          each form keeps only its own arguments in scalar registers (one kernel for all three spilled 44 of them).
 // Measured and dropped (profiles/r03_experiments/bpe_lane_*.txt): one wave running the rounds for the words of four tiles
 // (fewer instructions, but three waves of four idle meanwhile: 0.229 against 0.200 ms), tiles that place their own output by a
 // decoupled look-back, and tiles that plan themselves (two launches instead of four).
-// Token ids, offsets and the launches around the kernel (plan, scan, gather / the dedup records) are those of the kernel above.
 template <int Cap>
 struct LaneLds {
   static constexpr int Blocks = Cap / 64;
@@ -743,8 +253,8 @@ __device__ __forceinline__ void lane_classes(LaneLds<Cap> &L, const uint8_t *__r
   L.cls2[lane] = w;
 }
 
-// ---- A + B/C of one chunk: stage the bytes, then 64 bytes per step: classes, word structure from ballot masks (as in the
-// kernel above), the dense symbols, the list of word starts, and the table value of every adjacent pair of a word.
+// ---- A + B/C of one chunk: stage the bytes, then 64 bytes per step: classes, word structure from ballot masks, the dense
+// symbols, the list of word starts, and the table value of every adjacent pair of a word.
 template <int Cap>
 __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint8_t *__restrict__ text, uint64_t n_bytes,
                                            const uint64_t *__restrict__ sent_off, const uint8_t *__restrict__ cls_tab,
@@ -1216,7 +726,6 @@ struct swt_bpe_table {
   std::vector<uint32_t> h_merged;  // merged symbol id by rank
   bool packed = false;             // slot value = rank << 16 | (merged - SWT_SYM_BASE)
   bool proper = false;             // every pair ranks above the merges that produce its symbols (any trained table)
-  bool lane_kernel = true;         // bpe_lane_kernel (default) or the byte-lane kernel of rounds 1-2 (SWT_BPE_KERNEL=bytes)
   BpeSlot *d_slots = nullptr;
   uint32_t *d_merged = nullptr;
   uint32_t bits = 0;
@@ -1243,23 +752,6 @@ static int bpe_upload(swt_bpe_table *t) {
   return SWT_OK;
 }
 
-template <bool Packed, int Cap>
-static void launch_encode_kernel_as(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
-                                    const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot,
-                                    unsigned long long *d_rec, unsigned long long *d_drec, hipStream_t st) {
-  const uint32_t sh = 32u - t->bits;
-  if (d_rec)
-    hipLaunchKernelGGL((bpe_encode_kernel<Packed, Cap, 1>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, t->d_slots, sh, t->d_merged, ws.scratch.as<uint32_t>(),
-                       ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0},
-                       (uint32_t)ablation_knob(0));
-  else
-    hipLaunchKernelGGL((bpe_encode_kernel<Packed, Cap, 0>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, t->d_slots, sh, t->d_merged, ws.scratch.as<uint32_t>(),
-                       ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0},
-                       (uint32_t)ablation_knob(0));
-}
-
 // the word-lane kernel: running text, or the unique words of the dedup path (d_rec)
 template <bool Packed, bool Proper, int Cap>
 static void launch_lane_kernel_as(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
@@ -1277,15 +769,6 @@ static void launch_lane_kernel_as(swt_bpe_table *t, uint64_t n_tiles, const Tile
 }
 
 extern "C" {
-
-// diagnostics (not part of include/swt.h): resident workgroups per CU the runtime grants the encode kernel
-int swt_debug_occupancy(int which) try {
-  int n = -1;
-  hipError_t e = which == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bpe_lane_kernel<true, true, kLaneCap, 0>, 64, 0)
-                 : which  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bpe_encode_kernel<false, kBpeCap, 0>, 64, 0)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bpe_encode_kernel<true, kBpeCap, 0>, 64, 0);
-  return e == hipSuccess ? n : -(int)e;
-} SWT_API_CATCH
 
 // diagnostics (not part of include/swt.h): what swt_bpe_table_create decided.  0: log2 of the slots, 1: packed values,
 // 2: proper (every pair ranks above the merges producing its symbols), 3: entries in the table, 4: every entry is found where
@@ -1367,9 +850,6 @@ int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint
         }
       }
   }
-  if (const char *e = getenv("SWT_BPE_KERNEL")) t->lane_kernel = strcmp(e, "bytes") != 0;
-  if (const char *e = getenv("SWT_BPE_UTILE")) t->opt_unique_tile = atoi(e);  // measurement knob, as SWT_OPT_UNIQUE_TILE
-  if (const char *e = getenv("SWT_BPE_DEDUP")) t->dd.opt_mode = atoi(e);       // measurement knob, as SWT_OPT_DEDUP (0 auto, 1 never, 2 always)
   t->h_merged.assign(merged, merged + n_merges);
   // packed values when every rank and every merged-symbol index fits 16 bits (any realistic table below 65k merges)
   t->packed = n_merges < 0xFFFEu;
@@ -1419,34 +899,24 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
 // cap = staged bytes per chunk (LDS footprint ~ 20 B per byte): 512 for running text, less for the unique-word pass
 static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
                                  const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot, unsigned long long *d_rec,
-                                 unsigned long long *d_drec, hipStream_t st, int cap = kBpeCap) {
-#define SWT_ENC(P, C) launch_encode_kernel_as<P, C>(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, d_uslot, d_rec, d_drec, st)
+                                 unsigned long long *d_drec, hipStream_t st, int cap = kLaneCap) {
 #define SWT_LANE(P, R, C) launch_lane_kernel_as<P, R, C>(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, d_uslot, d_rec, d_drec, st)
 #define SWT_LANE_CAPS(P, R) do { if (cap == 128) SWT_LANE(P, R, 128); else if (cap == 256) SWT_LANE(P, R, 256); else SWT_LANE(P, R, 512); } while (0)
-  if (t->lane_kernel && !d_rec) {  // running text: the one chunk size the tile was chosen for
+  if (!d_rec) {  // running text: the one chunk size the tile was chosen for
     if (t->packed) { if (t->proper) SWT_LANE(true, true, kLaneCap); else SWT_LANE(true, false, kLaneCap); }
     else { if (t->proper) SWT_LANE(false, true, kLaneCap); else SWT_LANE(false, false, kLaneCap); }
     return;
   }
-  if (t->lane_kernel) {
-    if (t->packed) { if (t->proper) SWT_LANE_CAPS(true, true); else SWT_LANE_CAPS(true, false); }
-    else { if (t->proper) SWT_LANE_CAPS(false, true); else SWT_LANE_CAPS(false, false); }
-    return;
-  }
-  if (t->packed) {
-    if (cap == 128) SWT_ENC(true, 128); else if (cap == 256) SWT_ENC(true, 256); else SWT_ENC(true, 512);
-  } else {
-    if (cap == 128) SWT_ENC(false, 128); else if (cap == 256) SWT_ENC(false, 256); else SWT_ENC(false, 512);
-  }
+  if (t->packed) { if (t->proper) SWT_LANE_CAPS(true, true); else SWT_LANE_CAPS(true, false); }
+  else { if (t->proper) SWT_LANE_CAPS(false, true); else SWT_LANE_CAPS(false, false); }
 #undef SWT_LANE_CAPS
 #undef SWT_LANE
-#undef SWT_ENC
 }
 
 static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls,
                              hipStream_t st) {
-  const uint32_t tile = t->lane_kernel ? (uint32_t)kLaneTile : (uint32_t)kBpeTile;
+  const uint32_t tile = (uint32_t)kLaneTile;
   const uint64_t n_tiles = tile_count(n_bytes, tile);
   if (n_tiles > 0x7FFFFFFFull)
     return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
@@ -1461,17 +931,8 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
                          t->d_merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
                          (unsigned long long *)nullptr, (unsigned long long *)nullptr, direct);
     };
-    auto one_bytes = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, t->d_slots, sh,
-                         t->d_merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
-                         (unsigned long long *)nullptr, (unsigned long long *)nullptr, direct, 0u);
-    };
-    if (t->lane_kernel) {
-      if (t->packed) { if (t->proper) one_lane(bpe_lane_kernel<true, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<true, false, kLaneCap, 2>); }
-      else { if (t->proper) one_lane(bpe_lane_kernel<false, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2>); }
-    } else {
-      if (t->packed) one_bytes(bpe_encode_kernel<true, kBpeCap, 2>); else one_bytes(bpe_encode_kernel<false, kBpeCap, 2>);
-    }
+    if (t->packed) { if (t->proper) one_lane(bpe_lane_kernel<true, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<true, false, kLaneCap, 2>); }
+    else { if (t->proper) one_lane(bpe_lane_kernel<false, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2>); }
     SWT_HIP(hipGetLastError());
     return SWT_OK;
   }
@@ -1479,7 +940,7 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, n_tiles, tile, ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st, t->lane_kernel ? kLaneCap : kBpeCap);
+  launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st);
   prof_end(st);
   launch_scan_gather(d_sent_off, n_sent, n_tiles, ws, d_out_ids, d_out_off, d_n_tokens, st);
   prof_end(st, 2);
@@ -1490,13 +951,14 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
 // The dedup path (swt_dedup.h): eight launches, no host round trip -- the number of unique words stays on the device, so
 // the unique-word encode has a fixed number of workgroups and its tile size follows on the device (ureg_kernel writes its plan).
 // Returns 1 when the batch is too large for the 32-bit fields of this path (the caller takes the direct path).
-constexpr int kUTile = 128;            // smallest tile of the unique-word pass (chunk = 2 such tiles); measured: 64 -> 84 us, 128 -> 72 us, 256 -> 88 us
 constexpr uint64_t kUMaxTiles = 8192;  // its launch size: 256 CUs x 32 single-wave workgroups
 static int bpe_encode_dedup(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                             uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls, hipStream_t st) {
   int rc;
-  // the word-lane kernel wants a batch of words per tile: 256-byte tiles (S85k-lex: 64 -> 0.182, 128 -> 0.174, 256 -> 0.168 ms per call)
-  const uint32_t tile2 = t->opt_unique_tile == 256 ? 256u : (t->opt_unique_tile == 64 ? 64u : (t->opt_unique_tile == 128 || !t->lane_kernel ? (uint32_t)kUTile : 256u));
+  // tile of the unique-word pass (chunk = 2 such tiles): the kernel wants a batch of words per tile, so 256 bytes unless
+  // SWT_OPT_UNIQUE_TILE says otherwise (S85k-lex: 64 -> 0.182, 128 -> 0.174, 256 -> 0.168 ms per call)
+  const int ut = t->opt_unique_tile;
+  const uint32_t tile2 = (ut == 64 || ut == 128) ? (uint32_t)ut : 256u;
   uint64_t n_tiles2 = tile_count(n_bytes, tile2);  // the unique words together are no longer than the text
   if (n_tiles2 > kUMaxTiles) n_tiles2 = kUMaxTiles;
   if (n_bytes > kDedupMaxBytes) return 1;

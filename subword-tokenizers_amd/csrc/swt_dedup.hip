@@ -1,5 +1,4 @@
 // swt_dedup.hip -- word-level dedup inside one encode call (see swt_dedup.h), the kernels and the two host halves.
-#include <cstdlib>
 
 #include "swt_dedup.h"
 
@@ -31,7 +30,6 @@ struct DedupTab {
   unsigned long long *rec;       // per slot: the inserter leaves the byte length; the unique-word encode replaces it by
                                  // token count:32 | place of the tokens in its scratch:32
   uint64_t n_bytes;              // size of the text (wide compares stay inside it)
-  uint32_t diag;                 // diagnostics: bit 0 tallies CAS successes / failures behind `overflow`
   uint32_t bits;
   uint32_t epoch;
   // The table is kept SMALL (a few MB: its hot lines stay in the 4-MiB L2 of every XCD) and is not sized for the worst
@@ -44,7 +42,6 @@ struct DedupTab {
   // (count, bytes) numbers the words afterwards (bpe_ureg_kernel).
   unsigned long long *newlist;   // slot:32 | position:32 (the inserter leaves the byte length in rec[slot]); a tile's entries start at [span_base >> 1]
   unsigned long long *tile_new;  // per tile: new words:32 | their bytes:32 (a dedup call holds at most 2^30 bytes)
-  unsigned int *overflow;
 };
 
 constexpr uint32_t kDdMaxProbes = 24;
@@ -126,39 +123,36 @@ __device__ __forceinline__ uint32_t dd_find_or_insert_lds(const DedupTab &D, con
   uint32_t probes = 0;
   const unsigned long long head = ((unsigned long long)D.epoch << 56) | (((h >> 40) & 0xFFull) << 48) | ((unsigned long long)lf << 40);
   uint32_t idx = (uint32_t)h & mask;
-  if (!(D.diag & 2u)) {
-    // The common case first, through the caches: a word of running text has usually been tabled long ago, and a slot of this
-    // call is written once and never changes, so a plain (L2-cached) load can only show it complete or not at all -- a hit
-    // found here is exact, anything else (the slot looks free, or stale from an earlier call, or holds another word twice in a
-    // row) is settled by the coherent path below, from the home slot.  The device-scope loads of that path fetch a 64-byte
-    // line from the fabric per lookup: 1.4 GB of the FastWP call's 2.8 GB (profiles/r03_wp_encode_FETCH_SIZE_per_kernel.csv).
-    uint32_t j = idx;
-    for (int p = 0; p < 2; p++) {
-      const unsigned long long v = D.slot[j];
-      if ((v & ~kDOffMask) == head) {
-        const uint64_t ro = v & kDOffMask;
-        if (ro + 16 <= D.n_bytes) {
-          const uint8_t *rep = text + ro;
-          unsigned long long r0 = *reinterpret_cast<const u64u *>(rep), r1 = *reinterpret_cast<const u64u *>(rep + 8);
-          if (len < 8) { r0 &= (1ull << (8 * len)) - 1ull; r1 = 0; }
-          else if (len < 16) r1 &= (1ull << (8 * (len - 8))) - 1ull;
-          bool same = r0 == w0 && r1 == w1;
-          for (uint32_t i = 16; i < len && same; i++) same = rep[i] == mine[i];
-          if (same) return j;
-        } else {
-          break;
-        }
-      } else if ((uint32_t)(v >> 56) != D.epoch) {
+  // The common case first, through the caches: a word of running text has usually been tabled long ago, and a slot of this
+  // call is written once and never changes, so a plain (L2-cached) load can only show it complete or not at all -- a hit
+  // found here is exact, anything else (the slot looks free, or stale from an earlier call, or holds another word twice in a
+  // row) is settled by the coherent path below, from the home slot.  The device-scope loads of that path fetch a 64-byte
+  // line from the fabric per lookup: 1.4 GB of the FastWP call's 2.8 GB (profiles/r03_wp_encode_FETCH_SIZE_per_kernel.csv).
+  uint32_t j = idx;
+  for (int p = 0; p < 2; p++) {
+    const unsigned long long v = D.slot[j];
+    if ((v & ~kDOffMask) == head) {
+      const uint64_t ro = v & kDOffMask;
+      if (ro + 16 <= D.n_bytes) {
+        const uint8_t *rep = text + ro;
+        unsigned long long r0 = *reinterpret_cast<const u64u *>(rep), r1 = *reinterpret_cast<const u64u *>(rep + 8);
+        if (len < 8) { r0 &= (1ull << (8 * len)) - 1ull; r1 = 0; }
+        else if (len < 16) r1 &= (1ull << (8 * (len - 8))) - 1ull;
+        bool same = r0 == w0 && r1 == w1;
+        for (uint32_t i = 16; i < len && same; i++) same = rep[i] == mine[i];
+        if (same) return j;
+      } else {
         break;
       }
-      j = (j + 1) & mask;
+    } else if ((uint32_t)(v >> 56) != D.epoch) {
+      break;
     }
+    j = (j + 1) & mask;
   }
   for (;;) {
     unsigned long long v = __hip_atomic_load(&D.slot[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((uint32_t)(v >> 56) != D.epoch) {  // free in this call (never used, or left over from an earlier call)
       const unsigned long long prev = atomicCAS(&D.slot[idx], v, head | gpos);
-      if (D.diag & 1u) atomicAdd(&D.overflow[prev == v ? 1 : 2], 1u);
       if (prev == v) {
         is_new = true;  // listed by the caller
         return idx;
@@ -188,16 +182,13 @@ __device__ __forceinline__ uint32_t dd_find_or_insert_lds(const DedupTab &D, con
   }
 }
 
-// ---- the split, sixteen bytes per lane (FastWP chunks) -------------------------------------------------------------------------
-// wordref_kernel<kDedupWp> issues 254 M vector and 199 M scalar instructions per 141 MB call -- 81 % of the vector pipe's time
-// (profiles/r03_sq_counters.txt) -- and two thirds of them are the split loop: one byte per lane, 64 bytes per trip, five
-// ballots and ~70 scalar mask operations per trip.  A chunk between str.isspace characters needs none of the pre-tokenizer's
-// classes, so the lane form takes SIXTEEN bytes per lane (one ds_read_b128), finds the ASCII whitespace of its four dwords with
-// carry-free byte arithmetic, looks only its (rare) non-ASCII lead bytes up in the class table, and does the mask algebra of the
-// byte-lane loop on its own 16 bits -- the whitespace smear and the "byte before me" across the lane boundary from the lane
-// below (one shuffle) -- a whole KiB per trip.  It leaves EXACTLY what the byte-lane loop leaves (endm / wst / nwb per 64-byte
-// block, the list of word starts, the cut): the rest of the kernel does not know the difference, and every dedup test compares
-// the two forms' outputs through the oracle.  SWT_DD_OLD_SPLIT=1 runs the byte-lane loop instead (comparison).
+// ---- the split, sixteen bytes per lane -------------------------------------------------------------------------------------------
+// Each lane takes SIXTEEN bytes (one ds_read_b128), finds the ASCII whitespace (and, for BPE words, punctuation) of its four
+// dwords with carry-free byte arithmetic, looks only its (rare) non-ASCII lead bytes up in the class table, and does the mask
+// algebra on its own 16 bits -- the whitespace smear and the "byte before me" across the lane boundary from the lane below
+// (one shuffle) -- a whole KiB per trip.  It leaves, per 64-byte block, endm (word ends) / wst (word starts) / nwb (words
+// before the block), plus the list of word starts and the cut.  (A split of one byte per lane spent two thirds of the kernel's
+// instructions on 64 bytes per trip: profiles/r03_sq_counters.txt.)
 __device__ __forceinline__ uint32_t dd_nibble(uint32_t flags_bit7) {  // bit 7 of each of the 4 bytes -> 4 bits, byte 0 lowest
   return ((((flags_bit7 >> 7) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu;
 }
@@ -217,13 +208,11 @@ struct WordrefLds {
 // Mode kDedupBpe: words end at BertPreTokenizer whitespace, every punctuation code point is a word of its own, and a
 // one-symbol word is recorded as its own token.  Mode kDedupWp: words are the chunks between str.isspace characters and
 // every one of them goes through the table.
-// Lanes16: the split takes sixteen bytes per lane (an instance of its own, so that neither form pays the other's registers)
-template <int Mode, bool Lanes16 = false>
+template <int Mode>
 __global__ __launch_bounds__(64, SWT_WORDREF_WAVES) void wordref_kernel(const uint8_t *__restrict__ text, uint64_t n_bytes,
                                                      const uint64_t *__restrict__ sent_off, const uint64_t *__restrict__ plan,
                                                      const uint8_t *__restrict__ cls_tab, DedupTab D, uint32_t *__restrict__ wref,
-                                                     uint32_t *__restrict__ sent_word, uint32_t *__restrict__ tile_words,
-                                                     uint32_t dbg) {
+                                                     uint32_t *__restrict__ sent_word, uint32_t *__restrict__ tile_words) {
   constexpr uint8_t kWsBit = Mode == kDedupWp ? kClsPySpace : kClsWs;
   constexpr bool kPunctSplits = Mode == kDedupBpe;
   __shared__ WordrefLds L;
@@ -280,155 +269,105 @@ __global__ __launch_bounds__(64, SWT_WORDREF_WAVES) void wordref_kernel(const ui
     }
     __syncthreads();
     uint32_t nw = 0;
-    bool prev_wb = true;
     int cut = -1;
-    if (Lanes16) {
-      // carried from trip to trip: the last lane's raw whitespace and continuation bits (the lane below lane 0)
-      uint32_t carry_wb = 0x8000u, carry_ct = 0u;  // chunk start: "the byte before belongs to whitespace"
-      const uint32_t n_groups = nblk * 4;          // 16-byte groups that lie in the blocks the kernel looks at
-      for (uint32_t g0 = 0; g0 < n_groups; g0 += 64) {
-        const uint32_t g = g0 + (uint32_t)lane, p0 = g * 16;
-        const uint4 x = *reinterpret_cast<const uint4 *>(&L.txt[p0 < (uint32_t)kDCap ? p0 : 0]);
-        uint32_t sp_all = 0, pn_all = 0, ct_all = 0, hi_all = 0;
+    // carried from trip to trip: the last lane's raw whitespace and continuation bits (the lane below lane 0)
+    uint32_t carry_wb = 0x8000u, carry_ct = 0u;  // chunk start: "the byte before belongs to whitespace"
+    const uint32_t n_groups = nblk * 4;          // 16-byte groups that lie in the blocks the kernel looks at
+    for (uint32_t g0 = 0; g0 < n_groups; g0 += 64) {
+      const uint32_t g = g0 + (uint32_t)lane, p0 = g * 16;
+      const uint4 x = *reinterpret_cast<const uint4 *>(&L.txt[p0 < (uint32_t)kDCap ? p0 : 0]);
+      uint32_t sp_all = 0, pn_all = 0, ct_all = 0, hi_all = 0;
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const uint32_t w = q == 0 ? x.x : (q == 1 ? x.y : (q == 2 ? x.z : x.w)), x7 = w & 0x7F7F7F7Fu, hi = w & 0x80808080u;
-          // a byte below 0x80 lies in [lo, hi] iff bit 7 of (b + 0x80 - lo) is set and bit 7 of (b + 0x7F - hi) is not: no carry
-          // leaves a byte.  The ASCII ranges are checked against the class table on the host (dedup_front).
+      for (int q = 0; q < 4; q++) {
+        const uint32_t w = q == 0 ? x.x : (q == 1 ? x.y : (q == 2 ? x.z : x.w)), x7 = w & 0x7F7F7F7Fu, hi = w & 0x80808080u;
+        // a byte below 0x80 lies in [lo, hi] iff bit 7 of (b + 0x80 - lo) is set and bit 7 of (b + 0x7F - hi) is not: no carry
+        // leaves a byte.  tests/test_host_logic.py::test_ascii_ranges_of_the_split_match_the_class_table keeps these ranges
+        // equal to the class table's.
 #define SWT_IN(lo_, hi_) ((x7 + (0x80u - (lo_)) * 0x01010101u) & ~(x7 + (0x7Fu - (hi_)) * 0x01010101u))
-          uint32_t in_ws, in_pn = 0;
-          if (Mode == kDedupWp) {
-            in_ws = SWT_IN(0x09u, 0x0Du) | SWT_IN(0x1Cu, 0x20u);  // str.isspace
-          } else {
-            in_ws = SWT_IN(0x09u, 0x0Du) | SWT_IN(0x20u, 0x20u);  // the pre-tokenizer's whitespace ...
-            in_pn = SWT_IN(0x21u, 0x2Fu) | SWT_IN(0x3Au, 0x40u) | SWT_IN(0x5Bu, 0x60u) | SWT_IN(0x7Bu, 0x7Eu);  // ... and punctuation
-          }
+        uint32_t in_ws, in_pn = 0;
+        if (Mode == kDedupWp) {
+          in_ws = SWT_IN(0x09u, 0x0Du) | SWT_IN(0x1Cu, 0x20u);  // str.isspace
+        } else {
+          in_ws = SWT_IN(0x09u, 0x0Du) | SWT_IN(0x20u, 0x20u);  // the pre-tokenizer's whitespace ...
+          in_pn = SWT_IN(0x21u, 0x2Fu) | SWT_IN(0x3Au, 0x40u) | SWT_IN(0x5Bu, 0x60u) | SWT_IN(0x7Bu, 0x7Eu);  // ... and punctuation
+        }
 #undef SWT_IN
-          sp_all |= dd_nibble(in_ws & ~hi & 0x80808080u) << (4 * q);
-          if (kPunctSplits) pn_all |= dd_nibble(in_pn & ~hi & 0x80808080u) << (4 * q);
-          ct_all |= dd_nibble(hi & ~(w << 1)) << (4 * q);  // 10xxxxxx: a continuation byte
-          hi_all |= dd_nibble(hi & (w << 1)) << (4 * q);   // 11xxxxxx: a lead byte whose class the table knows
-        }
-        // my 16 bytes' place in [off0, staged)
-        const uint32_t lo = off0 > p0 ? (off0 - p0 < 16u ? off0 - p0 : 16u) : 0u;
-        const uint32_t hi_n = staged > p0 ? (staged - p0 < 16u ? staged - p0 : 16u) : 0u;
-        const uint32_t inr16 = (((1u << hi_n) - 1u) & ~((1u << lo) - 1u)) & 0xFFFFu;
-        uint32_t sp16 = sp_all & inr16, pn16 = pn_all & inr16;
-        const uint32_t ct16 = ct_all & inr16;
-        // the non-ASCII lead bytes: decode and look up, as the byte-lane loop does for every byte
-        for (uint32_t m = hi_all & inr16; m; m &= m - 1u) {
-          const uint32_t j = (uint32_t)__builtin_ctz(m), p = p0 + j;
-          const uint8_t b = L.txt[p];
-          int len = utf8_len(b);
-          if (p + len > staged) len = (int)(staged - p);
-          uint32_t cp = b;
-          if (len > 1) {
-            cp = b & (0xFF >> (len + 1));
-            for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
-          }
-          uint32_t c2;  // bit 0: whitespace of the mode, bit 1: punctuation
-          if (cp < (uint32_t)kClsLds) {
-            c2 = (L.cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u;
-          } else {
-            const uint8_t c = cp < kNumCodePoints ? cls_tab[cp] : (uint8_t)0;
-            c2 = ((c & kWsBit) ? 1u : 0u) | ((kPunctSplits && (c & kClsPunct)) ? 2u : 0u);
-          }
-          if (c2 & 1u) sp16 |= 1u << j;
-          if (c2 & 2u) pn16 |= 1u << j;
-        }
-        const uint32_t wsm16 = (sp16 | ~inr16) & 0xFFFFu;  // bytes outside the chunk behave as whitespace
-        const uint32_t lead16 = ~ct16 & 0xFFFFu;
-        // whitespace smear over continuation bytes and "the byte before me", with the lane below as the low half of a window
-        const uint32_t raw16 = wsm16 | pn16;  // bytes of whitespace / punctuation characters, before the smear
-        uint32_t below_wb = __shfl_up(raw16, 1), below_ct = __shfl_up(ct16, 1);
-        if (lane == 0) { below_wb = carry_wb; below_ct = carry_ct; }
-        const uint32_t c32 = below_ct | (ct16 << 16);
-        uint32_t wb32 = below_wb | (raw16 << 16);
-        wb32 |= (wb32 << 1) & c32;
-        wb32 |= (wb32 << 1) & c32;
-        wb32 |= (wb32 << 1) & c32;
-        const uint32_t ss16 = reinterpret_cast<const uint16_t *>(L.sbits)[g < (uint32_t)(kDBlocks + 1) * 4u ? g : 0];
-        const uint32_t first16 = g == 0 ? (1u << off0) : 0u;
-        const uint32_t before16 = ((wb32 >> 15) | ss16 | first16) & 0xFFFFu;
-        const uint32_t sym16 = lead16 & ~wsm16 & inr16;
-        const uint32_t ws16 = sym16 & (pn16 | before16);
-        // chunk cut candidates: word boundaries strictly inside, with room for a whole UTF-8 char behind them
-        const uint32_t c_lo = off0 + 1u > p0 ? (off0 + 1u - p0 < 16u ? off0 + 1u - p0 : 16u) : 0u;
-        const uint32_t c_hi = staged >= p0 + 4u ? (staged - 3u - p0 < 16u ? staged - 3u - p0 : 16u) : 0u;  // p + 4 <= staged
-        const uint32_t cutr16 = (c_hi > c_lo ? (((1u << c_hi) - 1u) & ~((1u << c_lo) - 1u)) : 0u) & 0xFFFFu;
-        const uint32_t cut16 = lead16 & (wsm16 | pn16 | ss16) & cutr16 & inr16;
-        const unsigned long long CUTL = __ballot(cut16 != 0u);
-        if (CUTL) {
-          const int src = 63 - __builtin_clzll(CUTL);
-          const uint32_t top = __shfl(cut16, src);
-          cut = (int)((g0 + (uint32_t)src) * 16u + 31u - (uint32_t)__builtin_clz(top));
-        }
-        // words: ranks by a wave scan of the lanes' counts
-        const uint32_t n_mine = (uint32_t)__popc(ws16);
-        uint32_t incl = n_mine;
-        for (int d = 1; d < 64; d <<= 1) {
-          const uint32_t y = __shfl_up(incl, d);
-          if (lane >= d) incl += y;
-        }
-        uint32_t at = nw + incl - n_mine;
-        if (g < n_groups) {
-          reinterpret_cast<uint16_t *>(L.endm)[g] = (uint16_t)(wsm16 | ws16);
-          reinterpret_cast<uint16_t *>(L.wst)[g] = (uint16_t)ws16;
-          if ((g & 3u) == 0u) L.nwb[g >> 2] = at;
-          for (uint32_t m = ws16; m; m &= m - 1u) L.wl[at++] = (uint16_t)(p0 + (uint32_t)__builtin_ctz(m));
-        }
-        nw += __shfl(incl, 63);
-        carry_wb = __shfl(raw16, 63);
-        carry_ct = __shfl(ct16, 63);
+        sp_all |= dd_nibble(in_ws & ~hi & 0x80808080u) << (4 * q);
+        if (kPunctSplits) pn_all |= dd_nibble(in_pn & ~hi & 0x80808080u) << (4 * q);
+        ct_all |= dd_nibble(hi & ~(w << 1)) << (4 * q);  // 10xxxxxx: a continuation byte
+        hi_all |= dd_nibble(hi & (w << 1)) << (4 * q);   // 11xxxxxx: a lead byte whose class the table knows
       }
-    } else
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-      const uint32_t p = blk * 64 + lane;
-      const bool inr = p >= off0 && p < staged;
-      const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
-      const bool lead = !utf8_is_cont(b);
-      uint32_t cp = b;
-      if (b >= 0xC0) {
+      // my 16 bytes' place in [off0, staged)
+      const uint32_t lo = off0 > p0 ? (off0 - p0 < 16u ? off0 - p0 : 16u) : 0u;
+      const uint32_t hi_n = staged > p0 ? (staged - p0 < 16u ? staged - p0 : 16u) : 0u;
+      const uint32_t inr16 = (((1u << hi_n) - 1u) & ~((1u << lo) - 1u)) & 0xFFFFu;
+      uint32_t sp16 = sp_all & inr16, pn16 = pn_all & inr16;
+      const uint32_t ct16 = ct_all & inr16;
+      // the non-ASCII lead bytes: decode and look up
+      for (uint32_t m = hi_all & inr16; m; m &= m - 1u) {
+        const uint32_t j = (uint32_t)__builtin_ctz(m), p = p0 + j;
+        const uint8_t b = L.txt[p];
         int len = utf8_len(b);
         if (p + len > staged) len = (int)(staged - p);
+        uint32_t cp = b;
         if (len > 1) {
           cp = b & (0xFF >> (len + 1));
           for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
         }
-      }
-      uint32_t c2 = 1u;  // bit 0: whitespace of the mode (bytes outside the chunk count as such), bit 1: punctuation
-      if (inr && lead) {
+        uint32_t c2;  // bit 0: whitespace of the mode, bit 1: punctuation
         if (cp < (uint32_t)kClsLds) {
           c2 = (L.cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u;
         } else {
           const uint8_t c = cp < kNumCodePoints ? cls_tab[cp] : (uint8_t)0;
           c2 = ((c & kWsBit) ? 1u : 0u) | ((kPunctSplits && (c & kClsPunct)) ? 2u : 0u);
         }
+        if (c2 & 1u) sp16 |= 1u << j;
+        if (c2 & 2u) pn16 |= 1u << j;
       }
-      const unsigned long long INR = __ballot(inr);
-      const unsigned long long LEAD = __ballot(lead);
-      const unsigned long long WSm = __ballot(lead && (c2 & 1u));
-      const unsigned long long PNm = kPunctSplits ? __ballot(lead && (c2 & 2u)) : 0ull;
-      const unsigned long long CONT = ~LEAD;
-      unsigned long long WB = WSm | PNm | ((prev_wb && (CONT & 1ull)) ? 1ull : 0ull);
-      WB |= (WB << 1) & CONT;
-      WB |= (WB << 1) & CONT;
-      WB |= (WB << 1) & CONT;
-      const unsigned long long SS = L.sbits[blk];
-      const unsigned long long first_bit = blk == 0 ? (1ull << off0) : 0ull;
-      const unsigned long long before = (WB << 1) | (prev_wb ? 1ull : 0ull) | SS | first_bit;
-      const unsigned long long SYM = LEAD & ~WSm & INR;
-      const unsigned long long WSTART = SYM & (PNm | before);
-      const unsigned long long CUT = LEAD & (WSm | PNm | SS) & __ballot(inr && p > off0 && p + 4 <= staged);
-      if (CUT) cut = (int)(blk * 64 + 63 - __builtin_clzll(CUT));
-      if (lane == 0) {
-        L.endm[blk] = WSm | WSTART | ~INR;
-        L.wst[blk] = WSTART;
-        L.nwb[blk] = nw;
+      const uint32_t wsm16 = (sp16 | ~inr16) & 0xFFFFu;  // bytes outside the chunk behave as whitespace
+      const uint32_t lead16 = ~ct16 & 0xFFFFu;
+      // whitespace smear over continuation bytes and "the byte before me", with the lane below as the low half of a window
+      const uint32_t raw16 = wsm16 | pn16;  // bytes of whitespace / punctuation characters, before the smear
+      uint32_t below_wb = __shfl_up(raw16, 1), below_ct = __shfl_up(ct16, 1);
+      if (lane == 0) { below_wb = carry_wb; below_ct = carry_ct; }
+      const uint32_t c32 = below_ct | (ct16 << 16);
+      uint32_t wb32 = below_wb | (raw16 << 16);
+      wb32 |= (wb32 << 1) & c32;
+      wb32 |= (wb32 << 1) & c32;
+      wb32 |= (wb32 << 1) & c32;
+      const uint32_t ss16 = reinterpret_cast<const uint16_t *>(L.sbits)[g < (uint32_t)(kDBlocks + 1) * 4u ? g : 0];
+      const uint32_t first16 = g == 0 ? (1u << off0) : 0u;
+      const uint32_t before16 = ((wb32 >> 15) | ss16 | first16) & 0xFFFFu;
+      const uint32_t sym16 = lead16 & ~wsm16 & inr16;
+      const uint32_t ws16 = sym16 & (pn16 | before16);
+      // chunk cut candidates: word boundaries strictly inside, with room for a whole UTF-8 char behind them
+      const uint32_t c_lo = off0 + 1u > p0 ? (off0 + 1u - p0 < 16u ? off0 + 1u - p0 : 16u) : 0u;
+      const uint32_t c_hi = staged >= p0 + 4u ? (staged - 3u - p0 < 16u ? staged - 3u - p0 : 16u) : 0u;  // p + 4 <= staged
+      const uint32_t cutr16 = (c_hi > c_lo ? (((1u << c_hi) - 1u) & ~((1u << c_lo) - 1u)) : 0u) & 0xFFFFu;
+      const uint32_t cut16 = lead16 & (wsm16 | pn16 | ss16) & cutr16 & inr16;
+      const unsigned long long CUTL = __ballot(cut16 != 0u);
+      if (CUTL) {
+        const int src = 63 - __builtin_clzll(CUTL);
+        const uint32_t top = __shfl(cut16, src);
+        cut = (int)((g0 + (uint32_t)src) * 16u + 31u - (uint32_t)__builtin_clz(top));
       }
-      if ((WSTART >> lane) & 1ull) L.wl[nw + __popcll(WSTART & lt)] = (uint16_t)p;
-      nw += __popcll(WSTART);
-      prev_wb = (WB >> 63) & 1ull;
+      // words: ranks by a wave scan of the lanes' counts
+      const uint32_t n_mine = (uint32_t)__popc(ws16);
+      uint32_t incl = n_mine;
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d);
+        if (lane >= d) incl += y;
+      }
+      uint32_t at = nw + incl - n_mine;
+      if (g < n_groups) {
+        reinterpret_cast<uint16_t *>(L.endm)[g] = (uint16_t)(wsm16 | ws16);
+        reinterpret_cast<uint16_t *>(L.wst)[g] = (uint16_t)ws16;
+        if ((g & 3u) == 0u) L.nwb[g >> 2] = at;
+        for (uint32_t m = ws16; m; m &= m - 1u) L.wl[at++] = (uint16_t)(p0 + (uint32_t)__builtin_ctz(m));
+      }
+      nw += __shfl(incl, 63);
+      carry_wb = __shfl(raw16, 63);
+      carry_ct = __shfl(ct16, 63);
     }
     __syncthreads();
     uint32_t ce = staged;
@@ -501,7 +440,6 @@ __global__ __launch_bounds__(64, SWT_WORDREF_WAVES) void wordref_kernel(const ui
     }
     // one lane per word
     const uint32_t wd0 = words_done;
-    if (!(dbg & 1))
     for (uint32_t k0 = 0; k0 < nw; k0 += 64) {
       const uint32_t k = k0 + lane;
       const uint32_t s = k < nw ? L.wl[k] : 0xFFFFu;
@@ -923,8 +861,6 @@ int dedup_front(DedupEngine &E, TileWorkspace &ws, const uint8_t *d_text, uint64
   // (see DedupTab); never cleared (epoch).  rec[] = the table's slots, then the own slots of the words that overflowed.
   uint32_t bits = 16;
   while ((1ull << bits) < n_bytes / 32 && bits < 24) bits++;
-  static const int env_bits = getenv("SWT_DD_BITS") ? atoi(getenv("SWT_DD_BITS")) : 0;  // measurement knob
-  if (env_bits >= 4 && env_bits <= 24 && !E.opt_table_bits) bits = (uint32_t)env_bits;
   if (E.opt_table_bits) {  // SWT_OPT_DEDUP_TABLE_BITS (tests: a table so small that words overflow it)
     bits = E.opt_table_bits;
     if (bits != E.bits) E.bits = 0;
@@ -954,54 +890,31 @@ int dedup_front(DedupEngine &E, TileWorkspace &ws, const uint8_t *d_text, uint64
     if ((rc = E.new_blk.reserve((2 * nb_new + 2) * 8))) return rc;
     SWT_HIP(hipMemsetAsync(E.new_blk.p, 0, E.new_blk.cap, st));  // the scan's ticket starts at zero (and leaves it so)
   }
-  unsigned long long *d_misc = E.misc.as<unsigned long long>();  // [0] unique words:32 | their bytes:32, [1..2] diagnostics
+  unsigned long long *d_misc = E.misc.as<unsigned long long>();  // [0] unique words:32 | their bytes:32
   DedupTab D;
   D.slot = E.slot.as<unsigned long long>();
   D.rec = E.rec.as<unsigned long long>();
   D.n_bytes = n_bytes;
-  static const bool coherent_only = getenv("SWT_DD_COHERENT") != nullptr;  // comparison runs: no cached first look
-  D.diag = ((ablation_knob(2) & 4) ? 1u : 0u) | (coherent_only ? 2u : 0u);
   D.bits = E.bits;
   D.epoch = E.epoch;
   D.ovf_shift = ovf_shift;
   D.newlist = E.newlist.as<unsigned long long>();
   D.tile_new = E.tile_new.as<unsigned long long>();
-  D.overflow = reinterpret_cast<unsigned int *>(d_misc + 1);
-  if (D.diag & 1u) SWT_HIP(hipMemsetAsync(d_misc, 0, 32, st));
   uint32_t *wref = ws.scratch.as<uint32_t>();
   uint64_t *plan1 = ws.plan.as<uint64_t>();
   unsigned long long *new_local = E.new_local.as<unsigned long long>(), *new_blk = E.new_blk.as<unsigned long long>();
   launch_plan(d_sent_off, n_sent, n_tiles, kDTile, plan1, st);
-  // the lane-per-16-bytes split knows str.isspace in ASCII as two ranges: if the class table ever says otherwise, or on request
-  // (SWT_DD_OLD_SPLIT=1), the byte-lane loop runs
-  static const bool ascii_ok = [] {
-    const uint8_t *cls = host_class_table();
-    for (uint32_t c = 0; c < 128; c++) {
-      if (((cls[c] & kClsPySpace) != 0) != ((c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20))) return false;
-      if (((cls[c] & kClsWs) != 0) != ((c >= 0x09 && c <= 0x0D) || c == 0x20)) return false;
-      if (((cls[c] & kClsPunct) != 0) != ((c >= 0x21 && c <= 0x2F) || (c >= 0x3A && c <= 0x40) || (c >= 0x5B && c <= 0x60) || (c >= 0x7B && c <= 0x7E))) return false;
-    }
-    return true;
-  }();
-  const char *old_split = getenv("SWT_DD_OLD_SPLIT");
-  const uint32_t split_flag = (!ascii_ok || (old_split && *old_split && *old_split != '0')) ? 0x80000000u : 0u;
   prof_begin(st, 3);
   // (Two launches -- a first one over 1/8 .. 1/128 of the tiles to table the frequent words, so that every compute unit of the
   // second finds them through its caches -- were measured: 0.843 - 0.862 ms against 0.839 ms per FastWP call.  One launch.)
   {
     const dim3 grid((unsigned)n_tiles);
-    if (mode == kDedupWp && !split_flag)
-      hipLaunchKernelGGL((wordref_kernel<kDedupWp, true>), grid, dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan1, d_cls, D,
-                         wref, ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>(), (uint32_t)ablation_knob(2));
-    else if (mode == kDedupWp)
+    if (mode == kDedupWp)
       hipLaunchKernelGGL(wordref_kernel<kDedupWp>, grid, dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan1, d_cls, D, wref,
-                         ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>(), (uint32_t)ablation_knob(2));
-    else if (!split_flag)
-      hipLaunchKernelGGL((wordref_kernel<kDedupBpe, true>), grid, dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan1, d_cls, D,
-                         wref, ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>(), (uint32_t)ablation_knob(2));
+                         ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>());
     else
       hipLaunchKernelGGL(wordref_kernel<kDedupBpe>, grid, dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan1, d_cls, D, wref,
-                         ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>(), (uint32_t)ablation_knob(2));
+                         ws.sent_local.as<uint32_t>(), E.tile_words.as<uint32_t>());
   }
   prof_end(st, 3);
   launch_scan_u64(n_tiles, D.tile_new, new_local, new_blk, reinterpret_cast<uint64_t *>(d_misc), st);
@@ -1014,14 +927,6 @@ int dedup_front(DedupEngine &E, TileWorkspace &ws, const uint8_t *d_text, uint64
                        new_blk + 1 + nb_new, d_misc, E.uslot.as<uint32_t>(), E.uoff.as<uint64_t>(), E.utext.as<uint8_t>(), d_plan2,
                        n_tiles2, tile2_min);
   SWT_HIP(hipGetLastError());
-  if (D.diag & 1u) {
-    unsigned long long h[3] = {0, 0, 0};
-    SWT_HIP(hipMemcpyAsync(h, d_misc, 24, hipMemcpyDeviceToHost, st));
-    SWT_HIP(hipStreamSynchronize(st));
-    const unsigned int *c = reinterpret_cast<const unsigned int *>(h + 1);
-    fprintf(stderr, "[swt] dedup: %llu unique words, %llu bytes; CAS %u inserted, %u lost to another lane\n", h[0] >> 32,
-            h[0] & 0xFFFFFFFFull, c[1], c[2]);
-  }
   return SWT_OK;
 }
 

@@ -120,6 +120,19 @@ def test_class_table_matches_fixture(native, golden):
                     assert not native.class_of(cp) & bit, (name, hex(cp))
 
 
+def test_ascii_ranges_of_the_split_match_the_class_table(native):
+    """the dedup split (wordref_kernel) finds ASCII whitespace and punctuation by fixed byte ranges, not through the table"""
+    def ranges(*rs):
+        return {c for lo, hi in rs for c in range(lo, hi + 1)}
+    expect = {
+        native.CLS_PY_SPACE: ranges((0x09, 0x0D), (0x1C, 0x20)),
+        native.CLS_BERT_WS: ranges((0x09, 0x0D), (0x20, 0x20)),
+        native.CLS_BERT_PUNCT: ranges((0x21, 0x2F), (0x3A, 0x40), (0x5B, 0x60), (0x7B, 0x7E)),
+    }
+    for bit, cps in expect.items():
+        assert {c for c in range(128) if native.class_of(c) & bit} == cps, bit
+
+
 def test_preprocessing_matches_reference(swt, golden):
     base = swt.SubwordTokenizer()
     for case in golden("pretok_fuzz.json"):

@@ -1,4 +1,4 @@
-"""per-dispatch durations of the training kernels along a run, from a rocprofv3 kernel trace (tools/gpu_r02_trainprof.sh)"""
+"""per-dispatch durations of the training kernels along a run, from a rocprofv3 --kernel-trace run of a training call"""
 import csv, sys
 import numpy as np
 rows = list(csv.DictReader(open(sys.argv[1])))
