@@ -191,6 +191,22 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
                       uint64_t *d_n_tokens, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * NaiveWP encode over the same trie: replaces NaiveWP.tokenize (source/wordpiece.py:160-179) -- the pre-tokenizer split of
+ * SubwordTokenizer.preprocessing (source/utils.py:26-29) and, per word, the longest-prefix loop of NaiveWP.encode_word
+ * (source/wordpiece.py:132-159: "##" in front of every remainder, "[UNK]" = n_vocab+1 for the whole word when no prefix
+ * matches).  Arguments, ids and statuses as the swt_wp_encode trio; the only status besides SWT_WP_OK is
+ * SWT_WP_NONTERMINATING (a word of the sentence keeps the reference looping; the sentence gets no tokens).  out_cap >= n_bytes
+ * is always sufficient.  SWT_ERR_UNSUPPORTED for a vocabulary with a token of three or more leading '#' followed by
+ * another character: only there can a word yield more tokens than it has bytes. */
+int swt_wp_encode_naive(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                        uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens);
+int swt_wp_encode_naive_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                               uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host);
+int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                            uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status,
+                            uint64_t *d_n_tokens, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's
  * zipf_distribution (source/benchmarks.py:240-253), over ids -- a '##' token and the same token without the prefix are
  * different strings and different ids.  counts has 2 * id_cap entries: counts[id & 0x7FFFFFFF] for ids without SWT_BPE_CONT,

@@ -57,6 +57,10 @@ SIGNATURES = {
     "swt_wp_encode_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, u8p]),
     "swt_wp_encode_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_wp_encode_naive": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p]),
+    "swt_wp_encode_naive_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, u8p]),
+    "swt_wp_encode_naive_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -487,6 +491,34 @@ class WpTrie:
 
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
+
+    def encode_naive(self, text_u8, sent_off):
+        """NaiveWP.tokenize over lowercased packed text -> (ids, offsets, status)"""
+        n_sent = int(sent_off.size - 1)
+        n_bytes = int(sent_off[-1])
+        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
+        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
+        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
+        nt = C.c_uint64()
+        check(lib().swt_wp_encode_naive(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
+                                        ptr(out_off, u64p), ptr(status, u8p), C.byref(nt)))
+        return out[:nt.value], out_off, status[:n_sent]
+
+    def encode_naive_joined(self, joined, n_sent):
+        """join_texts' bytes in (not lowercased) -> (ids, offsets, status), or None when a sentence needs the host's str.lower()"""
+        out = np.empty(max(int(joined.size), 1), dtype=np.uint32)
+        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
+        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
+        need = np.zeros(max(n_sent, 1), dtype=np.uint8)
+        nt = C.c_uint64()
+        check(lib().swt_wp_encode_naive_joined(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
+                                               ptr(out_off, u64p), ptr(status, u8p), C.byref(nt), ptr(need, u8p)))
+        if nt.value == 0xFFFFFFFFFFFFFFFF:
+            return None
+        return out[:nt.value], out_off, status[:n_sent]
+
+    def encode_naive_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
+        check(lib().swt_wp_encode_naive_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
 
 
 class BpeTrainer:

@@ -428,6 +428,8 @@ struct HostTrie {
   uint32_t n_vocab = 0;
   std::vector<uint32_t> corner;
   bool corner_nonterm = false;
+  uint32_t sharp_depth = 0;   // length of the longest path of '#' edges from the root
+  bool naive_excess = false;  // a token "###..." + other chars: NaiveWP.encode_word can emit more tokens than its word has bytes
 
   uint32_t new_node(uint32_t c, int32_t par) {
     ch.push_back(c); is_end.push_back(0); tok.push_back(-1); link.push_back(-1); parent.push_back(par);
@@ -467,6 +469,9 @@ static int build_trie(HostTrie &H, const uint32_t *blob, const uint64_t *off, ui
       if (blob[i] >= kNumCodePoints) return fail(SWT_ERR_INVALID, "vocab entry %u holds an invalid code point", v);
     const uint32_t node = H.insert(blob + off[v], off[v + 1] - off[v]);
     if (H.tok[node] < 0) H.tok[node] = (int32_t)v;
+    uint64_t lead = 0;
+    while (off[v] + lead < off[v + 1] && blob[off[v] + lead] == '#') lead++;
+    if (lead >= 3 && off[v] + lead < off[v + 1]) H.naive_excess = true;
     if (H.ch.size() > kMaxNodes) return fail(SWT_ERR_UNSUPPORTED, "trie larger than %u nodes", kMaxNodes);
   }
   // utils.py:108-139: BFS from [root, root_sharp]
@@ -505,6 +510,7 @@ static int build_trie(HostTrie &H, const uint32_t *blob, const uint64_t *off, ui
       chain.push_back((uint32_t)c);
     }
     const uint64_t D = chain.size() - 1;
+    H.sharp_depth = (uint32_t)D;
     uint64_t L = 2, guard = 0;
     std::vector<uint8_t> visited(D + 8, 0);
     for (;;) {
@@ -545,6 +551,334 @@ __global__ __launch_bounds__(64) void wp_urec_kernel(const uint64_t *__restrict_
   }
 }
 
+// ---- NaiveWP encode: SubwordTokenizer.preprocessing (utils.py:15-29) + NaiveWP.encode_word (wordpiece.py:132-159) ----------
+//
+// The state of encode_word is the string "#" * L + word[p:] (L leading '#' that no character of the word stands for: the "##"
+// put in front of every remainder, wordpiece.py:155-156).  A step matches the longest prefix of that string that is a
+// vocabulary token (tok[] of the node, not is_end: root_sharp is marked whether "##" is a token or not).  A match that ends
+// inside the leading '#' leaves p where it is and sets L = L - m + 2.  At a fixed p at most sharp_depth + 1 values of L can
+// occur before the walk either leaves p or cannot come back (L beyond the '#' chain of the trie, where every match is the same
+// run of '#', grows or stays): so more than sharp_depth + 2 steps at one p mean the reference never returns.
+struct WpNaiveDev {
+  WpDev T;             // edges only
+  const int32_t *tok;  // node -> vocabulary id, -1 for none
+  uint32_t unk_id;     // "[UNK]"
+  uint32_t max_steps;  // sharp_depth + 2
+};
+
+// One word [wb, we) of txt: its ids to out[0..room), the count returned.  nonterm = true: the reference never returns (count 0).
+__device__ uint32_t naive_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpNaiveDev &N, uint32_t *out, uint32_t room,
+                               bool &nonterm) {
+  uint32_t nt = 0, L = 0, steps = 0;
+  uint64_t p = wb;
+  for (;;) {
+    uint32_t node = kWpRoot, best_sh = 0;
+    int32_t best = -1;
+    uint64_t best_end = p;
+    uint32_t k = 0;
+    for (; k < L; k++) {
+      const int32_t c = edge_lookup(N.T, node, '#');
+      if (c < 0) break;
+      node = (uint32_t)c;
+      const int32_t v = N.tok[node];
+      if (v >= 0) { best = v; best_sh = k + 1; }
+    }
+    if (k == L) {
+      for (uint64_t q = p; q < we;) {
+        const uint8_t b = txt[q];
+        int n = utf8_len(b);
+        if (q + n > we) n = (int)(we - q);
+        uint32_t cp = b;
+        if (b >= 0x80 && n > 1) {
+          cp = b & (0xFF >> (n + 1));
+          for (int i = 1; i < n; i++) cp = (cp << 6) | (txt[q + i] & 0x3F);
+        }
+        q += n;
+        while (q < we && utf8_is_cont(txt[q])) q++;
+        const int32_t c = edge_lookup(N.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = N.tok[node];
+        if (v >= 0) { best = v; best_sh = L; best_end = q; }
+      }
+    }
+    if (best < 0) {  // wordpiece.py:148-149: the whole word is one "[UNK]", the pieces stored so far are dropped
+      for (uint32_t k = 1; k < nt && k < room; k++) out[k] = kInvalidTok;
+      out[0] = N.unk_id;
+      return 1;
+    }
+    if (nt < room) out[nt] = (uint32_t)best;
+    nt++;
+    if (best_sh == L && best_end == we) return nt;  // nothing left
+    if (best_end > p) {
+      p = best_end;
+      L = 2;
+      steps = 0;
+    } else {
+      L = L - best_sh + 2;
+      if (++steps > N.max_steps) { nonterm = true; return 0; }
+    }
+  }
+}
+
+__device__ __forceinline__ uint8_t bert_class(const uint8_t *cls_tab, uint32_t cp) {
+  return cp < kNumCodePoints ? (uint8_t)(cls_tab[cp] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)) : (uint8_t)0;
+}
+
+// A whole sentence [b, e) by one lane (sentences longer than a chunk): split as SubwordTokenizer._split, each word's tokens
+// within that word's bytes of out.  Returns the count (0 when status != OK).
+__device__ uint32_t naive_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
+                                   const WpNaiveDev &N, int &status) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint32_t nt = 0;
+  status = SWT_WP_OK;
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    bool nonterm = false;
+    nt += naive_word(txt, p, q, N, out + nt, (uint32_t)(q - p), nonterm);
+    if (nonterm) { status = SWT_WP_NONTERMINATING; return 0; }
+    p = q;
+  }
+  return nt;
+}
+
+struct WpNaiveLds {
+  __attribute__((aligned(16))) uint8_t txt[kWpCap + 16];
+  uint32_t tok[kWpCap];                      // per byte position: a token id or kInvalidTok
+  uint16_t cand[kWpCap];                     // word starts, in position order
+  unsigned long long sbits[kWpBlocks + 1];   // sentence-start bit per byte
+  unsigned long long stop[kWpBlocks + 1];    // a word ends before this byte: white space, punctuation, a sentence start, outside
+  unsigned long long pbits[kWpBlocks + 1];   // a punctuation character (a word of its own) starts here
+  unsigned long long nonterm[kWpBlocks + 1]; // per sentence-start position: a word of the sentence never returns
+  unsigned long long vmask[kWpBlocks + 1];
+  uint32_t blkpre[kWpBlocks + 1];
+  __attribute__((aligned(16))) uint8_t cls_lo[kWpClsLds];
+  WpGiant giant;
+};
+
+// One 64-lane wavefront per tile, the skeleton of wp_encode_kernel (swt_tile.h).  Word boundaries do not depend on the
+// vocabulary here, so there is nothing to speculate about:
+//   B  64 bytes per step: BERT white-space / punctuation ballots -> word starts and word ends
+//   C  one lane per word runs the MaxMatch walk, writing its ids into the word's own bytes of tok[] (a terminating word of n
+//      bytes has at most n tokens: swt_wp_encode_naive_dev refuses the vocabularies for which that does not hold)
+//   D  a sentence with a word that never returns gets status SWT_WP_NONTERMINATING and no tokens
+//   E/F  ballot compaction to the tile's output run, per-sentence offsets
+__global__ __launch_bounds__(64) void wp_naive_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpNaiveDev N, uint32_t *__restrict__ scratch,
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+  __shared__ WpNaiveLds L;
+  const int lane = threadIdx.x;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const uint64_t t = blockIdx.x;
+  const uint64_t s_lo = direct.off ? 0 : plan[t], s_hi = direct.off ? direct.n_sent : plan[t + 1];
+  if (s_lo == s_hi) {
+    if (lane == 0) tile_tok[t] = 0;
+    return;
+  }
+  reinterpret_cast<uint4 *>(L.cls_lo)[lane] = reinterpret_cast<const uint4 *>(cls_tab)[lane];
+  const uint64_t span_base = sent_off[s_lo], span_end = sent_off[s_hi];
+  uint32_t *const tile_out = scratch + span_base;
+  uint32_t run = 0;
+  uint64_t s_next = s_lo;
+  uint64_t cb = span_base;
+
+  for (;;) {
+    const uint64_t abase = cb & ~15ull;
+    const uint32_t off0 = (uint32_t)(cb - abase);
+    const uint64_t avail = span_end - abase;
+    const bool last = avail <= (uint64_t)kWpCap;
+    const uint32_t staged = last ? (uint32_t)avail : (uint32_t)kWpCap;
+    const uint32_t nblk = (staged + 63) >> 6;
+
+    // ---- A. stage
+    for (uint32_t c = lane * 16; c < staged; c += 64 * 16) {
+      const uint64_t g = abase + c;
+      if (g + 16 <= n_bytes && ((reinterpret_cast<uintptr_t>(text + g) & 15) == 0)) {
+        *reinterpret_cast<uint4 *>(&L.txt[c]) = *reinterpret_cast<const uint4 *>(text + g);
+      } else {
+        for (int i = 0; i < 16; i++) L.txt[c + i] = (g + i < n_bytes) ? text[g + i] : (uint8_t)' ';
+      }
+    }
+    if (lane <= kWpBlocks) { L.sbits[lane] = 0ull; L.nonterm[lane] = 0ull; }
+    __syncthreads();
+    int cut = -1;
+    uint32_t n_in = 0;
+    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
+      const uint64_t o = sent_off[s];
+      if (o >= abase + staged) break;
+      atomicOr(&L.sbits[(o - abase) >> 6], 1ull << ((o - abase) & 63));
+      if (o > cb) cut = (int)(o - abase);
+      n_in++;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+      cut = max(cut, __shfl_xor(cut, d));
+      n_in += __shfl_xor(n_in, d);
+    }
+    __syncthreads();
+
+    uint32_t ce = staged;
+    if (!last) {
+      uint64_t s_after = s_next + n_in;
+      const bool whole = s_after < s_hi && sent_off[s_after] == abase + staged;
+      if (whole) ce = staged;
+      else if (cut >= 0) ce = (uint32_t)cut;
+      else {
+        // one sentence longer than the LDS chunk: one lane walks it in global memory
+        if (lane == 0) {
+          uint64_t s = s_next;
+          while (s + 1 < s_hi && sent_off[s + 1] <= cb) s++;
+          int stt;
+          const uint64_t e = sent_off[s + 1];
+          const uint32_t n = naive_sentence(text, cls_tab, cb, e, tile_out + run, N, stt);
+          for (uint64_t z = s_next; z <= s; z++) {
+            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
+            status[z] = SWT_WP_OK;
+          }
+          status[s] = (uint8_t)stt;
+          L.giant.end = e;
+          L.giant.ntok = n;
+          L.giant.nsent = (uint32_t)(s - s_next + 1);
+        }
+        __syncthreads();
+        s_next += L.giant.nsent;
+        run += L.giant.ntok;
+        cb = L.giant.end;
+        __syncthreads();
+        if (cb >= span_end) {
+          for (uint64_t z = s_next + lane; z < s_hi; z += 64) {
+            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
+            status[z] = SWT_WP_OK;
+          }
+          break;
+        }
+        continue;
+      }
+    }
+
+    // ---- B. classes -> word starts and ends
+    uint32_t nc = 0;
+    bool prev_stop = true;  // the char owning the byte before this block is white space or punctuation
+    for (uint32_t blk = 0; blk < nblk; blk++) {
+      const uint32_t p = blk * 64 + lane;
+      const bool inr = p >= off0 && p < ce;
+      const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
+      const bool lead = !utf8_is_cont(b);
+      uint32_t cp = b;
+      if (b >= 0xC0) {
+        int len = utf8_len(b);
+        if (p + len > ce) len = (int)(ce - p);
+        if (len > 1) {
+          cp = b & (0xFF >> (len + 1));
+          for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
+        }
+      }
+      uint8_t c = SWT_CLS_BERT_WS;  // bytes outside the chunk behave as white space
+      if (inr && lead) c = cp < (uint32_t)kWpClsLds ? (uint8_t)(L.cls_lo[cp] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)) : bert_class(cls_tab, cp);
+      const unsigned long long INR = __ballot(inr);
+      const unsigned long long LEAD = __ballot(lead);
+      const unsigned long long WSm = __ballot(lead && (c & SWT_CLS_BERT_WS));
+      const unsigned long long PUm = __ballot(lead && (c & SWT_CLS_BERT_PUNCT) && !(c & SWT_CLS_BERT_WS));
+      const unsigned long long CONT = ~LEAD;
+      unsigned long long STb = WSm | PUm | ((prev_stop && (CONT & 1ull)) ? 1ull : 0ull);
+      STb |= (STb << 1) & CONT; STb |= (STb << 1) & CONT; STb |= (STb << 1) & CONT;
+      const unsigned long long SS = L.sbits[blk] & INR;
+      const unsigned long long before = ((STb << 1) | (prev_stop ? 1ull : 0ull)) & ~SS;  // no context across a sentence start
+      const unsigned long long CAND = INR & LEAD & ~WSm & (SS | before | PUm);
+      if (lane == 0) { L.stop[blk] = WSm | PUm | SS | ~INR; L.pbits[blk] = PUm & INR; }
+      if ((CAND >> lane) & 1ull) L.cand[nc + __popcll(CAND & lt)] = (uint16_t)p;
+      nc += __popcll(CAND);
+      L.tok[p] = kInvalidTok;
+      prev_stop = (STb >> 63) & 1ull;
+    }
+    __syncthreads();
+
+    // ---- C. one lane per word
+    for (uint32_t k = lane; k < nc; k += 64) {
+      const uint32_t p0 = L.cand[k];
+      uint32_t we;
+      if (wbit(L.pbits, p0)) {
+        we = p0 + 1;
+        while (we < ce && utf8_is_cont(L.txt[we])) we++;
+      } else {
+        int w = (int)(p0 >> 6);
+        unsigned long long m = (p0 & 63) == 63 ? 0ull : (L.stop[w] & ~((2ull << (p0 & 63)) - 1ull));
+        while (!m && w + 1 < (int)nblk) m = L.stop[++w];
+        we = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ce;
+        if (we > ce) we = ce;
+      }
+      bool nt_word = false;
+      naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word);
+      if (nt_word) {
+        int w = (int)(p0 >> 6);
+        unsigned long long m = L.sbits[w] & ((2ull << (p0 & 63)) - 1ull);
+        while (!m && w > 0) m = L.sbits[--w];
+        const uint32_t s0 = m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : off0;
+        atomicOr(&L.nonterm[s0 >> 6], 1ull << (s0 & 63));
+      }
+    }
+    __syncthreads();
+
+    // ---- D. per sentence: status; a sentence that never returns keeps no tokens
+    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
+      const uint64_t o = sent_off[s];
+      const uint64_t rel = o - abase;
+      if (rel > ce || (rel == ce && !last)) break;
+      const uint64_t e = sent_off[s + 1] - abase;
+      int stt = SWT_WP_OK;
+      if (rel < e && wbit(L.nonterm, (uint32_t)rel)) {
+        stt = SWT_WP_NONTERMINATING;
+        for (uint64_t q = rel; q < e; q++) L.tok[q] = kInvalidTok;
+      }
+      status[s] = (uint8_t)stt;
+    }
+    __syncthreads();
+
+    // ---- E. compaction, F. sentence offsets
+    uint32_t total = 0;
+    for (uint32_t blk = 0; blk < nblk; blk++) {
+      const uint32_t p = blk * 64 + lane;
+      const uint32_t sv = (p >= off0 && p < ce) ? L.tok[p] : kInvalidTok;
+      const unsigned long long m = __ballot(sv != kInvalidTok);
+      if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
+      if (sv != kInvalidTok) tile_out[run + total + __popcll(m & lt)] = sv;
+      total += __popcll(m);
+    }
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
+      const uint64_t rel = sent_off[s] - abase;
+      if (rel > ce || (rel == ce && !last)) break;
+      uint32_t ex = total;
+      if (rel < ce && (rel >> 6) < nblk) ex = L.blkpre[rel >> 6] + __popcll(L.vmask[rel >> 6] & ((1ull << (rel & 63)) - 1ull));
+      if (direct.off) direct.off[s] = run + ex; else sent_local[s] = run + ex;
+      mine++;
+    }
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+    s_next += mine;
+    run += total;
+    if (last) break;
+    cb = abase + ce;
+    __syncthreads();
+  }
+  if (lane == 0) {
+    if (direct.off) { direct.off[s_hi] = run; *direct.n_tokens = run; }
+    else tile_tok[t] = run;
+  }
+}
+
 }  // namespace swt
 
 using namespace swt;
@@ -560,6 +894,7 @@ struct swt_wp_trie {
   uint64_t *d_edges = nullptr;
   WpNode *d_nodes = nullptr;
   uint32_t *d_pops = nullptr;
+  int32_t *d_tok = nullptr;  // node -> vocabulary id (NaiveWP encode), uploaded on its first call
   TileWorkspace ws;
   DevBuf in_text, in_off, out_ids, out_off, out_status, n_tok;
   // word-level dedup inside one call (swt_dedup.h): possible when no vocabulary token holds a str.isspace character
@@ -582,6 +917,14 @@ static int wp_upload(swt_wp_trie *t) {
   SWT_HIP(hipMalloc((void **)&t->d_pops, (t->h_pops.size() + 1) * 4));
   if (!t->h_pops.empty())
     SWT_HIP(hipMemcpy(t->d_pops, t->h_pops.data(), t->h_pops.size() * 4, hipMemcpyHostToDevice));
+  return SWT_OK;
+}
+
+static int wp_upload_naive(swt_wp_trie *t) {
+  int rc = wp_upload(t);
+  if (rc || t->d_tok) return rc;
+  SWT_HIP(hipMalloc((void **)&t->d_tok, t->H.tok.size() * 4));
+  SWT_HIP(hipMemcpy(t->d_tok, t->H.tok.data(), t->H.tok.size() * 4, hipMemcpyHostToDevice));
   return SWT_OK;
 }
 
@@ -647,6 +990,7 @@ void swt_wp_trie_destroy(swt_wp_trie *t) try {
   if (t->d_edges) (void)hipFree(t->d_edges);
   if (t->d_nodes) (void)hipFree(t->d_nodes);
   if (t->d_pops) (void)hipFree(t->d_pops);
+  if (t->d_tok) (void)hipFree(t->d_tok);
   t->ws.release();
   t->ws2.release();
   t->dd.release();
@@ -775,16 +1119,69 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
   return SWT_OK;
 } SWT_API_CATCH
 
+int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                            uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
+  if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_sent && !d_status) || (n_bytes && (!d_text || !d_out_ids)))
+    return fail(SWT_ERR_INVALID, "null argument");
+  if (t->H.naive_excess)
+    return fail(SWT_ERR_UNSUPPORTED, "a vocabulary token starts with three or more '#' and goes on: NaiveWP.encode_word could emit "
+                                     "more tokens than its word has bytes");
+  int rc = wp_upload_naive(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t *d_cls = nullptr;
+  if ((rc = device_class_table(&d_cls))) return rc;
+  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
+  if (n_tiles > 0x7FFFFFFFull)
+    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
+  if ((rc = t->ws.reserve(n_bytes, n_sent, n_tiles))) return rc;
+  if (n_sent == 0) {
+    SWT_HIP(hipMemsetAsync(d_out_off, 0, 8, st));
+    SWT_HIP(hipMemsetAsync(d_n_tokens, 0, 8, st));
+    return SWT_OK;
+  }
+  WpNaiveDev N;
+  N.T = WpDev{};
+  N.T.edges = t->d_edges;
+  N.T.edge_bits = t->edge_bits;
+  N.tok = t->d_tok;
+  N.unk_id = t->H.n_vocab + 1;
+  N.max_steps = t->H.sharp_depth + 2;
+  if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents) {
+    // one workgroup, one launch, the caller's arrays written by the kernel (DirectOut, swt_tile.h)
+    hipLaunchKernelGGL(wp_naive_kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, N,
+                       d_out_ids, t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status,
+                       DirectOut{d_out_off, d_n_tokens, n_sent});
+    SWT_HIP(hipGetLastError());
+    return SWT_OK;
+  }
+  prof_begin(st, 2);
+  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
+  prof_begin(st);
+  hipLaunchKernelGGL(wp_naive_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                     t->ws.plan.as<uint64_t>(), d_cls, N, t->ws.scratch.as<uint32_t>(), t->ws.sent_local.as<uint32_t>(),
+                     t->ws.tile_tok.as<uint32_t>(), d_status, DirectOut{nullptr, nullptr, 0});
+  prof_end(st);
+  launch_scan_gather(d_sent_off, n_sent, n_tiles, t->ws, d_out_ids, d_out_off, d_n_tokens, st);
+  prof_end(st, 2);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+} SWT_API_CATCH
+
+// the device-buffer form the host entry points below go through (swt_wp_encode_dev or swt_wp_encode_naive_dev)
+typedef int (*WpEncodeDev)(swt_wp_trie *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint8_t *,
+                           uint64_t *, void *);
+
 // text and offsets on the device -> ids, offsets, statuses and the count in the caller's host arrays
-static int wp_encode_to_host(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent,
+static int wp_encode_to_host(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent,
                              uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
   int rc;
   if ((rc = t->out_ids.reserve((n_bytes + 64) * 4))) return rc;
   if ((rc = t->out_off.reserve((n_sent + 1) * 8))) return rc;
   if ((rc = t->out_status.reserve(n_sent + 8))) return rc;
   if ((rc = t->n_tok.reserve(8))) return rc;
-  rc = swt_wp_encode_dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->out_status.as<uint8_t>(),
-                         t->n_tok.as<uint64_t>(), nullptr);
+  rc = dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->out_status.as<uint8_t>(),
+           t->n_tok.as<uint64_t>(), nullptr);
   if (rc) return rc;
   uint64_t nt = 0;
   SWT_HIP(hipMemcpy(&nt, t->n_tok.p, 8, hipMemcpyDeviceToHost));
@@ -797,8 +1194,8 @@ static int wp_encode_to_host(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_b
   return SWT_OK;
 }
 
-int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
-                  uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
+static int wp_encode_host(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                          uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
   if (!t || !sent_off || !out_off || !n_tokens || (n_sent && !status)) return fail(SWT_ERR_INVALID, "null argument");
   int rc = wp_upload(t);
   if (rc) return rc;
@@ -819,9 +1216,9 @@ int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off,
     if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
     memset(h + off_bytes + n_bytes, ' ', 64);
     uint8_t *o = h + out_at;
-    rc = swt_wp_encode_dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent,
-                           reinterpret_cast<uint32_t *>(o + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(o + 16), o + 16 + off_bytes,
-                           reinterpret_cast<uint64_t *>(o), nullptr);
+    rc = dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent,
+             reinterpret_cast<uint32_t *>(o + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(o + 16), o + 16 + off_bytes,
+             reinterpret_cast<uint64_t *>(o), nullptr);
     if (rc) return rc;
     SWT_HIP(hipStreamSynchronize(0));
     const uint64_t nt = *reinterpret_cast<const volatile uint64_t *>(o);
@@ -846,9 +1243,9 @@ int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off,
     if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
     SWT_HIP(hipMemcpyAsync(t->small_in.p, h, off_bytes + n_bytes, hipMemcpyHostToDevice, 0));
     uint8_t *d_in = t->small_in.as<uint8_t>(), *d_out = t->small_out.as<uint8_t>();
-    rc = swt_wp_encode_dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
-                           reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
-                           d_out + 16 + off_bytes, reinterpret_cast<uint64_t *>(d_out), nullptr);
+    rc = dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
+             reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
+             d_out + 16 + off_bytes, reinterpret_cast<uint64_t *>(d_out), nullptr);
     if (rc) return rc;
     SWT_HIP(hipMemcpyAsync(h, d_out, 16 + off_bytes + st_bytes + (n_bytes + 64) * 4, hipMemcpyDeviceToHost, 0));
     SWT_HIP(hipStreamSynchronize(0));
@@ -865,25 +1262,46 @@ int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off,
   if ((rc = t->in_off.reserve((n_sent + 1) * 8))) return rc;
   if (n_bytes) SWT_HIP(hipMemcpyAsync(t->in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
   SWT_HIP(hipMemcpyAsync(t->in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  return wp_encode_to_host(t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, status, n_tokens);
+  return wp_encode_to_host(dev, t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, status,
+                           n_tokens);
+}
+
+int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                  uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
+  return wp_encode_host(swt_wp_encode_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
 } SWT_API_CATCH
+
+int swt_wp_encode_naive(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                        uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
+  return wp_encode_host(swt_wp_encode_naive_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+} SWT_API_CATCH
+
+static int wp_encode_joined(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                            uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) {
+  if (!t || !out_off || !n_tokens || (n_sent && (!need_host || !status)) || (n_joined && !joined)) return fail(SWT_ERR_INVALID, "null argument");
+  int rc = wp_upload(t);
+  if (rc) return rc;
+  *n_tokens = UINT64_MAX;
+  struct Ctx { WpEncodeDev dev; swt_wp_trie *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off; uint8_t *status; uint64_t *n_tokens; };
+  Ctx c{dev, t, n_sent, out_ids, out_cap, out_off, status, n_tokens};
+  bool consumed = false;
+  return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
+      [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
+        Ctx *c = static_cast<Ctx *>(p);
+        return wp_encode_to_host(c->dev, c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->status, c->n_tokens);
+      }, &c);
+}
 
 // list[str] joined with U+0000 -> ids, the prepared text staying on the device (see swt_bpe_encode_joined).
 // *n_tokens = UINT64_MAX on return: a sentence needs the host's str.lower() and nothing was encoded.
 int swt_wp_encode_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
                          uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) try {
-  if (!t || !out_off || !n_tokens || (n_sent && (!need_host || !status)) || (n_joined && !joined)) return fail(SWT_ERR_INVALID, "null argument");
-  int rc = wp_upload(t);
-  if (rc) return rc;
-  *n_tokens = UINT64_MAX;
-  struct Ctx { swt_wp_trie *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off; uint8_t *status; uint64_t *n_tokens; };
-  Ctx c{t, n_sent, out_ids, out_cap, out_off, status, n_tokens};
-  bool consumed = false;
-  return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
-      [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
-        Ctx *c = static_cast<Ctx *>(p);
-        return wp_encode_to_host(c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->status, c->n_tokens);
-      }, &c);
+  return wp_encode_joined(swt_wp_encode_dev, t, joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
+} SWT_API_CATCH
+
+int swt_wp_encode_naive_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                               uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) try {
+  return wp_encode_joined(swt_wp_encode_naive_dev, t, joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
 } SWT_API_CATCH
 
 }  // extern "C"

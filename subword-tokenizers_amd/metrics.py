@@ -161,13 +161,20 @@ def _encode_packed(tokenizer, text_u8, off):
         if ids.size and int(ids.max()) > n_vocab + 1:
             raise NotImplementedError("a multi-token NaiveWP.encode_word('##') corner (wordpiece.py:260-261) is not counted on the device")
         return ids, ooff, n_vocab + 3
+    if hasattr(tokenizer, "_naive_trie") and not hasattr(tokenizer, "_trie"):  # NaiveWP
+        ids, ooff, status = tokenizer._ensure_naive_trie().encode_naive(text_u8, off)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            i = int(bad[0])
+            tokenizer._raise_naive_status(int(status[i]), text_u8[int(off[i]):int(off[i + 1])].tobytes().decode("utf-8", "replace"))
+        return ids, ooff, len(tokenizer._naive_tokens) + 2
     table = tokenizer._ensure_table()  # FastBPE
     ids, ooff = table.encode(text_u8, off)
     return ids, ooff, N.SYM_BASE + len(tokenizer._syms.strings) + 1
 
 
 def quality_metrics(tokenizer, test_corpus: List[str]) -> Dict[str, Any]:
-    """Every tokenization metric of benchmarks() (benchmarks.py:331-346 and 354-357) for a FastBPE / FastWP of this package:
+    """Every tokenization metric of benchmarks() (benchmarks.py:331-346 and 354-357) for a FastBPE / NaiveWP / FastWP of this package:
     two batched encodes and one device histogram instead of a Python call per sentence and per unique word."""
     if not isinstance(test_corpus, list) or not all(isinstance(s, str) for s in test_corpus):
         raise TypeError("Text must be a string.")

@@ -6,7 +6,7 @@ Same names, constructor, methods, attributes and error behaviour as phtryll/subw
     SubwordTokenizer   utils.py:5-41      preprocessing(), vocab_length()
     NaiveBPE           bpe.py:9-189       train() on the device; encode_word()/tokenize() stay the slow didactic loop
     FastBPE            bpe.py:192-263     train() + tokenize()/encode_word() on the device
-    NaiveWP            wordpiece.py:8-208 CPU Python (out of the GPU scope: SURVEY.md section 2, row 10)
+    NaiveWP            wordpiece.py:8-208 train() on the device; tokenize() stays the Python loop, the batch calls run it on the device
     FastWP             wordpiece.py:211-330  trie build in C++, tokenize() on the device
 
 plus batch entry points the reference lacks (`tokenize_batch`, `encode_ids_batch`), because one sentence per
@@ -419,7 +419,8 @@ class _WpSymbols:
 class NaiveWP(SubwordTokenizer):
     """WordPiece by the likelihood score (wordpiece.py:8-208).  `train` runs on the device: the
     BPE trainer's stream, histogram and merge-apply with exact symbol frequencies and the score as the argmax key;
-    `encode_word`/`tokenize` keep the reference's longest-prefix loop in Python (FastWP is the device encoder)."""
+    `encode_word`/`tokenize` keep the reference's longest-prefix loop in Python; `encode_ids_batch`/`tokenize_batch` run the
+    same loop on the device over the vocabulary's trie (swt_wp_encode_naive)."""
 
     def __init__(self, tokenizer=None):
         super().__init__(tokenizer)
@@ -427,6 +428,9 @@ class NaiveWP(SubwordTokenizer):
         self._trainer: Optional[N.BpeTrainer] = None
         self._train_syms: Optional[_WpSymbols] = None
         self._corpus_cache = None
+        self._naive_trie: Optional[N.WpTrie] = None  # built from sorted(vocab) on the first batch call
+        self._naive_tokens: List[str] = []
+        self._naive_vocab: Optional[frozenset] = None  # the vocabulary the handle was built from
 
     # -- wordpiece.py:29-103: the merge loop, on the device
     def train(self, corpus, max_vocab: int = 30_000):
@@ -533,9 +537,53 @@ class NaiveWP(SubwordTokenizer):
             out.extend(self.encode_word(w))
         return out
 
+    # -- batch entry points (not in the reference)
+    def _drop_naive_trie(self) -> None:
+        if self._naive_trie is not None:
+            self._naive_trie.close()
+        self._naive_trie, self._naive_tokens, self._naive_vocab = None, [], None
+
+    def _ensure_naive_trie(self) -> N.WpTrie:
+        # ids = position in the sorted vocabulary, as FastWP's; rebuilt when `vocab` was changed in place since the last build
+        if self._naive_trie is None or self.vocab != self._naive_vocab:
+            self._drop_naive_trie()
+            self._naive_vocab = frozenset(self.vocab)
+            self._naive_tokens = sorted(self._naive_vocab)
+            self._naive_trie = N.WpTrie(self._naive_tokens)
+        return self._naive_trie
+
+    def encode_ids_batch(self, texts: List[str]):
+        """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]): tokenize() of every text on the device.  ids index
+        sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns."""
+        if not isinstance(texts, list) or (len(texts) <= 64 and not all(isinstance(t, str) for t in texts)):
+            raise TypeError("Text to tokenize must be a string.")
+        trie = self._ensure_naive_trie()
+        if len(texts) > 64:
+            joined, n_nul = N.join_texts(texts, "Text to tokenize must be a string.")
+            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
+                got = trie.encode_naive_joined(joined, len(texts))
+                if got is not None:
+                    return got
+        text, off = N.pack_and_lower(texts)  # utils.py:27 lower(), on the device
+        return trie.encode_naive(text, off)
+
+    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
+        """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
+        deviation: the reference hangs)."""
+        ids, off, status = self.encode_ids_batch(texts)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            self._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
+        return N.nested_lists(self._naive_tokens + ["['UNK']", "[UNK]"], ids, off)
+
+    @staticmethod
+    def _raise_naive_status(st: int, text: str) -> None:
+        raise RuntimeError("NaiveWP.tokenize: the reference does not terminate on this input (status %d): %r" % (st, text[:80]))
+
     # -- wordpiece.py:183-208
     def reset(self) -> None:
         self.vocab.clear()
+        self._drop_naive_trie()
         if self._trainer is not None:
             self._trainer.close()
         self._trainer, self._train_syms, self._corpus_cache = None, None, None
@@ -550,6 +598,7 @@ class NaiveWP(SubwordTokenizer):
         if os.path.isfile(vocab_file):
             with open(vocab_file, "r", encoding="utf-8") as f:
                 self.vocab = set(json.load(f))
+            self._drop_naive_trie()
 
 
 class TrieNodeView:
