@@ -175,6 +175,9 @@ struct LaneLds {
   unsigned long long vmask[Blocks + 1];    // phase E: live-token bit per symbol
   uint32_t sympre[Blocks + 1];             // symbols before each 64-byte block
   uint32_t blkpre[Blocks + 1];             // tokens before each block of 64 symbols
+};
+// what outlives a chunk: kept out of LaneLds so that a chunk's arrays stay one block
+struct LaneShared {
   uint32_t cls2[64];                       // classes of U+0000..U+03FF, two bits each
   GiantResult giant;
 };
@@ -238,8 +241,7 @@ __device__ void slow_word(uint32_t *S, uint32_t *V, const uint32_t n0, const Bpe
 }
 
 // classes of the first 1,024 code points: 16 per lane, two bits each (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)
-template <int Cap>
-__device__ __forceinline__ void lane_classes(LaneLds<Cap> &L, const uint8_t *__restrict__ cls_tab, int lane) {
+__device__ __forceinline__ void lane_classes(LaneShared &L, const uint8_t *__restrict__ cls_tab, int lane) {
   uint32_t w = 0;
   if (cls_tab) {
     const uint4 v = reinterpret_cast<const uint4 *>(cls_tab)[lane];
@@ -256,7 +258,7 @@ __device__ __forceinline__ void lane_classes(LaneLds<Cap> &L, const uint8_t *__r
 // ---- A + B/C of one chunk: stage the bytes, then 64 bytes per step: classes, word structure from ballot masks, the dense
 // symbols, the list of word starts, and the table value of every adjacent pair of a word.
 template <int Cap>
-__device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint8_t *__restrict__ text, uint64_t n_bytes,
+__device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2, const uint8_t *__restrict__ text, uint64_t n_bytes,
                                            const uint64_t *__restrict__ sent_off, const uint8_t *__restrict__ cls_tab,
                                            const BpeSlot *__restrict__ slots, uint32_t sh, const LaneTile &T, LaneChunk &C, int lane) {
   constexpr int Blocks = Cap / 64;
@@ -309,7 +311,7 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint8_t *__res
     }
     uint32_t c = kClsWs;  // bytes outside the chunk behave as whitespace
     if (inr && lead)
-      c = cp < 1024u ? ((L.cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u) : ((cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u);
+      c = cp < 1024u ? ((cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u) : ((cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u);
     const unsigned long long INR = __ballot(inr);
     const unsigned long long LEAD = __ballot(lead);
     const unsigned long long WSm = __ballot(lead && (c & kClsWs));
@@ -376,9 +378,9 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint8_t *__res
 }
 
 // ---- the end of a chunk that does not end the tile: one word longer than the staged bytes goes to the one-lane walker (and the
-// chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list either way.
+// chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list and moves T.cb past the chunk.
 template <int Cap, int Mode>
-__device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
+__device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
                                                const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
                                                LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
                                                const uint32_t *__restrict__ uslot, unsigned long long *__restrict__ rec,
@@ -391,10 +393,10 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, const uint8_t *_
         uint64_t s = T.s_next;
         while (s < T.s_hi && sent_off[s] <= T.cb) s++;
         const uint64_t send = sent_off[s];  // s <= s_hi and sent_off[s_hi] = span_end > cb
-        L.giant = giant_word(text, T.cb, send, cls_tab, slots, sh, T.tile_out + T.run);
+        giant = giant_word(text, T.cb, send, cls_tab, slots, sh, T.tile_out + T.run);
       }
       wave_sync();
-      const GiantResult g = L.giant;
+      const GiantResult g = giant;
       uint32_t mine = 0;
       for (uint64_t s = T.s_next + lane; s < T.s_hi; s += 64) {
         if (sent_off[s] >= g.end) break;
@@ -426,10 +428,11 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, const uint8_t *_
     C.nw = keep;
   }
   if (lane == 0) L.wl[C.nw] = (uint16_t)C.nsym;
+  T.cb = C.abase + C.ce;
   wave_sync();
 }
 
-// ---- W. the words with two symbols or more by length class: how many, then their entries (tag | index in wl[]) into a list
+// ---- W. the words with two symbols or more by length class: how many, then their entries (the word's index in wl[]) into a list
 // that holds all 9+ words first, then the 5-8, then the 2-4 (o2 / o1 / o0 = where this wave's share of each class begins)
 template <int Cap>
 __device__ __forceinline__ void lane_words_count(const LaneLds<Cap> &L, uint32_t nw, int lane, uint32_t &c2, uint32_t &c1, uint32_t &c0) {
@@ -444,15 +447,15 @@ __device__ __forceinline__ void lane_words_count(const LaneLds<Cap> &L, uint32_t
 }
 template <int Cap>
 __device__ __forceinline__ void lane_words_write(const LaneLds<Cap> &L, uint32_t nw, int lane, uint16_t *list, uint32_t o2, uint32_t o1,
-                                                 uint32_t o0, uint32_t tag) {
+                                                 uint32_t o0) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   for (uint32_t k0 = 0; k0 < nw; k0 += 64) {
     const uint32_t k = k0 + lane;
     const uint32_t n = k < nw ? (uint32_t)L.wl[k + 1] - (uint32_t)L.wl[k] : 0u;
     const unsigned long long M0 = __ballot(n >= 2 && n <= 4), M1 = __ballot(n >= 5 && n <= 8), M2 = __ballot(n >= 9);
-    if (n >= 9) list[o2 + (uint32_t)__popcll(M2 & lt)] = (uint16_t)(tag | k);
-    else if (n >= 5) list[o1 + (uint32_t)__popcll(M1 & lt)] = (uint16_t)(tag | k);
-    else if (n >= 2) list[o0 + (uint32_t)__popcll(M0 & lt)] = (uint16_t)(tag | k);
+    if (n >= 9) list[o2 + (uint32_t)__popcll(M2 & lt)] = (uint16_t)k;
+    else if (n >= 5) list[o1 + (uint32_t)__popcll(M1 & lt)] = (uint16_t)k;
+    else if (n >= 2) list[o0 + (uint32_t)__popcll(M0 & lt)] = (uint16_t)k;
     o0 += (uint32_t)__popcll(M0);
     o1 += (uint32_t)__popcll(M1);
     o2 += (uint32_t)__popcll(M2);
@@ -461,7 +464,7 @@ __device__ __forceinline__ void lane_words_write(const LaneLds<Cap> &L, uint32_t
 
 // ---- D. merge rounds (bpe.py:210-238) over a list of words, one lane per word.  A lane whose word is finished takes the next
 // one of the list, so the wave goes through about as many rounds as its longest word needs -- the short words fill the lanes
-// beside it.  An entry is tile:4 | index:12 into that tile's wl[] (LL = the tiles of the workgroup).
+// beside it.  An entry of the list is an index into wl[].
 //
 // The minimum of a round is found as a KEY = rank | slot (packed values: rank:16 | merged:16 -> rank:16 | 0:11 | slot:5; wide
 // values: rank << 5 | slot), so one min per slot yields the leftmost smallest rank and its place; a dead slot's value is all
@@ -484,16 +487,21 @@ __device__ __forceinline__ uint32_t scan_key(const uint32_t *V, uint32_t n) {
   }
   return key;
 }
+// A lane's word as the rounds hand it to their tail.
+struct LaneWord {
+  uint32_t n, alive;  // symbols (0: the lane holds no word), live slots (bit i: slot i still holds a symbol)
+  uint32_t where;     // first symbol of the word in sym[] / val[]
+};
+
 // ---- the tail of the rounds.  Two thirds of a tile's rounds run with a handful of words left -- the longest ones, which started
 // first -- and a round costs the wave the same whether 60 lanes take part or 5 (S85k-open, simulated from the oracle: 13.8 rounds per
 // tile, 8.8 of them with <= 16 words, 6.9 with <= 8).  So the last 64 / TL words get TL lanes each: lane j of a word scans its share
 // of the slots, a shuffle finds the word's minimum, every lane of the group follows the merge (same values, LDS broadcasts), lane 0
-// writes it and looks the left pair up while lane 1 looks up the right.  LEAD = the lanes that hold a word's state on entry; the
-// function returns when at most `stop` words are left, their state in the first lane of each group (and in all of its lanes).
-template <bool Packed, uint32_t TL>
-__device__ __forceinline__ void lane_tail(uint32_t *sym0, uint32_t *val0, uint32_t *&S, uint32_t *&V, uint32_t &n, uint32_t &alive,
-                                          unsigned long long LEAD, uint32_t stop, int lane, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                          const uint32_t *__restrict__ merged_of_rank) {
+// writes it and looks the left pair up while lane 1 looks up the right.  LEAD = the lanes that hold a word's state on entry (at
+// most 64 / TL of them); the function returns when every word is finished.
+template <bool Packed, uint32_t TL, int Cap>
+__device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, unsigned long long LEAD, int lane, const BpeSlot *__restrict__ slots,
+                                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
   constexpr uint32_t kNoKey = Packed ? 0xFFFF0000u : 0xFFFFFFE0u;
   // group g of TL lanes takes over the g-th word
   const uint32_t g = (uint32_t)lane / TL, j = (uint32_t)lane % TL;
@@ -501,15 +509,11 @@ __device__ __forceinline__ void lane_tail(uint32_t *sym0, uint32_t *val0, uint32
   for (uint32_t i = 0; i < g; i++) mrest &= mrest - 1ull;
   const bool have = mrest != 0ull;
   const int src = have ? __builtin_ctzll(mrest) : 0;
-  const uint32_t sidx = (uint32_t)(S - sym0), vidx = (uint32_t)(V - val0);
-  const uint32_t t_s = __shfl(sidx, src), t_v = __shfl(vidx, src), t_n = __shfl(n, src), t_alive = __shfl(alive, src);
-  S = sym0 + t_s;
-  V = val0 + t_v;
-  n = have ? t_n : 0u;
-  alive = t_alive;
+  const uint32_t t_w = __shfl(W.where, src), t_n = __shfl(W.n, src), t_alive = __shfl(W.alive, src);
+  uint32_t *const S = L.sym + t_w, *const V = L.val + t_w;
+  uint32_t n = have ? t_n : 0u, alive = t_alive;
   for (;;) {
-    const unsigned long long BUSY = __ballot(n != 0u);
-    if ((uint32_t)__popcll(BUSY) <= stop * TL) break;
+    if (__ballot(n != 0u) == 0ull) break;
     if (n != 0u) {
       const uint32_t nm1 = n - 1u;
       uint32_t k = 0xFFFFFFFFu;
@@ -554,27 +558,27 @@ __device__ __forceinline__ void lane_tail(uint32_t *sym0, uint32_t *val0, uint32
   }
 }
 
+// The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
 template <bool Packed, bool Proper, int Cap>
-__device__ __forceinline__ void lane_rounds(LaneLds<Cap> *LL, const uint16_t *list, uint32_t n_list, int lane,
-                                            const BpeSlot *__restrict__ slots, uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
+__device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t *list, uint32_t n_list, int lane,
+                                                const BpeSlot *__restrict__ slots, uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
   constexpr uint32_t kNoKey = Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
   const unsigned long long lt = (1ull << lane) - 1ull;
-  uint32_t next = 0;          // first word of the list no lane has taken (the same in every lane)
-  uint32_t n = 0, alive = 0;  // this lane's word: symbols (0: none), live slots
-  uint32_t key = 0xFFFFFFFFu; // its smallest rank | the slot that holds it
-  uint32_t *S = LL[0].sym, *V = LL[0].val;
+  uint32_t next = 0;  // first word of the list no lane has taken (the same in every lane)
+  uint32_t n = 0, alive = 0, where = 0;  // this lane's word: symbols (0: none), live slots, first slot
+  uint32_t key = 0xFFFFFFFFu;            // its smallest rank | the slot that holds it
+  uint32_t *S = L.sym, *V = L.val;
   for (;;) {
     const unsigned long long IDLE = __ballot(n == 0u);
     if (IDLE && next < n_list) {
       const uint32_t k = next + (uint32_t)__popcll(IDLE & lt);
       if (n == 0u && k < n_list) {
         const uint32_t e = list[k];
-        LaneLds<Cap> &L = LL[e >> 12];
-        const uint32_t base = L.wl[e & 0xFFFu];
-        n = (uint32_t)L.wl[(e & 0xFFFu) + 1] - base;
-        S = &L.sym[base];
-        V = &L.val[base];
-        alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;  // bit i: slot i still holds a symbol
+        where = L.wl[e];
+        n = (uint32_t)L.wl[e + 1] - where;
+        S = &L.sym[where];
+        V = &L.val[where];
+        alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
         if (!Proper || n > 32u) {
           slow_word<Packed>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
@@ -585,11 +589,8 @@ __device__ __forceinline__ void lane_rounds(LaneLds<Cap> *LL, const uint16_t *li
       next += (uint32_t)__popcll(IDLE);
     }
     const unsigned long long BUSY = __ballot(n != 0u);
-    if (BUSY == 0ull) {
-      if (next >= n_list) break;
-      continue;
-    }
-    if (next >= n_list && __popcll(BUSY) <= 16) break;  // the last few (long) words: several lanes each, below
+    if (next >= n_list && __popcll(BUSY) <= 16) break;  // the last few (long) words: several lanes each, lane_tail
+    if (BUSY == 0ull) continue;  // every word just taken went through slow_word: take the next ones
     if (n != 0u) {
       // slot im merges with the next live slot r; pl / rr = the live slots either side of the pair
       const uint32_t im = key & 31u;
@@ -616,16 +617,12 @@ __device__ __forceinline__ void lane_rounds(LaneLds<Cap> *LL, const uint16_t *li
       }
     }
   }
-  // ---- the tail (lane_tail above): four lanes a word once 16 words are left
-  {
-    const unsigned long long BUSY = __ballot(n != 0u);
-    if (BUSY != 0ull) lane_tail<Packed, 4>(LL[0].sym, LL[0].val, S, V, n, alive, BUSY, 0u, lane, slots, sh, merged_of_rank);
-  }
+  return LaneWord{n, alive, where};
 }
 
 // ---- E + F of one chunk: order-preserving compaction of the live symbols into the tile's output run, then the tile-local
 // token offset of every sentence starting in [cb, ce) (and == ce on the last chunk): byte -> symbol through the split's
-// masks, symbol -> token through phase E's.  Advances the tile.
+// masks, symbol -> token through phase E's.  Advances the tile's sentences and its run.
 template <int Cap, int Mode>
 __device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__restrict__ sent_off, LaneTile &T, const LaneChunk &C, int lane,
                                           uint32_t *__restrict__ sent_local, const uint32_t *__restrict__ uslot,
@@ -665,7 +662,6 @@ __device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__res
   for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
   T.s_next += mine;
   T.run += total;
-  T.cb = C.abase + C.ce;
   wave_sync();
 }
 
@@ -678,8 +674,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, const uint32_t *__restrict__ uslot,
     unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec, DirectOut direct) {
   constexpr bool kDirect = Mode == 2;
-  static_assert(Cap % 64 == 0 && Cap <= 4032, "an entry of the word list is tile:4 | word:12, and wl[] holds 16-bit symbol indices");
+  static_assert(Cap % 64 == 0 && Cap <= 4032, "12 B of LDS per staged byte; wl[] and the word list hold 16-bit indices");
   __shared__ LaneLds<Cap> L;
+  __shared__ LaneShared SH;
   const int lane = threadIdx.x;
   const uint64_t t = blockIdx.x;
   LaneTile T;
@@ -689,7 +686,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     if (Mode == 0 && lane == 0) tile_tok[t] = 0;
     return;
   }
-  lane_classes(L, cls_tab, lane);
+  lane_classes(SH, cls_tab, lane);
   T.span_base = sent_off[T.s_lo];
   T.span_end = sent_off[T.s_hi];
   T.tile_out = scratch + T.span_base;
@@ -699,14 +696,17 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   uint16_t *const list = reinterpret_cast<uint16_t *>(L.txt);  // the staged bytes are not read again once the split is done
   for (;;) {
     LaneChunk C;
-    lane_split(L, text, n_bytes, sent_off, cls_tab, slots, sh, T, C, lane);
-    lane_chunk_end<Cap, Mode>(L, text, sent_off, cls_tab, slots, sh, T, C, lane, sent_local, uslot, rec, drec, direct);
+    lane_split(L, SH.cls2, text, n_bytes, sent_off, cls_tab, slots, sh, T, C, lane);
+    lane_chunk_end<Cap, Mode>(L, SH.giant, text, sent_off, cls_tab, slots, sh, T, C, lane, sent_local, uslot, rec, drec, direct);
     if (C.giant) continue;
     uint32_t c2, c1, c0;
     lane_words_count(L, C.nw, lane, c2, c1, c0);
-    lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1, 0u);
+    lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1);
     wave_sync();
-    lane_rounds<Packed, Proper, Cap>(&L, list, c2 + c1 + c0, lane, slots, sh, merged_of_rank);
+    // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
+    const LaneWord W = lane_rounds<Packed, Proper, Cap>(L, list, c2 + c1 + c0, lane, slots, sh, merged_of_rank);
+    const unsigned long long BUSY = __ballot(W.n != 0u);
+    if (BUSY != 0ull) lane_tail<Packed, 4, Cap>(L, W, BUSY, lane, slots, sh, merged_of_rank);
     wave_sync();
     lane_emit<Cap, Mode>(L, sent_off, T, C, lane, sent_local, uslot, rec, drec, direct);
     if (C.last) break;
