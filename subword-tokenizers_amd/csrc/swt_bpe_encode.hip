@@ -42,6 +42,8 @@ constexpr uint32_t kNoRank = 0xFFFFFFFFu;
 #endif
 constexpr int kLaneTile = SWT_LANE_TILE;  // the word-lane kernel (bpe_lane_kernel): bytes of sentence starts per tile ...
 constexpr int kLaneCap = SWT_LANE_CAP;    // ... and staged bytes per chunk (a batch of 64 word lanes wants ~350 bytes of text)
+// A wave of the running-text form takes a SPAN of K consecutive tiles (lane_span below) as one long tile, chunk by chunk.
+constexpr uint32_t kLaneMaxSpan = 16;
 constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one workgroup and one launch do the whole call
 
 // The rank table is a two-choice cuckoo table (built once on the host, swt_bpe_table_create): a pair lives in slot h1 or in
@@ -665,6 +667,12 @@ __device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__res
   wave_sync();
 }
 
+#ifdef SWT_STAMPS
+// diagnostic builds only: wall_clock64() at the begin and the end of Mode 0 wave t, [2t] and [2t + 1] (zero: the wave had no work)
+constexpr uint32_t kLaneStamps = 32768;
+__device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
+#endif
+
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
 template <bool Packed, bool Proper, int Cap, int Mode>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
@@ -679,6 +687,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   __shared__ LaneShared SH;
   const int lane = threadIdx.x;
   const uint64_t t = blockIdx.x;
+#ifdef SWT_STAMPS
+  const unsigned long long stamp0 = wall_clock64();
+#endif
   LaneTile T;
   T.s_lo = kDirect ? 0 : plan[t];
   T.s_hi = kDirect ? direct.n_sent : plan[t + 1];
@@ -714,6 +725,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   if (lane == 0) {
     if (kDirect) { direct.off[T.s_hi] = T.run; *direct.n_tokens = T.run; }
     else if (Mode == 0) tile_tok[t] = T.run;
+#ifdef SWT_STAMPS
+    if (Mode == 0 && t < kLaneStamps) { g_lane_stamp[2 * t] = stamp0; g_lane_stamp[2 * t + 1] = wall_clock64(); }
+#endif
   }
 }
 
@@ -738,6 +752,7 @@ struct swt_bpe_table {
   PinnedBuf pin;       // small host calls: inputs and outputs staged in one pinned buffer, one copy each way
   DevBuf small_in, small_out;
   int opt_unique_tile = 0;  // SWT_OPT_UNIQUE_TILE
+  int opt_lane_span = 0;    // SWT_OPT_LANE_SPAN
 };
 
 static int bpe_upload(swt_bpe_table *t) {
@@ -792,6 +807,18 @@ int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   }
   return which == 3 ? (int)n : (placed ? 1 : 0);
 } SWT_API_CATCH
+
+#ifdef SWT_STAMPS
+// diagnostic builds only: copies the stamps of the last Mode 0 launch out (2 * 32,768 values) and clears them
+int swt_debug_lane_stamps(unsigned long long *out) try {
+  void *d = nullptr;
+  SWT_HIP(hipDeviceSynchronize());
+  SWT_HIP(hipGetSymbolAddress(&d, HIP_SYMBOL(g_lane_stamp)));
+  SWT_HIP(hipMemcpy(out, d, sizeof(unsigned long long) * 2 * kLaneStamps, hipMemcpyDeviceToHost));
+  SWT_HIP(hipMemset(d, 0, sizeof(unsigned long long) * 2 * kLaneStamps));
+  return SWT_OK;
+} SWT_API_CATCH
+#endif
 
 int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges,
                          swt_bpe_table **out) try {
@@ -877,6 +904,10 @@ int swt_bpe_table_set_option(swt_bpe_table *t, int option, int value) try {
       if (value != 0 && value != 64 && value != 128 && value != 256) return fail(SWT_ERR_INVALID, "SWT_OPT_UNIQUE_TILE takes 0, 64, 128 or 256");
       t->opt_unique_tile = value;
       return SWT_OK;
+    case SWT_OPT_LANE_SPAN:
+      if (value < 0 || value > (int)kLaneMaxSpan) return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_SPAN takes 0..%u", kLaneMaxSpan);
+      t->opt_lane_span = value;
+      return SWT_OK;
   }
   return fail(SWT_ERR_INVALID, "no such option");
 } SWT_API_CATCH
@@ -913,10 +944,17 @@ static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileW
 #undef SWT_LANE
 }
 
+// Tiles per wave of the running-text form: ONE.  Longer spans were measured and lost (profiles/lane_spans.txt: K = 2 costs the
+// kernel +5 %, K = 4 -- every wave of S85k resident from the start -- +10 %, K = 8 +38 %), so SWT_OPT_LANE_SPAN stays what it is
+// in the header: a knob for tests and sweeps.
+static uint32_t lane_span(const swt_bpe_table *t) { return t->opt_lane_span ? (uint32_t)t->opt_lane_span : 1u; }
+
 static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls,
                              hipStream_t st) {
-  const uint32_t tile = (uint32_t)kLaneTile;
+  // plan, scan and gather see a span as one tile of K * kLaneTile bytes (plan[j] of that size IS plan[j * K] of the tiles), and so
+  // does the kernel: its chunk loop walks the span kLaneCap bytes at a time
+  const uint32_t tile = (uint32_t)kLaneTile * lane_span(t);
   const uint64_t n_tiles = tile_count(n_bytes, tile);
   if (n_tiles > 0x7FFFFFFFull)
     return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);

@@ -3,7 +3,8 @@
 
 namespace swt {
 
-// plan[t] = first sentence whose first byte is >= t * tile  (lower bound; plan[n_tiles] = n_sent)
+// plan[t] = first sentence whose first byte is >= t * tile  (lower bound; plan[n_tiles] = n_sent).  Two forms, the same result:
+// the search (one thread per tile, log2(n_sent) dependent loads) for texts of few long sentences, and the pass below.
 __global__ void plan_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile,
                             uint64_t *__restrict__ plan) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -16,6 +17,32 @@ __global__ void plan_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_se
     if (sent_off[mid] < target) lo = mid + 1; else hi = mid;
   }
   plan[t] = lo;
+}
+
+// The pass: one thread per sentence, no dependent load.  Sentence s is the answer for every tile boundary in
+// (sent_off[s-1], sent_off[s]] (from 0 for s = 0; an empty sentence owns none, so the first of several at one offset wins), and
+// "sentence" n_sent for the boundaries past the last sentence's start and for plan[n_tiles].  A thread writes up to four
+// entries itself; a longer range (a sentence of many tiles) is written by its whole wave, so one giant sentence costs a wave
+// n / 64 steps and not one thread n.
+__global__ __launch_bounds__(256) void plan_pass_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, uint64_t n_tiles,
+                                                        uint32_t tile, uint64_t *__restrict__ plan) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  uint64_t lo = 1, hi = 0;  // tiles [lo, hi] get s; empty for the threads past n_sent
+  if (s <= n_sent) {
+    lo = s ? sent_off[s - 1] / tile + 1 : 0;
+    hi = sent_off[s] / tile;
+    if (s == n_sent) { hi = n_tiles; if (lo > hi) lo = hi; }  // plan[n_tiles] is written here and only here
+    else if (hi >= n_tiles) hi = n_tiles - 1;
+  }
+  const uint64_t cnt = hi + 1 > lo ? hi + 1 - lo : 0;
+  if (cnt <= 4)
+    for (uint64_t t = lo; t <= hi; t++) plan[t] = s;
+  for (unsigned long long LONG = __ballot(cnt > 4); LONG; LONG &= LONG - 1ull) {
+    const int src = __builtin_ctzll(LONG);
+    const uint64_t l = __shfl(lo, src), h = __shfl(hi, src), v = __shfl(s, src);
+    for (uint64_t t = l + lane; t <= h; t += 64) plan[t] = v;
+  }
 }
 
 // Exclusive scan of the tile totals, one launch: every workgroup scans its 1024 tiles locally and publishes its total;
@@ -76,6 +103,46 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(const T *__restrict__ t
   }
 }
 
+// The same scan for up to kScanOne tiles in ONE workgroup: eight tiles per thread, nothing handed from workgroup to workgroup.
+// It fills what the gather reads of the form above: tile_base[t] = the global base, blk_base[t >> 10] = 0.  32 bits hold the base:
+// the tokens of a call are no more than its bytes, and those no more than 8,192 tiles (a few KiB each at most).
+constexpr uint64_t kScanOne = 8192;
+__global__ __launch_bounds__(1024) void tile_scan_one_kernel(const uint32_t *__restrict__ tile_tok, uint32_t n_tiles,
+                                                             uint32_t *__restrict__ tile_base, unsigned long long *__restrict__ blk_base,
+                                                             uint64_t *__restrict__ n_tokens) {
+  __shared__ uint32_t wsum[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t i0 = (uint32_t)tid * 8;
+  uint32_t v[8];
+  if (i0 + 8 <= n_tiles) {  // tile_tok and tile_base come from hipMalloc: 32 bytes into them is 16-byte aligned
+    const uint4 a = *reinterpret_cast<const uint4 *>(tile_tok + i0), b = *reinterpret_cast<const uint4 *>(tile_tok + i0 + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+    for (int k = 0; k < 8; k++) v[k] = i0 + k < n_tiles ? tile_tok[i0 + k] : 0u;
+  }
+  uint32_t mine = 0;
+  for (int k = 0; k < 8; k++) mine += v[k];
+  uint32_t x = mine;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint32_t wb = 0, all = 0;
+  for (int w = 0; w < 16; w++) {
+    if (w < wave) wb += wsum[w];
+    all += wsum[w];
+  }
+  uint32_t run = wb + x - mine;
+  for (int k = 0; k < 8; k++) {
+    if (i0 + k < n_tiles) tile_base[i0 + k] = run;
+    run += v[k];
+  }
+  if ((uint32_t)tid < ((n_tiles + 1023u) >> 10)) blk_base[tid] = 0ull;
+  if (tid == 0) *n_tokens = all;
+}
+
 // A tile's tokens are contiguous in the output: copy its run and turn local sentence offsets into global ones.  A tile holds
 // a few dozen tokens: one WAVE per tile (a workgroup per tile spent most of the launch on dispatching 66 k workgroups).
 __global__ __launch_bounds__(kThreads) void gather_kernel(const uint64_t *__restrict__ sent_off, const uint64_t *__restrict__ plan,
@@ -119,7 +186,11 @@ void TileWorkspace::release() {
 }
 
 void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile, uint64_t *d_plan, hipStream_t st) {
-  hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, n_tiles, tile, d_plan);
+  // the pass reads every sentence offset once; the search is the better form only where sentences are few and tiles many
+  if (n_sent / 256 <= n_tiles)
+    hipLaunchKernelGGL(plan_pass_kernel, dim3((unsigned)((n_sent + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, n_tiles, tile, d_plan);
+  else
+    hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, n_tiles, tile, d_plan);
 }
 
 void launch_scan_only(uint64_t n_tiles, const TileWorkspace &ws, uint64_t *d_n_tokens, hipStream_t st) {
@@ -143,8 +214,12 @@ void launch_scan_gather(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_
   unsigned long long *b = ws.blk.as<unsigned long long>();
   unsigned int *ticket = reinterpret_cast<unsigned int *>(b);
   unsigned long long *blk_tot = b + 1, *blk_base = b + 1 + nb;
-  hipLaunchKernelGGL(tile_scan_kernel<uint32_t>, dim3((unsigned)nb), dim3(1024), 0, st, ws.tile_tok.as<uint32_t>(), n_tiles,
-                     ws.tile_base.as<uint32_t>(), blk_tot, blk_base, ticket, d_n_tokens);
+  if (n_tiles <= kScanOne)
+    hipLaunchKernelGGL(tile_scan_one_kernel, dim3(1), dim3(1024), 0, st, ws.tile_tok.as<uint32_t>(), (uint32_t)n_tiles,
+                       ws.tile_base.as<uint32_t>(), blk_base, d_n_tokens);
+  else
+    hipLaunchKernelGGL(tile_scan_kernel<uint32_t>, dim3((unsigned)nb), dim3(1024), 0, st, ws.tile_tok.as<uint32_t>(), n_tiles,
+                       ws.tile_base.as<uint32_t>(), blk_tot, blk_base, ticket, d_n_tokens);
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n_tiles + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, d_sent_off, ws.plan.as<uint64_t>(), n_tiles,
                      n_sent, ws.scratch.as<uint32_t>(), ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(),
                      ws.tile_base.as<uint32_t>(), blk_base, d_n_tokens, d_out_ids, d_out_off);
