@@ -129,8 +129,9 @@ unsigned swt_class_of(uint32_t code_point);
  */
 typedef struct swt_bpe_table swt_bpe_table;
 
-/* merges in list order as symbol-id triples; a later duplicate (left,right) overrides an earlier one
- * (dict semantics of source/bpe.py:257). */
+/* merges in list order as symbol-id triples; for swt_bpe_encode* a later duplicate (left,right) overrides an earlier one
+ * (dict semantics of source/bpe.py:257), for swt_bpe_encode_naive* every position counts (list semantics of
+ * source/bpe.py:126-127). */
 int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint32_t *merged,
                          uint32_t n_merges, swt_bpe_table **out);
 void swt_bpe_table_destroy(swt_bpe_table *t);
@@ -159,6 +160,25 @@ int swt_bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_jo
 int swt_bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                        uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens,
                        uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * NaiveBPE encode over the same table: replaces NaiveBPE.tokenize (source/bpe.py:136-158) -- the pre-tokenizer split of
+ * SubwordTokenizer.preprocessing (source/utils.py:26-29) and, per word, NaiveBPE.encode_word (source/bpe.py:114-134): every
+ * merge of the list applied IN LIST ORDER to all left-to-right non-overlapping occurrences (source/bpe.py:126-127 over
+ * _replace_pair, source/bpe.py:25-48), '##' = SWT_BPE_CONT on every token after the first of its word (source/bpe.py:130-132).
+ * A pair listed twice is applied at both of its positions (list semantics, not the dict of source/bpe.py:257).  Arguments, token
+ * ids, flags (SWT_BPE_RAW_WORDS = NaiveBPE.encode_word batched; SWT_BPE_NO_DEDUP), need_host / *n_tokens = UINT64_MAX and
+ * capacities (out_cap >= n_bytes, >= n_joined for the joined form, is always sufficient) as the swt_bpe_encode trio.
+ * swt_bpe_table_create decides whether list order can differ from FastBPE's lowest rank first: it cannot when no pair is listed
+ * twice and every pair ranks above the merges that produce its symbols (any trained list).  Such a table runs the FastBPE
+ * kernels unchanged; only the others take the ordered form of the kernel (one lane per word, csrc/swt_bpe_encode.hip). */
+int swt_bpe_encode_naive(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                         uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags);
+int swt_bpe_encode_naive_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                                uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags);
+int swt_bpe_encode_naive_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                             uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens,
+                             uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * FastWP encode: replaces WPTrie_E2E (source/utils.py:66-139: insert + precompute, built on the host

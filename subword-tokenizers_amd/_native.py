@@ -47,6 +47,10 @@ SIGNATURES = {
     "swt_bpe_encode_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u64p, u8p, C.c_uint32]),
     "swt_bpe_encode_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_uint32, C.c_void_p]),
+    "swt_bpe_encode_naive": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u64p, C.c_uint32]),
+    "swt_bpe_encode_naive_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u64p, u8p, C.c_uint32]),
+    "swt_bpe_encode_naive_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_void_p]),
     "swt_wp_trie_create": (C.c_int, [u32p, u64p, C.c_uint32, vpp]),
     "swt_wp_trie_destroy": (None, [C.c_void_p]),
     "swt_wp_trie_stats": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
@@ -384,26 +388,33 @@ class BpeTable:
     def set_option(self, option, value):
         check(lib().swt_bpe_table_set_option(self._h, option, value))
 
-    def encode(self, text_u8, sent_off, flags=0):
+    def order_equivalent(self):
+        """True when NaiveBPE's list order and FastBPE's lowest rank first cannot differ on this table (no pair listed twice,
+        every pair above the merges that produce its symbols): encode_naive* then run the FastBPE kernels"""
+        fn = lib().swt_debug_bpe_table_info
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+        return fn(self._h, 5) == 1
+
+    def encode(self, text_u8, sent_off, flags=0, _entry="swt_bpe_encode"):
         """host buffers in -> (ids uint32, offsets uint64[n+1])"""
         n_sent = int(sent_off.size - 1)
         n_bytes = int(sent_off[-1])
         out = np.empty(max(n_bytes, 1), dtype=np.uint32)
         out_off = np.zeros(n_sent + 1, dtype=np.uint64)
         nt = C.c_uint64()
-        check(lib().swt_bpe_encode(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
-                                   ptr(out_off, u64p), C.byref(nt), flags))
+        check(getattr(lib(), _entry)(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
+                                     ptr(out_off, u64p), C.byref(nt), flags))
         return out[:nt.value], out_off
 
-    def encode_joined(self, joined, n_sent, flags=0):
+    def encode_joined(self, joined, n_sent, flags=0, _entry="swt_bpe_encode_joined"):
         """join_texts' bytes in (not lowercased) -> (ids, offsets), the prepared text staying on the device; None when a sentence
         needs the host's str.lower() (the caller goes pack_and_lower -> encode)"""
         out = np.empty(max(int(joined.size), 1), dtype=np.uint32)
         out_off = np.zeros(n_sent + 1, dtype=np.uint64)
         need = np.zeros(max(n_sent, 1), dtype=np.uint8)
         nt = C.c_uint64()
-        check(lib().swt_bpe_encode_joined(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
-                                          ptr(out_off, u64p), C.byref(nt), ptr(need, u8p), flags))
+        check(getattr(lib(), _entry)(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
+                                     ptr(out_off, u64p), C.byref(nt), ptr(need, u8p), flags))
         if nt.value == 0xFFFFFFFFFFFFFFFF:
             return None
         return out[:nt.value], out_off
@@ -411,6 +422,16 @@ class BpeTable:
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags=0, stream=0):
         """device pointers (ints) in; enqueues on `stream` and returns"""
         check(lib().swt_bpe_encode_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags, stream))
+
+    # the merges in LIST order (NaiveBPE.encode_word, bpe.py:114-134): same arguments and results as the three above
+    def encode_naive(self, text_u8, sent_off, flags=0):
+        return self.encode(text_u8, sent_off, flags, _entry="swt_bpe_encode_naive")
+
+    def encode_naive_joined(self, joined, n_sent, flags=0):
+        return self.encode_joined(joined, n_sent, flags, _entry="swt_bpe_encode_naive_joined")
+
+    def encode_naive_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags=0, stream=0):
+        check(lib().swt_bpe_encode_naive_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags, stream))
 
 
 class WpTrie:

@@ -14,6 +14,14 @@
 // ONE LANE OWNS ONE WORD through the merge rounds (live-slot mask, a lane takes the next word when its own is finished, four
 // lanes a word once few words are left); the phases are described where the kernel stands, below.
 // A word longer than a chunk falls to a one-lane global-memory path (correct, slow, pathological inputs only).
+//
+// The ORDERED form of the same kernel (template parameter Ordered, entry points swt_bpe_encode_naive*) is NaiveBPE.encode_word,
+// /root/reference/source/bpe.py:114-134: the merges applied in LIST order (bpe.py:126-127 over _replace_pair, bpe.py:25-48), which
+// differs from FastBPE's lowest-rank-first on lists that repeat a pair or rank a pair below a merge producing one of its symbols.
+// Only such lists take it (any trained list is order-equivalent and runs the FastBPE kernels as they are), so it is written for
+// correctness, not speed: ONE LANE PER WORD through ordered_word(), no one-occurrence rounds, no four-lane tail.  On S85k-open it
+// costs 0.418 ms per call against FastBPE's 0.153 (2.7 x), 2 % more than the FastBPE kernel on the same improper table
+// (slow_word): DESIGN.md section 4.2d.
 #include <cstring>
 #include <unordered_map>
 #include <utility>
@@ -102,13 +110,61 @@ __device__ uint32_t merge_word(uint32_t *s, uint32_t n, const BpeSlot *__restric
   return n;
 }
 
+// ---- NaiveBPE's list order (bpe.py:126-127) as a RISING FLOOR f: a round takes the smallest list position >= f over the
+// word's adjacent pairs, merges all occurrences of that pair left to right (bpe.py:25-48) and sets f = position + 1.  That is the
+// literal loop: the merges below f have been applied or found nothing to apply to, and no position between f and the minimum
+// has an occurrence in the word.  A pair listed several times has several positions; the ordered table (swt_bpe_table::h_oslots)
+// holds the FIRST, and info[2 * i + 1] chains position i to the next position of the same pair (kNoRank at the end);
+// info[2 * i] is the merged symbol of position i.
+// v = the table value of a pair -> the value of its first position >= floor, kNoRank when there is none.
+template <bool Packed>
+__device__ __forceinline__ uint32_t ordered_value(uint32_t v, uint32_t floor, const uint32_t *__restrict__ info) {
+  if (v == kNoRank) return v;
+  uint32_t r = Packed ? (v >> 16) : v;
+  if (r >= floor) return v;
+  do r = info[2 * r + 1]; while (r != kNoRank && r < floor);
+  if (r == kNoRank) return kNoRank;
+  return Packed ? ((r << 16) | (info[2 * r] - SWT_SYM_BASE)) : r;
+}
+
+// NaiveBPE.encode_word on a symbol array (bpe.py:124-127), serial form for the one-lane fallback.  Returns the new length.
+template <bool Packed>
+__device__ uint32_t merge_word_ordered(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh,
+                                       const uint32_t *__restrict__ info) {
+  uint32_t floor = 0;
+  while (n >= 2) {
+    uint32_t best = kNoRank, bl = 0, br = 0;
+    uint32_t a = s[0];
+    for (uint32_t i = 0; i + 1 < n; i++) {
+      const uint32_t b = s[i + 1];
+      const uint32_t v = ordered_value<Packed>(slot_value(slots, sh, a, b), floor, info);
+      if (v < best) { best = v; bl = a; br = b; }
+      a = b;
+    }
+    if (best == kNoRank) break;
+    const uint32_t rank = Packed ? (best >> 16) : best;
+    const uint32_t bm = info[2 * rank];
+    uint32_t j = 0, i = 0;
+    while (i < n) {
+      const uint32_t x = s[i];
+      if (i + 1 < n && x == bl && s[i + 1] == br) { s[j++] = bm; i += 2; }
+      else { s[j++] = x; i++; }
+    }
+    n = j;
+    floor = rank + 1u;
+  }
+  return n;
+}
+
 struct GiantResult { uint64_t end; uint32_t ntok; };
 
 // One lane, global memory only: the word (or single separator) starting at byte `pos`, bounded by
 // `send` (end of its sentence).  Tokens go to `out` (which doubles as the symbol workspace).
+// Ordered: the merges in list order (merge_word_ordered; `info` is its chain, unused otherwise).
+template <bool Packed, bool Ordered>
 __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos, uint64_t send,
                                   const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                  uint32_t *out) {
+                                  const uint32_t *__restrict__ info, uint32_t *out) {
   GiantResult r{pos, 0};
   uint32_t n = 0;
   bool first = true;
@@ -128,7 +184,7 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
     r.end += len;
     first = false;
   }
-  n = merge_word(out, n, slots, sh);
+  n = Ordered ? merge_word_ordered<Packed>(out, n, slots, sh, info) : merge_word(out, n, slots, sh);
   for (uint32_t i = 1; i < n; i++) out[i] |= SWT_BPE_CONT;
   r.ntok = n;
   return r;
@@ -162,6 +218,10 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //          drec[s], and length | s to the word's table slot, rec[uslot[s]]; nobody needs a scan or a gather of that launch's
 //          output), 2 = one workgroup writing the caller's arrays (DirectOut).  A template parameter, not a run-time test:
 //          each form keeps only its own arguments in scalar registers (one kernel for all three spilled 44 of them).
+//   Ordered: NaiveBPE's list order (bpe.py:126-127) instead of lowest rank first: `slots` is the table of FIRST list positions,
+//          `merged_of_rank` the interleaved (merged symbol, next position of the same pair) array, and every multi-symbol word
+//          goes through ordered_word() / merge_word_ordered(), one lane per word.  Launched only for a table that is not
+//          order-equivalent (swt_bpe_table::order_equivalent), where the two orders can disagree.
 // Measured and dropped (profiles/r03_experiments/bpe_lane_*.txt): one wave running the rounds for the words of four tiles
 // (fewer instructions, but three waves of four idle meanwhile: 0.229 against 0.200 ms), tiles that place their own output by a
 // decoupled look-back, and tiles that plan themselves (two launches instead of four).
@@ -238,6 +298,42 @@ __device__ void slow_word(uint32_t *S, uint32_t *V, const uint32_t n0, const Bpe
     V[n - 1] = kNoRank;
     for (uint32_t k = 0; k + 1 < n; k++)
       if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT);
+  }
+  for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
+}
+
+// NaiveBPE.encode_word (bpe.py:124-127) on the same layout, modelled on slow_word: a round merges all occurrences of the pair
+// with the smallest list position >= floor and raises the floor past it.  The values the split left come from the table of
+// first positions, so they are valid at floor 0; a cached value above the round's minimum is a position >= the new floor and
+// stays the pair's first such position, so only the pairs a merge created are probed again -- and walk the chain of their
+// pair's positions up to the floor (ordered_value).  All slots of the winning pair hold the same value, so V[i] == m finds them.
+template <bool Packed>
+__device__ void ordered_word(uint32_t *S, uint32_t *V, const uint32_t n0, const BpeSlot *__restrict__ slots, uint32_t sh,
+                             const uint32_t *__restrict__ info) {
+  uint32_t n = n0;
+  for (;;) {
+    uint32_t m = kNoRank;
+    for (uint32_t i = 0; i + 1 < n; i++) m = min(m, V[i]);
+    if (m == kNoRank) break;
+    const uint32_t rank = Packed ? (m >> 16) : m;
+    const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : info[2 * rank];
+    const uint32_t floor = rank + 1u;
+    uint32_t i = 0, j = 0;
+    while (i < n) {
+      const uint32_t vi = V[i];
+      const bool take = i + 1 < n && vi == m;
+      const uint32_t s = take ? mg : (S[i] & ~SWT_BPE_CONT);
+      if (take && j) V[j - 1] = kDirtyVal;
+      S[j] = j ? (s | SWT_BPE_CONT) : s;
+      V[j] = take ? kDirtyVal : vi;
+      i += take ? 2u : 1u;
+      j++;
+    }
+    n = j;
+    V[n - 1] = kNoRank;
+    for (uint32_t k = 0; k + 1 < n; k++)
+      if (V[k] == kDirtyVal)
+        V[k] = ordered_value<Packed>(slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT), floor, info);
   }
   for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
 }
@@ -381,10 +477,10 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2
 
 // ---- the end of a chunk that does not end the tile: one word longer than the staged bytes goes to the one-lane walker (and the
 // chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list and moves T.cb past the chunk.
-template <int Cap, int Mode>
+template <int Cap, int Mode, bool Packed, bool Ordered>
 __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
                                                const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                               LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
+                                               const uint32_t *__restrict__ merged_of_rank, LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
                                                const uint32_t *__restrict__ uslot, unsigned long long *__restrict__ rec,
                                                unsigned long long *__restrict__ drec, const DirectOut &direct) {
   constexpr bool kDirect = Mode == 2, kRec = Mode == 1;
@@ -395,7 +491,7 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, GiantResult &gia
         uint64_t s = T.s_next;
         while (s < T.s_hi && sent_off[s] <= T.cb) s++;
         const uint64_t send = sent_off[s];  // s <= s_hi and sent_off[s_hi] = span_end > cb
-        giant = giant_word(text, T.cb, send, cls_tab, slots, sh, T.tile_out + T.run);
+        giant = giant_word<Packed, Ordered>(text, T.cb, send, cls_tab, slots, sh, merged_of_rank, T.tile_out + T.run);
       }
       wave_sync();
       const GiantResult g = giant;
@@ -561,7 +657,7 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, un
 }
 
 // The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
-template <bool Packed, bool Proper, int Cap>
+template <bool Packed, bool Proper, int Cap, bool Ordered>
 __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t *list, uint32_t n_list, int lane,
                                                 const BpeSlot *__restrict__ slots, uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
   constexpr uint32_t kNoKey = Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
@@ -581,7 +677,10 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t 
         S = &L.sym[where];
         V = &L.val[where];
         alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
-        if (!Proper || n > 32u) {
+        if (Ordered) {
+          ordered_word<Packed>(S, V, n, slots, sh, merged_of_rank);
+          n = 0u;
+        } else if (!Proper || n > 32u) {
           slow_word<Packed>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
         } else {
@@ -674,7 +773,7 @@ __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 #endif
 
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
-template <bool Packed, bool Proper, int Cap, int Mode>
+template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots,
@@ -708,14 +807,14 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   for (;;) {
     LaneChunk C;
     lane_split(L, SH.cls2, text, n_bytes, sent_off, cls_tab, slots, sh, T, C, lane);
-    lane_chunk_end<Cap, Mode>(L, SH.giant, text, sent_off, cls_tab, slots, sh, T, C, lane, sent_local, uslot, rec, drec, direct);
+    lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, slots, sh, merged_of_rank, T, C, lane, sent_local, uslot, rec, drec, direct);
     if (C.giant) continue;
     uint32_t c2, c1, c0;
     lane_words_count(L, C.nw, lane, c2, c1, c0);
     lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1);
     wave_sync();
     // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
-    const LaneWord W = lane_rounds<Packed, Proper, Cap>(L, list, c2 + c1 + c0, lane, slots, sh, merged_of_rank);
+    const LaneWord W = lane_rounds<Packed, Proper, Cap, Ordered>(L, list, c2 + c1 + c0, lane, slots, sh, merged_of_rank);
     const unsigned long long BUSY = __ballot(W.n != 0u);
     if (BUSY != 0ull) lane_tail<Packed, 4, Cap>(L, W, BUSY, lane, slots, sh, merged_of_rank);
     wave_sync();
@@ -743,6 +842,16 @@ struct swt_bpe_table {
   BpeSlot *d_slots = nullptr;
   uint32_t *d_merged = nullptr;
   uint32_t bits = 0;
+  // NaiveBPE's list order (swt_bpe_encode_naive*).  order_equivalent: no pair listed twice and the table proper, so list order
+  // and lowest-rank-first give the same tokens and the naive entry points run the FastBPE path as it is.  Otherwise the ordered
+  // form of the kernel runs over h_oslots (the FIRST list position of every pair, same layout and hashes as h_slots) and h_oinfo
+  // ([2i] merged symbol of position i, [2i + 1] next position of the same pair or kNoRank), uploaded on the first naive call.
+  bool order_equivalent = false;
+  std::vector<BpeSlot> h_oslots;
+  std::vector<uint32_t> h_oinfo;
+  BpeSlot *d_oslots = nullptr;
+  uint32_t *d_oinfo = nullptr;
+  uint32_t obits = 0;
   uint32_t n_merges = 0;
   TileWorkspace ws;
   DevBuf in_text, in_off, out_ids, out_off, n_tok;  // staging for the host-buffer entry point
@@ -767,19 +876,35 @@ static int bpe_upload(swt_bpe_table *t) {
   return SWT_OK;
 }
 
+static int bpe_upload_ordered(swt_bpe_table *t) {
+  if (t->d_oslots || t->order_equivalent) return SWT_OK;
+  SWT_HIP(hipMalloc((void **)&t->d_oslots, t->h_oslots.size() * sizeof(BpeSlot)));
+  SWT_HIP(hipMemcpy(t->d_oslots, t->h_oslots.data(), t->h_oslots.size() * sizeof(BpeSlot), hipMemcpyHostToDevice));
+  SWT_HIP(hipMalloc((void **)&t->d_oinfo, (t->h_oinfo.size() + 2) * 4));
+  if (!t->h_oinfo.empty())
+    SWT_HIP(hipMemcpy(t->d_oinfo, t->h_oinfo.data(), t->h_oinfo.size() * 4, hipMemcpyHostToDevice));
+  return SWT_OK;
+}
+
+// what a launch reads the ranks from: the FastBPE table, or the ordered one (first positions + chain)
+struct BpeView { const BpeSlot *slots; const uint32_t *merged; uint32_t sh; };
+static BpeView bpe_view(const swt_bpe_table *t, bool ordered) {
+  return ordered ? BpeView{t->d_oslots, t->d_oinfo, 32u - t->obits} : BpeView{t->d_slots, t->d_merged, 32u - t->bits};
+}
+
 // the word-lane kernel: running text, or the unique words of the dedup path (d_rec)
-template <bool Packed, bool Proper, int Cap>
+template <bool Packed, bool Proper, int Cap, bool Ordered = false>
 static void launch_lane_kernel_as(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
                                   const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot,
                                   unsigned long long *d_rec, unsigned long long *d_drec, hipStream_t st) {
-  const uint32_t sh = 32u - t->bits;
+  const BpeView v = bpe_view(t, Ordered);
   if (d_rec)
-    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 1>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, t->d_slots, sh, t->d_merged, ws.scratch.as<uint32_t>(),
+    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 1, Ordered>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                       ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
                        ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
   else
-    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 0>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, t->d_slots, sh, t->d_merged, ws.scratch.as<uint32_t>(),
+    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 0, Ordered>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                       ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
                        ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
 }
 
@@ -787,12 +912,20 @@ extern "C" {
 
 // diagnostics (not part of include/swt.h): what swt_bpe_table_create decided.  0: log2 of the slots, 1: packed values,
 // 2: proper (every pair ranks above the merges producing its symbols), 3: entries in the table, 4: every entry is found where
-// a device lookup looks for it (its first or its second slot) and nowhere else
+// a device lookup looks for it (its first or its second slot) and nowhere else, 5: order-equivalent (no pair listed twice and
+// proper: NaiveBPE's list order, bpe.py:126-127, gives what FastBPE's lowest rank first gives, and swt_bpe_encode_naive* run the
+// FastBPE path), 6: entries in the ordered table (0 for an order-equivalent table, which has none)
 int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   if (!t) return -1;
   if (which == 0) return (int)t->bits;
   if (which == 1) return t->packed ? 1 : 0;
   if (which == 2) return t->proper ? 1 : 0;
+  if (which == 5) return t->order_equivalent ? 1 : 0;
+  if (which == 6) {
+    int n = 0;
+    for (const BpeSlot &sl : t->h_oslots) n += sl.key != kEmptyKey;
+    return n;
+  }
   uint32_t n = 0;
   bool placed = true;
   const uint32_t sh = 32u - t->bits;
@@ -820,28 +953,22 @@ int swt_debug_lane_stamps(unsigned long long *out) try {
 } SWT_API_CATCH
 #endif
 
-int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges,
-                         swt_bpe_table **out) try {
-  if (!out || (n_merges && (!left || !right || !merged))) return fail(SWT_ERR_INVALID, "null argument");
-  for (uint32_t i = 0; i < n_merges; i++)
-    if ((left[i] | right[i] | merged[i]) & SWT_BPE_CONT) return fail(SWT_ERR_INVALID, "symbol id out of range at merge %u", i);
-  // {pair: i} (bpe.py:257): a later duplicate overwrites, so only the LAST index of a pair goes into the table
-  std::unordered_map<uint64_t, uint32_t> last;
-  last.reserve((size_t)n_merges * 2 + 16);
-  for (uint32_t i = 0; i < n_merges; i++) last[pair_key(left[i], right[i])] = i;
+}  // extern "C"
+
+// Two-choice cuckoo placement (see slot_lookup) of the merges i with pick[pair] == i; a table that does not settle gets twice
+// the slots.  False when it cannot be placed.
+static bool place_slots(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges,
+                        std::unordered_map<uint64_t, uint32_t> &pick, std::vector<BpeSlot> &slots, uint32_t &bits_out) {
   uint32_t bits = 4;
   while ((1ull << bits) < 2ull * n_merges + 2) bits++;
-  auto *t = new swt_bpe_table();
-  std::vector<BpeSlot> &slots = t->h_slots;
-  // two-choice cuckoo placement (see slot_lookup); a table that does not settle gets twice the slots
   const uint32_t bits0 = bits;
   for (;; bits++) {
-    if (bits > 28 || bits > bits0 + 4) { delete t; return fail(SWT_ERR_UNSUPPORTED, "the rank table could not be placed (%u pairs)", n_merges); }
+    if (bits > 28 || bits > bits0 + 4) return false;
     const uint32_t sh = 32u - bits;
     slots.assign((size_t)1 << bits, BpeSlot{kEmptyKey, 0u, 0u});
     bool ok = true;
     for (uint32_t i = 0; i < n_merges && ok; i++) {
-      if (last[pair_key(left[i], right[i])] != i) continue;
+      if (pick[pair_key(left[i], right[i])] != i) continue;
       BpeSlot cur{pair_key(left[i], right[i]), i, merged[i]};
       uint32_t avoid = 0xFFFFFFFFu;
       ok = false;
@@ -857,7 +984,27 @@ int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint
     }
     if (ok) break;
   }
-  t->bits = bits;
+  bits_out = bits;
+  return true;
+}
+
+extern "C" {
+
+int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges,
+                         swt_bpe_table **out) try {
+  if (!out || (n_merges && (!left || !right || !merged))) return fail(SWT_ERR_INVALID, "null argument");
+  for (uint32_t i = 0; i < n_merges; i++)
+    if ((left[i] | right[i] | merged[i]) & SWT_BPE_CONT) return fail(SWT_ERR_INVALID, "symbol id out of range at merge %u", i);
+  // {pair: i} (bpe.py:257): a later duplicate overwrites, so only the LAST index of a pair goes into the table
+  std::unordered_map<uint64_t, uint32_t> last;
+  last.reserve((size_t)n_merges * 2 + 16);
+  for (uint32_t i = 0; i < n_merges; i++) last[pair_key(left[i], right[i])] = i;
+  auto *t = new swt_bpe_table();
+  std::vector<BpeSlot> &slots = t->h_slots;
+  if (!place_slots(left, right, merged, n_merges, last, slots, t->bits)) {
+    delete t;
+    return fail(SWT_ERR_UNSUPPORTED, "the rank table could not be placed (%u pairs)", n_merges);
+  }
   t->n_merges = n_merges;
   // proper: every pair ranks above every merge that produces one of its symbols, so the pairs a merge creates rank above it
   // and "one occurrence of the best pair per round" equals the reference's "all occurrences" (bpe_lane_kernel)
@@ -882,9 +1029,34 @@ int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint
   t->packed = n_merges < 0xFFFEu;
   for (uint32_t i = 0; i < n_merges && t->packed; i++)
     if (merged[i] < SWT_SYM_BASE || merged[i] - SWT_SYM_BASE >= 0xFFFFu) t->packed = false;
-  if (t->packed)
+  // NaiveBPE applies the list in order (bpe.py:126-127), every position of a repeated pair in its turn.  Without repeats and
+  // on a proper table that is FastBPE's result and nothing more is built; otherwise the ordered form of the kernel gets the
+  // first position of every pair and the chain through its later ones (ordered_value).
+  t->order_equivalent = t->proper && last.size() == n_merges;
+  if (!t->order_equivalent) {
+    std::unordered_map<uint64_t, uint32_t> first, seen;
+    first.reserve((size_t)n_merges * 2 + 16);
+    seen.reserve((size_t)n_merges * 2 + 16);
+    t->h_oinfo.assign((size_t)n_merges * 2, kNoRank);
+    for (uint32_t i = n_merges; i-- > 0;) {
+      const uint64_t k = pair_key(left[i], right[i]);
+      auto it = seen.find(k);
+      t->h_oinfo[2 * (size_t)i] = merged[i];
+      if (it != seen.end()) t->h_oinfo[2 * (size_t)i + 1] = it->second;
+      seen[k] = i;
+      first[k] = i;
+    }
+    if (!place_slots(left, right, merged, n_merges, first, t->h_oslots, t->obits)) {
+      delete t;
+      return fail(SWT_ERR_UNSUPPORTED, "the ordered rank table could not be placed (%u pairs)", n_merges);
+    }
+  }
+  if (t->packed) {
     for (auto &sl : slots)
       if (sl.key != kEmptyKey) sl.rank = (sl.rank << 16) | (sl.merged - SWT_SYM_BASE);
+    for (auto &sl : t->h_oslots)
+      if (sl.key != kEmptyKey) sl.rank = (sl.rank << 16) | (sl.merged - SWT_SYM_BASE);
+  }
   *out = t;
   return SWT_OK;
 } SWT_API_CATCH
@@ -916,6 +1088,8 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
   if (!t) return;
   if (t->d_slots) (void)hipFree(t->d_slots);
   if (t->d_merged) (void)hipFree(t->d_merged);
+  if (t->d_oslots) (void)hipFree(t->d_oslots);
+  if (t->d_oinfo) (void)hipFree(t->d_oinfo);
   t->ws.release();
   t->ws2.release();
   t->dd.release();
@@ -930,9 +1104,15 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
 // cap = staged bytes per chunk (LDS footprint ~ 20 B per byte): 512 for running text, less for the unique-word pass
 static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
                                  const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot, unsigned long long *d_rec,
-                                 unsigned long long *d_drec, hipStream_t st, int cap = kLaneCap) {
-#define SWT_LANE(P, R, C) launch_lane_kernel_as<P, R, C>(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, d_uslot, d_rec, d_drec, st)
-#define SWT_LANE_CAPS(P, R) do { if (cap == 128) SWT_LANE(P, R, 128); else if (cap == 256) SWT_LANE(P, R, 256); else SWT_LANE(P, R, 512); } while (0)
+                                 unsigned long long *d_drec, hipStream_t st, bool ordered, int cap = kLaneCap) {
+#define SWT_LANE(P, R, C, ...) launch_lane_kernel_as<P, R, C, ##__VA_ARGS__>(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, d_uslot, d_rec, d_drec, st)
+#define SWT_LANE_CAPS(P, R, ...) do { if (cap == 128) SWT_LANE(P, R, 128, ##__VA_ARGS__); else if (cap == 256) SWT_LANE(P, R, 256, ##__VA_ARGS__); else SWT_LANE(P, R, 512, ##__VA_ARGS__); } while (0)
+  if (ordered) {  // list order: the same chunk sizes, every word through ordered_word
+    if (!d_rec) { if (t->packed) SWT_LANE(true, false, kLaneCap, true); else SWT_LANE(false, false, kLaneCap, true); }
+    else if (t->packed) SWT_LANE_CAPS(true, false, true);
+    else SWT_LANE_CAPS(false, false, true);
+    return;
+  }
   if (!d_rec) {  // running text: the one chunk size the tile was chosen for
     if (t->packed) { if (t->proper) SWT_LANE(true, true, kLaneCap); else SWT_LANE(true, false, kLaneCap); }
     else { if (t->proper) SWT_LANE(false, true, kLaneCap); else SWT_LANE(false, false, kLaneCap); }
@@ -951,7 +1131,7 @@ static uint32_t lane_span(const swt_bpe_table *t) { return t->opt_lane_span ? (u
 
 static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls,
-                             hipStream_t st) {
+                             hipStream_t st, bool ordered) {
   // plan, scan and gather see a span as one tile of K * kLaneTile bytes (plan[j] of that size IS plan[j * K] of the tiles), and so
   // does the kernel: its chunk loop walks the span kLaneCap bytes at a time
   const uint32_t tile = (uint32_t)kLaneTile * lane_span(t);
@@ -963,13 +1143,14 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
     // a sentence or a few: one workgroup, one launch, the caller's arrays written by the kernel (DirectOut)
     if ((rc = ws.reserve(64, 0, 1))) return rc;
     const DirectOut direct{d_out_off, d_n_tokens, n_sent};
-    const uint32_t sh = 32u - t->bits;
+    const BpeView v = bpe_view(t, ordered);
     auto one_lane = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, t->d_slots, sh,
-                         t->d_merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
+      hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots, v.sh,
+                         v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
                          (unsigned long long *)nullptr, (unsigned long long *)nullptr, direct);
     };
-    if (t->packed) { if (t->proper) one_lane(bpe_lane_kernel<true, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<true, false, kLaneCap, 2>); }
+    if (ordered) { if (t->packed) one_lane(bpe_lane_kernel<true, false, kLaneCap, 2, true>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2, true>); }
+    else if (t->packed) { if (t->proper) one_lane(bpe_lane_kernel<true, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<true, false, kLaneCap, 2>); }
     else { if (t->proper) one_lane(bpe_lane_kernel<false, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2>); }
     SWT_HIP(hipGetLastError());
     return SWT_OK;
@@ -978,7 +1159,7 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, n_tiles, tile, ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st);
+  launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st, ordered);
   prof_end(st);
   launch_scan_gather(d_sent_off, n_sent, n_tiles, ws, d_out_ids, d_out_off, d_n_tokens, st);
   prof_end(st, 2);
@@ -991,7 +1172,8 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
 // Returns 1 when the batch is too large for the 32-bit fields of this path (the caller takes the direct path).
 constexpr uint64_t kUMaxTiles = 8192;  // its launch size: 256 CUs x 32 single-wave workgroups
 static int bpe_encode_dedup(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
-                            uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls, hipStream_t st) {
+                            uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls, hipStream_t st,
+                            bool ordered) {
   int rc;
   // tile of the unique-word pass (chunk = 2 such tiles): the kernel wants a batch of words per tile, so 256 bytes unless
   // SWT_OPT_UNIQUE_TILE says otherwise (S85k-lex: 64 -> 0.182, 128 -> 0.174, 256 -> 0.168 ms per call)
@@ -1008,7 +1190,7 @@ static int bpe_encode_dedup(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_
   // phase F of the kernel leaves count | place in rec[slot]
   prof_begin(st);
   launch_encode_kernel(t, n_tiles2, t->ws2, t->dd.utext.as<uint8_t>(), n_bytes, t->dd.uoff.as<uint64_t>(), nullptr,
-                       t->dd.uslot.as<uint32_t>(), t->dd.rec_ptr(), t->dd.drec_ptr(), st, (int)(2 * tile2));
+                       t->dd.uslot.as<uint32_t>(), t->dd.rec_ptr(), t->dd.drec_ptr(), st, ordered, (int)(2 * tile2));
   prof_end(st);
   rc = dedup_back(t->dd, t->ws, d_sent_off, n_sent, n_bytes, t->ws2.scratch.as<uint32_t>(), kDedupBpe, nullptr, d_out_ids, d_out_off,
                   d_n_tokens, st);
@@ -1016,13 +1198,20 @@ static int bpe_encode_dedup(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_
   return rc;
 }
 
-int swt_bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
-                       uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
-                       void *stream) try {
+}  // extern "C"
+
+// The three entry points, for both orders.  A call that came through swt_bpe_encode_naive* on a table that is not
+// order-equivalent takes the ordered form of the kernel (bpe_ordered); every other call launches exactly what it launched before.
+static bool bpe_ordered(const swt_bpe_table *t) { return t && !t->order_equivalent; }
+
+static int bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                          uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
+                          void *stream, bool ordered) {
   if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_bytes && (!d_text || !d_out_ids)))
     return fail(SWT_ERR_INVALID, "null argument");
   int rc = bpe_upload(t);
   if (rc) return rc;
+  if (ordered && (rc = bpe_upload_ordered(t))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const uint8_t *d_cls = nullptr;
   if ((rc = device_class_table(&d_cls))) return rc;
@@ -1035,23 +1224,23 @@ int swt_bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes
   // debug knob 1: bit 0 = never dedup, bit 1 = dedup whatever the batch size (tests)
   if (!raw && !(flags & SWT_BPE_NO_DEDUP) && t->dd.opt_mode != 1 &&
       (t->dd.opt_mode == 2 || (n_bytes >= kDedupMinBytes && t->dd.pays(n_bytes)))) {
-    rc = bpe_encode_dedup(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, d_cls, st);
+    rc = bpe_encode_dedup(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, d_cls, st, ordered);
     if (rc == 0 && t->dd.opt_mode == 0) t->dd.note(n_bytes, st);
     if (rc <= 0) return rc;  // done, or a real error
   }
   // raw-word mode: no classes, so nothing splits and nothing is dropped
-  return bpe_encode_direct(t, t->ws, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, raw ? nullptr : d_cls, st);
-} SWT_API_CATCH
+  return bpe_encode_direct(t, t->ws, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, raw ? nullptr : d_cls, st, ordered);
+}
 
 // text and offsets on the device -> ids, offsets and the count in the caller's host arrays
 static int bpe_encode_to_host(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent,
-                              uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags) {
+                              uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered) {
   int rc;
   if ((rc = t->out_ids.reserve((n_bytes + 64) * 4))) return rc;
   if ((rc = t->out_off.reserve((n_sent + 1) * 8))) return rc;
   if ((rc = t->n_tok.reserve(8))) return rc;
-  rc = swt_bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->n_tok.as<uint64_t>(),
-                          flags, nullptr);
+  rc = bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->n_tok.as<uint64_t>(),
+                      flags, nullptr, ordered);
   if (rc) return rc;
   uint64_t nt = 0;
   SWT_HIP(hipMemcpy(&nt, t->n_tok.p, 8, hipMemcpyDeviceToHost));
@@ -1063,8 +1252,8 @@ static int bpe_encode_to_host(swt_bpe_table *t, const uint8_t *d_text, uint64_t 
   return SWT_OK;
 }
 
-int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
-                   uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags) try {
+static int bpe_encode_host(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                           uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered) {
   if (!t || !sent_off || !out_off || !n_tokens) return fail(SWT_ERR_INVALID, "null argument");
   int rc = bpe_upload(t);
   if (rc) return rc;
@@ -1088,8 +1277,8 @@ int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_o
     if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
     memset(h + off_bytes + n_bytes, ' ', 64);
     uint8_t *o = h + out_at;
-    rc = swt_bpe_encode_dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent, reinterpret_cast<uint32_t *>(o + 16 + off_bytes),
-                            reinterpret_cast<uint64_t *>(o + 16), reinterpret_cast<uint64_t *>(o), flags, nullptr);
+    rc = bpe_encode_dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent, reinterpret_cast<uint32_t *>(o + 16 + off_bytes),
+                        reinterpret_cast<uint64_t *>(o + 16), reinterpret_cast<uint64_t *>(o), flags, nullptr, ordered);
     if (rc) return rc;
     SWT_HIP(hipStreamSynchronize(0));
     const uint64_t nt = *reinterpret_cast<const volatile uint64_t *>(o);
@@ -1114,9 +1303,9 @@ int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_o
     if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
     SWT_HIP(hipMemcpyAsync(t->small_in.p, h, off_bytes + n_bytes, hipMemcpyHostToDevice, 0));
     uint8_t *d_in = t->small_in.as<uint8_t>(), *d_out = t->small_out.as<uint8_t>();
-    rc = swt_bpe_encode_dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
-                            reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
-                            reinterpret_cast<uint64_t *>(d_out), flags, nullptr);
+    rc = bpe_encode_dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
+                        reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
+                        reinterpret_cast<uint64_t *>(d_out), flags, nullptr, ordered);
     if (rc) return rc;
     SWT_HIP(hipMemcpyAsync(h, d_out, 16 + off_bytes + (n_bytes + 64) * 4, hipMemcpyDeviceToHost, 0));
     SWT_HIP(hipStreamSynchronize(0));
@@ -1132,26 +1321,62 @@ int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_o
   if ((rc = t->in_off.reserve((n_sent + 1) * 8))) return rc;
   if (n_bytes) SWT_HIP(hipMemcpyAsync(t->in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
   SWT_HIP(hipMemcpyAsync(t->in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  return bpe_encode_to_host(t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, n_tokens, flags);
-} SWT_API_CATCH
+  return bpe_encode_to_host(t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, n_tokens, flags, ordered);
+}
 
 // list[str] joined with U+0000 -> ids without the prepared text ever coming back to the host (swt_utf8_prepare_joined +
 // swt_bpe_encode in one call).  *n_tokens = UINT64_MAX on return: a sentence needs the host's str.lower() (need_host says
 // which) and nothing was encoded.
-int swt_bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
-                          uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags) try {
+static int bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
+                             uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags, bool ordered) {
   if (!t || !out_off || !n_tokens || (n_sent && !need_host) || (n_joined && !joined)) return fail(SWT_ERR_INVALID, "null argument");
   int rc = bpe_upload(t);
   if (rc) return rc;
   *n_tokens = UINT64_MAX;
-  struct Ctx { swt_bpe_table *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off, *n_tokens; uint32_t flags; };
-  Ctx c{t, n_sent, out_ids, out_cap, out_off, n_tokens, flags};
+  struct Ctx { swt_bpe_table *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off, *n_tokens; uint32_t flags; bool ordered; };
+  Ctx c{t, n_sent, out_ids, out_cap, out_off, n_tokens, flags, ordered};
   bool consumed = false;
   return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
       [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
         Ctx *c = static_cast<Ctx *>(p);
-        return bpe_encode_to_host(c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->n_tokens, c->flags);
+        return bpe_encode_to_host(c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->n_tokens, c->flags, c->ordered);
       }, &c);
+}
+
+extern "C" {
+
+int swt_bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                       uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
+                       void *stream) try {
+  return bpe_encode_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, flags, stream, false);
+} SWT_API_CATCH
+
+int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                   uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags) try {
+  return bpe_encode_host(t, text, sent_off, n_sent, out_ids, out_cap, out_off, n_tokens, flags, false);
+} SWT_API_CATCH
+
+int swt_bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
+                          uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags) try {
+  return bpe_encode_joined(t, joined, n_joined, n_sent, out_ids, out_cap, out_off, n_tokens, need_host, flags, false);
+} SWT_API_CATCH
+
+// NaiveBPE.tokenize (bpe.py:136-158: the split of utils.py:26-29, then encode_word, bpe.py:114-134, per word) for a batch: the
+// merges applied in list order.  Same arguments, ids and flags as the three above.
+int swt_bpe_encode_naive_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                             uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
+                             void *stream) try {
+  return bpe_encode_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, flags, stream, bpe_ordered(t));
+} SWT_API_CATCH
+
+int swt_bpe_encode_naive(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                         uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags) try {
+  return bpe_encode_host(t, text, sent_off, n_sent, out_ids, out_cap, out_off, n_tokens, flags, bpe_ordered(t));
+} SWT_API_CATCH
+
+int swt_bpe_encode_naive_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                                uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags) try {
+  return bpe_encode_joined(t, joined, n_joined, n_sent, out_ids, out_cap, out_off, n_tokens, need_host, flags, bpe_ordered(t));
 } SWT_API_CATCH
 
 }  // extern "C"

@@ -4,7 +4,7 @@ Same names, constructor, methods, attributes and error behaviour as phtryll/subw
 (`source/bpe.py`, `source/wordpiece.py`, `source/utils.py`; citations below are relative to /root/reference):
 
     SubwordTokenizer   utils.py:5-41      preprocessing(), vocab_length()
-    NaiveBPE           bpe.py:9-189       train() on the device; encode_word()/tokenize() stay the slow didactic loop
+    NaiveBPE           bpe.py:9-189       train() on the device; encode_word()/tokenize() stay the slow didactic loop, the batch calls run it on the device
     FastBPE            bpe.py:192-263     train() + tokenize()/encode_word() on the device
     NaiveWP            wordpiece.py:8-208 train() on the device; tokenize() stays the Python loop, the batch calls run it on the device
     FastWP             wordpiece.py:211-330  trie build in C++, tokenize() on the device
@@ -116,7 +116,8 @@ _PLAIN_INTERN = _SymbolTable.intern  # (a test swaps intern() for another to for
 
 class NaiveBPE(SubwordTokenizer):
     """Byte-Pair Encoding (bpe.py:9-189).  `train` runs on the device; `encode_word`/`tokenize` keep the
-    reference's didactic O(merges x length) loop in Python (out of the GPU scope)."""
+    reference's didactic O(merges x length) loop in Python (out of the GPU scope, SURVEY.md section 2 row 11);
+    `encode_ids_batch`/`tokenize_batch` run the same loop -- the merges in LIST order -- on the device (swt_bpe_encode_naive)."""
 
     def __init__(self, tokenizer=None) -> None:
         super().__init__(tokenizer)
@@ -126,6 +127,10 @@ class NaiveBPE(SubwordTokenizer):
         self._train_syms: Optional[_SymbolTable] = None
         self._train_ids = None  # (left, right, merged) ids of merges_list as the device named them, when no replay was needed
         self._corpus_cache = None
+        self._naive_table: Optional[N.BpeTable] = None  # built from merges_list on the first batch call
+        self._naive_syms = _SymbolTable()
+        self._naive_merges: Optional[list] = None  # the list the handle was built from
+        self._train_merges: Optional[list] = None  # the merges _train_ids name (merges_list itself may be changed later)
 
     # -- bpe.py:25-48
     def _replace_pair(self, pair: Tuple[str, str], word: List[str]) -> List[str]:
@@ -221,6 +226,7 @@ class NaiveBPE(SubwordTokenizer):
                     trainer.apply(l_, r_, m_)
                 exhausted = False
         self._trainer, self._train_syms, self._corpus_cache = trainer, syms, None
+        self._train_merges = list(self.merges_list)
         if clean:
             self._train_ids = (np.concatenate([l for l, _, _ in runs]) if runs else np.zeros(0, np.uint32),
                                np.concatenate([r for _, r, _ in runs]) if runs else np.zeros(0, np.uint32),
@@ -257,14 +263,68 @@ class NaiveBPE(SubwordTokenizer):
             out += self.encode_word(w)
         return out
 
+    # -- batch entry points (not in the reference): tokenize() of every text on the device, the merges in list order
+    def _drop_naive_table(self) -> None:
+        if self._naive_table is not None:
+            self._naive_table.close()
+        self._naive_table, self._naive_syms, self._naive_merges = None, _SymbolTable(), None
+
+    def _ensure_naive_table(self) -> N.BpeTable:
+        # rebuilt when merges_list was assigned or changed in place since the last build (train/reset/load_resources drop it)
+        if self._naive_table is None or self.merges_list != self._naive_merges:
+            self._drop_naive_table()
+            merges = [tuple(pair) for pair in self.merges_list]
+            syms = _SymbolTable()
+            if self._train_ids is not None and self._train_syms is not None and merges == self._train_merges:
+                # the device named the symbols of the merges it chose exactly as the loop below would (FastBPE.train)
+                syms.strings, syms.index = list(self._train_syms.strings), dict(self._train_syms.index)
+                left, right, merged = self._train_ids
+            else:
+                intern = syms.intern  # the interning order of FastBPE._build_table
+                ids = np.array([x for l, r in merges for x in (intern(l), intern(r), intern(l + r))], dtype=np.uint32).reshape(-1, 3)
+                left, right, merged = ids[:, 0], ids[:, 1], ids[:, 2]
+            self._naive_table, self._naive_syms, self._naive_merges = N.BpeTable(left, right, merged), syms, merges
+        return self._naive_table
+
+    def encode_ids_batch(self, texts: List[str]) -> Tuple[np.ndarray, np.ndarray]:
+        """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
+        over this object's own symbol table (decode_ids spells them)."""
+        if not isinstance(texts, list) or (len(texts) <= 64 and not all(isinstance(t, str) for t in texts)):
+            raise TypeError("Text to tokenize must be a string.")
+        table = self._ensure_naive_table()
+        if len(texts) > 64:
+            joined, n_nul = N.join_texts(texts, "Text to tokenize must be a string.")  # as FastBPE.encode_ids_batch
+            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
+                got = table.encode_naive_joined(joined, len(texts))
+                if got is not None:
+                    return got
+        text, off = N.pack_and_lower(texts)  # utils.py:27 lower()
+        return table.encode_naive(text, off)
+
+    def decode_ids(self, ids) -> List[str]:
+        st = self._naive_syms
+        return [("##" + st.string(t)) if t & N.BPE_CONT else st.string(t) for t in map(int, np.asarray(ids, dtype=np.uint32))]
+
+    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
+        """[tokenize(t) for t in texts]"""
+        ids, off = self.encode_ids_batch(texts)
+        if ids.size < 4096:
+            toks = self.decode_ids(ids)
+            return [toks[int(off[i]):int(off[i + 1])] for i in range(len(texts))]
+        st = self._naive_syms
+        key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit: each DISTINCT id is spelled once
+        spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
+        return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, off)
+
     # -- bpe.py:160-164
     def reset(self) -> None:
         self.merges_list.clear()
         self.vocab.clear()
+        self._drop_naive_table()
         if self._trainer is not None:
             self._trainer.close()
         self._trainer, self._train_syms, self._corpus_cache = None, None, None
-        self._train_ids = None
+        self._train_ids = self._train_merges = None
 
     # -- bpe.py:167-189
     def save_resources(self, path: str) -> None:
@@ -277,6 +337,7 @@ class NaiveBPE(SubwordTokenizer):
         if os.path.isfile(merges_file):  # a missing file is silently ignored (bpe.py:187)
             with open(merges_file, "r", encoding="utf-8") as f:
                 self.merges_list = [tuple(pair) for pair in json.load(f)]
+            self._drop_naive_table()
 
 
 class FastBPE(NaiveBPE):

@@ -1,0 +1,239 @@
+"""NaiveBPE.tokenize (bpe.py:114-158: the merges applied in list order) against the reference's own output
+(tests/golden/naivebpe.json, made by make_golden_naivebpe.py), through the rising-floor model the device runs
+(csrc/swt_bpe_encode.hip, ordered_word) and through the package's Python loop.  The device encoder
+(tests/test_gpu_naive_bpe.py) is checked against the same fixture and model.  No GPU needed here."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _load(rel):
+    path, _, key = rel.partition("#")
+    with open(os.path.join(GOLDEN, path), encoding="utf-8") as f:
+        obj = json.load(f)
+    if key == "sentences":
+        return [c["text"] for c in obj["sentences"]]
+    return obj[key] if key else obj
+
+
+def naivebpe_cases():
+    """[(name, merges as tuples, texts, tokens, case dict)]"""
+    out = []
+    for c in _load("naivebpe.json")["cases"]:
+        merges = [tuple(p) for p in (c["merges"] if "merges" in c else _load(c["merges_ref"]))]
+        texts = _load(c["texts_ref"])
+        if "index" in c:
+            texts = [texts[i] for i in c["index"]]
+        tokens = c["tokens"] if "tokens" in c else _load(c["tokens_ref"])
+        assert len(texts) == len(tokens)
+        out.append((c["name"], merges, texts, tokens, c))
+    return out
+
+
+HAND_MADE = ["listed_twice", "listed_twice_second_applies", "below_its_producer", "same_string", "not_producible", "empty",
+             "multibyte_punctuation", "long", "long_against_order"]
+NOT_ORDER_EQUIVALENT = ["listed_twice", "listed_twice_second_applies", "below_its_producer", "multibyte_punctuation",
+                        "long_against_order"]
+
+
+class RisingFloor:
+    """NaiveBPE.encode_word as the device runs it: a round takes the smallest list position >= floor over the word's adjacent
+    pairs (a pair listed several times counts with its first position >= floor), merges all occurrences of that pair left to
+    right and raises the floor past it; the loop ends when no adjacent pair has a position >= floor."""
+
+    def __init__(self, merges):
+        self.positions = {}
+        for i, pair in enumerate(merges):
+            self.positions.setdefault(tuple(pair), []).append(i)
+        self.memo = {}
+
+    def position(self, pair, floor):
+        for i in self.positions.get(pair, ()):
+            if i >= floor:
+                return i
+        return None
+
+    def encode_word(self, word):
+        got = self.memo.get(word)
+        if got is not None:
+            return got
+        s, floor = list(word), 0
+        while len(s) > 1:
+            best = None
+            for k in range(len(s) - 1):
+                r = self.position((s[k], s[k + 1]), floor)
+                if r is not None and (best is None or r < best[0]):
+                    best = (r, s[k], s[k + 1])
+            if best is None:
+                break
+            r, left, right = best
+            out, k = [], 0
+            while k < len(s):
+                if k + 1 < len(s) and s[k] == left and s[k + 1] == right:
+                    out.append(left + right)
+                    k += 2
+                else:
+                    out.append(s[k])
+                    k += 1
+            s, floor = out, r + 1
+        got = self.memo[word] = s[:1] + ["##" + p for p in s[1:]]
+        return got
+
+    def tokenize(self, text, split):
+        return [t for w in split(text) for t in self.encode_word(w)]
+
+
+def splitter():
+    from subword_tokenizers_amd.tokenizers import SubwordTokenizer
+
+    return lambda text: [w for w, _ in SubwordTokenizer._split(text.lower())]
+
+
+def table_info(native, merges, which):
+    """swt_debug_bpe_table_info of the table NaiveBPE builds from `merges` (host only: nothing is uploaded)"""
+    import subword_tokenizers_amd as S
+
+    tok = S.NaiveBPE()
+    tok.merges_list = list(merges)
+    lib = native.lib()
+    lib.swt_debug_bpe_table_info.restype = ctypes.c_int
+    lib.swt_debug_bpe_table_info.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    return lib.swt_debug_bpe_table_info(tok._ensure_naive_table()._h, which)
+
+
+def test_rising_floor_model_equals_the_reference(swt):
+    split = splitter()
+    for name, merges, texts, tokens, _ in naivebpe_cases():
+        m = RisingFloor(merges)
+        for text, want in zip(texts, tokens):
+            assert m.tokenize(text, split) == want, (name, text[:60])
+
+
+@pytest.mark.parametrize("name", ["fuzz_tutorial", "pan_tadeusz_tutorial"] + HAND_MADE)
+def test_naive_bpe_tokenize_equals_the_reference(swt, name):
+    """the package's NaiveBPE.tokenize (the Python loop) on every case but the two with the 19,876 shipped merges ..."""
+    (merges, texts, tokens), = [(m, t, k) for n, m, t, k, _ in naivebpe_cases() if n == name]
+    tok = swt.NaiveBPE()
+    tok.merges_list = list(merges)
+    for text, want in zip(texts, tokens):
+        assert tok.tokenize(text) == want, text[:60]
+
+
+@pytest.mark.parametrize("name", ["pan_tadeusz_pretrained", "fuzz_pretrained"])
+def test_naive_bpe_tokenize_equals_the_reference_shipped_merges(swt, name):
+    """... where the loop takes ~30 ms a word: encode_word once per distinct word, as the fixture was made, on every case text"""
+    (merges, texts, tokens), = [(m, t, k) for n, m, t, k, _ in naivebpe_cases() if n == name]
+    tok = swt.NaiveBPE()
+    tok.merges_list = list(merges)
+    if name == "pan_tadeusz_pretrained":  # 3,309 distinct words would take minutes: every seventh sentence
+        texts, tokens = texts[::7], tokens[::7]
+    memo = {}
+    for text, want in zip(texts, tokens):
+        got = []
+        for w, _ in tok.preprocessing([text])[0]:
+            if w not in memo:
+                memo[w] = tok.encode_word(w)
+            got += memo[w]
+        assert got == want, text[:60]
+    assert tok.tokenize(texts[0]) == tokens[0]
+
+
+def test_fixture_covers_the_corners():
+    fx = _load("naivebpe.json")
+    cases = {name: (merges, texts, tokens, c) for name, merges, texts, tokens, c in naivebpe_cases()}
+    assert {"pan_tadeusz_pretrained", "fuzz_pretrained", "fuzz_tutorial", "pan_tadeusz_tutorial"} <= set(cases) and set(HAND_MADE) <= set(cases)
+    # the reference ships the same bytes for NaiveBPE and FastBPE: one copy under ref/ serves both
+    assert all(s["identical"] and os.path.isfile(os.path.join(GOLDEN, s["merges_ref"])) for s in fx["shipped"].values())
+    assert set(fx["shipped"]) == {"pretrained", "tests"}
+    # order matters on the hand-made lists, and does not on the shipped (trained) ones
+    for name in ("listed_twice", "listed_twice_second_applies", "below_its_producer", "long_against_order"):
+        assert cases[name][3]["differs_from_fastbpe"] > 0, name
+    for name in ("pan_tadeusz_pretrained", "fuzz_pretrained", "fuzz_tutorial", "pan_tadeusz_tutorial", "empty", "same_string"):
+        assert cases[name][3]["differs_from_fastbpe"] == 0, name
+    merges, texts, tokens, _ = cases["listed_twice"]
+    assert merges.count(("b", "c")) == 2 and merges.count(("x", "y")) == 2
+    assert tokens[texts.index("abc")] == ["a", "##bc"]  # ("b", "c") at its FIRST position; the dict of bpe.py:257 gives ab ##c
+    assert tokens[texts.index("xyx")] == ["xy", "##x"]
+    merges, texts, tokens, _ = cases["below_its_producer"]
+    assert merges.index(("ab", "c")) < merges.index(("a", "b")) and tokens[texts.index("abc")] == ["ab", "##c"]
+    merges, texts, tokens, _ = cases["listed_twice_second_applies"]
+    assert merges.count(("ab", "ab")) == 3 and merges.index(("ab", "ab")) < merges.index(("a", "b"))
+    assert tokens[texts.index("abab")] == ["abab"] and tokens[texts.index("babab")] == ["b", "##abab"]  # the dict: bab ##ab
+    merges, texts, tokens, _ = cases["same_string"]
+    assert ("a", "bc") in merges and ("ab", "c") in merges and tokens[texts.index("abcabc")] == ["abcabc"]
+    merges, _, _, _ = cases["not_producible"]
+    produced = {l + r for l, r in merges}
+    assert any(len(l) > 1 and l not in produced for l, _ in merges) and any(len(r) > 1 and r not in produced for _, r in merges)
+    assert cases["empty"][0] == [] and cases["empty"][2][cases["empty"][1].index("abc")] == ["a", "##b", "##c"]
+    merges, texts, tokens, _ = cases["multibyte_punctuation"]
+    assert any(ord(c) > 0xFFFF for l, r in merges for c in l + r) and ("!", "!") in merges
+    assert tokens[texts.index("!!")] == ["!", "!"]  # the pre-tokenizer isolates punctuation: the pair never meets in tokenize()
+    # words longer than 32 symbols (the live-slot mask of the FastBPE rounds) and longer than a 512-byte chunk (one lane, global memory)
+    long_texts = fx["texts"]
+    assert any(32 < len(t) < 100 and " " not in t for t in long_texts) and any(len(t) > 512 and " " not in t for t in long_texts)
+    assert any(cases["fuzz_pretrained"][3]["whole"]) and cases["pan_tadeusz_pretrained"][3]["whole"]
+    size = os.path.getsize(os.path.join(GOLDEN, "naivebpe.json"))
+    assert size <= os.path.getsize(os.path.join(GOLDEN, "fuzz_bpe.json"))
+
+
+def test_naive_bpe_has_batch_entry_points_apart_from_fast_bpe(swt, native):
+    """the device batch calls exist on NaiveBPE (and in the binding) and FastBPE keeps its own"""
+    for name in ("encode_ids_batch", "tokenize_batch", "decode_ids"):
+        assert callable(getattr(swt.NaiveBPE, name))
+        assert getattr(swt.FastBPE, name) is not getattr(swt.NaiveBPE, name)
+    for name in ("encode_naive", "encode_naive_joined", "encode_naive_dev"):
+        assert callable(getattr(native.BpeTable, name))
+    tok = swt.NaiveBPE()
+    with pytest.raises(TypeError, match="Text to tokenize must be a string."):
+        tok.tokenize_batch("not a list")
+    with pytest.raises(TypeError, match="Text to tokenize must be a string."):
+        tok.encode_ids_batch(["a", 1])
+    with pytest.raises(TypeError, match="Text to tokenize must be a string."):
+        tok.encode_ids_batch(["a"] * 70 + [1])
+    # the Python loop stays what it was
+    tok.merges_list = [("a", "b")]
+    assert tok.tokenize("ab c") == ["ab", "c"] and tok.encode_word("abab") == ["ab", "##ab"]
+
+
+def test_order_equivalence_is_decided_at_table_create(swt, native, golden):
+    """swt_debug_bpe_table_info(t, 5): 1 = list order cannot differ from lowest rank first (no pair twice, proper)"""
+    fx = golden("naivebpe.json")
+    for s in fx["shipped"].values():
+        merges = [tuple(p) for p in golden(s["merges_ref"])]
+        assert table_info(native, merges, 5) == 1 and table_info(native, merges, 6) == 0
+    # lists the reference's own training produced (the CPU reference's NaiveBPE.train on micro corpora): always order-equivalent
+    micro = golden("bpe_train_micro.json")
+    assert sum(len(m["merges"]) > 3 for m in micro) > 50
+    for m in micro:
+        assert table_info(native, [tuple(p) for p in m["merges"]], 5) == 1, m["corpus"]
+    cases = {name: merges for name, merges, _, _, _ in naivebpe_cases()}
+    for name in NOT_ORDER_EQUIVALENT:
+        assert table_info(native, cases[name], 5) == 0, name
+        assert table_info(native, cases[name], 6) == len(set(cases[name])), name  # one entry per distinct pair
+    for name in ("same_string", "not_producible", "empty", "long"):
+        assert table_info(native, cases[name], 5) == 1, name
+    # the FastBPE view of the same handle is what it was: the LAST position of a repeated pair (bpe.py:257)
+    assert table_info(native, cases["listed_twice"], 3) == len(set(cases["listed_twice"]))
+
+
+def test_table_follows_merges_list(swt, native):
+    """the handle is rebuilt when merges_list is assigned, changed in place, reset or loaded"""
+    tok = swt.NaiveBPE()
+    tok.merges_list = [("a", "b")]
+    t1 = tok._ensure_naive_table()
+    assert tok._ensure_naive_table() is t1 and t1.n_merges == 1
+    tok.merges_list.append(("ab", "c"))
+    t2 = tok._ensure_naive_table()
+    assert t2 is not t1 and t2.n_merges == 2 and tok._naive_syms.strings == ["ab", "abc"]
+    tok.merges_list = [("b", "c")]
+    assert tok._ensure_naive_table().n_merges == 1 and tok._naive_syms.strings == ["bc"]
+    tok.reset()
+    assert tok._naive_table is None and tok._ensure_naive_table().n_merges == 0
+    assert not hasattr(swt.NaiveBPE(), "_table")  # FastBPE's attributes stay FastBPE's
+    f = swt.FastBPE()
+    assert f._naive_table is None and np.asarray(f._syms.strings).size == 0
