@@ -240,6 +240,41 @@ int swt_token_histogram_dev(const uint32_t *d_ids, uint64_t n, uint32_t id_cap, 
                             void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Token-sequence equivalence of two tokenizers on the device: the counting of the reference's token_sequence_equivalence
+ * (source/benchmarks.py:113-183, what `--benchmark --pretrained --compare` prints) over two id streams with the same rows
+ * (CSR offsets off_a[n_rows+1], off_b[n_rows+1]) instead of two lists of token strings per sentence and per word.
+ *
+ * The reference compares tokens as STRINGS after `tok[2:] if tok.startswith("##") else tok` (source/benchmarks.py:144-145,
+ * 164-165), so the two streams need a common id space: the caller interns the stripped strings of both tokenizers in one
+ * table and hands over one uint32 map per stream.  The canonical id of a token `id` is, with s = id & 0x7FFFFFFF:
+ *     s                                                              when s < map_base
+ *     map[(s - map_base) + ((flagged && (id >> 31)) ? n_map : 0)]    otherwise
+ * (a BPE stream: map_base = SWT_SYM_BASE, flagged = 1, 2 * n_map entries, the second half for ids with SWT_BPE_CONT; a
+ * WordPiece stream: map_base = 0, flagged = 0, n_map entries).  A token with s - map_base >= n_map, or whose map entry is
+ * 0xFFFFFFFF, has no canonical id: it is tallied in totals[4] and takes part in nothing.
+ *
+ * Per row, with t1 / t2 the row's canonical ids (source/benchmarks.py:148-156, 166):
+ *     positions    min(len(t1), len(t2))
+ *     pos_matches  #{i < positions : t1[i] == t2[i]}
+ *     unordered    sum over tokens of min(count in t1, count in t2)    (the multiset intersection)
+ *     has_common   1 when set(t1) & set(t2) is not empty, else 0
+ * per_row[4 r .. 4 r + 4) receives these four (may be NULL); totals[0..4) their sums over the rows, each row multiplied by
+ * weight[r] (NULL = 1; the word pass runs once per DISTINCT word with its number of occurrences); totals has 5 entries.
+ * Rows of any length are counted exactly and on the device (csrc/swt_metrics.hip; swt_token_equivalence_capacity reports the
+ * row sizes at which the kernels change form: the shorter side's length up to which one wavefront takes the row, and the
+ * distinct tokens one pass of the workgroup kernel holds).  The `_dev` form takes device pointers, zeroes its outputs itself,
+ * enqueues on the stream and does not synchronise.
+ */
+int swt_token_equivalence(const uint32_t *ids_a, const uint64_t *off_a, const uint32_t *map_a, uint32_t map_base_a, uint32_t n_map_a,
+                          int flagged_a, const uint32_t *ids_b, const uint64_t *off_b, const uint32_t *map_b, uint32_t map_base_b,
+                          uint32_t n_map_b, int flagged_b, uint64_t n_rows, const uint32_t *weight, uint64_t *totals, uint32_t *per_row);
+int swt_token_equivalence_dev(const uint32_t *d_ids_a, const uint64_t *d_off_a, const uint32_t *d_map_a, uint32_t map_base_a,
+                              uint32_t n_map_a, int flagged_a, const uint32_t *d_ids_b, const uint64_t *d_off_b, const uint32_t *d_map_b,
+                              uint32_t map_base_b, uint32_t n_map_b, int flagged_b, uint64_t n_rows, const uint32_t *d_weight,
+                              uint64_t *d_totals, uint32_t *d_per_row, void *stream);
+int swt_token_equivalence_capacity(uint32_t *wave_cap, uint32_t *block_cap);
+
+/* ------------------------------------------------------------------------------------------------
  * BPE training: replaces the merge loop of NaiveBPE.train (source/bpe.py:88-111; FastBPE.train
  * inherits it, source/bpe.py:198-200) and its word dedup (source/bpe.py:73-81).
  *

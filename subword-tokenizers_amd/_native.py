@@ -73,6 +73,12 @@ SIGNATURES = {
     "swt_utf8_lower_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "swt_token_histogram": (C.c_int, [u32p, C.c_uint64, C.c_uint32, u64p, u64p]),
     "swt_token_histogram_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_token_equivalence": (C.c_int, [u32p, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int,
+                                        C.c_uint64, u32p, u64p, u32p]),
+    "swt_token_equivalence_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "swt_token_equivalence_capacity": (C.c_int, [u32p, u32p]),
     "swt_bpe_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
     "swt_bpe_train_create_joined": (C.c_int, [u8p, C.c_uint64, C.c_uint64, u8p, vpp]),
     "swt_wp_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
@@ -364,6 +370,48 @@ def token_histogram(ids, id_cap):
     if oor.value:
         raise ValueError("%d token ids are outside [0, %d)" % (oor.value, id_cap))
     return counts
+
+
+def token_equivalence_capacity():
+    """-> (wave_cap, block_cap): the shorter side's length up to which one wavefront counts a row of token_equivalence, and the
+    distinct tokens one pass of the workgroup kernel holds for the longer rows (csrc/swt_metrics.hip)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_token_equivalence_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def token_equivalence(side_a, side_b, weight=None, per_row=False):
+    """The counting of benchmarks.py:113-183 over two id streams with the same rows, on the device (swt_token_equivalence).
+    side = (ids uint32, offsets uint64[n_rows + 1], map uint32, map_base, flagged): see include/swt.h for the canonical id a
+    map gives a token; a flagged map has two halves.  weight: uint32 per row, or None = 1.
+    -> totals uint64[4] = (positions, pos_matches, unordered, has_common), each row times its weight; with per_row also the
+    uint32[n_rows, 4] of the rows themselves.  ValueError when an id lies beyond its map."""
+    args, keep = [], []
+    n_rows = int(np.asarray(side_a[1]).size) - 1
+    for ids, off, cmap, base, flagged in (side_a, side_b):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
+        if int(off.size) - 1 != n_rows or n_rows < 0:
+            raise ValueError("the two streams must have the same rows")
+        if off[0] != 0 or int(off[-1]) != ids.size:
+            raise ValueError("offsets must run from 0 to the number of ids")
+        if flagged and cmap.size % 2:
+            raise ValueError("a flagged map has two halves of equal size")
+        keep += [ids, off, cmap]
+        args += [ptr(ids, u32p) if ids.size else None, ptr(off, u64p), ptr(cmap, u32p) if cmap.size else None, int(base),
+                 int(cmap.size) // 2 if flagged else int(cmap.size), int(bool(flagged))]
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.uint32)
+        if weight.size != n_rows:
+            raise ValueError("one weight per row")
+    totals = np.zeros(5, dtype=np.uint64)
+    rows = np.zeros((n_rows, 4), dtype=np.uint32) if per_row else None
+    check(lib().swt_token_equivalence(*args, n_rows, ptr(weight, u32p) if weight is not None and n_rows else None, ptr(totals, u64p),
+                                      ptr(rows, u32p) if per_row and n_rows else None))
+    if totals[4]:
+        raise ValueError("%d token ids are outside their canonical maps" % int(totals[4]))
+    return (totals[:4], rows) if per_row else totals[:4]
 
 
 class BpeTable:

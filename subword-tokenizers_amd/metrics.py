@@ -29,7 +29,7 @@ from . import _native as N
 
 __all__ = ["avg_tokens_per_sentence", "avg_tokens_per_word", "normalized_sequence_length", "subword_fragmentation_rate",
            "vocabulary_coverage_rate", "compression_rate", "zipf_distribution", "zipf_from_counts", "quality_metrics",
-           "token_sequence_equivalence", "tokenization_performance", "training_performance", "benchmarks"]
+           "equivalence_metrics", "token_sequence_equivalence", "tokenization_performance", "training_performance", "benchmarks"]
 
 
 # ---- the reference's function surface (benchmarks.py:7-110) ---------------------------------------------------------------
@@ -231,9 +231,9 @@ def _strip(tokens):
     return [t[2:] if t.startswith("##") else t for t in tokens]
 
 
-def token_sequence_equivalence(tokenizer1: Any, tokenizer2: Any, input: List[str]):
-    """benchmarks.py:113-183: positional / unordered / per-word agreement of two tokenizers.  The token lists come from the
-    batch calls where a class has them (one call for the sentences, one for all the words); the counting is the reference's."""
+def _equivalence_in_python(tokenizer1: Any, tokenizer2: Any, input: List[str]):
+    """benchmarks.py:113-183 on token STRINGS, for anything that has `tokenize`.  The token lists come from the batch calls
+    where a class has them (one call for the sentences, one for all the words); the counting is the reference's."""
     from collections import Counter
 
     def many(tok, texts):
@@ -259,6 +259,120 @@ def token_sequence_equivalence(tokenizer1: Any, tokenizer2: Any, input: List[str
     return (total_pos_matches, total_positions, (total_pos_matches / total_positions * 100) if total_positions else 0.0,
             total_unordered_matches, (total_unordered_matches / total_positions * 100) if total_positions else 0.0,
             total_word_matches, total_words, (total_word_matches / total_words * 100) if total_words else 0.0)
+
+
+# ---- the same numbers from ids: canonical maps, two encodes per tokenizer, two kernel calls --------------------------------
+
+class _Canon:
+    """One id per STRIPPED token string, shared by the two tokenizers of a comparison (the interning of tokenizers._SymbolTable):
+    a one-code-point string -> its ordinal, any other string (the empty one too) -> SYM_BASE + k in order of first appearance."""
+
+    def __init__(self):
+        self.index: Dict[str, int] = {}
+
+    def intern(self, s: str) -> int:
+        if len(s) == 1:
+            return ord(s)
+        k = self.index.get(s)
+        if k is None:
+            k = self.index[s] = len(self.index)
+        return N.SYM_BASE + k
+
+
+def _strip1(t: str) -> str:
+    return t[2:] if t.startswith("##") else t  # benchmarks.py:144
+
+
+def _canonical_map(tokenizer, canon: _Canon):
+    """-> (map uint32, map_base, flagged) of one of this package's tokenizers: what swt_token_equivalence needs to turn the ids
+    of its encode_ids_batch into canonical ids (include/swt.h).
+    BPE: 2 * n_sym entries over the merged symbols; [k] = strip(string_k) for an id without SWT_BPE_CONT, [n_sym + k] = string_k
+    for an id with it (the token is "##" + string_k, which strips back to string_k); one-code-point symbols are their own
+    canonical id, map_base = SYM_BASE.  WordPiece: strip(token) in id order, then "['UNK']", then "[UNK]"; map_base = 0."""
+    from . import tokenizers as T
+
+    intern = canon.intern
+    if isinstance(tokenizer, T.NaiveBPE):
+        if isinstance(tokenizer, T.FastBPE):
+            tokenizer._ensure_table()
+            strings = tokenizer._syms.strings
+        else:
+            tokenizer._ensure_naive_table()
+            strings = tokenizer._naive_syms.strings
+        cmap = [intern(_strip1(s)) for s in strings] + [intern(s) for s in strings]
+        return np.array(cmap, dtype=np.uint32), N.SYM_BASE, True
+    if isinstance(tokenizer, T.FastWP):
+        tokens = tokenizer._tokens
+    else:
+        tokenizer._ensure_naive_trie()
+        tokens = tokenizer._naive_tokens
+    cmap = [intern(_strip1(t)) for t in tokens] + [intern("['UNK']"), intern("[UNK]")]
+    return np.array(cmap, dtype=np.uint32), 0, False
+
+
+def _encode_ids(tokenizer, texts: List[str]):
+    """encode_ids_batch -> (ids, offsets), raising what tokenize_batch raises for a WordPiece status; None when a FastWP output
+    holds the multi-token corner marker (wordpiece.py:260-261: one id there stands for several tokens)"""
+    if not texts:
+        if not isinstance(texts, list):
+            raise TypeError("Text must be a string.")
+        return np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
+    from . import tokenizers as T
+
+    got = tokenizer.encode_ids_batch(texts)
+    if isinstance(tokenizer, T.NaiveBPE):
+        return got
+    ids, off, status = got
+    bad = np.flatnonzero(status)
+    if isinstance(tokenizer, T.FastWP):
+        if bad.size:
+            tokenizer._raise_for_status(int(status[int(bad[0])]), texts[int(bad[0])])
+            raise RuntimeError("FastWP.encode_ids_batch: unknown status %d" % int(status[int(bad[0])]))
+        if ids.size and int(ids.max()) > len(tokenizer._tokens) + 1:
+            return None
+    elif bad.size:
+        tokenizer._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
+    return ids, off
+
+
+def equivalence_metrics(tokenizer1, tokenizer2, corpus: List[str]):
+    """token_sequence_equivalence (benchmarks.py:113-183) of two of this package's tokenizers without spelling a token: the
+    sentences and the distinct words (with their number of occurrences) go through encode_ids_batch of both, and
+    swt_token_equivalence counts positional, unordered and per-word agreement over the canonical ids.  The integers are exact
+    and the rates come from them through the reference's expressions, so the tuple is the reference's.  A FastWP whose
+    encode_word("##") corner is multi-token AND occurs in the output is counted by the Python body instead."""
+    from collections import Counter
+
+    s1 = _encode_ids(tokenizer1, corpus)
+    s2 = _encode_ids(tokenizer2, corpus)
+    if s1 is None or s2 is None:
+        return _equivalence_in_python(tokenizer1, tokenizer2, corpus)
+    counts = Counter(" ".join(corpus).split())  # the occurrences of sentence.split() per sentence (benchmarks.py:159)
+    uniq = list(counts)
+    w1 = _encode_ids(tokenizer1, uniq)
+    w2 = _encode_ids(tokenizer2, uniq)
+    if w1 is None or w2 is None:
+        return _equivalence_in_python(tokenizer1, tokenizer2, corpus)
+    canon = _Canon()
+    m1, m2 = _canonical_map(tokenizer1, canon), _canonical_map(tokenizer2, canon)
+    positions, pos, unordered, _ = (int(x) for x in N.token_equivalence(s1 + m1, s2 + m2))
+    weight = np.fromiter(counts.values(), dtype=np.uint32, count=len(uniq))
+    word_matches = int(N.token_equivalence(w1 + m1, w2 + m2, weight=weight)[3])
+    total_words = sum(counts.values())
+    return (pos, positions, (pos / positions * 100) if positions else 0.0,
+            unordered, (unordered / positions * 100) if positions else 0.0,
+            word_matches, total_words, (word_matches / total_words * 100) if total_words else 0.0)
+
+
+def token_sequence_equivalence(tokenizer1: Any, tokenizer2: Any, input: List[str]):
+    """benchmarks.py:113-183: positional / unordered / per-word agreement of two tokenizers.  Two of this package's classes are
+    compared on the device over ids (equivalence_metrics); anything else that has `tokenize` through its token strings."""
+    from . import tokenizers as T
+
+    ours = (T.NaiveBPE, T.FastBPE, T.NaiveWP, T.FastWP)
+    if type(tokenizer1) in ours and type(tokenizer2) in ours:
+        return equivalence_metrics(tokenizer1, tokenizer2, input)
+    return _equivalence_in_python(tokenizer1, tokenizer2, input)
 
 
 def _report_pretrained(tokenizer, name, test_corpus):
