@@ -854,12 +854,10 @@ struct swt_bpe_table {
   uint32_t obits = 0;
   uint32_t n_merges = 0;
   TileWorkspace ws;
-  DevBuf in_text, in_off, out_ids, out_off, n_tok;  // staging for the host-buffer entry point
+  HostStage stage;  // the host entry points (host_encode*, swt_tile.h)
   // word-level dedup inside one call
   TileWorkspace ws2;          // workspaces of the encode over the unique words
   DedupEngine dd;
-  PinnedBuf pin;       // small host calls: inputs and outputs staged in one pinned buffer, one copy each way
-  DevBuf small_in, small_out;
   int opt_unique_tile = 0;  // SWT_OPT_UNIQUE_TILE
   int opt_lane_span = 0;    // SWT_OPT_LANE_SPAN
 };
@@ -892,20 +890,24 @@ static BpeView bpe_view(const swt_bpe_table *t, bool ordered) {
   return ordered ? BpeView{t->d_oslots, t->d_oinfo, 32u - t->obits} : BpeView{t->d_slots, t->d_merged, 32u - t->bits};
 }
 
-// the word-lane kernel: running text, or the unique words of the dedup path (d_rec)
-template <bool Packed, bool Proper, int Cap, bool Ordered = false>
-static void launch_lane_kernel_as(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
-                                  const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot,
-                                  unsigned long long *d_rec, unsigned long long *d_drec, hipStream_t st) {
-  const BpeView v = bpe_view(t, Ordered);
-  if (d_rec)
-    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 1, Ordered>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
-                       ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
-  else
-    hipLaunchKernelGGL((bpe_lane_kernel<Packed, Proper, Cap, 0, Ordered>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                       ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
-                       ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
+// Which bpe_lane_kernel a launch gets.  Mode (the kernel's: 0 tiles of running text, 1 the unique words of the dedup path, 2 the
+// single workgroup) is the caller's; from the table come Packed and Proper, from the entry point Ordered (which has no Proper
+// form: every word goes through ordered_word), from the tile size of the launch the chunk size -- `cap` bytes where the tiled
+// forms have it (128, 256), kLaneCap otherwise; the single workgroup exists at kLaneCap only.
+using LaneKernel = decltype(&bpe_lane_kernel<true, true, kLaneCap, 0>);
+template <int Cap, int Mode>
+static LaneKernel lane_kernel_at(bool packed, bool proper, bool ordered) {
+  if (ordered) return packed ? bpe_lane_kernel<true, false, Cap, Mode, true> : bpe_lane_kernel<false, false, Cap, Mode, true>;
+  if (packed) return proper ? bpe_lane_kernel<true, true, Cap, Mode> : bpe_lane_kernel<true, false, Cap, Mode>;
+  return proper ? bpe_lane_kernel<false, true, Cap, Mode> : bpe_lane_kernel<false, false, Cap, Mode>;
+}
+template <int Mode>
+static LaneKernel lane_kernel(const swt_bpe_table *t, bool ordered, int cap = kLaneCap) {
+  if constexpr (Mode != 2) {
+    if (cap == 128) return lane_kernel_at<128, Mode>(t->packed, t->proper, ordered);
+    if (cap == 256) return lane_kernel_at<256, Mode>(t->packed, t->proper, ordered);
+  }
+  return lane_kernel_at<kLaneCap, Mode>(t->packed, t->proper, ordered);
 }
 
 extern "C" {
@@ -1093,35 +1095,19 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
   t->ws.release();
   t->ws2.release();
   t->dd.release();
-  t->pin.release();
-  t->small_in.release();
-  t->small_out.release();
-  for (DevBuf *b : {&t->in_text, &t->in_off, &t->out_ids, &t->out_off, &t->n_tok}) b->release();
+  t->stage.release();
   delete t;
 } SWT_API_CATCH_VOID
 
-// the direct path: every word occurrence goes through the merge rounds
-// cap = staged bytes per chunk (LDS footprint ~ 20 B per byte): 512 for running text, less for the unique-word pass
+// The tiled forms of the word-lane kernel: running text, or (d_rec) the unique words of the dedup path.
+// cap = staged bytes per chunk (LDS footprint ~ 12 B per byte): kLaneCap for running text, less for the unique-word pass
 static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
                                  const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot, unsigned long long *d_rec,
                                  unsigned long long *d_drec, hipStream_t st, bool ordered, int cap = kLaneCap) {
-#define SWT_LANE(P, R, C, ...) launch_lane_kernel_as<P, R, C, ##__VA_ARGS__>(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, d_uslot, d_rec, d_drec, st)
-#define SWT_LANE_CAPS(P, R, ...) do { if (cap == 128) SWT_LANE(P, R, 128, ##__VA_ARGS__); else if (cap == 256) SWT_LANE(P, R, 256, ##__VA_ARGS__); else SWT_LANE(P, R, 512, ##__VA_ARGS__); } while (0)
-  if (ordered) {  // list order: the same chunk sizes, every word through ordered_word
-    if (!d_rec) { if (t->packed) SWT_LANE(true, false, kLaneCap, true); else SWT_LANE(false, false, kLaneCap, true); }
-    else if (t->packed) SWT_LANE_CAPS(true, false, true);
-    else SWT_LANE_CAPS(false, false, true);
-    return;
-  }
-  if (!d_rec) {  // running text: the one chunk size the tile was chosen for
-    if (t->packed) { if (t->proper) SWT_LANE(true, true, kLaneCap); else SWT_LANE(true, false, kLaneCap); }
-    else { if (t->proper) SWT_LANE(false, true, kLaneCap); else SWT_LANE(false, false, kLaneCap); }
-    return;
-  }
-  if (t->packed) { if (t->proper) SWT_LANE_CAPS(true, true); else SWT_LANE_CAPS(true, false); }
-  else { if (t->proper) SWT_LANE_CAPS(false, true); else SWT_LANE_CAPS(false, false); }
-#undef SWT_LANE_CAPS
-#undef SWT_LANE
+  const BpeView v = bpe_view(t, ordered);
+  hipLaunchKernelGGL(d_rec ? lane_kernel<1>(t, ordered, cap) : lane_kernel<0>(t, ordered, cap), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text,
+                     n_bytes, d_sent_off, ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
+                     ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
 }
 
 // Tiles per wave of the running-text form: ONE.  Longer spans were measured and lost (profiles/lane_spans.txt: K = 2 costs the
@@ -1142,16 +1128,10 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
   if (n_bytes <= kDirectBytes && n_sent <= kDirectSents) {
     // a sentence or a few: one workgroup, one launch, the caller's arrays written by the kernel (DirectOut)
     if ((rc = ws.reserve(64, 0, 1))) return rc;
-    const DirectOut direct{d_out_off, d_n_tokens, n_sent};
     const BpeView v = bpe_view(t, ordered);
-    auto one_lane = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots, v.sh,
-                         v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
-                         (unsigned long long *)nullptr, (unsigned long long *)nullptr, direct);
-    };
-    if (ordered) { if (t->packed) one_lane(bpe_lane_kernel<true, false, kLaneCap, 2, true>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2, true>); }
-    else if (t->packed) { if (t->proper) one_lane(bpe_lane_kernel<true, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<true, false, kLaneCap, 2>); }
-    else { if (t->proper) one_lane(bpe_lane_kernel<false, true, kLaneCap, 2>); else one_lane(bpe_lane_kernel<false, false, kLaneCap, 2>); }
+    hipLaunchKernelGGL(lane_kernel<2>(t, ordered), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots,
+                       v.sh, v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
+                       (unsigned long long *)nullptr, (unsigned long long *)nullptr, DirectOut{d_out_off, d_n_tokens, n_sent});
     SWT_HIP(hipGetLastError());
     return SWT_OK;
   }
@@ -1232,115 +1212,24 @@ static int bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_by
   return bpe_encode_direct(t, t->ws, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, raw ? nullptr : d_cls, st, ordered);
 }
 
-// text and offsets on the device -> ids, offsets and the count in the caller's host arrays
-static int bpe_encode_to_host(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent,
-                              uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered) {
-  int rc;
-  if ((rc = t->out_ids.reserve((n_bytes + 64) * 4))) return rc;
-  if ((rc = t->out_off.reserve((n_sent + 1) * 8))) return rc;
-  if ((rc = t->n_tok.reserve(8))) return rc;
-  rc = bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->n_tok.as<uint64_t>(),
-                      flags, nullptr, ordered);
-  if (rc) return rc;
-  uint64_t nt = 0;
-  SWT_HIP(hipMemcpy(&nt, t->n_tok.p, 8, hipMemcpyDeviceToHost));
-  *n_tokens = nt;
-  SWT_HIP(hipMemcpy(out_off, t->out_off.p, (n_sent + 1) * 8, hipMemcpyDeviceToHost));
-  if (nt > out_cap)
-    return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-  if (nt) SWT_HIP(hipMemcpy(out_ids, t->out_ids.p, nt * 4, hipMemcpyDeviceToHost));
-  return SWT_OK;
+// What the host-call layer (swt_tile.h) needs to know of this encoder, in either order.
+static HostEncoder bpe_host(swt_bpe_table *t, uint32_t flags, bool ordered) {
+  return HostEncoder{[t] { return bpe_upload(t); },
+                     [t, flags, ordered](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent, uint32_t *d_ids,
+                                         uint64_t *d_out_off, uint8_t *, uint64_t *d_n_tokens) {
+                       return bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, d_ids, d_out_off, d_n_tokens, flags, nullptr, ordered);
+                     },
+                     kDirectBytes, kDirectSents, false};
 }
-
 static int bpe_encode_host(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
                            uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered) {
-  if (!t || !sent_off || !out_off || !n_tokens) return fail(SWT_ERR_INVALID, "null argument");
-  int rc = bpe_upload(t);
-  if (rc) return rc;
-  const uint64_t n_bytes = sent_off[n_sent];
-  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
-  for (uint64_t s = 0; s < n_sent; s++)
-    if (sent_off[s] > sent_off[s + 1])
-      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
-  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
-  if (n_bytes <= kDirectBytes && n_sent <= kDirectSents && n_sent > 0) {
-    // tokenize(text) on one sentence (bpe.py:245): the single workgroup of the direct form reads the text and the offsets from
-    // pinned host memory and writes the count, the offsets and the ids there -- one launch and one synchronisation, no copy
-    // call at all.  Measured: 43.1 -> 40.7 us per call from Python; a launch + hipStreamSynchronize is 11 us here, spinning on
-    // a host word instead would save 4.5 of them (tools/micro/sync_probe.hip), the rest is the kernel's own latency chain
-    // (~10 merge rounds, one L2 probe each) and ctypes.
-    const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15, text_bytes = (n_bytes + 64 + 15) & ~(size_t)15;
-    const size_t out_at = off_bytes + text_bytes;
-    if ((rc = t->pin.reserve(out_at + 16 + off_bytes + (n_bytes + 64) * 4))) return rc;
-    uint8_t *h = t->pin.as<uint8_t>();
-    memcpy(h, sent_off, (n_sent + 1) * 8);
-    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
-    memset(h + off_bytes + n_bytes, ' ', 64);
-    uint8_t *o = h + out_at;
-    rc = bpe_encode_dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent, reinterpret_cast<uint32_t *>(o + 16 + off_bytes),
-                        reinterpret_cast<uint64_t *>(o + 16), reinterpret_cast<uint64_t *>(o), flags, nullptr, ordered);
-    if (rc) return rc;
-    SWT_HIP(hipStreamSynchronize(0));
-    const uint64_t nt = *reinterpret_cast<const volatile uint64_t *>(o);
-    *n_tokens = nt;
-    memcpy(out_off, o + 16, (n_sent + 1) * 8);
-    if (nt > out_cap)
-      return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-    if (nt) memcpy(out_ids, o + 16 + off_bytes, nt * 4);
-    return SWT_OK;
-  }
-  if (n_bytes <= kSmallCallBytes && n_sent <= kSmallCallSents) {
-    // The reference-style call (one sentence, or a few): five small copies and their synchronisations cost more than the
-    // kernels.  Offsets + text go up in ONE copy from pinned memory, token count + offsets + ids come back in ONE.
-    const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15;
-    const size_t in_bytes = off_bytes + n_bytes + 64;
-    const size_t out_bytes = 16 + off_bytes + (n_bytes + 64) * 4;
-    if ((rc = t->pin.reserve(in_bytes > out_bytes ? in_bytes : out_bytes)) || (rc = t->small_in.reserve(in_bytes)) ||
-        (rc = t->small_out.reserve(out_bytes)))
-      return rc;
-    uint8_t *h = t->pin.as<uint8_t>();
-    memcpy(h, sent_off, (n_sent + 1) * 8);
-    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
-    SWT_HIP(hipMemcpyAsync(t->small_in.p, h, off_bytes + n_bytes, hipMemcpyHostToDevice, 0));
-    uint8_t *d_in = t->small_in.as<uint8_t>(), *d_out = t->small_out.as<uint8_t>();
-    rc = bpe_encode_dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
-                        reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
-                        reinterpret_cast<uint64_t *>(d_out), flags, nullptr, ordered);
-    if (rc) return rc;
-    SWT_HIP(hipMemcpyAsync(h, d_out, 16 + off_bytes + (n_bytes + 64) * 4, hipMemcpyDeviceToHost, 0));
-    SWT_HIP(hipStreamSynchronize(0));
-    const uint64_t nt = *reinterpret_cast<const uint64_t *>(h);
-    *n_tokens = nt;
-    memcpy(out_off, h + 16, (n_sent + 1) * 8);
-    if (nt > out_cap)
-      return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-    if (nt) memcpy(out_ids, h + 16 + off_bytes, nt * 4);
-    return SWT_OK;
-  }
-  if ((rc = t->in_text.reserve(n_bytes + 64))) return rc;
-  if ((rc = t->in_off.reserve((n_sent + 1) * 8))) return rc;
-  if (n_bytes) SWT_HIP(hipMemcpyAsync(t->in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
-  SWT_HIP(hipMemcpyAsync(t->in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  return bpe_encode_to_host(t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, n_tokens, flags, ordered);
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  return host_encode(t->stage, bpe_host(t, flags, ordered), text, sent_off, n_sent, out_ids, out_cap, out_off, nullptr, n_tokens);
 }
-
-// list[str] joined with U+0000 -> ids without the prepared text ever coming back to the host (swt_utf8_prepare_joined +
-// swt_bpe_encode in one call).  *n_tokens = UINT64_MAX on return: a sentence needs the host's str.lower() (need_host says
-// which) and nothing was encoded.
 static int bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
                              uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags, bool ordered) {
-  if (!t || !out_off || !n_tokens || (n_sent && !need_host) || (n_joined && !joined)) return fail(SWT_ERR_INVALID, "null argument");
-  int rc = bpe_upload(t);
-  if (rc) return rc;
-  *n_tokens = UINT64_MAX;
-  struct Ctx { swt_bpe_table *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off, *n_tokens; uint32_t flags; bool ordered; };
-  Ctx c{t, n_sent, out_ids, out_cap, out_off, n_tokens, flags, ordered};
-  bool consumed = false;
-  return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
-      [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
-        Ctx *c = static_cast<Ctx *>(p);
-        return bpe_encode_to_host(c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->n_tokens, c->flags, c->ordered);
-      }, &c);
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  return host_encode_joined(t->stage, bpe_host(t, flags, ordered), joined, n_joined, n_sent, out_ids, out_cap, out_off, nullptr, n_tokens, need_host);
 }
 
 extern "C" {

@@ -1,5 +1,7 @@
-// swt_tile.hip -- the skeleton's own kernels: plan (tile -> first sentence), scan of tile totals, gather.
+// swt_tile.hip -- the skeleton's own kernels: plan (tile -> first sentence), scan of tile totals, gather; and the host-call layer
+// of the encoders (host_encode*).
 #include "swt_tile.h"
+#include "swt_words.h"
 
 namespace swt {
 
@@ -223,6 +225,125 @@ void launch_scan_gather(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_
   hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n_tiles + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, d_sent_off, ws.plan.as<uint64_t>(), n_tiles,
                      n_sent, ws.scratch.as<uint32_t>(), ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(),
                      ws.tile_base.as<uint32_t>(), blk_base, d_n_tokens, d_out_ids, d_out_off);
+}
+
+// ---- the host-call layer --------------------------------------------------------------------------------------------
+
+void HostStage::release() {
+  for (DevBuf *b : {&in_text, &in_off, &out_ids, &out_off, &out_status, &n_tok, &small_in, &small_out}) b->release();
+  pin.release();
+}
+
+// A call's results to the caller's arrays: the count, the offsets and the statuses (st, null for none) first, the ids only if
+// they fit.  device: the sources are device buffers (blocking copies); otherwise host memory the device has finished writing.
+static int unpack(const void *count, const void *off, const void *st, const void *ids, bool device, uint64_t n_sent, uint32_t *out_ids,
+                  uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+  const auto get = [device](void *dst, const void *src, size_t n) {
+    if (device) return hipMemcpy(dst, src, n, hipMemcpyDeviceToHost);
+    memcpy(dst, src, n);
+    return hipSuccess;
+  };
+  uint64_t nt = 0;
+  SWT_HIP(get(&nt, count, 8));
+  *n_tokens = nt;
+  SWT_HIP(get(out_off, off, (n_sent + 1) * 8));
+  if (st && n_sent) SWT_HIP(get(status, st, n_sent));
+  if (nt > out_cap)
+    return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
+  if (nt) SWT_HIP(get(out_ids, ids, nt * 4));
+  return SWT_OK;
+}
+
+int host_encode_from_device(HostStage &hs, const HostEncoder &enc, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off,
+                            uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+  int rc;
+  if ((rc = hs.out_ids.reserve((n_bytes + 64) * 4))) return rc;
+  if ((rc = hs.out_off.reserve((n_sent + 1) * 8))) return rc;
+  if (enc.has_status && (rc = hs.out_status.reserve(n_sent + 8))) return rc;
+  if ((rc = hs.n_tok.reserve(8))) return rc;
+  uint8_t *const d_status = enc.has_status ? hs.out_status.as<uint8_t>() : nullptr;
+  if ((rc = enc.dev(d_text, n_bytes, d_off, n_sent, hs.out_ids.as<uint32_t>(), hs.out_off.as<uint64_t>(), d_status, hs.n_tok.as<uint64_t>())))
+    return rc;
+  return unpack(hs.n_tok.p, hs.out_off.p, d_status, hs.out_ids.p, true, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+}
+
+int host_encode(HostStage &hs, const HostEncoder &enc, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+  if (!sent_off || !out_off || !n_tokens || (enc.has_status && n_sent && !status)) return fail(SWT_ERR_INVALID, "null argument");
+  int rc = enc.upload();
+  if (rc) return rc;
+  const uint64_t n_bytes = sent_off[n_sent];
+  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
+  for (uint64_t s = 0; s < n_sent; s++)
+    if (sent_off[s] > sent_off[s + 1])
+      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
+  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
+  // The two small paths move one block each way.  In: the offsets, then the text.  Out: the count at 0, the offsets at 16, the
+  // statuses behind them, the ids last -- every part at a multiple of 16.
+  const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15, st_bytes = enc.has_status ? (n_sent + 15) & ~(size_t)15 : 0;
+  const size_t st_at = 16 + off_bytes, ids_at = st_at + st_bytes, out_bytes = ids_at + (n_bytes + 64) * 4;
+  const auto encode = [&](const uint8_t *in, uint8_t *o) {
+    return enc.dev(in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(in), n_sent, reinterpret_cast<uint32_t *>(o + ids_at),
+                   reinterpret_cast<uint64_t *>(o + 16), enc.has_status ? o + st_at : nullptr, reinterpret_cast<uint64_t *>(o));
+  };
+  const auto unpack_block = [&](const uint8_t *o) {
+    return unpack(o, o + 16, enc.has_status ? o + st_at : nullptr, o + ids_at, false, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+  };
+  if (n_bytes <= enc.direct_bytes && n_sent <= enc.direct_sents && n_sent > 0) {
+    // tokenize(text) on one sentence, the reference's call: the single workgroup of the direct form reads the text and the
+    // offsets from pinned host memory and writes the out block there -- one launch and one synchronisation, no copy call at all.
+    // Measured (FastBPE): 43.1 -> 40.7 us per call from Python; a launch + hipStreamSynchronize is 11 us here, spinning on a host
+    // word instead would save 4.5 of them (tools/micro/sync_probe.hip), the rest is the kernel's own latency chain and ctypes.
+    // By size alone: FastWP under SWT_OPT_DEDUP = 2 runs its dedup pipeline over this pinned memory.
+    const size_t out_at = off_bytes + ((n_bytes + 64 + 15) & ~(size_t)15);
+    if ((rc = hs.pin.reserve(out_at + out_bytes))) return rc;
+    uint8_t *h = hs.pin.as<uint8_t>();
+    memcpy(h, sent_off, (n_sent + 1) * 8);
+    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
+    memset(h + off_bytes + n_bytes, ' ', 64);
+    if ((rc = encode(h, h + out_at))) return rc;
+    SWT_HIP(hipStreamSynchronize(0));
+    return unpack_block(h + out_at);
+  }
+  if (n_bytes <= kSmallCallBytes && n_sent <= kSmallCallSents) {
+    // A few sentences: five small copies and their synchronisations cost more than the kernels.  The in block goes up in ONE
+    // copy from pinned memory, the out block comes back in ONE.
+    const size_t in_bytes = off_bytes + n_bytes + 64;
+    if ((rc = hs.pin.reserve(in_bytes > out_bytes ? in_bytes : out_bytes)) || (rc = hs.small_in.reserve(in_bytes)) ||
+        (rc = hs.small_out.reserve(out_bytes)))
+      return rc;
+    uint8_t *h = hs.pin.as<uint8_t>();
+    memcpy(h, sent_off, (n_sent + 1) * 8);
+    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
+    SWT_HIP(hipMemcpyAsync(hs.small_in.p, h, off_bytes + n_bytes, hipMemcpyHostToDevice, 0));
+    if ((rc = encode(hs.small_in.as<uint8_t>(), hs.small_out.as<uint8_t>()))) return rc;
+    SWT_HIP(hipMemcpyAsync(h, hs.small_out.p, out_bytes, hipMemcpyDeviceToHost, 0));
+    SWT_HIP(hipStreamSynchronize(0));
+    return unpack_block(h);
+  }
+  if ((rc = hs.in_text.reserve(n_bytes + 64))) return rc;
+  if ((rc = hs.in_off.reserve((n_sent + 1) * 8))) return rc;
+  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
+  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
+  return host_encode_from_device(hs, enc, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off,
+                                 status, n_tokens);
+}
+
+int host_encode_joined(HostStage &hs, const HostEncoder &enc, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent,
+                       uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) {
+  if (!out_off || !n_tokens || (n_sent && (!need_host || (enc.has_status && !status))) || (n_joined && !joined))
+    return fail(SWT_ERR_INVALID, "null argument");
+  int rc = enc.upload();
+  if (rc) return rc;
+  *n_tokens = UINT64_MAX;
+  auto consume = [&](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
+    return host_encode_from_device(hs, enc, d_text, n_bytes, d_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+  };
+  using Consume = decltype(consume);
+  bool consumed = false;
+  return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
+      [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) { return (*static_cast<Consume *>(p))(d_text, n_bytes, d_off); },
+      &consume);
 }
 
 }  // namespace swt

@@ -169,32 +169,239 @@ constexpr uint64_t kWpDirectBytes = 2048, kWpDirectSents = 64;  // up to here on
 constexpr uint32_t kWpUTile = 256;       // smallest tile of the encode over the unique chunks (dedup path)
 constexpr uint64_t kWpUMaxTiles = 8192;  // its fixed launch size
 
+// ======================================================================================================================
+// The tile skeleton of the two WordPiece kernels (wp_encode_kernel, wp_naive_kernel): one 64-lane wavefront per tile
+// (workgroup = one wave), the tile's span walked in chunks of kWpCap staged bytes that end at sentence starts.  Written once:
+//   wp_tile_begin   the tile's sentences and span, the LDS copy of the first 1,024 classes
+//   wp_stage        A: the chunk's bytes into LDS
+//   wp_mark         sentence starts -> sbits; where the chunk ends (false: one sentence is longer than the staged bytes)
+//   wp_giant        that sentence, by one lane in global memory with the kernel's one-lane walker
+//   wp_emit         E/F: ballot compaction of tok[] to the tile's output run, per-sentence offsets
+//   wp_tile_end     the tile's total (or the caller's closing offset and count, DirectOut)
+// B (classes -> candidates), C (one lane per candidate or word) and D (per-sentence status) are the kernels' own.
 struct WpGiant { uint64_t end; uint32_t ntok; uint32_t nsent; };
 
-struct WpLds {
-  __attribute__((aligned(16))) uint8_t txt[kWpCap + 16];
+// What both kernels keep in LDS; each puts its own masks behind it.  txt and cls_lo are moved 16 bytes at a time: they stand at
+// multiples of 16 here, and the structs that begin with this one are aligned to 16.
+struct WpTileLds {
+  uint8_t txt[kWpCap + 16];
+  uint8_t cls_lo[kWpClsLds];
   uint32_t tok[kWpCap];                      // per byte position: a token id or kInvalidTok
-  uint16_t cand[kWpCap];                     // segment-start candidates, in position order
+  uint16_t cand[kWpCap];                     // segment-start candidates / word starts, in position order
   unsigned long long sbits[kWpBlocks + 1];   // sentence-start bit per byte
-  unsigned long long ppunc[kWpBlocks + 1];   // the char before this byte (same sentence) is punctuation-class
-  unsigned long long irr[kWpBlocks + 1];     // per sentence-start position: needs the sequential walk
   unsigned long long vmask[kWpBlocks + 1];
-  uint32_t blkpre[kWpBlocks + 1];
-  __attribute__((aligned(16))) uint8_t cls_lo[kWpClsLds];
   WpGiant giant;
+  uint32_t blkpre[kWpBlocks + 1];
+};
+static_assert((kWpCap + 16) % 16 == 0, "cls_lo must stand at a multiple of 16");
+
+// What a wave carries from chunk to chunk of its tile, and what it knows about the chunk at hand.
+struct WpTile {
+  uint64_t s_hi;       // end of the tile's sentences
+  uint64_t span_end;   // end of their bytes
+  uint64_t s_next;     // first sentence whose local offset is not recorded yet
+  uint64_t cb;         // first byte not encoded yet
+  uint32_t *tile_out;  // the tile's run in scratch
+  uint32_t run;        // tokens emitted so far
+};
+struct WpChunk {
+  uint64_t abase;               // 16-byte aligned base of the staged bytes
+  uint32_t off0, staged, nblk;  // first byte of the chunk inside the staged bytes, staged bytes, 64-byte blocks
+  uint32_t ce;                  // end of the chunk: a sentence start, or staged
+  bool last;                    // the tile ends with this chunk
+};
+// where a tile's per-sentence results go
+struct WpOut {
+  uint32_t *sent_local;
+  uint8_t *status;
+  DirectOut direct;
+  __device__ __forceinline__ void off(uint64_t s, uint32_t v) const {
+    if (direct.off) direct.off[s] = v; else sent_local[s] = v;
+  }
 };
 
 __device__ __forceinline__ bool wbit(const unsigned long long *m, uint32_t p) { return (m[p >> 6] >> (p & 63)) & 1ull; }
 
-// One 64-lane wavefront per tile (workgroup = one wave).  Segments of a sentence depend on each other only through
-// where the previous one ended (wordpiece.py:265-269), and that is almost always the next static boundary.  So:
+// False: the tile holds no sentence (its total is written, the wave is done).
+__device__ __forceinline__ bool wp_tile_begin(WpTileLds &L, WpTile &tile, const uint64_t *__restrict__ sent_off,
+                                              const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab,
+                                              uint32_t *__restrict__ scratch, uint32_t *__restrict__ tile_tok, const DirectOut &direct,
+                                              int lane) {
+  const uint64_t t = blockIdx.x;
+  const uint64_t s_lo = direct.off ? 0 : plan[t];
+  tile.s_hi = direct.off ? direct.n_sent : plan[t + 1];
+  if (s_lo == tile.s_hi) {
+    if (lane == 0) tile_tok[t] = 0;
+    return false;
+  }
+  reinterpret_cast<uint4 *>(L.cls_lo)[lane] = reinterpret_cast<const uint4 *>(cls_tab)[lane];
+  const uint64_t span_base = sent_off[s_lo];
+  tile.span_end = sent_off[tile.s_hi];
+  tile.tile_out = scratch + span_base;
+  tile.run = 0;
+  tile.s_next = s_lo;
+  tile.cb = span_base;
+  return true;
+}
+
+// ---- A. stage [abase, abase + staged), clear the sentence-start bits.  The caller clears its own masks and synchronises.
+__device__ __forceinline__ void wp_stage(WpTileLds &L, const WpTile &tile, WpChunk &ch, const uint8_t *__restrict__ text, uint64_t n_bytes,
+                                         int lane) {
+  ch.abase = tile.cb & ~15ull;
+  ch.off0 = (uint32_t)(tile.cb - ch.abase);
+  const uint64_t avail = tile.span_end - ch.abase;
+  ch.last = avail <= (uint64_t)kWpCap;
+  ch.staged = ch.last ? (uint32_t)avail : (uint32_t)kWpCap;
+  ch.nblk = (ch.staged + 63) >> 6;
+  for (uint32_t c = lane * 16; c < ch.staged; c += 64 * 16) {
+    const uint64_t g = ch.abase + c;
+    if (g + 16 <= n_bytes && ((reinterpret_cast<uintptr_t>(text + g) & 15) == 0)) {
+      *reinterpret_cast<uint4 *>(&L.txt[c]) = *reinterpret_cast<const uint4 *>(text + g);
+    } else {
+      for (int i = 0; i < 16; i++) L.txt[c + i] = (g + i < n_bytes) ? text[g + i] : (uint8_t)' ';
+    }
+  }
+  if (lane <= kWpBlocks) L.sbits[lane] = 0ull;
+}
+
+// Sentence starts inside the staged bytes -> sbits; the chunk ends at the last one that leaves its predecessor whole (ch.ce).
+// False: there is none, one sentence is longer than the LDS chunk (wp_giant).
+__device__ __forceinline__ bool wp_mark(WpTileLds &L, const WpTile &tile, WpChunk &ch, const uint64_t *__restrict__ sent_off, int lane) {
+  int cut = -1;
+  uint32_t n_in = 0;  // sentences starting in [cb, abase + staged)
+  for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+    const uint64_t o = sent_off[s];
+    if (o >= ch.abase + ch.staged) break;
+    atomicOr(&L.sbits[(o - ch.abase) >> 6], 1ull << ((o - ch.abase) & 63));
+    if (o > tile.cb) cut = (int)(o - ch.abase);
+    n_in++;
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    cut = max(cut, __shfl_xor(cut, d));
+    n_in += __shfl_xor(n_in, d);
+  }
+  __syncthreads();
+  ch.ce = ch.staged;
+  if (ch.last) return true;
+  // does a sentence start exactly at the end of the staged bytes?  then everything staged is whole
+  const uint64_t s_after = tile.s_next + n_in;
+  if (s_after < tile.s_hi && sent_off[s_after] == ch.abase + ch.staged) return true;
+  if (cut < 0) return false;
+  ch.ce = (uint32_t)cut;
+  return true;
+}
+
+// One sentence longer than the LDS chunk: lane 0 walks it in global memory (walk(b, e, out, status) -> token count).  The empty
+// sentences that also start at cb come first and get no tokens and `empty_status`.  True: the tile ends with it.
+template <class Walk>
+__device__ __forceinline__ bool wp_giant(WpTileLds &L, WpTile &tile, const uint64_t *__restrict__ sent_off, const WpOut &out,
+                                         uint32_t empty_status, Walk walk, int lane) {
+  if (lane == 0) {
+    uint64_t s = tile.s_next;
+    while (s + 1 < tile.s_hi && sent_off[s + 1] <= tile.cb) s++;  // the last sentence that starts at cb
+    int stt;
+    const uint64_t e = sent_off[s + 1];
+    const uint32_t n = walk(tile.cb, e, tile.tile_out + tile.run, stt);
+    for (uint64_t z = tile.s_next; z <= s; z++) {
+      out.off(z, tile.run);
+      out.status[z] = (uint8_t)empty_status;
+    }
+    out.status[s] = (uint8_t)stt;
+    L.giant.end = e;
+    L.giant.ntok = n;
+    L.giant.nsent = (uint32_t)(s - tile.s_next + 1);
+  }
+  __syncthreads();
+  tile.s_next += L.giant.nsent;
+  tile.run += L.giant.ntok;
+  tile.cb = L.giant.end;
+  __syncthreads();
+  if (tile.cb < tile.span_end) return false;
+  // trailing empty sentences at the very end of the span
+  for (uint64_t z = tile.s_next + lane; z < tile.s_hi; z += 64) {
+    out.off(z, tile.run);
+    out.status[z] = (uint8_t)empty_status;
+  }
+  return true;
+}
+
+// Byte p of the chunk as phase B sees it: inside the chunk (outside counts as a space), a lead byte, its code point (a
+// sequence is clipped at the chunk's end).
+__device__ __forceinline__ uint32_t wp_decode(const WpTileLds &L, const WpChunk &ch, uint32_t p, bool &inr, bool &lead) {
+  inr = p >= ch.off0 && p < ch.ce;
+  const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
+  lead = !utf8_is_cont(b);
+  uint32_t cp = b;
+  if (b >= 0xC0) {
+    int len = utf8_len(b);
+    if (p + len > ch.ce) len = (int)(ch.ce - p);
+    if (len > 1) {
+      cp = b & (0xFF >> (len + 1));
+      for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
+    }
+  }
+  return cp;
+}
+
+// the start of the sentence around byte p0 of the chunk
+__device__ __forceinline__ uint32_t wp_sentence_start(const WpTileLds &L, const WpChunk &ch, uint32_t p0) {
+  int w = (int)(p0 >> 6);
+  unsigned long long m = L.sbits[w] & ((2ull << (p0 & 63)) - 1ull);
+  while (!m && w > 0) m = L.sbits[--w];
+  return m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : ch.off0;
+}
+
+// ---- E. compaction, F. sentence offsets.  Advances the tile; true: that was its last chunk.
+__device__ __forceinline__ bool wp_emit(WpTileLds &L, WpTile &tile, const WpChunk &ch, const uint64_t *__restrict__ sent_off,
+                                        const WpOut &out, int lane) {
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  uint32_t total = 0;
+  for (uint32_t blk = 0; blk < ch.nblk; blk++) {
+    const uint32_t p = blk * 64 + lane;
+    const uint32_t sv = (p >= ch.off0 && p < ch.ce) ? L.tok[p] : kInvalidTok;
+    const unsigned long long m = __ballot(sv != kInvalidTok);
+    if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
+    if (sv != kInvalidTok) tile.tile_out[tile.run + total + __popcll(m & lt)] = sv;
+    total += __popcll(m);
+  }
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+    const uint64_t rel = sent_off[s] - ch.abase;
+    if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+    uint32_t ex = total;
+    if (rel < ch.ce && (rel >> 6) < ch.nblk) ex = L.blkpre[rel >> 6] + __popcll(L.vmask[rel >> 6] & ((1ull << (rel & 63)) - 1ull));
+    out.off(s, tile.run + ex);
+    mine++;
+  }
+  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+  tile.s_next += mine;
+  tile.run += total;
+  if (ch.last) return true;
+  tile.cb = ch.abase + ch.ce;
+  __syncthreads();
+  return false;
+}
+
+__device__ __forceinline__ void wp_tile_end(const WpTile &tile, uint32_t *__restrict__ tile_tok, const DirectOut &direct, int lane) {
+  if (lane != 0) return;
+  if (direct.off) { direct.off[tile.s_hi] = tile.run; *direct.n_tokens = tile.run; }
+  else tile_tok[blockIdx.x] = tile.run;
+}
+
+struct alignas(16) WpLds : WpTileLds {
+  unsigned long long ppunc[kWpBlocks + 1];   // the char before this byte (same sentence) is punctuation-class
+  unsigned long long irr[kWpBlocks + 1];     // per sentence-start position: needs the sequential walk
+};
+
+// The skeleton above with these phases.  Segments of a sentence depend on each other only through where the previous one
+// ended (wordpiece.py:265-269), and that is almost always the next static boundary.  So:
 //   B  64 bytes per step: classes (str.isspace / str.isalnum) -> ballot masks -> the positions where a segment CAN
 //      start (sentence start; a non-space char after a space; either side of a punctuation-class char)
 //   C  one lane per candidate walks the trie from there (matchloop + validity + skip), writing its tokens into its own
 //      territory [candidate, next candidate); it certifies itself when it ended exactly at the next candidate
 //   D  a sentence with an uncertified candidate (a vocabulary entry spanning a boundary, a non-terminating or raising
 //      input) is redone by one lane with the sequential walker -- exactness never rests on the speculation
-//   E/F  ballot compaction to the tile's output run, per-sentence offsets and statuses
 __global__ __launch_bounds__(64) void wp_encode_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpDev T, uint32_t *__restrict__ scratch,
@@ -202,114 +409,30 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
   __shared__ WpLds L;
   const int lane = threadIdx.x;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  const uint64_t t = blockIdx.x;
-  const uint64_t s_lo = direct.off ? 0 : plan[t], s_hi = direct.off ? direct.n_sent : plan[t + 1];
-  if (s_lo == s_hi) {
-    if (lane == 0) tile_tok[t] = 0;
-    return;
-  }
-  reinterpret_cast<uint4 *>(L.cls_lo)[lane] = reinterpret_cast<const uint4 *>(cls_tab)[lane];
-  const uint64_t span_base = sent_off[s_lo], span_end = sent_off[s_hi];
-  uint32_t *const tile_out = scratch + span_base;
-  uint32_t run = 0;
-  uint64_t s_next = s_lo;
-  uint64_t cb = span_base;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
+  const WpOut out{sent_local, status, direct};
 
   for (;;) {
-    const uint64_t abase = cb & ~15ull;
-    const uint32_t off0 = (uint32_t)(cb - abase);
-    const uint64_t avail = span_end - abase;
-    const bool last = avail <= (uint64_t)kWpCap;
-    const uint32_t staged = last ? (uint32_t)avail : (uint32_t)kWpCap;
-    const uint32_t nblk = (staged + 63) >> 6;
-
-    // ---- A. stage
-    for (uint32_t c = lane * 16; c < staged; c += 64 * 16) {
-      const uint64_t g = abase + c;
-      if (g + 16 <= n_bytes && ((reinterpret_cast<uintptr_t>(text + g) & 15) == 0)) {
-        *reinterpret_cast<uint4 *>(&L.txt[c]) = *reinterpret_cast<const uint4 *>(text + g);
-      } else {
-        for (int i = 0; i < 16; i++) L.txt[c + i] = (g + i < n_bytes) ? text[g + i] : (uint8_t)' ';
-      }
-    }
-    if (lane <= kWpBlocks) { L.sbits[lane] = 0ull; L.irr[lane] = 0ull; }
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    if (lane <= kWpBlocks) L.irr[lane] = 0ull;
     __syncthreads();
-    // sentence starts inside the staged bytes; the chunk ends at the last one that leaves its predecessor whole
-    int cut = -1;
-    uint32_t n_in = 0;  // sentences starting in [cb, abase + staged)
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t o = sent_off[s];
-      if (o >= abase + staged) break;
-      atomicOr(&L.sbits[(o - abase) >> 6], 1ull << ((o - abase) & 63));
-      if (o > cb) cut = (int)(o - abase);
-      n_in++;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-      cut = max(cut, __shfl_xor(cut, d));
-      n_in += __shfl_xor(n_in, d);
-    }
-    __syncthreads();
-
-    uint32_t ce = staged;
-    if (!last) {
-      // does a sentence start exactly at the end of the staged bytes?  then everything staged is whole
-      uint64_t s_after = s_next + n_in;
-      const bool whole = s_after < s_hi && sent_off[s_after] == abase + staged;
-      if (whole) ce = staged;
-      else if (cut >= 0) ce = (uint32_t)cut;
-      else {
-        // one sentence longer than the LDS chunk: one lane walks it in global memory
-        if (lane == 0) {
-          uint64_t s = s_next;
-          while (s + 1 < s_hi && sent_off[s + 1] <= cb) s++;  // the last sentence that starts at cb
-          int stt;
-          TxtSrc src{text, nullptr, cls_tab};
-          const uint64_t e = sent_off[s + 1];
-          const uint32_t n = wp_sentence(src, cb, e, tile_out + run, T, stt);
-          // empty sentences that also start at cb come first and get no tokens
-          for (uint64_t z = s_next; z <= s; z++) {
-            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
-            status[z] = (uint8_t)T.empty_status;
-          }
-          status[s] = (uint8_t)stt;
-          L.giant.end = e;
-          L.giant.ntok = n;
-          L.giant.nsent = (uint32_t)(s - s_next + 1);
-        }
-        __syncthreads();
-        s_next += L.giant.nsent;
-        run += L.giant.ntok;
-        cb = L.giant.end;
-        __syncthreads();
-        if (cb >= span_end) {
-          // trailing empty sentences at the very end of the span
-          for (uint64_t z = s_next + lane; z < s_hi; z += 64) {
-            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
-            status[z] = (uint8_t)T.empty_status;
-          }
-          break;
-        }
-        continue;
-      }
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt) {
+        return wp_sentence(TxtSrc{text, nullptr, cls_tab}, b, e, o, T, stt);
+      };
+      if (wp_giant(L, tile, sent_off, out, T.empty_status, walk, lane)) break;
+      continue;
     }
 
     // ---- B. classes -> masks -> candidates
     uint32_t nc = 0;
     bool prev_sp = true, prev_pu = false;  // class of the char owning the byte before this block
-    for (uint32_t blk = 0; blk < nblk; blk++) {
+    for (uint32_t blk = 0; blk < ch.nblk; blk++) {
       const uint32_t p = blk * 64 + lane;
-      const bool inr = p >= off0 && p < ce;
-      const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
-      const bool lead = !utf8_is_cont(b);
-      uint32_t cp = b;
-      if (b >= 0xC0) {
-        int len = utf8_len(b);
-        if (p + len > ce) len = (int)(ce - p);
-        if (len > 1) {
-          cp = b & (0xFF >> (len + 1));
-          for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
-        }
-      }
+      bool inr, lead;
+      const uint32_t cp = wp_decode(L, ch, p, inr, lead);
       uint8_t c = SWT_CLS_PY_SPACE;  // bytes outside the chunk behave as spaces
       if (inr && lead) c = cp < (uint32_t)kWpClsLds ? L.cls_lo[cp] : (cp < kNumCodePoints ? cls_tab[cp] : (uint8_t)0);
       const unsigned long long INR = __ballot(inr);
@@ -339,17 +462,14 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
     for (uint32_t k = lane; k < nc; k += 64) {
       const uint32_t p0 = L.cand[k];
       // the sentence around p0: [s0, e)
-      uint32_t s0, e;
+      const uint32_t s0 = wp_sentence_start(L, ch, p0);
+      uint32_t e;
       {
         int w = (int)(p0 >> 6);
-        unsigned long long m = L.sbits[w] & ((2ull << (p0 & 63)) - 1ull);
-        while (!m && w > 0) m = L.sbits[--w];
-        s0 = m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : off0;
-        w = (int)(p0 >> 6);
-        m = (p0 & 63) == 63 ? 0ull : (L.sbits[w] & ~((2ull << (p0 & 63)) - 1ull));
-        while (!m && w + 1 < (int)nblk) m = L.sbits[++w];
-        e = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ce;
-        if (e > ce) e = ce;
+        unsigned long long m = (p0 & 63) == 63 ? 0ull : (L.sbits[w] & ~((2ull << (p0 & 63)) - 1ull));
+        while (!m && w + 1 < (int)ch.nblk) m = L.sbits[++w];
+        e = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ch.ce;
+        if (e > ch.ce) e = ch.ce;
       }
       const bool has_succ = k + 1 < nc && L.cand[k + 1] < e;
       const uint32_t terr_end = has_succ ? L.cand[k + 1] : e;
@@ -363,18 +483,16 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
     __syncthreads();
 
     // ---- D. per sentence: status; the sequential walk where the speculation was not certified
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t o = sent_off[s];
-      const uint64_t rel = o - abase;
-      if (rel > ce || (rel == ce && !last)) break;
-      const uint64_t e = sent_off[s + 1] - abase;  // <= ce: chunks end at sentence starts
+    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+      const uint64_t rel = sent_off[s] - ch.abase;
+      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+      const uint64_t e = sent_off[s + 1] - ch.abase;  // <= ce: chunks end at sentence starts
       int stt = T.empty_status;
       if (rel < e) {
         stt = SWT_WP_OK;
         if (wbit(L.irr, (uint32_t)rel)) {
           TxtSrc src{L.txt, L.cls_lo, cls_tab};
-          // tokens are staged in the global output run first (the territory array still feeds no one, but the walker
-          // must not overwrite text it has not read: it only reads L.txt, so L.tok is free to take them)
+          // the walker only reads L.txt, so the sentence's own bytes of L.tok are free to take its tokens
           const uint32_t n = wp_sentence(src, rel, e, &L.tok[rel], T, stt);
           for (uint64_t q = rel + n; q < e; q++) L.tok[q] = kInvalidTok;
         }
@@ -383,37 +501,9 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
     }
     __syncthreads();
 
-    // ---- E. compaction, F. sentence offsets
-    uint32_t total = 0;
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-      const uint32_t p = blk * 64 + lane;
-      const uint32_t sv = (p >= off0 && p < ce) ? L.tok[p] : kInvalidTok;
-      const unsigned long long m = __ballot(sv != kInvalidTok);
-      if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
-      if (sv != kInvalidTok) tile_out[run + total + __popcll(m & lt)] = sv;
-      total += __popcll(m);
-    }
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t rel = sent_off[s] - abase;
-      if (rel > ce || (rel == ce && !last)) break;
-      uint32_t ex = total;
-      if (rel < ce && (rel >> 6) < nblk) ex = L.blkpre[rel >> 6] + __popcll(L.vmask[rel >> 6] & ((1ull << (rel & 63)) - 1ull));
-      if (direct.off) direct.off[s] = run + ex; else sent_local[s] = run + ex;
-      mine++;
-    }
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-    s_next += mine;
-    run += total;
-    if (last) break;
-    cb = abase + ce;
-    __syncthreads();
+    if (wp_emit(L, tile, ch, sent_off, out, lane)) break;
   }
-  if (lane == 0) {
-    if (direct.off) { direct.off[s_hi] = run; *direct.n_tokens = run; }
-    else tile_tok[t] = run;
-  }
+  wp_tile_end(tile, tile_tok, direct, lane);
 }
 
 // ---- host: trie build (utils.py:75-139) and flattening -------------------------------------------
@@ -654,27 +744,18 @@ __device__ uint32_t naive_sentence(const uint8_t *txt, const uint8_t *cls_tab, u
   return nt;
 }
 
-struct WpNaiveLds {
-  __attribute__((aligned(16))) uint8_t txt[kWpCap + 16];
-  uint32_t tok[kWpCap];                      // per byte position: a token id or kInvalidTok
-  uint16_t cand[kWpCap];                     // word starts, in position order
-  unsigned long long sbits[kWpBlocks + 1];   // sentence-start bit per byte
+struct alignas(16) WpNaiveLds : WpTileLds {
   unsigned long long stop[kWpBlocks + 1];    // a word ends before this byte: white space, punctuation, a sentence start, outside
   unsigned long long pbits[kWpBlocks + 1];   // a punctuation character (a word of its own) starts here
   unsigned long long nonterm[kWpBlocks + 1]; // per sentence-start position: a word of the sentence never returns
-  unsigned long long vmask[kWpBlocks + 1];
-  uint32_t blkpre[kWpBlocks + 1];
-  __attribute__((aligned(16))) uint8_t cls_lo[kWpClsLds];
-  WpGiant giant;
 };
 
-// One 64-lane wavefront per tile, the skeleton of wp_encode_kernel (swt_tile.h).  Word boundaries do not depend on the
+// The skeleton of wp_encode_kernel (wp_tile_begin .. wp_tile_end) with these phases.  Word boundaries do not depend on the
 // vocabulary here, so there is nothing to speculate about:
 //   B  64 bytes per step: BERT white-space / punctuation ballots -> word starts and word ends
 //   C  one lane per word runs the MaxMatch walk, writing its ids into the word's own bytes of tok[] (a terminating word of n
 //      bytes has at most n tokens: swt_wp_encode_naive_dev refuses the vocabularies for which that does not hold)
 //   D  a sentence with a word that never returns gets status SWT_WP_NONTERMINATING and no tokens
-//   E/F  ballot compaction to the tile's output run, per-sentence offsets
 __global__ __launch_bounds__(64) void wp_naive_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpNaiveDev N, uint32_t *__restrict__ scratch,
@@ -682,109 +763,28 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
   __shared__ WpNaiveLds L;
   const int lane = threadIdx.x;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  const uint64_t t = blockIdx.x;
-  const uint64_t s_lo = direct.off ? 0 : plan[t], s_hi = direct.off ? direct.n_sent : plan[t + 1];
-  if (s_lo == s_hi) {
-    if (lane == 0) tile_tok[t] = 0;
-    return;
-  }
-  reinterpret_cast<uint4 *>(L.cls_lo)[lane] = reinterpret_cast<const uint4 *>(cls_tab)[lane];
-  const uint64_t span_base = sent_off[s_lo], span_end = sent_off[s_hi];
-  uint32_t *const tile_out = scratch + span_base;
-  uint32_t run = 0;
-  uint64_t s_next = s_lo;
-  uint64_t cb = span_base;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
+  const WpOut out{sent_local, status, direct};
 
   for (;;) {
-    const uint64_t abase = cb & ~15ull;
-    const uint32_t off0 = (uint32_t)(cb - abase);
-    const uint64_t avail = span_end - abase;
-    const bool last = avail <= (uint64_t)kWpCap;
-    const uint32_t staged = last ? (uint32_t)avail : (uint32_t)kWpCap;
-    const uint32_t nblk = (staged + 63) >> 6;
-
-    // ---- A. stage
-    for (uint32_t c = lane * 16; c < staged; c += 64 * 16) {
-      const uint64_t g = abase + c;
-      if (g + 16 <= n_bytes && ((reinterpret_cast<uintptr_t>(text + g) & 15) == 0)) {
-        *reinterpret_cast<uint4 *>(&L.txt[c]) = *reinterpret_cast<const uint4 *>(text + g);
-      } else {
-        for (int i = 0; i < 16; i++) L.txt[c + i] = (g + i < n_bytes) ? text[g + i] : (uint8_t)' ';
-      }
-    }
-    if (lane <= kWpBlocks) { L.sbits[lane] = 0ull; L.nonterm[lane] = 0ull; }
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    if (lane <= kWpBlocks) L.nonterm[lane] = 0ull;
     __syncthreads();
-    int cut = -1;
-    uint32_t n_in = 0;
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t o = sent_off[s];
-      if (o >= abase + staged) break;
-      atomicOr(&L.sbits[(o - abase) >> 6], 1ull << ((o - abase) & 63));
-      if (o > cb) cut = (int)(o - abase);
-      n_in++;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-      cut = max(cut, __shfl_xor(cut, d));
-      n_in += __shfl_xor(n_in, d);
-    }
-    __syncthreads();
-
-    uint32_t ce = staged;
-    if (!last) {
-      uint64_t s_after = s_next + n_in;
-      const bool whole = s_after < s_hi && sent_off[s_after] == abase + staged;
-      if (whole) ce = staged;
-      else if (cut >= 0) ce = (uint32_t)cut;
-      else {
-        // one sentence longer than the LDS chunk: one lane walks it in global memory
-        if (lane == 0) {
-          uint64_t s = s_next;
-          while (s + 1 < s_hi && sent_off[s + 1] <= cb) s++;
-          int stt;
-          const uint64_t e = sent_off[s + 1];
-          const uint32_t n = naive_sentence(text, cls_tab, cb, e, tile_out + run, N, stt);
-          for (uint64_t z = s_next; z <= s; z++) {
-            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
-            status[z] = SWT_WP_OK;
-          }
-          status[s] = (uint8_t)stt;
-          L.giant.end = e;
-          L.giant.ntok = n;
-          L.giant.nsent = (uint32_t)(s - s_next + 1);
-        }
-        __syncthreads();
-        s_next += L.giant.nsent;
-        run += L.giant.ntok;
-        cb = L.giant.end;
-        __syncthreads();
-        if (cb >= span_end) {
-          for (uint64_t z = s_next + lane; z < s_hi; z += 64) {
-            if (direct.off) direct.off[z] = run; else sent_local[z] = run;
-            status[z] = SWT_WP_OK;
-          }
-          break;
-        }
-        continue;
-      }
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt) { return naive_sentence(text, cls_tab, b, e, o, N, stt); };
+      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
+      continue;
     }
 
     // ---- B. classes -> word starts and ends
     uint32_t nc = 0;
     bool prev_stop = true;  // the char owning the byte before this block is white space or punctuation
-    for (uint32_t blk = 0; blk < nblk; blk++) {
+    for (uint32_t blk = 0; blk < ch.nblk; blk++) {
       const uint32_t p = blk * 64 + lane;
-      const bool inr = p >= off0 && p < ce;
-      const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
-      const bool lead = !utf8_is_cont(b);
-      uint32_t cp = b;
-      if (b >= 0xC0) {
-        int len = utf8_len(b);
-        if (p + len > ce) len = (int)(ce - p);
-        if (len > 1) {
-          cp = b & (0xFF >> (len + 1));
-          for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
-        }
-      }
+      bool inr, lead;
+      const uint32_t cp = wp_decode(L, ch, p, inr, lead);
       uint8_t c = SWT_CLS_BERT_WS;  // bytes outside the chunk behave as white space
       if (inr && lead) c = cp < (uint32_t)kWpClsLds ? (uint8_t)(L.cls_lo[cp] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)) : bert_class(cls_tab, cp);
       const unsigned long long INR = __ballot(inr);
@@ -811,32 +811,28 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
       uint32_t we;
       if (wbit(L.pbits, p0)) {
         we = p0 + 1;
-        while (we < ce && utf8_is_cont(L.txt[we])) we++;
+        while (we < ch.ce && utf8_is_cont(L.txt[we])) we++;
       } else {
         int w = (int)(p0 >> 6);
         unsigned long long m = (p0 & 63) == 63 ? 0ull : (L.stop[w] & ~((2ull << (p0 & 63)) - 1ull));
-        while (!m && w + 1 < (int)nblk) m = L.stop[++w];
-        we = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ce;
-        if (we > ce) we = ce;
+        while (!m && w + 1 < (int)ch.nblk) m = L.stop[++w];
+        we = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ch.ce;
+        if (we > ch.ce) we = ch.ce;
       }
       bool nt_word = false;
       naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word);
       if (nt_word) {
-        int w = (int)(p0 >> 6);
-        unsigned long long m = L.sbits[w] & ((2ull << (p0 & 63)) - 1ull);
-        while (!m && w > 0) m = L.sbits[--w];
-        const uint32_t s0 = m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : off0;
+        const uint32_t s0 = wp_sentence_start(L, ch, p0);
         atomicOr(&L.nonterm[s0 >> 6], 1ull << (s0 & 63));
       }
     }
     __syncthreads();
 
     // ---- D. per sentence: status; a sentence that never returns keeps no tokens
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t o = sent_off[s];
-      const uint64_t rel = o - abase;
-      if (rel > ce || (rel == ce && !last)) break;
-      const uint64_t e = sent_off[s + 1] - abase;
+    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+      const uint64_t rel = sent_off[s] - ch.abase;
+      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+      const uint64_t e = sent_off[s + 1] - ch.abase;
       int stt = SWT_WP_OK;
       if (rel < e && wbit(L.nonterm, (uint32_t)rel)) {
         stt = SWT_WP_NONTERMINATING;
@@ -846,37 +842,9 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
     }
     __syncthreads();
 
-    // ---- E. compaction, F. sentence offsets
-    uint32_t total = 0;
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-      const uint32_t p = blk * 64 + lane;
-      const uint32_t sv = (p >= off0 && p < ce) ? L.tok[p] : kInvalidTok;
-      const unsigned long long m = __ballot(sv != kInvalidTok);
-      if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
-      if (sv != kInvalidTok) tile_out[run + total + __popcll(m & lt)] = sv;
-      total += __popcll(m);
-    }
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint64_t s = s_next + lane; s < s_hi; s += 64) {
-      const uint64_t rel = sent_off[s] - abase;
-      if (rel > ce || (rel == ce && !last)) break;
-      uint32_t ex = total;
-      if (rel < ce && (rel >> 6) < nblk) ex = L.blkpre[rel >> 6] + __popcll(L.vmask[rel >> 6] & ((1ull << (rel & 63)) - 1ull));
-      if (direct.off) direct.off[s] = run + ex; else sent_local[s] = run + ex;
-      mine++;
-    }
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-    s_next += mine;
-    run += total;
-    if (last) break;
-    cb = abase + ce;
-    __syncthreads();
+    if (wp_emit(L, tile, ch, sent_off, out, lane)) break;
   }
-  if (lane == 0) {
-    if (direct.off) { direct.off[s_hi] = run; *direct.n_tokens = run; }
-    else tile_tok[t] = run;
-  }
+  wp_tile_end(tile, tile_tok, direct, lane);
 }
 
 }  // namespace swt
@@ -896,14 +864,12 @@ struct swt_wp_trie {
   uint32_t *d_pops = nullptr;
   int32_t *d_tok = nullptr;  // node -> vocabulary id (NaiveWP encode), uploaded on its first call
   TileWorkspace ws;
-  DevBuf in_text, in_off, out_ids, out_off, out_status, n_tok;
+  HostStage stage;  // the host entry points (host_encode*, swt_tile.h)
   // word-level dedup inside one call (swt_dedup.h): possible when no vocabulary token holds a str.isspace character
   bool dedup_ok = false;
   DedupEngine dd;
   TileWorkspace ws2;  // the encode over the unique chunks
   DevBuf u_status;
-  PinnedBuf pin;  // small host calls: one copy each way
-  DevBuf small_in, small_out;
 };
 
 static int wp_upload(swt_wp_trie *t) {
@@ -994,10 +960,8 @@ void swt_wp_trie_destroy(swt_wp_trie *t) try {
   t->ws.release();
   t->ws2.release();
   t->dd.release();
-  t->pin.release();
-  t->small_in.release();
-  t->small_out.release();
-  for (DevBuf *b : {&t->in_text, &t->in_off, &t->out_ids, &t->out_off, &t->out_status, &t->n_tok, &t->u_status}) b->release();
+  t->stage.release();
+  t->u_status.release();
   delete t;
 } SWT_API_CATCH_VOID
 
@@ -1168,102 +1132,26 @@ int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_by
   return SWT_OK;
 } SWT_API_CATCH
 
-// the device-buffer form the host entry points below go through (swt_wp_encode_dev or swt_wp_encode_naive_dev)
+// What the host-call layer (swt_tile.h) needs to know of FastWP (swt_wp_encode_dev) or NaiveWP (swt_wp_encode_naive_dev).
 typedef int (*WpEncodeDev)(swt_wp_trie *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint8_t *,
                            uint64_t *, void *);
-
-// text and offsets on the device -> ids, offsets, statuses and the count in the caller's host arrays
-static int wp_encode_to_host(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent,
-                             uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
-  int rc;
-  if ((rc = t->out_ids.reserve((n_bytes + 64) * 4))) return rc;
-  if ((rc = t->out_off.reserve((n_sent + 1) * 8))) return rc;
-  if ((rc = t->out_status.reserve(n_sent + 8))) return rc;
-  if ((rc = t->n_tok.reserve(8))) return rc;
-  rc = dev(t, d_text, n_bytes, d_off, n_sent, t->out_ids.as<uint32_t>(), t->out_off.as<uint64_t>(), t->out_status.as<uint8_t>(),
-           t->n_tok.as<uint64_t>(), nullptr);
-  if (rc) return rc;
-  uint64_t nt = 0;
-  SWT_HIP(hipMemcpy(&nt, t->n_tok.p, 8, hipMemcpyDeviceToHost));
-  *n_tokens = nt;
-  SWT_HIP(hipMemcpy(out_off, t->out_off.p, (n_sent + 1) * 8, hipMemcpyDeviceToHost));
-  if (n_sent) SWT_HIP(hipMemcpy(status, t->out_status.p, n_sent, hipMemcpyDeviceToHost));
-  if (nt > out_cap)
-    return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-  if (nt) SWT_HIP(hipMemcpy(out_ids, t->out_ids.p, nt * 4, hipMemcpyDeviceToHost));
-  return SWT_OK;
+static HostEncoder wp_host(swt_wp_trie *t, WpEncodeDev dev) {
+  return HostEncoder{[t] { return wp_upload(t); },
+                     [t, dev](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent, uint32_t *d_ids,
+                              uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens) {
+                       return dev(t, d_text, n_bytes, d_off, n_sent, d_ids, d_out_off, d_status, d_n_tokens, nullptr);
+                     },
+                     kWpDirectBytes, kWpDirectSents, true};
 }
-
 static int wp_encode_host(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
                           uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
-  if (!t || !sent_off || !out_off || !n_tokens || (n_sent && !status)) return fail(SWT_ERR_INVALID, "null argument");
-  int rc = wp_upload(t);
-  if (rc) return rc;
-  const uint64_t n_bytes = sent_off[n_sent];
-  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
-  for (uint64_t s = 0; s < n_sent; s++)
-    if (sent_off[s] > sent_off[s + 1])
-      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
-  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
-  if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents && n_sent > 0) {
-    // tokenize(text) on one sentence (wordpiece.py:233): the kernels read the text and the offsets from pinned host memory and
-    // write the count, the offsets, the statuses and the ids there -- no copy call at all (see swt_bpe_encode)
-    const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15, st_bytes = (n_sent + 15) & ~(size_t)15;
-    const size_t text_bytes = (n_bytes + 64 + 15) & ~(size_t)15, out_at = off_bytes + text_bytes;
-    if ((rc = t->pin.reserve(out_at + 16 + off_bytes + st_bytes + (n_bytes + 64) * 4))) return rc;
-    uint8_t *h = t->pin.as<uint8_t>();
-    memcpy(h, sent_off, (n_sent + 1) * 8);
-    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
-    memset(h + off_bytes + n_bytes, ' ', 64);
-    uint8_t *o = h + out_at;
-    rc = dev(t, h + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(h), n_sent,
-             reinterpret_cast<uint32_t *>(o + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(o + 16), o + 16 + off_bytes,
-             reinterpret_cast<uint64_t *>(o), nullptr);
-    if (rc) return rc;
-    SWT_HIP(hipStreamSynchronize(0));
-    const uint64_t nt = *reinterpret_cast<const volatile uint64_t *>(o);
-    *n_tokens = nt;
-    memcpy(out_off, o + 16, (n_sent + 1) * 8);
-    if (n_sent) memcpy(status, o + 16 + off_bytes, n_sent);
-    if (nt > out_cap)
-      return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-    if (nt) memcpy(out_ids, o + 16 + off_bytes + st_bytes, nt * 4);
-    return SWT_OK;
-  }
-  if (n_bytes <= kSmallCallBytes && n_sent <= kSmallCallSents) {
-    // the reference-style call (one sentence, or a few): one copy up (offsets + text), one copy down (count, offsets, statuses, ids)
-    const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15, st_bytes = (n_sent + 15) & ~(size_t)15;
-    const size_t in_bytes = off_bytes + n_bytes + 64;
-    const size_t out_bytes = 16 + off_bytes + st_bytes + (n_bytes + 64) * 4;
-    if ((rc = t->pin.reserve(in_bytes > out_bytes ? in_bytes : out_bytes)) || (rc = t->small_in.reserve(in_bytes)) ||
-        (rc = t->small_out.reserve(out_bytes)))
-      return rc;
-    uint8_t *h = t->pin.as<uint8_t>();
-    memcpy(h, sent_off, (n_sent + 1) * 8);
-    if (n_bytes) memcpy(h + off_bytes, text, n_bytes);
-    SWT_HIP(hipMemcpyAsync(t->small_in.p, h, off_bytes + n_bytes, hipMemcpyHostToDevice, 0));
-    uint8_t *d_in = t->small_in.as<uint8_t>(), *d_out = t->small_out.as<uint8_t>();
-    rc = dev(t, d_in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(d_in), n_sent,
-             reinterpret_cast<uint32_t *>(d_out + 16 + off_bytes + st_bytes), reinterpret_cast<uint64_t *>(d_out + 16),
-             d_out + 16 + off_bytes, reinterpret_cast<uint64_t *>(d_out), nullptr);
-    if (rc) return rc;
-    SWT_HIP(hipMemcpyAsync(h, d_out, 16 + off_bytes + st_bytes + (n_bytes + 64) * 4, hipMemcpyDeviceToHost, 0));
-    SWT_HIP(hipStreamSynchronize(0));
-    const uint64_t nt = *reinterpret_cast<const uint64_t *>(h);
-    *n_tokens = nt;
-    memcpy(out_off, h + 16, (n_sent + 1) * 8);
-    if (n_sent) memcpy(status, h + 16 + off_bytes, n_sent);
-    if (nt > out_cap)
-      return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
-    if (nt) memcpy(out_ids, h + 16 + off_bytes + st_bytes, nt * 4);
-    return SWT_OK;
-  }
-  if ((rc = t->in_text.reserve(n_bytes + 64))) return rc;
-  if ((rc = t->in_off.reserve((n_sent + 1) * 8))) return rc;
-  if (n_bytes) SWT_HIP(hipMemcpyAsync(t->in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
-  SWT_HIP(hipMemcpyAsync(t->in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  return wp_encode_to_host(dev, t, t->in_text.as<uint8_t>(), n_bytes, t->in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off, status,
-                           n_tokens);
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  return host_encode(t->stage, wp_host(t, dev), text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+}
+static int wp_encode_joined(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                            uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) {
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  return host_encode_joined(t->stage, wp_host(t, dev), joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
 }
 
 int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
@@ -1275,22 +1163,6 @@ int swt_wp_encode_naive(swt_wp_trie *t, const uint8_t *text, const uint64_t *sen
                         uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
   return wp_encode_host(swt_wp_encode_naive_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
 } SWT_API_CATCH
-
-static int wp_encode_joined(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
-                            uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) {
-  if (!t || !out_off || !n_tokens || (n_sent && (!need_host || !status)) || (n_joined && !joined)) return fail(SWT_ERR_INVALID, "null argument");
-  int rc = wp_upload(t);
-  if (rc) return rc;
-  *n_tokens = UINT64_MAX;
-  struct Ctx { WpEncodeDev dev; swt_wp_trie *t; uint64_t n_sent; uint32_t *out_ids; uint64_t out_cap; uint64_t *out_off; uint8_t *status; uint64_t *n_tokens; };
-  Ctx c{dev, t, n_sent, out_ids, out_cap, out_off, status, n_tokens};
-  bool consumed = false;
-  return with_prepared_joined(joined, n_joined, n_sent, need_host, &consumed,
-      [](void *p, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off) {
-        Ctx *c = static_cast<Ctx *>(p);
-        return wp_encode_to_host(c->dev, c->t, d_text, n_bytes, d_off, c->n_sent, c->out_ids, c->out_cap, c->out_off, c->status, c->n_tokens);
-      }, &c);
-}
 
 // list[str] joined with U+0000 -> ids, the prepared text staying on the device (see swt_bpe_encode_joined).
 // *n_tokens = UINT64_MAX on return: a sentence needs the host's str.lower() and nothing was encoded.
