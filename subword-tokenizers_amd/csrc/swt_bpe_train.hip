@@ -3211,9 +3211,9 @@ int swt_bpe_train_stats(const swt_bpe_trainer *t, uint64_t *out, uint32_t n) try
   if (!t->d_st || !t->T.bits) return fail(SWT_ERR_STATE, "the trainer has no device state");
   TrainState r;
   SWT_HIP(hipMemcpy(&r, t->d_st, sizeof r, hipMemcpyDeviceToHost));
-  const uint64_t v[10] = {t->n_replans, t->theta, r.n_cand, r.idx_cursor, (uint64_t)(1ull << t->T.bits), r.flags, t->step_no, r.n_used,
-                          r.ent_scanned, r.tie_words};
-  for (uint32_t i = 0; i < n && i < 10; i++) out[i] = v[i];
+  const uint64_t v[11] = {t->n_replans, t->theta, r.n_cand, r.idx_cursor, (uint64_t)(1ull << t->T.bits), r.flags, t->step_no, r.n_used,
+                          r.ent_scanned, r.tie_words, t->n_squeezes};
+  for (uint32_t i = 0; i < n && i < 11; i++) out[i] = v[i];
   return SWT_OK;
 } SWT_API_CATCH
 
