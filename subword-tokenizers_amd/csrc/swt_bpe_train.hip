@@ -31,8 +31,8 @@
 //
 // Per merge, enqueued back to back with no host round trip (swt_bpe_train_run, up to 256 merges per batch):
 //   cand_argmax (or argmax_full) -> tie_kernel -> decide_kernel -> apply_kernel
-// Workgroup partials are combined redundantly by the consumers (a kernel boundary is the barrier; no tickets, no
-// __threadfence chains).
+// Workgroup partials are combined redundantly by the consumers: a kernel boundary is the barrier.  The one exception is
+// wp_step_kernel, whose last workgroup to finish (a ticket behind a workgroup-scope fence) decides the step.
 //
 // WordPiece mode (NaiveWP.train, /root/reference/source/wordpiece.py:29-103): the same stream, histogram,
 // index and merge-apply; symbols are the word's first character and "##c" (= 0x110000 + c) for the others; a dense
@@ -473,22 +473,9 @@ __global__ __launch_bounds__(256) void argmax_full_kernel(const unsigned long lo
 }
 
 // ---- bpe.py:102 tie-break ----------------------------------------------------------------------------------------------
-// The earliest (word, offset) whose pair holds the maximum.  An untied step costs a handful of workgroups that return at once.
-// best_pos = word << 32 | offset of the pair's left symbol inside the word.
-__global__ __launch_bounds__(kTrainThreads) void tie_kernel(const uint32_t *__restrict__ sym, const uint64_t *__restrict__ woff,
-                                                            uint64_t n_words, TrainCtx C, const ArgPart *__restrict__ parts, uint32_t n_parts) {
-  __shared__ unsigned long long s_mx, s_tied;
-  if (threadIdx.x < 64) {
-    unsigned long long m, c, k;
-    arg_collect(parts, n_parts, m, c, k);
-    if (threadIdx.x == 0) { s_mx = m; s_tied = c; }
-  }
-  __syncthreads();
-  if (s_tied < 2 || s_mx == 0) return;
-  if (cand_dry(C, s_mx)) return;  // decide_kernel reports it
-  const unsigned long long mx = s_mx;
-  // plateau cursor (BPE only: a WordPiece score moves whenever a symbol frequency does)
-  const uint64_t start = (!C.sfreq && C.st->plateau == mx) ? (uint64_t)C.st->cursor_w : 0ull;
+// The stream scan, one lane per word from word `start`: the first pair of a word whose value is `mx` goes into best_pos.
+__device__ __forceinline__ void tie_scan_stream(const uint32_t *__restrict__ sym, const uint64_t *__restrict__ woff, uint64_t n_words,
+                                                const TrainCtx &C, unsigned long long mx, uint64_t start) {
   for (uint64_t w = start + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
     if ((w << 32) >= __hip_atomic_load(&C.st->best_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;  // words only get later
     const uint64_t b0 = woff[w], b1 = woff[w + 1];
@@ -508,6 +495,24 @@ __global__ __launch_bounds__(kTrainThreads) void tie_kernel(const uint32_t *__re
       ai = i;
     }
   }
+}
+
+// The earliest (word, offset) whose pair holds the maximum.  An untied step costs a handful of workgroups that return at once.
+// best_pos = word << 32 | offset of the pair's left symbol inside the word.
+__global__ __launch_bounds__(kTrainThreads) void tie_kernel(const uint32_t *__restrict__ sym, const uint64_t *__restrict__ woff,
+                                                            uint64_t n_words, TrainCtx C, const ArgPart *__restrict__ parts, uint32_t n_parts) {
+  __shared__ unsigned long long s_mx, s_tied;
+  if (threadIdx.x < 64) {
+    unsigned long long m, c, k;
+    arg_collect(parts, n_parts, m, c, k);
+    if (threadIdx.x == 0) { s_mx = m; s_tied = c; }
+  }
+  __syncthreads();
+  if (s_tied < 2 || s_mx == 0) return;
+  if (cand_dry(C, s_mx)) return;  // decide_kernel reports it
+  const unsigned long long mx = s_mx;
+  // plateau cursor (BPE only: a WordPiece score moves whenever a symbol frequency does)
+  tie_scan_stream(sym, woff, n_words, C, mx, (!C.sfreq && C.st->plateau == mx) ? (uint64_t)C.st->cursor_w : 0ull);
 }
 
 // WordPiece: the symbol frequencies follow the merge.  A pair of two different symbols cannot overlap itself, so the merge
@@ -553,6 +558,27 @@ __device__ __forceinline__ void open_step(const TrainCtx &C, uint32_t merged, bo
   else st->flags |= kFlagIndexBroken;  // the id already names a symbol: its pairs are no longer born in one step
 }
 
+// A one-merge step is decided: `key` merges into `merged`, or there is no merge and `stop` says why (2 no pair left, 3 the
+// candidate list cannot answer, 4 an exchange block overflowed).  The command for apply_kernel, the step's index segment, the
+// WordPiece frequencies and the log row; what the deciding kernels keep in TrainState differs and stays with them.
+__device__ __forceinline__ void commit_pair(const TrainCtx &C, StepCmd *cmd, StepLog &row, unsigned long long key, uint32_t merged,
+                                            unsigned long long mx, unsigned long long tied, unsigned long long n_cand, unsigned long long stop) {
+  const bool ok = stop == 0;
+  cmd->l = (uint32_t)(key >> 32);
+  cmd->r = (uint32_t)key;
+  cmd->m = merged;
+  cmd->valid = ok ? 1u : 0u;
+  open_step(C, merged, ok);
+  if (ok && C.sfreq) wp_move_freq(C.T, cmd->l, cmd->r, merged, C.sfreq);
+  row.l = cmd->l;
+  row.r = cmd->r;
+  row.count = mx;
+  row.flag = stop;
+  row.n_syms = C.st->n_syms;
+  row.n_tied = tied;
+  row.n_cand = n_cand;
+}
+
 // One wave: the step's decision.  Combines the partials, resolves a tie from best_pos, writes the merge command for
 // apply_kernel and the step's log line, registers the merged symbol's index segment, moves the plateau cursor.
 // cmd == nullptr: host-driven swt_bpe_train_best -- only the result fields are written.
@@ -572,7 +598,6 @@ __global__ __launch_bounds__(64) void decide_kernel(const uint32_t *__restrict__
   st->max_count = dry ? 0 : mx;
   st->n_tied = (dry || !mx) ? 0 : tied;
   st->best_key = key;
-  st->win_key = key;
   st->res_pos = pos;
   st->best_pos = kEmptyKey;
   if (dry) st->flags |= kFlagReplan;
@@ -582,20 +607,7 @@ __global__ __launch_bounds__(64) void decide_kernel(const uint32_t *__restrict__
     else if (st->plateau != mx) { st->plateau = mx; st->cursor_w = 0; }
   }
   if (!cmd) return;
-  const bool ok = !dry && mx > 0 && key != kEmptyKey;
-  cmd->l = (uint32_t)(key >> 32);
-  cmd->r = (uint32_t)key;
-  cmd->m = merged;
-  cmd->valid = ok ? 1u : 0u;
-  open_step(C, merged, ok);
-  if (ok && C.sfreq) wp_move_freq(C.T, cmd->l, cmd->r, merged, C.sfreq);
-  log[log_i].l = cmd->l;
-  log[log_i].r = cmd->r;
-  log[log_i].count = mx;
-  log[log_i].flag = ok ? 0ull : (dry ? 3ull : 2ull);
-  log[log_i].n_syms = st->n_syms;
-  log[log_i].n_tied = tied;
-  log[log_i].n_cand = st->n_cand;
+  commit_pair(C, cmd, log[log_i], key, merged, mx, tied, st->n_cand, dry ? 3ull : (mx > 0 && key != kEmptyKey ? 0ull : 2ull));
 }
 
 // host-driven step (swt_bpe_train_apply): the command comes from the caller
@@ -1194,26 +1206,8 @@ __global__ __launch_bounds__(kTrainThreads) void wp_tie_index_kernel(const uint3
   if (cand_dry(C, s_mx)) return;  // decide_kernel reports it
   const unsigned long long mx = s_mx;
   TrainState *st = C.st;
-  if (st->flags & kFlagIndexBroken) {  // the stream scan of tie_kernel
-    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
-      if ((w << 32) >= __hip_atomic_load(&st->best_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-      const uint64_t b0 = woff[w], b1 = woff[w + 1];
-      uint32_t a = kHole;
-      uint64_t ai = 0;
-      for (uint64_t i = b0; i < b1; i++) {
-        const uint32_t b = sym[i];
-        if (b == kHole) continue;
-        if (a != kHole) {
-          const unsigned long long key = pair_key(a, b);
-          if (pair_value(key, table_get(C.T, key), C.sfreq) == mx) {
-            atomicMin(&st->best_pos, (unsigned long long)((w << 32) | (ai - b0)));
-            break;
-          }
-        }
-        a = b;
-        ai = i;
-      }
-    }
+  if (st->flags & kFlagIndexBroken) {
+    tie_scan_stream(sym, woff, n_words, C, mx, 0);
     return;
   }
   unsigned long long n = st->n_cand;
@@ -1702,6 +1696,101 @@ __global__ __launch_bounds__(kTrainThreads) void fast_tie_kernel(const uint32_t 
 #endif
 }
 
+// ---- what the two apply launches of the fast path (fast_apply_kernel, fast_apply_sharded_kernel) have in common -----------
+// The opening.  What the launch itself may change (workgroup 0 raises flags / halt) is read once per workgroup: its lanes
+// must agree.  false: the step is idle -- nothing runs until the host has looked (a re-plan is due, the device halted, the
+// round trip's log is full, or, sharded, an exchange block overflowed: halt_ext) -- and the merges logged so far have been
+// handed to the next step's parity.  true: `flags` and `run_done` are the workgroup's view, and the plan is empty.
+__device__ __forceinline__ bool fast_step_open(const TrainCtx &C, BatchPlan &P, uint32_t first_merged, uint32_t limit, unsigned int &flags,
+                                               unsigned long long &run_done) {
+  __shared__ unsigned long long hdr[3];
+  TrainState *st = C.st;
+  const unsigned par = C.step & 1u;
+  if (threadIdx.x == 0) { hdr[0] = st->flags; hdr[1] = st->run_done[par]; hdr[2] = st->halt; }
+  __syncthreads();
+  flags = (unsigned int)hdr[0];
+  run_done = hdr[1];
+  if ((flags & kFlagReplan) || hdr[2] || run_done >= limit || (C.halt_ext && *C.halt_ext)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->run_done[par ^ 1u] = run_done;
+    return false;
+  }
+  if (threadIdx.x == 0) {
+    P.K = 0;
+    P.first_m = first_merged + (uint32_t)run_done;
+    for (int u = 0; u < (int)kMaxBatch; u++) { P.l[u] = kHole; P.r[u] = kHole; }
+  }
+  return true;
+}
+
+// The prefix rule (see above), settled by the first wave with shuffles and ballots: lane rk < nsel holds candidate rk, in the
+// order of the first positions -- its pair (a, b), whether it is dangerous, whether it lies beyond the window every workgroup
+// scanned (`far`).  The step merges the longest prefix whose members share no symbol, up to and including the first
+// dangerous one, before the first far one, and no more than the round trip has room for.  Writes the members into P and
+// returns K; `why` is set when the prefix is cut (1 beyond the window, 2 shared symbol, 3 dangerous, 4 the round trip's cap).
+__device__ __forceinline__ uint32_t batch_prefix(BatchPlan &P, uint32_t a, uint32_t b, bool dng, bool far, unsigned int nsel,
+                                                 unsigned long long room, int &why) {
+  const unsigned int rk = threadIdx.x;
+  bool clash = false;  // with any pair before it (were one of those left out, the prefix would end there anyway)
+#pragma unroll
+  for (int jj = 0; jj < (int)kMaxBatch; jj++) {
+    const uint32_t aj = __shfl(a, jj), bj = __shfl(b, jj);
+    if ((unsigned int)jj < rk && rk < nsel) clash |= a == aj || a == bj || b == aj || b == bj;
+  }
+  const unsigned long long m_clash = __ballot(clash), m_far = __ballot(far && rk > 0 && rk < nsel), m_dng = __ballot(dng && rk < nsel);
+  uint32_t K = nsel;
+  if (m_far && (uint32_t)__builtin_ctzll(m_far) < K) { K = (uint32_t)__builtin_ctzll(m_far); why = 1; }
+  if (m_clash && (uint32_t)__builtin_ctzll(m_clash) < K) { K = (uint32_t)__builtin_ctzll(m_clash); why = 2; }
+  if (m_dng && (uint32_t)__builtin_ctzll(m_dng) + 1 < K) { K = (uint32_t)__builtin_ctzll(m_dng) + 1; why = 3; }
+  else if (m_dng && (uint32_t)__builtin_ctzll(m_dng) + 1 == K) why = 3;
+  if ((unsigned long long)K > room) { K = (uint32_t)room; why = 4; }
+  if (rk < K) { P.l[rk] = a; P.r[rk] = b; }
+  if (rk == 0) P.K = K;
+  return K;
+}
+
+// The commit, once the K members and the lengths of their lists (P.ent0[1..K]) are in P, a barrier ago: the lengths become
+// running sums; workgroup 0 writes the state -- `pos`: the earliest tied occurrence the step knows of in this shard, `tied`:
+// the pairs tied here (both only move the plateau cursor) -- and one lane per member the birth step and the log row
+// (`row_tied`: its n_tied).  Ends in a barrier: the plan is complete behind it.
+__device__ __forceinline__ void fast_step_commit(const TrainCtx &C, BatchPlan &P, StepLog *__restrict__ log, unsigned long long run_done,
+                                                 unsigned long long mx, unsigned long long pos, unsigned long long tied,
+                                                 unsigned long long row_tied) {
+  TrainState *st = C.st;
+  const unsigned par = C.step & 1u;
+  const uint32_t K = P.K;
+  if (threadIdx.x == 0) {
+    P.ent0[0] = 0;
+    for (uint32_t q = 0; q < K; q++) P.ent0[q + 1] += P.ent0[q];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->res_pos = pos;
+    st->best2[par ^ 1u] = kEmptyKey;    // the next step's scan starts from a clean minimum
+    st->n_synced = st->n_synced_next;  // the tie launch mirrored the candidates up to there
+    // the plateau cursor: a plain store beside the other workgroups' atomicMin of the words they touch -- both orders leave a
+    // valid lower bound (every tied pair of this shard lies at or after its earliest tied occurrence, and the first member's
+    // first word is the first word this step touches)
+    if (tied >= 2 && pos != kEmptyKey) { st->plateau = mx; st->cursor_w = (uint32_t)(pos >> 32); }
+    else if (st->plateau != mx) { st->plateau = mx; st->cursor_w = 0; }
+    st->run_done[par ^ 1u] = run_done + K;
+    st->run_active += 1;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < K) {  // one lane per member: its birth step, its log line
+    const uint32_t q = threadIdx.x, merged = P.first_m + q;
+    const unsigned long long n_syms = st->step_syms, n_cand = st->n_cand;
+    if (merged >= C.id_base && merged - C.id_base < C.seg_cap && C.seg_of[merged - C.id_base] == 0) C.seg_of[merged - C.id_base] = C.step;
+    else atomicOr(&st->flags, kFlagBrokenPending);  // the next step's tie launch turns it into kFlagIndexBroken
+    StepLog &row = log[run_done + q];
+    row.l = P.l[q];
+    row.r = P.r[q];
+    row.count = mx;
+    row.flag = 0ull;
+    row.n_syms = n_syms;  // of the step: the members after the first saw a few symbols less
+    row.n_tied = row_tied;
+    row.n_cand = n_cand;
+  }
+  __syncthreads();
+}
+
 // `first_merged`: the symbol id of the round trip's first merge; `limit`: merges the round trip may log
 __global__ __launch_bounds__(kTrainThreads) void fast_apply_kernel(uint32_t *__restrict__ sym, const uint64_t *__restrict__ woff,
                                                                    const uint32_t *__restrict__ freq, uint64_t n_words, TrainCtx C,
@@ -1714,24 +1803,14 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_kernel(uint32_t *__r
   SWT_SPAN(1, C.step);
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   const unsigned par = C.step & 1u;
-  // what this launch itself may change (workgroup 0 raises flags / halt) is read once per workgroup: its lanes must agree
-  __shared__ unsigned long long hdr[3];
-  if (threadIdx.x == 0) { hdr[0] = st->flags; hdr[1] = st->run_done[par]; hdr[2] = st->halt; }
   const unsigned long long mx = st->max_count, tied = st->n_tied, n_list = st->n_list[par], win_end = st->win_end;
-  __syncthreads();
-  const unsigned int flags = (unsigned int)hdr[0];
-  const unsigned long long run_done = hdr[1];
-  if ((flags & kFlagReplan) || hdr[2] || run_done >= limit) {  // nothing runs until the host has looked
-    if (lead) st->run_done[par ^ 1u] = run_done;
-    return;
-  }
+  unsigned int flags;
+  unsigned long long run_done;
+  if (!fast_step_open(C, P, first_merged, limit, flags, run_done)) return;
   // ---- what this step merges (every workgroup decides for itself, from what the tie launch left) ----
   if (threadIdx.x == 0) {
     n_found = 0;
     p1_pos = kEmptyKey;
-    P.K = 0;
-    P.first_m = first_merged + (uint32_t)run_done;
-    for (int u = 0; u < (int)kMaxBatch; u++) { P.l[u] = kHole; P.r[u] = kHole; }
   }
   __syncthreads();
   TiedPlan my_plan{0, 0, 0, 0};  // lane t: the list of tied pair t (the tie launch's planner has looked it up) ...
@@ -1763,9 +1842,7 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_kernel(uint32_t *__r
       if (rank < kMaxBatch) ord[rank] = my_k;
     }
     __syncthreads();
-    if (threadIdx.x < 64 && nf) {
-      // the longest prefix whose members share no symbol, up to and including the first dangerous one (see above): the first
-      // wave holds one candidate per lane, in order, and settles it with shuffles and ballots
+    if (threadIdx.x < 64 && nf) {  // the first wave holds one candidate per lane, in order
       const unsigned int nsel = nf < kMaxBatch ? nf : kMaxBatch;
       const unsigned int rk = threadIdx.x;
       uint32_t a = kHole, b = kHole, dng = 0;
@@ -1777,30 +1854,13 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_kernel(uint32_t *__r
         pos = f_pos[e];
         dng = f_dng[e];
       }
-      bool clash = false;  // with any pair before it (were one of those left out, the prefix would end there anyway)
-#pragma unroll
-      for (int jj = 0; jj < (int)kMaxBatch; jj++) {
-        const uint32_t aj = __shfl(a, jj), bj = __shfl(b, jj);
-        if ((unsigned int)jj < rk && rk < nsel) clash |= a == aj || a == bj || b == aj || b == bj;
-      }
-      const bool far = rk > 0 && rk < nsel && pos >= win_end;  // not every workgroup scanned that far
-      const unsigned long long m_clash = __ballot(clash), m_far = __ballot(far), m_dng = __ballot(dng != 0 && rk < nsel);
-      const unsigned long long room = (unsigned long long)limit - run_done;
-      uint32_t K = nsel;
-      int why = nf > kMaxBatch ? 5 : 0;  // 0: every pair seen is in, 1 beyond the window, 2 shared symbol, 3 dangerous, 4 the round trip's cap, 5 kMaxBatch
-      if (m_far && (uint32_t)__builtin_ctzll(m_far) < K) { K = (uint32_t)__builtin_ctzll(m_far); why = 1; }
-      if (m_clash && (uint32_t)__builtin_ctzll(m_clash) < K) { K = (uint32_t)__builtin_ctzll(m_clash); why = 2; }
-      if (m_dng && (uint32_t)__builtin_ctzll(m_dng) + 1 < K) { K = (uint32_t)__builtin_ctzll(m_dng) + 1; why = 3; }
-      else if (m_dng && (uint32_t)__builtin_ctzll(m_dng) + 1 == K) why = 3;
-      if ((unsigned long long)K > room) { K = (uint32_t)room; why = 4; }
-      if (rk < K) { P.l[rk] = a; P.r[rk] = b; }
+      int why = nf > kMaxBatch ? 5 : 0;  // 0: every pair seen is in, 5 kMaxBatch; 1..4: batch_prefix
+      // (far: not every workgroup scanned that far)
+      [[maybe_unused]] const uint32_t n_batch = batch_prefix(P, a, b, dng != 0, pos >= win_end, nsel, (unsigned long long)limit - run_done, why);
       if (rk == 0) {
-        P.K = K;
         p1_pos = pos;
 #ifdef SWT_STAMPS
-        if (blockIdx.x == 0) { atomicAdd(&g_why[K], 1ull); atomicAdd(&g_why[16 + why], 1ull); atomicAdd(&g_why[24], (unsigned long long)nf); atomicAdd(&g_why[25], n_list); }
-#else
-        (void)why;
+        if (blockIdx.x == 0) { atomicAdd(&g_why[n_batch], 1ull); atomicAdd(&g_why[16 + why], 1ull); atomicAdd(&g_why[24], (unsigned long long)nf); atomicAdd(&g_why[25], n_list); }
 #endif
       }
     }
@@ -1826,41 +1886,10 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_kernel(uint32_t *__r
   }
   if (my_rank < K) P.ent0[my_rank + 1] = (flags & kFlagIndexBroken) ? 0ull : plan_take(C, P, (int)my_rank, my_plan);  // lengths ...
   __syncthreads();
-  if (threadIdx.x == 0) {  // ... to running sums
-    P.ent0[0] = 0;
-    for (uint32_t q = 0; q < K; q++) P.ent0[q + 1] += P.ent0[q];
-  }
 #ifdef SWT_STAMPS
   if (lead) g_kstep[C.step & (kSpanSteps - 1)] = K;
 #endif
-  if (lead) {
-    const unsigned long long pos = p1_pos;
-    st->res_pos = pos;
-    st->win_key = pair_key(P.l[0], P.r[0]);
-    st->best2[par ^ 1u] = kEmptyKey;    // the next step's scan starts from a clean minimum
-    st->n_synced = st->n_synced_next;  // the tie launch mirrored the candidates up to there
-    // the plateau cursor: a plain store beside the other workgroups' atomicMin of the words they touch -- both orders leave a
-    // valid lower bound (the first member's first word is the first word this step touches)
-    if (tied >= 2 && pos != kEmptyKey) { st->plateau = mx; st->cursor_w = (uint32_t)(pos >> 32); }
-    else if (st->plateau != mx) { st->plateau = mx; st->cursor_w = 0; }
-    st->run_done[par ^ 1u] = run_done + K;
-    st->run_active += 1;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < K) {  // one lane per member: its birth step, its log line
-    const uint32_t q = threadIdx.x, merged = P.first_m + q;
-    const unsigned long long n_syms = st->step_syms, n_cand = st->n_cand;
-    if (merged >= C.id_base && merged - C.id_base < C.seg_cap && C.seg_of[merged - C.id_base] == 0) C.seg_of[merged - C.id_base] = C.step;
-    else atomicOr(&st->flags, kFlagBrokenPending);  // the next step's tie launch turns it into kFlagIndexBroken
-    StepLog &row = log[run_done + q];
-    row.l = P.l[q];
-    row.r = P.r[q];
-    row.count = mx;
-    row.flag = 0ull;
-    row.n_syms = n_syms;  // of the step: the members after the first saw a few symbols less
-    row.n_tied = tied;
-    row.n_cand = n_cand;
-  }
-  __syncthreads();
+  fast_step_commit(C, P, log, run_done, mx, p1_pos, tied, tied);  // ... to running sums
   apply_body(sym, woff, freq, n_words, C, P);
 }
 
@@ -1959,32 +1988,22 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_sharded_kernel(uint3
   __shared__ unsigned long long g_key[kMaxBatch];
   __shared__ uint32_t g_lo[kMaxBatch][2], g_hi[kMaxBatch][2], g_dng[kMaxBatch];
   __shared__ unsigned int g_n;
+  __shared__ unsigned int g_lone;
   TrainState *st = C.st;
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   const unsigned par = C.step & 1u;
-  __shared__ unsigned long long hdr[3];
-  if (threadIdx.x == 0) { hdr[0] = st->flags; hdr[1] = st->run_done[par]; hdr[2] = st->halt; }
   const unsigned long long mx = st->max_count, tied_here = st->n_tied, n_list = st->n_list[par];
-  __syncthreads();
-  const unsigned int flags = (unsigned int)hdr[0];
-  const unsigned long long run_done = hdr[1];
-  if ((flags & kFlagReplan) || hdr[2] || run_done >= limit || (C.halt_ext && *C.halt_ext)) {
-    if (lead) st->run_done[par ^ 1u] = run_done;
-    return;
-  }
+  unsigned int flags;
+  unsigned long long run_done;
+  if (!fast_step_open(C, P, first_merged, limit, flags, run_done)) return;
   if (threadIdx.x == 0) {
     g_n = 0;
-    P.K = 0;
-    P.first_m = first_merged + (uint32_t)run_done;
-    for (int u = 0; u < (int)kMaxBatch; u++) { P.l[u] = kHole; P.r[u] = kHole; }
+    g_lone = 0;
   }
   __syncthreads();
   // ---- the batch, from the gathered messages alone (so every workgroup of every rank decides alike) ----
   // ranks in order; the first wave collects, the workgroup's barriers carry g_n from rank to rank (uniform trip count: the
   // loop looks at nothing but the gathered messages and g_n)
-  __shared__ unsigned int g_lone;
-  if (threadIdx.x == 0) g_lone = 0;
-  __syncthreads();
   if (mx) {
     for (uint32_t r = 0; r < C.world; r++) {
       const TieMsg &m = C.tie_all[r];
@@ -2050,31 +2069,17 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_sharded_kernel(uint3
     __syncthreads();
   }
   if (threadIdx.x < 64 && mx) {
-    const int lane = threadIdx.x;
-    const unsigned int gn = g_n;
-    // the longest prefix whose members share no symbol, up to and including the first dangerous one (fast_apply_kernel)
-    const unsigned int nsel = gn;
-    const unsigned int rk = lane;
-    uint32_t a = kHole, b = kHole, dng = 0;
+    // the collected pairs are in order and all certain (none is "far"): lane rk holds pair rk
+    const unsigned int nsel = g_n, rk = threadIdx.x;
+    uint32_t a = kHole, b = kHole;
+    bool dng = false;
     if (rk < nsel) {
       a = (uint32_t)(g_key[rk] >> 32);
       b = (uint32_t)g_key[rk];
       dng = g_dng[rk] && !(g_lo[rk][0] < g_hi[rk][0] && g_lo[rk][1] < g_hi[rk][1] && a != b);
     }
-    bool clash = false;
-#pragma unroll
-    for (int jj = 0; jj < (int)kMaxBatch; jj++) {
-      const uint32_t aj = __shfl(a, jj), bj = __shfl(b, jj);
-      if ((unsigned int)jj < rk && rk < nsel) clash |= a == aj || a == bj || b == aj || b == bj;
-    }
-    const unsigned long long m_clash = __ballot(clash), m_dng = __ballot(dng != 0 && rk < nsel);
-    const unsigned long long room = (unsigned long long)limit - run_done;
-    uint32_t K = nsel;
-    if (m_clash && (uint32_t)__builtin_ctzll(m_clash) < K) K = (uint32_t)__builtin_ctzll(m_clash);
-    if (m_dng && (uint32_t)__builtin_ctzll(m_dng) + 1 < K) K = (uint32_t)__builtin_ctzll(m_dng) + 1;
-    if ((unsigned long long)K > room) K = (uint32_t)room;
-    if (rk < K) { P.l[rk] = a; P.r[rk] = b; }
-    if (rk == 0) P.K = K;
+    int why = 0;
+    (void)batch_prefix(P, a, b, dng, false, nsel, (unsigned long long)limit - run_done, why);
   }
   __syncthreads();
   const uint32_t K = P.K;
@@ -2098,37 +2103,8 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_sharded_kernel(uint3
   if (threadIdx.x < K && P.ent0[threadIdx.x + 1] == ~0ull)
     P.ent0[threadIdx.x + 1] = (flags & kFlagIndexBroken) ? 0ull : plan_member(C, P, (int)threadIdx.x);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    P.ent0[0] = 0;
-    for (uint32_t q = 0; q < K; q++) P.ent0[q + 1] += P.ent0[q];
-  }
-  if (lead) {
-    const unsigned long long my_pos = st->best2[par];  // this shard's earliest tied occurrence (the scan went on until it had one)
-    st->res_pos = my_pos;
-    st->win_key = pair_key(P.l[0], P.r[0]);
-    st->best2[par ^ 1u] = kEmptyKey;
-    st->n_synced = st->n_synced_next;
-    // the plateau cursor is local: every tied pair of this shard lies at or after its earliest tied occurrence
-    if (tied_here >= 2 && my_pos != kEmptyKey) { st->plateau = mx; st->cursor_w = (uint32_t)(my_pos >> 32); }
-    else if (st->plateau != mx) { st->plateau = mx; st->cursor_w = 0; }
-    st->run_done[par ^ 1u] = run_done + K;
-    st->run_active += 1;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < K) {
-    const uint32_t q = threadIdx.x, merged = P.first_m + q;
-    const unsigned long long n_syms = st->step_syms, n_cand = st->n_cand;
-    if (merged >= C.id_base && merged - C.id_base < C.seg_cap && C.seg_of[merged - C.id_base] == 0) C.seg_of[merged - C.id_base] = C.step;
-    else atomicOr(&st->flags, kFlagBrokenPending);
-    StepLog &row = log[run_done + q];
-    row.l = P.l[q];
-    row.r = P.r[q];
-    row.count = mx;
-    row.flag = 0ull;
-    row.n_syms = n_syms;
-    row.n_tied = g_n;
-    row.n_cand = n_cand;
-  }
-  __syncthreads();
+  // the plateau cursor is local: this shard's earliest tied occurrence (the scan went on until it had one)
+  fast_step_commit(C, P, log, run_done, mx, lead ? st->best2[par] : kEmptyKey, tied_here, g_n);
   apply_body(sym, woff, freq, n_words, C, P);
 }
 
@@ -2137,9 +2113,9 @@ __global__ __launch_bounds__(kTrainThreads) void fast_apply_sharded_kernel(uint3
 // launches: ~8 us each, the work inside them is small (S85k-lex: ~2,400 live pairs, a few dozen words per merge).  While the
 // list of live pairs is short (kWpStepList), every workgroup takes the maximum score over it by itself -- as fast_tie_kernel
 // does for BPE -- the waves share the tied pairs' index lookups (wp_tie_by_index), and the workgroup that finishes LAST (a
-// ticket) reads the final first position and does what decide_kernel does: the merge command for apply_kernel, the log line,
-// the step's index segment, the symbol frequencies.  No apply is in flight during this launch, so the stream, the counts and
-// the frequencies stand still.  Two launches per merge instead of four.
+// ticket) reads the final first position and decides as decide_kernel does (commit_pair: the merge command for apply_kernel,
+// the log line, the step's index segment, the symbol frequencies).  No apply is in flight during this launch, so the stream,
+// the counts and the frequencies stand still.  Two launches per merge instead of four.
 __global__ __launch_bounds__(kTrainThreads) void wp_step_kernel(const uint32_t *__restrict__ sym, const uint64_t *__restrict__ woff,
                                                                 uint64_t n_words, TrainCtx C, StepCmd *cmd, StepLog *log, uint32_t log_i,
                                                                 uint32_t merged) {
@@ -2191,29 +2167,8 @@ __global__ __launch_bounds__(kTrainThreads) void wp_step_kernel(const uint32_t *
   const BlockArg a = block_reduce(m, c, k);
   const bool dry = (flags & kFlagReplan) || n_all > C.cand_cap;  // cand_dry at theta 1: the list lost a pair, or was voided
   if (!dry && a.mx && a.tied >= 2) {
-    if (flags & kFlagIndexBroken) {  // no index: the stream scan (tie_kernel)
-      for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
-        if ((w << 32) >= __hip_atomic_load(&st->best_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        const uint64_t b0 = woff[w], b1 = woff[w + 1];
-        uint32_t x = kHole;
-        uint64_t xi = 0;
-        for (uint64_t i = b0; i < b1; i++) {
-          const uint32_t y = sym[i];
-          if (y == kHole) continue;
-          if (x != kHole) {
-            const unsigned long long key = pair_key(x, y);
-            if (pair_value(key, table_get(C.T, key), C.sfreq) == a.mx) {
-              atomicMin(&st->best_pos, (unsigned long long)((w << 32) | (xi - b0)));
-              break;
-            }
-          }
-          x = y;
-          xi = i;
-        }
-      }
-    } else {
-      wp_tie_by_index(sym, woff, n_words, C, a.mx, n, n_synced);
-    }
+    if (flags & kFlagIndexBroken) tie_scan_stream(sym, woff, n_words, C, a.mx, 0);  // no index
+    else wp_tie_by_index(sym, woff, n_words, C, a.mx, n, n_synced);
   }
   // ---- the last workgroup to get here decides.  Everything the workgroups tell each other in this launch travels in device-scope
   // atomics (best_pos, the ticket), so all the ticket needs is that this workgroup's atomics have been performed: a workgroup-scope
@@ -2242,25 +2197,11 @@ __global__ __launch_bounds__(kTrainThreads) void wp_step_kernel(const uint32_t *
   st->max_count = dry ? 0 : a.mx;
   st->n_tied = (dry || !a.mx) ? 0 : a.tied;
   st->best_key = key;
-  st->win_key = key;
   st->res_pos = pos;
   st->best_pos = kEmptyKey;
   if (dry) st->flags |= kFlagReplan;
   st->n_synced = n;
-  const bool ok = !dry && a.mx > 0 && key != kEmptyKey;
-  cmd->l = (uint32_t)(key >> 32);
-  cmd->r = (uint32_t)key;
-  cmd->m = merged;
-  cmd->valid = ok ? 1u : 0u;
-  open_step(C, merged, ok);
-  if (ok) wp_move_freq(C.T, cmd->l, cmd->r, merged, C.sfreq);
-  log[log_i].l = cmd->l;
-  log[log_i].r = cmd->r;
-  log[log_i].count = a.mx;
-  log[log_i].flag = ok ? 0ull : (dry ? 3ull : 2ull);
-  log[log_i].n_syms = st->n_syms;
-  log[log_i].n_tied = a.tied;
-  log[log_i].n_cand = n_all;
+  commit_pair(C, cmd, log[log_i], key, merged, a.mx, a.tied, n_all, dry ? 3ull : (a.mx > 0 && key != kEmptyKey ? 0ull : 2ull));
 }
 
 // ---- candidates --------------------------------------------------------------------------------------------------------
@@ -2453,26 +2394,15 @@ __global__ __launch_bounds__(64) void decide_sharded_kernel(TrainCtx C, const Ar
   st->n_tied = (dry || !mx) ? 0 : tied;
   st->best_key = key;
   if (dry) st->flags |= kFlagReplan;
-  const bool ok = !dry && !halted && mx > 0 && key != kEmptyKey;
-  cmd->l = (uint32_t)(key >> 32);
-  cmd->r = (uint32_t)key;
-  cmd->m = merged;
-  cmd->valid = ok ? 1u : 0u;
-  open_step(C, merged, ok);
-  log[log_i].l = cmd->l;
-  log[log_i].r = cmd->r;
-  log[log_i].count = mx;
-  log[log_i].flag = ok ? 0ull : (halted ? 4ull : (dry ? 3ull : 2ull));
-  log[log_i].n_syms = st->n_syms;
-  log[log_i].n_tied = tied;
-  log[log_i].n_cand = st->n_cand;
+  commit_pair(C, cmd, log[log_i], key, merged, mx, tied, st->n_cand,
+              halted ? 4ull : (dry ? 3ull : (mx > 0 && key != kEmptyKey ? 0ull : 2ull)));
 }
 
 }  // namespace swt
 
 using namespace swt;
 
-static double host_now() {
+double swt::host_now() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
@@ -3308,27 +3238,16 @@ int swt_bpe_train_run(swt_bpe_trainer *t, uint32_t max_steps, uint32_t first_mer
   *n_done = 0;
   if ((rc = t->ready())) return rc;
   std::vector<StepLog> hlog(kMaxRunSteps);
-  uint32_t done = 0;
+  RunOut out{left, right, count, 0, 0, 1.0, getenv("SWT_TRAIN_DEBUG") != nullptr};
   bool exhausted = false;
-  int dry_runs = 0;
-  double per_step = 1.0;  // merges a step of the fast path has carried lately: sizes the next round trip
-  while (done < max_steps && !exhausted) {
-    const uint32_t remaining = max_steps - done;
+  while (out.done < max_steps && !exhausted) {
+    const uint32_t remaining = max_steps - out.done;
     // One round trip: `steps` launch sequences that may log up to `cap` merges.  A step of the fast path carries one merge or
     // several (fast_apply_kernel); every other path carries exactly one.
     const bool maybe_fast = !t->d_sfreq && t->n_words;
-    uint32_t steps = remaining < kRunBatch ? remaining : kRunBatch;
-    uint32_t cap = steps;
-    if (maybe_fast) {
-      const double want = (double)remaining / per_step * 1.05 + 1.0;
-      if (want < (double)steps) steps = (uint32_t)want;
-      if (steps < 8) steps = remaining < 8 ? remaining : 8;
-      double c = (double)steps * per_step * 1.5 + 8.0;
-      if (c > (double)remaining) c = (double)remaining;
-      if (c > (double)kMaxRunSteps) c = (double)kMaxRunSteps;
-      cap = (uint32_t)c;
-      if (cap < steps) cap = steps;
-    }
+    ShardTrip trip{remaining < kRunBatch ? remaining : kRunBatch, 0, false, false};
+    trip.cap = trip.steps;
+    if (maybe_fast) trainer_trip_size(remaining, out.per_step, &trip);
     // room for everything the round trip may create (the symbol count grows by one per merge, counts never grow)
     // New pairs per merge: two per occurrence (occurrences <= the pair's count, and counts never grow: the maximum at the start
     // of the trip bounds every merge of it), and never more than (x, m) / (m, y) over the distinct symbols plus (m, m) -- the
@@ -3337,14 +3256,14 @@ int swt_bpe_train_run(swt_bpe_trainer *t, uint32_t max_steps, uint32_t first_mer
     // 1/2 -- silently, until check_state() looked: tools/gpu_soak.py seed 12787955, profiles/r03h_soak.txt.)
     const uint64_t by_count = (!t->d_sfreq && t->h_st.max_count) ? 2 * t->h_st.max_count : ~0ull;  // (WordPiece: max_count is a score)
     uint64_t extra = 0;
-    for (uint32_t k2 = 0; k2 < cap; k2++) {  // merge k2 of the trip sees n_base + n_applied + k2 symbols
+    for (uint32_t k2 = 0; k2 < trip.cap; k2++) {  // merge k2 of the trip sees n_base + n_applied + k2 symbols
       const uint64_t by_sym = 2 * (t->n_base + t->n_applied + k2 + 1) + 1;
       extra += by_sym < by_count ? by_sym : by_count;
     }
     // (every new pair costs the stream a symbol: a round trip cannot make more than two per live symbol)
     if (!t->sharded && t->h_st.n_syms && 2 * t->h_st.n_syms + 64 < extra) extra = 2 * t->h_st.n_syms + 64;
     if ((rc = ensure_room(t, extra))) return rc;
-    if ((rc = ensure_steps(t, steps, first_merged + done + cap))) return rc;
+    if ((rc = ensure_steps(t, trip.steps, first_merged + out.done + trip.cap))) return rc;
     // BPE re-plans once pushes have grown the (short) list past kCandHigh; WordPiece lists every live pair and re-plans when
     // three quarters of its room are used (dead entries are dropped on the way; a list that overflows in mid trip says so
     // on the device -- cand_dry -- and the host comes back here)
@@ -3354,108 +3273,50 @@ int swt_bpe_train_run(swt_bpe_trainer *t, uint32_t max_steps, uint32_t first_mer
       if (maybe_fast && t->h_st.n_syms && t->h_st.n_syms * 10 < t->extent * 7 && (rc = squeeze_stream(t))) return rc;
       if ((rc = t->replan())) return rc;
     }
-    const bool fast = t->theta && maybe_fast;
-    if (fast && t->theta > 1 && t->cand_built) {
-      // A list that runs dry in mid trip turns the rest of the trip into steps that do nothing (two launches each).  A list of
-      // n pairs has been good for about dry_ratio * n merges: the trip ends there, and the next one starts with a new threshold.
-      const double budget = t->dry_ratio * (double)t->cand_built - (double)t->since_replan;
-      if (budget < 24.0 && (double)remaining > budget && t->since_replan) {
-        if (t->dry_ratio < 2.0) t->dry_ratio *= 1.1;  // it never ran dry: the list may be good for more than was thought
-        t->cand_valid = false;
-        continue;  // re-plan now (a cheaper stop than a dry trip)
-      }
-      const double most = budget / per_step + 1.0;
-      if (most < (double)steps) {
-        steps = most < 8.0 ? 8u : (uint32_t)most;
-        if (steps > remaining) steps = remaining;
-        if (cap > steps * kMaxBatch) cap = steps * kMaxBatch;
-      }
+    trip.fast = t->theta && maybe_fast;
+    if (trip.fast && trainer_dry_point(t, remaining, out.per_step, &trip)) {
+      t->cand_valid = false;
+      continue;  // re-plan now (a cheaper stop than a dry trip)
     }
-    if (!fast) {
-      if (steps > remaining) steps = remaining;
-      cap = steps;
-    } else {
-      // the step counters of the fast path start from zero, and no position of an earlier round trip is left
-      SWT_HIP(hipMemsetAsync(&t->d_st->run_done[0], 0, 8 * 8, t->stream));
-      SWT_HIP(hipMemsetAsync(&t->d_st->best2[0], 0xFF, 2 * 8, t->stream));  // steps that did nothing may have left either parity behind
-      SWT_HIP(hipMemsetAsync(t->d_gpos, 0xFF, 2 * (size_t)t->cand_cap * 8, t->stream));
-      SWT_HIP(hipMemsetAsync(t->d_gnb_min, 0xFF, 4 * (size_t)t->cand_cap * 4, t->stream));
-      SWT_HIP(hipMemsetAsync(t->d_gnb_max, 0, 4 * (size_t)t->cand_cap * 4, t->stream));
+    if (!trip.fast) {
+      if (trip.steps > remaining) trip.steps = remaining;
+      trip.cap = trip.steps;
+    } else if ((rc = trainer_fast_begin(t))) {
+      return rc;
     }
     // (the list may grow past the limit within the trip: the kernel's loops are strided, only slower then)
     const bool wp_fused = t->d_sfreq && t->theta && t->n_words && t->h_st.n_cand <= kWpStepList && !getenv("SWT_WP_GENERIC");
     prof_begin(t->stream);  // one bracket around the whole batch of merge steps: bench.py divides by the merges done
-    const double enq0 = getenv("SWT_TRAIN_DEBUG") ? host_now() : 0.0;
-    for (uint32_t i = 0; i < steps; i++) {
+    const double enq0 = out.debug ? host_now() : 0.0;
+    for (uint32_t i = 0; i < trip.steps; i++) {
       t->step_no++;
-      if (fast) {
-        t->enqueue_fast_step(first_merged + done, cap);
+      if (trip.fast) {
+        t->enqueue_fast_step(first_merged + out.done, trip.cap);
         continue;
       }
       if (wp_fused) {  // WordPiece, a short list: argmax + tie-break + decision in one launch
         hipLaunchKernelGGL(wp_step_kernel, dim3(kWpStepBlocks), dim3(kTrainThreads), 0, t->stream, t->d_sym, t->d_woff, t->n_words, t->ctx(),
-                           t->d_cmd, t->d_steplog, i, first_merged + done + i);
+                           t->d_cmd, t->d_steplog, i, first_merged + out.done + i);
         hipLaunchKernelGGL(apply_kernel, dim3(kFastApplyBlocks), dim3(kTrainThreads), 0, t->stream, t->d_sym, t->d_woff, t->d_freq, t->n_words,
                            t->ctx(), t->d_cmd);
         continue;
       }
       t->enqueue_argmax();
       hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(64), 0, t->stream, t->d_sym, t->d_woff, t->ctx(), t->d_parts, t->n_parts, t->d_cmd,
-                         t->d_steplog, i, first_merged + done + i);
+                         t->d_steplog, i, first_merged + out.done + i);
       t->enqueue_apply();
     }
     prof_end(t->stream);
-    const double enq1 = getenv("SWT_TRAIN_DEBUG") ? host_now() : 0.0;
+    const double enq1 = out.debug ? host_now() : 0.0;
     SWT_HIP(hipGetLastError());
-    if (cap > kMaxRunSteps) return fail(SWT_ERR_STATE, "a round trip was sized beyond the step log (%u rows)", cap);
-    SWT_HIP(hipMemcpyAsync(hlog.data(), t->d_steplog, cap * sizeof(StepLog), hipMemcpyDeviceToHost, t->stream));
+    if (trip.cap > kMaxRunSteps) return fail(SWT_ERR_STATE, "a round trip was sized beyond the step log (%u rows)", trip.cap);
+    SWT_HIP(hipMemcpyAsync(hlog.data(), t->d_steplog, trip.cap * sizeof(StepLog), hipMemcpyDeviceToHost, t->stream));
     if ((rc = t->sync_state()) || (rc = t->check_state())) return rc;
-    uint32_t good = 0;
-    unsigned long long stop = 0;  // why the device stopped before `cap`: 0 (it did not), 2 no pair left, 3 re-plan
-    if (fast) {
-      const unsigned long long logged = t->h_st.run_done[(t->step_no + 1) & 1u];
-      if (logged > cap) return fail(SWT_ERR_STATE, "the step log overran its round trip");
-      good = (uint32_t)logged;
-      stop = t->h_st.halt;
-      for (uint32_t i = 0; i < good; i++)
-        if (hlog[i].flag != 0) return fail(SWT_ERR_STATE, "the step log has a hole");
-    } else {
-      while (good < cap && hlog[good].flag == 0) good++;
-      if (good < cap) stop = hlog[good].flag;
-    }
-    for (uint32_t i = 0; i < good; i++) {
-      left[done] = hlog[i].l;
-      right[done] = hlog[i].r;
-      count[done] = hlog[i].count;
-      t->trace.push_back(hlog[i]);
-      done++;
-    }
-    if (getenv("SWT_TRAIN_DEBUG"))
-      fprintf(stderr, "trip: steps %u (host enqueue %.1f us) cap %u -> %u merges, stop %llu, per_step %.2f, listed %llu since %llu ratio %.2f, max %llu theta %llu\n", steps,
-              (enq1 - enq0) * 1e6, cap, good, stop, per_step, (unsigned long long)t->cand_built, (unsigned long long)t->since_replan, t->dry_ratio,
-              (unsigned long long)(good ? hlog[good - 1].count : 0), (unsigned long long)t->theta);
-    t->n_applied += good;
-    t->since_replan += good;
-    if (good && !t->d_sfreq) t->h_st.max_count = hlog[good - 1].count;  // counts never grow: bound for the next batch
-    if (stop == 3) {  // the candidate list ran dry: later steps of the batch were no-ops; new theta, go on
-      if (fast && t->theta > 1 && t->cand_built && t->since_replan) {
-        t->dry_ratio = 0.9 * (double)t->since_replan / (double)t->cand_built;
-        t->dry_ratio = t->dry_ratio < 0.3 ? 0.3 : (t->dry_ratio > 2.0 ? 2.0 : t->dry_ratio);
-      }
-      t->cand_valid = false;
-      if (!good && ++dry_runs > 64) return fail(SWT_ERR_STATE, "the candidate list cannot be rebuilt");
-    } else if (stop) {
-      exhausted = true;  // bpe.py:98-99: no pair left
-    }
-    if (fast && good && t->h_st.run_active) {
-      // what a working step carried (the steps after a dry point or a full log do nothing and do not count)
-      per_step = (double)good / (double)t->h_st.run_active;
-      if (per_step < 1.0) per_step = 1.0;
-      if (per_step > (double)kMaxBatch) per_step = (double)kMaxBatch;
-    }
-    if (good) dry_runs = 0;
+    TripResult res;
+    if ((rc = trainer_harvest_trip(&t, 1, hlog.data(), trip, enq1 - enq0, &out, &res))) return rc;
+    exhausted = res.stop == 2;  // bpe.py:98-99: no pair left (the device stops a trip for 2 or 3 only)
   }
-  *n_done = done;
+  *n_done = out.done;
   return SWT_OK;
 } SWT_API_CATCH
 
@@ -3574,19 +3435,6 @@ int trainer_add_records(swt_bpe_trainer *t, const DeltaRec *d_recs, uint64_t n) 
   return t->sync_state();
 }
 
-int trainer_prepare_batch(swt_bpe_trainer *t, uint32_t k, uint32_t max_merged) {
-  int rc = t->sync_state();
-  if (rc) return rc;
-  // every rank's new pairs land in every replica: the bound is over the whole corpus
-  const uint64_t by_sym = 2 * (t->n_base_global + t->n_applied + k + 1) + 1;
-  uint64_t per = t->h_st.max_count ? 2 * t->h_st.max_count : by_sym;
-  if (by_sym < per) per = by_sym;
-  if ((rc = ensure_room(t, per * k))) return rc;
-  if ((rc = ensure_steps(t, k, max_merged))) return rc;
-  if ((!t->cand_valid || !t->theta) && (rc = t->replan())) return rc;
-  return SWT_OK;
-}
-
 void trainer_enqueue_tie_send(swt_bpe_trainer *t) {
   t->enqueue_argmax();
   hipLaunchKernelGGL(tie_send_kernel, dim3(1), dim3(64), 0, t->stream, t->ctx(), t->d_parts, t->n_parts, t->d_sym, t->d_woff, t->d_tie_line);
@@ -3603,12 +3451,13 @@ void trainer_enqueue_decide_apply(swt_bpe_trainer *t, uint32_t rank, uint32_t lo
   trainer_enqueue_pack(t);
 }
 
-// ---- the sharded fast path: the host side of one round trip (the sizing rules of swt_bpe_train_run, over the whole corpus) ----
-// Every number below is a function of state that is the same on every rank (the counts, theta, the candidate list's length,
-// the merges done) -- except whether this rank's table had to grow, which voids its candidate list: that is why the runner
-// ORs `replan_first` over the ranks and all of them re-plan together, or their dry-point estimates would drift apart and
-// they would enqueue different numbers of steps.
-static void fast_trip_size(const swt_bpe_trainer *t, uint32_t remaining, double per_step, ShardTrip *trip) {
+// ---- one host round trip: its size, its harvest (swt_bpe_train_run and the sharded runner of swt_dist.hip) -------------------
+// Sharded, every number below is a function of state that is the same on every rank (the counts, theta, the candidate list's
+// length, the merges done) -- except whether this rank's table had to grow, which voids its candidate list: that is why the
+// runner ORs `replan_first` over the ranks and all of them re-plan together, or their dry-point estimates would drift apart
+// and they would enqueue different numbers of steps.
+// `steps` launch sequences of the fast path, which have carried `per_step` merges each lately, and the merges they may log
+void trainer_trip_size(uint32_t remaining, double per_step, ShardTrip *trip) {
   uint32_t steps = remaining < kRunBatch ? remaining : kRunBatch;
   const double want = (double)remaining / per_step * 1.05 + 1.0;
   if (want < (double)steps) steps = (uint32_t)want;
@@ -3622,10 +3471,29 @@ static void fast_trip_size(const swt_bpe_trainer *t, uint32_t remaining, double 
   trip->cap = cap;
 }
 
+// A list that runs dry in mid trip turns the rest of the trip into steps that do nothing (two launches each).  A list of n
+// pairs has been good for about dry_ratio * n merges: the trip ends there, and the next one starts with a new threshold.
+// true: that point is too near -- re-plan now (a cheaper stop than a dry trip).
+bool trainer_dry_point(swt_bpe_trainer *t, uint32_t remaining, double per_step, ShardTrip *trip) {
+  if (t->theta <= 1 || !t->cand_built) return false;
+  const double budget = t->dry_ratio * (double)t->cand_built - (double)t->since_replan;
+  if (budget < 24.0 && (double)remaining > budget && t->since_replan) {
+    if (t->dry_ratio < 2.0) t->dry_ratio *= 1.1;  // it never ran dry: the list may be good for more than was thought
+    return true;
+  }
+  const double most = budget / per_step + 1.0;
+  if (most < (double)trip->steps) {
+    trip->steps = most < 8.0 ? 8u : (uint32_t)most;
+    if (trip->steps > remaining) trip->steps = remaining;
+    if (trip->cap > trip->steps * kMaxBatch) trip->cap = trip->steps * kMaxBatch;
+  }
+  return false;
+}
+
 int trainer_fast_room(swt_bpe_trainer *t, uint32_t remaining, double per_step, ShardTrip *trip) {
   int rc;
-  fast_trip_size(t, remaining, per_step, trip);
-  // every rank's new pairs land in every replica: the bound is over the whole corpus (trainer_prepare_batch)
+  trainer_trip_size(remaining, per_step, trip);
+  // every rank's new pairs land in every replica: the bound is over the whole corpus
   const uint64_t by_sym = 2 * (t->n_base_global + t->n_applied + trip->cap + 1) + 1;
   uint64_t per = t->h_st.max_count ? 2 * t->h_st.max_count : by_sym;
   if (by_sym < per) per = by_sym;
@@ -3634,30 +3502,19 @@ int trainer_fast_room(swt_bpe_trainer *t, uint32_t remaining, double per_step, S
   return SWT_OK;
 }
 
-int trainer_fast_plan(swt_bpe_trainer *t, uint32_t remaining, double per_step, bool replan, uint32_t first_id, ShardTrip *trip) {
+// `generic`: the one-merge-per-step form is asked for (SWT_DIST_GENERIC)
+int trainer_fast_plan(swt_bpe_trainer *t, uint32_t remaining, double per_step, bool replan, bool generic, uint32_t first_id, ShardTrip *trip) {
   int rc;
   for (int pass = 0;; pass++) {
     if (replan && (rc = t->replan())) return rc;
-    fast_trip_size(t, remaining, per_step, trip);
-    trip->fast = t->theta != 0;
+    trainer_trip_size(remaining, per_step, trip);
+    trip->fast = t->theta != 0 && !generic;
     if (!trip->fast) {  // a plateau wider than the list: the generic step with the full-table argmax until the next re-plan
       if (trip->steps > remaining) trip->steps = remaining;
       trip->cap = trip->steps;
-      return ensure_steps(t, trip->steps, first_id + trip->cap);
-    }
-    if (t->theta > 1 && t->cand_built && pass == 0) {  // the dry point of the list (swt_bpe_train_run)
-      const double budget = t->dry_ratio * (double)t->cand_built - (double)t->since_replan;
-      if (budget < 24.0 && (double)remaining > budget && t->since_replan) {
-        if (t->dry_ratio < 2.0) t->dry_ratio *= 1.1;
-        replan = true;
-        continue;
-      }
-      const double most = budget / per_step + 1.0;
-      if (most < (double)trip->steps) {
-        trip->steps = most < 8.0 ? 8u : (uint32_t)most;
-        if (trip->steps > remaining) trip->steps = remaining;
-        if (trip->cap > trip->steps * kMaxBatch) trip->cap = trip->steps * kMaxBatch;
-      }
+    } else if (pass == 0 && trainer_dry_point(t, remaining, per_step, trip)) {
+      replan = true;
+      continue;
     }
     return ensure_steps(t, trip->steps, first_id + trip->cap);
   }
@@ -3666,10 +3523,68 @@ int trainer_fast_plan(swt_bpe_trainer *t, uint32_t remaining, double per_step, b
 // the step counters of the fast path start from zero, and no position of an earlier round trip is left
 int trainer_fast_begin(swt_bpe_trainer *t) {
   SWT_HIP(hipMemsetAsync(&t->d_st->run_done[0], 0, 8 * 8, t->stream));
-  SWT_HIP(hipMemsetAsync(&t->d_st->best2[0], 0xFF, 2 * 8, t->stream));
+  SWT_HIP(hipMemsetAsync(&t->d_st->best2[0], 0xFF, 2 * 8, t->stream));  // steps that did nothing may have left either parity behind
   SWT_HIP(hipMemsetAsync(t->d_gpos, 0xFF, 2 * (size_t)t->cand_cap * 8, t->stream));
   SWT_HIP(hipMemsetAsync(t->d_gnb_min, 0xFF, 4 * (size_t)t->cand_cap * 4, t->stream));
   SWT_HIP(hipMemsetAsync(t->d_gnb_max, 0, 4 * (size_t)t->cand_cap * 4, t->stream));
+  return SWT_OK;
+}
+
+// After the round trip's synchronisation and check_state(): what the device logged, taken into the caller's outputs and into
+// the `n` trainers of this process (tr[0] holds the log and the counters; sharded, every trainer keeps the same books).
+// good: merges logged; stop: why the device stopped before `cap` -- 0 (it did not), 2 no pair left, 3 the candidate list ran
+// dry or was lost: later steps of the trip were no-ops, the next trip re-plans; 4 is the sharded runner's (an exchange to
+// repeat) and changes nothing here.
+int trainer_harvest_trip(swt_bpe_trainer *const *tr, uint32_t n, const StepLog *hlog, const ShardTrip &trip, double enqueue_s,
+                         RunOut *out, TripResult *res) {
+  const swt_bpe_trainer *t0 = tr[0];
+  uint32_t good = 0;
+  unsigned long long stop = 0;
+  if (trip.fast) {
+    const unsigned long long logged = t0->h_st.run_done[(t0->step_no + 1) & 1u];
+    if (logged > trip.cap) return fail(SWT_ERR_STATE, "the step log overran its round trip");
+    good = (uint32_t)logged;
+    stop = t0->h_st.halt;
+    for (uint32_t i = 0; i < good; i++)
+      if (hlog[i].flag != 0) return fail(SWT_ERR_STATE, "the step log has a hole");
+  } else {
+    while (good < trip.cap && hlog[good].flag == 0) good++;
+    if (good < trip.cap) stop = hlog[good].flag;
+  }
+  for (uint32_t g = 0; g < good; g++) {
+    out->left[out->done] = hlog[g].l;
+    out->right[out->done] = hlog[g].r;
+    out->count[out->done] = hlog[g].count;
+    for (uint32_t i = 0; i < n; i++) tr[i]->trace.push_back(hlog[g]);
+    out->done++;
+  }
+  if (out->debug)
+    fprintf(stderr, "trip: steps %u (host enqueue %.1f us) cap %u -> %u merges, stop %llu, per_step %.2f, listed %llu since %llu ratio %.2f, max %llu theta %llu\n",
+            trip.steps, enqueue_s * 1e6, trip.cap, good, stop, out->per_step, (unsigned long long)t0->cand_built, (unsigned long long)t0->since_replan,
+            t0->dry_ratio, (unsigned long long)(good ? hlog[good - 1].count : 0), (unsigned long long)t0->theta);
+  for (uint32_t i = 0; i < n; i++) {
+    swt_bpe_trainer *t = tr[i];
+    t->n_applied += good;
+    t->since_replan += good;
+    if (good && !t->d_sfreq) t->h_st.max_count = hlog[good - 1].count;  // counts never grow: bound for the next trip (WordPiece: a score)
+    if (stop == 3) {
+      if (trip.fast && t->theta > 1 && t->cand_built && t->since_replan) {
+        t->dry_ratio = 0.9 * (double)t->since_replan / (double)t->cand_built;
+        t->dry_ratio = t->dry_ratio < 0.3 ? 0.3 : (t->dry_ratio > 2.0 ? 2.0 : t->dry_ratio);
+      }
+      t->cand_valid = false;
+    }
+  }
+  if (trip.fast && good && t0->h_st.run_active) {
+    // what a working step carried (the steps after a dry point or a full log do nothing and do not count)
+    out->per_step = (double)good / (double)t0->h_st.run_active;
+    if (out->per_step < 1.0) out->per_step = 1.0;
+    if (out->per_step > (double)kMaxBatch) out->per_step = (double)kMaxBatch;
+  }
+  if (good) out->dry_runs = 0;
+  else if (stop == 3 && ++out->dry_runs > 64) return fail(SWT_ERR_STATE, "the candidate list cannot be rebuilt");
+  res->good = good;
+  res->stop = stop;
   return SWT_OK;
 }
 

@@ -320,17 +320,16 @@ static int enqueue_generic_steps(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_l
 // The fast path, sharded: per STEP fast_tie + tie_pack -> ONE all-gather of the ranks' tie messages (sizeof(TieMsg) bytes each)
 // -> fast_apply_sharded (every rank derives the same batch of up to 16 tied merges) + pack -> ONE all-gather of the record
 // blocks -> add + finish.  Up to 256 steps per host round trip, nothing synchronises in between.
-static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local, uint32_t max_steps, uint32_t first_merged, uint32_t *left,
-                            uint32_t *right, uint64_t *count, uint32_t *n_done) {
+// `generic`: every trip takes the one-merge-per-step form instead (SWT_DIST_GENERIC=1: the comparison form).
+static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local, bool generic, uint32_t max_steps, uint32_t first_merged,
+                            uint32_t *left, uint32_t *right, uint64_t *count, uint32_t *n_done) {
   int rc;
   std::vector<StepLog> hlog(kMaxRunSteps);
-  uint32_t done = 0;
+  RunOut out{left, right, count, 0, 0, 1.0, getenv("SWT_TRAIN_DEBUG") != nullptr};
   bool exhausted = false;
-  int dry_runs = 0;
-  double per_step = 1.0;
   int deferred_rc = 0;  // an error found after a trip: it leaves through the gather below, so that EVERY rank leaves
-  while (done < max_steps && !exhausted) {
-    const uint32_t remaining = max_steps - done;
+  while (out.done < max_steps && !exhausted) {
+    const uint32_t remaining = max_steps - out.done;
     // head room on every local trainer; does any rank need a re-plan (its table grew, its list is long)?  All or none.
     // An error on one rank (a capacity check, an allocation) must not leave the others waiting in a collective: the ranks
     // exchange a status byte with the re-plan bit, and all of them return when one of them failed.
@@ -339,7 +338,7 @@ static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local,
     int local_rc = deferred_rc;
     for (uint32_t i = 0; i < n_local && !local_rc; i++) {
       if ((local_rc = tr[i]->sync_state()) || (local_rc = tr[i]->check_state())) break;
-      if ((local_rc = trainer_fast_room(tr[i], remaining, per_step, &trips[i]))) break;
+      if ((local_rc = trainer_fast_room(tr[i], remaining, out.per_step, &trips[i]))) break;
       msg[0] |= trips[i].replan_first ? 1 : 0;
     }
     msg[1] = local_rc ? 1 : 0;
@@ -358,7 +357,7 @@ static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local,
     }
     const uint8_t want = msg[0];
     for (uint32_t i = 0; i < n_local; i++)
-      if ((rc = trainer_fast_plan(tr[i], remaining, per_step, want != 0, first_merged + done, &trips[i]))) return rc;
+      if ((rc = trainer_fast_plan(tr[i], remaining, out.per_step, want != 0, generic, first_merged + out.done, &trips[i]))) return rc;
     const ShardTrip trip = trips[0];
     for (uint32_t i = 1; i < n_local; i++)
       if (trips[i].steps != trip.steps || trips[i].cap != trip.cap || trips[i].fast != trip.fast)
@@ -382,6 +381,7 @@ static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local,
         }
     }
     prof_begin(tr[0]->stream);
+    const double enq0 = out.debug ? host_now() : 0.0;
     if (trip.fast) {
       for (uint32_t i = 0; i < n_local; i++)
         if ((rc = trainer_fast_begin(tr[i]))) return rc;
@@ -394,75 +394,39 @@ static int run_sharded_fast(swt_dist *d, swt_bpe_trainer **tr, uint32_t n_local,
         if ((rc = gather_dev(d, tr, n_local, sizeof(TieMsg), [](swt_bpe_trainer *t) { return (const void *)t->d_tie_msg; },
                              [](swt_bpe_trainer *t) { return (void *)t->d_tie_msgs; })))
           return rc;
-        for (uint32_t i = 0; i < n_local; i++) trainer_enqueue_fast_apply(tr[i], first_merged + done, trip.cap);
+        for (uint32_t i = 0; i < n_local; i++) trainer_enqueue_fast_apply(tr[i], first_merged + out.done, trip.cap);
         if ((rc = gather_dev(d, tr, n_local, tr[0]->block_cap * sizeof(DeltaRec), [](swt_bpe_trainer *t) { return (const void *)t->d_block; },
                              [](swt_bpe_trainer *t) { return (void *)t->d_blocks_all; })))
           return rc;
         for (uint32_t i = 0; i < n_local; i++) trainer_enqueue_add_blocks(tr[i]);
       }
-    } else if ((rc = enqueue_generic_steps(d, tr, n_local, trip.steps, first_merged + done))) {
+    } else if ((rc = enqueue_generic_steps(d, tr, n_local, trip.steps, first_merged + out.done))) {
       return rc;
     }
     prof_end(tr[0]->stream);
+    const double enq1 = out.debug ? host_now() : 0.0;
     SWT_HIP(hipGetLastError());
     unsigned int halt = 0;
     SWT_HIP(hipMemcpyAsync(hlog.data(), tr[0]->d_steplog, trip.cap * sizeof(StepLog), hipMemcpyDeviceToHost, tr[0]->stream));
     SWT_HIP(hipMemcpyAsync(&halt, tr[0]->d_halt, 4, hipMemcpyDeviceToHost, tr[0]->stream));
     for (uint32_t i = 0; i < n_local && !deferred_rc; i++)
       if ((deferred_rc = tr[i]->sync_state()) || (deferred_rc = tr[i]->check_state())) break;
-    if (deferred_rc) continue;  // (through the status gather at the top)
-    uint32_t good = 0;
-    unsigned long long stop = 0;  // 0, 2 no pair left, 3 re-plan
-    if (trip.fast) {
-      const unsigned long long logged = tr[0]->h_st.run_done[(tr[0]->step_no + 1) & 1u];
-      if (logged > trip.cap) { deferred_rc = fail(SWT_ERR_STATE, "the step log overran its round trip"); continue; }
-      good = (uint32_t)logged;
-      stop = tr[0]->h_st.halt;
-      for (uint32_t i = 0; i < good && !deferred_rc; i++)
-        if (hlog[i].flag != 0) deferred_rc = fail(SWT_ERR_STATE, "the step log has a hole");
-      for (uint32_t i = 1; i < n_local && !deferred_rc; i++)
-        if (tr[i]->h_st.run_done[(tr[i]->step_no + 1) & 1u] != logged)
-          deferred_rc = fail(SWT_ERR_STATE, "the shards logged different numbers of merges: their replicas have diverged");
-      if (deferred_rc) continue;
-    } else {
-      while (good < trip.cap && hlog[good].flag == 0) good++;
-      if (good < trip.cap && hlog[good].flag != 4) stop = hlog[good].flag;
-    }
-    for (uint32_t g = 0; g < good; g++) {
-      left[done] = hlog[g].l;
-      right[done] = hlog[g].r;
-      count[done] = hlog[g].count;
-      for (uint32_t i = 0; i < n_local; i++) tr[i]->trace.push_back(hlog[g]);
-      done++;
-    }
-    for (uint32_t i = 0; i < n_local; i++) {
-      swt_bpe_trainer *t = tr[i];
-      t->n_applied += good;
-      t->since_replan += good;
-      if (good) t->h_st.max_count = hlog[good - 1].count;
-      if (stop == 3) {
-        if (trip.fast && t->theta > 1 && t->cand_built && t->since_replan) {
-          t->dry_ratio = 0.9 * (double)t->since_replan / (double)t->cand_built;
-          t->dry_ratio = t->dry_ratio < 0.3 ? 0.3 : (t->dry_ratio > 2.0 ? 2.0 : t->dry_ratio);
-        }
-        t->cand_valid = false;
-      }
-    }
-    if (halt) {  // the last step was applied everywhere but its deltas did not fit: bigger blocks, that exchange again
-      if ((rc = exchange_again(d, tr, n_local))) return rc;
-    } else if (stop == 3) {
-      if (!good && ++dry_runs > 64) return fail(SWT_ERR_STATE, "the candidate list cannot be rebuilt");
-    } else if (stop) {
-      exhausted = true;  // bpe.py:98-99: no pair left anywhere
-    }
-    if (trip.fast && good && tr[0]->h_st.run_active) {
-      per_step = (double)good / (double)tr[0]->h_st.run_active;
-      if (per_step < 1.0) per_step = 1.0;
-      if (per_step > (double)kMaxBatch) per_step = (double)kMaxBatch;
-    }
-    if (good) dry_runs = 0;
+    for (uint32_t i = 1; i < n_local && !deferred_rc && trip.fast; i++)
+      if (tr[i]->h_st.run_done[(tr[i]->step_no + 1) & 1u] != tr[0]->h_st.run_done[(tr[0]->step_no + 1) & 1u])
+        deferred_rc = fail(SWT_ERR_STATE, "the shards logged different numbers of merges: their replicas have diverged");
+    TripResult res;
+    if (deferred_rc || (deferred_rc = trainer_harvest_trip(tr, n_local, hlog.data(), trip, enq1 - enq0, &out, &res)))
+      continue;  // (through the status gather at the top -- the harvest's "candidate list cannot be rebuilt" too, which used to
+                 // return from here directly: every rank meets it in the same trip, and now all of them leave together)
+    // a step logged flag 4, or the fast steps went idle: the last step was applied everywhere but its deltas did not fit --
+    // bigger blocks, that exchange again.  A halted trip and a stop of 2 or 3 exclude each other, so the harvest may act on
+    // `stop` without knowing of `halt`: a generic step that meets the halt logs 4, which the harvest passes by; a fast step
+    // that meets halt_ext is idle and never sets st->halt, and a step that set st->halt (2: it merged nothing, 3: before its
+    // apply) sent no deltas that could overflow; the overflowing step itself logged its merges, so good > 0.
+    if (halt && (rc = exchange_again(d, tr, n_local))) return rc;
+    exhausted = res.stop == 2;  // bpe.py:98-99: no pair left anywhere
   }
-  *n_done = done;
+  *n_done = out.done;
   return SWT_OK;
 }
 
@@ -476,67 +440,9 @@ int swt_bpe_train_run_sharded(swt_bpe_trainer **tr, uint32_t n_local, swt_dist *
     if (!tr[i]->sharded) return fail(SWT_ERR_STATE, "call swt_bpe_train_shard_begin first");
   if ((uint64_t)first_merged + max_steps >= 0xFFFFFFFFull) return fail(SWT_ERR_UNSUPPORTED, "merged symbol ids would reach the reserved id");
   *n_done = 0;
-  // SWT_DIST_GENERIC=1: the one-merge-per-step runner of round 2 (kept for comparison and as the fallback form)
+  // SWT_DIST_GENERIC=1: one merge per step throughout (kept for comparison; read at every call: tests switch it in mid process)
   const char *generic = getenv("SWT_DIST_GENERIC");
-  if (!generic || !*generic || *generic == '0') return run_sharded_fast(d, tr, n_local, max_steps, first_merged, left, right, count, n_done);
-  std::vector<StepLog> hlog(kMaxRunSteps);
-  uint32_t done = 0;
-  bool exhausted = false;
-  int dry_runs = 0;
-  while (done < max_steps && !exhausted) {
-    uint32_t k = max_steps - done;
-    if (k > kRunBatch) k = kRunBatch;
-    for (uint32_t i = 0; i < n_local; i++)
-      if ((rc = trainer_prepare_batch(tr[i], k, first_merged + done + k))) return rc;
-    prof_begin(tr[0]->stream);
-    for (uint32_t s = 0; s < k; s++) {
-      for (uint32_t i = 0; i < n_local; i++) {
-        tr[i]->step_no++;
-        trainer_enqueue_tie_send(tr[i]);
-      }
-      if ((rc = gather_dev(d, tr, n_local, 16, [](swt_bpe_trainer *t) { return (const void *)t->d_tie_line; },
-                           [](swt_bpe_trainer *t) { return (void *)t->d_tie_all; })))
-        return rc;
-      for (uint32_t i = 0; i < n_local; i++) trainer_enqueue_decide_apply(tr[i], (uint32_t)rank_of(d, i), s, first_merged + done + s);
-      if ((rc = gather_dev(d, tr, n_local, tr[0]->block_cap * sizeof(DeltaRec), [](swt_bpe_trainer *t) { return (const void *)t->d_block; },
-                           [](swt_bpe_trainer *t) { return (void *)t->d_blocks_all; })))
-        return rc;
-      for (uint32_t i = 0; i < n_local; i++) trainer_enqueue_add_blocks(tr[i]);
-    }
-    prof_end(tr[0]->stream);
-    SWT_HIP(hipGetLastError());
-    unsigned int halt = 0;
-    SWT_HIP(hipMemcpyAsync(hlog.data(), tr[0]->d_steplog, k * sizeof(StepLog), hipMemcpyDeviceToHost, tr[0]->stream));
-    SWT_HIP(hipMemcpyAsync(&halt, tr[0]->d_halt, 4, hipMemcpyDeviceToHost, tr[0]->stream));
-    for (uint32_t i = 0; i < n_local; i++)
-      if ((rc = tr[i]->sync_state()) || (rc = tr[i]->check_state())) return rc;
-    uint32_t good = 0;
-    while (good < k && hlog[good].flag == 0) {
-      left[done] = hlog[good].l;
-      right[done] = hlog[good].r;
-      count[done] = hlog[good].count;
-      for (uint32_t i = 0; i < n_local; i++) tr[i]->trace.push_back(hlog[good]);
-      done++;
-      good++;
-    }
-    for (uint32_t i = 0; i < n_local; i++) {
-      tr[i]->n_applied += good;
-      if (good) tr[i]->h_st.max_count = hlog[good - 1].count;
-    }
-    if (halt) {  // the last good merge was applied everywhere but its deltas did not fit: bigger blocks, that exchange again
-      if ((rc = exchange_again(d, tr, n_local))) return rc;
-    } else if (good < k) {
-      if (hlog[good].flag == 3) {
-        for (uint32_t i = 0; i < n_local; i++) tr[i]->cand_valid = false;
-        if (!good && ++dry_runs > 64) return fail(SWT_ERR_STATE, "the candidate list cannot be rebuilt");
-      } else {
-        exhausted = true;  // bpe.py:98-99: no pair left anywhere
-      }
-    }
-    if (good) dry_runs = 0;
-  }
-  *n_done = done;
-  return SWT_OK;
+  return run_sharded_fast(d, tr, n_local, generic && *generic && *generic != '0', max_steps, first_merged, left, right, count, n_done);
 } SWT_API_CATCH
 
 }  // extern "C"

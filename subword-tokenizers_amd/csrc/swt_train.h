@@ -45,7 +45,6 @@ struct TrainState {
   unsigned long long n_used;     // distinct keys in the table
   unsigned long long res_pos;    //   position of the tie winner in this shard (kEmptyKey: not tied / not here)
   unsigned long long n_syms;     // live symbols
-  unsigned long long win_key;
   unsigned long long n_cand;     // candidate list length
   unsigned long long idx_cursor; // entries in the index log
   unsigned long long plateau;    // count level the tie cursor holds for
@@ -258,16 +257,25 @@ int trainer_enter_sharded(swt_bpe_trainer *t, uint32_t world, uint64_t block_cap
 int trainer_set_block_cap(swt_bpe_trainer *t, uint64_t block_cap);
 int trainer_export_records(swt_bpe_trainer *t, DeltaRec *d_out, uint64_t cap, uint64_t *n);
 int trainer_add_records(swt_bpe_trainer *t, const DeltaRec *d_recs, uint64_t n);
-int trainer_prepare_batch(swt_bpe_trainer *t, uint32_t k, uint32_t max_merged);
 void trainer_enqueue_tie_send(swt_bpe_trainer *t);
 void trainer_enqueue_decide_apply(swt_bpe_trainer *t, uint32_t rank, uint32_t log_i, uint32_t merged);
 void trainer_enqueue_pack(swt_bpe_trainer *t);
 void trainer_enqueue_add_blocks(swt_bpe_trainer *t);
-// the fast two-launch step, sharded (several tied merges per step; see fast_apply_sharded_kernel)
+// one host round trip: `steps` launch sequences that may log up to `cap` merges; fast: the two-launch step that carries
+// several tied merges (fast_apply_kernel, fast_apply_sharded_kernel), else one merge per step
 struct ShardTrip { uint32_t steps, cap; bool replan_first, fast; };
+// where a run's merges go and what it carries from trip to trip (per_step: merges a step of the fast path has carried
+// lately, which sizes the next trip; debug: SWT_TRAIN_DEBUG); what one trip's log came to
+struct RunOut { uint32_t *left, *right; uint64_t *count; uint32_t done; int dry_runs; double per_step; bool debug; };
+struct TripResult { uint32_t good; unsigned long long stop; };
+double host_now();  // monotonic seconds (what the SWT_TRAIN_DEBUG line times the host's enqueue with)
+void trainer_trip_size(uint32_t remaining, double per_step, ShardTrip *trip);
+bool trainer_dry_point(swt_bpe_trainer *t, uint32_t remaining, double per_step, ShardTrip *trip);
 int trainer_fast_room(swt_bpe_trainer *t, uint32_t remaining, double per_step, ShardTrip *trip);  // head room, wants a re-plan?
-int trainer_fast_plan(swt_bpe_trainer *t, uint32_t remaining, double per_step, bool replan, uint32_t first_id, ShardTrip *trip);
+int trainer_fast_plan(swt_bpe_trainer *t, uint32_t remaining, double per_step, bool replan, bool generic, uint32_t first_id, ShardTrip *trip);
 int trainer_fast_begin(swt_bpe_trainer *t);
+int trainer_harvest_trip(swt_bpe_trainer *const *tr, uint32_t n, const StepLog *hlog, const ShardTrip &trip, double enqueue_s,
+                         RunOut *out, TripResult *res);
 void trainer_enqueue_fast_tie(swt_bpe_trainer *t, uint32_t limit);
 void trainer_enqueue_fast_apply(swt_bpe_trainer *t, uint32_t first_merged, uint32_t limit);
 }  // namespace swt

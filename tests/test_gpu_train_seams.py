@@ -281,11 +281,26 @@ def test_wordpiece_seams(swt, dev, oracle, monkeypatch, kind, generic):
 
 # ---------------------------------------------------------------------------------------------------------------- sharded
 
-@pytest.mark.parametrize("cuts", [(0.4,), (0.0,), (0.3, 0.3), (0.5, 1.0)], ids=["2", "2_first_empty", "3_middle_empty", "3_last_empty"])
-@pytest.mark.parametrize("name", T.SHARDED)
-def test_sharded_seams(dev, oracle, monkeypatch, name, cuts):
-    """the same words cut into 2 and 3 contiguous ranges (one of them empty) through the loop-back communicator, fast form"""
-    monkeypatch.setenv("SWT_DIST_GENERIC", "0")
+def _rank0_live_before(sym, off, n_words0, ids):
+    """live symbols in the first n_words0 words before every merge of `ids` (l, r, m): the recount model on rank 0's words"""
+    model = T.RecountModel(sym[:int(off[n_words0])], off[:n_words0 + 1], [1] * n_words0)
+    live = []
+    for l, r, m in np.asarray(ids).tolist():
+        live.append(sum(len(w) for w in model.words))
+        model.apply(l, r, m)
+    return live
+
+
+_SHARDED_FAST = [pytest.param(n, c, False, id="%s-%s" % (n, c)) for n in T.SHARDED for c in T.SHARDED_ONLY.get(n, tuple(T.SHARDED_CUTS))]
+_SHARDED_GENERIC = [pytest.param(n, c, True, id="%s-%s-generic" % (n, c)) for n, c in T.SHARDED_GENERIC]
+
+
+@pytest.mark.parametrize("name,cut,generic", _SHARDED_FAST + _SHARDED_GENERIC)
+def test_sharded_seams(dev, oracle, monkeypatch, name, cut, generic):
+    """the same words cut into 2 and 3 contiguous ranges (one of them empty) through the loop-back communicator: the fast
+    form, and for the smallest tied inputs the forced one-merge-per-step form as well"""
+    monkeypatch.setenv("SWT_DIST_GENERIC", "1" if generic else "0")
+    cuts = T.SHARDED_CUTS[cut]
     case = T.BY_NAME[name]
     ref = T.reference(oracle, case)
     sym, off, freq = ref["input"]
@@ -316,7 +331,18 @@ def test_sharded_seams(dev, oracle, monkeypatch, name, cuts):
         # rank 0's log, whose last column is rank 0's live symbols when the step began.  Rows that differ there belong to
         # different steps; rows that agree belong to one step if that step's first pair occurs in rank 0's words, because
         # the step then took symbols from rank 0 and every later step logs fewer.
-        if edges[1] > 0 and name in ("overflow_tied", "plateau_17", "plateau_257"):
+        if generic:
+            # every step size is 1: row k logs rank 0's live symbols before merge k itself, where a step of several merges
+            # logs the count it began with in all its rows.  (step_sizes() cannot say it: two rows agree here whenever the
+            # merge between them left rank 0's words alone, so the rows are held against the recount model of those words.)
+            live = trainers[0].step_trace()[:, 3].astype(np.int64).tolist()
+            want = _rank0_live_before(sym, off, edges[1], ref["ids"])
+            assert want[0] > want[-1] and live == want, (name, cut, live[:8], want[:8])
+        elif name == "cand_8300":
+            for t in trainers:  # the re-plan behind the first merge listed nothing: generic steps inside the fast runner
+                st = t.stats()
+                assert st["theta"] == 0 and st["replans"] >= 2, (name, cut, st)
+        elif edges[1] > 0 and name in ("overflow_tied", "plateau_17", "plateau_257"):
             row = 1 if name == "plateau_257" else 0  # a plateau wider than the tie set opens with a single merge
             key = (int(ref["ids"][row][0]) << 32) | int(ref["ids"][row][1])
             assert key in T.pair_keys(sym[:int(off[edges[1]])], off[:edges[1] + 1])[0].tolist(), "rank 0 does not hold the step's first pair"

@@ -290,7 +290,13 @@ CASES = [
 BY_NAME = {c.name: c for c in CASES}
 
 REUSE = ("long_words", "overflow_tied", "plateau_17")  # the corpora of the id-reuse test (30 merges)
-SHARDED = ("long_words", "overflow_single", "overflow_tied", "plateau_17", "plateau_257")
+SHARDED = ("long_words", "overflow_single", "overflow_tied", "plateau_17", "plateau_257", "cand_8300")
+SHARDED_CUTS = {"2": (0.4,), "2_first_empty": (0.0,), "3_middle_empty": (0.3, 0.3), "3_last_empty": (0.5, 1.0)}  # fractions of the words
+# cand_8300 takes the sharded runner through its other branch: after the first merge 8,300 pairs tie, more than kCandCap / 2,
+# so the re-plan lists nothing (theta = 0) and the rest of the run is generic steps inside the fast runner.  One cut shows it.
+SHARDED_ONLY = {"cand_8300": ("2",)}
+# the forced one-merge-per-step form (SWT_DIST_GENERIC=1): the smallest inputs with ties, with and without an empty rank
+SHARDED_GENERIC = tuple((n, c) for n in ("plateau_17", "overflow_tied") for c in ("2", "3_middle_empty"))
 WP_KINDS = ("long", "overflow", "twin")
 
 
