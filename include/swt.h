@@ -275,6 +275,53 @@ int swt_token_equivalence_dev(const uint32_t *d_ids_a, const uint64_t *d_off_a, 
 int swt_token_equivalence_capacity(uint32_t *wave_cap, uint32_t *block_cap);
 
 /* ------------------------------------------------------------------------------------------------
+ * Token spans on the device: for every token of an id stream, where in its sentence it came from (offset_mapping) and the index
+ * of its pre-tokenizer word (word_ids).  SubwordTokenizer.preprocessing (source/utils.py:15-29) returns (word, (start, end)) per
+ * word; this carries the offsets on to the tokens of NaiveBPE, FastBPE and NaiveWP, whose tokens are grouped by word and tile
+ * it: a token covers as many code points as its string has after the '##', NaiveWP's "[UNK]" its whole word
+ * (source/wordpiece.py:132-159).  FastWP is NOT covered: its segments end where the trie walk ends, not at character classes.
+ *
+ * In: the lowercased text with sent_off[n_sent+1]; ids with tok_off[n_sent+1] (the CSR the encoders return; spans, word and the
+ * ids are indexed by the same token slots tok_off[0] .. tok_off[n_sent]); a length table in the (base, n, flagged) convention of
+ * swt_token_equivalence.  With s = id & 0x7FFFFFFF the token covers
+ *     1 code point                       when s < len_base
+ *     len[s - len_base] & 0xFFFFFF       otherwise; 0 = its whole word (the unknown token); s - len_base >= n_len: no length
+ * and it continues its word when flagged ? bit 31 of the id (SWT_BPE_CONT) : bit 31 of its entry (ids below len_base: never).
+ * (BPE: len_base = SWT_SYM_BASE, flagged = 1.  NaiveWP: len_base = 0, flagged = 0, n_vocab + 2 entries, the last two 0.)
+ *
+ * The text is split by the preprocessing rule over the library's class table: SWT_CLS_BERT_WS code points are dropped, every
+ * SWT_CLS_BERT_PUNCT code point is a word, anything else forms runs.  Generalised UTF-8: surrogates pass through; a lead byte
+ * takes the continuation bytes that follow it, up to its length and the end of its sentence; a continuation byte no lead takes
+ * is one code point.  The k-th word of a sentence belongs to its k-th token group; a group starts at a token that is not a
+ * continuation.
+ *
+ * Out: spans[2 t], spans[2 t + 1] = start and end of token t relative to its sentence's first byte, in bytes, or in code
+ * points with SWT_SPAN_CODEPOINTS; word[t] (may be NULL) = index of its word in the sentence; status[s] = SWT_SPAN_OK, or
+ * SWT_SPAN_MISMATCH when the ids of sentence s do not tile its text: another number of groups than words, a group whose lengths
+ * do not add up to its word, a whole-word token with company in its group, a first token that continues, an id without a
+ * length (or, in the `_dev` form, offsets of the sentence that decrease or pass n_bytes).  Such a sentence gets (0, 0) for
+ * every span and 0 for every word index; it causes no access outside the arrays and leaves its neighbours alone, so the call
+ * is safe with ids made by another table or from another text.
+ *
+ * swt_token_spans: host buffers; SWT_ERR_INVALID for a NULL required pointer, decreasing offsets or a sentence of 2^32 bytes or
+ * more.  The `_dev` form takes device pointers (offsets that do not decrease), writes every entry of its outputs itself,
+ * enqueues on the stream and does not synchronise; its scratch is one grow-only workspace of the process (12 bytes per text
+ * byte), so two calls must not run at the same time on different streams.  swt_token_spans_capacity: the byte sizes at which
+ * the kernel changes form (csrc/swt_spans.hip) -- block: what one wavefront classifies per step (bytes, and tokens), counted from
+ * the sentence's first; chunk: what it stages at a time, likewise; tile: the window of text whose sentence starts one workgroup
+ * owns. */
+#define SWT_SPAN_CODEPOINTS 1u
+#define SWT_SPAN_OK 0
+#define SWT_SPAN_MISMATCH 1
+int swt_token_spans(const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, const uint32_t *ids, const uint64_t *tok_off,
+                    const uint32_t *len, uint32_t len_base, uint32_t n_len, int flagged, uint32_t flags, uint32_t *spans, uint32_t *word,
+                    uint8_t *status);
+int swt_token_spans_dev(const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, const uint32_t *d_ids,
+                        const uint64_t *d_tok_off, const uint32_t *d_len, uint32_t len_base, uint32_t n_len, int flagged, uint32_t flags,
+                        uint32_t *d_spans, uint32_t *d_word, uint8_t *d_status, void *stream);
+int swt_token_spans_capacity(uint32_t *block, uint32_t *chunk, uint32_t *tile);
+
+/* ------------------------------------------------------------------------------------------------
  * BPE training: replaces the merge loop of NaiveBPE.train (source/bpe.py:88-111; FastBPE.train
  * inherits it, source/bpe.py:198-200) and its word dedup (source/bpe.py:73-81).
  *

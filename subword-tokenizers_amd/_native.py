@@ -20,6 +20,10 @@ WP_OK, WP_NONTERMINATING, WP_INDEXERROR = 0, 1, 2
 ERR_NO_DEVICE, ERR_INVALID, ERR_CAPACITY, ERR_HIP, ERR_UNSUPPORTED, ERR_STATE, ERR_NOMEM, ERR_INTERNAL = -1, -2, -3, -4, -5, -6, -7, -8
 CLS_BERT_WS, CLS_BERT_PUNCT, CLS_PY_SPACE, CLS_PY_ALNUM = 1, 2, 4, 8
 NO_POS = 0xFFFFFFFFFFFFFFFF
+SPAN_CODEPOINTS = 1
+SPAN_OK, SPAN_MISMATCH = 0, 1
+SPAN_WHOLE_WORD = 0  # a length-table entry: the token stands for its whole word ("[UNK]")
+SPAN_LEN_CONT = 0x80000000  # a length-table entry of an unflagged stream: the token continues its word ('##')
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -79,6 +83,10 @@ SIGNATURES = {
                                             C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "swt_token_equivalence_capacity": (C.c_int, [u32p, u32p]),
+    "swt_token_spans": (C.c_int, [u8p, u64p, C.c_uint64, u32p, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u32p, u32p, u8p]),
+    "swt_token_spans_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                      C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_token_spans_capacity": (C.c_int, [u32p, u32p, u32p]),
     "swt_bpe_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
     "swt_bpe_train_create_joined": (C.c_int, [u8p, C.c_uint64, C.c_uint64, u8p, vpp]),
     "swt_wp_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
@@ -412,6 +420,53 @@ def token_equivalence(side_a, side_b, weight=None, per_row=False):
     if totals[4]:
         raise ValueError("%d token ids are outside their canonical maps" % int(totals[4]))
     return (totals[:4], rows) if per_row else totals[:4]
+
+
+def token_spans_capacity():
+    """-> (block, chunk, tile): the byte sizes at which the span kernel changes form (csrc/swt_spans.hip): what one wavefront
+    classifies per step and stages at a time, both counted from a sentence's first byte, and the window of text whose sentence
+    starts one workgroup owns"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_token_spans_capacity(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def token_spans(text_u8, off, ids, tok_off, len_table, len_base, flagged, codepoints=True):
+    """Where every token came from, on the device (swt_token_spans): lowercased UTF-8 text with byte offsets[n_sent + 1], ids with
+    their CSR offsets, a length table (include/swt.h) -> (spans uint32[n, 2] = start and end inside the sentence, in code points
+    or bytes; word uint32[n] = index of the token's word in its sentence; status uint8[n_sent], SPAN_OK or SPAN_MISMATCH)."""
+    text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    len_table = np.ascontiguousarray(len_table, dtype=np.uint32)
+    n_sent = int(off.size) - 1
+    if n_sent < 0 or tok_off.size != off.size:
+        raise ValueError("text and ids must have the same sentences")
+    if n_sent and (int(off[-1]) > text_u8.size or int(tok_off[-1]) > ids.size):
+        raise ValueError("offsets run past their array")
+    spans = np.zeros((ids.size, 2), dtype=np.uint32)
+    word = np.zeros(ids.size, dtype=np.uint32)
+    status = np.zeros(n_sent, dtype=np.uint8)
+    check(lib().swt_token_spans(ptr(text_u8, u8p) if text_u8.size else None, ptr(off, u64p), n_sent, ptr(ids, u32p) if ids.size else None,
+                                ptr(tok_off, u64p), ptr(len_table, u32p) if len_table.size else None, int(len_base), int(len_table.size),
+                                int(bool(flagged)), SPAN_CODEPOINTS if codepoints else 0, ptr(spans, u32p) if ids.size else None,
+                                ptr(word, u32p) if ids.size else None, ptr(status, u8p) if n_sent else None))
+    return spans, word, status
+
+
+def bpe_length_table(strings):
+    """The length table of a BPE id stream: code points of every interned symbol string (len_base = SYM_BASE, flagged = 1)."""
+    return np.fromiter(map(len, strings), dtype=np.uint32, count=len(strings))
+
+
+def wp_length_table(tokens):
+    """The length table of a NaiveWP id stream over `tokens` = sorted(vocab): code points after the '##' with SPAN_LEN_CONT on the
+    '##' tokens, then SPAN_WHOLE_WORD for n_vocab ("['UNK']") and n_vocab + 1 ("[UNK]") (len_base = 0, flagged = 0)."""
+    out = np.zeros(len(tokens) + 2, dtype=np.uint32)
+    for i, tok in enumerate(tokens):
+        out[i] = (len(tok) - 2) | SPAN_LEN_CONT if tok.startswith("##") else len(tok)
+    return out
 
 
 class BpeTable:

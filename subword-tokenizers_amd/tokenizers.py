@@ -316,6 +316,40 @@ class NaiveBPE(SubwordTokenizer):
         spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
         return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, off)
 
+    # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
+    def _span_parts(self):
+        """-> (the host-buffer encode of this class, the symbol table its ids are spelled from)"""
+        table = self._ensure_naive_table()
+        return table.encode_naive, self._naive_syms
+
+    def _span_lengths(self, syms) -> np.ndarray:
+        # rebuilt whenever the table it belongs to was: a rebuild makes a new _SymbolTable
+        cached = getattr(self, "_span_len", None)
+        if cached is None or cached[0] is not syms or cached[1] != len(syms.strings):
+            cached = self._span_len = (syms, len(syms.strings), N.bpe_length_table(syms.strings))
+        return cached[2]
+
+    def encode_spans_batch(self, texts: List[str]):
+        """texts -> (ids, offsets, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its (start, end) in
+        code points of text.lower() -- preprocessing's convention (utils.py:27-29) -- and the index of its word in the sentence.
+        The text is packed once and sent to the device twice, for the encode and for swt_token_spans."""
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Text to tokenize must be a string.")
+        encode, syms = self._span_parts()
+        text, off = N.pack_and_lower(texts)
+        ids, tok_off = encode(text, off)
+        spans, word, status = N.token_spans(text, off, ids, tok_off, self._span_lengths(syms), N.SYM_BASE, True)
+        if status.any():
+            raise RuntimeError("token spans: the tokens of text %d do not tile it (a bug in this library)" % int(np.flatnonzero(status)[0]))
+        return ids, tok_off, spans, word
+
+    def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
+        """[(token, (start, end)), ...]: tokenize(text) in the shape of one preprocessing row"""
+        if not isinstance(text, str):
+            raise TypeError("Text to tokenize must be a string.")
+        ids, _, spans, _ = self.encode_spans_batch([text])
+        return [(tok, (int(s), int(e))) for tok, (s, e) in zip(self.decode_ids(ids), spans.tolist())]
+
     # -- bpe.py:160-164
     def reset(self) -> None:
         self.merges_list.clear()
@@ -426,6 +460,9 @@ class FastBPE(NaiveBPE):
         key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit
         spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
         return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, off)
+
+    def _span_parts(self):
+        return self._ensure_table().encode, self._syms
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -636,6 +673,40 @@ class NaiveWP(SubwordTokenizer):
         if bad.size:
             self._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
         return N.nested_lists(self._naive_tokens + ["['UNK']", "[UNK]"], ids, off)
+
+    # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
+    def _span_lengths(self) -> np.ndarray:
+        # rebuilt whenever the trie was: _ensure_naive_trie makes a new token list
+        cached = getattr(self, "_span_len", None)
+        if cached is None or cached[0] is not self._naive_tokens:
+            cached = self._span_len = (self._naive_tokens, N.wp_length_table(self._naive_tokens))
+        return cached[1]
+
+    def encode_spans_batch(self, texts: List[str]):
+        """texts -> (ids, offsets, status, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its
+        (start, end) in code points of text.lower() (utils.py:27-29; "[UNK]" spans its whole word) and the index of its word in
+        the sentence.  A text on which the reference never returns raises as in tokenize_batch.  The text is packed once and sent
+        to the device twice, for the encode and for swt_token_spans."""
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Text to tokenize must be a string.")
+        trie = self._ensure_naive_trie()
+        text, off = N.pack_and_lower(texts)
+        ids, tok_off, status = trie.encode_naive(text, off)
+        bad = np.flatnonzero(status)
+        if bad.size:
+            self._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
+        spans, word, st = N.token_spans(text, off, ids, tok_off, self._span_lengths(), 0, False)
+        if st.any():
+            raise RuntimeError("token spans: the tokens of text %d do not tile it (a bug in this library)" % int(np.flatnonzero(st)[0]))
+        return ids, tok_off, status, spans, word
+
+    def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
+        """[(token, (start, end)), ...]: NaiveWP.tokenize(text) in the shape of one preprocessing row"""
+        if not isinstance(text, str):
+            raise TypeError("Text to tokenize must be a string.")
+        ids, _, _, spans, _ = self.encode_spans_batch([text])
+        names = self._naive_tokens + ["['UNK']", "[UNK]"]
+        return [(names[i], (int(s), int(e))) for i, (s, e) in zip(ids.tolist(), spans.tolist())]
 
     @staticmethod
     def _raise_naive_status(st: int, text: str) -> None:
