@@ -279,7 +279,8 @@ int swt_token_equivalence_capacity(uint32_t *wave_cap, uint32_t *block_cap);
  * of its pre-tokenizer word (word_ids).  SubwordTokenizer.preprocessing (source/utils.py:15-29) returns (word, (start, end)) per
  * word; this carries the offsets on to the tokens of NaiveBPE, FastBPE and NaiveWP, whose tokens are grouped by word and tile
  * it: a token covers as many code points as its string has after the '##', NaiveWP's "[UNK]" its whole word
- * (source/wordpiece.py:132-159).  FastWP is NOT covered: its segments end where the trie walk ends, not at character classes.
+ * (source/wordpiece.py:132-159).  FastWP is NOT covered here: its segments end where the trie walk ends, not at character
+ * classes.  Its spans come out of the walk itself: swt_wp_encode_spans below.
  *
  * In: the lowercased text with sent_off[n_sent+1]; ids with tok_off[n_sent+1] (the CSR the encoders return; spans, word and the
  * ids are indexed by the same token slots tok_off[0] .. tok_off[n_sent]); a length table in the (base, n, flagged) convention of
@@ -320,6 +321,38 @@ int swt_token_spans_dev(const uint8_t *d_text, uint64_t n_bytes, const uint64_t 
                         const uint64_t *d_tok_off, const uint32_t *d_len, uint32_t len_base, uint32_t n_len, int flagged, uint32_t flags,
                         uint32_t *d_spans, uint32_t *d_word, uint8_t *d_status, void *stream);
 int swt_token_spans_capacity(uint32_t *block, uint32_t *chunk, uint32_t *tile);
+
+/* ------------------------------------------------------------------------------------------------
+ * FastWP with token spans: FastWP.tokenize (source/wordpiece.py:233-270) where every token comes with the characters it covers
+ * and the index of its segment.  Each pass of the loop at wordpiece.py:251 is one segment starting at i0; matchloop leaves it
+ * at i1.  The tokens of a valid segment cover a prefix of s[i0:i1] one after the other: the first covers len(token) code points
+ * (a literal "##ing" in the text covers five), every later one -- it begins with "##" -- len(token) - 2.  The prefix may be
+ * shorter than the segment: source/utils.py:136-137 redirects the failure link of every non-alphanumeric node and drops the
+ * path of the old link target, and nothing covers those characters.  The "['UNK']" of an invalid segment (wordpiece.py:255-257)
+ * covers (i0, b), b the first iswdbndry position at or after i1 (the sentence's length at most).  The one id of the "##" corner
+ * (wordpiece.py:260-261) covers (i0, i0 + 2).  The word index numbers the segments of a sentence that emit at least one token.
+ * A span never passes its sentence's end (a vocabulary token that holds a space could cover the appended one).
+ *
+ * Arguments, ids, offsets and statuses are exactly those of swt_wp_encode / swt_wp_encode_dev, bit for bit.  spans[2 t],
+ * spans[2 t + 1] = start and end of token t relative to its sentence's first byte, in bytes, or in code points with
+ * SWT_SPAN_CODEPOINTS (the unit is a lead byte with the continuation bytes that ride with it); word[t] (may be NULL) its word
+ * index; both are indexed by the token slots of out_ids.  spans needs two words and word one for every id out_ids has room for
+ * (out_cap in the host form, n_bytes in the `_dev` form); any 4-byte alignment will do.  A sentence whose status is not
+ * SWT_WP_OK has no tokens and no spans.  SWT_ERR_INVALID for NULL spans or an unknown flag.
+ *
+ * The span form of the kernel is a second instantiation (csrc/swt_wp.hip); the length of every vocabulary token is kept by the
+ * trie handle and uploaded by the first call, and the handle's grow-only workspace takes 12 more bytes per text byte.  The
+ * word-level dedup pipeline is never taken, whatever SWT_OPT_DEDUP says: a unique chunk has no position.
+ * swt_wp_encode_spans_capacity: the sizes at which the call changes form -- block: bytes classified per step; chunk: bytes
+ * staged at a time (a longer sentence is walked by one lane); tile: the window of sentence starts of one workgroup;
+ * direct_bytes, direct_sents: up to here one workgroup and one launch do the whole call. */
+int swt_wp_encode_spans(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                        uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint32_t flags, uint32_t *spans,
+                        uint32_t *word);
+int swt_wp_encode_spans_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                            uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint32_t flags,
+                            uint32_t *d_spans, uint32_t *d_word, void *stream);
+int swt_wp_encode_spans_capacity(uint32_t *block, uint32_t *chunk, uint32_t *tile, uint32_t *direct_bytes, uint32_t *direct_sents);
 
 /* ------------------------------------------------------------------------------------------------
  * BPE training: replaces the merge loop of NaiveBPE.train (source/bpe.py:88-111; FastBPE.train

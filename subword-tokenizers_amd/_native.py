@@ -87,6 +87,10 @@ SIGNATURES = {
     "swt_token_spans_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                       C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "swt_token_spans_capacity": (C.c_int, [u32p, u32p, u32p]),
+    "swt_wp_encode_spans": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, C.c_uint32, u32p, u32p]),
+    "swt_wp_encode_spans_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_wp_encode_spans_capacity": (C.c_int, [u32p, u32p, u32p, u32p, u32p]),
     "swt_bpe_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
     "swt_bpe_train_create_joined": (C.c_int, [u8p, C.c_uint64, C.c_uint64, u8p, vpp]),
     "swt_wp_train_create_text": (C.c_int, [u8p, u64p, C.c_uint64, vpp]),
@@ -615,6 +619,35 @@ class WpTrie:
 
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
+
+    def encode_spans(self, text_u8, sent_off, codepoints=True):
+        """encode() with, per token, where it came from (swt_wp_encode_spans) -> (ids, offsets, status, spans uint32[n, 2] = start
+        and end inside the sentence in code points or bytes, word uint32[n] = index of the token's segment among those of its
+        sentence that emit a token)"""
+        n_sent = int(sent_off.size - 1)
+        n_bytes = int(sent_off[-1])
+        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
+        spans = np.zeros((out.size, 2), dtype=np.uint32)
+        word = np.zeros(out.size, dtype=np.uint32)
+        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
+        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
+        nt = C.c_uint64()
+        check(lib().swt_wp_encode_spans(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
+                                        ptr(out_off, u64p), ptr(status, u8p), C.byref(nt), SPAN_CODEPOINTS if codepoints else 0,
+                                        ptr(spans, u32p), ptr(word, u32p)))
+        return out[:nt.value], out_off, status[:n_sent], spans[:nt.value], word[:nt.value]
+
+    def encode_spans_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, d_spans, d_word, codepoints=True,
+                         stream=0):
+        check(lib().swt_wp_encode_spans_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok,
+                                            SPAN_CODEPOINTS if codepoints else 0, d_spans, d_word, stream))
+
+    @staticmethod
+    def encode_spans_capacity():
+        """-> (block, chunk, tile, direct_bytes, direct_sents): the sizes at which the spans call changes form (include/swt.h)"""
+        v = [C.c_uint32() for _ in range(5)]
+        check(lib().swt_wp_encode_spans_capacity(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def encode_naive(self, text_u8, sent_off):
         """NaiveWP.tokenize over lowercased packed text -> (ids, offsets, status)"""

@@ -53,6 +53,10 @@ void launch_scan_u64(uint64_t n, const unsigned long long *d_in, unsigned long l
                      uint64_t *d_total, hipStream_t st);
 void launch_scan_gather(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_tiles, const TileWorkspace &ws,
                         uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, hipStream_t st);
+// After launch_scan_gather, with its tile bases: what travelled through scratch next to the ids of the same tiles -- a span
+// (two words) and a word index per token slot -- to the same slots of the caller's arrays.
+void launch_gather_spans(const uint64_t *d_sent_off, uint64_t n_tiles, const TileWorkspace &ws, const uint32_t *d_sp_scratch,
+                         const uint32_t *d_wd_scratch, uint32_t *d_spans, uint32_t *d_word, hipStream_t st);
 
 // ---- the host-call layer: what stands between a host entry point (swt_*_encode, swt_*_encode_joined and their naive forms) and
 // the encoder's _dev call.  An encoder describes itself in a HostEncoder, keeps a HostStage in its handle, and its extern "C"
@@ -64,7 +68,15 @@ struct HostStage {
   DevBuf out_ids, out_off, out_status, n_tok;  // device text -> the caller's host arrays (the large path, the joined form)
   PinnedBuf pin;                               // the two small paths: inputs and outputs in one pinned buffer
   DevBuf small_in, small_out;                  // the one-copy path
+  DevBuf out_spans, out_word;                  // the large path of an encoder with extra outputs (HostExtra)
   void release();
+};
+
+// Optional extra outputs of a host call, per token slot next to the ids: spans (two words each) and word indices (may be null).
+// Every path of host_encode carries them behind the ids, sized as the ids are; they are copied out only when the ids fit.
+struct HostExtra {
+  uint32_t *spans;
+  uint32_t *word;
 };
 
 struct HostEncoder {
@@ -75,16 +87,22 @@ struct HostEncoder {
                     uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens)> dev;
   uint64_t direct_bytes, direct_sents;  // up to here the _dev call is ONE launch that writes the caller's arrays (DirectOut)
   bool has_status;                      // per-sentence statuses (WordPiece)
+  // the same with spans and word indices (device arrays of 2 * (n_bytes + 64) and n_bytes + 64 words); used instead of dev when
+  // the host call was given a HostExtra
+  std::function<int(const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent, uint32_t *d_ids,
+                    uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint32_t *d_spans, uint32_t *d_word)> dev_extra = {};
 };
 
 // Text and offsets on the device -> ids, offsets, statuses and the count in the caller's host arrays.  Offsets, statuses and
 // *n_tokens are written before SWT_ERR_CAPACITY is returned, here and below.
 int host_encode_from_device(HostStage &hs, const HostEncoder &enc, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off,
-                            uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens);
+                            uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens,
+                            const HostExtra *extra = nullptr);
 // Host buffers -> ids.  By size alone: up to the single-launch limits the kernel reads and writes pinned host memory (no copy
 // call at all); up to kSmallCallBytes / kSmallCallSents one copy up and one down; beyond, plain copies.
 int host_encode(HostStage &hs, const HostEncoder &enc, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
-                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens);
+                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens,
+                const HostExtra *extra = nullptr);
 // list[str] joined with U+0000 -> ids, the prepared text never coming back to the host (with_prepared_joined, swt_words.h).
 // *n_tokens = UINT64_MAX on return: a sentence needs the host's str.lower() (need_host says which) and nothing was encoded.
 int host_encode_joined(HostStage &hs, const HostEncoder &enc, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent,

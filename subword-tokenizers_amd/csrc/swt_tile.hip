@@ -166,6 +166,28 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const uint64_t *__rest
   for (uint64_t s = s_lo + lane; s < s_hi; s += 64) out_off[s] = base + sent_local[s];
 }
 
+// The gather of what travels next to the ids (token spans and word indices): the same tiles, the same bases, the same slots.
+__global__ __launch_bounds__(kThreads) void gather_spans_kernel(const uint64_t *__restrict__ sent_off, const uint64_t *__restrict__ plan,
+                                                                uint64_t n_tiles, const uint32_t *__restrict__ sp_scratch,
+                                                                const uint32_t *__restrict__ wd_scratch, const uint32_t *__restrict__ tile_tok,
+                                                                const uint32_t *__restrict__ tile_base,
+                                                                const unsigned long long *__restrict__ blk_base, uint32_t *__restrict__ out_spans,
+                                                                uint32_t *__restrict__ out_word) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t t = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;
+  const uint64_t s_lo = plan[t], s_hi = plan[t + 1];
+  if (s_lo == s_hi) return;
+  const uint64_t base = blk_base[t >> 10] + tile_base[t];
+  const uint32_t n = tile_tok[t];
+  const uint64_t src = sent_off[s_lo];
+  for (uint32_t i = lane; i < n; i += 64) {
+    out_spans[2 * (base + i)] = sp_scratch[2 * (src + i)];
+    out_spans[2 * (base + i) + 1] = sp_scratch[2 * (src + i) + 1];
+    if (out_word) out_word[base + i] = wd_scratch[src + i];
+  }
+}
+
 int TileWorkspace::reserve(uint64_t n_bytes, uint64_t n_sent, uint64_t n_tiles) {
   int rc;
   if ((rc = plan.reserve((n_tiles + 1) * 8))) return rc;
@@ -227,17 +249,28 @@ void launch_scan_gather(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_
                      ws.tile_base.as<uint32_t>(), blk_base, d_n_tokens, d_out_ids, d_out_off);
 }
 
+void launch_gather_spans(const uint64_t *d_sent_off, uint64_t n_tiles, const TileWorkspace &ws, const uint32_t *d_sp_scratch,
+                         const uint32_t *d_wd_scratch, uint32_t *d_spans, uint32_t *d_word, hipStream_t st) {
+  const uint64_t nb = (n_tiles + 1023) / 1024;
+  const unsigned long long *blk_base = ws.blk.as<unsigned long long>() + 1 + nb;
+  hipLaunchKernelGGL(gather_spans_kernel, dim3((unsigned)((n_tiles + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, d_sent_off,
+                     ws.plan.as<uint64_t>(), n_tiles, d_sp_scratch, d_wd_scratch, ws.tile_tok.as<uint32_t>(), ws.tile_base.as<uint32_t>(),
+                     blk_base, d_spans, d_word);
+}
+
 // ---- the host-call layer --------------------------------------------------------------------------------------------
 
 void HostStage::release() {
-  for (DevBuf *b : {&in_text, &in_off, &out_ids, &out_off, &out_status, &n_tok, &small_in, &small_out}) b->release();
+  for (DevBuf *b : {&in_text, &in_off, &out_ids, &out_off, &out_status, &n_tok, &small_in, &small_out, &out_spans, &out_word}) b->release();
   pin.release();
 }
 
 // A call's results to the caller's arrays: the count, the offsets and the statuses (st, null for none) first, the ids only if
 // they fit.  device: the sources are device buffers (blocking copies); otherwise host memory the device has finished writing.
+// extra with its sources sp and wd: the spans and word indices of the same token slots, copied when the ids are.
 static int unpack(const void *count, const void *off, const void *st, const void *ids, bool device, uint64_t n_sent, uint32_t *out_ids,
-                  uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+                  uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, const HostExtra *extra = nullptr,
+                  const void *sp = nullptr, const void *wd = nullptr) {
   const auto get = [device](void *dst, const void *src, size_t n) {
     if (device) return hipMemcpy(dst, src, n, hipMemcpyDeviceToHost);
     memcpy(dst, src, n);
@@ -251,25 +284,39 @@ static int unpack(const void *count, const void *off, const void *st, const void
   if (nt > out_cap)
     return fail(SWT_ERR_CAPACITY, "out_ids too small: need %llu ids, have %llu", (unsigned long long)nt, (unsigned long long)out_cap);
   if (nt) SWT_HIP(get(out_ids, ids, nt * 4));
+  if (nt && extra) {
+    SWT_HIP(get(extra->spans, sp, nt * 8));
+    if (extra->word) SWT_HIP(get(extra->word, wd, nt * 4));
+  }
   return SWT_OK;
 }
 
 int host_encode_from_device(HostStage &hs, const HostEncoder &enc, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off,
-                            uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+                            uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens,
+                            const HostExtra *extra) {
   int rc;
   if ((rc = hs.out_ids.reserve((n_bytes + 64) * 4))) return rc;
   if ((rc = hs.out_off.reserve((n_sent + 1) * 8))) return rc;
   if (enc.has_status && (rc = hs.out_status.reserve(n_sent + 8))) return rc;
   if ((rc = hs.n_tok.reserve(8))) return rc;
   uint8_t *const d_status = enc.has_status ? hs.out_status.as<uint8_t>() : nullptr;
+  if (extra) {
+    if ((rc = hs.out_spans.reserve((n_bytes + 64) * 8)) || (rc = hs.out_word.reserve((n_bytes + 64) * 4))) return rc;
+    if ((rc = enc.dev_extra(d_text, n_bytes, d_off, n_sent, hs.out_ids.as<uint32_t>(), hs.out_off.as<uint64_t>(), d_status,
+                            hs.n_tok.as<uint64_t>(), hs.out_spans.as<uint32_t>(), hs.out_word.as<uint32_t>())))
+      return rc;
+    return unpack(hs.n_tok.p, hs.out_off.p, d_status, hs.out_ids.p, true, n_sent, out_ids, out_cap, out_off, status, n_tokens, extra,
+                  hs.out_spans.p, hs.out_word.p);
+  }
   if ((rc = enc.dev(d_text, n_bytes, d_off, n_sent, hs.out_ids.as<uint32_t>(), hs.out_off.as<uint64_t>(), d_status, hs.n_tok.as<uint64_t>())))
     return rc;
   return unpack(hs.n_tok.p, hs.out_off.p, d_status, hs.out_ids.p, true, n_sent, out_ids, out_cap, out_off, status, n_tokens);
 }
 
 int host_encode(HostStage &hs, const HostEncoder &enc, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
-                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) {
+                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, const HostExtra *extra) {
   if (!sent_off || !out_off || !n_tokens || (enc.has_status && n_sent && !status)) return fail(SWT_ERR_INVALID, "null argument");
+  if (extra && (!extra->spans || !enc.dev_extra)) return fail(SWT_ERR_INVALID, "null spans");
   int rc = enc.upload();
   if (rc) return rc;
   const uint64_t n_bytes = sent_off[n_sent];
@@ -281,13 +328,20 @@ int host_encode(HostStage &hs, const HostEncoder &enc, const uint8_t *text, cons
   // The two small paths move one block each way.  In: the offsets, then the text.  Out: the count at 0, the offsets at 16, the
   // statuses behind them, the ids last -- every part at a multiple of 16.
   const size_t off_bytes = ((n_sent + 1) * 8 + 15) & ~(size_t)15, st_bytes = enc.has_status ? (n_sent + 15) & ~(size_t)15 : 0;
-  const size_t st_at = 16 + off_bytes, ids_at = st_at + st_bytes, out_bytes = ids_at + (n_bytes + 64) * 4;
+  // With a HostExtra the spans and the word indices follow the ids.
+  const size_t st_at = 16 + off_bytes, ids_at = st_at + st_bytes, sp_at = ids_at + (n_bytes + 64) * 4, wd_at = sp_at + (n_bytes + 64) * 8;
+  const size_t out_bytes = extra ? wd_at + (n_bytes + 64) * 4 : sp_at;
   const auto encode = [&](const uint8_t *in, uint8_t *o) {
+    if (extra)
+      return enc.dev_extra(in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(in), n_sent, reinterpret_cast<uint32_t *>(o + ids_at),
+                           reinterpret_cast<uint64_t *>(o + 16), enc.has_status ? o + st_at : nullptr, reinterpret_cast<uint64_t *>(o),
+                           reinterpret_cast<uint32_t *>(o + sp_at), reinterpret_cast<uint32_t *>(o + wd_at));
     return enc.dev(in + off_bytes, n_bytes, reinterpret_cast<const uint64_t *>(in), n_sent, reinterpret_cast<uint32_t *>(o + ids_at),
                    reinterpret_cast<uint64_t *>(o + 16), enc.has_status ? o + st_at : nullptr, reinterpret_cast<uint64_t *>(o));
   };
   const auto unpack_block = [&](const uint8_t *o) {
-    return unpack(o, o + 16, enc.has_status ? o + st_at : nullptr, o + ids_at, false, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+    return unpack(o, o + 16, enc.has_status ? o + st_at : nullptr, o + ids_at, false, n_sent, out_ids, out_cap, out_off, status, n_tokens,
+                  extra, o + sp_at, o + wd_at);
   };
   if (n_bytes <= enc.direct_bytes && n_sent <= enc.direct_sents && n_sent > 0) {
     // tokenize(text) on one sentence, the reference's call: the single workgroup of the direct form reads the text and the
@@ -326,7 +380,7 @@ int host_encode(HostStage &hs, const HostEncoder &enc, const uint8_t *text, cons
   if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
   SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
   return host_encode_from_device(hs, enc, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, out_ids, out_cap, out_off,
-                                 status, n_tokens);
+                                 status, n_tokens, extra);
 }
 
 int host_encode_joined(HostStage &hs, const HostEncoder &enc, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent,

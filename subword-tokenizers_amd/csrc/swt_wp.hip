@@ -79,6 +79,95 @@ struct TxtSrc {
     while (q < e && utf8_is_cont(txt[q])) q++;  // stray continuation bytes ride with the previous char
     len = (uint32_t)(q - p);
   }
+  // the bytes of the code point at p as load() counts them, without its class (the span pass)
+  __device__ __forceinline__ uint32_t step(uint64_t p, uint64_t e) const {
+    uint64_t q = p + utf8_len(txt[p]);
+    if (q > e) q = e;
+    while (q < e && utf8_is_cont(txt[q])) q++;
+    return (uint32_t)(q - p);
+  }
+};
+
+// ---- token spans out of the walk (swt_wp_encode_spans) ---------------------------------------------------------
+// A segment of FastWP.tokenize starts at i0; matchloop leaves it at i1.  Its tokens cover a prefix of s[i0:i1], one after the
+// other: the first covers len(token) code points, every later one (it begins with '##') len(token) - 2.  The "['UNK']" of an
+// invalid segment covers (i0, b) with b the first iswdbndry position at or after i1; the '##' corner covers (i0, i0 + 2).  The
+// word index of a token numbers the segments of its sentence that emit at least one token.
+// segment() hands what it knows to a sink of this shape; WpNoSpans is the ids-only form and leaves no instruction behind.
+constexpr int kSegValid = 0, kSegUnk = 1, kSegCorner = 2;
+struct WpNoSpans {
+  static constexpr bool on = false;
+};
+constexpr uint32_t kWpLenCont = 0x80000000u;  // length-table entry: the token begins with '##'
+struct WpSpanTab {
+  const uint32_t *len;  // code points of every vocabulary token, kWpLenCont on the '##' ones
+  uint32_t n_vocab;
+  uint32_t unit_cp;     // SWT_SPAN_CODEPOINTS
+};
+// Where the spans of ONE walker go.  The walker's positions are byte offsets in its text source; b0 is its sentence's first byte.
+// sp runs parallel to the ids the segment stored (sp[k] belongs to out[k]).  The word index is either written next to the ids
+// (wd: the one-lane walk in global memory, which counts as it goes) or left as a bit per first token slot in an LDS mask (emit:
+// the kernel takes popcounts from the sentence start afterwards).  seq: the sink is carried from segment to segment of a
+// sentence and advances itself; otherwise it serves one segment and cp0 is given.
+struct WpSpanSink {
+  static constexpr bool on = true;
+  WpSpanTab tab;
+  uint32_t *sp;    // two words per token
+  uint32_t *wd;
+  unsigned long long *emit;
+  uint32_t slot;   // bit of sp[0] in emit
+  uint64_t b0;
+  uint32_t cp0;    // code points between b0 and the segment's start
+  uint32_t nw;     // token-bearing segments so far
+  bool seq;
+  template <class Src>
+  __device__ __forceinline__ void put(const Src &src, uint64_t i0, uint64_t bnd, uint64_t next, uint64_t e, int kind,
+                                      const uint32_t *ids, uint32_t n) {
+    uint64_t q = i0;
+    uint32_t c = 0;
+    const auto walk_cps = [&](uint32_t want) {  // `want` code points on from q, never past the sentence
+      for (uint32_t j = 0; j < want && q < e; j++) { q += src.step(q, e); c++; }
+    };
+    const auto walk_to = [&](uint64_t stop) {
+      while (q < stop && q < e) { q += src.step(q, e); c++; }
+    };
+    const auto put_span = [&](uint32_t k, uint64_t q0, uint32_t c0) {
+      sp[2 * k] = tab.unit_cp ? cp0 + c0 : (uint32_t)(q0 - b0);
+      sp[2 * k + 1] = tab.unit_cp ? cp0 + c : (uint32_t)(q - b0);
+    };
+    if (n) {
+      if (kind == kSegUnk) {
+        walk_to(bnd);
+        put_span(0, i0, 0);
+      } else if (kind == kSegCorner) {
+        walk_cps(2);
+        put_span(0, i0, 0);
+      } else {
+        for (uint32_t k = 0; k < n; k++) {
+          const uint32_t id = ids[k];
+          const uint32_t ent = id < tab.n_vocab ? tab.len[id] : 0u;
+          uint32_t L = ent & 0xFFFFFFu;
+          if (k && (ent & kWpLenCont)) L = L >= 2 ? L - 2 : 0;
+          const uint64_t q0 = q;
+          const uint32_t c0 = c;
+          walk_cps(L);
+          put_span(k, q0, c0);
+        }
+      }
+      if (emit) atomicOr(&emit[slot >> 6], 1ull << (slot & 63));
+      if (wd)
+        for (uint32_t k = 0; k < n; k++) wd[k] = nw;
+    }
+    if (!seq) return;
+    if (tab.unit_cp) {
+      walk_to(next);
+      cp0 += c;
+    }
+    sp += 2 * n;
+    slot += n;
+    if (wd) wd += n;
+    nw += n ? 1u : 0u;
+  }
 };
 
 // State of a walk through one sentence occupying bytes [b, e): i == e is the appended space (wordpiece.py:248),
@@ -106,9 +195,11 @@ struct WpWalk {
   }
   // One iteration of the loop at wordpiece.py:251-269: match a segment from i, emit its tokens to out[0..) (at most
   // `room` are stored), move i to the start of the next segment.  Returns the token count; status != OK aborts.
-  template <class Out>
-  __device__ __forceinline__ uint32_t segment(Out out, uint32_t room, int &status) {
+  // sp: where the tokens' spans go (WpSpanSink), or nowhere (WpNoSpans).
+  template <class Out, class Sp>
+  __device__ __forceinline__ uint32_t segment(Out out, uint32_t room, int &status, Sp &sp) {
     const uint64_t seg_i = i;
+    int kind = kSegValid;
     uint32_t nt = 0;
     uint32_t node = kWpRoot;
     bool stop = false;
@@ -134,14 +225,18 @@ struct WpWalk {
       for (uint32_t k = 1; k < nt && k < room; k++) out[k] = kInvalidTok;
       if (room) out[0] = T.unk_id;
       nt = 1;
+      kind = kSegUnk;
     } else if (node == T.root_sharp && nt == 0) {  // wordpiece.py:260-261
       if (T.corner_nonterm) { status = SWT_WP_NONTERMINATING; return 0; }
       if (room) out[0] = T.corner_id;
       nt = 1;
+      kind = kSegCorner;
     }
     while (i <= e && !bndry()) adv();          // wordpiece.py:265-266
+    const uint64_t bnd_i = i;
     while (i <= e && (cc & kPySpace)) adv();   // wordpiece.py:268-269
     if (i == seg_i) { status = SWT_WP_NONTERMINATING; return 0; }  // same state again: the reference spins
+    if constexpr (Sp::on) sp.put(src, seg_i, bnd_i, i, e, kind, &out[0], nt < room ? nt : room);
     return nt;
   }
 };
@@ -149,13 +244,13 @@ struct WpWalk {
 // FastWP.tokenize on one whole sentence, segment after segment (the sequential form: sentences the parallel form
 // cannot certify, and sentences longer than a chunk).  out[k] receives the k-th id.  Returns the token count
 // (0 when status != OK).  wordpiece.py:248-270.
-template <class Src, class Out>
-__device__ uint32_t wp_sentence(const Src &src, uint64_t b, uint64_t e, Out out, const WpDev &T, int &status) {
+template <class Src, class Out, class Sp>
+__device__ uint32_t wp_sentence(const Src &src, uint64_t b, uint64_t e, Out out, const WpDev &T, int &status, Sp &sp) {
   WpWalk<Src> w(src, T, b, e, false);
   uint32_t nt = 0;
   status = SWT_WP_OK;
   while (w.i <= e) {  // wordpiece.py:251
-    nt += w.segment(out + nt, 0xFFFFFFFFu, status);
+    nt += w.segment(out + nt, 0xFFFFFFFFu, status, sp);
     if (status != SWT_WP_OK) return 0;
   }
   return nt;
@@ -351,9 +446,14 @@ __device__ __forceinline__ uint32_t wp_sentence_start(const WpTileLds &L, const 
   return m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : ch.off0;
 }
 
-// ---- E. compaction, F. sentence offsets.  Advances the tile; true: that was its last chunk.
+// ---- E. compaction, F. sentence offsets.  Advances the tile; true: that was its last chunk.  extra(p, k): what else travels with
+// the token at byte p of the chunk to slot k of the tile's run (the span form; WpNoExtra for ids alone).
+struct WpNoExtra {
+  __device__ __forceinline__ void operator()(uint32_t, uint32_t) const {}
+};
+template <class Extra>
 __device__ __forceinline__ bool wp_emit(WpTileLds &L, WpTile &tile, const WpChunk &ch, const uint64_t *__restrict__ sent_off,
-                                        const WpOut &out, int lane) {
+                                        const WpOut &out, int lane, Extra extra) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   uint32_t total = 0;
   for (uint32_t blk = 0; blk < ch.nblk; blk++) {
@@ -361,7 +461,11 @@ __device__ __forceinline__ bool wp_emit(WpTileLds &L, WpTile &tile, const WpChun
     const uint32_t sv = (p >= ch.off0 && p < ch.ce) ? L.tok[p] : kInvalidTok;
     const unsigned long long m = __ballot(sv != kInvalidTok);
     if (lane == 0) { L.vmask[blk] = m; L.blkpre[blk] = total; }
-    if (sv != kInvalidTok) tile.tile_out[tile.run + total + __popcll(m & lt)] = sv;
+    if (sv != kInvalidTok) {
+      const uint32_t k = tile.run + total + __popcll(m & lt);
+      tile.tile_out[k] = sv;
+      extra(p, k);
+    }
     total += __popcll(m);
   }
   __syncthreads();
@@ -392,7 +496,42 @@ __device__ __forceinline__ void wp_tile_end(const WpTile &tile, uint32_t *__rest
 struct alignas(16) WpLds : WpTileLds {
   unsigned long long ppunc[kWpBlocks + 1];   // the char before this byte (same sentence) is punctuation-class
   unsigned long long irr[kWpBlocks + 1];     // per sentence-start position: needs the sequential walk
+  static constexpr bool spans = false;
 };
+// The span form keeps, next to tok[]: the span of the token in each byte's slot, the code-point starts (the unit of
+// SWT_SPAN_CODEPOINTS), and a bit at the slot of the first token of every segment that emitted one, with its block prefix.
+struct alignas(16) WpSpanLds : WpLds {
+  uint32_t sp[2 * kWpCap];  // two words per token slot
+  unsigned long long lead[kWpBlocks + 1];
+  unsigned long long emit[kWpBlocks + 1];
+  uint32_t epre[kWpBlocks + 1];
+  static constexpr bool spans = true;
+};
+// What the span kernel is given beyond the ids kernel's arguments: the length table, the unit, and the scratch runs (or, in the
+// direct form, the caller's arrays) of spans and word indices, indexed as the ids' scratch is.
+struct WpSpanArgs {
+  WpSpanTab tab;
+  uint32_t *sp;  // two words per token: any 4-byte aligned array of the caller will do
+  uint32_t *wd;
+};
+struct WpNoSpanArgs {};
+
+// set bits of m[] at positions [a, b), a <= b
+__device__ __forceinline__ uint32_t wp_count(const unsigned long long *m, uint32_t a, uint32_t b) {
+  uint32_t n = 0;
+  for (uint32_t w = a >> 6; w <= (b >> 6); w++) {
+    unsigned long long x = m[w];
+    if (w == (a >> 6)) x &= ~((1ull << (a & 63)) - 1ull);
+    if (w == (b >> 6)) x &= (1ull << (b & 63)) - 1ull;
+    n += __popcll(x);
+  }
+  return n;
+}
+
+// set bits of m[] below position p (pre[w] = set bits of the words before w)
+__device__ __forceinline__ uint32_t wp_rank(const unsigned long long *m, const uint32_t *pre, uint32_t p) {
+  return pre[p >> 6] + __popcll(m[p >> 6] & ((1ull << (p & 63)) - 1ull));
+}
 
 // The skeleton above with these phases.  Segments of a sentence depend on each other only through where the previous one
 // ended (wordpiece.py:265-269), and that is almost always the next static boundary.  So:
@@ -402,25 +541,54 @@ struct alignas(16) WpLds : WpTileLds {
 //      territory [candidate, next candidate); it certifies itself when it ended exactly at the next candidate
 //   D  a sentence with an uncertified candidate (a vocabulary entry spanning a boundary, a non-terminating or raising
 //      input) is redone by one lane with the sequential walker -- exactness never rests on the speculation
+// Two instantiations: wp_encode_kernel<WpLds>, the ids alone -- its arguments, resources and instructions are those of the kernel
+// before there was a second one -- and wp_encode_kernel<WpSpanLds, WpSpanArgs>, every token with its span and word index (one more
+// argument).  In the span form every one of the four ways a token is made carries them:
+//   C      the lane's sink writes sp[] next to its tok[] and marks its candidate in emit when it stored a token
+//   D      the redone sentence's bits of emit are cleared and set again at the slots its segments' first tokens went to
+//   E      a token's word index = the emit bits from its sentence's start up to its slot, less one: popcounts, no scan
+//   giant  lane 0 writes spans and word indices next to the ids, counting as it goes
+// and the direct form differs only in where the tile's run lies (the caller's arrays).
+__device__ __forceinline__ WpNoSpanArgs wp_span_args() { return {}; }
+__device__ __forceinline__ const WpSpanArgs &wp_span_args(const WpSpanArgs &a) { return a; }
+
+template <class Lds, class... SpanArgs>
 __global__ __launch_bounds__(64) void wp_encode_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpDev T, uint32_t *__restrict__ scratch,
-    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
-  __shared__ WpLds L;
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct,
+    SpanArgs... span_args) {
+  __shared__ Lds L;
+  const auto sa = wp_span_args(span_args...);
   const int lane = threadIdx.x;
   const unsigned long long lt = (1ull << lane) - 1ull;
   WpTile tile;
   if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
   const WpOut out{sent_local, status, direct};
+  uint32_t *tile_sp = nullptr;   // the tile's runs of spans and word indices, parallel to tile.tile_out
+  uint32_t *tile_wd = nullptr;
+  if constexpr (Lds::spans) {
+    tile_sp = sa.sp + 2 * (tile.tile_out - scratch);
+    tile_wd = sa.wd + (tile.tile_out - scratch);
+  }
 
   for (;;) {
     WpChunk ch;
     wp_stage(L, tile, ch, text, n_bytes, lane);
     if (lane <= kWpBlocks) L.irr[lane] = 0ull;
+    if constexpr (Lds::spans) {
+      if (lane <= kWpBlocks) L.emit[lane] = 0ull;
+    }
     __syncthreads();
     if (!wp_mark(L, tile, ch, sent_off, lane)) {
       const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt) {
-        return wp_sentence(TxtSrc{text, nullptr, cls_tab}, b, e, o, T, stt);
+        if constexpr (Lds::spans) {
+          WpSpanSink sink{sa.tab, tile_sp + 2 * (o - tile.tile_out), tile_wd + (o - tile.tile_out), nullptr, 0, b, 0, 0, true};
+          return wp_sentence(TxtSrc{text, nullptr, cls_tab}, b, e, o, T, stt, sink);
+        } else {
+          WpNoSpans none;
+          return wp_sentence(TxtSrc{text, nullptr, cls_tab}, b, e, o, T, stt, none);
+        }
       };
       if (wp_giant(L, tile, sent_off, out, T.empty_status, walk, lane)) break;
       continue;
@@ -450,6 +618,9 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
       const unsigned long long before_pu = ((PUb << 1) | (prev_pu ? 1ull : 0ull)) & ~SS;
       const unsigned long long CAND = INR & (SS | (LEAD & ~SPm & (before_sp | before_pu | PUm)));
       if (lane == 0) L.ppunc[blk] = before_pu;
+      if constexpr (Lds::spans) {
+        if (lane == 0) L.lead[blk] = LEAD & INR;
+      }
       if ((CAND >> lane) & 1ull) L.cand[nc + __popcll(CAND & lt)] = (uint16_t)p;
       nc += __popcll(CAND);
       L.tok[p] = kInvalidTok;
@@ -477,7 +648,16 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
       TxtSrc src{L.txt, L.cls_lo, cls_tab};
       WpWalk<TxtSrc> w(src, T, p0, e, p0 != s0 && wbit(L.ppunc, p0));
       int stt = SWT_WP_OK;
-      const uint32_t n = w.segment(&L.tok[p0], terr_end - p0, stt);
+      uint32_t n;
+      if constexpr (Lds::spans) {
+        uint32_t cp0 = 0;  // code points of the sentence in front of the candidate
+        if (sa.tab.unit_cp) cp0 = wp_count(L.lead, s0, p0);
+        WpSpanSink sink{sa.tab, &L.sp[2 * p0], nullptr, L.emit, p0, s0, cp0, 0, false};
+        n = w.segment(&L.tok[p0], terr_end - p0, stt, sink);
+      } else {
+        WpNoSpans none;
+        n = w.segment(&L.tok[p0], terr_end - p0, stt, none);
+      }
       if (stt != SWT_WP_OK || w.i != want_next || n > terr_end - p0) atomicOr(&L.irr[s0 >> 6], 1ull << (s0 & 63));
     }
     __syncthreads();
@@ -493,7 +673,21 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
         if (wbit(L.irr, (uint32_t)rel)) {
           TxtSrc src{L.txt, L.cls_lo, cls_tab};
           // the walker only reads L.txt, so the sentence's own bytes of L.tok are free to take its tokens
-          const uint32_t n = wp_sentence(src, rel, e, &L.tok[rel], T, stt);
+          uint32_t n;
+          if constexpr (Lds::spans) {
+            // what the candidates of this sentence left in emit goes; the redone segments mark their first slots
+            for (uint32_t wq = (uint32_t)rel >> 6; wq <= ((uint32_t)e - 1) >> 6; wq++) {
+              unsigned long long keep = 0ull;
+              if (wq == (uint32_t)rel >> 6) keep |= (1ull << (rel & 63)) - 1ull;
+              if (wq == (uint32_t)e >> 6) keep |= ~((1ull << (e & 63)) - 1ull);
+              atomicAnd(&L.emit[wq], keep);
+            }
+            WpSpanSink sink{sa.tab, &L.sp[2 * rel], nullptr, L.emit, (uint32_t)rel, rel, 0, 0, true};
+            n = wp_sentence(src, rel, e, &L.tok[rel], T, stt, sink);
+          } else {
+            WpNoSpans none;
+            n = wp_sentence(src, rel, e, &L.tok[rel], T, stt, none);
+          }
           for (uint64_t q = rel + n; q < e; q++) L.tok[q] = kInvalidTok;
         }
       }
@@ -501,7 +695,23 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
     }
     __syncthreads();
 
-    if (wp_emit(L, tile, ch, sent_off, out, lane)) break;
+    if constexpr (Lds::spans) {
+      if (lane <= kWpBlocks) {
+        uint32_t before = 0;
+        for (int wq = 0; wq < lane; wq++) before += __popcll(L.emit[wq]);
+        L.epre[lane] = before;
+      }
+      __syncthreads();
+      const auto extra = [&](uint32_t p, uint32_t k) {
+        const uint32_t s0 = wp_sentence_start(L, ch, p);
+        tile_sp[2 * k] = L.sp[2 * p];
+        tile_sp[2 * k + 1] = L.sp[2 * p + 1];
+        tile_wd[k] = wp_rank(L.emit, L.epre, p + 1) - wp_rank(L.emit, L.epre, s0) - 1u;
+      };
+      if (wp_emit(L, tile, ch, sent_off, out, lane, extra)) break;
+    } else {
+      if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
+    }
   }
   wp_tile_end(tile, tile_tok, direct, lane);
 }
@@ -842,7 +1052,7 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
     }
     __syncthreads();
 
-    if (wp_emit(L, tile, ch, sent_off, out, lane)) break;
+    if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
   }
   wp_tile_end(tile, tile_tok, direct, lane);
 }
@@ -870,7 +1080,26 @@ struct swt_wp_trie {
   DedupEngine dd;
   TileWorkspace ws2;  // the encode over the unique chunks
   DevBuf u_status;
+  // token spans (swt_wp_encode_spans): code points of every vocabulary token with kWpLenCont on the '##' ones, built with the
+  // trie and uploaded by the first spans call; the scratch runs of spans (8 bytes per text byte) and word indices (4), grow-only
+  std::vector<uint32_t> h_len;
+  uint32_t *d_len = nullptr;
+  DevBuf sp_scratch, wd_scratch;
 };
+
+static WpDev wp_dev(const swt_wp_trie *t) {
+  WpDev T;
+  T.edges = t->d_edges;
+  T.edge_bits = t->edge_bits;
+  T.nodes = t->d_nodes;
+  T.pops = t->d_pops;
+  T.root_sharp = t->H.root_sharp;
+  T.unk_id = t->H.n_vocab;
+  T.corner_nonterm = t->H.corner_nonterm ? 1u : 0u;
+  T.empty_status = t->H.child(t->H.root, ' ') >= 0 ? SWT_WP_INDEXERROR : SWT_WP_OK;
+  T.corner_id = t->H.corner.size() == 1 ? t->H.corner[0] : t->H.n_vocab + 2;
+  return T;
+}
 
 static int wp_upload(swt_wp_trie *t) {
   if (t->d_edges) return SWT_OK;
@@ -894,6 +1123,14 @@ static int wp_upload_naive(swt_wp_trie *t) {
   return SWT_OK;
 }
 
+static int wp_upload_spans(swt_wp_trie *t) {
+  int rc = wp_upload(t);
+  if (rc || t->d_len) return rc;
+  SWT_HIP(hipMalloc((void **)&t->d_len, (t->h_len.size() + 1) * 4));
+  if (!t->h_len.empty()) SWT_HIP(hipMemcpy(t->d_len, t->h_len.data(), t->h_len.size() * 4, hipMemcpyHostToDevice));
+  return SWT_OK;
+}
+
 extern "C" {
 
 int swt_wp_trie_create(const uint32_t *vocab_cps, const uint64_t *vocab_off, uint32_t n_vocab, swt_wp_trie **out) try {
@@ -904,6 +1141,13 @@ int swt_wp_trie_create(const uint32_t *vocab_cps, const uint64_t *vocab_off, uin
   if (rc) { delete t; return rc; }
   const HostTrie &H = t->H;
   const size_t n_nodes = H.ch.size();
+  // the length table of the spans call: the strings are at hand here and only here
+  t->h_len.resize(n_vocab);
+  for (uint32_t v = 0; v < n_vocab; v++) {
+    const uint64_t a = vocab_off[v], n = vocab_off[v + 1] - a;
+    const bool cont = n >= 2 && vocab_cps[a] == '#' && vocab_cps[a + 1] == '#';
+    t->h_len[v] = (uint32_t)(n < 0xFFFFFFu ? n : 0xFFFFFFu) | (cont ? kWpLenCont : 0u);
+  }
   // flatten: nodes + pops
   t->h_nodes.resize(n_nodes);
   for (size_t k = 0; k < n_nodes; k++) {
@@ -957,6 +1201,9 @@ void swt_wp_trie_destroy(swt_wp_trie *t) try {
   if (t->d_nodes) (void)hipFree(t->d_nodes);
   if (t->d_pops) (void)hipFree(t->d_pops);
   if (t->d_tok) (void)hipFree(t->d_tok);
+  if (t->d_len) (void)hipFree(t->d_len);
+  t->sp_scratch.release();
+  t->wd_scratch.release();
   t->ws.release();
   t->ws2.release();
   t->dd.release();
@@ -1024,19 +1271,10 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
     SWT_HIP(hipMemsetAsync(d_n_tokens, 0, 8, st));
     return SWT_OK;
   }
-  WpDev T;
-  T.edges = t->d_edges;
-  T.edge_bits = t->edge_bits;
-  T.nodes = t->d_nodes;
-  T.pops = t->d_pops;
-  T.root_sharp = t->H.root_sharp;
-  T.unk_id = t->H.n_vocab;
-  T.corner_nonterm = t->H.corner_nonterm ? 1u : 0u;
-  T.empty_status = t->H.child(t->H.root, ' ') >= 0 ? SWT_WP_INDEXERROR : SWT_WP_OK;
-  T.corner_id = t->H.corner.size() == 1 ? t->H.corner[0] : t->H.n_vocab + 2;
+  const WpDev T = wp_dev(t);
   if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents && t->dd.opt_mode != 2) {
     // a sentence or a few: one workgroup, one launch, the caller's arrays written by the kernel (DirectOut, swt_tile.h)
-    hipLaunchKernelGGL(wp_encode_kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, T,
+    hipLaunchKernelGGL((wp_encode_kernel<WpLds>), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, T,
                        d_out_ids, t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status,
                        DirectOut{d_out_off, d_n_tokens, n_sent});
     SWT_HIP(hipGetLastError());
@@ -1057,7 +1295,7 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
                           kWpUTile)))
       return rc;
     prof_begin(st);
-    hipLaunchKernelGGL(wp_encode_kernel, dim3((unsigned)n_tiles2), dim3(64), 0, st, t->dd.utext.as<uint8_t>(), n_bytes,
+    hipLaunchKernelGGL((wp_encode_kernel<WpLds>), dim3((unsigned)n_tiles2), dim3(64), 0, st, t->dd.utext.as<uint8_t>(), n_bytes,
                        t->dd.uoff.as<uint64_t>(), t->ws2.plan.as<uint64_t>(), d_cls, T, t->ws2.scratch.as<uint32_t>(),
                        t->ws2.sent_local.as<uint32_t>(), t->ws2.tile_tok.as<uint32_t>(), t->u_status.as<uint8_t>(),
                        DirectOut{nullptr, nullptr, 0});
@@ -1073,7 +1311,7 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  hipLaunchKernelGGL(wp_encode_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+  hipLaunchKernelGGL((wp_encode_kernel<WpLds>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
                      t->ws.plan.as<uint64_t>(), d_cls, T, t->ws.scratch.as<uint32_t>(), t->ws.sent_local.as<uint32_t>(),
                      t->ws.tile_tok.as<uint32_t>(), d_status, DirectOut{nullptr, nullptr, 0});
   prof_end(st);
@@ -1132,6 +1370,64 @@ int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_by
   return SWT_OK;
 } SWT_API_CATCH
 
+// FastWP with token spans: swt_wp_encode_dev's direct and tiled paths with the span instantiation of the kernel, the spans and
+// word indices through their own scratch runs and launch_gather_spans.  The word-level dedup pipeline is never taken, whatever
+// the batch size and SWT_OPT_DEDUP say: a unique chunk is encoded once for all its occurrences and has no position.
+int swt_wp_encode_spans_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                            uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint32_t flags,
+                            uint32_t *d_spans, uint32_t *d_word, void *stream) try {
+  if (!t || !d_sent_off || !d_out_off || !d_n_tokens || !d_spans || (n_sent && !d_status) || (n_bytes && (!d_text || !d_out_ids)))
+    return fail(SWT_ERR_INVALID, "null argument");
+  if (flags & ~SWT_SPAN_CODEPOINTS) return fail(SWT_ERR_INVALID, "unknown flag");
+  int rc = wp_upload_spans(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t *d_cls = nullptr;
+  if ((rc = device_class_table(&d_cls))) return rc;
+  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
+  if (n_tiles > 0x7FFFFFFFull)
+    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
+  if ((rc = t->ws.reserve(n_bytes, n_sent, n_tiles)) || (rc = t->sp_scratch.reserve((n_bytes + 64) * 8)) ||
+      (rc = t->wd_scratch.reserve((n_bytes + 64) * 4)))
+    return rc;
+  if (n_sent == 0) {
+    SWT_HIP(hipMemsetAsync(d_out_off, 0, 8, st));
+    SWT_HIP(hipMemsetAsync(d_n_tokens, 0, 8, st));
+    return SWT_OK;
+  }
+  const WpDev T = wp_dev(t);
+  const WpSpanTab tab{t->d_len, t->H.n_vocab, flags & SWT_SPAN_CODEPOINTS};
+  if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents) {
+    hipLaunchKernelGGL((wp_encode_kernel<WpSpanLds, WpSpanArgs>), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, T,
+                       d_out_ids, t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status,
+                       DirectOut{d_out_off, d_n_tokens, n_sent}, WpSpanArgs{tab, d_spans, d_word ? d_word : t->wd_scratch.as<uint32_t>()});
+    SWT_HIP(hipGetLastError());
+    return SWT_OK;
+  }
+  prof_begin(st, 2);
+  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
+  prof_begin(st);
+  hipLaunchKernelGGL((wp_encode_kernel<WpSpanLds, WpSpanArgs>), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                     t->ws.plan.as<uint64_t>(), d_cls, T, t->ws.scratch.as<uint32_t>(), t->ws.sent_local.as<uint32_t>(),
+                     t->ws.tile_tok.as<uint32_t>(), d_status, DirectOut{nullptr, nullptr, 0},
+                     WpSpanArgs{tab, t->sp_scratch.as<uint32_t>(), t->wd_scratch.as<uint32_t>()});
+  prof_end(st);
+  launch_scan_gather(d_sent_off, n_sent, n_tiles, t->ws, d_out_ids, d_out_off, d_n_tokens, st);
+  launch_gather_spans(d_sent_off, n_tiles, t->ws, t->sp_scratch.as<uint32_t>(), t->wd_scratch.as<uint32_t>(), d_spans, d_word, st);
+  prof_end(st, 2);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+} SWT_API_CATCH
+
+int swt_wp_encode_spans_capacity(uint32_t *block, uint32_t *chunk, uint32_t *tile, uint32_t *direct_bytes, uint32_t *direct_sents) try {
+  if (block) *block = 64;
+  if (chunk) *chunk = kWpCap;
+  if (tile) *tile = kWpTile;
+  if (direct_bytes) *direct_bytes = (uint32_t)kWpDirectBytes;
+  if (direct_sents) *direct_sents = (uint32_t)kWpDirectSents;
+  return SWT_OK;
+} SWT_API_CATCH
+
 // What the host-call layer (swt_tile.h) needs to know of FastWP (swt_wp_encode_dev) or NaiveWP (swt_wp_encode_naive_dev).
 typedef int (*WpEncodeDev)(swt_wp_trie *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint8_t *,
                            uint64_t *, void *);
@@ -1157,6 +1453,22 @@ static int wp_encode_joined(WpEncodeDev dev, swt_wp_trie *t, const uint8_t *join
 int swt_wp_encode(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
                   uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
   return wp_encode_host(swt_wp_encode_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+} SWT_API_CATCH
+
+// FastWP with token spans, host buffers: the one host-call layer with its optional extra outputs (HostExtra, swt_tile.h).
+int swt_wp_encode_spans(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                        uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint32_t flags, uint32_t *spans,
+                        uint32_t *word) try {
+  if (!t || !spans) return fail(SWT_ERR_INVALID, "null argument");
+  if (flags & ~SWT_SPAN_CODEPOINTS) return fail(SWT_ERR_INVALID, "unknown flag");
+  HostEncoder enc = wp_host(t, swt_wp_encode_dev);
+  enc.upload = [t] { return wp_upload_spans(t); };
+  enc.dev_extra = [t, flags](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n, uint32_t *d_ids,
+                             uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint32_t *d_spans, uint32_t *d_word) {
+    return swt_wp_encode_spans_dev(t, d_text, n_bytes, d_off, n, d_ids, d_out_off, d_status, d_n_tokens, flags, d_spans, d_word, nullptr);
+  };
+  const HostExtra extra{spans, word};
+  return host_encode(t->stage, enc, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens, &extra);
 } SWT_API_CATCH
 
 int swt_wp_encode_naive(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,

@@ -686,7 +686,8 @@ class NaiveWP(SubwordTokenizer):
         """texts -> (ids, offsets, status, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its
         (start, end) in code points of text.lower() (utils.py:27-29; "[UNK]" spans its whole word) and the index of its word in
         the sentence.  A text on which the reference never returns raises as in tokenize_batch.  The text is packed once and sent
-        to the device twice, for the encode and for swt_token_spans."""
+        to the device twice, for the encode and for swt_token_spans.  FastWP inherits this method unchanged: called on a FastWP
+        it answers with NaiveWP's tokens over the same vocabulary; FastWP's own tokens come from fast_encode_spans_batch."""
         if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
             raise TypeError("Text to tokenize must be a string.")
         trie = self._ensure_naive_trie()
@@ -701,7 +702,8 @@ class NaiveWP(SubwordTokenizer):
         return ids, tok_off, status, spans, word
 
     def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
-        """[(token, (start, end)), ...]: NaiveWP.tokenize(text) in the shape of one preprocessing row"""
+        """[(token, (start, end)), ...]: NaiveWP.tokenize(text) in the shape of one preprocessing row (on a FastWP too, which
+        inherits it: FastWP.tokenize with offsets is fast_tokenize_with_offsets)"""
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
         ids, _, _, spans, _ = self.encode_spans_batch([text])
@@ -876,6 +878,36 @@ class FastWP(NaiveWP):
                 self._decode_list = list(self._tokens) + [self.UNK, "[UNK]"]
             return N.nested_lists(self._decode_list, ids, off)
         return [self._decode(ids[int(off[i]):int(off[i + 1])]) for i in range(len(texts))]
+
+    # -- token spans (not in the reference): they come out of the trie walk itself (swt_wp_encode_spans).
+    # The inherited encode_spans_batch / tokenize_with_offsets are NaiveWP's: they answer with NaiveWP's tokens over this
+    # vocabulary, not with FastWP's.  FastWP's own are the two methods below.
+    def fast_encode_spans_batch(self, texts: List[str]):
+        """texts -> (ids, offsets, status, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its
+        (start, end) in code points of text.lower() and the index of its segment among those of the sentence that emit a token
+        (include/swt.h: a valid segment's tokens cover a prefix of it, "['UNK']" reaches to the next boundary, the '##' corner
+        covers two).  A multi-token corner is one id (len(vocab) + 2) with the corner's span.  A text the reference does not
+        return from raises as in tokenize_batch.  One pack, one trip to the device."""
+        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+            raise TypeError("Text to tokenize must be a string.")
+        if self._trie is None:
+            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")
+        text, off = N.pack_and_lower(texts)
+        ids, tok_off, status, spans, word = self._trie.encode_spans(text, off, codepoints=True)
+        for i in np.flatnonzero(status):
+            self._raise_for_status(int(status[i]), texts[int(i)])
+        return ids, tok_off, status, spans, word
+
+    def fast_tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
+        """[(token, (start, end)), ...]: FastWP.tokenize(text) with the code points of text.lower() every token covers; a
+        multi-token '##' corner is spelled as its tokens, each with the corner's span"""
+        if not isinstance(text, str):
+            raise TypeError("Text to tokenize must be a string.")
+        ids, _, _, spans, _ = self.fast_encode_spans_batch([text])
+        out = []
+        for i, (s, e) in zip(ids.tolist(), spans.tolist()):
+            out.extend((tok, (int(s), int(e))) for tok in self._decode([i]))
+        return out
 
     @staticmethod
     def _raise_for_status(st: int, text: str) -> None:
