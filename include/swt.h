@@ -463,6 +463,54 @@ int swt_bpe_train_shard_begin(swt_bpe_trainer **trainers, uint32_t n_local, swt_
 /* As swt_bpe_train_run, over all shards. */
 int swt_bpe_train_run_sharded(swt_bpe_trainer **trainers, uint32_t n_local, swt_dist *d, uint32_t max_steps, uint32_t first_merged,
                               uint32_t *left, uint32_t *right, uint64_t *count, uint32_t *n_done);
+
+/* ------------------------------------------------------------------------------------------------
+ * Model-ready batches on the device: the CSR pair the encoders return (ids, tok_off[n_rows+1]) as dense, padded rows of a fixed
+ * width with the attention mask -- what a model's embedding layer takes, and where the reference stops at lists of strings
+ * (source/bpe.py:244, source/wordpiece.py:270).  A post-pass over the ids: nothing is encoded again, no text is needed.
+ *
+ * Per source row r: n = tok_off[r+1] - tok_off[r] tokens; cap = width - (cls present) - (sep present) tokens fit a row.
+ *   truncation (default)   one output row per source row; its body is the first min(n, cap) tokens
+ *   SWT_BATCH_WINDOWS      step = cap - stride; k = 1 when n <= cap, else 1 + ceil((n - cap) / step) rows; window w holds the
+ *                          tokens [w step, min(n, w step + cap)) and is output row row_base[r] + w, row_base the exclusive sum
+ *                          of k (swt_batch_plan).  A row without tokens gives one row of specials and padding
+ * An output row is [cls?] body [sep?] and then pad_id up to width; with SWT_BATCH_PAD_LEFT the padding comes first.  The mask is
+ * 1 on cls, body and sep and 0 on padding; out_len[row] counts its ones; out_sample[row] = r.
+ * Dense ids: with s = id & 0x7FFFFFFF a token becomes map[s + ((flagged && id >> 31) ? n_map : 0)]; the map has n_map entries,
+ * 2 n_map when flagged.  map == NULL (only with flagged == 0) is the identity on s, n_map still bounding it.  s >= n_map or the
+ * entry 0xFFFFFFFF gives unk_id and counts in info[2], once per output slot written.  Payloads (each given together with its
+ * output): spans (two words per token) and word (one), as the span calls write them, go to out_spans[row, col, 0..1] and
+ * out_word[row, col]; specials and padding get (0, 0) and 0xFFFFFFFF.  out_ids is int32[rows, width], int64 with SWT_BATCH_IDS64.
+ *
+ * SWT_ERR_INVALID: cap < 1, stride >= cap, an unknown flag, pad_id / unk_id = SWT_BATCH_NONE (the plan calls look at these only
+ * with SWT_BATCH_WINDOWS, so a caller can ask for the longest row before it picks a width); NULL out_ids or out_mask; flagged
+ * without a map; SWT_BATCH_WINDOWS without row_base; 2^32 rows or more.  row_base may be NULL without SWT_BATCH_WINDOWS;
+ * out_sample, out_len and info may always be NULL.  The spec is a host pointer in both forms.  The host forms check everything --
+ * decreasing offsets and a row_base that is not the plan of the offsets included -- before anything touches the device, and
+ * swt_batch_rows returns SWT_ERR_CAPACITY with info[0] = the rows needed when they exceed rows_cap.  The `_dev` forms take device
+ * pointers (offsets that do not decrease; outputs aligned to their element type, to 16 bytes for the wide stores), enqueue on
+ * the stream and do not synchronise; swt_batch_rows_dev writes every element of the rows < min(rows needed, rows_cap) of every
+ * output given and nothing at or beyond rows_cap * width, whatever ids and row_base hold.  swt_batch_plan_dev scans in one
+ * grow-only workspace of the process: two plans must not run at once on different streams.  swt_batch_capacity: the columns one
+ * wavefront writes per step and the rows of one scan group of the plan (csrc/swt_batch.hip). */
+#define SWT_BATCH_NONE 0xFFFFFFFFu
+#define SWT_BATCH_WINDOWS 1u
+#define SWT_BATCH_PAD_LEFT 2u
+#define SWT_BATCH_IDS64 4u
+typedef struct swt_batch_spec { uint32_t width, stride, flags, pad_id, unk_id, cls_id, sep_id; } swt_batch_spec;  /* cls/sep = NONE: absent */
+
+/* row_base[n_rows+1] (exclusive sum of window counts; r itself without WINDOWS), info[0] = rows out, info[1] = longest source row in tokens */
+int swt_batch_plan(const uint64_t *tok_off, uint64_t n_rows, const swt_batch_spec *spec, uint64_t *row_base, uint64_t *info);
+int swt_batch_plan_dev(const uint64_t *d_tok_off, uint64_t n_rows, const swt_batch_spec *spec, uint64_t *d_row_base, uint64_t *d_info, void *stream);
+/* info[0] rows written, info[1] source rows that lost tokens (only without WINDOWS), info[2] tokens sent to unk_id */
+int swt_batch_rows(const uint32_t *ids, const uint64_t *tok_off, uint64_t n_rows, const uint32_t *map, uint32_t n_map, int flagged,
+                   const uint32_t *spans, const uint32_t *word, const swt_batch_spec *spec, const uint64_t *row_base, uint64_t rows_cap,
+                   void *out_ids, uint8_t *out_mask, uint32_t *out_spans, uint32_t *out_word, uint32_t *out_sample, uint32_t *out_len, uint64_t *info);
+int swt_batch_rows_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, uint64_t n_rows, const uint32_t *d_map, uint32_t n_map, int flagged,
+                       const uint32_t *d_spans, const uint32_t *d_word, const swt_batch_spec *spec, const uint64_t *d_row_base, uint64_t rows_cap,
+                       void *d_out_ids, uint8_t *d_out_mask, uint32_t *d_out_spans, uint32_t *d_out_word, uint32_t *d_out_sample, uint32_t *d_out_len,
+                       uint64_t *d_info, void *stream);
+int swt_batch_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
 #ifdef __cplusplus
 }
 #endif

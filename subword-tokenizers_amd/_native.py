@@ -24,6 +24,8 @@ SPAN_CODEPOINTS = 1
 SPAN_OK, SPAN_MISMATCH = 0, 1
 SPAN_WHOLE_WORD = 0  # a length-table entry: the token stands for its whole word ("[UNK]")
 SPAN_LEN_CONT = 0x80000000  # a length-table entry of an unflagged stream: the token continues its word ('##')
+BATCH_NONE = 0xFFFFFFFF  # swt_batch_spec: an absent cls_id / sep_id; a map entry without a dense id
+BATCH_WINDOWS, BATCH_PAD_LEFT, BATCH_IDS64 = 1, 2, 4
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -31,6 +33,14 @@ i32p = C.POINTER(C.c_int32)
 u64p = C.POINTER(C.c_uint64)
 i64p = C.POINTER(C.c_int64)
 vpp = C.POINTER(C.c_void_p)
+
+
+class BatchSpec(C.Structure):
+    """swt_batch_spec (include/swt.h): the shape of a padded batch"""
+    _fields_ = [(name, C.c_uint32) for name in ("width", "stride", "flags", "pad_id", "unk_id", "cls_id", "sep_id")]
+
+
+bsp = C.POINTER(BatchSpec)
 
 # every symbol include/swt.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -114,6 +124,14 @@ SIGNATURES = {
     "swt_dist_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "swt_bpe_train_shard_begin": (C.c_int, [vpp, C.c_uint32, C.c_void_p, u32p, C.c_uint32, u32p]),
     "swt_bpe_train_run_sharded": (C.c_int, [vpp, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p, u64p, u32p]),
+    "swt_batch_plan": (C.c_int, [u64p, C.c_uint64, bsp, u64p, u64p]),
+    "swt_batch_plan_dev": (C.c_int, [C.c_void_p, C.c_uint64, bsp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_batch_rows": (C.c_int, [u32p, u64p, C.c_uint64, u32p, C.c_uint32, C.c_int, u32p, u32p, bsp, u64p, C.c_uint64, C.c_void_p, u8p, u32p,
+                                 u32p, u32p, u32p, u64p]),
+    "swt_batch_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, bsp,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "swt_batch_capacity": (C.c_int, [u32p, u32p]),
 }
 
 
@@ -457,6 +475,96 @@ def token_spans(text_u8, off, ids, tok_off, len_table, len_base, flagged, codepo
                                 int(bool(flagged)), SPAN_CODEPOINTS if codepoints else 0, ptr(spans, u32p) if ids.size else None,
                                 ptr(word, u32p) if ids.size else None, ptr(status, u8p) if n_sent else None))
     return spans, word, status
+
+
+def batch_spec(width, stride=0, windows=False, pad_left=False, ids64=False, pad_id=0, unk_id=1, cls_id=None, sep_id=None):
+    """-> BatchSpec; cls_id / sep_id None: the row has no such token"""
+    flags = (BATCH_WINDOWS if windows else 0) | (BATCH_PAD_LEFT if pad_left else 0) | (BATCH_IDS64 if ids64 else 0)
+    return BatchSpec(int(width), int(stride), flags, int(pad_id), int(unk_id), BATCH_NONE if cls_id is None else int(cls_id),
+                     BATCH_NONE if sep_id is None else int(sep_id))
+
+
+def batch_capacity():
+    """-> (cols_per_step, scan_group): the columns one wavefront of the batch kernel writes per step, and the rows of one scan
+    group of the plan (csrc/swt_batch.hip)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_batch_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def batch_plan(tok_off, spec):
+    """token offsets uint64[n_rows + 1] and a BatchSpec -> (row_base uint64[n_rows + 1] = the first output row of every source row,
+    closed by the number of output rows; the longest source row in tokens), from the device (swt_batch_plan).  Without
+    BATCH_WINDOWS the spec's width is not looked at."""
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    if tok_off.size < 1:
+        raise ValueError("offsets hold n_rows + 1 entries")
+    row_base = np.zeros(tok_off.size, dtype=np.uint64)
+    info = np.zeros(2, dtype=np.uint64)
+    check(lib().swt_batch_plan(ptr(tok_off, u64p), int(tok_off.size) - 1, C.byref(spec), ptr(row_base, u64p), ptr(info, u64p)))
+    return row_base, int(info[1])
+
+
+def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=None, word=None, row_base=None, rows_cap=None):
+    """An id stream as padded rows, on the device (swt_batch_rows).  ids uint32 with offsets uint64[n_rows + 1]; cmap: the dense
+    id of every sparse id (two halves of n_map entries when flagged), None = the identity below n_map; spans uint32[n, 2] and
+    word uint32[n]: what the span calls return, carried along.  row_base: batch_plan's, needed with BATCH_WINDOWS.
+    -> dict: input_ids int32 or int64 [rows, width], attention_mask uint8, length and sample uint32[rows], info uint64[3]
+    (rows, source rows that lost tokens, tokens sent to unk_id), and offset_mapping uint32[rows, width, 2] / word_ids
+    int32[rows, width] when the payloads were given."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    n_rows = int(tok_off.size) - 1
+    if n_rows < 0 or (n_rows and int(tok_off[-1]) > ids.size):
+        raise ValueError("offsets run past their array")
+    if cmap is not None:
+        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
+        if n_map is None:
+            n_map = int(cmap.size) // 2 if flagged else int(cmap.size)
+        if cmap.size != (2 * n_map if flagged else n_map):
+            raise ValueError("a flagged map has two halves of n_map entries")
+    elif n_map is None:
+        n_map = 0x80000000
+    n_tok = int(tok_off[-1]) if n_rows else 0
+    if spans is not None:
+        spans = np.ascontiguousarray(spans, dtype=np.uint32)
+        if spans.size < 2 * n_tok:
+            raise ValueError("two span words per token")
+    if word is not None:
+        word = np.ascontiguousarray(word, dtype=np.uint32)
+        if word.size < n_tok:
+            raise ValueError("one word index per token")
+    if row_base is not None:
+        row_base = np.ascontiguousarray(row_base, dtype=np.uint64)
+        if row_base.size != tok_off.size:
+            raise ValueError("row_base holds n_rows + 1 entries")
+    if rows_cap is None:
+        rows_cap = int(row_base[-1]) if row_base is not None else n_rows
+    rows_cap, width = int(rows_cap), int(spec.width)
+    out = {
+        "input_ids": np.zeros((rows_cap, width), dtype=np.int64 if spec.flags & BATCH_IDS64 else np.int32),
+        "attention_mask": np.zeros((rows_cap, width), dtype=np.uint8),
+        "length": np.zeros(rows_cap, dtype=np.uint32),
+        "sample": np.zeros(rows_cap, dtype=np.uint32),
+        "info": np.zeros(3, dtype=np.uint64),
+    }
+    if spans is not None:
+        out["offset_mapping"] = np.zeros((rows_cap, width, 2), dtype=np.uint32)
+    if word is not None:
+        out["word_ids"] = np.zeros((rows_cap, width), dtype=np.int32)
+    if rows_cap == 0 and n_rows == 0:
+        return out  # no row in, no row out: nothing for the device to do
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    cast = lambda a, typ: C.cast(vp(a), typ) if a is not None and a.size else None
+    rc = lib().swt_batch_rows(cast(ids, u32p), ptr(tok_off, u64p), n_rows, cast(cmap, u32p), int(n_map), int(bool(flagged)),
+                              ptr(spans, u32p) if spans is not None else None, ptr(word, u32p) if word is not None else None,
+                              C.byref(spec), ptr(row_base, u64p) if row_base is not None else None, rows_cap,
+                              out["input_ids"].ctypes.data_as(C.c_void_p), ptr(out["attention_mask"], u8p),
+                              ptr(out["offset_mapping"], u32p) if spans is not None else None,
+                              C.cast(out["word_ids"].ctypes.data_as(C.c_void_p), u32p) if word is not None else None,
+                              ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p))
+    check(rc)
+    return out
 
 
 def bpe_length_table(strings):

@@ -1,0 +1,199 @@
+"""Model-ready batches: what stands between the tokenizer classes and swt_batch_plan / swt_batch_rows.
+
+A tokenizer class gives its `Vocabulary` (`_batch_vocabulary`: specials and token strings in dense-id order, and the map from the
+encoder's ids to dense ids) and its encode calls (`encode_ids_batch`, `_batch_encode_spans`, `_batch_encode_dev`); `encode_batch`
+pads, truncates or windows the rows on the device -- through the host forms of the C ABI into NumPy arrays, or with
+`device=True` on torch tensors without the ids ever leaving the device."""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+SPECIALS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]")
+# Code points every BPE vocabulary holds besides those of its merges: merges.json is all a BPE model saves (bpe.py:167-177), and a
+# code point that never merged -- every punctuation mark: the pre-tokenizer isolates them -- is in no merge.  Basic Latin, Latin-1
+# Supplement and Latin Extended-A without controls and spaces.
+BPE_BASE_ALPHABET = [chr(c) for c in range(0x21, 0x180) if not 0x7F <= c <= 0xA0]
+
+
+class Vocabulary:
+    """tokens: strings in dense-id order; index: string -> dense id; cmap, n_map, flagged: the encoder's ids -> dense ids in the
+    convention of swt_batch_rows; special: name -> dense id"""
+
+    def __init__(self, tokens, index, cmap, n_map, flagged):
+        self.tokens, self.index, self.cmap, self.n_map, self.flagged = tokens, index, cmap, n_map, flagged
+        self.special = {name: index[s] for name, s in zip(("pad", "unk", "cls", "sep"), SPECIALS)}
+        self.d_cmap = None  # the map as a torch tensor, made by the first device call
+
+
+def bpe_vocabulary(merges, syms):
+    """The four specials, the symbol strings sorted, the same strings with '##'.  The strings are those of merges.json -- both
+    sides and the result of every merge, and their code points -- and BPE_BASE_ALPHABET: nothing that save_resources does not
+    keep.  Any other code point has no dense id and becomes [UNK]."""
+    strings = set(BPE_BASE_ALPHABET)
+    for left, right in merges:
+        strings.update((left, right, left + right))
+    strings.update(c for s in list(strings) for c in s)
+    strings.discard("")
+    strings = sorted(strings)
+    n = len(strings)
+    tokens = list(SPECIALS) + strings + ["##" + s for s in strings]
+    index = {}
+    for i, tok in enumerate(tokens):
+        index.setdefault(tok, i)
+    n_map = N.SYM_BASE + len(syms.strings)
+    cmap = np.full(2 * n_map, N.BATCH_NONE, dtype=np.uint32)
+    for i, s in enumerate(strings):
+        sid = ord(s) if len(s) == 1 else syms.index.get(s)
+        if sid is None:
+            continue  # a string no id of this table spells
+        if len(s) > 1:
+            sid += N.SYM_BASE
+        cmap[sid] = len(SPECIALS) + i
+        cmap[n_map + sid] = len(SPECIALS) + n + i
+    return Vocabulary(tokens, index, cmap, n_map, True)
+
+
+def wp_vocabulary(sorted_tokens):
+    """The vocabulary in the encoder's own order (ids index sorted(vocab): vocab.json is a set's order, wordpiece.py:196), so the
+    map is the identity on it; a special takes its index where the vocabulary has the string and is appended where not.  Both
+    unknown ids (n_vocab "['UNK']", n_vocab + 1 "[UNK]") go to [UNK]; the marker of a multi-token '##' corner has no dense id."""
+    tokens = list(sorted_tokens)
+    index = {tok: i for i, tok in enumerate(tokens)}
+    for s in SPECIALS:
+        if s not in index:
+            index[s] = len(tokens)
+            tokens.append(s)
+    index.setdefault("['UNK']", index["[UNK]"])
+    n = len(sorted_tokens)
+    cmap = np.concatenate([np.arange(n, dtype=np.uint32), np.array([index["[UNK]"], index["[UNK]"], N.BATCH_NONE], dtype=np.uint32)])
+    return Vocabulary(tokens, index, cmap, n + 3, False)
+
+
+def _width(longest, n_special, max_length, padding, multiple):
+    if padding not in ("longest", "max_length"):
+        raise ValueError("padding is 'longest' or 'max_length'")
+    if padding == "max_length":
+        if max_length is None:
+            raise ValueError("padding='max_length' needs a max_length")
+        width = int(max_length)
+    else:
+        width = max(longest, 1) + n_special
+        if max_length is not None:
+            width = min(width, int(max_length))
+    if multiple:
+        width = -(-width // int(multiple)) * int(multiple)
+    return width
+
+
+def _spec(tok, voc, width, stride, windows, add_special_tokens, padding_side, int64):
+    if padding_side not in ("right", "left"):
+        raise ValueError("padding_side is 'right' or 'left'")
+    sp = voc.special
+    return N.batch_spec(width, stride, windows, padding_side == "left", int64, sp["pad"], sp["unk"],
+                        sp["cls"] if add_special_tokens else None, sp["sep"] if add_special_tokens else None)
+
+
+def _check(texts, max_length, stride, return_overflowing):
+    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+        raise TypeError("Text to tokenize must be a string.")
+    if return_overflowing and max_length is None:
+        raise ValueError("return_overflowing needs a max_length")
+    if stride < 0:
+        raise ValueError("stride must not be negative")
+
+
+def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_to_multiple_of=None, add_special_tokens=True,
+                 padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False):
+    _check(texts, max_length, stride, return_overflowing)
+    voc = tok._batch_vocabulary()
+    n_special = 2 if add_special_tokens else 0
+    if device:
+        return _encode_batch_device(tok, voc, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
+                                    return_overflowing, return_offsets, int64, n_special)
+    spans = word = None
+    if return_offsets:
+        got = tok._batch_encode_spans(texts)
+        ids, tok_off, spans, word = got[0], got[1], got[-2], got[-1]
+    else:
+        got = tok.encode_ids_batch(texts)
+        ids, tok_off = got[0], got[1]
+    _, longest = N.batch_plan(tok_off, N.batch_spec(0))
+    width = _width(longest, n_special, max_length, padding, pad_to_multiple_of)
+    spec = _spec(tok, voc, width, stride, return_overflowing, add_special_tokens, padding_side, int64)
+    row_base = N.batch_plan(tok_off, spec)[0] if return_overflowing else None
+    out = N.batch_rows(ids, tok_off, spec, voc.cmap, voc.n_map, voc.flagged, spans, word, row_base)
+    return _result(out, return_overflowing, return_offsets, int(out["info"][2]))
+
+
+def _result(out, overflowing, offsets, n_unknown):
+    res = {"input_ids": out["input_ids"], "attention_mask": out["attention_mask"], "length": out["length"], "n_unknown": n_unknown}
+    if overflowing:
+        res["overflow_to_sample_mapping"] = out["sample"]
+    if offsets:
+        res["offset_mapping"], res["word_ids"] = out["offset_mapping"], out["word_ids"]
+    return res
+
+
+def _encode_batch_device(tok, voc, texts, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
+                         int64, n_special):
+    """The same on torch tensors, on the current device and stream: the lowercased text goes up once, the encoder's `_dev` call
+    (or its span form), swt_batch_plan_dev and swt_batch_rows_dev run on torch-owned buffers, and only `info` and the token
+    count come back."""
+    import torch
+    text, off = N.pack_utf8([t.lower() for t in texts])
+    n_bytes, n_rows = int(text.size), len(texts)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    lib = N.lib()
+
+    def empty(n, dtype):
+        return torch.empty(n, dtype=dtype, device=dev)
+
+    d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+    d_ids, d_tok_off, d_ntok = empty(n_bytes + 64, torch.int32), empty(n_rows + 1, torch.int64), torch.zeros(1, dtype=torch.int64, device=dev)
+    d_spans = empty(2 * (n_bytes + 64), torch.int32) if offsets else None
+    d_word = empty(n_bytes + 64, torch.int32) if offsets else None
+    if n_rows == 0:
+        out = {"input_ids": empty((0, 0), torch.int64 if int64 else torch.int32), "attention_mask": empty((0, 0), torch.uint8),
+               "length": empty(0, torch.int32), "sample": empty(0, torch.int32), "offset_mapping": empty((0, 0, 2), torch.int32),
+               "word_ids": empty((0, 0), torch.int32)}
+        return _result(out, overflowing, offsets, 0)
+    checks = []
+    if n_bytes == 0:
+        d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
+    else:
+        checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_rows, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None,
+                                       d_word.data_ptr() if offsets else None, stream, empty)
+    if offsets:  # as the host span calls, which raise; the ids alone come back with an empty row for such a text
+        for d_status, complain in checks:
+            status = d_status[:n_rows].cpu().numpy()
+            bad = np.flatnonzero(status)
+            if bad.size:
+                complain(int(status[int(bad[0])]), int(bad[0]), texts[int(bad[0])])
+    if voc.d_cmap is None or voc.d_cmap.device != dev:
+        voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
+    d_row_base, d_info = empty(n_rows + 1, torch.int64), empty(4, torch.int64)
+    check = N.check
+    check(lib.swt_batch_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(N.batch_spec(0)), d_row_base.data_ptr(), d_info.data_ptr(), stream))
+    longest = int(d_info[1].item())
+    width = _width(longest, n_special, max_length, padding, multiple)
+    spec = _spec(tok, voc, width, stride, overflowing, add_special_tokens, padding_side, int64)
+    rows = n_rows
+    if overflowing:
+        check(lib.swt_batch_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(spec), d_row_base.data_ptr(), d_info.data_ptr(), stream))
+        rows = int(d_info[0].item())
+    out = {"input_ids": empty((rows, width), torch.int64 if int64 else torch.int32), "attention_mask": empty((rows, width), torch.uint8),
+           "length": empty(rows, torch.int32), "sample": empty(rows, torch.int32)}
+    if offsets:
+        out["offset_mapping"], out["word_ids"] = empty((rows, width, 2), torch.int32), empty((rows, width), torch.int32)
+    check(lib.swt_batch_rows_dev(d_ids.data_ptr(), d_tok_off.data_ptr(), n_rows, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged),
+                                 d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None, C.byref(spec),
+                                 d_row_base.data_ptr() if overflowing else None, rows, out["input_ids"].data_ptr(),
+                                 out["attention_mask"].data_ptr(), out["offset_mapping"].data_ptr() if offsets else None,
+                                 out["word_ids"].data_ptr() if offsets else None, out["sample"].data_ptr(), out["length"].data_ptr(),
+                                 d_info.data_ptr(), stream))
+    return _result(out, overflowing, offsets, int(d_info[2].item()))

@@ -24,6 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from . import batching
 
 __all__ = ["SubwordTokenizer", "NaiveBPE", "FastBPE", "NaiveWP", "FastWP", "TrieView"]
 
@@ -75,6 +76,38 @@ class SubwordTokenizer:
     def vocab_length(self, corpus: List[str]) -> int:
         return len({symbol for example in corpus for symbol in example})
 
+    # -- model-ready batches (not in the reference; batching.py).  A class supplies _batch_vocabulary,
+    # encode_ids_batch, _batch_encode_spans and _batch_encode_dev.
+    def vocab_list(self) -> List[str]:
+        """The token strings in dense-id order: row i of a model's embedding table belongs to vocab_list()[i].  It depends on
+        nothing but what save_resources keeps."""
+        return list(self._batch_vocabulary().tokens)
+
+    def token_to_id(self, token: str) -> int:
+        """dense id of a token string; [UNK]'s for a string the vocabulary does not hold"""
+        voc = self._batch_vocabulary()
+        return voc.index.get(token, voc.special["unk"])
+
+    def special_ids(self) -> Dict[str, int]:
+        """{"pad", "unk", "cls", "sep"} -> dense id"""
+        return dict(self._batch_vocabulary().special)
+
+    def encode_batch(self, texts: List[str], max_length: Optional[int] = None, stride: int = 0, padding: str = "longest",
+                     pad_to_multiple_of: Optional[int] = None, add_special_tokens: bool = True, padding_side: str = "right",
+                     return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False) -> dict:
+        """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
+        [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
+        min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
+        is truncated, or with return_overflowing cut into windows that overlap by `stride` tokens ("overflow_to_sample_mapping"
+        names each row's text).  return_offsets adds "offset_mapping" [rows, width, 2] and "word_ids" [rows, width] (-1 on
+        specials and padding) from this class's span call.  device=False: NumPy arrays; device=True: torch tensors on the
+        current device and stream, the ids never leaving the device."""
+        return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
+                                     return_overflowing, return_offsets, int64, device)
+
+    def _batch_encode_spans(self, texts):
+        return self.encode_spans_batch(texts)
+
 
 _CLS_CACHE: Dict[str, int] = {}
 
@@ -109,6 +142,10 @@ class _SymbolTable:
     def string(self, sid: int) -> str:
         sid &= 0x7FFFFFFF
         return chr(sid) if sid < N.SYM_BASE else self.strings[sid - N.SYM_BASE]
+
+
+def _raise_span_mismatch(status: int, i: int, text: str) -> None:
+    raise RuntimeError("token spans: the tokens of text %d do not tile it (a bug in this library)" % i)
 
 
 _PLAIN_INTERN = _SymbolTable.intern  # (a test swaps intern() for another to force the collision replay: then the Python loop runs)
@@ -350,6 +387,33 @@ class NaiveBPE(SubwordTokenizer):
         ids, _, spans, _ = self.encode_spans_batch([text])
         return [(tok, (int(s), int(e))) for tok, (s, e) in zip(self.decode_ids(ids), spans.tolist())]
 
+    # -- model-ready batches: the hooks of SubwordTokenizer.encode_batch
+    def _batch_vocabulary(self):
+        _, syms = self._span_parts()
+        key = (len(syms.strings), len(self.merges_list))
+        cached = getattr(self, "_batch_voc", None)
+        if cached is None or cached[0] is not syms or cached[1] != key:  # a rebuilt table has a new _SymbolTable
+            cached = self._batch_voc = (syms, key, batching.bpe_vocabulary(self.merges_list, syms))
+        return cached[2]
+
+    def _batch_dev_call(self):
+        return self._ensure_naive_table().encode_naive_dev
+
+    def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
+        """the `_dev` encode on the caller's torch buffers, then swt_token_spans_dev when spans are wanted
+        -> [(status tensor, what to raise for a status)]"""
+        import torch
+        self._batch_dev_call()(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
+        if d_spans is None:
+            return []
+        lengths = self._span_lengths(self._span_parts()[1])
+        d_len = empty(lengths.size + 4, torch.int32)
+        d_len[:lengths.size].copy_(torch.from_numpy(lengths.view(np.int32)))
+        d_status = empty(n_sent + 8, torch.uint8)
+        N.check(N.lib().swt_token_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_len.data_ptr(), N.SYM_BASE, int(lengths.size),
+                                            1, N.SPAN_CODEPOINTS, d_spans, d_word, d_status.data_ptr(), stream))
+        return [(d_status, _raise_span_mismatch)]
+
     # -- bpe.py:160-164
     def reset(self) -> None:
         self.merges_list.clear()
@@ -463,6 +527,9 @@ class FastBPE(NaiveBPE):
 
     def _span_parts(self):
         return self._ensure_table().encode, self._syms
+
+    def _batch_dev_call(self):
+        return self._ensure_table().encode_dev
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -710,6 +777,33 @@ class NaiveWP(SubwordTokenizer):
         names = self._naive_tokens + ["['UNK']", "[UNK]"]
         return [(names[i], (int(s), int(e))) for i, (s, e) in zip(ids.tolist(), spans.tolist())]
 
+    # -- model-ready batches: the hooks of SubwordTokenizer.encode_batch
+    def _batch_tokens(self) -> List[str]:
+        self._ensure_naive_trie()
+        return self._naive_tokens
+
+    def _batch_vocabulary(self):
+        tokens = self._batch_tokens()
+        cached = getattr(self, "_batch_voc", None)
+        if cached is None or cached[0] is not tokens:  # a rebuilt trie has a new token list
+            cached = self._batch_voc = (tokens, batching.wp_vocabulary(tokens))
+        return cached[1]
+
+    def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
+        import torch
+        d_status = empty(n_sent + 8, torch.uint8)
+        self._ensure_naive_trie().encode_naive_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
+        checks = [(d_status, lambda st, i, text: self._raise_naive_status(st, text))]
+        if d_spans is not None:
+            lengths = self._span_lengths()
+            d_len = empty(lengths.size + 4, torch.int32)
+            d_len[:lengths.size].copy_(torch.from_numpy(lengths.view(np.int32)))
+            d_span_status = empty(n_sent + 8, torch.uint8)
+            N.check(N.lib().swt_token_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_len.data_ptr(), 0, int(lengths.size), 0,
+                                                N.SPAN_CODEPOINTS, d_spans, d_word, d_span_status.data_ptr(), stream))
+            checks.append((d_span_status, _raise_span_mismatch))
+        return checks
+
     @staticmethod
     def _raise_naive_status(st: int, text: str) -> None:
         raise RuntimeError("NaiveWP.tokenize: the reference does not terminate on this input (status %d): %r" % (st, text[:80]))
@@ -908,6 +1002,25 @@ class FastWP(NaiveWP):
         for i, (s, e) in zip(ids.tolist(), spans.tolist()):
             out.extend((tok, (int(s), int(e))) for tok in self._decode([i]))
         return out
+
+    # -- model-ready batches: FastWP's own ids and, with offsets, the spans of its trie walk
+    def _batch_tokens(self) -> List[str]:
+        if self._trie is None:
+            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")
+        return self._tokens
+
+    def _batch_encode_spans(self, texts):
+        return self.fast_encode_spans_batch(texts)
+
+    def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
+        import torch
+        d_status = empty(n_sent + 8, torch.uint8)
+        if d_spans is None:
+            self._trie.encode_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
+        else:
+            self._trie.encode_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, d_spans, d_word,
+                                        True, stream)
+        return [(d_status, lambda st, i, text: self._raise_for_status(st, text))]
 
     @staticmethod
     def _raise_for_status(st: int, text: str) -> None:
