@@ -511,6 +511,75 @@ int swt_batch_rows_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, uint64_
                        void *d_out_ids, uint8_t *d_out_mask, uint32_t *d_out_spans, uint32_t *d_out_word, uint32_t *d_out_sample, uint32_t *d_out_len,
                        uint64_t *d_info, void *stream);
 int swt_batch_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sentence-pair batches: rows [cls] A [sep] B [sep] for the two-segment tasks (question answering, NLI), with token types,
+ * truncation that spares one side and windows that slide over one side while the other is repeated in every row -- what the
+ * `tokenizers` wheel gives with the template "[CLS] $A [SEP] $B:1 [SEP]:1", enable_truncation(width, stride, strategy) and
+ * enable_padding(length=width).  The same post-pass as above with the same spec; cls_id and sep_id are both ids or both
+ * SWT_BATCH_NONE, and cap = width - 3 with them, width without.
+ *
+ * off_a[n_rows+1] and off_b[n_rows+1] index ONE stream ids / spans / word: pair r is the tokens [off_a[r], off_a[r+1]) and
+ * [off_b[r], off_b[r+1]), na and nb of them.  One encoder call over texts + text_pairs gives tok_off[2 n_rows + 1]; off_a =
+ * tok_off and off_b = tok_off + n_rows are the two arrays, with no second encode and no copy.  Any two arrays that do not
+ * decrease will do.
+ *   a pair that fits (na + nb <= cap)   one row, whatever the strategy and the stride
+ *   SWT_PAIR_ONLY_SECOND   A whole, B in a budget of cap - na tokens: its first cap - na, or with SWT_BATCH_WINDOWS windows of
+ *                          the budget that advance by budget - stride, counted and placed as the windows above; every window
+ *                          row repeats A
+ *   SWT_PAIR_ONLY_FIRST    the mirror image: B whole, A cut or windowed in cap - nb
+ *   SWT_PAIR_LONGEST_FIRST with n1 <= n2 the two lengths (A is n1 on a tie): n2 = n1 if n1 > cap, else max(n1, cap - n1); if
+ *                          n1 + n2 > cap then n1 = cap / 2, n2 = n1 + cap % 2; each side keeps its first n1 or n2 tokens.
+ *                          Truncation only: with SWT_BATCH_WINDOWS the wheel emits the cross product of both sides' windows
+ *                          in an order nobody relies on, which is out of scope here -- SWT_ERR_INVALID
+ * A pair that does not fit and whose cut side has a budget below 1 -- or, with SWT_BATCH_WINDOWS, a budget <= stride -- is
+ * REFUSED (the wheel raises "Sequence to truncate too short" / "`stride` must be strictly less than `max_len`"): status[r] =
+ * SWT_PAIR_REFUSED, and the pair still gives exactly one row: pad_id everywhere, mask 0, length 0.  Only the two ONLY
+ * strategies refuse.  The call succeeds; info[3] counts such pairs.
+ *
+ * Per column, besides the outputs of swt_batch_rows: out_type (the element type of out_ids: it indexes an embedding table) 0 on
+ * cls, A and the first sep, 1 on B and the last sep, 0 on padding; out_special 1 on cls, sep and padding; out_seq 0 on A's
+ * tokens, 1 on B's, -1 elsewhere.  Spans and word indices are each side's own, as the span calls wrote them: B's start again
+ * at 0.  An empty A gives cls sep B sep, two empty sides cls sep sep with types 0 0 1.  Without cls and sep the row is A's
+ * tokens and then B's.  Dense ids, unk_id and the padding side are those of swt_batch_rows.
+ *
+ * info[5]: [0] rows out, [1] the largest na + nb, [2] tokens sent to unk_id (once per slot written), [3] refused pairs, [4]
+ * pairs that lost tokens (without SWT_BATCH_WINDOWS; a refused pair is not among them).  The plan fills [0], [1] and [3] and
+ * zeroes the rest; with a zero width (and no SWT_BATCH_WINDOWS) it takes every pair as fitting, for a caller that wants [1]
+ * before it picks a width.  The row call fills all five, [3] and [4] over the pairs whose rows lie below rows_cap.
+ * row_base[n_rows+1] and status[n_rows] come from the plan.  The row call takes row_base as swt_batch_rows does (NULL only
+ * without SWT_BATCH_WINDOWS).  status may be NULL: the kernel takes every pair's cut from its offsets, as it takes the window
+ * counts; the host form checks a status it is given.  out_type, out_special, out_seq, out_sample, out_len, info and the payload
+ * outputs may be NULL.
+ *
+ * SWT_ERR_INVALID: what swt_batch_rows refuses; cls_id without sep_id or the reverse; a strategy that is none of the three;
+ * SWT_PAIR_LONGEST_FIRST with SWT_BATCH_WINDOWS; in the plan a NULL row_base, status or info.  The host forms check everything
+ * -- decreasing offsets, a row_base or a status that is not the plan of these offsets -- before anything touches the device,
+ * and swt_batch_pair_rows returns SWT_ERR_CAPACITY with info[0] = the rows needed when they exceed rows_cap.  The `_dev` forms
+ * enqueue and do not synchronise; swt_batch_pair_rows_dev writes every element of the rows < min(rows needed, rows_cap) of
+ * every output given and nothing at or beyond rows_cap * width, whatever ids, row_base and status hold.  The plan scans in the
+ * workspace of swt_batch_plan_dev: no two plans of either kind at once on different streams.  swt_batch_pair_capacity: as
+ * swt_batch_capacity, for the pair kernels (csrc/swt_batch.hip). */
+#define SWT_PAIR_LONGEST_FIRST 0u
+#define SWT_PAIR_ONLY_FIRST 1u
+#define SWT_PAIR_ONLY_SECOND 2u
+#define SWT_PAIR_OK 0
+#define SWT_PAIR_REFUSED 1
+int swt_batch_pair_plan(const uint64_t *off_a, const uint64_t *off_b, uint64_t n_rows, const swt_batch_spec *spec, uint32_t strategy,
+                        uint64_t *row_base, uint8_t *status, uint64_t *info);
+int swt_batch_pair_plan_dev(const uint64_t *d_off_a, const uint64_t *d_off_b, uint64_t n_rows, const swt_batch_spec *spec, uint32_t strategy,
+                            uint64_t *d_row_base, uint8_t *d_status, uint64_t *d_info, void *stream);
+int swt_batch_pair_rows(const uint32_t *ids, const uint64_t *off_a, const uint64_t *off_b, uint64_t n_rows, const uint32_t *map, uint32_t n_map,
+                        int flagged, const uint32_t *spans, const uint32_t *word, const swt_batch_spec *spec, uint32_t strategy,
+                        const uint64_t *row_base, const uint8_t *status, uint64_t rows_cap, void *out_ids, uint8_t *out_mask, void *out_type,
+                        uint8_t *out_special, int8_t *out_seq, uint32_t *out_spans, uint32_t *out_word, uint32_t *out_sample, uint32_t *out_len,
+                        uint64_t *info);
+int swt_batch_pair_rows_dev(const uint32_t *d_ids, const uint64_t *d_off_a, const uint64_t *d_off_b, uint64_t n_rows, const uint32_t *d_map,
+                            uint32_t n_map, int flagged, const uint32_t *d_spans, const uint32_t *d_word, const swt_batch_spec *spec,
+                            uint32_t strategy, const uint64_t *d_row_base, const uint8_t *d_status, uint64_t rows_cap, void *d_out_ids,
+                            uint8_t *d_out_mask, void *d_out_type, uint8_t *d_out_special, int8_t *d_out_seq, uint32_t *d_out_spans,
+                            uint32_t *d_out_word, uint32_t *d_out_sample, uint32_t *d_out_len, uint64_t *d_info, void *stream);
+int swt_batch_pair_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
 #ifdef __cplusplus
 }
 #endif

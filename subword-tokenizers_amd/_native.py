@@ -26,6 +26,8 @@ SPAN_WHOLE_WORD = 0  # a length-table entry: the token stands for its whole word
 SPAN_LEN_CONT = 0x80000000  # a length-table entry of an unflagged stream: the token continues its word ('##')
 BATCH_NONE = 0xFFFFFFFF  # swt_batch_spec: an absent cls_id / sep_id; a map entry without a dense id
 BATCH_WINDOWS, BATCH_PAD_LEFT, BATCH_IDS64 = 1, 2, 4
+PAIR_LONGEST_FIRST, PAIR_ONLY_FIRST, PAIR_ONLY_SECOND = 0, 1, 2  # the truncation strategies of swt_batch_pair_*
+PAIR_OK, PAIR_REFUSED = 0, 1
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -132,6 +134,13 @@ SIGNATURES = {
                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "swt_batch_capacity": (C.c_int, [u32p, u32p]),
+    "swt_batch_pair_plan": (C.c_int, [u64p, u64p, C.c_uint64, bsp, C.c_uint32, u64p, u8p, u64p]),
+    "swt_batch_pair_plan_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, bsp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_batch_pair_rows": (C.c_int, [u32p, u64p, u64p, C.c_uint64, u32p, C.c_uint32, C.c_int, u32p, u32p, bsp, C.c_uint32, u64p, u8p, C.c_uint64,
+                                      C.c_void_p, u8p, C.c_void_p, u8p, C.c_void_p, u32p, u32p, u32p, u32p, u64p]),
+    "swt_batch_pair_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                          bsp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 11),
+    "swt_batch_pair_capacity": (C.c_int, [u32p, u32p]),
 }
 
 
@@ -564,6 +573,103 @@ def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=N
                               C.cast(out["word_ids"].ctypes.data_as(C.c_void_p), u32p) if word is not None else None,
                               ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p))
     check(rc)
+    return out
+
+
+def batch_pair_capacity():
+    """-> (cols_per_step, scan_group) of the pair kernels, as batch_capacity"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_batch_pair_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _pair_offsets(off_a, off_b):
+    off_a, off_b = np.ascontiguousarray(off_a, dtype=np.uint64), np.ascontiguousarray(off_b, dtype=np.uint64)
+    if off_a.size < 1 or off_a.size != off_b.size:
+        raise ValueError("both offset arrays hold n_rows + 1 entries")
+    return off_a, off_b
+
+
+def batch_pair_plan(off_a, off_b, spec, strategy):
+    """The offsets of both sides into one id stream (uint64[n_rows + 1] each), a BatchSpec and a PAIR_* strategy -> (row_base
+    uint64[n_rows + 1], status uint8[n_rows] = PAIR_OK / PAIR_REFUSED, info uint64[5]: rows out, the largest na + nb, 0, refused
+    pairs, 0), from the device (swt_batch_pair_plan).  A spec of width 0 asks for the largest pair alone."""
+    off_a, off_b = _pair_offsets(off_a, off_b)
+    row_base = np.zeros(off_a.size, dtype=np.uint64)
+    status = np.zeros(off_a.size, dtype=np.uint8)  # one entry to spare: never an empty array
+    info = np.zeros(5, dtype=np.uint64)
+    check(lib().swt_batch_pair_plan(ptr(off_a, u64p), ptr(off_b, u64p), int(off_a.size) - 1, C.byref(spec), int(strategy), ptr(row_base, u64p),
+                                    ptr(status, u8p), ptr(info, u64p)))
+    return row_base, status[:-1], info
+
+
+def batch_pair_rows(ids, off_a, off_b, spec, strategy, cmap=None, n_map=None, flagged=False, spans=None, word=None, row_base=None,
+                    status=None, rows_cap=None):
+    """Pairs of one id stream as padded rows [cls] A [sep] B [sep], on the device (swt_batch_pair_rows).  The arguments of
+    batch_rows with two offset arrays, the strategy and the plan's status.  -> the dict of batch_rows and token_type_ids (the
+    type of input_ids), special_tokens_mask uint8, sequence_ids int8 [rows, width]; info uint64[5] (rows, the largest na + nb,
+    tokens sent to unk_id, refused pairs, pairs that lost tokens)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    off_a, off_b = _pair_offsets(off_a, off_b)
+    n_rows = int(off_a.size) - 1
+    n_tok = max(int(off_a[-1]), int(off_b[-1])) if n_rows else 0
+    if n_tok > ids.size:
+        raise ValueError("offsets run past their array")
+    if cmap is not None:
+        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
+        if n_map is None:
+            n_map = int(cmap.size) // 2 if flagged else int(cmap.size)
+        if cmap.size != (2 * n_map if flagged else n_map):
+            raise ValueError("a flagged map has two halves of n_map entries")
+    elif n_map is None:
+        n_map = 0x80000000
+    if spans is not None:
+        spans = np.ascontiguousarray(spans, dtype=np.uint32)
+        if spans.size < 2 * n_tok:
+            raise ValueError("two span words per token")
+    if word is not None:
+        word = np.ascontiguousarray(word, dtype=np.uint32)
+        if word.size < n_tok:
+            raise ValueError("one word index per token")
+    if row_base is not None:
+        row_base = np.ascontiguousarray(row_base, dtype=np.uint64)
+        if row_base.size != off_a.size:
+            raise ValueError("row_base holds n_rows + 1 entries")
+    if status is not None:
+        status = np.ascontiguousarray(status, dtype=np.uint8)
+        if status.size != n_rows:
+            raise ValueError("status holds n_rows entries")
+    if rows_cap is None:
+        rows_cap = int(row_base[-1]) if row_base is not None else n_rows
+    rows_cap, width = int(rows_cap), int(spec.width)
+    idt = np.int64 if spec.flags & BATCH_IDS64 else np.int32
+    out = {
+        "input_ids": np.zeros((rows_cap, width), dtype=idt),
+        "attention_mask": np.zeros((rows_cap, width), dtype=np.uint8),
+        "token_type_ids": np.zeros((rows_cap, width), dtype=idt),
+        "special_tokens_mask": np.zeros((rows_cap, width), dtype=np.uint8),
+        "sequence_ids": np.zeros((rows_cap, width), dtype=np.int8),
+        "length": np.zeros(rows_cap, dtype=np.uint32),
+        "sample": np.zeros(rows_cap, dtype=np.uint32),
+        "info": np.zeros(5, dtype=np.uint64),
+    }
+    if spans is not None:
+        out["offset_mapping"] = np.zeros((rows_cap, width, 2), dtype=np.uint32)
+    if word is not None:
+        out["word_ids"] = np.zeros((rows_cap, width), dtype=np.int32)
+    if rows_cap == 0 and n_rows == 0:
+        return out  # no pair in, no row out: nothing for the device to do
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    cast = lambda a, typ: C.cast(vp(a), typ) if a is not None and a.size else None
+    check(lib().swt_batch_pair_rows(cast(ids, u32p), ptr(off_a, u64p), ptr(off_b, u64p), n_rows, cast(cmap, u32p), int(n_map),
+                                    int(bool(flagged)), ptr(spans, u32p) if spans is not None else None,
+                                    ptr(word, u32p) if word is not None else None, C.byref(spec), int(strategy),
+                                    ptr(row_base, u64p) if row_base is not None else None, cast(status, u8p), rows_cap,
+                                    vp(out["input_ids"]), cast(out["attention_mask"], u8p), vp(out["token_type_ids"]),
+                                    cast(out["special_tokens_mask"], u8p), vp(out["sequence_ids"]),
+                                    ptr(out["offset_mapping"], u32p) if spans is not None else None,
+                                    C.cast(vp(out["word_ids"]), u32p) if word is not None else None,
+                                    ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p)))
     return out
 
 

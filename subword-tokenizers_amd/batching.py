@@ -104,10 +104,78 @@ def _check(texts, max_length, stride, return_overflowing):
         raise ValueError("stride must not be negative")
 
 
+STRATEGIES = {"longest_first": N.PAIR_LONGEST_FIRST, "only_first": N.PAIR_ONLY_FIRST, "only_second": N.PAIR_ONLY_SECOND}
+
+
+def _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask):
+    if truncation not in STRATEGIES:
+        raise ValueError("truncation is 'longest_first', 'only_first' or 'only_second'")
+    if text_pairs is None:
+        if truncation != "longest_first" or return_token_type_ids or return_special_tokens_mask:
+            raise ValueError("truncation strategies, token types and the special-tokens mask need text_pairs")
+        return
+    if not isinstance(text_pairs, list) or not all(isinstance(t, str) for t in text_pairs):
+        raise TypeError("Text to tokenize must be a string.")
+    if len(text_pairs) != len(texts):
+        raise ValueError("text_pairs holds one text for every text")
+    if return_overflowing and truncation == "longest_first":
+        raise ValueError("return_overflowing with pairs needs truncation='only_first' or 'only_second'")
+
+
+def _raise_refused(status, off_a, off_b, cap, stride, windows, truncation):
+    """the ValueError for the first refused pair; off_a, off_b: the offsets of both sides as NumPy arrays"""
+    r = int(np.flatnonzero(status)[0])
+    na, nb = int(off_a[r + 1] - off_a[r]), int(off_b[r + 1] - off_b[r])
+    budget = cap - (nb if truncation == "only_first" else na)
+    why = "no token" if budget < 1 else "%d tokens, not more than the stride %d" % (budget, stride) if windows else "%d tokens" % budget
+    raise ValueError("pair %d (%d and %d tokens) cannot be truncated with %r: %d tokens fit a row and the other side leaves %s"
+                     % (r, na, nb, truncation, cap, why))
+
+
+def _pair_result(out, overflowing, offsets, token_types, special_mask):
+    res = _result(out, overflowing, offsets, int(out["info"][2]))
+    res["sequence_ids"] = out["sequence_ids"]
+    if token_types:
+        res["token_type_ids"] = out["token_type_ids"]
+    if special_mask:
+        res["special_tokens_mask"] = out["special_tokens_mask"]
+    return res
+
+
+def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
+                  int64, truncation, token_types, special_mask):
+    """pairs through the host forms: ONE encode of texts + text_pairs, whose offsets from len(texts) on are those of the B sides"""
+    n, strategy, n_special = len(texts), STRATEGIES[truncation], 3 if add_special_tokens else 0
+    spans = word = None
+    if offsets:
+        got = tok._batch_encode_spans(texts + text_pairs)
+        ids, tok_off, spans, word = got[0], got[1], got[-2], got[-1]
+    else:
+        got = tok.encode_ids_batch(texts + text_pairs)
+        ids, tok_off = got[0], got[1]
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    off_a, off_b = tok_off[:n + 1], tok_off[n:]
+    longest = int(N.batch_pair_plan(off_a, off_b, N.batch_spec(0), strategy)[2][1])
+    width = _width(longest, n_special, max_length, padding, multiple)
+    spec = _spec(tok, voc, width, stride, overflowing, add_special_tokens, padding_side, int64)
+    row_base, status, info = N.batch_pair_plan(off_a, off_b, spec, strategy)
+    if info[3]:
+        _raise_refused(status, off_a, off_b, width - n_special, stride, overflowing, truncation)
+    out = N.batch_pair_rows(ids, off_a, off_b, spec, strategy, voc.cmap, voc.n_map, voc.flagged, spans, word, row_base, status)
+    return _pair_result(out, overflowing, offsets, token_types, special_mask)
+
+
 def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_to_multiple_of=None, add_special_tokens=True,
-                 padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False):
+                 padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False, text_pairs=None,
+                 truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False):
     _check(texts, max_length, stride, return_overflowing)
+    _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask)
     voc = tok._batch_vocabulary()
+    if text_pairs is not None:
+        token_types = return_token_type_ids is None or bool(return_token_type_ids)
+        run = _encode_pairs_device if device else _encode_pairs
+        return run(tok, voc, texts, text_pairs, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
+                   return_overflowing, return_offsets, int64, truncation, token_types, bool(return_special_tokens_mask))
     n_special = 2 if add_special_tokens else 0
     if device:
         return _encode_batch_device(tok, voc, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
@@ -197,3 +265,76 @@ def _encode_batch_device(tok, voc, texts, max_length, stride, padding, multiple,
                                  out["word_ids"].data_ptr() if offsets else None, out["sample"].data_ptr(), out["length"].data_ptr(),
                                  d_info.data_ptr(), stream))
     return _result(out, overflowing, offsets, int(d_info[2].item()))
+
+
+def _encode_pairs_device(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing,
+                         offsets, int64, truncation, token_types, special_mask):
+    """Pairs on torch tensors, on the current device and stream: ONE upload of the lowercased texts + text_pairs, one `_dev`
+    encode (or its span form), swt_batch_pair_plan_dev and swt_batch_pair_rows_dev; `info`, and the statuses of a batch that
+    holds a refused pair, are all that comes back."""
+    import torch
+    both = texts + text_pairs
+    text, off = N.pack_utf8([t.lower() for t in both])
+    n_bytes, n, n_sent = int(text.size), len(texts), len(both)
+    strategy, n_special = STRATEGIES[truncation], 3 if add_special_tokens else 0
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    lib, check = N.lib(), N.check
+    idt = torch.int64 if int64 else torch.int32
+
+    def empty(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    if n == 0:
+        out = {"input_ids": empty((0, 0), idt), "attention_mask": empty((0, 0), torch.uint8), "token_type_ids": empty((0, 0), idt),
+               "special_tokens_mask": empty((0, 0), torch.uint8), "sequence_ids": empty((0, 0), torch.int8), "length": empty(0, torch.int32),
+               "sample": empty(0, torch.int32), "offset_mapping": empty((0, 0, 2), torch.int32), "word_ids": empty((0, 0), torch.int32),
+               "info": [0] * 5}
+        return _pair_result(out, overflowing, offsets, token_types, special_mask)
+    d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+    d_ids, d_tok_off, d_ntok = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64), torch.zeros(1, dtype=torch.int64, device=dev)
+    d_spans = empty(2 * (n_bytes + 64), torch.int32) if offsets else None
+    d_word = empty(n_bytes + 64, torch.int32) if offsets else None
+    checks = []
+    if n_bytes == 0:
+        d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
+    else:
+        checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None,
+                                       d_word.data_ptr() if offsets else None, stream, empty)
+    if offsets:  # as the host span calls, which raise
+        for d_status, complain in checks:
+            status = d_status[:n_sent].cpu().numpy()
+            bad = np.flatnonzero(status)
+            if bad.size:
+                complain(int(status[int(bad[0])]), int(bad[0]), both[int(bad[0])])
+    if voc.d_cmap is None or voc.d_cmap.device != dev:
+        voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
+    p_a, p_b = d_tok_off.data_ptr(), d_tok_off.data_ptr() + 8 * n  # the B sides' offsets start where the A sides' end
+    d_row_base, d_status, d_info = empty(n + 1, torch.int64), empty(n + 8, torch.uint8), empty(8, torch.int64)
+    check(lib.swt_batch_pair_plan_dev(p_a, p_b, n, C.byref(N.batch_spec(0)), strategy, d_row_base.data_ptr(), d_status.data_ptr(),
+                                      d_info.data_ptr(), stream))
+    width = _width(int(d_info[1].item()), n_special, max_length, padding, multiple)
+    spec = _spec(tok, voc, width, stride, overflowing, add_special_tokens, padding_side, int64)
+    check(lib.swt_batch_pair_plan_dev(p_a, p_b, n, C.byref(spec), strategy, d_row_base.data_ptr(), d_status.data_ptr(), d_info.data_ptr(),
+                                      stream))
+    info = d_info[:5].cpu().numpy()
+    if info[3]:
+        h_off = d_tok_off.cpu().numpy()
+        _raise_refused(d_status[:n].cpu().numpy(), h_off[:n + 1], h_off[n:], width - n_special, stride, overflowing, truncation)
+    rows = int(info[0])
+    out = {"input_ids": empty((rows, width), idt), "attention_mask": empty((rows, width), torch.uint8),
+           "token_type_ids": empty((rows, width), idt) if token_types else None,
+           "special_tokens_mask": empty((rows, width), torch.uint8) if special_mask else None,
+           "sequence_ids": empty((rows, width), torch.int8), "length": empty(rows, torch.int32), "sample": empty(rows, torch.int32),
+           "offset_mapping": empty((rows, width, 2), torch.int32) if offsets else None,
+           "word_ids": empty((rows, width), torch.int32) if offsets else None}
+    p = {k: (v.data_ptr() if v is not None else None) for k, v in out.items()}
+    check(lib.swt_batch_pair_rows_dev(d_ids.data_ptr(), p_a, p_b, n, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged),
+                                      d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None, C.byref(spec), strategy,
+                                      d_row_base.data_ptr(), d_status.data_ptr(), rows, p["input_ids"], p["attention_mask"],
+                                      p["token_type_ids"], p["special_tokens_mask"], p["sequence_ids"], p["offset_mapping"], p["word_ids"],
+                                      p["sample"], p["length"], d_info.data_ptr(), stream))
+    out["info"] = d_info[:5].cpu().numpy()
+    return _pair_result(out, overflowing, offsets, token_types, special_mask)

@@ -94,16 +94,27 @@ class SubwordTokenizer:
 
     def encode_batch(self, texts: List[str], max_length: Optional[int] = None, stride: int = 0, padding: str = "longest",
                      pad_to_multiple_of: Optional[int] = None, add_special_tokens: bool = True, padding_side: str = "right",
-                     return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False) -> dict:
+                     return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False,
+                     text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
+                     return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
         is truncated, or with return_overflowing cut into windows that overlap by `stride` tokens ("overflow_to_sample_mapping"
         names each row's text).  return_offsets adds "offset_mapping" [rows, width, 2] and "word_ids" [rows, width] (-1 on
         specials and padding) from this class's span call.  device=False: NumPy arrays; device=True: torch tensors on the
-        current device and stream, the ids never leaving the device."""
+        current device and stream, the ids never leaving the device.
+
+        text_pairs (one text per text) makes every row a pair, [CLS] text [SEP] pair [SEP] (swt_batch_pair_rows): the result
+        gains "sequence_ids" (0 on the text's tokens, 1 on the pair's, -1 elsewhere), "token_type_ids" (unless
+        return_token_type_ids=False) and with return_special_tokens_mask "special_tokens_mask"; offsets and word ids are each
+        side's own.  truncation: "longest_first" takes from the longer side, "only_first" / "only_second" cut the named side
+        and spare the other; with return_overflowing the cut side is windowed and the other repeated in every row
+        ("longest_first" has no windows).  A pair whose spared side leaves the other no room raises ValueError.  Without
+        text_pairs these keywords have nothing to act on and any value but the default raises ValueError."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
-                                     return_overflowing, return_offsets, int64, device)
+                                     return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
+                                     return_special_tokens_mask)
 
     def _batch_encode_spans(self, texts):
         return self.encode_spans_batch(texts)
