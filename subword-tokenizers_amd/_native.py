@@ -526,6 +526,34 @@ def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=N
     n_rows = int(tok_off.size) - 1
     if n_rows < 0 or (n_rows and int(tok_off[-1]) > ids.size):
         raise ValueError("offsets run past their array")
+    n_tok = int(tok_off[-1]) if n_rows else 0
+    cmap, n_map, spans, word, row_base, rows_cap, out = _batch_rows_setup(n_rows, n_tok, spec, cmap, n_map, flagged, spans, word, row_base,
+                                                                          rows_cap, 3)
+    if rows_cap == 0 and n_rows == 0:
+        return out  # no row in, no row out: nothing for the device to do
+    check(lib().swt_batch_rows(_cast(ids, u32p), ptr(tok_off, u64p), n_rows, _cast(cmap, u32p), n_map, int(bool(flagged)),
+                               ptr(spans, u32p) if spans is not None else None, ptr(word, u32p) if word is not None else None,
+                               C.byref(spec), ptr(row_base, u64p) if row_base is not None else None, rows_cap,
+                               out["input_ids"].ctypes.data_as(C.c_void_p), ptr(out["attention_mask"], u8p),
+                               ptr(out["offset_mapping"], u32p) if spans is not None else None,
+                               C.cast(out["word_ids"].ctypes.data_as(C.c_void_p), u32p) if word is not None else None,
+                               ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p)))
+    return out
+
+
+def _vp(a):
+    """the data of a NumPy array as void *; None for no array and for an empty one"""
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def _cast(a, typ):
+    return C.cast(_vp(a), typ) if a is not None and a.size else None
+
+
+def _batch_rows_setup(n_rows, n_tok, spec, cmap, n_map, flagged, spans, word, row_base, rows_cap, n_info):
+    """What batch_rows and batch_pair_rows do alike with their arguments: the map, the payloads of n_tok tokens and row_base as
+    contiguous arrays of their types, each held to its size; n_map and rows_cap where they were left out; and the outputs both
+    return, zeroed.  -> (cmap, n_map, spans, word, row_base, rows_cap, out)"""
     if cmap is not None:
         cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
         if n_map is None:
@@ -534,7 +562,6 @@ def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=N
             raise ValueError("a flagged map has two halves of n_map entries")
     elif n_map is None:
         n_map = 0x80000000
-    n_tok = int(tok_off[-1]) if n_rows else 0
     if spans is not None:
         spans = np.ascontiguousarray(spans, dtype=np.uint32)
         if spans.size < 2 * n_tok:
@@ -545,7 +572,7 @@ def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=N
             raise ValueError("one word index per token")
     if row_base is not None:
         row_base = np.ascontiguousarray(row_base, dtype=np.uint64)
-        if row_base.size != tok_off.size:
+        if row_base.size != n_rows + 1:
             raise ValueError("row_base holds n_rows + 1 entries")
     if rows_cap is None:
         rows_cap = int(row_base[-1]) if row_base is not None else n_rows
@@ -555,25 +582,13 @@ def batch_rows(ids, tok_off, spec, cmap=None, n_map=None, flagged=False, spans=N
         "attention_mask": np.zeros((rows_cap, width), dtype=np.uint8),
         "length": np.zeros(rows_cap, dtype=np.uint32),
         "sample": np.zeros(rows_cap, dtype=np.uint32),
-        "info": np.zeros(3, dtype=np.uint64),
+        "info": np.zeros(n_info, dtype=np.uint64),
     }
     if spans is not None:
         out["offset_mapping"] = np.zeros((rows_cap, width, 2), dtype=np.uint32)
     if word is not None:
         out["word_ids"] = np.zeros((rows_cap, width), dtype=np.int32)
-    if rows_cap == 0 and n_rows == 0:
-        return out  # no row in, no row out: nothing for the device to do
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-    cast = lambda a, typ: C.cast(vp(a), typ) if a is not None and a.size else None
-    rc = lib().swt_batch_rows(cast(ids, u32p), ptr(tok_off, u64p), n_rows, cast(cmap, u32p), int(n_map), int(bool(flagged)),
-                              ptr(spans, u32p) if spans is not None else None, ptr(word, u32p) if word is not None else None,
-                              C.byref(spec), ptr(row_base, u64p) if row_base is not None else None, rows_cap,
-                              out["input_ids"].ctypes.data_as(C.c_void_p), ptr(out["attention_mask"], u8p),
-                              ptr(out["offset_mapping"], u32p) if spans is not None else None,
-                              C.cast(out["word_ids"].ctypes.data_as(C.c_void_p), u32p) if word is not None else None,
-                              ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p))
-    check(rc)
-    return out
+    return cmap, int(n_map), spans, word, row_base, rows_cap, out
 
 
 def batch_pair_capacity():
@@ -615,60 +630,26 @@ def batch_pair_rows(ids, off_a, off_b, spec, strategy, cmap=None, n_map=None, fl
     n_tok = max(int(off_a[-1]), int(off_b[-1])) if n_rows else 0
     if n_tok > ids.size:
         raise ValueError("offsets run past their array")
-    if cmap is not None:
-        cmap = np.ascontiguousarray(cmap, dtype=np.uint32)
-        if n_map is None:
-            n_map = int(cmap.size) // 2 if flagged else int(cmap.size)
-        if cmap.size != (2 * n_map if flagged else n_map):
-            raise ValueError("a flagged map has two halves of n_map entries")
-    elif n_map is None:
-        n_map = 0x80000000
-    if spans is not None:
-        spans = np.ascontiguousarray(spans, dtype=np.uint32)
-        if spans.size < 2 * n_tok:
-            raise ValueError("two span words per token")
-    if word is not None:
-        word = np.ascontiguousarray(word, dtype=np.uint32)
-        if word.size < n_tok:
-            raise ValueError("one word index per token")
-    if row_base is not None:
-        row_base = np.ascontiguousarray(row_base, dtype=np.uint64)
-        if row_base.size != off_a.size:
-            raise ValueError("row_base holds n_rows + 1 entries")
+    cmap, n_map, spans, word, row_base, rows_cap, out = _batch_rows_setup(n_rows, n_tok, spec, cmap, n_map, flagged, spans, word, row_base,
+                                                                          rows_cap, 5)
     if status is not None:
         status = np.ascontiguousarray(status, dtype=np.uint8)
         if status.size != n_rows:
             raise ValueError("status holds n_rows entries")
-    if rows_cap is None:
-        rows_cap = int(row_base[-1]) if row_base is not None else n_rows
-    rows_cap, width = int(rows_cap), int(spec.width)
-    idt = np.int64 if spec.flags & BATCH_IDS64 else np.int32
-    out = {
-        "input_ids": np.zeros((rows_cap, width), dtype=idt),
-        "attention_mask": np.zeros((rows_cap, width), dtype=np.uint8),
-        "token_type_ids": np.zeros((rows_cap, width), dtype=idt),
-        "special_tokens_mask": np.zeros((rows_cap, width), dtype=np.uint8),
-        "sequence_ids": np.zeros((rows_cap, width), dtype=np.int8),
-        "length": np.zeros(rows_cap, dtype=np.uint32),
-        "sample": np.zeros(rows_cap, dtype=np.uint32),
-        "info": np.zeros(5, dtype=np.uint64),
-    }
-    if spans is not None:
-        out["offset_mapping"] = np.zeros((rows_cap, width, 2), dtype=np.uint32)
-    if word is not None:
-        out["word_ids"] = np.zeros((rows_cap, width), dtype=np.int32)
+    shape = out["input_ids"].shape
+    out["token_type_ids"] = np.zeros(shape, dtype=out["input_ids"].dtype)
+    out["special_tokens_mask"] = np.zeros(shape, dtype=np.uint8)
+    out["sequence_ids"] = np.zeros(shape, dtype=np.int8)
     if rows_cap == 0 and n_rows == 0:
         return out  # no pair in, no row out: nothing for the device to do
-    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-    cast = lambda a, typ: C.cast(vp(a), typ) if a is not None and a.size else None
-    check(lib().swt_batch_pair_rows(cast(ids, u32p), ptr(off_a, u64p), ptr(off_b, u64p), n_rows, cast(cmap, u32p), int(n_map),
+    check(lib().swt_batch_pair_rows(_cast(ids, u32p), ptr(off_a, u64p), ptr(off_b, u64p), n_rows, _cast(cmap, u32p), n_map,
                                     int(bool(flagged)), ptr(spans, u32p) if spans is not None else None,
                                     ptr(word, u32p) if word is not None else None, C.byref(spec), int(strategy),
-                                    ptr(row_base, u64p) if row_base is not None else None, cast(status, u8p), rows_cap,
-                                    vp(out["input_ids"]), cast(out["attention_mask"], u8p), vp(out["token_type_ids"]),
-                                    cast(out["special_tokens_mask"], u8p), vp(out["sequence_ids"]),
+                                    ptr(row_base, u64p) if row_base is not None else None, _cast(status, u8p), rows_cap,
+                                    _vp(out["input_ids"]), _cast(out["attention_mask"], u8p), _vp(out["token_type_ids"]),
+                                    _cast(out["special_tokens_mask"], u8p), _vp(out["sequence_ids"]),
                                     ptr(out["offset_mapping"], u32p) if spans is not None else None,
-                                    C.cast(vp(out["word_ids"]), u32p) if word is not None else None,
+                                    C.cast(_vp(out["word_ids"]), u32p) if word is not None else None,
                                     ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p)))
     return out
 

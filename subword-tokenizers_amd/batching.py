@@ -142,17 +142,20 @@ def _pair_result(out, overflowing, offsets, token_types, special_mask):
     return res
 
 
+def _encode_host(tok, texts, offsets):
+    """one encode through the host forms -> (ids, tok_off, spans, word); spans and word are None without offsets"""
+    if offsets:
+        got = tok._batch_encode_spans(texts)
+        return got[0], got[1], got[-2], got[-1]
+    got = tok.encode_ids_batch(texts)
+    return got[0], got[1], None, None
+
+
 def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
                   int64, truncation, token_types, special_mask):
     """pairs through the host forms: ONE encode of texts + text_pairs, whose offsets from len(texts) on are those of the B sides"""
     n, strategy, n_special = len(texts), STRATEGIES[truncation], 3 if add_special_tokens else 0
-    spans = word = None
-    if offsets:
-        got = tok._batch_encode_spans(texts + text_pairs)
-        ids, tok_off, spans, word = got[0], got[1], got[-2], got[-1]
-    else:
-        got = tok.encode_ids_batch(texts + text_pairs)
-        ids, tok_off = got[0], got[1]
+    ids, tok_off, spans, word = _encode_host(tok, texts + text_pairs, offsets)
     tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
     off_a, off_b = tok_off[:n + 1], tok_off[n:]
     longest = int(N.batch_pair_plan(off_a, off_b, N.batch_spec(0), strategy)[2][1])
@@ -171,24 +174,19 @@ def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_t
     _check(texts, max_length, stride, return_overflowing)
     _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask)
     voc = tok._batch_vocabulary()
+    geometry = (max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing, return_offsets, int64)
     if text_pairs is not None:
-        token_types = return_token_type_ids is None or bool(return_token_type_ids)
-        run = _encode_pairs_device if device else _encode_pairs
-        return run(tok, voc, texts, text_pairs, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
-                   return_overflowing, return_offsets, int64, truncation, token_types, bool(return_special_tokens_mask))
-    n_special = 2 if add_special_tokens else 0
+        token_types, special_mask = return_token_type_ids is None or bool(return_token_type_ids), bool(return_special_tokens_mask)
+        if not device:
+            return _encode_pairs(tok, voc, texts, text_pairs, *geometry, truncation, token_types, special_mask)
+        out = _encode_device(tok, voc, texts + text_pairs, len(texts), *geometry, (truncation, token_types, special_mask))
+        return _pair_result(out, return_overflowing, return_offsets, token_types, special_mask)
     if device:
-        return _encode_batch_device(tok, voc, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
-                                    return_overflowing, return_offsets, int64, n_special)
-    spans = word = None
-    if return_offsets:
-        got = tok._batch_encode_spans(texts)
-        ids, tok_off, spans, word = got[0], got[1], got[-2], got[-1]
-    else:
-        got = tok.encode_ids_batch(texts)
-        ids, tok_off = got[0], got[1]
+        out = _encode_device(tok, voc, texts, len(texts), *geometry)
+        return _result(out, return_overflowing, return_offsets, int(out["info"][2]))
+    ids, tok_off, spans, word = _encode_host(tok, texts, return_offsets)
     _, longest = N.batch_plan(tok_off, N.batch_spec(0))
-    width = _width(longest, n_special, max_length, padding, pad_to_multiple_of)
+    width = _width(longest, 2 if add_special_tokens else 0, max_length, padding, pad_to_multiple_of)
     spec = _spec(tok, voc, width, stride, return_overflowing, add_special_tokens, padding_side, int64)
     row_base = N.batch_plan(tok_off, spec)[0] if return_overflowing else None
     out = N.batch_rows(ids, tok_off, spec, voc.cmap, voc.n_map, voc.flagged, spans, word, row_base)
@@ -204,137 +202,89 @@ def _result(out, overflowing, offsets, n_unknown):
     return res
 
 
-def _encode_batch_device(tok, voc, texts, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
-                         int64, n_special):
-    """The same on torch tensors, on the current device and stream: the lowercased text goes up once, the encoder's `_dev` call
-    (or its span form), swt_batch_plan_dev and swt_batch_rows_dev run on torch-owned buffers, and only `info` and the token
-    count come back."""
+def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
+                   int64, pair=None):
+    """The same on torch tensors, on the current device and stream: ONE upload of the lowercased texts, one `_dev` encode (or its
+    span form), the plan and the rows call on torch-owned buffers; `info`, the token count and, of a batch that holds a refused
+    pair, the statuses are all that comes back.  texts: every text of the call -- of pairs the A sides and then the B sides,
+    n_rows of each, so that the B sides' offsets start where the A sides' end.  pair: None for single rows (swt_batch_plan_dev,
+    swt_batch_rows_dev), else (truncation, token_types, special_mask) (swt_batch_pair_plan_dev, swt_batch_pair_rows_dev).
+    -> the arrays of _native.batch_rows / batch_pair_rows as tensors, an output nobody asked for None, and "info"."""
     import torch
     text, off = N.pack_utf8([t.lower() for t in texts])
-    n_bytes, n_rows = int(text.size), len(texts)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.current_stream().cuda_stream
-    lib = N.lib()
-
-    def empty(n, dtype):
-        return torch.empty(n, dtype=dtype, device=dev)
-
-    d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
-    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
-    d_ids, d_tok_off, d_ntok = empty(n_bytes + 64, torch.int32), empty(n_rows + 1, torch.int64), torch.zeros(1, dtype=torch.int64, device=dev)
-    d_spans = empty(2 * (n_bytes + 64), torch.int32) if offsets else None
-    d_word = empty(n_bytes + 64, torch.int32) if offsets else None
-    if n_rows == 0:
-        out = {"input_ids": empty((0, 0), torch.int64 if int64 else torch.int32), "attention_mask": empty((0, 0), torch.uint8),
-               "length": empty(0, torch.int32), "sample": empty(0, torch.int32), "offset_mapping": empty((0, 0, 2), torch.int32),
-               "word_ids": empty((0, 0), torch.int32)}
-        return _result(out, overflowing, offsets, 0)
-    checks = []
-    if n_bytes == 0:
-        d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
-    else:
-        checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_rows, d_ids.data_ptr(), d_tok_off.data_ptr(),
-                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None,
-                                       d_word.data_ptr() if offsets else None, stream, empty)
-    if offsets:  # as the host span calls, which raise; the ids alone come back with an empty row for such a text
-        for d_status, complain in checks:
-            status = d_status[:n_rows].cpu().numpy()
-            bad = np.flatnonzero(status)
-            if bad.size:
-                complain(int(status[int(bad[0])]), int(bad[0]), texts[int(bad[0])])
-    if voc.d_cmap is None or voc.d_cmap.device != dev:
-        voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
-    d_row_base, d_info = empty(n_rows + 1, torch.int64), empty(4, torch.int64)
-    check = N.check
-    check(lib.swt_batch_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(N.batch_spec(0)), d_row_base.data_ptr(), d_info.data_ptr(), stream))
-    longest = int(d_info[1].item())
-    width = _width(longest, n_special, max_length, padding, multiple)
-    spec = _spec(tok, voc, width, stride, overflowing, add_special_tokens, padding_side, int64)
-    rows = n_rows
-    if overflowing:
-        check(lib.swt_batch_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(spec), d_row_base.data_ptr(), d_info.data_ptr(), stream))
-        rows = int(d_info[0].item())
-    out = {"input_ids": empty((rows, width), torch.int64 if int64 else torch.int32), "attention_mask": empty((rows, width), torch.uint8),
-           "length": empty(rows, torch.int32), "sample": empty(rows, torch.int32)}
-    if offsets:
-        out["offset_mapping"], out["word_ids"] = empty((rows, width, 2), torch.int32), empty((rows, width), torch.int32)
-    check(lib.swt_batch_rows_dev(d_ids.data_ptr(), d_tok_off.data_ptr(), n_rows, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged),
-                                 d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None, C.byref(spec),
-                                 d_row_base.data_ptr() if overflowing else None, rows, out["input_ids"].data_ptr(),
-                                 out["attention_mask"].data_ptr(), out["offset_mapping"].data_ptr() if offsets else None,
-                                 out["word_ids"].data_ptr() if offsets else None, out["sample"].data_ptr(), out["length"].data_ptr(),
-                                 d_info.data_ptr(), stream))
-    return _result(out, overflowing, offsets, int(d_info[2].item()))
-
-
-def _encode_pairs_device(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing,
-                         offsets, int64, truncation, token_types, special_mask):
-    """Pairs on torch tensors, on the current device and stream: ONE upload of the lowercased texts + text_pairs, one `_dev`
-    encode (or its span form), swt_batch_pair_plan_dev and swt_batch_pair_rows_dev; `info`, and the statuses of a batch that
-    holds a refused pair, are all that comes back."""
-    import torch
-    both = texts + text_pairs
-    text, off = N.pack_utf8([t.lower() for t in both])
-    n_bytes, n, n_sent = int(text.size), len(texts), len(both)
-    strategy, n_special = STRATEGIES[truncation], 3 if add_special_tokens else 0
+    n_bytes, n_sent = int(text.size), len(texts)
+    truncation, token_types, special_mask = pair or (None, False, False)
+    n_special, n_info = ((3 if pair else 2) if add_special_tokens else 0), (5 if pair else 3)
     dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.current_stream().cuda_stream
     lib, check = N.lib(), N.check
     idt = torch.int64 if int64 else torch.int32
 
-    def empty(shape, dtype):
-        return torch.empty(shape, dtype=dtype, device=dev)
+    def empty(shape, dtype, wanted=True):
+        return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
 
-    if n == 0:
-        out = {"input_ids": empty((0, 0), idt), "attention_mask": empty((0, 0), torch.uint8), "token_type_ids": empty((0, 0), idt),
-               "special_tokens_mask": empty((0, 0), torch.uint8), "sequence_ids": empty((0, 0), torch.int8), "length": empty(0, torch.int32),
-               "sample": empty(0, torch.int32), "offset_mapping": empty((0, 0, 2), torch.int32), "word_ids": empty((0, 0), torch.int32),
-               "info": [0] * 5}
-        return _pair_result(out, overflowing, offsets, token_types, special_mask)
+    def outputs(rows, width):
+        out = {"input_ids": empty((rows, width), idt), "attention_mask": empty((rows, width), torch.uint8),
+               "length": empty(rows, torch.int32), "sample": empty(rows, torch.int32),
+               "offset_mapping": empty((rows, width, 2), torch.int32, offsets), "word_ids": empty((rows, width), torch.int32, offsets)}
+        if pair:
+            out.update({"token_type_ids": empty((rows, width), idt, token_types),
+                        "special_tokens_mask": empty((rows, width), torch.uint8, special_mask),
+                        "sequence_ids": empty((rows, width), torch.int8)})
+        return out
+
+    if n_rows == 0:
+        return dict(outputs(0, 0), info=[0] * n_info)
     d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
     d_off = torch.from_numpy(off.view(np.int64)).to(dev)
     d_ids, d_tok_off, d_ntok = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64), torch.zeros(1, dtype=torch.int64, device=dev)
-    d_spans = empty(2 * (n_bytes + 64), torch.int32) if offsets else None
-    d_word = empty(n_bytes + 64, torch.int32) if offsets else None
+    d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, offsets), empty(n_bytes + 64, torch.int32, offsets)
+    p_spans, p_word = (d_spans.data_ptr(), d_word.data_ptr()) if offsets else (None, None)
     checks = []
     if n_bytes == 0:
         d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
     else:
         checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
-                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None,
-                                       d_word.data_ptr() if offsets else None, stream, empty)
-    if offsets:  # as the host span calls, which raise
-        for d_status, complain in checks:
-            status = d_status[:n_sent].cpu().numpy()
+                                       d_ntok.data_ptr(), p_spans, p_word, stream, empty)
+    if offsets:  # as the host span calls, which raise; the ids alone come back with an empty row for such a text
+        for d_flags, complain in checks:
+            status = d_flags[:n_sent].cpu().numpy()
             bad = np.flatnonzero(status)
             if bad.size:
-                complain(int(status[int(bad[0])]), int(bad[0]), both[int(bad[0])])
+                complain(int(status[int(bad[0])]), int(bad[0]), texts[int(bad[0])])
     if voc.d_cmap is None or voc.d_cmap.device != dev:
         voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
-    p_a, p_b = d_tok_off.data_ptr(), d_tok_off.data_ptr() + 8 * n  # the B sides' offsets start where the A sides' end
-    d_row_base, d_status, d_info = empty(n + 1, torch.int64), empty(n + 8, torch.uint8), empty(8, torch.int64)
-    check(lib.swt_batch_pair_plan_dev(p_a, p_b, n, C.byref(N.batch_spec(0)), strategy, d_row_base.data_ptr(), d_status.data_ptr(),
-                                      d_info.data_ptr(), stream))
-    width = _width(int(d_info[1].item()), n_special, max_length, padding, multiple)
+    d_row_base, d_info = empty(n_rows + 1, torch.int64), empty(8, torch.int64)
+    p_off = (d_tok_off.data_ptr(),)
+    if pair:
+        p_off += (d_tok_off.data_ptr() + 8 * n_rows,)
+        strategy, d_status = STRATEGIES[truncation], empty(n_rows + 8, torch.uint8)
+
+    def plan(spec):
+        if pair:
+            check(lib.swt_batch_pair_plan_dev(*p_off, n_rows, C.byref(spec), strategy, d_row_base.data_ptr(), d_status.data_ptr(),
+                                              d_info.data_ptr(), stream))
+        else:
+            check(lib.swt_batch_plan_dev(*p_off, n_rows, C.byref(spec), d_row_base.data_ptr(), d_info.data_ptr(), stream))
+        return d_info[:n_info].cpu().numpy()
+
+    width = _width(int(plan(N.batch_spec(0))[1]), n_special, max_length, padding, multiple)
     spec = _spec(tok, voc, width, stride, overflowing, add_special_tokens, padding_side, int64)
-    check(lib.swt_batch_pair_plan_dev(p_a, p_b, n, C.byref(spec), strategy, d_row_base.data_ptr(), d_status.data_ptr(), d_info.data_ptr(),
-                                      stream))
-    info = d_info[:5].cpu().numpy()
-    if info[3]:
-        h_off = d_tok_off.cpu().numpy()
-        _raise_refused(d_status[:n].cpu().numpy(), h_off[:n + 1], h_off[n:], width - n_special, stride, overflowing, truncation)
-    rows = int(info[0])
-    out = {"input_ids": empty((rows, width), idt), "attention_mask": empty((rows, width), torch.uint8),
-           "token_type_ids": empty((rows, width), idt) if token_types else None,
-           "special_tokens_mask": empty((rows, width), torch.uint8) if special_mask else None,
-           "sequence_ids": empty((rows, width), torch.int8), "length": empty(rows, torch.int32), "sample": empty(rows, torch.int32),
-           "offset_mapping": empty((rows, width, 2), torch.int32) if offsets else None,
-           "word_ids": empty((rows, width), torch.int32) if offsets else None}
+    rows = n_rows
+    if pair or overflowing:  # a pair's plan also says whether one is refused
+        info = plan(spec)
+        if pair and info[3]:
+            h_off = d_tok_off.cpu().numpy()
+            _raise_refused(d_status[:n_rows].cpu().numpy(), h_off[:n_rows + 1], h_off[n_rows:], width - n_special, stride, overflowing, truncation)
+        rows = int(info[0])
+    out = outputs(rows, width)
     p = {k: (v.data_ptr() if v is not None else None) for k, v in out.items()}
-    check(lib.swt_batch_pair_rows_dev(d_ids.data_ptr(), p_a, p_b, n, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged),
-                                      d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None, C.byref(spec), strategy,
-                                      d_row_base.data_ptr(), d_status.data_ptr(), rows, p["input_ids"], p["attention_mask"],
-                                      p["token_type_ids"], p["special_tokens_mask"], p["sequence_ids"], p["offset_mapping"], p["word_ids"],
-                                      p["sample"], p["length"], d_info.data_ptr(), stream))
-    out["info"] = d_info[:5].cpu().numpy()
-    return _pair_result(out, overflowing, offsets, token_types, special_mask)
+    head = (d_ids.data_ptr(), *p_off, n_rows, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged), p_spans, p_word, C.byref(spec))
+    tail = (p["offset_mapping"], p["word_ids"], p["sample"], p["length"], d_info.data_ptr(), stream)
+    if pair:
+        check(lib.swt_batch_pair_rows_dev(*head, strategy, d_row_base.data_ptr(), d_status.data_ptr(), rows, p["input_ids"], p["attention_mask"],
+                                          p["token_type_ids"], p["special_tokens_mask"], p["sequence_ids"], *tail))
+    else:
+        check(lib.swt_batch_rows_dev(*head, d_row_base.data_ptr() if overflowing else None, rows, p["input_ids"], p["attention_mask"], *tail))
+    out["info"] = d_info[:n_info].cpu().numpy()
+    return out

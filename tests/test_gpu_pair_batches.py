@@ -7,8 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import batch_cases as B
 from tests import pair_cases as P
 from tests.test_gpu_model_batches import GARBAGE, Fenced, _to_numpy, _tokenizer
+from tests.test_gpu_model_batches import run as run_single
 
 pytestmark = pytest.mark.gpu
 
@@ -263,6 +265,29 @@ def test_map_edges(dev, form):
             assert cmap is None or want["n_unknown"] > 0
             _, res, _ = run(dev, form, ids, off_a, off_b, s, strategy, cmap, want=want)
             agree(res, want)
+
+
+@pytest.mark.parametrize("width", [6, 64, 65])
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_a_pair_with_an_empty_side_is_the_single_batch_of_the_other_side(dev, form, width):
+    """The two instantiations of the one skeleton against each other: without specials, only_first with (n, 0) and only_second
+    with (0, n), windowed and truncating, and longest_first with (n, 0) truncating, write what swt_batch_plan / swt_batch_rows
+    write for the side that holds the tokens, and refuse no pair.  A two-lane group, a full group on the wide stores, and the
+    element-by-element path one past it; each run is also held to its own model, row_base included."""
+    stride = width // 3
+    lengths = B.seam_lengths(width, width - stride) + [3 * width + 1]
+    for strategy, windows in ((FIRST, True), (SECOND, True), (FIRST, False), (SECOND, False), (LONGEST, False)):
+        side = int(strategy == SECOND)
+        rows_a, rows_b, ids, off_a, off_b, pay = P.pair_stream([(0, n) if side else (n, 0) for n in lengths], seed=width)
+        s = P.spec(width, stride, windows)
+        want = P.expected_pair_batch(rows_a, rows_b, s, strategy, None, pay)
+        want_single = B.expected_batch(rows_b if side else rows_a, s, None, pay[side])
+        _, pair, _ = run(dev, form, ids, off_a, off_b, s, strategy, None, pay, want=want)
+        _, single, _ = run_single(dev, form, ids, off_b if side else off_a, s, None, pay[side], want_rows=want_single["row_base"])
+        assert np.array_equal(want["row_base"], want_single["row_base"])
+        for k in ("input_ids", "attention_mask", "length", "sample", "offset_mapping", "word_ids"):
+            assert np.array_equal(pair[k], single[k]), (k, strategy, windows)
+        assert int(pair["info"][3]) == 0 and int(pair["info"][0]) == int(single["info"][0]) == int(want["row_base"][-1])
 
 
 # ---- through the classes

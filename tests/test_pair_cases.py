@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from . import batch_cases as B
 from . import pair_cases as P
 
 
@@ -119,6 +120,33 @@ def test_model_dense_ids_and_payloads():
     assert got["word_ids"].tolist() == [[-1, 0, 0, 1, -1, 0, 1, 1, -1]]  # B's word indices start again at 0
     assert got["offset_mapping"][0, 5].tolist() == [10, 11] and got["offset_mapping"][0, 4].tolist() == [0, 0]
     assert got["n_unknown"] == 3 and got["lost"] == 1 and got["longest"] == 7
+
+
+ONE_SIDED = ((P.ONLY_FIRST, True), (P.ONLY_SECOND, True), (P.ONLY_FIRST, False), (P.ONLY_SECOND, False), (P.LONGEST_FIRST, False))
+SINGLE_KEYS = ("input_ids", "attention_mask", "length", "sample", "row_base", "offset_mapping", "word_ids")
+
+
+def test_a_pair_with_an_empty_side_is_the_single_batch_of_the_other_side():
+    """Without specials the two models meet: only_first with (n, 0) and only_second with (0, n), windowed and truncating, and
+    longest_first with (n, 0) truncating, give the single-sequence batch of the side that holds the tokens, and refuse no pair.
+    Widths of one token up to one past a full lane group, the strides 0, cap // 3 and cap - 1, both padding sides, the lengths
+    at the window seams and one of several windows."""
+    n_cases = 0
+    for width in (1, 4, 6, 9, 63, 64, 65):
+        for stride in sorted({0, width // 3, width - 1}):
+            lengths = B.seam_lengths(width, width - stride) + [3 * width + 1]
+            for left in (False, True):
+                for strategy, windows in ONE_SIDED:
+                    n_cases += 1
+                    side = int(strategy == P.ONLY_SECOND)
+                    rows_a, rows_b, _, _, _, pay = P.pair_stream([(0, n) if side else (n, 0) for n in lengths], seed=width)
+                    s = P.spec(width, stride, windows, pad_left=left)
+                    pair = P.expected_pair_batch(rows_a, rows_b, s, strategy, None, pay)
+                    single = B.expected_batch(rows_b if side else rows_a, s, None, pay[side])
+                    assert pair["refused"] == 0 and not pair["status"].any()
+                    for k in SINGLE_KEYS:
+                        assert np.array_equal(pair[k], single[k]), (k, width, stride, left, strategy, windows)
+    assert n_cases == 190
 
 
 # ---- the host forms refuse bad arguments before they look for a device
