@@ -580,6 +580,65 @@ int swt_batch_pair_rows_dev(const uint32_t *d_ids, const uint64_t *d_off_a, cons
                             uint8_t *d_out_mask, void *d_out_type, uint8_t *d_out_special, int8_t *d_out_seq, uint32_t *d_out_spans,
                             uint32_t *d_out_word, uint32_t *d_out_sample, uint32_t *d_out_len, uint64_t *d_info, void *stream);
 int swt_batch_pair_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
+
+/* ------------------------------------------------------------------------------------------------
+ * Packed batches: several short source rows share one model row, so that a batch at pre-training widths is tokens and not
+ * padding; the model gets the position of every column inside its sentence and a segment number per column to keep attention
+ * inside a sentence.  The same post-pass over (ids, tok_off) as swt_batch_rows, with the same dense ids and the same spec: width,
+ * pad_id, unk_id, cls_id, sep_id and SWT_BATCH_IDS64 are used; stride must be 0, SWT_BATCH_WINDOWS and SWT_BATCH_PAD_LEFT are
+ * refused.  The reference has nothing of the sort; tests/pack_cases.py holds these semantics.
+ *
+ * A source row r gives a SEGMENT [cls?] body [sep?] of L(r) columns.  P is the exclusive sum of L, T = P[n_rows].
+ *   SWT_PACK_WHOLE   no segment is split.  The body is the first min(n, cap) tokens, cap = width - (cls present) - (sep present),
+ *                    so L(r) <= width.  Next-fit in source order: a packed row that starts at source row r holds the source rows
+ *                    r .. next(r) - 1, next(r) the largest q <= n_rows with P[q] - P[r] <= width; the packed rows are the orbit of
+ *                    0 under next.  Segments of no column (an empty text without specials) ride along in the row that is open.
+ *                    n_rows >= 1 gives at least one packed row (T == 0: one row of padding).
+ *   SWT_PACK_SPLIT   concatenate and cut: no truncation, L(r) = n + specials; the segments are one stream of T columns and packed
+ *                    row b holds the stream positions [b width, min(T, (b + 1) width)); rows = ceil(T / width), the last one
+ *                    padded.  With SWT_PACK_DROP_LAST (or-ed into the mode; SPLIT only) a last row that is not full is
+ *                    dropped: rows = floor(T / width).
+ * The plan: slot[n_rows+1], the flat output position row * width + col of every segment's first column (SPLIT: P[r]; WHOLE:
+ * bin(r) width + P[r] - P[first row of the bin]), slot[n_rows] the end of the last segment; row_first[n_rows+1], whose first
+ * `rows` entries are the source row that owns column 0 of each packed row (WHOLE: the packed row's first source row; SPLIT:
+ * the r with P[r] <= b width < P[r+1]) and whose entries from row_first[rows] on are n_rows.  SPLIT can give more packed rows
+ * than source rows: row_first then holds the owners of the first n_rows + 1 packed rows, and the row call, which finds a SPLIT
+ * row's owner by a search in slot, does not read it.  info[4]: [0] rows out, [1] the longest source row in tokens, [2] 0, [3] T
+ * (WHOLE: after truncation).
+ *
+ * The rows, [rows, width] each: out_ids (int32, int64 with SWT_BATCH_IDS64; padding pad_id) and out_mask (uint8; 0) are
+ * required.  out_pos (uint32; may be NULL): the column's position inside its segment, stream position - P[r], 0 on the cls --
+ * in SPLIT it carries on across a cut; padding 0.  out_seg (uint32; may be NULL): r - row_first[row]; padding 0xFFFFFFFF.
+ * out_doc (uint32; may be NULL): r; padding 0xFFFFFFFF.  out_len[row] (may be NULL): the columns that are not padding.
+ * info[3] (may be NULL): [0] rows written, [1] source rows that lost tokens (WHOLE only), [2] tokens sent to unk_id, once per
+ * column written.
+ *
+ * SWT_ERR_INVALID: cap < 1, a stride, SWT_BATCH_WINDOWS, SWT_BATCH_PAD_LEFT, an unknown flag, pad_id / unk_id =
+ * SWT_BATCH_NONE, a mode that is not exactly one of WHOLE and SPLIT, SWT_PACK_DROP_LAST without SPLIT, NULL out_ids or out_mask,
+ * NULL slot or row_first, flagged without a map, 2^32 source rows or more.  The host forms check everything -- decreasing offsets
+ * and a slot / row_first that is not the plan of the offsets included -- before anything touches the device, and swt_pack_rows
+ * returns SWT_ERR_CAPACITY with info[0] = the rows needed when they exceed rows_cap.  The `_dev` forms take device pointers
+ * (offsets that do not decrease; outputs aligned to their element type, to 16 bytes for the wide stores), enqueue on the stream
+ * and do not synchronise; swt_pack_rows_dev writes every element of the rows < min(rows, rows_cap) of every output given and
+ * nothing at or beyond rows_cap * width, whatever ids, slot and row_first hold.  swt_pack_plan_dev scans in the workspace of
+ * swt_batch_plan_dev and keeps its own beside it: no two plans of any kind at once on different streams.  swt_pack_capacity:
+ * the columns one wavefront writes per step, the rows of one scan group, and the rows of one group of the orbit step of the
+ * WHOLE plan (csrc/swt_pack.hip). */
+#define SWT_PACK_WHOLE 1u
+#define SWT_PACK_SPLIT 2u
+#define SWT_PACK_DROP_LAST 4u
+int swt_pack_plan(const uint64_t *tok_off, uint64_t n_rows, const swt_batch_spec *spec, uint32_t mode, uint64_t *slot, uint64_t *row_first,
+                  uint64_t *info);
+int swt_pack_plan_dev(const uint64_t *d_tok_off, uint64_t n_rows, const swt_batch_spec *spec, uint32_t mode, uint64_t *d_slot,
+                      uint64_t *d_row_first, uint64_t *d_info, void *stream);
+int swt_pack_rows(const uint32_t *ids, const uint64_t *tok_off, uint64_t n_rows, const uint32_t *map, uint32_t n_map, int flagged,
+                  const swt_batch_spec *spec, uint32_t mode, const uint64_t *slot, const uint64_t *row_first, uint64_t rows_cap, void *out_ids,
+                  uint8_t *out_mask, uint32_t *out_pos, uint32_t *out_seg, uint32_t *out_doc, uint32_t *out_len, uint64_t *info);
+int swt_pack_rows_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, uint64_t n_rows, const uint32_t *d_map, uint32_t n_map, int flagged,
+                      const swt_batch_spec *spec, uint32_t mode, const uint64_t *d_slot, const uint64_t *d_row_first, uint64_t rows_cap,
+                      void *d_out_ids, uint8_t *d_out_mask, uint32_t *d_out_pos, uint32_t *d_out_seg, uint32_t *d_out_doc,
+                      uint32_t *d_out_len, uint64_t *d_info, void *stream);
+int swt_pack_capacity(uint32_t *cols_per_step, uint32_t *scan_group, uint32_t *orbit_group);
 #ifdef __cplusplus
 }
 #endif

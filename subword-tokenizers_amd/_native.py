@@ -28,6 +28,7 @@ BATCH_NONE = 0xFFFFFFFF  # swt_batch_spec: an absent cls_id / sep_id; a map entr
 BATCH_WINDOWS, BATCH_PAD_LEFT, BATCH_IDS64 = 1, 2, 4
 PAIR_LONGEST_FIRST, PAIR_ONLY_FIRST, PAIR_ONLY_SECOND = 0, 1, 2  # the truncation strategies of swt_batch_pair_*
 PAIR_OK, PAIR_REFUSED = 0, 1
+PACK_WHOLE, PACK_SPLIT, PACK_DROP_LAST = 1, 2, 4  # the mode of swt_pack_*: one of the first two, DROP_LAST or-ed to SPLIT
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -141,6 +142,13 @@ SIGNATURES = {
     "swt_batch_pair_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
                                           bsp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 11),
     "swt_batch_pair_capacity": (C.c_int, [u32p, u32p]),
+    "swt_pack_plan": (C.c_int, [u64p, C.c_uint64, bsp, C.c_uint32, u64p, u64p, u64p]),
+    "swt_pack_plan_dev": (C.c_int, [C.c_void_p, C.c_uint64, bsp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_pack_rows": (C.c_int, [u32p, u64p, C.c_uint64, u32p, C.c_uint32, C.c_int, bsp, C.c_uint32, u64p, u64p, C.c_uint64, C.c_void_p, u8p,
+                                u32p, u32p, u32p, u32p, u64p]),
+    "swt_pack_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, bsp, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
+    "swt_pack_capacity": (C.c_int, [u32p, u32p, u32p]),
 }
 
 
@@ -651,6 +659,72 @@ def batch_pair_rows(ids, off_a, off_b, spec, strategy, cmap=None, n_map=None, fl
                                     ptr(out["offset_mapping"], u32p) if spans is not None else None,
                                     C.cast(_vp(out["word_ids"]), u32p) if word is not None else None,
                                     ptr(out["sample"], u32p), ptr(out["length"], u32p), ptr(out["info"], u64p)))
+    return out
+
+
+def pack_capacity():
+    """-> (cols_per_step, scan_group, orbit_group): the columns one wavefront of the packing kernel writes per step, the rows
+    of one scan group of its plan and the rows of one group of the WHOLE plan's orbit step (csrc/swt_pack.hip)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_pack_capacity(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def pack_plan(tok_off, spec, mode):
+    """token offsets uint64[n_rows + 1], a BatchSpec and a PACK_* mode -> (slot uint64[n_rows + 1]: the flat output position of
+    every source row's segment, closed by the end of the last one; row_first uint64[n_rows + 1]: the source row that owns column 0
+    of each packed row, n_rows from the last packed row on; info uint64[4]: packed rows, the longest source row in tokens, 0,
+    the columns of all segments), from the device (swt_pack_plan)."""
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    if tok_off.size < 1:
+        raise ValueError("offsets hold n_rows + 1 entries")
+    slot, row_first = np.zeros(tok_off.size, dtype=np.uint64), np.zeros(tok_off.size, dtype=np.uint64)
+    info = np.zeros(4, dtype=np.uint64)
+    check(lib().swt_pack_plan(ptr(tok_off, u64p), int(tok_off.size) - 1, C.byref(spec), int(mode), ptr(slot, u64p), ptr(row_first, u64p),
+                              ptr(info, u64p)))
+    return slot, row_first, info
+
+
+def pack_rows(ids, tok_off, spec, mode, slot, row_first, cmap=None, n_map=None, flagged=False, rows_cap=None):
+    """An id stream as packed rows, on the device (swt_pack_rows).  ids, tok_off, cmap, n_map, flagged as batch_rows takes them;
+    slot and row_first: pack_plan's.  rows_cap: the rows of the outputs; None = what the plan needs.
+    -> dict: input_ids int32 or int64 [rows, width], attention_mask uint8, position_ids uint32, sequence_ids and sample_ids int32
+    (-1 on padding), length uint32[rows], info uint64[3] (rows, source rows that lost tokens, tokens sent to unk_id)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    slot, row_first = np.ascontiguousarray(slot, dtype=np.uint64), np.ascontiguousarray(row_first, dtype=np.uint64)
+    n_rows = int(tok_off.size) - 1
+    if n_rows < 0 or (n_rows and int(tok_off[-1]) > ids.size):
+        raise ValueError("offsets run past their array")
+    if slot.size != n_rows + 1 or row_first.size != n_rows + 1:
+        raise ValueError("slot and row_first hold n_rows + 1 entries")
+    cmap, n_map = _batch_rows_setup(n_rows, 0, spec, cmap, n_map, flagged, None, None, None, 0, 3)[:2]
+    width = int(spec.width)
+    if rows_cap is None:
+        rows_cap = 0
+        if n_rows:
+            end = int(slot[-1])
+            rows_cap = end // width if mode & PACK_DROP_LAST else -(-end // width)
+            if mode & PACK_WHOLE:
+                rows_cap = max(rows_cap, 1)
+    rows_cap = int(rows_cap)
+    out = {
+        "input_ids": np.zeros((rows_cap, width), dtype=np.int64 if spec.flags & BATCH_IDS64 else np.int32),
+        "attention_mask": np.zeros((rows_cap, width), dtype=np.uint8),
+        "position_ids": np.zeros((rows_cap, width), dtype=np.uint32),
+        "sequence_ids": np.zeros((rows_cap, width), dtype=np.int32),
+        "sample_ids": np.zeros((rows_cap, width), dtype=np.int32),
+        "length": np.zeros(rows_cap, dtype=np.uint32),
+        "info": np.zeros(3, dtype=np.uint64),
+    }
+    if rows_cap == 0 and n_rows == 0:
+        return out
+    one = np.zeros(4, dtype=np.uint64)  # an output of no row still needs an address
+    at = lambda a, typ: C.cast(_vp(a) if a.size else _vp(one), typ)
+    check(lib().swt_pack_rows(_cast(ids, u32p), ptr(tok_off, u64p), n_rows, _cast(cmap, u32p), n_map, int(bool(flagged)), C.byref(spec),
+                              int(mode), ptr(slot, u64p), ptr(row_first, u64p), rows_cap, at(out["input_ids"], C.c_void_p),
+                              at(out["attention_mask"], u8p), at(out["position_ids"], u32p), at(out["sequence_ids"], u32p),
+                              at(out["sample_ids"], u32p), at(out["length"], u32p), ptr(out["info"], u64p)))
     return out
 
 

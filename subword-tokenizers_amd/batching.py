@@ -170,10 +170,15 @@ def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, mult
 
 def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_to_multiple_of=None, add_special_tokens=True,
                  padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False, text_pairs=None,
-                 truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False):
+                 truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False, packing=None, drop_last=False):
     _check(texts, max_length, stride, return_overflowing)
     _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask)
     voc = tok._batch_vocabulary()
+    if packing is not None or drop_last:
+        mode = _pack_mode(packing, drop_last, max_length, stride, padding_side, return_overflowing, return_offsets, text_pairs)
+        width = _width(0, 0, max_length, "max_length", pad_to_multiple_of)
+        spec = _spec(tok, voc, width, 0, False, add_special_tokens, "right", int64)
+        return (_pack_device if device else _pack_host)(tok, voc, texts, spec, mode)
     geometry = (max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing, return_offsets, int64)
     if text_pairs is not None:
         token_types, special_mask = return_token_type_ids is None or bool(return_token_type_ids), bool(return_special_tokens_mask)
@@ -191,6 +196,94 @@ def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_t
     row_base = N.batch_plan(tok_off, spec)[0] if return_overflowing else None
     out = N.batch_rows(ids, tok_off, spec, voc.cmap, voc.n_map, voc.flagged, spans, word, row_base)
     return _result(out, return_overflowing, return_offsets, int(out["info"][2]))
+
+
+PACKINGS = {"whole": N.PACK_WHOLE, "split": N.PACK_SPLIT}
+
+
+def _pack_mode(packing, drop_last, max_length, stride, padding_side, overflowing, offsets, text_pairs):
+    """the PACK_* mode of a call, or the ValueError for what does not go with packing"""
+    if drop_last and packing != "split":
+        raise ValueError("drop_last needs packing='split'")
+    if packing not in PACKINGS:
+        raise ValueError("packing is None, 'whole' or 'split'")
+    if max_length is None:
+        raise ValueError("packing needs a max_length: the width of a packed row")
+    if padding_side != "right":
+        raise ValueError("padding_side is 'right' or 'left'" if padding_side != "left" else "packed rows are padded on the right")
+    for given, name in ((text_pairs is not None, "text_pairs"), (overflowing, "return_overflowing"), (stride, "stride"),
+                        (offsets, "return_offsets")):
+        if given:
+            raise ValueError("%s does not go with packing" % name)
+    return PACKINGS[packing] | (N.PACK_DROP_LAST if drop_last else 0)
+
+
+def _pack_result(out, slot, tok_off, spec, mode, info, plan_info, xp):
+    """the arrays of a pack call and its plan as encode_batch returns them.  xp: numpy or torch, whichever holds the arrays"""
+    n_rows, width = int(slot.shape[0]) - 1, int(spec.width)
+    rows = int(out["input_ids"].shape[0])
+    n_special = (spec.cls_id != N.BATCH_NONE) + (spec.sep_id != N.BATCH_NONE)
+    tokens = tok_off[1:] - tok_off[:-1]
+    if mode & N.PACK_WHOLE:
+        tokens = xp.clip(tokens, 0, width - n_special) if xp is np else tokens.clamp(max=width - n_special)
+    return {"input_ids": out["input_ids"], "attention_mask": out["attention_mask"], "position_ids": out["position_ids"],
+            "sequence_ids": out["sequence_ids"], "sample_ids": out["sample_ids"], "length": out["length"],
+            "n_unknown": int(info[2]), "n_truncated": int(info[1]),
+            "segment_row": slot[:n_rows] // width, "segment_col": slot[:n_rows] % width, "segment_length": tokens + n_special,
+            "density": float(min(int(plan_info[3]), rows * width)) / (rows * width) if rows else 0.0}
+
+
+def _pack_host(tok, voc, texts, spec, mode):
+    ids, tok_off = tok.encode_ids_batch(texts)[:2]
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    slot, row_first, plan_info = N.pack_plan(tok_off, spec, mode)
+    out = N.pack_rows(ids, tok_off, spec, mode, slot, row_first, voc.cmap, voc.n_map, voc.flagged, rows_cap=int(plan_info[0]))
+    return _pack_result(out, slot.astype(np.int64), tok_off.astype(np.int64), spec, mode, out["info"], plan_info, np)
+
+
+def _pack_device(tok, voc, texts, spec, mode):
+    """as _encode_device: one upload of the texts, one `_dev` encode, the packing plan and rows on torch-owned buffers on the
+    current stream; the plan's info (for the rows to allocate) and the rows' info are all that comes back"""
+    import torch
+    n_rows, width = len(texts), int(spec.width)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    lib, check = N.lib(), N.check
+    idt = torch.int64 if spec.flags & N.BATCH_IDS64 else torch.int32
+
+    def empty(shape, dtype, wanted=True):
+        return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
+
+    text, off = N.pack_utf8([t.lower() for t in texts])
+    n_bytes = int(text.size)
+    d_tok_off = empty(n_rows + 1, torch.int64)
+    d_ids = empty(n_bytes + 64, torch.int32)
+    if n_bytes == 0:
+        d_tok_off.zero_()
+    else:
+        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+        d_ntok = torch.zeros(1, dtype=torch.int64, device=dev)
+        tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_rows, d_ids.data_ptr(), d_tok_off.data_ptr(), d_ntok.data_ptr(),
+                              None, None, stream, empty)
+    if voc.d_cmap is None or voc.d_cmap.device != dev:
+        voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
+    d_slot, d_first, d_info = empty(n_rows + 1, torch.int64), empty(n_rows + 1, torch.int64), empty(8, torch.int64)
+    check(lib.swt_pack_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(spec), mode, d_slot.data_ptr(), d_first.data_ptr(), d_info.data_ptr(),
+                                stream))
+    plan_info = d_info[:4].cpu().numpy()
+    rows = int(plan_info[0])
+    out = {"input_ids": empty((rows, width), idt), "attention_mask": empty((rows, width), torch.uint8),
+           "position_ids": empty((rows, width), torch.int32), "sequence_ids": empty((rows, width), torch.int32),
+           "sample_ids": empty((rows, width), torch.int32), "length": empty(rows, torch.int32)}
+    info = np.zeros(3, dtype=np.int64)
+    if rows:
+        check(lib.swt_pack_rows_dev(d_ids.data_ptr(), d_tok_off.data_ptr(), n_rows, voc.d_cmap.data_ptr(), voc.n_map, int(voc.flagged),
+                                    C.byref(spec), mode, d_slot.data_ptr(), d_first.data_ptr(), rows, out["input_ids"].data_ptr(),
+                                    out["attention_mask"].data_ptr(), out["position_ids"].data_ptr(), out["sequence_ids"].data_ptr(),
+                                    out["sample_ids"].data_ptr(), out["length"].data_ptr(), d_info.data_ptr(), stream))
+        info = d_info[:3].cpu().numpy()
+    return _pack_result(out, d_slot, d_tok_off, spec, mode, info, plan_info, torch)
 
 
 def _result(out, overflowing, offsets, n_unknown):

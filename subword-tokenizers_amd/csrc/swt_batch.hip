@@ -19,32 +19,18 @@
 //        where the width is no multiple of four or an output is not aligned.  The counters of info are folded over the
 //        wavefront, then the workgroup (64 bytes of LDS, 128 for pairs), and added once per workgroup.  No scratch; no other
 //        atomics.
-#include <deque>
-#include <initializer_list>
-#include <vector>
-
-#include "swt_tile.h"
+#include "swt_batch.h"
 
 namespace swt {
 
 constexpr int kBtThreads = 256;
 constexpr int kBtWaves = kBtThreads / 64;
-constexpr uint32_t kBtQuad = 4;                // columns of one lane per step
-constexpr uint32_t kBtCols = 64 * kBtQuad;     // columns of one wavefront per step
 constexpr uint32_t kBtIter = 4;                // sets of rows one wavefront walks
-constexpr uint32_t kBtScanGroup = 1024;        // rows of one scan group (launch_scan_u64)
 constexpr uint32_t kBtFlags = SWT_BATCH_WINDOWS | SWT_BATCH_PAD_LEFT | SWT_BATCH_IDS64;
 
 // Output rows of a source row of n tokens in windows of cap tokens that advance by step.
 __host__ __device__ inline uint64_t bt_windows(uint64_t n, uint32_t cap, uint32_t step) {
   return n <= cap ? 1 : 1 + (n - cap + step - 1) / step;
-}
-
-// The tokens of row r of an offset array, and where they start.
-__device__ inline uint64_t bt_tokens(const uint64_t *__restrict__ off, uint64_t r, uint64_t &first) {
-  first = off[r];
-  const uint64_t end = off[r + 1];
-  return end > first ? end - first : 0;
 }
 
 __device__ inline unsigned long long bt_add_sat(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
@@ -159,22 +145,6 @@ struct PairLayout {  // [cls] A [sep] B [sep], all three specials or none; only 
   __device__ uint32_t in_b(uint32_t p) const { return p >= pb; }  // the type of a position: B from its first token on
   __device__ uint64_t token(uint32_t p) const { return in_b(p) ? b0 + fb + (p - pb) : a0 + fa + (p - pa); }
 };
-
-// four elements of an id-typed output: one 16-byte store, two with 64-bit ids
-__device__ inline void bt_store_quad(void *out, uint64_t slot, bool ids64, const uint32_t (&v)[kBtQuad]) {
-  if (ids64) {
-    uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<uint64_t *>(out) + slot);
-    o[0] = make_uint4(v[0], 0, v[1], 0);
-    o[1] = make_uint4(v[2], 0, v[3], 0);
-  } else {
-    *reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(out) + slot) = make_uint4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-__device__ inline void bt_store_one(void *out, uint64_t slot, bool ids64, uint32_t v) {
-  if (ids64) reinterpret_cast<uint64_t *>(out)[slot] = v;
-  else reinterpret_cast<uint32_t *>(out)[slot] = v;
-}
 
 __device__ inline void bt_store_spans(uint32_t *out, uint64_t slot, const uint32_t (&a)[kBtQuad], const uint32_t (&b)[kBtQuad]) {
   uint4 *o = reinterpret_cast<uint4 *>(out + 2 * slot);
@@ -363,12 +333,20 @@ __global__ __launch_bounds__(kBtThreads) void batch_base_kernel(const unsigned l
   else if (i == n_rows) row_base[n_rows] = info[0];
 }
 
-// grow-only, shared by all calls of the process (the calls carry no handle); a plan uses it on its own stream, so plans on
-// different streams must not overlap -- the header says so
-struct BatchWorkspace {
-  DevBuf local, blk;
-};
-static BatchWorkspace g_batch_ws;
+BatchWorkspace g_batch_ws;
+
+int BatchWorkspace::reserve(uint64_t n_rows) {
+  int rc;
+  const uint64_t nb = (n_rows + kBtScanGroup - 1) / kBtScanGroup;
+  if ((rc = local.reserve((size_t)n_rows * 8 + 16))) return rc;
+  const void *before = blk.p;
+  if ((rc = blk.reserve((size_t)(2 * nb + 4) * 8))) return rc;
+  if (blk.p != before) {  // a new buffer: zero the scan's ticket once (the scan resets it itself afterwards)
+    SWT_HIP(hipMemset(blk.p, 0, 8));
+    SWT_HIP(hipDeviceSynchronize());
+  }
+  return SWT_OK;
+}
 
 // The spec of a call.  strategy: null for single rows (cls and sep each count), else the pair's: cls and sep together or not at
 // all, three specials with them.  The width is looked at with need_width only; *cap_out = the tokens of a row, 0 without.
@@ -406,13 +384,6 @@ static int batch_check_rows(const uint32_t *map, int flagged, const uint32_t *sp
   return SWT_OK;
 }
 
-// every pointer of the list is a multiple of a (a null pointer is)
-static bool bt_aligned(uintptr_t a, std::initializer_list<const void *> ps) {
-  for (const void *p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & (a - 1)) return false;
-  return true;
-}
-
 // The plan of both kinds on device pointers, the spec checked: info cleared (16 bytes; 40 for pairs), count, scan, bases.
 template <bool kPair>
 static int batch_plan_launch(const uint64_t *d_off_a, const uint64_t *d_off_b, uint64_t n_rows, const swt_batch_spec *spec, uint32_t cap,
@@ -424,15 +395,7 @@ static int batch_plan_launch(const uint64_t *d_off_a, const uint64_t *d_off_b, u
   unsigned long long *rb = reinterpret_cast<unsigned long long *>(d_row_base), *info = reinterpret_cast<unsigned long long *>(d_info);
   BatchWorkspace &ws = g_batch_ws;
   const uint64_t nb = (n_rows + kBtScanGroup - 1) / kBtScanGroup;
-  if (windows && n_rows) {
-    if ((rc = ws.local.reserve((size_t)n_rows * 8 + 16))) return rc;
-    const void *before = ws.blk.p;
-    if ((rc = ws.blk.reserve((size_t)(2 * nb + 4) * 8))) return rc;
-    if (ws.blk.p != before) {  // a new buffer: zero the scan's ticket once (the scan resets it itself afterwards)
-      SWT_HIP(hipMemset(ws.blk.p, 0, 8));
-      SWT_HIP(hipDeviceSynchronize());
-    }
-  }
+  if (windows && n_rows && (rc = ws.reserve(n_rows))) return rc;
   SWT_HIP(hipMemsetAsync(d_info, 0, kPair ? 40 : 16, st));
   if (!n_rows) {
     SWT_HIP(hipMemsetAsync(d_row_base, 0, 8, st));
@@ -474,44 +437,6 @@ static int batch_rows_launch(RowsArgs A, void *stream) {
   SWT_HIP(hipGetLastError());
   return SWT_OK;
 }
-
-// The device side of a host form.  in(): a host array goes up and its device copy comes back -- none for a null pointer, unless
-// the call takes the array even when it is empty (always); out(): room for an output that was given; fetch(): after the call,
-// the stream drained, every output back where it belongs.  A failure stays in rc and hands out null pointers from then on;
-// whatever ends the call, the buffers are released.
-struct BatchStage {
-  struct Out { void *host; const void *dev; size_t bytes; };
-  std::deque<DevBuf> bufs;
-  std::vector<Out> outs;
-  int rc = SWT_OK;
-  ~BatchStage() { for (DevBuf &b : bufs) b.release(); }
-  void *room(size_t bytes) {
-    if (rc) return nullptr;
-    bufs.emplace_back();
-    rc = bufs.back().reserve(bytes + 16);
-    return rc ? nullptr : bufs.back().p;
-  }
-  int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-    if (bytes) SWT_HIP(hipMemcpy(dst, src, bytes, kind));
-    return SWT_OK;
-  }
-  template <class T> T *in(const T *host, size_t bytes, bool always = false) {
-    void *d = host || always ? room(bytes) : nullptr;
-    if (d && host) rc = copy(d, host, bytes, hipMemcpyHostToDevice);
-    return rc ? nullptr : static_cast<T *>(d);
-  }
-  template <class T> T *out(T *host, size_t bytes) {
-    void *d = host ? room(bytes) : nullptr;
-    if (d) outs.push_back({host, d, bytes});
-    return static_cast<T *>(d);
-  }
-  int fetch() {
-    SWT_HIP(hipStreamSynchronize(nullptr));
-    for (const Out &o : outs)
-      if ((rc = copy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost))) return rc;
-    return SWT_OK;
-  }
-};
 
 }  // namespace swt
 

@@ -96,7 +96,8 @@ class SubwordTokenizer:
                      pad_to_multiple_of: Optional[int] = None, add_special_tokens: bool = True, padding_side: str = "right",
                      return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False,
                      text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
-                     return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False) -> dict:
+                     return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False,
+                     packing: Optional[str] = None, drop_last: bool = False) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
@@ -111,10 +112,18 @@ class SubwordTokenizer:
         side's own.  truncation: "longest_first" takes from the longer side, "only_first" / "only_second" cut the named side
         and spare the other; with return_overflowing the cut side is windowed and the other repeated in every row
         ("longest_first" has no windows).  A pair whose spared side leaves the other no room raises ValueError.  Without
-        text_pairs these keywords have nothing to act on and any value but the default raises ValueError."""
+        text_pairs these keywords have nothing to act on and any value but the default raises ValueError.
+
+        packing="whole" or "split" (swt_pack_rows; needs max_length, the width) puts several texts into one row: "whole" next-fit
+        in the order given, no text split and a text longer than the width truncated; "split" all texts end to end, cut every
+        width columns, with drop_last without a last row that is not full.  The result holds "input_ids", "attention_mask",
+        "position_ids" (the column's position inside its text's segment), "sequence_ids" (the segment's number in its row, -1 on
+        padding), "sample_ids" (the text's index, -1 on padding), "length", "n_unknown", "n_truncated", per text "segment_row",
+        "segment_col" and "segment_length", and "density", the share of columns that are not padding.  Pairs, windows, offsets
+        and left padding do not go with packing: ValueError."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                                     return_special_tokens_mask)
+                                     return_special_tokens_mask, packing, drop_last)
 
     def _batch_encode_spans(self, texts):
         return self.encode_spans_batch(texts)
