@@ -639,6 +639,52 @@ int swt_pack_rows_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, uint64_t
                       void *d_out_ids, uint8_t *d_out_mask, uint32_t *d_out_pos, uint32_t *d_out_seg, uint32_t *d_out_doc,
                       uint32_t *d_out_len, uint64_t *d_info, void *stream);
 int swt_pack_capacity(uint32_t *cols_per_step, uint32_t *scan_group, uint32_t *orbit_group);
+
+/* ------------------------------------------------------------------------------------------------
+ * Masked-LM batches: over finished rows ids[rows, width] of dense ids (int32, int64 with SWT_MLM_IDS64; C-contiguous; any
+ * input_ids of the batch calls above), the columns the masked-LM objective selects, what stands in their place, and the labels.
+ * The reference has nothing of the sort; tests/mlm_cases.py holds these semantics, and the kernel equals it bit for bit.
+ *
+ * The class of a column comes from cls_tab[n_class] (uint8) at its id: 0 starts a word, 1 continues one ('##' and more), 2 is
+ * never masked ([PAD], [UNK], [CLS], [SEP], [MASK]); an id that is negative or >= n_class is class 2, as is any other value of the
+ * table.  Nothing but the id decides: there is no attention mask, padding is [PAD].  A column of class 0 or 1 is ELIGIBLE.  It is
+ * a HEAD when its class is 0, or when its class is 1 and the column to its left in the row is class 2 or does not exist (a word
+ * cut by truncation, a window or a split row); head(c) = the largest head column <= c.  Without SWT_MLM_WHOLE_WORD every
+ * eligible column is its own head.
+ *
+ * A draw is Philox4x32-10 (Random123: multipliers D2511F53 CD9E8D57, Weyl constants 9E3779B9 BB67AE85) of the counter (column,
+ * row, epoch, 0) under the key (seed's low word, seed's high word); x0 .. x3 its four output words.  The thresholds
+ * select_below, mask_below <= random_below are integers in [0, 2^32]: there is no floating point on the device.
+ *   an eligible column c is SELECTED iff x0 of the draw at (head(c), row) < select_below: a word is selected whole;
+ *   a selected column, by x1 and x2 of its OWN draw: x1 < mask_below -> mask_id; else x1 < random_below ->
+ *   rand_ids[(x2 * n_rand) >> 32]; else its id stays.
+ * out_ids: the id of every column not replaced, else the replacement.  out_labels: the id before replacement on selected columns,
+ * -100 elsewhere.  out_selected (uint8; may be NULL): 1 on selected columns.  info[5] (may be NULL): eligible columns, selected,
+ * replaced by mask_id, replaced by a random id, selected and kept.  The result is a function of (seed, epoch, row, column) and the
+ * row's content alone -- not of the launch, of the other rows of the call or of the integer width; a new epoch masks the same
+ * rows anew.  rand_ids may be NULL when mask_below == random_below: nothing is replaced by a random id.
+ *
+ * SWT_ERR_INVALID, swt_last_error naming the argument: NULL ids, out_ids, out_labels, cls_tab or spec; width == 0 with rows > 0;
+ * 2^32 rows or more; 2^31 columns or more; an unknown flag; a threshold above 2^32 or mask_below > random_below; n_class == 0;
+ * rand_ids NULL or n_rand == 0 where a random replacement can be drawn; an output that overlaps ids (a lane reads its
+ * neighbours' classes: not in place).  rows == 0 succeeds and zeroes info.  The spec is a host pointer in both forms.  The host
+ * form checks everything before anything touches the device.  The `_dev` form takes device pointers (aligned to their element
+ * type, to 16 bytes for the wide loads and stores), enqueues on the stream and does not synchronise; it writes every element of
+ * every output given and nothing outside rows * width, whatever ids holds, and fills d_info[0..4] (zeroes for no row).  With
+ * d_info it keeps the workgroups' counts between its two launches in a workspace of the process: no two such calls at once on
+ * different streams.
+ * swt_mlm_capacity: the columns of a row one step covers, and the most rows that share a wavefront (csrc/swt_mlm.hip). */
+#define SWT_MLM_WHOLE_WORD 1u
+#define SWT_MLM_IDS64 4u /* the value of SWT_BATCH_IDS64 */
+typedef struct swt_mlm_spec {
+  uint64_t seed, select_below, mask_below, random_below;
+  uint32_t epoch, flags, mask_id, n_class;
+} swt_mlm_spec;
+int swt_mlm_mask(const void *ids, uint64_t rows, uint32_t width, const uint8_t *cls_tab, const uint32_t *rand_ids, uint32_t n_rand,
+                 const swt_mlm_spec *spec, void *out_ids, void *out_labels, uint8_t *out_selected, uint64_t *info);
+int swt_mlm_mask_dev(const void *d_ids, uint64_t rows, uint32_t width, const uint8_t *d_cls_tab, const uint32_t *d_rand_ids, uint32_t n_rand,
+                     const swt_mlm_spec *spec, void *d_out_ids, void *d_out_labels, uint8_t *d_out_selected, uint64_t *d_info, void *stream);
+int swt_mlm_capacity(uint32_t *cols_per_step, uint32_t *rows_per_wave_max);
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,17 @@ class BatchSpec(C.Structure):
 
 
 bsp = C.POINTER(BatchSpec)
+MLM_WHOLE_WORD, MLM_IDS64 = 1, 4  # the flags of swt_mlm_spec
+MLM_IGNORE = -100  # the label of a column that is not selected
+
+
+class MlmSpec(C.Structure):
+    """swt_mlm_spec (include/swt.h): the draws and thresholds of a masked-LM call"""
+    _fields_ = [(name, C.c_uint64) for name in ("seed", "select_below", "mask_below", "random_below")] + \
+               [(name, C.c_uint32) for name in ("epoch", "flags", "mask_id", "n_class")]
+
+
+msp = C.POINTER(MlmSpec)
 
 # every symbol include/swt.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -149,6 +160,9 @@ SIGNATURES = {
     "swt_pack_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, bsp, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_uint64] + [C.c_void_p] * 8),
     "swt_pack_capacity": (C.c_int, [u32p, u32p, u32p]),
+    "swt_mlm_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, msp, C.c_void_p, C.c_void_p, u8p, u64p]),
+    "swt_mlm_mask_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, msp] + [C.c_void_p] * 5),
+    "swt_mlm_capacity": (C.c_int, [u32p, u32p]),
 }
 
 
@@ -725,6 +739,43 @@ def pack_rows(ids, tok_off, spec, mode, slot, row_first, cmap=None, n_map=None, 
                               int(mode), ptr(slot, u64p), ptr(row_first, u64p), rows_cap, at(out["input_ids"], C.c_void_p),
                               at(out["attention_mask"], u8p), at(out["position_ids"], u32p), at(out["sequence_ids"], u32p),
                               at(out["sample_ids"], u32p), at(out["length"], u32p), ptr(out["info"], u64p)))
+    return out
+
+
+def mlm_capacity():
+    """-> (cols_per_step, rows_per_wave_max): the columns of a row one step of the masking kernel covers, and the most rows
+    that share one of its wavefronts (csrc/swt_mlm.hip)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_mlm_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def mlm_spec(n_class, mask_id, select_below, mask_below, random_below, seed=0, epoch=0, whole_word=True, ids64=False):
+    """an MlmSpec; the thresholds are integers in [0, 2^32]"""
+    return MlmSpec(int(seed), int(select_below), int(mask_below), int(random_below), int(epoch),
+                   (MLM_WHOLE_WORD if whole_word else 0) | (MLM_IDS64 if ids64 else 0), int(mask_id), int(n_class))
+
+
+def mlm_mask(ids, cls_tab, rand_ids, spec, selected=True, info=True):
+    """Rows of dense ids (a 2-D C-contiguous int32 or int64 array; the spec's MLM_IDS64 says which) masked for the masked-LM
+    objective on the device (swt_mlm_mask).  cls_tab uint8[spec.n_class]; rand_ids uint32 or None.
+    -> dict: input_ids and labels as ids, selected uint8 (or None), info uint64[5] (or None): eligible, selected, masked, random, kept."""
+    want = np.int64 if spec.flags & MLM_IDS64 else np.int32
+    if not isinstance(ids, np.ndarray) or ids.dtype != want or ids.ndim != 2 or not ids.flags.c_contiguous:
+        raise TypeError("ids: a 2-D C-contiguous array of %s" % np.dtype(want).name)
+    cls_tab = np.ascontiguousarray(cls_tab, dtype=np.uint8)
+    if cls_tab.size < spec.n_class:
+        raise ValueError("cls_tab holds n_class entries")
+    if rand_ids is not None:
+        rand_ids = np.ascontiguousarray(rand_ids, dtype=np.uint32)
+    rows, width = ids.shape
+    out = {"input_ids": np.zeros_like(ids), "labels": np.zeros_like(ids),
+           "selected": np.zeros(ids.shape, dtype=np.uint8) if selected else None, "info": np.zeros(5, dtype=np.uint64) if info else None}
+    one = np.zeros(4, dtype=np.uint64)  # an array of no element still needs an address
+    at = lambda a, typ: None if a is None else C.cast(_vp(a) if a.size else _vp(one), typ)
+    check(lib().swt_mlm_mask(at(ids, C.c_void_p), rows, width, at(cls_tab, u8p), at(rand_ids, u32p), 0 if rand_ids is None else int(rand_ids.size),
+                             C.byref(spec), at(out["input_ids"], C.c_void_p), at(out["labels"], C.c_void_p), at(out["selected"], u8p),
+                             at(out["info"], u64p)))
     return out
 
 

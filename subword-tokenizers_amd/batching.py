@@ -3,7 +3,8 @@
 A tokenizer class gives its `Vocabulary` (`_batch_vocabulary`: specials and token strings in dense-id order, and the map from the
 encoder's ids to dense ids) and its encode calls (`encode_ids_batch`, `_batch_encode_spans`, `_batch_encode_dev`); `encode_batch`
 pads, truncates or windows the rows on the device -- through the host forms of the C ABI into NumPy arrays, or with
-`device=True` on torch tensors without the ids ever leaving the device."""
+`device=True` on torch tensors without the ids ever leaving the device.  `mask_tokens` masks such rows for the masked-LM
+objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ import numpy as np
 from . import _native as N
 
 SPECIALS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]")
+MASK = "[MASK]"
 # Code points every BPE vocabulary holds besides those of its merges: merges.json is all a BPE model saves (bpe.py:167-177), and a
 # code point that never merged -- every punctuation mark: the pre-tokenizer isolates them -- is in no merge.  Basic Latin, Latin-1
 # Supplement and Latin Extended-A without controls and spaces.
@@ -25,6 +27,25 @@ class Vocabulary:
         self.tokens, self.index, self.cmap, self.n_map, self.flagged = tokens, index, cmap, n_map, flagged
         self.special = {name: index[s] for name, s in zip(("pad", "unk", "cls", "sep"), SPECIALS)}
         self.d_cmap = None  # the map as a torch tensor, made by the first device call
+        self.mask_id = index.get(MASK, len(tokens))  # one past the end where the vocabulary has no "[MASK]": no dense id moves
+        self._cls_tab = self._rand_ids = None
+        self.d_mlm = None  # (device, cls_tab, rand_ids) as torch tensors, made by the first device call of mask_tokens
+
+    @property
+    def cls_tab(self):
+        """uint8 per dense id: 0 starts a word, 1 continues one ('##' and more), 2 is never masked (the specials and [MASK])"""
+        if self._cls_tab is None:
+            never = set(SPECIALS) | {MASK}
+            self._cls_tab = np.fromiter((2 if t in never else 1 if len(t) > 2 and t.startswith("##") else 0 for t in self.tokens),
+                                        dtype=np.uint8, count=len(self.tokens))
+        return self._cls_tab
+
+    @property
+    def rand_ids(self):
+        """uint32, ascending: every dense id a random replacement may be (class 0 or 1)"""
+        if self._rand_ids is None:
+            self._rand_ids = np.flatnonzero(self.cls_tab < 2).astype(np.uint32)
+        return self._rand_ids
 
 
 def bpe_vocabulary(merges, syms):
@@ -170,7 +191,24 @@ def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, mult
 
 def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_to_multiple_of=None, add_special_tokens=True,
                  padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False, text_pairs=None,
-                 truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False, packing=None, drop_last=False):
+                 truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False, packing=None, drop_last=False,
+                 mlm=None):
+    if mlm is None:
+        return _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
+                             return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
+                             return_special_tokens_mask, packing, drop_last)
+    if not isinstance(mlm, dict):
+        raise TypeError("mlm is None or a dict of mask_tokens keywords")
+    _mlm_thresholds(**{k: v for k, v in mlm.items() if k != "return_selected"})  # refused before anything is encoded
+    res = _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing,
+                        return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing,
+                        drop_last)
+    res.update(mask_tokens(tok, res["input_ids"], **mlm))
+    return res
+
+
+def _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing,
+                  return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing, drop_last):
     _check(texts, max_length, stride, return_overflowing)
     _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask)
     voc = tok._batch_vocabulary()
@@ -381,3 +419,63 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
         check(lib.swt_batch_rows_dev(*head, d_row_base.data_ptr() if overflowing else None, rows, p["input_ids"], p["attention_mask"], *tail))
     out["info"] = d_info[:n_info].cpu().numpy()
     return out
+
+
+MLM_COUNTS = ("n_eligible", "n_selected", "n_masked", "n_random", "n_kept")
+
+
+def _mlm_thresholds(probability=0.15, whole_word=True, seed=0, epoch=0, mask_share=0.8, random_share=0.1):
+    """-> (select_below, mask_below, random_below): the integer thresholds of swt_mlm_spec, or the ValueError for arguments that
+    give none.  The device compares 32-bit draws with them and knows no floating point."""
+    for name, x in (("probability", probability), ("mask_share", mask_share), ("random_share", random_share)):
+        if not 0.0 <= float(x) <= 1.0:
+            raise ValueError("%s lies in [0, 1]" % name)
+    if float(mask_share) + float(random_share) > 1.0 + 1e-12:  # the floors of the two thresholds still add up to 2^32 at most
+        raise ValueError("mask_share + random_share must not exceed 1")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed lies in [0, 2^64)")
+    if not 0 <= int(epoch) < 1 << 32:
+        raise ValueError("epoch lies in [0, 2^32)")
+    mask_below = int(float(mask_share) * 4294967296.0)
+    return int(float(probability) * 4294967296.0), mask_below, mask_below + int(float(random_share) * 4294967296.0)
+
+
+def mask_tokens(tok, input_ids, probability=0.15, whole_word=True, seed=0, epoch=0, mask_share=0.8, random_share=0.1, return_selected=False):
+    """SubwordTokenizer.mask_tokens: a NumPy array through swt_mlm_mask, a torch tensor on the GPU through swt_mlm_mask_dev on the
+    current device and stream, with `info` the only read-back."""
+    select_below, mask_below, random_below = _mlm_thresholds(probability, whole_word, seed, epoch, mask_share, random_share)
+    voc = tok._batch_vocabulary()
+    if isinstance(input_ids, np.ndarray):
+        if input_ids.dtype not in (np.int32, np.int64) or input_ids.ndim != 2 or not input_ids.flags.c_contiguous:
+            raise TypeError("input_ids: a 2-D C-contiguous array of int32 or int64")
+        spec = N.mlm_spec(voc.cls_tab.size, voc.mask_id, select_below, mask_below, random_below, seed, epoch, whole_word,
+                          input_ids.dtype == np.int64)
+        out = N.mlm_mask(input_ids, voc.cls_tab, voc.rand_ids, spec, selected=return_selected)
+        info = out["info"]
+    else:
+        import torch
+        if not isinstance(input_ids, torch.Tensor) or not input_ids.is_cuda or input_ids.dtype not in (torch.int32, torch.int64) \
+                or input_ids.dim() != 2 or not input_ids.is_contiguous():
+            raise TypeError("input_ids: a 2-D C-contiguous NumPy array, or torch tensor on the GPU, of int32 or int64")
+        dev = input_ids.device
+        spec = N.mlm_spec(voc.cls_tab.size, voc.mask_id, select_below, mask_below, random_below, seed, epoch, whole_word,
+                          input_ids.dtype == torch.int64)
+        with torch.cuda.device(dev):
+            if voc.d_mlm is None or voc.d_mlm[0] != dev:
+                voc.d_mlm = (dev, torch.from_numpy(voc.cls_tab).to(dev), torch.from_numpy(voc.rand_ids.view(np.int32)).to(dev))
+            _, d_cls, d_rand = voc.d_mlm
+            out = {"input_ids": torch.empty_like(input_ids), "labels": torch.empty_like(input_ids),
+                   "selected": torch.empty(input_ids.shape, dtype=torch.uint8, device=dev) if return_selected else None}
+            d_info = torch.empty(len(MLM_COUNTS), dtype=torch.int64, device=dev)
+            rows, width = input_ids.shape
+            N.check(N.lib().swt_mlm_mask_dev(input_ids.data_ptr() or d_info.data_ptr(), rows, width, d_cls.data_ptr(), d_rand.data_ptr(),
+                                             int(d_rand.numel()), C.byref(spec), out["input_ids"].data_ptr() or d_info.data_ptr(),
+                                             out["labels"].data_ptr() or d_info.data_ptr(),
+                                             out["selected"].data_ptr() or d_info.data_ptr() if return_selected else None,
+                                             d_info.data_ptr(), torch.cuda.current_stream().cuda_stream))
+            info = d_info.cpu().numpy()
+    res = {"input_ids": out["input_ids"], "labels": out["labels"]}
+    if return_selected:
+        res["selected"] = out["selected"]
+    res.update((name, int(x)) for name, x in zip(MLM_COUNTS, info))
+    return res

@@ -97,7 +97,7 @@ class SubwordTokenizer:
                      return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False,
                      text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
                      return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False,
-                     packing: Optional[str] = None, drop_last: bool = False) -> dict:
+                     packing: Optional[str] = None, drop_last: bool = False, mlm: Optional[dict] = None) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
@@ -120,10 +120,33 @@ class SubwordTokenizer:
         "position_ids" (the column's position inside its text's segment), "sequence_ids" (the segment's number in its row, -1 on
         padding), "sample_ids" (the text's index, -1 on padding), "length", "n_unknown", "n_truncated", per text "segment_row",
         "segment_col" and "segment_length", and "density", the share of columns that are not padding.  Pairs, windows, offsets
-        and left padding do not go with packing: ValueError."""
+        and left padding do not go with packing: ValueError.
+
+        mlm, a dict of mask_tokens keywords ({} for its defaults), masks the finished rows of any of these forms for the masked-LM
+        objective: "input_ids" are the masked ids and the result gains "labels" and the five counts of mask_tokens."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                                     return_special_tokens_mask, packing, drop_last)
+                                     return_special_tokens_mask, packing, drop_last, mlm)
+
+    def mask_id(self) -> int:
+        """The dense id of "[MASK]": its index where the vocabulary holds the string, else len(vocab_list()), one past the end,
+        so that no other dense id moves.  An embedding table needs max(len(vocab_list()), mask_id() + 1) rows."""
+        return int(self._batch_vocabulary().mask_id)
+
+    def mask_tokens(self, input_ids, probability: float = 0.15, whole_word: bool = True, seed: int = 0, epoch: int = 0,
+                    mask_share: float = 0.8, random_share: float = 0.1, return_selected: bool = False) -> dict:
+        """Rows of dense ids (any "input_ids" of encode_batch) masked for the masked-LM objective, on the device (swt_mlm_mask).
+        A word -- a token and the '##' tokens after it; with whole_word=False every token by itself -- is selected with
+        `probability`; of the selected tokens a mask_share becomes mask_id(), a random_share a random token of the vocabulary
+        that is no special, the rest stay.  [PAD], [UNK], [CLS], [SEP] and [MASK] are never selected.  The draws are
+        Philox4x32-10 by (seed, epoch, row, column): the same call gives the same masks whatever the batch around a row, a
+        new epoch new ones over the same rows.
+        input_ids: a 2-D C-contiguous int32 or int64 NumPy array, or such a torch tensor on the GPU (masked on the current
+        stream, the ids never leaving the device); anything else raises TypeError.
+        -> {"input_ids", "labels" (the id before masking on selected columns, -100 elsewhere), with return_selected "selected"
+        (uint8), "n_eligible", "n_selected", "n_masked", "n_random", "n_kept"}.  ValueError: a probability or share outside
+        [0, 1], mask_share + random_share > 1, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
+        return batching.mask_tokens(self, input_ids, probability, whole_word, seed, epoch, mask_share, random_share, return_selected)
 
     def _batch_encode_spans(self, texts):
         return self.encode_spans_batch(texts)
