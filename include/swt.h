@@ -107,11 +107,22 @@ int swt_utf8_lower_dev(uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent
  *   SWT_OPT_DEDUP_TABLE_BITS  log2 of the dedup word table's slots, 4..24; 0 (default): sized from the batch.  A tiny table
  *                             makes words overflow into their own slots; results stay exact
  *   SWT_OPT_UNIQUE_TILE       (FastBPE) tile size of the pass over the unique words: 0 (default), 64, 128 or 256
- *   SWT_OPT_LANE_SPAN         (FastBPE) consecutive tiles one wavefront of the direct path takes: 0 (default: one) or 1..16 */
+ *   SWT_OPT_LANE_SPAN         (FastBPE) consecutive tiles one wavefront of the direct path takes: 0 (default: one) or 1..16.
+ *                             A span above one keeps tiles of one size, whatever SWT_OPT_LANE_TAPER says
+ *   SWT_OPT_LANE_TAPER        (FastBPE) tile sizes of the direct path, falling from 384 to 128 bytes towards the end of the text so
+ *                             that the wavefronts started last are short: 0 (default): the library's choice (its own factor, and
+ *                             tiles of one size for a text that does not fill the device's slots twice); 1: tiles of one size;
+ *                             v = 2..64: a tile is the largest of 384, 256, 192, 128 bytes that is no more than the bytes still
+ *                             to be handed out / (v / 8 x the wavefront slots of the device); v + 256: the same with 192 bytes
+ *                             as the smallest size
+ *   SWT_OPT_LANE_SLOTS        (FastBPE) the wavefront slots SWT_OPT_LANE_TAPER counts with: 0 (default): those of the device;
+ *                             1..1048576: that many, so that a text of a few KiB walks through every tile size */
 #define SWT_OPT_DEDUP 1
 #define SWT_OPT_DEDUP_TABLE_BITS 2
 #define SWT_OPT_UNIQUE_TILE 3
 #define SWT_OPT_LANE_SPAN 4
+#define SWT_OPT_LANE_TAPER 5
+#define SWT_OPT_LANE_SLOTS 6
 
 /* Code-point classes compiled into the library (fixture data probed from the wheel/interpreter the
  * reference runs on; tools/gen_unicode_tables.py).  bit0 pre-tokenizer whitespace, bit1 pre-tokenizer

@@ -230,7 +230,7 @@ def init(device=0):
     check(lib().swt_init(device))
 
 
-OPT_DEDUP, OPT_DEDUP_TABLE_BITS, OPT_UNIQUE_TILE, OPT_LANE_SPAN = 1, 2, 3, 4
+OPT_DEDUP, OPT_DEDUP_TABLE_BITS, OPT_UNIQUE_TILE, OPT_LANE_SPAN, OPT_LANE_TAPER, OPT_LANE_SLOTS = 1, 2, 3, 4, 5, 6
 DEDUP_AUTO, DEDUP_NEVER, DEDUP_ALWAYS = 0, 1, 2
 
 

@@ -52,6 +52,11 @@ constexpr int kLaneTile = SWT_LANE_TILE;  // the word-lane kernel (bpe_lane_kern
 constexpr int kLaneCap = SWT_LANE_CAP;    // ... and staged bytes per chunk (a batch of 64 word lanes wants ~350 bytes of text)
 // A wave of the running-text form takes a SPAN of K consecutive tiles (lane_span below) as one long tile, chunk by chunk.
 constexpr uint32_t kLaneMaxSpan = 16;
+// The tiles of the running-text form taper towards the end of the text (lane_map below, swt_tilemap.h): no tile is larger than
+// kLaneTile, so LDS, registers and the chunk loop are those of the uniform geometry.
+constexpr uint32_t kTaperSizes[4] = {(uint32_t)kLaneTile, 256u, 192u, 128u};
+constexpr uint32_t kTaperMaxC8 = 64, kTaperMaxSlots = 1u << 20;  // the ranges of SWT_OPT_LANE_TAPER and SWT_OPT_LANE_SLOTS
+constexpr int kTaperDefault = 256 + 3;  // what SWT_OPT_LANE_TAPER = 0 means: c = 3/8, 192 bytes the smallest (profiles/lane_taper.txt section 2)
 constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one workgroup and one launch do the whole call
 
 // The rank table is a two-choice cuckoo table (built once on the host, swt_bpe_table_create): a pair lives in slot h1 or in
@@ -768,7 +773,7 @@ __device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__res
 
 #ifdef SWT_STAMPS
 // diagnostic builds only: wall_clock64() at the begin and the end of Mode 0 wave t, [2t] and [2t + 1] (zero: the wave had no work)
-constexpr uint32_t kLaneStamps = 32768;
+constexpr uint32_t kLaneStamps = 65536;  // S85k in tapering tiles: 31 k to 45 k waves
 __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 #endif
 
@@ -860,6 +865,9 @@ struct swt_bpe_table {
   DedupEngine dd;
   int opt_unique_tile = 0;  // SWT_OPT_UNIQUE_TILE
   int opt_lane_span = 0;    // SWT_OPT_LANE_SPAN
+  int opt_lane_taper = 0;   // SWT_OPT_LANE_TAPER
+  int opt_lane_slots = 0;   // SWT_OPT_LANE_SLOTS
+  uint64_t lane_slots[2] = {0, 0};  // wave slots of the device for the running-text kernel of this table ([1]: its ordered form)
 };
 
 static int bpe_upload(swt_bpe_table *t) {
@@ -944,7 +952,8 @@ int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
 } SWT_API_CATCH
 
 #ifdef SWT_STAMPS
-// diagnostic builds only: copies the stamps of the last Mode 0 launch out (2 * 32,768 values) and clears them
+// diagnostic builds only: copies the stamps of the last Mode 0 launch out (2 * swt_debug_lane_stamp_count() values) and clears them
+int swt_debug_lane_stamp_count() { return (int)kLaneStamps; }
 int swt_debug_lane_stamps(unsigned long long *out) try {
   void *d = nullptr;
   SWT_HIP(hipDeviceSynchronize());
@@ -1082,6 +1091,15 @@ int swt_bpe_table_set_option(swt_bpe_table *t, int option, int value) try {
       if (value < 0 || value > (int)kLaneMaxSpan) return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_SPAN takes 0..%u", kLaneMaxSpan);
       t->opt_lane_span = value;
       return SWT_OK;
+    case SWT_OPT_LANE_TAPER:
+      if (value < 0 || ((value & ~256) > (int)kTaperMaxC8) || value == 256 || value == 257)
+        return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_TAPER takes 0, 1, 2..%u or 256 + 2..%u", kTaperMaxC8, kTaperMaxC8);
+      t->opt_lane_taper = value;
+      return SWT_OK;
+    case SWT_OPT_LANE_SLOTS:
+      if (value < 0 || value > (int)kTaperMaxSlots) return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_SLOTS takes 0..%u", kTaperMaxSlots);
+      t->opt_lane_slots = value;
+      return SWT_OK;
   }
   return fail(SWT_ERR_INVALID, "no such option");
 } SWT_API_CATCH
@@ -1112,16 +1130,69 @@ static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileW
 
 // Tiles per wave of the running-text form: ONE.  Longer spans were measured and lost (profiles/lane_spans.txt: K = 2 costs the
 // kernel +5 %, K = 4 -- every wave of S85k resident from the start -- +10 %, K = 8 +38 %), so SWT_OPT_LANE_SPAN stays what it is
-// in the header: a knob for tests and sweeps.
+// in the header: a knob for tests and sweeps.  Why they lost is not what that file says ("the price of the dispatcher refilling a
+// CU"): the residency curve (profiles/lane_taper.txt section 1) shows 23 - 24 waves per CU of the 24 that fit from 2 us to the
+// last begin -- the dispatcher refills a slot as fast as it empties -- and nine tenths of the empty slot-time in the DRAIN behind
+// the last begin, which lasts as long as the longest life among the waves begun last (45 us at K = 1: the two-chunk tiles).
+// A span makes every life K times as long and the drain with it.  The taper below goes the other way.
 static uint32_t lane_span(const swt_bpe_table *t) { return t->opt_lane_span ? (uint32_t)t->opt_lane_span : 1u; }
+
+// Wave slots of the device for the running-text kernel this table gets: CUs x resident workgroups per CU, asked once per handle.
+static uint64_t lane_slots(swt_bpe_table *t, bool ordered) {
+  if (t->opt_lane_slots) return (uint64_t)t->opt_lane_slots;
+  uint64_t &slots = t->lane_slots[ordered ? 1 : 0];
+  if (!slots) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lane_kernel<0>(t, ordered), 64, 0) != hipSuccess || per_cu < 1) {
+      (void)hipGetLastError();
+      per_cu = 24;  // what the stamps show resident on gfx950
+    }
+    slots = (uint64_t)device_cus() * (uint64_t)per_cu;
+  }
+  return slots;
+}
+
+// Where the tiles of a running-text call begin.  A span K > 1 (SWT_OPT_LANE_SPAN) keeps its K x kLaneTile tiles of one size; the
+// library's own geometry tapers: tiles of kLaneTile bytes while the bytes still to be handed out would fill c x slots such tiles,
+// then 256, 192 and 128 bytes by the same rule (tilemap_taper), so that the waves started last have short lives.  A short tile
+// is dear (a wave's life is ~12 us + 0.047 us per byte), so the taper is short: c = 3/8 and no tile under 192 bytes unless
+// SWT_OPT_LANE_TAPER says otherwise (profiles/lane_taper.txt section 2: c = 1 down to 128 bytes LOSES 6 us to tiles of one size).
+static TileMap lane_map(swt_bpe_table *t, uint64_t n_bytes, bool ordered) {
+  const uint32_t span = lane_span(t);
+  const int v = t->opt_lane_taper ? t->opt_lane_taper : kTaperDefault;
+  if (span > 1 || v == 1 || kLaneTile <= 256) return tilemap_uniform(n_bytes, (uint32_t)kLaneTile * span);
+  const uint64_t slots = lane_slots(t, ordered);
+  // The floor of the library's own choice: a text under two chip-fulls of full tiles keeps tiles of one size (2.5 MB measured
+  // 2.2 us slower tapered, profiles/lane_taper.txt section 3).  An explicit SWT_OPT_LANE_TAPER tapers whatever the size.
+  if (!t->opt_lane_taper && n_bytes < 2ull * (uint64_t)kLaneTile * slots) return tilemap_uniform(n_bytes, (uint32_t)kLaneTile);
+  return tilemap_taper(n_bytes, slots, (uint32_t)(v & ~256), kTaperSizes, (v & 256) ? 3 : 4);
+}
+
+// diagnostics (not part of include/swt.h): the tile map a running-text call of n_bytes would get under the handle's options --
+// out[0] = tiles, then per segment the first byte, the first tile and the tile size (zeros for a segment that is not there)
+int swt_debug_bpe_tile_map(swt_bpe_table *t, uint64_t n_bytes, uint64_t *out) try {
+  if (!t || !out) return fail(SWT_ERR_INVALID, "null argument");
+  int rc = bpe_upload(t);
+  if (rc) return rc;
+  const TileMap m = lane_map(t, n_bytes, false);
+  out[0] = m.n_tiles;
+  for (int k = 0; k < kTileMapSegs; k++) {
+    const bool there = k < (int)m.n_segs;
+    out[1 + 3 * k] = there ? m.first_byte[k] : 0;
+    out[2 + 3 * k] = there ? m.first_tile[k] : 0;
+    out[3 + 3 * k] = there ? m.tile_bytes[k] : 0;
+  }
+  return SWT_OK;
+} SWT_API_CATCH
 
 static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls,
                              hipStream_t st, bool ordered) {
   // plan, scan and gather see a span as one tile of K * kLaneTile bytes (plan[j] of that size IS plan[j * K] of the tiles), and so
-  // does the kernel: its chunk loop walks the span kLaneCap bytes at a time
-  const uint32_t tile = (uint32_t)kLaneTile * lane_span(t);
-  const uint64_t n_tiles = tile_count(n_bytes, tile);
+  // does the kernel: its chunk loop walks the span kLaneCap bytes at a time.  None of them learns a tile's size: the map goes to
+  // the plan and everything behind it reads plan[t] and plan[t + 1].
+  const TileMap map = n_bytes <= kDirectBytes && n_sent <= kDirectSents ? tilemap_uniform(n_bytes, kLaneTile) : lane_map(t, n_bytes, ordered);
+  const uint64_t n_tiles = map.n_tiles;
   if (n_tiles > 0x7FFFFFFFull)
     return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
   int rc;
@@ -1137,7 +1208,7 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
   }
   if ((rc = ws.reserve(n_bytes, n_sent, n_tiles))) return rc;
   prof_begin(st, 2);
-  launch_plan(d_sent_off, n_sent, n_tiles, tile, ws.plan.as<uint64_t>(), st);
+  launch_plan(d_sent_off, n_sent, map, ws.plan.as<uint64_t>(), st);
   prof_begin(st);
   launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st, ordered);
   prof_end(st);

@@ -21,6 +21,7 @@
 #include <functional>
 
 #include "swt_common.h"
+#include "swt_tilemap.h"
 
 namespace swt {
 
@@ -42,9 +43,12 @@ struct TileWorkspace {
   void release();
 };
 
-inline uint64_t tile_count(uint64_t n_bytes, uint32_t tile) { return n_bytes ? (n_bytes + tile - 1) / tile : 1; }
+// tile_count(n_bytes, tile): swt_tilemap.h
 
 // Host launchers of the skeleton's own kernels (defined in swt_tile.hip).
+// plan[t] = the first sentence that begins at or behind map.boundary(t), for t in [0, map.n_tiles]; plan[n_tiles] = n_sent
+void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, const TileMap &map, uint64_t *d_plan, hipStream_t st);
+// the same for n_tiles tiles of one size (a one-segment map)
 void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile, uint64_t *d_plan, hipStream_t st);
 void launch_scan_only(uint64_t n_tiles, const TileWorkspace &ws, uint64_t *d_n_tokens, hipStream_t st);
 // the same scan over 64-bit values: d_local[i] = exclusive sum inside i's group of 1024, blk = [ticket (zero), totals[nb],

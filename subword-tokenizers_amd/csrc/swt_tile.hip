@@ -5,20 +5,13 @@
 
 namespace swt {
 
-// plan[t] = first sentence whose first byte is >= t * tile  (lower bound; plan[n_tiles] = n_sent).  Two forms, the same result:
-// the search (one thread per tile, log2(n_sent) dependent loads) for texts of few long sentences, and the pass below.
-__global__ void plan_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile,
-                            uint64_t *__restrict__ plan) {
+// plan[t] = first sentence whose first byte is >= map.boundary(t)  (lower bound; plan[n_tiles] = n_sent).  Two forms, the same result:
+// the search (one thread per tile, log2(n_sent) dependent loads) for texts of few long sentences, and the pass below.  The
+// arithmetic of both is in swt_tilemap.h (plan_search, plan_range), where a CPU test runs it.
+__global__ void plan_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, TileMap map, uint64_t *__restrict__ plan) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > n_tiles) return;
-  if (t == n_tiles) { plan[t] = n_sent; return; }
-  const uint64_t target = t * (uint64_t)tile;
-  uint64_t lo = 0, hi = n_sent;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (sent_off[mid] < target) lo = mid + 1; else hi = mid;
-  }
-  plan[t] = lo;
+  if (t > map.n_tiles) return;
+  plan[t] = plan_search(map, sent_off, n_sent, t);
 }
 
 // The pass: one thread per sentence, no dependent load.  Sentence s is the answer for every tile boundary in
@@ -26,17 +19,12 @@ __global__ void plan_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_se
 // "sentence" n_sent for the boundaries past the last sentence's start and for plan[n_tiles].  A thread writes up to four
 // entries itself; a longer range (a sentence of many tiles) is written by its whole wave, so one giant sentence costs a wave
 // n / 64 steps and not one thread n.
-__global__ __launch_bounds__(256) void plan_pass_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, uint64_t n_tiles,
-                                                        uint32_t tile, uint64_t *__restrict__ plan) {
+__global__ __launch_bounds__(256) void plan_pass_kernel(const uint64_t *__restrict__ sent_off, uint64_t n_sent, TileMap map,
+                                                        uint64_t *__restrict__ plan) {
   const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   uint64_t lo = 1, hi = 0;  // tiles [lo, hi] get s; empty for the threads past n_sent
-  if (s <= n_sent) {
-    lo = s ? sent_off[s - 1] / tile + 1 : 0;
-    hi = sent_off[s] / tile;
-    if (s == n_sent) { hi = n_tiles; if (lo > hi) lo = hi; }  // plan[n_tiles] is written here and only here
-    else if (hi >= n_tiles) hi = n_tiles - 1;
-  }
+  if (s <= n_sent) plan_range(map, sent_off, n_sent, s, lo, hi);
   const uint64_t cnt = hi + 1 > lo ? hi + 1 - lo : 0;
   if (cnt <= 4)
     for (uint64_t t = lo; t <= hi; t++) plan[t] = s;
@@ -209,12 +197,19 @@ void TileWorkspace::release() {
   plan.release(); scratch.release(); sent_local.release(); tile_tok.release(); tile_base.release(); blk.release();
 }
 
-void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile, uint64_t *d_plan, hipStream_t st) {
+void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, const TileMap &map, uint64_t *d_plan, hipStream_t st) {
+  const uint64_t n_tiles = map.n_tiles;
   // the pass reads every sentence offset once; the search is the better form only where sentences are few and tiles many
   if (n_sent / 256 <= n_tiles)
-    hipLaunchKernelGGL(plan_pass_kernel, dim3((unsigned)((n_sent + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, n_tiles, tile, d_plan);
+    hipLaunchKernelGGL(plan_pass_kernel, dim3((unsigned)((n_sent + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, map, d_plan);
   else
-    hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, n_tiles, tile, d_plan);
+    hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, st, d_sent_off, n_sent, map, d_plan);
+}
+
+void launch_plan(const uint64_t *d_sent_off, uint64_t n_sent, uint64_t n_tiles, uint32_t tile, uint64_t *d_plan, hipStream_t st) {
+  TileMap map = tilemap_uniform(0, tile);
+  map.n_tiles = n_tiles;  // the caller's count: the dedup path plans fewer tiles than its text would have
+  launch_plan(d_sent_off, n_sent, map, d_plan, st);
 }
 
 void launch_scan_only(uint64_t n_tiles, const TileWorkspace &ws, uint64_t *d_n_tokens, hipStream_t st) {
