@@ -116,13 +116,20 @@ int swt_utf8_lower_dev(uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent
  *                             to be handed out / (v / 8 x the wavefront slots of the device); v + 256: the same with 192 bytes
  *                             as the smallest size
  *   SWT_OPT_LANE_SLOTS        (FastBPE) the wavefront slots SWT_OPT_LANE_TAPER counts with: 0 (default): those of the device;
- *                             1..1048576: that many, so that a text of a few KiB walks through every tile size */
+ *                             1..1048576: that many, so that a text of a few KiB walks through every tile size
+ *   SWT_OPT_LANE_NARROW       (FastBPE) the direct path of a table below 32 k symbols keeps 16-bit symbol codes on chip and takes
+ *                             512-byte tiles at the top instead of 384: 0 (default): for a text that fills the device's slots
+ *                             with 384-byte tiles once, tapering from there up; the 512-byte tiles in the library's own
+ *                             geometry only (a SWT_OPT_LANE_TAPER or SWT_OPT_LANE_SPAN that is set counts from 384); 1: never;
+ *                             2: at every size (tiles of one size under that floor), and the tile sizes fall from 512 under a
+ *                             set SWT_OPT_LANE_TAPER / SWT_OPT_LANE_SPAN too */
 #define SWT_OPT_DEDUP 1
 #define SWT_OPT_DEDUP_TABLE_BITS 2
 #define SWT_OPT_UNIQUE_TILE 3
 #define SWT_OPT_LANE_SPAN 4
 #define SWT_OPT_LANE_TAPER 5
 #define SWT_OPT_LANE_SLOTS 6
+#define SWT_OPT_LANE_NARROW 7
 
 /* Code-point classes compiled into the library (fixture data probed from the wheel/interpreter the
  * reference runs on; tools/gen_unicode_tables.py).  bit0 pre-tokenizer whitespace, bit1 pre-tokenizer

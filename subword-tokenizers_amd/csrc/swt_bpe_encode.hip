@@ -26,6 +26,7 @@
 #include <unordered_map>
 #include <utility>
 
+#include "swt_bpe_narrow.h"
 #include "swt_dedup.h"
 #include "swt_tile.h"
 #include "swt_words.h"
@@ -55,6 +56,11 @@ constexpr uint32_t kLaneMaxSpan = 16;
 // The tiles of the running-text form taper towards the end of the text (lane_map below, swt_tilemap.h): no tile is larger than
 // kLaneTile, so LDS, registers and the chunk loop are those of the uniform geometry.
 constexpr uint32_t kTaperSizes[4] = {(uint32_t)kLaneTile, 256u, 192u, 128u};
+// The NARROW form of the running-text kernel (16-bit symbols in LDS, swt_bpe_narrow.h; LaneLds below) spends the LDS it saves on
+// bytes: a larger chunk in the same LDS per wave, and a tile that keeps the 128 bytes of headroom kLaneTile has under kLaneCap.
+constexpr int kNarrowCap = 640, kNarrowTile = kNarrowCap - (SWT_LANE_CAP - SWT_LANE_TILE);
+constexpr uint32_t kNarrowTaperSizes[4] = {(uint32_t)kNarrowTile, 256u, 192u, 128u};
+constexpr int kNarrowTaperDefault = 256 + 2;  // SWT_OPT_LANE_TAPER = 0 under the narrow sizes: c = 2/8, 192 bytes the smallest (profiles/lane_narrow.txt)
 constexpr uint32_t kTaperMaxC8 = 64, kTaperMaxSlots = 1u << 20;  // the ranges of SWT_OPT_LANE_TAPER and SWT_OPT_LANE_SLOTS
 constexpr int kTaperDefault = 256 + 3;  // what SWT_OPT_LANE_TAPER = 0 means: c = 3/8, 192 bytes the smallest (profiles/lane_taper.txt section 2)
 constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one workgroup and one launch do the whole call
@@ -63,13 +69,9 @@ constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one wo
 // slot h2, so a lookup is two independent 16-byte loads and two compares -- no probe loop, and a wave never goes round
 // again because one of its lanes met a collision.  The hashes are 24-bit multiplies (full-rate v_mul_u32_u24; symbol ids
 // are below 2^24 for any table under five million merges, larger ids only hash worse) with one xor-shift between them.
-struct BpeHash { uint32_t a, b, c; };
-constexpr BpeHash kHash1{0x9E3779u, 0x85EBCBu, 0xC2B2AFu}, kHash2{0x27D4EBu, 0x165667u, 0x9E3779u};
-__host__ __device__ __forceinline__ uint32_t bpe_hash(uint32_t l, uint32_t r, uint32_t sh, BpeHash k) {
-  uint32_t x = (l & 0xFFFFFFu) * k.a + (r & 0xFFFFFFu) * k.b;
-  x ^= x >> 16;
-  return ((x & 0xFFFFFFu) * k.c) >> sh;   // sh = 32 - log2(slots)
-}
+// (BpeHash, kHash1, kHash2, bpe_hash: swt_bpe_narrow.h, which the table of 16-bit codes shares them with.)
+static_assert(kNarrowSymBase == SWT_SYM_BASE, "swt_bpe_narrow.h numbers the merged symbols from SWT_SYM_BASE");
+static_assert((kNarrowCont << 16) == SWT_BPE_CONT, "the emit moves the continuation bit of a code to that of an id");
 
 __device__ __forceinline__ bool slot_lookup(const BpeSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r,
                                             uint32_t &rank, uint32_t &merged) {
@@ -90,6 +92,23 @@ __device__ __forceinline__ uint32_t slot_value(const BpeSlot *__restrict__ slots
   const uint32_t b = (r2.x == r && r2.y == l) ? r2.z : kNoRank;
   return a & b;
 }
+// The same over the table of 16-bit codes (swt_bpe_narrow.h): two 8-byte loads, one compare each.  l and r without kNarrowCont.
+__device__ __forceinline__ uint32_t slot_value(const NarrowSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r) {
+  const uint2 r1 = *reinterpret_cast<const uint2 *>(&slots[bpe_hash(l, r, sh, kHash1)]);
+  const uint2 r2 = *reinterpret_cast<const uint2 *>(&slots[bpe_hash(l, r, sh, kHash2)]);
+  const uint32_t key = narrow_key(l, r);
+  const uint32_t a = r1.x == key ? r1.y : kNoRank;
+  const uint32_t b = r2.x == key ? r2.y : kNoRank;
+  return a & b;
+}
+// What the narrow kernel reads beside its rank table, one record per handle in device memory (the kernel's merged_of_rank
+// argument, which a packed table does not use, points at it).
+struct NarrowDir {
+  const BpeSlot *wide_slots;   // the table of the ids, for the one-lane walker of a word longer than a chunk
+  const uint32_t *code_of_cp;  // [n_cps] code | class << 16 (NarrowTable::code_of_cp)
+  const uint32_t *cp_of_code;  // [letters] the alphabet, for the emit
+  uint32_t wide_sh, n_cps, letters, pad;
+};
 
 // FastBPE.encode_word on a symbol array (bpe.py:210-238), serial form for the one-lane fallback: repeat { lowest-rank
 // adjacent pair; replace all of its occurrences left to right, non-overlapping }.  Returns the new length.
@@ -230,11 +249,32 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 // Measured and dropped (profiles/r03_experiments/bpe_lane_*.txt): one wave running the rounds for the words of four tiles
 // (fewer instructions, but three waves of four idle meanwhile: 0.229 against 0.200 ms), tiles that place their own output by a
 // decoupled look-back, and tiles that plan themselves (two launches instead of four).
-template <int Cap>
+//   Narrow: the symbols in LDS are the 16-bit codes of swt_bpe_narrow.h and `slots` is the table keyed on them (NarrowSlot, with
+//          merged_of_rank pointing at a NarrowDir).  9 bytes of LDS per staged byte instead of 11, so kNarrowCap = 640 bytes fit
+//          where kLaneCap = 512 did, a wave pools a quarter more words for the same rounds, and the same number of waves reside.
+//          The split reads a code point's code AND its class from one table (code_of_cp), so the two-bit class copy in LDS and the
+//          1 KB every wave loads for it are gone.  A code point outside the alphabet is FOREIGN: it never merges, and its val[]
+//          entry -- which no lookup can fill -- carries the code point to the emit.  Running text (Mode 0) on a packed table
+//          below 32 k symbols only; Ordered, Modes 1 and 2 and every other table keep the wide kernel as it was.
+template <bool Narrow>
+struct LaneSym {  // how a symbol stands in LDS
+  using type = uint32_t;
+  using Slot = BpeSlot;
+  static constexpr uint32_t kCont = SWT_BPE_CONT, kDead = kInvalidTok;
+};
+template <>
+struct LaneSym<true> {
+  using type = uint16_t;
+  using Slot = NarrowSlot;
+  static constexpr uint32_t kCont = kNarrowCont, kDead = kNarrowDead;
+};
+template <int Cap, bool NarrowSyms = false>
 struct LaneLds {
   static constexpr int Blocks = Cap / 64;
+  static constexpr bool Narrow = NarrowSyms;
+  using Sym = typename LaneSym<Narrow>::type;
   __attribute__((aligned(16))) uint8_t txt[Cap + 16];  // staged bytes; once the split is done, a single-wave kernel's word list
-  uint32_t sym[Cap + 4];      // per symbol: id (| SWT_BPE_CONT unless it opens its word), kInvalidTok once consumed
+  Sym sym[Cap + 4];           // per symbol: id (| SWT_BPE_CONT unless it opens its word), kInvalidTok once consumed; Narrow: its code
   uint32_t val[Cap + 4];      // per symbol: table value of (this symbol, next live symbol of the word), kNoRank when none
   uint16_t wl[Cap + 2];       // first symbol of every word, in text order
   unsigned long long sbits[Blocks + 1];    // sentence-start bit per byte
@@ -244,8 +284,14 @@ struct LaneLds {
   uint32_t blkpre[Blocks + 1];             // tokens before each block of 64 symbols
 };
 // what outlives a chunk: kept out of LaneLds so that a chunk's arrays stay one block
+template <bool Narrow>
 struct LaneShared {
   uint32_t cls2[64];                       // classes of U+0000..U+03FF, two bits each
+  GiantResult giant;
+};
+template <>
+struct LaneShared<true> {                  // the narrow split reads the class beside the code (NarrowDir::code_of_cp)
+  static constexpr uint32_t *cls2 = nullptr;
   GiantResult giant;
 };
 
@@ -279,32 +325,35 @@ constexpr uint32_t kDirtyVal = 0xFFFFFFFEu;  // above every table value (ranks s
 
 // bpe.py:210-238 on one word whose symbols S[0..n) and pair values V[0..n) (V[n-1] = kNoRank) live in LDS: every round merges
 // ALL occurrences of the best pair left to right, compacts the word and probes only the pairs that changed.
-template <bool Packed>
-__device__ void slow_word(uint32_t *S, uint32_t *V, const uint32_t n0, const BpeSlot *__restrict__ slots, uint32_t sh,
-                          const uint32_t *__restrict__ merged_of_rank) {
+// Narrow: S holds 16-bit codes.  A FOREIGN symbol's V entry is its code point (>= kNarrowNoPair, so it is never the minimum); it
+// moves with the symbol when the word is compacted and is neither marked dirty nor reset.
+template <bool Packed, bool Narrow = false>
+__device__ void slow_word(typename LaneSym<Narrow>::type *S, uint32_t *V, const uint32_t n0, const typename LaneSym<Narrow>::Slot *__restrict__ slots,
+                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
+  constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   uint32_t n = n0;
   for (;;) {
     uint32_t m = kNoRank;
     for (uint32_t i = 0; i + 1 < n; i++) m = min(m, V[i]);
-    if (m == kNoRank) break;
-    const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+    if (Narrow ? m >= kNarrowNoPair : m == kNoRank) break;
+    const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
     uint32_t i = 0, j = 0;
     while (i < n) {
       const uint32_t vi = V[i];
       const bool take = i + 1 < n && vi == m;
-      const uint32_t s = take ? mg : (S[i] & ~SWT_BPE_CONT);
-      if (take && j) V[j - 1] = kDirtyVal;
-      S[j] = j ? (s | SWT_BPE_CONT) : s;
+      const uint32_t s = take ? mg : (S[i] & ~kCont);
+      if (take && j && !(Narrow && (S[j - 1] & ~kCont) == kNarrowForeign)) V[j - 1] = kDirtyVal;
+      S[j] = j ? (s | kCont) : s;
       V[j] = take ? kDirtyVal : vi;
       i += take ? 2u : 1u;
       j++;
     }
     n = j;
-    V[n - 1] = kNoRank;
+    if (!(Narrow && (S[n - 1] & ~kCont) == kNarrowForeign)) V[n - 1] = kNoRank;
     for (uint32_t k = 0; k + 1 < n; k++)
-      if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT);
+      if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~kCont, S[k + 1] & ~kCont);
   }
-  for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
+  for (uint32_t k = n; k < n0; k++) S[k] = kDead;
 }
 
 // NaiveBPE.encode_word (bpe.py:124-127) on the same layout, modelled on slow_word: a round merges all occurrences of the pair
@@ -344,7 +393,7 @@ __device__ void ordered_word(uint32_t *S, uint32_t *V, const uint32_t n0, const 
 }
 
 // classes of the first 1,024 code points: 16 per lane, two bits each (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)
-__device__ __forceinline__ void lane_classes(LaneShared &L, const uint8_t *__restrict__ cls_tab, int lane) {
+__device__ __forceinline__ void lane_classes(LaneShared<false> &L, const uint8_t *__restrict__ cls_tab, int lane) {
   uint32_t w = 0;
   if (cls_tab) {
     const uint4 v = reinterpret_cast<const uint4 *>(cls_tab)[lane];
@@ -360,11 +409,15 @@ __device__ __forceinline__ void lane_classes(LaneShared &L, const uint8_t *__res
 
 // ---- A + B/C of one chunk: stage the bytes, then 64 bytes per step: classes, word structure from ballot masks, the dense
 // symbols, the list of word starts, and the table value of every adjacent pair of a word.
-template <int Cap>
-__device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2, const uint8_t *__restrict__ text, uint64_t n_bytes,
-                                           const uint64_t *__restrict__ sent_off, const uint8_t *__restrict__ cls_tab,
-                                           const BpeSlot *__restrict__ slots, uint32_t sh, const LaneTile &T, LaneChunk &C, int lane) {
+// Narrow: the symbols are codes, read with the class from D.code_of_cp (cls2 is not there); a FOREIGN symbol's val[] entry gets
+// its code point.
+template <int Cap, bool Narrow>
+__device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32_t *cls2, const NarrowDir &D, const uint8_t *__restrict__ text,
+                                           uint64_t n_bytes, const uint64_t *__restrict__ sent_off, const uint8_t *__restrict__ cls_tab,
+                                           const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh, const LaneTile &T, LaneChunk &C,
+                                           int lane) {
   constexpr int Blocks = Cap / 64;
+  constexpr uint32_t kCont = LaneSym<Narrow>::kCont;
   const unsigned long long lt = (1ull << lane) - 1ull;  // lanes below me
   const unsigned long long le = (2ull << lane) - 1ull;  // me and below
   const uint64_t abase = T.cb & ~15ull;
@@ -413,7 +466,21 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2
       }
     }
     uint32_t c = kClsWs;  // bytes outside the chunk behave as whitespace
-    if (inr && lead)
+    uint32_t sy = cp;     // the symbol: the code point, or (Narrow) its code
+    if constexpr (Narrow) {
+      sy = kNarrowForeign;
+      if (inr && lead) {
+        if (cp < D.n_cps) {
+          const uint32_t e = D.code_of_cp[cp];
+          sy = e & 0xFFFFu;
+          c = cls_tab ? (e >> 16) : 0u;
+        } else {
+          c = (cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u;
+          // an ill-formed sequence that decodes past U+10FFFF reads as the symbol id it equals, as it does in the wide kernel
+          if (cp >= SWT_SYM_BASE && cp - SWT_SYM_BASE + D.letters < kNarrowMaxCodes) sy = cp - SWT_SYM_BASE + D.letters;
+        }
+      }
+    } else if (inr && lead)
       c = cp < 1024u ? ((cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u) : ((cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u);
     const unsigned long long INR = __ballot(inr);
     const unsigned long long LEAD = __ballot(lead);
@@ -441,18 +508,21 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2
     const uint32_t f = SYM ? (uint32_t)__builtin_ctzll(SYM) : 64u;
     const bool joins = pend_open && f < 64 && !((WSTART >> (f & 63)) & 1ull);
     const uint32_t si = nsym + (uint32_t)__popcll(SYM & lt);
-    const uint32_t cpn = __shfl(cp, (int)(q & 63));
-    // lane 63 never has a successor inside the block: it probes the pair that straddles the block boundary
-    const bool jp = joins && lane == 63;
-    const uint32_t cpf = __builtin_amdgcn_readlane(cp, (int)(f & 63));
+    const uint32_t cpn = __shfl(sy, (int)(q & 63));
+    // lane 63 never has a successor inside the block: it probes the pair that straddles the block boundary (Narrow: not behind a
+    // FOREIGN symbol, whose entry is taken)
+    const bool jp = joins && lane == 63 && !(Narrow && pend_cp == kNarrowForeign);
+    const uint32_t cpf = __builtin_amdgcn_readlane(sy, (int)(f & 63));
     const bool want = hasnext || jp;
     uint32_t v = kNoRank;
-    if (want) v = slot_value(slots, sh, jp ? pend_cp : cp, jp ? cpf : cpn);
+    if (want) v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn);
     if (is_sym) {
-      L.sym[si] = wstart ? cp : (cp | SWT_BPE_CONT);
+      L.sym[si] = wstart ? sy : (sy | kCont);
       if (!hasnext) L.val[si] = kNoRank;
     }
     if (want) L.val[jp ? nsym - 1 : si] = v;
+    if constexpr (Narrow)
+      if (is_sym && sy == kNarrowForeign) L.val[si] = kNarrowNoPair | (cp & kNarrowCpMask);
     if (wstart) L.wl[nw + (uint32_t)__popcll(WSTART & lt)] = (uint16_t)si;
     if (lane == 0) { L.symmask[blk] = SYM; L.sympre[blk] = nsym; }
     nw += (uint32_t)__popcll(WSTART);
@@ -461,7 +531,7 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2
       const int li = 63 - __builtin_clzll(SYM);
       const unsigned long long tail = li == 63 ? 0ull : ~((2ull << li) - 1ull);
       pend_open = ((WSm | PNm | SS) & tail) == 0ull && !((PNm >> li) & 1ull);
-      pend_cp = __builtin_amdgcn_readlane(cp, li);
+      pend_cp = __builtin_amdgcn_readlane(sy, li);
     } else {
       pend_open = false;  // a block without symbols holds whitespace: every word ended
     }
@@ -482,8 +552,8 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap> &L, const uint32_t *cls2
 
 // ---- the end of a chunk that does not end the tile: one word longer than the staged bytes goes to the one-lane walker (and the
 // chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list and moves T.cb past the chunk.
-template <int Cap, int Mode, bool Packed, bool Ordered>
-__device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
+template <int Cap, int Mode, bool Packed, bool Ordered, bool Narrow>
+__device__ __forceinline__ void lane_chunk_end(LaneLds<Cap, Narrow> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
                                                const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
                                                const uint32_t *__restrict__ merged_of_rank, LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
                                                const uint32_t *__restrict__ uslot, unsigned long long *__restrict__ rec,
@@ -537,8 +607,8 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap> &L, GiantResult &gia
 
 // ---- W. the words with two symbols or more by length class: how many, then their entries (the word's index in wl[]) into a list
 // that holds all 9+ words first, then the 5-8, then the 2-4 (o2 / o1 / o0 = where this wave's share of each class begins)
-template <int Cap>
-__device__ __forceinline__ void lane_words_count(const LaneLds<Cap> &L, uint32_t nw, int lane, uint32_t &c2, uint32_t &c1, uint32_t &c0) {
+template <int Cap, bool Narrow>
+__device__ __forceinline__ void lane_words_count(const LaneLds<Cap, Narrow> &L, uint32_t nw, int lane, uint32_t &c2, uint32_t &c1, uint32_t &c0) {
   c0 = c1 = c2 = 0;
   for (uint32_t k0 = 0; k0 < nw; k0 += 64) {
     const uint32_t k = k0 + lane;
@@ -548,8 +618,8 @@ __device__ __forceinline__ void lane_words_count(const LaneLds<Cap> &L, uint32_t
     c2 += (uint32_t)__popcll(__ballot(n >= 9));
   }
 }
-template <int Cap>
-__device__ __forceinline__ void lane_words_write(const LaneLds<Cap> &L, uint32_t nw, int lane, uint16_t *list, uint32_t o2, uint32_t o1,
+template <int Cap, bool Narrow>
+__device__ __forceinline__ void lane_words_write(const LaneLds<Cap, Narrow> &L, uint32_t nw, int lane, uint16_t *list, uint32_t o2, uint32_t o1,
                                                  uint32_t o0) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   for (uint32_t k0 = 0; k0 < nw; k0 += 64) {
@@ -602,10 +672,12 @@ struct LaneWord {
 // of the slots, a shuffle finds the word's minimum, every lane of the group follows the merge (same values, LDS broadcasts), lane 0
 // writes it and looks the left pair up while lane 1 looks up the right.  LEAD = the lanes that hold a word's state on entry (at
 // most 64 / TL of them); the function returns when every word is finished.
-template <bool Packed, uint32_t TL, int Cap>
-__device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, unsigned long long LEAD, int lane, const BpeSlot *__restrict__ slots,
-                                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
-  constexpr uint32_t kNoKey = Packed ? 0xFFFF0000u : 0xFFFFFFE0u;
+template <bool Packed, uint32_t TL, int Cap, bool Narrow>
+__device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWord &W, unsigned long long LEAD, int lane,
+                                          const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
+                                          const uint32_t *__restrict__ merged_of_rank) {
+  constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
+  constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   // group g of TL lanes takes over the g-th word
   const uint32_t g = (uint32_t)lane / TL, j = (uint32_t)lane % TL;
   unsigned long long mrest = LEAD;
@@ -613,7 +685,8 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, un
   const bool have = mrest != 0ull;
   const int src = have ? __builtin_ctzll(mrest) : 0;
   const uint32_t t_w = __shfl(W.where, src), t_n = __shfl(W.n, src), t_alive = __shfl(W.alive, src);
-  uint32_t *const S = L.sym + t_w, *const V = L.val + t_w;
+  typename LaneSym<Narrow>::type *const S = L.sym + t_w;
+  uint32_t *const V = L.val + t_w;
   uint32_t n = have ? t_n : 0u, alive = t_alive;
   for (;;) {
     if (__ballot(n != 0u) == 0ull) break;
@@ -642,17 +715,17 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, un
         const bool has_rr = hi2 != 0u, has_pl = lo != 0u;
         const uint32_t rr = has_rr ? (uint32_t)__builtin_ctz(hi2) : 0u, pl = has_pl ? 31u - (uint32_t)__builtin_clz(lo) : 0u;
         alive &= ~(1u << r);
-        const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
-        const uint32_t sl = S[pl] & ~SWT_BPE_CONT, sr = S[rr] & ~SWT_BPE_CONT;
+        const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+        const uint32_t sl = S[pl] & ~kCont, sr = S[rr] & ~kCont;
         wave_sync();  // every lane has read the old symbols before lane 0 changes them
         const bool left = j == 0u && has_pl, right = j == 1u && has_rr;
         uint32_t v = kNoRank;
         if (left || right) v = slot_value(slots, sh, left ? sl : mg, left ? mg : sr);
         if (j == 0u) {
-          S[im] = im ? (mg | SWT_BPE_CONT) : mg;
-          S[r] = kInvalidTok;
+          S[im] = im ? (mg | kCont) : mg;
+          S[r] = kDead;
           V[r] = kNoRank;
-          if (has_pl) V[pl] = v;
+          if (has_pl && !(Narrow && sl == kNarrowForeign)) V[pl] = v;  // a FOREIGN symbol's entry is its code point
         }
         if (j == 1u) V[im] = v;  // kNoRank when nothing follows
       }
@@ -662,15 +735,19 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap> &L, const LaneWord &W, un
 }
 
 // The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
-template <bool Packed, bool Proper, int Cap, bool Ordered>
-__device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t *list, uint32_t n_list, int lane,
-                                                const BpeSlot *__restrict__ slots, uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
-  constexpr uint32_t kNoKey = Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
+template <bool Packed, bool Proper, int Cap, bool Ordered, bool Narrow>
+__device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const uint16_t *list, uint32_t n_list, int lane,
+                                                const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
+                                                const uint32_t *__restrict__ merged_of_rank) {
+  static_assert(!(Narrow && (Ordered || !Packed)), "the narrow form is that of a packed table in FastBPE's order");
+  constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
+  constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   const unsigned long long lt = (1ull << lane) - 1ull;
   uint32_t next = 0;  // first word of the list no lane has taken (the same in every lane)
   uint32_t n = 0, alive = 0, where = 0;  // this lane's word: symbols (0: none), live slots, first slot
   uint32_t key = 0xFFFFFFFFu;            // its smallest rank | the slot that holds it
-  uint32_t *S = L.sym, *V = L.val;
+  typename LaneSym<Narrow>::type *S = L.sym;
+  uint32_t *V = L.val;
   for (;;) {
     const unsigned long long IDLE = __ballot(n == 0u);
     if (IDLE && next < n_list) {
@@ -682,11 +759,11 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t 
         S = &L.sym[where];
         V = &L.val[where];
         alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
-        if (Ordered) {
+        if constexpr (Ordered) {
           ordered_word<Packed>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
         } else if (!Proper || n > 32u) {
-          slow_word<Packed>(S, V, n, slots, sh, merged_of_rank);
+          slow_word<Packed, Narrow>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
         } else {
           key = scan_key<Packed>(V, n);
@@ -711,13 +788,13 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t 
         const bool has_rr = hi2 != 0u, has_pl = lo != 0u;
         const uint32_t rr = has_rr ? (uint32_t)__builtin_ctz(hi2) : 0u, pl = has_pl ? 31u - (uint32_t)__builtin_clz(lo) : im;
         alive &= ~(1u << r);
-        const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
-        const uint32_t sl = S[pl] & ~SWT_BPE_CONT, sr = S[rr] & ~SWT_BPE_CONT;
-        S[im] = im ? (mg | SWT_BPE_CONT) : mg;
-        S[r] = kInvalidTok;
+        const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+        const uint32_t sl = S[pl] & ~kCont, sr = S[rr] & ~kCont;
+        S[im] = im ? (mg | kCont) : mg;
+        S[r] = kDead;
         V[r] = kNoRank;
         const uint32_t v1 = slot_value(slots, sh, sl, mg), v2 = has_rr ? slot_value(slots, sh, mg, sr) : kNoRank;
-        if (has_pl) V[pl] = v1;
+        if (has_pl && !(Narrow && sl == kNarrowForeign)) V[pl] = v1;  // a FOREIGN symbol's entry is its code point
         V[im] = v2;
         key = scan_key<Packed>(V, n);
       }
@@ -729,8 +806,10 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap> &L, const uint16_t 
 // ---- E + F of one chunk: order-preserving compaction of the live symbols into the tile's output run, then the tile-local
 // token offset of every sentence starting in [cb, ce) (and == ce on the last chunk): byte -> symbol through the split's
 // masks, symbol -> token through phase E's.  Advances the tile's sentences and its run.
-template <int Cap, int Mode>
-__device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__restrict__ sent_off, LaneTile &T, const LaneChunk &C, int lane,
+// Narrow: a code goes out as the id it stands for -- a letter through D.cp_of_code, a merged symbol by its number, a FOREIGN one
+// from its val[] entry.
+template <int Cap, int Mode, bool Narrow>
+__device__ __forceinline__ void lane_emit(LaneLds<Cap, Narrow> &L, const NarrowDir &D, const uint64_t *__restrict__ sent_off, LaneTile &T, const LaneChunk &C, int lane,
                                           uint32_t *__restrict__ sent_local, const uint32_t *__restrict__ uslot,
                                           unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec,
                                           const DirectOut &direct) {
@@ -739,10 +818,19 @@ __device__ __forceinline__ void lane_emit(LaneLds<Cap> &L, const uint64_t *__res
   uint32_t total = 0;
   for (uint32_t j0 = 0; j0 < C.nsym; j0 += 64) {
     const uint32_t j = j0 + lane;
-    const uint32_t sv = j < C.nsym ? L.sym[j] : kInvalidTok;
-    const unsigned long long m = __ballot(sv != kInvalidTok);
+    constexpr uint32_t kDead = LaneSym<Narrow>::kDead;
+    const uint32_t sv = j < C.nsym ? L.sym[j] : kDead;
+    const unsigned long long m = __ballot(sv != kDead);
     if (lane == 0) { L.vmask[j0 >> 6] = m; L.blkpre[j0 >> 6] = total; }
-    if (sv != kInvalidTok) T.tile_out[T.run + total + (uint32_t)__popcll(m & lt)] = sv;
+    uint32_t id = sv;
+    if constexpr (Narrow) {
+      const uint32_t c = sv & ~kNarrowCont;  // (a dead slot's code is neither a letter nor FOREIGN: it reads nothing)
+      id = c + (SWT_SYM_BASE - D.letters);
+      if (c < D.letters) id = D.cp_of_code[c];
+      if (c == kNarrowForeign) id = L.val[j] & kNarrowCpMask;
+      id |= (sv & kNarrowCont) << 16;
+    }
+    if (sv != kDead) T.tile_out[T.run + total + (uint32_t)__popcll(m & lt)] = id;
     total += (uint32_t)__popcll(m);
   }
   wave_sync();
@@ -778,7 +866,7 @@ __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 #endif
 
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
-template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false>
+template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots,
@@ -786,9 +874,16 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, const uint32_t *__restrict__ uslot,
     unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec, DirectOut direct) {
   constexpr bool kDirect = Mode == 2;
-  static_assert(Cap % 64 == 0 && Cap <= 4032, "12 B of LDS per staged byte; wl[] and the word list hold 16-bit indices");
-  __shared__ LaneLds<Cap> L;
-  __shared__ LaneShared SH;
+  static_assert(Cap % 64 == 0 && Cap <= 4032, "11 B of LDS per staged byte and the masks (Narrow: 9 B); wl[] and the word list hold 16-bit indices");
+  static_assert(!Narrow || (Mode == 0 && Packed && !Ordered), "the narrow form: running text, a packed table, FastBPE's order");
+  static_assert(!Narrow || kLaneCap != 512 || sizeof(LaneLds<Cap, true>) + sizeof(LaneShared<true>) <= sizeof(LaneLds<kLaneCap>) + sizeof(LaneShared<false>),
+                "the narrow kernel's chunk is sized to the LDS of the wide one, so that as many waves reside");
+  using Slot = typename LaneSym<Narrow>::Slot;
+  __shared__ LaneLds<Cap, Narrow> L;
+  __shared__ LaneShared<Narrow> SH;
+  const Slot *const tab = reinterpret_cast<const Slot *>(slots);  // Narrow: the launch passes the table of the codes here
+  NarrowDir D{};
+  if constexpr (Narrow) D = *reinterpret_cast<const NarrowDir *>(merged_of_rank);
   const int lane = threadIdx.x;
   const uint64_t t = blockIdx.x;
 #ifdef SWT_STAMPS
@@ -801,7 +896,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     if (Mode == 0 && lane == 0) tile_tok[t] = 0;
     return;
   }
-  lane_classes(SH, cls_tab, lane);
+  if constexpr (!Narrow) lane_classes(SH, cls_tab, lane);
   T.span_base = sent_off[T.s_lo];
   T.span_end = sent_off[T.s_hi];
   T.tile_out = scratch + T.span_base;
@@ -811,19 +906,21 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   uint16_t *const list = reinterpret_cast<uint16_t *>(L.txt);  // the staged bytes are not read again once the split is done
   for (;;) {
     LaneChunk C;
-    lane_split(L, SH.cls2, text, n_bytes, sent_off, cls_tab, slots, sh, T, C, lane);
-    lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, slots, sh, merged_of_rank, T, C, lane, sent_local, uslot, rec, drec, direct);
+    lane_split(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
+    // (the one-lane walker of a word longer than a chunk works on ids, whatever the kernel's symbols are)
+    lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, Narrow ? D.wide_slots : slots, Narrow ? D.wide_sh : sh, merged_of_rank, T, C,
+                                               lane, sent_local, uslot, rec, drec, direct);
     if (C.giant) continue;
     uint32_t c2, c1, c0;
     lane_words_count(L, C.nw, lane, c2, c1, c0);
     lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1);
     wave_sync();
     // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
-    const LaneWord W = lane_rounds<Packed, Proper, Cap, Ordered>(L, list, c2 + c1 + c0, lane, slots, sh, merged_of_rank);
+    const LaneWord W = lane_rounds<Packed, Proper, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank);
     const unsigned long long BUSY = __ballot(W.n != 0u);
-    if (BUSY != 0ull) lane_tail<Packed, 4, Cap>(L, W, BUSY, lane, slots, sh, merged_of_rank);
+    if (BUSY != 0ull) lane_tail<Packed, 4, Cap>(L, W, BUSY, lane, tab, sh, merged_of_rank);
     wave_sync();
-    lane_emit<Cap, Mode>(L, sent_off, T, C, lane, sent_local, uslot, rec, drec, direct);
+    lane_emit<Cap, Mode>(L, D, sent_off, T, C, lane, sent_local, uslot, rec, drec, direct);
     if (C.last) break;
   }
   if (lane == 0) {
@@ -867,11 +964,48 @@ struct swt_bpe_table {
   int opt_lane_span = 0;    // SWT_OPT_LANE_SPAN
   int opt_lane_taper = 0;   // SWT_OPT_LANE_TAPER
   int opt_lane_slots = 0;   // SWT_OPT_LANE_SLOTS
-  uint64_t lane_slots[2] = {0, 0};  // wave slots of the device for the running-text kernel of this table ([1]: its ordered form)
+  int opt_lane_narrow = 0;  // SWT_OPT_LANE_NARROW
+  int last_lane_narrow = -1;  // what the last running-text launch took: 1 the narrow kernel, 0 a wide one, -1 none yet (diagnostics)
+  uint64_t lane_slots[3] = {0, 0, 0};  // wave slots of the device for the running-text kernel of this table ([1]: its ordered form, [2]: its narrow form)
+  // 16-bit symbol codes (swt_bpe_narrow.h) for the narrow form of the running-text kernel; empty unless narrow.eligible
+  NarrowTable narrow;
+  NarrowSlot *d_nslots = nullptr;
+  uint32_t *d_ncodes = nullptr;  // code_of_cp, then cp_of_code
+  NarrowDir *d_ndir = nullptr;
 };
 
+// The narrow kernel's tables.  The handle has them once d_ndir is set, and d_ndir is set last: a call that fails on the way
+// frees what it allocated and leaves the handle without them, so the next call tries again and no launch sees half of them.
+static int bpe_upload_narrow(swt_bpe_table *t) {
+  if (!t->narrow.eligible || t->d_ndir) return SWT_OK;
+  const NarrowTable &n = t->narrow;
+  std::vector<uint32_t> codes = n.code_of_cp(host_class_table());
+  const uint32_t n_cps = (uint32_t)codes.size();
+  codes.insert(codes.end(), n.cp_of_code.begin(), n.cp_of_code.end());
+  NarrowSlot *d_nslots = nullptr;
+  uint32_t *d_ncodes = nullptr;
+  NarrowDir *d_ndir = nullptr;
+  hipError_t e = hipMalloc((void **)&d_nslots, n.slots.size() * sizeof(NarrowSlot));
+  if (e == hipSuccess) e = hipMemcpy(d_nslots, n.slots.data(), n.slots.size() * sizeof(NarrowSlot), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_ncodes, (codes.size() + 1) * 4);
+  if (e == hipSuccess) e = hipMemcpy(d_ncodes, codes.data(), codes.size() * 4, hipMemcpyHostToDevice);
+  const NarrowDir dir{t->d_slots, d_ncodes, d_ncodes + n_cps, 32u - t->bits, n_cps, n.letters(), 0u};
+  if (e == hipSuccess) e = hipMalloc((void **)&d_ndir, sizeof dir);
+  if (e == hipSuccess) e = hipMemcpy(d_ndir, &dir, sizeof dir, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (d_nslots) (void)hipFree(d_nslots);
+    if (d_ncodes) (void)hipFree(d_ncodes);
+    if (d_ndir) (void)hipFree(d_ndir);
+    SWT_HIP(e);
+  }
+  t->d_nslots = d_nslots;
+  t->d_ncodes = d_ncodes;
+  t->d_ndir = d_ndir;
+  return SWT_OK;
+}
+
 static int bpe_upload(swt_bpe_table *t) {
-  if (t->d_slots) return SWT_OK;
+  if (t->d_slots) return bpe_upload_narrow(t);
   int rc = ensure_device();
   if (rc) return rc;
   SWT_HIP(hipMalloc((void **)&t->d_slots, t->h_slots.size() * sizeof(BpeSlot)));
@@ -879,7 +1013,7 @@ static int bpe_upload(swt_bpe_table *t) {
   SWT_HIP(hipMalloc((void **)&t->d_merged, (t->h_merged.size() + 1) * 4));
   if (!t->h_merged.empty())
     SWT_HIP(hipMemcpy(t->d_merged, t->h_merged.data(), t->h_merged.size() * 4, hipMemcpyHostToDevice));
-  return SWT_OK;
+  return bpe_upload_narrow(t);
 }
 
 static int bpe_upload_ordered(swt_bpe_table *t) {
@@ -917,6 +1051,26 @@ static LaneKernel lane_kernel(const swt_bpe_table *t, bool ordered, int cap = kL
   }
   return lane_kernel_at<kLaneCap, Mode>(t->packed, t->proper, ordered);
 }
+// The narrow form (16-bit symbols, kNarrowCap bytes a chunk) runs the running text of an eligible table in FastBPE's order from
+// one chip-full of kLaneTile-byte tiles up: below that every wave is resident at once, the call lasts as long as its longest
+// wave, and a larger tile only makes that wave longer (profiles/lane_narrow.txt section 5: 64 KB to 1 MB lose 5 - 11 us to the
+// narrow kernel, 2.5 MB gains 5).  SWT_OPT_LANE_NARROW = 1 keeps the wide kernel, 2 takes the narrow one at every size.  The
+// unique-word pass and the single workgroup stay wide: their chunks are sized by their tiles (128 to 512 bytes of words, one
+// short call), not by the LDS, so 16-bit symbols would buy them nothing.
+static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow);
+static bool lane_narrow(swt_bpe_table *t, bool ordered, uint64_t n_bytes) {
+  if (!t->narrow.eligible || ordered || t->opt_lane_narrow == 1) return false;
+  return t->opt_lane_narrow == 2 || n_bytes >= (uint64_t)kLaneTile * lane_slots(t, false, false);
+}
+static LaneKernel lane_kernel_narrow(const swt_bpe_table *t) {
+  return t->proper ? bpe_lane_kernel<true, true, kNarrowCap, 0, false, true> : bpe_lane_kernel<true, false, kNarrowCap, 0, false, true>;
+}
+// The largest tile of a running-text call.  The narrow kernel's own geometry has kNarrowTile; a call whose geometry is SET
+// (SWT_OPT_LANE_TAPER, SWT_OPT_LANE_SPAN) keeps the sizes those options are documented with, kLaneTile at the top, whichever
+// kernel runs it -- the narrow kernel takes any tile up to its own -- unless SWT_OPT_LANE_NARROW = 2 asks for the narrow sizes.
+static bool lane_narrow_tiles(swt_bpe_table *t, bool ordered, uint64_t n_bytes) {
+  return lane_narrow(t, ordered, n_bytes) && (t->opt_lane_narrow == 2 || (!t->opt_lane_taper && !t->opt_lane_span));
+}
 
 extern "C" {
 
@@ -924,9 +1078,17 @@ extern "C" {
 // 2: proper (every pair ranks above the merges producing its symbols), 3: entries in the table, 4: every entry is found where
 // a device lookup looks for it (its first or its second slot) and nowhere else, 5: order-equivalent (no pair listed twice and
 // proper: NaiveBPE's list order, bpe.py:126-127, gives what FastBPE's lowest rank first gives, and swt_bpe_encode_naive* run the
-// FastBPE path), 6: entries in the ordered table (0 for an order-equivalent table, which has none)
+// FastBPE path), 6: entries in the ordered table (0 for an order-equivalent table, which has none), 7: which running-text calls in
+// FastBPE's order take the NARROW kernel -- 0 none (not eligible, or SWT_OPT_LANE_NARROW = 1), 1 those of a chip-full of tiles
+// and more (the library's choice), 2 all (SWT_OPT_LANE_NARROW = 2), 8: eligible for it (packed and letters + merges <= 0x7FFD),
+// 9: letters of its alphabet (0 when not eligible), 11: the kernel the LAST running-text launch of this handle took, written where
+// the launch picks it -- 1 the narrow kernel, 0 a wide one, -1 no such launch yet
 int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   if (!t) return -1;
+  if (which == 7) return !t->narrow.eligible || t->opt_lane_narrow == 1 ? 0 : t->opt_lane_narrow == 2 ? 2 : 1;
+  if (which == 8) return t->narrow.eligible ? 1 : 0;
+  if (which == 9) return (int)t->narrow.letters();
+  if (which == 11) return t->last_lane_narrow;
   if (which == 0) return (int)t->bits;
   if (which == 1) return t->packed ? 1 : 0;
   if (which == 2) return t->proper ? 1 : 0;
@@ -1062,6 +1224,11 @@ int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint
       return fail(SWT_ERR_UNSUPPORTED, "the ordered rank table could not be placed (%u pairs)", n_merges);
     }
   }
+  {
+    std::vector<bool> live(n_merges);
+    for (uint32_t i = 0; i < n_merges; i++) live[i] = last[pair_key(left[i], right[i])] == i;
+    narrow_build(left, right, merged, n_merges, t->packed, live, t->narrow);
+  }
   if (t->packed) {
     for (auto &sl : slots)
       if (sl.key != kEmptyKey) sl.rank = (sl.rank << 16) | (sl.merged - SWT_SYM_BASE);
@@ -1100,6 +1267,10 @@ int swt_bpe_table_set_option(swt_bpe_table *t, int option, int value) try {
       if (value < 0 || value > (int)kTaperMaxSlots) return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_SLOTS takes 0..%u", kTaperMaxSlots);
       t->opt_lane_slots = value;
       return SWT_OK;
+    case SWT_OPT_LANE_NARROW:
+      if (value < 0 || value > 2) return fail(SWT_ERR_INVALID, "SWT_OPT_LANE_NARROW takes 0, 1 or 2");
+      t->opt_lane_narrow = value;
+      return SWT_OK;
   }
   return fail(SWT_ERR_INVALID, "no such option");
 } SWT_API_CATCH
@@ -1110,6 +1281,9 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
   if (t->d_merged) (void)hipFree(t->d_merged);
   if (t->d_oslots) (void)hipFree(t->d_oslots);
   if (t->d_oinfo) (void)hipFree(t->d_oinfo);
+  if (t->d_nslots) (void)hipFree(t->d_nslots);
+  if (t->d_ncodes) (void)hipFree(t->d_ncodes);
+  if (t->d_ndir) (void)hipFree(t->d_ndir);
   t->ws.release();
   t->ws2.release();
   t->dd.release();
@@ -1122,8 +1296,11 @@ void swt_bpe_table_destroy(swt_bpe_table *t) try {
 static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes,
                                  const uint64_t *d_sent_off, const uint8_t *d_cls, const uint32_t *d_uslot, unsigned long long *d_rec,
                                  unsigned long long *d_drec, hipStream_t st, bool ordered, int cap = kLaneCap) {
-  const BpeView v = bpe_view(t, ordered);
-  hipLaunchKernelGGL(d_rec ? lane_kernel<1>(t, ordered, cap) : lane_kernel<0>(t, ordered, cap), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text,
+  BpeView v = bpe_view(t, ordered);
+  const bool narrow = !d_rec && t->d_ndir && lane_narrow(t, ordered, n_bytes);
+  if (!d_rec) t->last_lane_narrow = narrow ? 1 : 0;
+  if (narrow) v = BpeView{reinterpret_cast<const BpeSlot *>(t->d_nslots), reinterpret_cast<const uint32_t *>(t->d_ndir), 32u - t->narrow.bits};
+  hipLaunchKernelGGL(narrow ? lane_kernel_narrow(t) : d_rec ? lane_kernel<1>(t, ordered, cap) : lane_kernel<0>(t, ordered, cap), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text,
                      n_bytes, d_sent_off, ws.plan.as<uint64_t>(), d_cls, v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(),
                      ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), d_uslot, d_rec, d_drec, DirectOut{nullptr, nullptr, 0});
 }
@@ -1138,12 +1315,12 @@ static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileW
 static uint32_t lane_span(const swt_bpe_table *t) { return t->opt_lane_span ? (uint32_t)t->opt_lane_span : 1u; }
 
 // Wave slots of the device for the running-text kernel this table gets: CUs x resident workgroups per CU, asked once per handle.
-static uint64_t lane_slots(swt_bpe_table *t, bool ordered) {
+static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow) {
   if (t->opt_lane_slots) return (uint64_t)t->opt_lane_slots;
-  uint64_t &slots = t->lane_slots[ordered ? 1 : 0];
+  uint64_t &slots = t->lane_slots[narrow ? 2 : ordered ? 1 : 0];
   if (!slots) {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lane_kernel<0>(t, ordered), 64, 0) != hipSuccess || per_cu < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow ? lane_kernel_narrow(t) : lane_kernel<0>(t, ordered), 64, 0) != hipSuccess || per_cu < 1) {
       (void)hipGetLastError();
       per_cu = 24;  // what the stamps show resident on gfx950
     }
@@ -1159,13 +1336,19 @@ static uint64_t lane_slots(swt_bpe_table *t, bool ordered) {
 // SWT_OPT_LANE_TAPER says otherwise (profiles/lane_taper.txt section 2: c = 1 down to 128 bytes LOSES 6 us to tiles of one size).
 static TileMap lane_map(swt_bpe_table *t, uint64_t n_bytes, bool ordered) {
   const uint32_t span = lane_span(t);
-  const int v = t->opt_lane_taper ? t->opt_lane_taper : kTaperDefault;
-  if (span > 1 || v == 1 || kLaneTile <= 256) return tilemap_uniform(n_bytes, (uint32_t)kLaneTile * span);
-  const uint64_t slots = lane_slots(t, ordered);
+  const bool wide = !lane_narrow_tiles(t, ordered, n_bytes);
+  const uint32_t tile = wide ? (uint32_t)kLaneTile : (uint32_t)kNarrowTile;
+  const int v = t->opt_lane_taper ? t->opt_lane_taper : wide ? kTaperDefault : kNarrowTaperDefault;
+  if (span > 1 || v == 1 || tile <= 256) return tilemap_uniform(n_bytes, tile * span);
+  const uint64_t slots = lane_slots(t, ordered, lane_narrow(t, ordered, n_bytes));
   // The floor of the library's own choice: a text under two chip-fulls of full tiles keeps tiles of one size (2.5 MB measured
   // 2.2 us slower tapered, profiles/lane_taper.txt section 3).  An explicit SWT_OPT_LANE_TAPER tapers whatever the size.
-  if (!t->opt_lane_taper && n_bytes < 2ull * (uint64_t)kLaneTile * slots) return tilemap_uniform(n_bytes, (uint32_t)kLaneTile);
-  return tilemap_taper(n_bytes, slots, (uint32_t)(v & ~256), kTaperSizes, (v & 256) ? 3 : 4);
+  // The narrow kernel's tiles taper wherever the library's own choice runs it, from one chip-full of kLaneTile-byte tiles (its
+  // floor, lane_narrow): tapered it gains 6 - 10 us on the parent at every size from 2.5 to 7 MB, in tiles of one size it lost 5 us
+  // at 5.6 MB (profiles/lane_narrow.txt section 5).  Below that floor (SWT_OPT_LANE_NARROW = 2) its tiles are of one size.
+  const uint64_t taper_floor = wide ? 2ull * (uint64_t)tile * slots : (uint64_t)kLaneTile * lane_slots(t, false, false);
+  if (!t->opt_lane_taper && n_bytes < taper_floor) return tilemap_uniform(n_bytes, tile);
+  return tilemap_taper(n_bytes, slots, (uint32_t)(v & ~256), wide ? kTaperSizes : kNarrowTaperSizes, (v & 256) ? 3 : 4);
 }
 
 // diagnostics (not part of include/swt.h): the tile map a running-text call of n_bytes would get under the handle's options --

@@ -1,11 +1,12 @@
 """the tapering tiles of the FastBPE direct path (SWT_OPT_LANE_TAPER, csrc/swt_bpe_encode.hip: lane_map) against tiles of one size.
 
-usage: python tools/gpu_lane_taper.py sweep [--passes P] [--settings 1,4,8,...]
+usage: python tools/gpu_lane_taper.py sweep [--passes P] [--settings 1,4,8,...] [--narrow V]
            bench.py's timed region of --workload bpe_encode (200 steps after 20, S85k resident in HBM, one perf_counter bracket
            round the steps) on S85k-open and S85k-lex for every setting in turn, P passes; beside it the lane kernel's own time
            from HIP events (swt_profile_read).  A setting is a value of SWT_OPT_LANE_TAPER: 1 = tiles of one size, v = 8 c, v + 256
-           = 192 bytes as the smallest size.
-       python tools/gpu_lane_taper.py midsize [--taper V] [--calls N]
+           = 192 bytes as the smallest size.  --narrow V sets SWT_OPT_LANE_NARROW first (only where the library has the option):
+           2 = the settings count from the narrow kernel's 512-byte tile, 1 = the wide kernel; setting 0 is the library's own choice.
+       python tools/gpu_lane_taper.py midsize [--taper V] [--calls N] [--sizes KB,KB,...]
            one call at a time (launch, synchronize) on the first 64 KB, 256 KB, 1 MB and 2.5 MB of S85k-open, the median of N
            calls; without --taper the handle is left as the library made it, so the same file measures a parent's tree when it
            is run from there (cd parent && python <this file> midsize)."""
@@ -24,6 +25,8 @@ ap.add_argument("mode", choices=["sweep", "midsize"])
 ap.add_argument("--passes", type=int, default=2)
 ap.add_argument("--settings", default="1,4,6,8,12,260,262,264,268")
 ap.add_argument("--taper", type=int, default=None)
+ap.add_argument("--narrow", type=int, default=None)
+ap.add_argument("--sizes", default="64,256,1024,2560", help="midsize: the sizes in KB")
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=20)
@@ -34,6 +37,8 @@ bpe = tokenizers.FastBPE()
 bpe.merges_list = list(synth.pretrained_merges()[:8000])
 bpe._build_table()
 h = bpe._table
+if args.narrow is not None:
+    h.set_option(7, args.narrow)  # SWT_OPT_LANE_NARROW
 stream = torch.cuda.current_stream().cuda_stream
 
 
@@ -57,7 +62,7 @@ class Corpus:
 
 
 def label(v):
-    return "uniform" if v == 1 else "c=%.2f min %d" % ((v & ~256) / 8.0, 192 if v & 256 else 128)
+    return "uniform" if v == 1 else "library" if v == 0 else "c=%.2f min %d" % ((v & ~256) / 8.0, 192 if v & 256 else 128)
 
 
 if args.mode == "sweep":
@@ -91,7 +96,7 @@ else:
     sents = synth.s85k_open()
     if args.taper is not None:
         h.set_option(N.OPT_LANE_TAPER, args.taper)
-    for size in (64 << 10, 256 << 10, 1 << 20, 5 << 19):
+    for size in [int(x) << 10 for x in args.sizes.split(",")]:
         take, total = [], 0
         for s in sents:
             take.append(s)
