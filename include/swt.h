@@ -703,6 +703,59 @@ int swt_mlm_mask(const void *ids, uint64_t rows, uint32_t width, const uint8_t *
 int swt_mlm_mask_dev(const void *d_ids, uint64_t rows, uint32_t width, const uint8_t *d_cls_tab, const uint32_t *d_rand_ids, uint32_t n_rand,
                      const swt_mlm_spec *spec, void *d_out_ids, void *d_out_labels, uint8_t *d_out_selected, uint64_t *d_info, void *stream);
 int swt_mlm_capacity(uint32_t *cols_per_step, uint32_t *rows_per_wave_max);
+
+/* ------------------------------------------------------------------------------------------------
+ * Decoding: finished rows ids[rows, width] of dense ids (int32, int64 with SWT_DECODE_IDS64; C-contiguous; any input_ids of the
+ * batch calls above, a model's output) back to text, as the reference's recover_sentence (utils.py:141-154) spells the rows'
+ * tokens.  tests/decode_cases.py holds these semantics, tests/golden/recover_sentence.json pins them to the reference's strings,
+ * and the kernel equals the model byte for byte.
+ *
+ * The vocabulary is tok_bytes (the UTF-8 of all tokens in dense-id order), tok_off[n_tok + 1] (uint32) and tok_flags[n_tok]
+ * (uint8), the vocabulary's bytes tok_off[n_tok] below 2^23 (a step's bytes are summed in 32 bits).  The bits of tok_flags:
+ * GLUE 1 ('##' and at least one more code point), NO_SPACE_BEFORE 2 (the first code point is one of . , ) ] \ U+2019 - ' /),
+ * NO_SPACE_AFTER 4 (the last is one of ( [ \ U+2019 - ' /), SPECIAL 8 ([PAD], [CLS], [SEP], [MASK]; not [UNK], which stands for a
+ * word of the text), BAD 16 (empty, or holding a code point Python's \s matches: the reference's regular expressions would act
+ * inside such a token, and its spelling is not guessed).
+ *
+ * A column is KEPT when mask (uint8[rows, width], as out_mask of swt_batch_rows; may be NULL) is nonzero there and, with
+ * SWT_DECODE_SKIP_SPECIAL, its token is not SPECIAL.  Nothing is looked up for a column whose mask is zero.  A kept column whose
+ * id is negative or >= n_tok sets bit 0 of status[row], one whose token is BAD sets bit 1; such a column WRITES nothing and is
+ * no neighbour of the columns that do.  Of the writing columns of a row, in order: the first writes its token as it is (a
+ * leading '##' stays); a GLUE token after another writes its bytes without the first two and no space; otherwise a token that is
+ * NO_SPACE_BEFORE, or follows one that is NO_SPACE_AFTER, writes its bytes; every other writes one space (0x20) and its bytes.
+ * There is no terminator.
+ *
+ * swt_decode_plan: text_off[rows + 1] (uint64), the exclusive sum of the rows' byte lengths; status[rows] (uint8);
+ * info[3]: total bytes, rows with a nonzero status, kept columns (those that set a status bit among them).
+ * swt_decode_rows: row r's bytes to out_text[text_off[r] .. text_off[r + 1]); SWT_ERR_CAPACITY when text_cap is below the total.
+ *
+ * SWT_ERR_INVALID, swt_last_error naming the argument: a NULL pointer other than mask; width == 0 with rows > 0; 2^32 rows or
+ * more; 2^31 columns or more; an unknown flag; n_tok == 0; in the host forms a tok_off that decreases or ends at 2^23 or more,
+ * and for swt_decode_rows a text_off that is not the plan of these ids.
+ * rows == 0 succeeds: text_off[0] = 0, info zeroed, nothing written by swt_decode_rows.  The host forms check everything before
+ * anything touches the device.  The `_dev` forms take device pointers aligned to their element type, enqueue on the stream and do
+ * not synchronise.  swt_decode_rows_dev recomputes every length from ids: it writes nothing at or beyond text_cap and nothing
+ * outside [text_off[r], text_off[r + 1]) for row r, whatever ids and text_off hold.  swt_decode_plan_dev scans in the workspace of
+ * swt_batch_plan_dev and keeps its workgroups' counts beside it: no two plans of any kind at once on different streams.
+ * swt_decode_capacity: the columns of a row one step covers, and the rows of one scan group (csrc/swt_decode.hip). */
+#define SWT_DECODE_SKIP_SPECIAL 1u
+#define SWT_DECODE_IDS64 4u /* the value of SWT_BATCH_IDS64 */
+#define SWT_TOK_GLUE 1u
+#define SWT_TOK_NO_SPACE_BEFORE 2u
+#define SWT_TOK_NO_SPACE_AFTER 4u
+#define SWT_TOK_SPECIAL 8u
+#define SWT_TOK_BAD 16u
+int swt_decode_plan(const void *ids, const uint8_t *mask, uint64_t rows, uint32_t width, const uint32_t *tok_off, const uint8_t *tok_flags,
+                    uint32_t n_tok, uint32_t flags, uint64_t *text_off, uint8_t *status, uint64_t *info);
+int swt_decode_plan_dev(const void *d_ids, const uint8_t *d_mask, uint64_t rows, uint32_t width, const uint32_t *d_tok_off,
+                        const uint8_t *d_tok_flags, uint32_t n_tok, uint32_t flags, uint64_t *d_text_off, uint8_t *d_status, uint64_t *d_info,
+                        void *stream);
+int swt_decode_rows(const void *ids, const uint8_t *mask, uint64_t rows, uint32_t width, const uint8_t *tok_bytes, const uint32_t *tok_off,
+                    const uint8_t *tok_flags, uint32_t n_tok, uint32_t flags, const uint64_t *text_off, uint8_t *out_text, uint64_t text_cap);
+int swt_decode_rows_dev(const void *d_ids, const uint8_t *d_mask, uint64_t rows, uint32_t width, const uint8_t *d_tok_bytes,
+                        const uint32_t *d_tok_off, const uint8_t *d_tok_flags, uint32_t n_tok, uint32_t flags, const uint64_t *d_text_off,
+                        uint8_t *d_out_text, uint64_t text_cap, void *stream);
+int swt_decode_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
 #ifdef __cplusplus
 }
 #endif

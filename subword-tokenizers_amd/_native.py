@@ -163,6 +163,14 @@ SIGNATURES = {
     "swt_mlm_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, msp, C.c_void_p, C.c_void_p, u8p, u64p]),
     "swt_mlm_mask_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, msp] + [C.c_void_p] * 5),
     "swt_mlm_capacity": (C.c_int, [u32p, u32p]),
+    "swt_decode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
+    "swt_decode_plan_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] +
+                            [C.c_void_p] * 4),
+    "swt_decode_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_uint64]),
+    "swt_decode_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "swt_decode_capacity": (C.c_int, [u32p, u32p]),
 }
 
 
@@ -777,6 +785,62 @@ def mlm_mask(ids, cls_tab, rand_ids, spec, selected=True, info=True):
                              C.byref(spec), at(out["input_ids"], C.c_void_p), at(out["labels"], C.c_void_p), at(out["selected"], u8p),
                              at(out["info"], u64p)))
     return out
+
+
+DECODE_SKIP_SPECIAL, DECODE_IDS64 = 1, 4  # the flags of swt_decode_*
+TOK_GLUE, TOK_NO_SPACE_BEFORE, TOK_NO_SPACE_AFTER, TOK_SPECIAL, TOK_BAD = 1, 2, 4, 8, 16  # the bits of tok_flags
+DECODE_BAD_ID, DECODE_BAD_TOKEN = 1, 2  # the bits of a row's status
+
+
+def decode_capacity():
+    """-> (cols_per_step, scan_group): the columns of a row one step of the decode kernel covers, the rows of one scan group of
+    its plan (csrc/swt_decode.hip)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_decode_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _decode_args(ids, mask, tok_off, tok_flags, n_tok):
+    if not isinstance(ids, np.ndarray) or ids.dtype not in (np.int32, np.int64) or ids.ndim != 2 or not ids.flags.c_contiguous:
+        raise TypeError("ids: a 2-D C-contiguous array of int32 or int64")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mask.shape != ids.shape:
+            raise ValueError("mask has the shape of ids")
+    tok_off, tok_flags = np.ascontiguousarray(tok_off, dtype=np.uint32), np.ascontiguousarray(tok_flags, dtype=np.uint8)
+    if tok_off.size < n_tok + 1 or tok_flags.size < n_tok:
+        raise ValueError("tok_off holds n_tok + 1 entries, tok_flags n_tok")
+    return mask, tok_off, tok_flags
+
+
+def decode_plan(ids, mask, tok_off, tok_flags, n_tok, skip_special=True):
+    """Rows of dense ids (a 2-D C-contiguous int32 or int64 array) and their mask (uint8 of the same shape, or None) planned for
+    decoding (swt_decode_plan) -> (text_off uint64[rows + 1], status uint8[rows], info uint64[3]: total bytes, rows with a
+    nonzero status, kept columns)"""
+    mask, tok_off, tok_flags = _decode_args(ids, mask, tok_off, tok_flags, n_tok)
+    rows, width = ids.shape
+    flags = (DECODE_SKIP_SPECIAL if skip_special else 0) | (DECODE_IDS64 if ids.dtype == np.int64 else 0)
+    text_off, status, info = np.zeros(rows + 1, dtype=np.uint64), np.zeros(max(rows, 1), dtype=np.uint8), np.zeros(3, dtype=np.uint64)
+    one = np.zeros(4, dtype=np.uint64)  # an array of no element still needs an address
+    check(lib().swt_decode_plan(_vp(ids) or _vp(one), _vp(mask), rows, width, _vp(tok_off), _vp(tok_flags), n_tok, flags, _vp(text_off),
+                                _vp(status), _vp(info)))
+    return text_off, status[:rows], info
+
+
+def decode_rows(ids, mask, tok_bytes, tok_off, tok_flags, n_tok, text_off, skip_special=True, text_cap=None):
+    """The bytes of a plan (swt_decode_rows) -> text uint8[text_off[-1]]; text_cap, for the tests, in place of the plan's total"""
+    mask, tok_off, tok_flags = _decode_args(ids, mask, tok_off, tok_flags, n_tok)
+    tok_bytes, text_off = np.ascontiguousarray(tok_bytes, dtype=np.uint8), np.ascontiguousarray(text_off, dtype=np.uint64)
+    rows, width = ids.shape
+    if text_off.size != rows + 1:
+        raise ValueError("text_off holds rows + 1 entries")
+    flags = (DECODE_SKIP_SPECIAL if skip_special else 0) | (DECODE_IDS64 if ids.dtype == np.int64 else 0)
+    cap = int(text_off[-1]) if text_cap is None else int(text_cap)
+    text = np.zeros(cap, dtype=np.uint8)
+    one = np.zeros(4, dtype=np.uint64)
+    check(lib().swt_decode_rows(_vp(ids) or _vp(one), _vp(mask), rows, width, _vp(tok_bytes) or _vp(one), _vp(tok_off), _vp(tok_flags), n_tok,
+                                flags, _vp(text_off), _vp(text) or _vp(one), cap))
+    return text
 
 
 def bpe_length_table(strings):

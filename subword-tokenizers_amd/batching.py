@@ -4,8 +4,10 @@ A tokenizer class gives its `Vocabulary` (`_batch_vocabulary`: specials and toke
 encoder's ids to dense ids) and its encode calls (`encode_ids_batch`, `_batch_encode_spans`, `_batch_encode_dev`); `encode_batch`
 pads, truncates or windows the rows on the device -- through the host forms of the C ABI into NumPy arrays, or with
 `device=True` on torch tensors without the ids ever leaving the device.  `mask_tokens` masks such rows for the masked-LM
-objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident."""
+objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident.  `decode_batch`
+spells rows of dense ids back as text (swt_decode_plan / swt_decode_rows)."""
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -30,6 +32,8 @@ class Vocabulary:
         self.mask_id = index.get(MASK, len(tokens))  # one past the end where the vocabulary has no "[MASK]": no dense id moves
         self._cls_tab = self._rand_ids = None
         self.d_mlm = None  # (device, cls_tab, rand_ids) as torch tensors, made by the first device call of mask_tokens
+        self._decode = None
+        self.d_decode = None  # (device, tok_bytes, tok_off, tok_flags) as torch tensors, made by the first device call of decode_batch
 
     @property
     def cls_tab(self):
@@ -46,6 +50,41 @@ class Vocabulary:
         if self._rand_ids is None:
             self._rand_ids = np.flatnonzero(self.cls_tab < 2).astype(np.uint32)
         return self._rand_ids
+
+    @property
+    def decode_tables(self):
+        """(tok_bytes uint8, tok_off uint32[n + 1], tok_flags uint8[n], n): the vocabulary of swt_decode_* (include/swt.h), with
+        "[MASK]" appended where mask_id is one past the end"""
+        if self._decode is None:
+            tokens = list(self.tokens) + ([MASK] if self.mask_id == len(self.tokens) else [])
+            raw = [t.encode("utf-8") for t in tokens]
+            off = np.zeros(len(raw) + 1, dtype=np.uint32)
+            total = sum(map(len, raw))
+            if total >= 1 << 23:
+                raise ValueError("decode: the vocabulary's tokens take %d bytes, swt_decode_* takes fewer than 2^23" % total)
+            off[1:] = np.cumsum([len(b) for b in raw], dtype=np.uint64)
+            flags = np.fromiter((_decode_flags(t) for t in tokens), dtype=np.uint8, count=len(tokens))
+            self._decode = (np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8), off, flags, len(tokens))
+        return self._decode
+
+
+_NO_SPACE_BEFORE, _NO_SPACE_AFTER = frozenset(".,)]\\’-'/"), frozenset("([\\’-'/")  # utils.py:150, 152
+_DECODE_SKIPPED = frozenset(("[PAD]", "[CLS]", "[SEP]", MASK))  # [UNK] stands for a word of the text: it is spelled
+_PY_SPACE = re.compile(r"\s")
+
+
+def _decode_flags(tok):
+    """the tok_flags byte of a token string (include/swt.h)"""
+    f = N.TOK_SPECIAL if tok in _DECODE_SKIPPED else 0
+    if not tok or _PY_SPACE.search(tok):
+        return f | N.TOK_BAD  # the reference's regular expressions would act inside it: not spelled by the join rule
+    if len(tok) >= 3 and tok.startswith("##"):
+        f |= N.TOK_GLUE
+    if tok[0] in _NO_SPACE_BEFORE:
+        f |= N.TOK_NO_SPACE_BEFORE
+    if tok[-1] in _NO_SPACE_AFTER:
+        f |= N.TOK_NO_SPACE_AFTER
+    return f
 
 
 def bpe_vocabulary(merges, syms):
@@ -479,3 +518,78 @@ def mask_tokens(tok, input_ids, probability=0.15, whole_word=True, seed=0, epoch
         res["selected"] = out["selected"]
     res.update((name, int(x)) for name, x in zip(MLM_COUNTS, info))
     return res
+
+
+def _raise_decode_status(status, row):
+    """the ValueError of a plan whose info counts reported rows: the first such row and its cause"""
+    causes = [text for bit, text in ((N.DECODE_BAD_ID, "an id outside the vocabulary on a kept column"),
+                                     (N.DECODE_BAD_TOKEN, "a token that is empty or holds whitespace, which recover_sentence does not spell"))
+              if status & bit]
+    raise ValueError("decode_batch: row %d holds %s" % (row, " and ".join(causes)))
+
+
+def decode_batch_bytes(tok, input_ids, attention_mask=None, skip_special_tokens=True):
+    """SubwordTokenizer.decode_batch_bytes: a NumPy array through swt_decode_plan / swt_decode_rows, a torch tensor on the GPU
+    through their `_dev` forms on the current device and stream, with `info` the only read-back."""
+    if isinstance(input_ids, np.ndarray):
+        if input_ids.dtype not in (np.int32, np.int64) or input_ids.ndim != 2 or not input_ids.flags.c_contiguous:
+            raise TypeError("input_ids: a 2-D C-contiguous array of int32 or int64")
+        voc = tok._batch_vocabulary()
+        tok_bytes, tok_off, tok_flags, n_tok = voc.decode_tables
+        mask = attention_mask
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.shape != input_ids.shape:
+                raise ValueError("attention_mask has the shape of input_ids")
+            mask = np.ascontiguousarray(mask if mask.dtype == np.uint8 else mask != 0, dtype=np.uint8)
+        text_off, status, info = N.decode_plan(input_ids, mask, tok_off, tok_flags, n_tok, skip_special_tokens)
+        if info[1]:
+            row = int(np.flatnonzero(status)[0])
+            _raise_decode_status(int(status[row]), row)
+        return N.decode_rows(input_ids, mask, tok_bytes, tok_off, tok_flags, n_tok, text_off, skip_special_tokens), text_off
+    import torch
+    if not isinstance(input_ids, torch.Tensor) or not input_ids.is_cuda or input_ids.dtype not in (torch.int32, torch.int64) \
+            or input_ids.dim() != 2 or not input_ids.is_contiguous():
+        raise TypeError("input_ids: a 2-D C-contiguous NumPy array, or torch tensor on the GPU, of int32 or int64")
+    dev = input_ids.device
+    voc = tok._batch_vocabulary()
+    tok_bytes, tok_off, tok_flags, n_tok = voc.decode_tables
+    flags = (N.DECODE_SKIP_SPECIAL if skip_special_tokens else 0) | (N.DECODE_IDS64 if input_ids.dtype == torch.int64 else 0)
+    with torch.cuda.device(dev):
+        mask = attention_mask
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.device != dev or mask.shape != input_ids.shape:
+                raise TypeError("attention_mask: a torch tensor on the device of input_ids and of its shape")
+            mask = (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
+        if voc.d_decode is None or voc.d_decode[0] != dev:
+            voc.d_decode = (dev, torch.from_numpy(tok_bytes.copy()).to(dev), torch.from_numpy(tok_off.view(np.int32)).to(dev),
+                            torch.from_numpy(tok_flags).to(dev))
+        _, d_bytes, d_off, d_flags = voc.d_decode
+        rows, width = input_ids.shape
+        stream = torch.cuda.current_stream().cuda_stream
+        d_text_off = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        d_status = torch.empty(max(rows, 1), dtype=torch.uint8, device=dev)
+        d_info = torch.empty(3, dtype=torch.int64, device=dev)
+        head = (input_ids.data_ptr() or d_info.data_ptr(), mask.data_ptr() or d_info.data_ptr() if mask is not None else None, rows, width)
+        lib = N.lib()
+        N.check(lib.swt_decode_plan_dev(*head, d_off.data_ptr(), d_flags.data_ptr(), n_tok, flags, d_text_off.data_ptr(), d_status.data_ptr(),
+                                        d_info.data_ptr(), stream))
+        info = d_info.cpu().numpy()  # the one read-back: the size of the text, and whether a row is reported
+        if info[1]:
+            status = d_status[:rows].cpu().numpy()
+            row = int(np.flatnonzero(status)[0])
+            _raise_decode_status(int(status[row]), row)
+        total = int(info[0])
+        text = torch.empty(total, dtype=torch.uint8, device=dev)
+        if total:
+            N.check(lib.swt_decode_rows_dev(*head, d_bytes.data_ptr(), d_off.data_ptr(), d_flags.data_ptr(), n_tok, flags, d_text_off.data_ptr(),
+                                            text.data_ptr(), total, stream))
+    return text, d_text_off.view(torch.uint64)
+
+
+def decode_batch(tok, input_ids, attention_mask=None, skip_special_tokens=True):
+    text, off = decode_batch_bytes(tok, input_ids, attention_mask, skip_special_tokens)
+    if not isinstance(text, np.ndarray):
+        text, off = text.cpu().numpy(), off.cpu().numpy()
+    raw, off = text.tobytes(), off.astype(np.int64).tolist()
+    return [raw[a:b].decode("utf-8") for a, b in zip(off[:-1], off[1:])]

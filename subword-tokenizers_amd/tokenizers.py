@@ -148,6 +148,37 @@ class SubwordTokenizer:
         [0, 1], mask_share + random_share > 1, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
         return batching.mask_tokens(self, input_ids, probability, whole_word, seed, epoch, mask_share, random_share, return_selected)
 
+    def decode_batch_bytes(self, input_ids, attention_mask=None, skip_special_tokens: bool = True):
+        """Rows of dense ids (any "input_ids" of encode_batch or mask_tokens, a model's output) back to text on the device
+        (swt_decode_plan / swt_decode_rows), as the reference's recover_sentence (utils.py:141-154) spells the rows' tokens: '##'
+        tokens glued to what precedes them, no space before . , ) ] \\ ’ - ' / nor after ( [ \\ ’ - ' /, one space elsewhere.
+        A column is kept where attention_mask (if given) is nonzero and, with skip_special_tokens, its id is not [PAD], [CLS],
+        [SEP] or mask_id(); [UNK] stands for a word of the text and is spelled "[UNK]" (WordPiece's "['UNK']" has the same
+        dense id and comes back as "[UNK]" too).  Like the reference this does not restore the text: whitespace and case are gone.
+        input_ids: a 2-D C-contiguous int32 or int64 NumPy array, or such a torch tensor on the GPU (decoded on the current
+        stream, the ids never leaving the device; the byte count is the one read-back); anything else raises TypeError.
+        -> (text uint8, offsets uint64[rows + 1]): row r is text[offsets[r]:offsets[r + 1]], UTF-8, no terminator.
+        ValueError, naming the first such row: a kept id outside the vocabulary, or a kept token that is empty or holds
+        whitespace (its spelling under the reference's regular expressions is not guessed)."""
+        return batching.decode_batch_bytes(self, input_ids, attention_mask, skip_special_tokens)
+
+    def decode_batch(self, input_ids, attention_mask=None, skip_special_tokens: bool = True) -> List[str]:
+        """decode_batch_bytes as one str per row"""
+        return batching.decode_batch(self, input_ids, attention_mask, skip_special_tokens)
+
+    def decode(self, ids, skip_special_tokens: bool = True) -> str:
+        """one sequence of dense ids (a list, a 1-D array or tensor) -> its text, as decode_batch"""
+        if not hasattr(ids, "dim"):  # no torch tensor
+            ids = np.asarray(ids)
+            if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+                raise TypeError("ids: one sequence of integers")
+            ids = np.ascontiguousarray(ids if ids.dtype in (np.int32, np.int64) else ids.astype(np.int64))
+        elif ids.dim() != 1:
+            raise TypeError("ids: one sequence of integers")
+        if len(ids) == 0:
+            return ""
+        return batching.decode_batch(self, ids.reshape(1, -1), None, skip_special_tokens)[0]
+
     def _batch_encode_spans(self, texts):
         return self.encode_spans_batch(texts)
 
