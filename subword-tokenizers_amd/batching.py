@@ -6,6 +6,7 @@ pads, truncates or windows the rows on the device -- through the host forms of t
 `device=True` on torch tensors without the ids ever leaving the device.  `mask_tokens` masks such rows for the masked-LM
 objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident.  `decode_batch`
 spells rows of dense ids back as text (swt_decode_plan / swt_decode_rows)."""
+import collections
 import ctypes as C
 import re
 
@@ -318,33 +319,49 @@ def _pack_host(tok, voc, texts, spec, mode):
     return _pack_result(out, slot.astype(np.int64), tok_off.astype(np.int64), spec, mode, out["info"], plan_info, np)
 
 
-def _pack_device(tok, voc, texts, spec, mode):
-    """as _encode_device: one upload of the texts, one `_dev` encode, the packing plan and rows on torch-owned buffers on the
-    current stream; the plan's info (for the rows to allocate) and the rows' info are all that comes back"""
+Encoded = collections.namedtuple("Encoded", "stream empty ids tok_off spans word checks")
+
+
+def _encode_on_device(tok, voc, texts, offsets=False):
+    """The front half of the device paths, on the current device and stream: ONE upload of the lowercased texts and one `_dev`
+    encode (with offsets its span form) into torch-owned buffers, and voc.d_cmap on that device.  -> Encoded: empty(shape, dtype,
+    wanted=True) allocates on the device; spans and word are None without offsets; checks: the (statuses, complain) pairs of the
+    span form, for the caller to read"""
     import torch
-    n_rows, width = len(texts), int(spec.width)
     dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.current_stream().cuda_stream
-    lib, check = N.lib(), N.check
-    idt = torch.int64 if spec.flags & N.BATCH_IDS64 else torch.int32
 
     def empty(shape, dtype, wanted=True):
         return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
 
     text, off = N.pack_utf8([t.lower() for t in texts])
-    n_bytes = int(text.size)
-    d_tok_off = empty(n_rows + 1, torch.int64)
-    d_ids = empty(n_bytes + 64, torch.int32)
+    n_bytes, n_sent = int(text.size), len(texts)
+    d_ids, d_tok_off = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64)
+    d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, offsets), empty(n_bytes + 64, torch.int32, offsets)
+    checks = []
     if n_bytes == 0:
-        d_tok_off.zero_()
+        d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
     else:
         d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
         d_off = torch.from_numpy(off.view(np.int64)).to(dev)
         d_ntok = torch.zeros(1, dtype=torch.int64, device=dev)
-        tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_rows, d_ids.data_ptr(), d_tok_off.data_ptr(), d_ntok.data_ptr(),
-                              None, None, stream, empty)
+        checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None,
+                                       stream, empty)
     if voc.d_cmap is None or voc.d_cmap.device != dev:
         voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
+    return Encoded(stream, empty, d_ids, d_tok_off, d_spans, d_word, checks)
+
+
+def _pack_device(tok, voc, texts, spec, mode):
+    """as _encode_device: one upload of the texts, one `_dev` encode, the packing plan and rows on torch-owned buffers on the
+    current stream; the plan's info (for the rows to allocate) and the rows' info are all that comes back"""
+    import torch
+    n_rows, width = len(texts), int(spec.width)
+    lib, check = N.lib(), N.check
+    idt = torch.int64 if spec.flags & N.BATCH_IDS64 else torch.int32
+    enc = _encode_on_device(tok, voc, texts)
+    stream, empty, d_ids, d_tok_off = enc.stream, enc.empty, enc.ids, enc.tok_off
     d_slot, d_first, d_info = empty(n_rows + 1, torch.int64), empty(n_rows + 1, torch.int64), empty(8, torch.int64)
     check(lib.swt_pack_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(spec), mode, d_slot.data_ptr(), d_first.data_ptr(), d_info.data_ptr(),
                                 stream))
@@ -381,17 +398,12 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
     swt_batch_rows_dev), else (truncation, token_types, special_mask) (swt_batch_pair_plan_dev, swt_batch_pair_rows_dev).
     -> the arrays of _native.batch_rows / batch_pair_rows as tensors, an output nobody asked for None, and "info"."""
     import torch
-    text, off = N.pack_utf8([t.lower() for t in texts])
-    n_bytes, n_sent = int(text.size), len(texts)
     truncation, token_types, special_mask = pair or (None, False, False)
     n_special, n_info = ((3 if pair else 2) if add_special_tokens else 0), (5 if pair else 3)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stream = torch.cuda.current_stream().cuda_stream
     lib, check = N.lib(), N.check
     idt = torch.int64 if int64 else torch.int32
-
-    def empty(shape, dtype, wanted=True):
-        return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
+    stream, empty, d_ids, d_tok_off, d_spans, d_word, checks = _encode_on_device(tok, voc, texts, offsets)
+    p_spans, p_word = (d_spans.data_ptr(), d_word.data_ptr()) if offsets else (None, None)
 
     def outputs(rows, width):
         out = {"input_ids": empty((rows, width), idt), "attention_mask": empty((rows, width), torch.uint8),
@@ -405,25 +417,12 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
 
     if n_rows == 0:
         return dict(outputs(0, 0), info=[0] * n_info)
-    d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
-    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
-    d_ids, d_tok_off, d_ntok = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64), torch.zeros(1, dtype=torch.int64, device=dev)
-    d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, offsets), empty(n_bytes + 64, torch.int32, offsets)
-    p_spans, p_word = (d_spans.data_ptr(), d_word.data_ptr()) if offsets else (None, None)
-    checks = []
-    if n_bytes == 0:
-        d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
-    else:
-        checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
-                                       d_ntok.data_ptr(), p_spans, p_word, stream, empty)
     if offsets:  # as the host span calls, which raise; the ids alone come back with an empty row for such a text
         for d_flags, complain in checks:
-            status = d_flags[:n_sent].cpu().numpy()
+            status = d_flags[:len(texts)].cpu().numpy()
             bad = np.flatnonzero(status)
             if bad.size:
                 complain(int(status[int(bad[0])]), int(bad[0]), texts[int(bad[0])])
-    if voc.d_cmap is None or voc.d_cmap.device != dev:
-        voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
     d_row_base, d_info = empty(n_rows + 1, torch.int64), empty(8, torch.int64)
     p_off = (d_tok_off.data_ptr(),)
     if pair:

@@ -8,17 +8,17 @@
 // single kernels hold nothing of the pairs, neither a load nor a register (the compiler report of DESIGN.md 4.10).
 //
 // plan   count_kernel<pair> leaves k(r) in row_base[r] and the longest row (pairs: the largest na + nb) in info[1], one
-//        atomicMax per wavefront; pairs also get status[r] and the refused rows in info[3].  launch_scan_u64 (swt_tile.h) scans
-//        row_base in groups of kBtScanGroup, batch_base_kernel adds the group bases.
-// rows   rows_kernel<Layout>: a group of g lanes per SOURCE row, g the power of two that covers the width at four columns a
-//        lane, so a wavefront holds 64 / g rows at a time and walks kBtIter such sets.  A group walks its row's windows: an
-//        output row is found from its source row (row_base[r] + w), never searched for.  A column's content follows from its
-//        position p in the row: the layout says whether p is a special or which token it is -- one id load and one map load per
-//        token column.  A lane's four columns are one 16-byte store of ids (two with 64-bit ids), one dword of mask, two 16-byte
-//        stores of spans; pairs store types as ids are, and special and sequence bytes as one dword each; element by element
-//        where the width is no multiple of four or an output is not aligned.  The counters of info are folded over the
-//        wavefront, then the workgroup (64 bytes of LDS, 128 for pairs), and added once per workgroup.  No scratch; no other
-//        atomics.
+//        atomicMax per wavefront; pairs also get status[r] and the refused rows in info[3].  launch_scan_bases makes row_base of
+//        the counts.
+// rows   rows_kernel<Layout>: a group of lanes per SOURCE row (swt_rows.h), a wavefront walking kBtIter sets of rows.  A group
+//        walks its row's windows: an output row is found from its source row (row_base[r] + w), never searched for.  A column's
+//        content follows from its position p in the row: the layout says whether p is a special or which token it is -- one id
+//        load and one map load per token column.  A lane's four columns are one 16-byte store of ids (two with 64-bit ids), one
+//        dword of mask, two 16-byte stores of spans; pairs store types as ids are, and special and sequence bytes as one dword
+//        each; element by element where the width is no multiple of four or an output is not aligned.  The counters of info are
+//        added once per workgroup.  No scratch; no other atomics.
+//
+// Also here, for every file of the family (declared in swt_batch.h): the scan workspace, launch_scan_bases, launch_counts_sum.
 #include "swt_batch.h"
 
 namespace swt {
@@ -209,11 +209,7 @@ __global__ __launch_bounds__(kBtThreads) void rows_kernel(RowsArgs A) {
             special &= ~(1u << (8 * j));
             seq &= ~((ty[j] ? 0xFEu : 0xFFu) << (8 * j));
           }
-          const uint32_t raw = A.ids[t], s = raw & 0x7FFFFFFFu;
-          uint32_t d = SWT_BATCH_NONE;
-          if (s < A.n_map) d = A.map ? A.map[(uint64_t)s + ((A.flagged && (raw >> 31)) ? (uint64_t)A.n_map : 0ull)] : s;
-          if (d == SWT_BATCH_NONE) { d = A.unk_id; n_unk++; }
-          id[j] = d;
+          id[j] = bt_dense_id(A.ids[t], A.map, A.n_map, A.flagged, A.unk_id, n_unk);
           if (A.spans) { sa[j] = A.spans[2 * t]; sb[j] = A.spans[2 * t + 1]; }
           if (A.word) wd[j] = A.word[t];
         }
@@ -252,6 +248,8 @@ __global__ __launch_bounds__(kBtThreads) void rows_kernel(RowsArgs A) {
   }
   if (!A.info) return;  // uniform over the workgroup
   // info: single rows [1] lost, [2] unknowns; pairs [1] the largest na + nb, [2] unknowns, [3] refused, [4] lost
+  // rows_kernel's own fold, the pairs' maximum in the same pass: with bt_fold_counts rows of width 512 measured 1.2 - 1.5 % slower
+  // 
   for (int d = 32; d; d >>= 1) {
     n_unk += __shfl_xor(n_unk, d, 64);
     n_lost += __shfl_xor(n_lost, d, 64);
@@ -323,17 +321,39 @@ __global__ __launch_bounds__(kBtThreads) void count_kernel(const uint64_t *__res
   }
 }
 
-// Plan, last pass: the group bases on top of the scan inside the groups; the total closes the array.
-__global__ __launch_bounds__(kBtThreads) void batch_base_kernel(const unsigned long long *__restrict__ local,
-                                                                const unsigned long long *__restrict__ blk_base, uint64_t n_rows,
-                                                                unsigned long long *__restrict__ row_base,
-                                                                const unsigned long long *__restrict__ info) {
+// A plan's last pass: the group bases on top of the scan inside the groups; the total closes the array.
+__global__ __launch_bounds__(kBtThreads) void scan_bases_kernel(const unsigned long long *__restrict__ local,
+                                                                const unsigned long long *__restrict__ blk_base, uint64_t n,
+                                                                unsigned long long *__restrict__ out,
+                                                                const unsigned long long *__restrict__ total) {
   const uint64_t i = (uint64_t)blockIdx.x * kBtThreads + threadIdx.x;
-  if (i < n_rows) row_base[i] = blk_base[i / kBtScanGroup] + local[i];
-  else if (i == n_rows) row_base[n_rows] = info[0];
+  if (i < n) out[i] = blk_base[i / kBtScanGroup] + local[i];
+  else if (i == n) out[n] = *total;
+}
+
+// out[k] = the workgroups' counts of counter k = blockIdx.x, summed
+__global__ __launch_bounds__(kBtThreads) void counts_sum_kernel(const unsigned long long *__restrict__ part, uint64_t n_blocks,
+                                                                uint32_t n_counts, unsigned long long *__restrict__ out) {
+  __shared__ unsigned long long waves[kBtWaves][1];
+  unsigned long long s[1] = {0};
+  for (uint64_t i = threadIdx.x; i < n_blocks; i += kBtThreads) s[0] += part[i * n_counts + blockIdx.x];
+  const unsigned long long sum = bt_fold_counts(s, waves);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
 BatchWorkspace g_batch_ws;
+
+void launch_scan_bases(uint64_t n, unsigned long long *d_vals, uint64_t *d_total, hipStream_t st) {
+  unsigned long long *local = g_batch_ws.local.as<unsigned long long>(), *blk = g_batch_ws.blk.as<unsigned long long>();
+  const uint64_t nb = (n + kBtScanGroup - 1) / kBtScanGroup;
+  launch_scan_u64(n, d_vals, local, blk, d_total, st);
+  hipLaunchKernelGGL(scan_bases_kernel, dim3((unsigned)((n + 1 + kBtThreads - 1) / kBtThreads)), dim3(kBtThreads), 0, st, local, blk + 1 + nb, n,
+                     d_vals, reinterpret_cast<const unsigned long long *>(d_total));
+}
+
+void launch_counts_sum(const unsigned long long *d_part, uint64_t n_blocks, uint32_t n_counts, unsigned long long *d_out, hipStream_t st) {
+  hipLaunchKernelGGL(counts_sum_kernel, dim3(n_counts), dim3(kBtThreads), 0, st, d_part, n_blocks, n_counts, d_out);
+}
 
 int BatchWorkspace::reserve(uint64_t n_rows) {
   int rc;
@@ -393,9 +413,7 @@ static int batch_plan_launch(const uint64_t *d_off_a, const uint64_t *d_off_b, u
   const bool windows = (spec->flags & SWT_BATCH_WINDOWS) != 0;
   hipStream_t st = (hipStream_t)stream;
   unsigned long long *rb = reinterpret_cast<unsigned long long *>(d_row_base), *info = reinterpret_cast<unsigned long long *>(d_info);
-  BatchWorkspace &ws = g_batch_ws;
-  const uint64_t nb = (n_rows + kBtScanGroup - 1) / kBtScanGroup;
-  if (windows && n_rows && (rc = ws.reserve(n_rows))) return rc;
+  if (windows && n_rows && (rc = g_batch_ws.reserve(n_rows))) return rc;
   SWT_HIP(hipMemsetAsync(d_info, 0, kPair ? 40 : 16, st));
   if (!n_rows) {
     SWT_HIP(hipMemsetAsync(d_row_base, 0, 8, st));
@@ -404,12 +422,7 @@ static int batch_plan_launch(const uint64_t *d_off_a, const uint64_t *d_off_b, u
   const unsigned grid = (unsigned)((n_rows + 1 + kBtThreads - 1) / kBtThreads);
   hipLaunchKernelGGL(count_kernel<kPair>, dim3(grid), dim3(kBtThreads), 0, st, d_off_a, d_off_b, n_rows, cap, spec->stride, windows ? 1 : 0,
                      strategy, rb, d_status, info);
-  if (windows) {
-    unsigned long long *blk = ws.blk.as<unsigned long long>();
-    launch_scan_u64(n_rows, rb, ws.local.as<unsigned long long>(), blk, d_info, st);
-    hipLaunchKernelGGL(batch_base_kernel, dim3(grid), dim3(kBtThreads), 0, st, ws.local.as<unsigned long long>(), blk + 1 + nb, n_rows, rb,
-                       info);
-  }
+  if (windows) launch_scan_bases(n_rows, rb, d_info, st);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
 }
@@ -429,7 +442,7 @@ static int batch_rows_launch(RowsArgs A, void *stream) {
   if (!A.n_rows || !A.rows_cap) return SWT_OK;
   A.vec = A.width % kBtQuad == 0 && bt_aligned(16, {A.out_ids, A.out_type, A.out_spans, A.out_word}) &&
           bt_aligned(4, {A.out_mask, A.out_special, A.out_seq});
-  for (A.group = 1; A.group < 64 && A.group * kBtQuad < A.width;) A.group *= 2;
+  A.group = bt_group(A.width);
   const uint64_t per_block = (uint64_t)kBtWaves * (64 / A.group) * kBtIter;  // source rows of a workgroup
   prof_begin(st);
   hipLaunchKernelGGL(rows_kernel<Layout>, dim3((unsigned)((A.n_rows + per_block - 1) / per_block)), dim3(kBtThreads), 0, st, A);

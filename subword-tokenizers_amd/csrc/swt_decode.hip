@@ -3,11 +3,10 @@
 // DESIGN.md 4.13.
 //
 // decode_kernel<T, kRows>: one routine, two instantiations -- the plan (kRows = false: a row's byte length and status, the
-// workgroup's counts) and the rows (kRows = true: the bytes).  ROW-major as mlm_kernel (swt_mlm.hip): a group of g lanes per row,
-// g the power of two that covers the width at four columns a lane, so that narrow rows share a wavefront; a row wider than 4 g
-// columns takes several steps.  A step:
-//   load     the lane's quad of ids and of the mask (one 16-byte load of int32, two of int64, one 4-byte load of the mask when
-//            the width is a multiple of four and the pointers are aligned; else column by column)
+// workgroup's counts) and the rows (kRows = true: the bytes).  ROW-major: a group of g lanes per row (swt_rows.h), so that narrow
+// rows share a wavefront; a row wider than 4 g columns takes several steps.  A step:
+//   load     the lane's quad of ids (bt_load_quad) and of the mask (one 4-byte load), when the width is a multiple of four and
+//            the pointer is aligned; else column by column
 //   flags    which columns are kept, which of them write, the status bits, the token's flags and bytes
 //   previous "the last writing column before this one: none, one that takes a space after it, one that is NO_SPACE_AFTER" --
 //            last-nonzero-scanned inside the quad, then over the lanes of the group (__shfl_up, a lane taking nothing from below
@@ -17,8 +16,8 @@
 //            g-th byte of its group's step and finds the byte's column by search -- coalesced stores.  A lane writing its own
 //            tokens byte by byte was the first build and lost (profiles/decode_rows.txt)
 // The loop over the steps and the sets is uniform over the wavefront (the width and the sets are the launch's), a row beyond
-// `rows` is masked, not skipped: every lane meets every shuffle.  The two counts of the plan are folded over the wavefront, then
-// the workgroup through LDS, and stored per workgroup; decode_counts_kernel sums them into info.  No atomic anywhere.
+// `rows` is masked, not skipped: every lane meets every shuffle.  The two counts of the plan are stored per workgroup;
+// launch_counts_sum sums them into info.  No atomic anywhere.
 #include "swt_batch.h"
 
 namespace swt {
@@ -47,16 +46,6 @@ struct DecodeArgs {
   uint32_t group;         // lanes per row: a power of two, 1 .. 64
   uint32_t sets;          // sets of rows a wavefront walks
 };
-
-template <class T> __device__ inline void dc_load_quad(const T *p, T (&v)[kBtQuad]);
-template <> __device__ inline void dc_load_quad<int32_t>(const int32_t *p, int32_t (&v)[kBtQuad]) {
-  const int4 q = *reinterpret_cast<const int4 *>(p);
-  v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-}
-template <> __device__ inline void dc_load_quad<int64_t>(const int64_t *p, int64_t (&v)[kBtQuad]) {
-  const longlong2 a = reinterpret_cast<const longlong2 *>(p)[0], b = reinterpret_cast<const longlong2 *>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
 
 template <class T, bool kRows>
 __global__ __launch_bounds__(kDcThreads) void decode_kernel(DecodeArgs A) {
@@ -88,7 +77,7 @@ __global__ __launch_bounds__(kDcThreads) void decode_kernel(DecodeArgs A) {
       T v[kBtQuad];
       uint32_t m = 0x01010101u;  // the quad's mask bytes
       if (A.vec_ids) {
-        if (whole) dc_load_quad<T>(ids + at + c0, v);
+        if (whole) bt_load_quad<T>(ids + at + c0, v);
       } else {
 #pragma unroll
         for (uint32_t j = 0; j < kBtQuad; j++)
@@ -197,45 +186,8 @@ __global__ __launch_bounds__(kDcThreads) void decode_kernel(DecodeArgs A) {
     }
   }
   if constexpr (!kRows) {
-#pragma unroll
-    for (uint32_t k = 0; k < kDcCounts; k++) {
-      unsigned long long s = n[k];
-      for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
-      if (lane == 0) counts[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kDcCounts) {
-      unsigned long long s = 0;
-      for (int w = 0; w < kDcWaves; w++) s += counts[w][threadIdx.x];
-      A.part[(uint64_t)blockIdx.x * kDcCounts + threadIdx.x] = s;
-    }
-  }
-}
-
-// Plan, after the scan: the group bases on top of the scan inside the groups; the total closes the array.
-__global__ __launch_bounds__(kDcThreads) void decode_base_kernel(const unsigned long long *__restrict__ local,
-                                                                 const unsigned long long *__restrict__ blk_base, uint64_t rows,
-                                                                 unsigned long long *__restrict__ text_off,
-                                                                 const unsigned long long *__restrict__ info) {
-  const uint64_t i = (uint64_t)blockIdx.x * kDcThreads + threadIdx.x;
-  if (i < rows) text_off[i] = blk_base[i / kBtScanGroup] + local[i];
-  else if (i == rows) text_off[rows] = info[0];
-}
-
-// info[1 + k] = the sum of the workgroups' counts: one workgroup per counter (mlm_counts_kernel says why there is no atomic)
-__global__ __launch_bounds__(kDcThreads) void decode_counts_kernel(const unsigned long long *__restrict__ part, uint64_t n_blocks,
-                                                                   unsigned long long *__restrict__ info) {
-  __shared__ unsigned long long waves[kDcWaves];
-  const uint32_t k = blockIdx.x;
-  unsigned long long s = 0;
-  for (uint64_t i = threadIdx.x; i < n_blocks; i += kDcThreads) s += part[i * kDcCounts + k];
-  for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < kDcWaves; w++) t += waves[w];
-    info[1 + k] = t;
+    const unsigned long long sum = bt_fold_counts(n, counts);
+    if (threadIdx.x < kDcCounts) A.part[(uint64_t)blockIdx.x * kDcCounts + threadIdx.x] = sum;
   }
 }
 
@@ -248,9 +200,7 @@ static int decode_check(const void *ids, uint64_t rows, uint32_t width, const ui
   if (!ids) return fail(SWT_ERR_INVALID, "null argument: ids");
   if (!tok_off) return fail(SWT_ERR_INVALID, "null argument: tok_off");
   if (!tok_flags) return fail(SWT_ERR_INVALID, "null argument: tok_flags");
-  if (rows && !width) return fail(SWT_ERR_INVALID, "width: rows of no column");
-  if (rows > 0xFFFFFFFFull) return fail(SWT_ERR_INVALID, "rows: 2^32 rows or more");
-  if (width > 0x7FFFFFFFu) return fail(SWT_ERR_INVALID, "width: 2^31 columns or more");
+  if (int rc = bt_check_shape(rows, width)) return rc;
   if (flags & ~kDcFlags) return fail(SWT_ERR_INVALID, "flags: unknown flag");
   if (!n_tok) return fail(SWT_ERR_INVALID, "n_tok: a vocabulary of no token");
   return SWT_OK;
@@ -267,12 +217,10 @@ static int decode_check_table(const uint32_t *tok_off, uint32_t n_tok) {
 static unsigned decode_shape(DecodeArgs &A) {
   A.vec_ids = A.width % kBtQuad == 0 && bt_aligned(16, {A.ids});
   A.vec_mask = A.width % kBtQuad == 0 && bt_aligned(4, {A.mask});
-  for (A.group = 1; A.group < 64 && (uint64_t)A.group * kBtQuad < A.width;) A.group *= 2;
-  const uint64_t per_set = (uint64_t)kDcWaves * (64 / A.group), max_blocks = 1u << 20;
-  uint64_t sets = A.group >= 16 ? 1 : 4;
-  while ((A.rows + per_set * sets - 1) / (per_set * sets) > max_blocks) sets *= 2;
-  A.sets = (uint32_t)sets;
-  return (unsigned)((A.rows + per_set * sets - 1) / (per_set * sets));
+  A.group = bt_group(A.width);
+  const RowShape shape = bt_shape(A.rows, A.group, kDcWaves);
+  A.sets = (uint32_t)shape.sets;
+  return shape.grid;
 }
 
 // The bytes and the status of one row on the host: what swt_decode_rows holds text_off against before the device is touched.
@@ -332,13 +280,8 @@ int swt_decode_plan_dev(const void *d_ids, const uint8_t *d_mask, uint64_t rows,
   A.part = g_decode_ws.as<unsigned long long>();
   if (flags & SWT_DECODE_IDS64) hipLaunchKernelGGL((decode_kernel<int64_t, false>), dim3(grid), dim3(kDcThreads), 0, st, A);
   else hipLaunchKernelGGL((decode_kernel<int32_t, false>), dim3(grid), dim3(kDcThreads), 0, st, A);
-  unsigned long long *local = g_batch_ws.local.as<unsigned long long>(), *blk = g_batch_ws.blk.as<unsigned long long>();
-  unsigned long long *info = reinterpret_cast<unsigned long long *>(d_info);
-  const uint64_t nb = (rows + kBtScanGroup - 1) / kBtScanGroup;
-  launch_scan_u64(rows, A.row_len, local, blk, d_info, st);
-  hipLaunchKernelGGL(decode_base_kernel, dim3((unsigned)((rows + 1 + kDcThreads - 1) / kDcThreads)), dim3(kDcThreads), 0, st, local, blk + 1 + nb,
-                     rows, A.row_len, info);
-  hipLaunchKernelGGL(decode_counts_kernel, dim3(kDcCounts), dim3(kDcThreads), 0, st, A.part, (uint64_t)grid, info);
+  launch_scan_bases(rows, A.row_len, d_info, st);
+  launch_counts_sum(A.part, grid, kDcCounts, reinterpret_cast<unsigned long long *>(d_info) + 1, st);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
 } SWT_API_CATCH

@@ -2,20 +2,21 @@
 // columns the objective selects, what stands in their place and the labels.  Semantics: include/swt.h; tests/mlm_cases.py holds
 // them in NumPy; the design and its measurements: DESIGN.md 4.12.
 //
-// mlm_kernel<T>: ROW-major as pack_rows_kernel (swt_pack.hip) -- a group of g lanes per row, g the power of two that covers the
-// width at four columns a lane, so that narrow rows share a wavefront; a row wider than 4 g columns takes several steps.  A step:
-//   load    the lane's quad (one 16-byte load of int32, two of int64, when the width is a multiple of four and the pointers
-//           are aligned; else column by column)
+// mlm_kernel<T>: ROW-major -- a group of g lanes per row (swt_rows.h), so that narrow rows share a wavefront; a row wider than
+// 4 g columns takes several steps.  A step:
+//   load    the lane's quad (bt_load_quad when the width is a multiple of four and the pointers are aligned; else column by
+//           column)
 //   class   from cls_tab, an id outside [0, n_class) is class 2
 //   heads   a column is a head by its class and its left neighbour's -- the quad's first column asks the lane to its left, the
 //           group's first lane the carry of the step before.  "head ? column : none" is max-scanned inside the quad, then over
-//           the lanes of the group (__shfl_up, a lane taking nothing from below its group), then joined with the carry: the last head of the steps before
+//           the lanes of the group (__shfl_up, a lane taking nothing from below its group), then joined with the carry: the
+//           last head of the steps before
 //   draws   Philox4x32-10 at (head, row) decides the word, at (column, row) what a selected column becomes; consecutive columns
 //           of one word share the head's draw, a head's own draw is its head's, and nothing is drawn for class 2
 //   stores  ids, labels, selected
 // The loop over the steps and the sets is uniform over the wavefront (the width and the sets are the launch's), a row beyond
-// `rows` is masked, not skipped: every lane meets every shuffle.  The five counts are folded over the wavefront, then the
-// workgroup through LDS, and stored per workgroup; mlm_counts_kernel sums the workgroups' counts into info.
+// `rows` is masked, not skipped: every lane meets every shuffle.  The five counts are stored per workgroup; launch_counts_sum
+// sums them into info.
 #include "swt_batch.h"
 
 namespace swt {
@@ -60,15 +61,6 @@ struct MlmArgs {
   uint32_t sets;   // sets of rows a wavefront walks
 };
 
-template <class T> __device__ inline void ml_load_quad(const T *p, T (&v)[kBtQuad]);
-template <> __device__ inline void ml_load_quad<int32_t>(const int32_t *p, int32_t (&v)[kBtQuad]) {
-  const int4 q = *reinterpret_cast<const int4 *>(p);
-  v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-}
-template <> __device__ inline void ml_load_quad<int64_t>(const int64_t *p, int64_t (&v)[kBtQuad]) {
-  const longlong2 a = reinterpret_cast<const longlong2 *>(p)[0], b = reinterpret_cast<const longlong2 *>(p)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
 template <class T> __device__ inline void ml_store_quad(T *p, const T (&v)[kBtQuad]);
 template <> __device__ inline void ml_store_quad<int32_t>(int32_t *p, const int32_t (&v)[kBtQuad]) {
   *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(kMlThreads) void mlm_kernel(MlmArgs A) {
       T v[kBtQuad];
       uint32_t cls[kBtQuad];
       if (A.vec) {
-        if (whole) ml_load_quad<T>(ids + at + c0, v);
+        if (whole) bt_load_quad<T>(ids + at + c0, v);
       } else {
 #pragma unroll
         for (uint32_t j = 0; j < kBtQuad; j++)
@@ -188,36 +180,8 @@ __global__ __launch_bounds__(kMlThreads) void mlm_kernel(MlmArgs A) {
     }
   }
   if (!A.part) return;  // uniform over the workgroup
-#pragma unroll
-  for (uint32_t k = 0; k < kMlCounts; k++) {
-    unsigned long long s = n[k];
-    for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
-    if (lane == 0) counts[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kMlCounts) {
-    unsigned long long s = 0;
-    for (int w = 0; w < kMlWaves; w++) s += counts[w][threadIdx.x];
-    A.part[(uint64_t)blockIdx.x * kMlCounts + threadIdx.x] = s;
-  }
-}
-
-// info[k] = the sum of the workgroups' counts: one workgroup per counter, and no atomic anywhere -- thousands of workgroups
-// adding to five words of one cache line cost more than the masking itself
-__global__ __launch_bounds__(kMlThreads) void mlm_counts_kernel(const unsigned long long *__restrict__ part, uint64_t n_blocks,
-                                                                unsigned long long *__restrict__ info) {
-  __shared__ unsigned long long waves[kMlWaves];
-  const uint32_t k = blockIdx.x;
-  unsigned long long s = 0;
-  for (uint64_t i = threadIdx.x; i < n_blocks; i += kMlThreads) s += part[i * kMlCounts + k];
-  for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < kMlWaves; w++) t += waves[w];
-    info[k] = t;
-  }
+  const unsigned long long sum = bt_fold_counts(n, counts);
+  if (threadIdx.x < kMlCounts) A.part[(uint64_t)blockIdx.x * kMlCounts + threadIdx.x] = sum;
 }
 
 // the workgroups' counts between the two launches: grow-only and shared by all calls of the process (the calls carry no
@@ -238,9 +202,7 @@ static int mlm_check(const void *ids, uint64_t rows, uint32_t width, const uint8
   if (!out_ids) return fail(SWT_ERR_INVALID, "null argument: out_ids");
   if (!out_labels) return fail(SWT_ERR_INVALID, "null argument: out_labels");
   if (!cls_tab) return fail(SWT_ERR_INVALID, "null argument: cls_tab");
-  if (rows && !width) return fail(SWT_ERR_INVALID, "width: rows of no column");
-  if (rows > 0xFFFFFFFFull) return fail(SWT_ERR_INVALID, "rows: 2^32 rows or more");
-  if (width > 0x7FFFFFFFu) return fail(SWT_ERR_INVALID, "width: 2^31 columns or more");
+  if (int rc = bt_check_shape(rows, width)) return rc;
   if (spec->flags & ~kMlFlags) return fail(SWT_ERR_INVALID, "flags: unknown flag");
   const uint64_t one = 1ull << 32;
   if (spec->select_below > one) return fail(SWT_ERR_INVALID, "select_below is above 2^32");
@@ -289,12 +251,10 @@ int swt_mlm_mask_dev(const void *d_ids, uint64_t rows, uint32_t width, const uin
             (spec->flags & SWT_MLM_WHOLE_WORD) ? 1u : 0u, spec->mask_id, spec->select_below, spec->mask_below, spec->random_below,
             d_out_ids, d_out_labels, d_out_selected, nullptr, 0, 1, 1};
   A.vec = width % kBtQuad == 0 && bt_aligned(16, {d_ids, d_out_ids, d_out_labels}) && bt_aligned(4, {d_out_selected});
-  for (A.group = 1; A.group < 64 && (uint64_t)A.group * kBtQuad < width;) A.group *= 2;
-  const uint64_t per_set = (uint64_t)kMlWaves * (64 / A.group), max_blocks = 1u << 20;
-  uint64_t sets = A.group >= 16 ? 1 : 4;
-  while ((rows + per_set * sets - 1) / (per_set * sets) > max_blocks) sets *= 2;
-  A.sets = (uint32_t)sets;
-  const unsigned grid = (unsigned)((rows + per_set * sets - 1) / (per_set * sets));
+  A.group = bt_group(width);
+  const RowShape shape = bt_shape(rows, A.group, kMlWaves);
+  A.sets = (uint32_t)shape.sets;
+  const unsigned grid = shape.grid;
   if (d_info) {
     if ((rc = g_mlm_ws.reserve((size_t)grid * kMlCounts * 8))) return rc;
     A.part = g_mlm_ws.as<unsigned long long>();
@@ -303,9 +263,7 @@ int swt_mlm_mask_dev(const void *d_ids, uint64_t rows, uint32_t width, const uin
   if (spec->flags & SWT_MLM_IDS64) hipLaunchKernelGGL(mlm_kernel<int64_t>, dim3(grid), dim3(kMlThreads), 0, st, A);
   else hipLaunchKernelGGL(mlm_kernel<int32_t>, dim3(grid), dim3(kMlThreads), 0, st, A);
   prof_end(st);
-  if (d_info)
-    hipLaunchKernelGGL(mlm_counts_kernel, dim3(kMlCounts), dim3(kMlThreads), 0, st, A.part, (uint64_t)grid,
-                       reinterpret_cast<unsigned long long *>(d_info));
+  if (d_info) launch_counts_sum(A.part, grid, kMlCounts, reinterpret_cast<unsigned long long *>(d_info), st);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
 } SWT_API_CATCH

@@ -16,12 +16,11 @@
 //          many groups: the exit is a row number); its workgroup fetches the heads of sixteen groups ahead in one round trip.  pack_mark_kernel, per group again: the rows the orbit visits from the
 //          entry, marked through the doubling tables from the longest jump down; a count scan and a max scan over the marks
 //          give every row its packed row and that row's first source row, hence slot and row_first.
-// rows   pack_rows_kernel<kSplit>: PACKED-row-major -- a group of g lanes per packed row, g the power of two that covers the
-//        width at four columns a lane, as rows_kernel (swt_batch.hip) has per source row.  A lane finds the segment of its
-//        column by a galloping search in slot from the packed row's first source row (one probe while it stays in a segment).
-//        One writer per output row, the aligned 16-byte stores kept, no atomics on the data path, and no store depends on
-//        what slot or row_first hold: a group writes the columns of its own row b < min(rows, rows_cap) and nothing else.
-//        The counters of info are folded over the wavefront, then the workgroup, and added once per workgroup.
+// rows   pack_rows_kernel<kSplit>: PACKED-row-major -- a group of lanes per packed row (swt_rows.h).  A lane finds the segment
+//        of its column by a galloping search in slot from the packed row's first source row (one probe while it stays in a
+//        segment).  One writer per output row, the aligned 16-byte stores kept, no atomics on the data path, and no store
+//        depends on what slot or row_first hold: a group writes the columns of its own row b < min(rows, rows_cap) and nothing
+//        else.  The counters of info are added once per workgroup.
 #include "swt_batch.h"
 
 namespace swt {
@@ -322,11 +321,7 @@ __global__ __launch_bounds__(kPkThreads) void pack_rows_kernel(PackArgs A) {
           if (has_cls && p == 0) { id[j] = A.cls_id; continue; }
           if (has_sep && p == len - 1) { id[j] = A.sep_id; continue; }
           const uint64_t t = tok0 + (p - has_cls);  // p - has_cls < body
-          const uint32_t raw = A.ids[t], s = raw & 0x7FFFFFFFu;
-          uint32_t d = SWT_BATCH_NONE;
-          if (s < A.n_map) d = A.map ? A.map[(uint64_t)s + ((A.flagged && (raw >> 31)) ? (uint64_t)A.n_map : 0ull)] : s;
-          if (d == SWT_BATCH_NONE) { d = A.unk_id; n_unk++; }
-          id[j] = d;
+          id[j] = bt_dense_id(A.ids[t], A.map, A.n_map, A.flagged, A.unk_id, n_unk);
         }
         const uint64_t o = slot0 + c0;
         if (A.vec) {
@@ -352,18 +347,9 @@ __global__ __launch_bounds__(kPkThreads) void pack_rows_kernel(PackArgs A) {
     if (live && sub == 0 && A.out_len) A.out_len[b] = filled;
   }
   if (!A.info) return;  // uniform over the workgroup
-  for (int d = 32; d; d >>= 1) {
-    n_unk += __shfl_xor(n_unk, d, 64);
-    n_lost += __shfl_xor(n_lost, d, 64);
-  }
-  if (lane == 0) { counts[wave][0] = n_lost; counts[wave][1] = n_unk; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long lost = 0, unk = 0;
-    for (int v = 0; v < kPkWaves; v++) { lost += counts[v][0]; unk += counts[v][1]; }
-    if (lost) atomicAdd(&A.info[1], lost);
-    if (unk) atomicAdd(&A.info[2], unk);
-  }
+  const uint32_t mine[2] = {n_lost, n_unk};  // info[1], info[2]
+  const unsigned long long sum = bt_fold_counts(mine, counts);
+  if (sum) atomicAdd(&A.info[1 + threadIdx.x], sum);  // threads 0 and 1 alone have one
 }
 
 // what the plan keeps between its launches, grow-only as the scan's workspace and under the same rule
@@ -522,17 +508,14 @@ int swt_pack_rows_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, uint64_t
              reinterpret_cast<const unsigned long long *>(d_row_first), rows_cap, d_out_ids, d_out_mask, d_out_pos, d_out_seg, d_out_doc,
              d_out_len, reinterpret_cast<unsigned long long *>(d_info), 0, 1, 1};
   A.vec = A.width % kBtQuad == 0 && bt_aligned(16, {d_out_ids, d_out_pos, d_out_seg, d_out_doc}) && bt_aligned(4, {d_out_mask});
-  for (A.group = 1; A.group < 64 && A.group * kBtQuad < A.width;) A.group *= 2;
-  // the packed rows are known to the device alone: room for rows_cap of them, the wavefronts walking more sets where that is many
-  const uint64_t per_set = (uint64_t)kPkWaves * (64 / A.group), max_blocks = 1u << 20;
-  uint64_t sets = A.group >= 16 ? 1 : 4;
-  while ((rows_cap + per_set * sets - 1) / (per_set * sets) > max_blocks) sets *= 2;
-  if (sets > 0xFFFFFFFFull) return fail(SWT_ERR_INVALID, "2^32 rows or more");
-  A.sets = (uint32_t)sets;
-  const unsigned grid = (unsigned)((rows_cap + per_set * sets - 1) / (per_set * sets));
+  A.group = bt_group(A.width);
+  // the packed rows are known to the device alone: room for rows_cap of them, which nothing bounds: the sets must fit their field
+  const RowShape shape = bt_shape(rows_cap, A.group, kPkWaves);
+  if (shape.sets > 0xFFFFFFFFull) return fail(SWT_ERR_INVALID, "2^32 rows or more");
+  A.sets = (uint32_t)shape.sets;
   prof_begin(st);
-  if (mode & SWT_PACK_SPLIT) hipLaunchKernelGGL(pack_rows_kernel<true>, dim3(grid), dim3(kPkThreads), 0, st, A);
-  else hipLaunchKernelGGL(pack_rows_kernel<false>, dim3(grid), dim3(kPkThreads), 0, st, A);
+  if (mode & SWT_PACK_SPLIT) hipLaunchKernelGGL(pack_rows_kernel<true>, dim3(shape.grid), dim3(kPkThreads), 0, st, A);
+  else hipLaunchKernelGGL(pack_rows_kernel<false>, dim3(shape.grid), dim3(kPkThreads), 0, st, A);
   prof_end(st);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
