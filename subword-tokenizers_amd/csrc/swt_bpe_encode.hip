@@ -107,8 +107,20 @@ struct NarrowDir {
   const BpeSlot *wide_slots;   // the table of the ids, for the one-lane walker of a word longer than a chunk
   const uint32_t *code_of_cp;  // [n_cps] code | class << 16 (NarrowTable::code_of_cp)
   const uint32_t *cp_of_code;  // [letters] the alphabet, for the emit
+  const uint32_t *code_of_rank;  // null for a sequential table (NarrowTable::sequential), whose kernel (Seq) does not read it; else [n_merges] the merged code of a rank
   uint32_t wide_sh, n_cps, letters, pad;
 };
+// Narrow: an entry of val[] is the round's KEY, rank << 16 | the slot's index in its word, so the minimum of a word is a plain
+// minimum over what a scan reads.  `v`: a table value (rank << 16 | code), or kNoRank -- which stays "no pair" (>= kNarrowNoPair)
+// under any slot.  Dead slots hold kNoRank, a FOREIGN symbol's entry kNarrowNoPair | code point: neither wins a minimum.
+__device__ __forceinline__ uint32_t slot_key(uint32_t v, uint32_t slot) { return (v & 0xFFFF0000u) | slot; }
+// the code of the symbol that the merge of rank `rank` produces.  Seq: the table is sequential (NarrowTable::sequential) and the
+// kernel keeps no pointer for it; a branch on the pointer in one kernel cost the sequential tables 0.75 M vector instructions a
+// launch and 1.6 % of the step in registers spilled around the rounds (profiles/lane_keys.txt section 6)
+template <bool Seq>
+__device__ __forceinline__ uint32_t narrow_merged(const NarrowDir &D, uint32_t rank) {
+  if constexpr (Seq) return D.letters + rank; else return D.code_of_rank[rank];
+}
 
 // FastBPE.encode_word on a symbol array (bpe.py:210-238), serial form for the one-lane fallback: repeat { lowest-rank
 // adjacent pair; replace all of its occurrences left to right, non-overlapping }.  Returns the new length.
@@ -256,6 +268,11 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //          1 KB every wave loads for it are gone.  A code point outside the alphabet is FOREIGN: it never merges, and its val[]
 //          entry -- which no lookup can fill -- carries the code point to the emit.  Running text (Mode 0) on a packed table
 //          below 32 k symbols only; Ordered, Modes 1 and 2 and every other table keep the wide kernel as it was.
+//          The val[] entry of a pair is the round's KEY, rank << 16 | the slot's index in its word (slot_key): the split writes
+//          it with the slot counted across its blocks, a round writes its two entries with theirs, and the three scans (scan_keys,
+//          lane_tail) are plain minima, 6 vector instructions and 2 ds_read2_b32 per four slots where building the keys from the
+//          values took 15 and 4 (profiles/lane_keys.txt).  The merged code comes from the key's rank (narrow_merged): letters + rank
+//          in the kernel of a sequential table (template parameter Seq), code_of_rank[rank] in that of any other.
 template <bool Narrow>
 struct LaneSym {  // how a symbol stands in LDS
   using type = uint32_t;
@@ -275,7 +292,7 @@ struct LaneLds {
   using Sym = typename LaneSym<Narrow>::type;
   __attribute__((aligned(16))) uint8_t txt[Cap + 16];  // staged bytes; once the split is done, a single-wave kernel's word list
   Sym sym[Cap + 4];           // per symbol: id (| SWT_BPE_CONT unless it opens its word), kInvalidTok once consumed; Narrow: its code
-  uint32_t val[Cap + 4];      // per symbol: table value of (this symbol, next live symbol of the word), kNoRank when none
+  uint32_t val[Cap + 4];      // per symbol: table value of (this symbol, next live symbol of the word), kNoRank when none; Narrow: its key (slot_key)
   uint16_t wl[Cap + 2];       // first symbol of every word, in text order
   unsigned long long sbits[Blocks + 1];    // sentence-start bit per byte
   unsigned long long symmask[Blocks + 1];  // symbol bit per byte
@@ -326,21 +343,24 @@ constexpr uint32_t kDirtyVal = 0xFFFFFFFEu;  // above every table value (ranks s
 // bpe.py:210-238 on one word whose symbols S[0..n) and pair values V[0..n) (V[n-1] = kNoRank) live in LDS: every round merges
 // ALL occurrences of the best pair left to right, compacts the word and probes only the pairs that changed.
 // Narrow: S holds 16-bit codes.  A FOREIGN symbol's V entry is its code point (>= kNarrowNoPair, so it is never the minimum); it
-// moves with the symbol when the word is compacted and is neither marked dirty nor reset.
-template <bool Packed, bool Narrow = false>
+// moves with the symbol when the word is compacted and is neither marked dirty nor reset.  The pair entries come in as keys
+// (slot_key) and are read by their RANK half alone: the word is finished here, so the low half -- the split's slot, stale once the
+// word is compacted, or the code of a value looked up here -- is never read as a slot.
+template <bool Packed, bool Narrow = false, bool Seq = false>
 __device__ void slow_word(typename LaneSym<Narrow>::type *S, uint32_t *V, const uint32_t n0, const typename LaneSym<Narrow>::Slot *__restrict__ slots,
-                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank) {
+                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D) {
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   uint32_t n = n0;
   for (;;) {
     uint32_t m = kNoRank;
     for (uint32_t i = 0; i + 1 < n; i++) m = min(m, V[i]);
     if (Narrow ? m >= kNarrowNoPair : m == kNoRank) break;
-    const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+    uint32_t mg;
+    if constexpr (Narrow) mg = narrow_merged<Seq>(D, m >> 16); else mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
     uint32_t i = 0, j = 0;
     while (i < n) {
       const uint32_t vi = V[i];
-      const bool take = i + 1 < n && vi == m;
+      const bool take = i + 1 < n && (Narrow ? (vi >> 16) == (m >> 16) : vi == m);  // (no other kind of entry has a rank's high half)
       const uint32_t s = take ? mg : (S[i] & ~kCont);
       if (take && j && !(Narrow && (S[j - 1] & ~kCont) == kNarrowForeign)) V[j - 1] = kDirtyVal;
       S[j] = j ? (s | kCont) : s;
@@ -450,6 +470,7 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
   bool prev_wb = true;        // the byte before this block belongs to a whitespace/punctuation char (or chunk start)
   bool pend_open = false;     // the last symbol of the previous block may have its successor in this one
   uint32_t pend_cp = 0;
+  uint32_t wbase = 0;         // Narrow: the symbol at which the word that is open at the block boundary began
   int cut = -1;               // last word boundary (for a span longer than the chunk)
   for (uint32_t blk = 0; blk < nblk; blk++) {
     const uint32_t p = blk * 64 + lane;
@@ -516,13 +537,22 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
     const bool want = hasnext || jp;
     uint32_t v = kNoRank;
     if (want) v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn);
+    if constexpr (Narrow) {
+      // the value goes in as the key of its slot (slot_key): the symbol's place in its word, counted from the word start at or
+      // below this lane -- whose lane knows its symbol index -- or, when the block has none down there, from wbase
+      const unsigned long long ws = WSTART & le;
+      const uint32_t first = __shfl(si, ws ? 63 - __builtin_clzll(ws) : 0);
+      v = slot_key(v, jp ? nsym - 1u - wbase : si - (ws ? first : wbase));
+    }
     if (is_sym) {
       L.sym[si] = wstart ? sy : (sy | kCont);
       if (!hasnext) L.val[si] = kNoRank;
     }
     if (want) L.val[jp ? nsym - 1 : si] = v;
-    if constexpr (Narrow)
+    if constexpr (Narrow) {
       if (is_sym && sy == kNarrowForeign) L.val[si] = kNarrowNoPair | (cp & kNarrowCpMask);
+      if (WSTART) wbase = nsym + (uint32_t)__popcll(SYM & ((1ull << (63 - __builtin_clzll(WSTART))) - 1ull));
+    }
     if (wstart) L.wl[nw + (uint32_t)__popcll(WSTART & lt)] = (uint16_t)si;
     if (lane == 0) { L.symmask[blk] = SYM; L.sympre[blk] = nsym; }
     nw += (uint32_t)__popcll(WSTART);
@@ -660,6 +690,36 @@ __device__ __forceinline__ uint32_t scan_key(const uint32_t *V, uint32_t n) {
   }
   return key;
 }
+// Narrow: val[] holds the keys themselves, so a trip is two reads of two entries off one clamped base and two min3.  The base of
+// the last trip is pulled back to n - 4 (a group that overlaps the one before is harmless to a minimum) and entry n - 1 -- the
+// last symbol's, never a pair -- may be read; a word of two or three symbols reads entries 0 and 1 twice (d = 0) or 0, 1, 2
+// (d = 1), never its neighbour's.
+struct KeyScan {
+  uint32_t lim4, d4;  // the largest base, and the second read's distance from the first; both in bytes
+  __device__ __forceinline__ explicit KeyScan(uint32_t n) : lim4(4u * (n - 2u - min(n - 2u, 2u))), d4(4u * min(n - 2u, 2u)) {}
+};
+#ifdef SWT_SCAN_TRIPS
+// diagnostic builds only: trips of the three scan loops as the WAVE executes them (one count per trip, by its first active lane):
+// [0] when a lane takes a word, [1] after a round, [2] in the tail
+__device__ unsigned long long g_scan_trips[3];
+#endif
+template <int Which>
+__device__ __forceinline__ uint32_t scan_trip(const uint32_t *V, uint32_t i0, const KeyScan &ks, uint32_t key) {  // i0: a multiple of 4
+#ifdef SWT_SCAN_TRIPS
+  if (threadIdx.x == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_scan_trips[Which], 1ull);
+#endif
+  const uint32_t o = min(4u * i0, ks.lim4);
+  const char *const v0 = reinterpret_cast<const char *>(V);
+  const uint32_t *a = reinterpret_cast<const uint32_t *>(v0 + o), *b = reinterpret_cast<const uint32_t *>(v0 + ks.d4 + o);
+  return min(min(min(min(key, a[0]), a[1]), b[0]), b[1]);
+}
+template <int Which>
+__device__ __forceinline__ uint32_t scan_keys(const uint32_t *V, uint32_t n, const KeyScan &ks) {
+  const uint32_t nm1 = n - 1u;
+  uint32_t key = 0xFFFFFFFFu;
+  for (uint32_t i0 = 0; i0 < nm1; i0 += 4) key = scan_trip<Which>(V, i0, ks, key);
+  return key;
+}
 // A lane's word as the rounds hand it to their tail.
 struct LaneWord {
   uint32_t n, alive;  // symbols (0: the lane holds no word), live slots (bit i: slot i still holds a symbol)
@@ -672,10 +732,10 @@ struct LaneWord {
 // of the slots, a shuffle finds the word's minimum, every lane of the group follows the merge (same values, LDS broadcasts), lane 0
 // writes it and looks the left pair up while lane 1 looks up the right.  LEAD = the lanes that hold a word's state on entry (at
 // most 64 / TL of them); the function returns when every word is finished.
-template <bool Packed, uint32_t TL, int Cap, bool Narrow>
+template <bool Packed, uint32_t TL, bool Seq, int Cap, bool Narrow>
 __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWord &W, unsigned long long LEAD, int lane,
                                           const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
-                                          const uint32_t *__restrict__ merged_of_rank) {
+                                          const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D) {
   constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   // group g of TL lanes takes over the g-th word
@@ -688,6 +748,7 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
   typename LaneSym<Narrow>::type *const S = L.sym + t_w;
   uint32_t *const V = L.val + t_w;
   uint32_t n = have ? t_n : 0u, alive = t_alive;
+  [[maybe_unused]] const KeyScan ks(max(n, 2u));
   for (;;) {
     if (__ballot(n != 0u) == 0ull) break;
     if (n != 0u) {
@@ -697,8 +758,12 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
       for (uint32_t q0 = 0; q0 < 32u / TL; q0 += 4) {  // this lane's share of the (at most 32) slots
         const uint32_t i0 = (32u / TL) * j + q0;
         if (i0 < nm1) {
-          const uint32_t i1 = min(i0 + 1u, nm1), i2 = min(i0 + 2u, nm1), i3 = min(i0 + 3u, nm1);
-          k = min(k, min(min(rank_key<Packed>(V[i0], i0), rank_key<Packed>(V[i1], i1)), min(rank_key<Packed>(V[i2], i2), rank_key<Packed>(V[i3], i3))));
+          if constexpr (Narrow) {
+            k = scan_trip<2>(V, i0, ks, k);
+          } else {
+            const uint32_t i1 = min(i0 + 1u, nm1), i2 = min(i0 + 2u, nm1), i3 = min(i0 + 3u, nm1);
+            k = min(k, min(min(rank_key<Packed>(V[i0], i0), rank_key<Packed>(V[i1], i1)), min(rank_key<Packed>(V[i2], i2), rank_key<Packed>(V[i3], i3))));
+          }
         }
       }
 #pragma unroll
@@ -708,19 +773,21 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
       if (k >= kNoKey || hi == 0u) {
         n = 0u;  // the same decision in all lanes of the group
       } else {
-        const uint32_t m = V[im];
+        const uint32_t m = Narrow ? k >> 16 : V[im];  // Narrow: the rank, which the key holds
         const uint32_t r = (uint32_t)__builtin_ctz(hi);
         const uint32_t hi2 = hi & (hi - 1u);
         const uint32_t lo = alive & ((1u << im) - 1u);
         const bool has_rr = hi2 != 0u, has_pl = lo != 0u;
         const uint32_t rr = has_rr ? (uint32_t)__builtin_ctz(hi2) : 0u, pl = has_pl ? 31u - (uint32_t)__builtin_clz(lo) : 0u;
         alive &= ~(1u << r);
-        const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+        uint32_t mg;
+        if constexpr (Narrow) mg = narrow_merged<Seq>(D, m); else mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
         const uint32_t sl = S[pl] & ~kCont, sr = S[rr] & ~kCont;
         wave_sync();  // every lane has read the old symbols before lane 0 changes them
         const bool left = j == 0u && has_pl, right = j == 1u && has_rr;
         uint32_t v = kNoRank;
         if (left || right) v = slot_value(slots, sh, left ? sl : mg, left ? mg : sr);
+        if constexpr (Narrow) v = slot_key(v, left ? pl : im);  // the entry of slot pl (lane 0) or im (lane 1)
         if (j == 0u) {
           S[im] = im ? (mg | kCont) : mg;
           S[r] = kDead;
@@ -735,10 +802,10 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
 }
 
 // The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
-template <bool Packed, bool Proper, int Cap, bool Ordered, bool Narrow>
+template <bool Packed, bool Proper, bool Seq, int Cap, bool Ordered, bool Narrow>
 __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const uint16_t *list, uint32_t n_list, int lane,
                                                 const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
-                                                const uint32_t *__restrict__ merged_of_rank) {
+                                                const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D) {
   static_assert(!(Narrow && (Ordered || !Packed)), "the narrow form is that of a packed table in FastBPE's order");
   constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
@@ -746,6 +813,7 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
   uint32_t next = 0;  // first word of the list no lane has taken (the same in every lane)
   uint32_t n = 0, alive = 0, where = 0;  // this lane's word: symbols (0: none), live slots, first slot
   uint32_t key = 0xFFFFFFFFu;            // its smallest rank | the slot that holds it
+  [[maybe_unused]] KeyScan ks(2u);       // Narrow: what a scan of its entries needs, kept with the word
   typename LaneSym<Narrow>::type *S = L.sym;
   uint32_t *V = L.val;
   for (;;) {
@@ -763,10 +831,10 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
           ordered_word<Packed>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
         } else if (!Proper || n > 32u) {
-          slow_word<Packed, Narrow>(S, V, n, slots, sh, merged_of_rank);
+          slow_word<Packed, Narrow, Seq>(S, V, n, slots, sh, merged_of_rank, D);
           n = 0u;
         } else {
-          key = scan_key<Packed>(V, n);
+          if constexpr (Narrow) { ks = KeyScan(n); key = scan_keys<0>(V, n, ks); } else key = scan_key<Packed>(V, n);
         }
       }
       next += (uint32_t)__popcll(IDLE);
@@ -781,22 +849,23 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
       if (key >= kNoKey || hi == 0u) {
         n = 0u;  // the word is finished (hi == 0 cannot happen: a slot with a pair value has a live successor)
       } else {
-        const uint32_t m = V[im];
+        const uint32_t m = Narrow ? key >> 16 : V[im];  // Narrow: the rank, which the key holds
         const uint32_t r = (uint32_t)__builtin_ctz(hi);
         const uint32_t hi2 = hi & (hi - 1u);
         const uint32_t lo = alive & ((1u << im) - 1u);
         const bool has_rr = hi2 != 0u, has_pl = lo != 0u;
         const uint32_t rr = has_rr ? (uint32_t)__builtin_ctz(hi2) : 0u, pl = has_pl ? 31u - (uint32_t)__builtin_clz(lo) : im;
         alive &= ~(1u << r);
-        const uint32_t mg = Narrow ? (m & 0xFFFFu) : Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+        uint32_t mg;
+        if constexpr (Narrow) mg = narrow_merged<Seq>(D, m); else mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
         const uint32_t sl = S[pl] & ~kCont, sr = S[rr] & ~kCont;
         S[im] = im ? (mg | kCont) : mg;
         S[r] = kDead;
         V[r] = kNoRank;
         const uint32_t v1 = slot_value(slots, sh, sl, mg), v2 = has_rr ? slot_value(slots, sh, mg, sr) : kNoRank;
-        if (has_pl && !(Narrow && sl == kNarrowForeign)) V[pl] = v1;  // a FOREIGN symbol's entry is its code point
-        V[im] = v2;
-        key = scan_key<Packed>(V, n);
+        if (has_pl && !(Narrow && sl == kNarrowForeign)) V[pl] = Narrow ? slot_key(v1, pl) : v1;  // a FOREIGN symbol's entry is its code point
+        V[im] = Narrow ? slot_key(v2, im) : v2;
+        if constexpr (Narrow) key = scan_keys<1>(V, n, ks); else key = scan_key<Packed>(V, n);
       }
     }
   }
@@ -866,7 +935,7 @@ __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 #endif
 
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
-template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false>
+template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false, bool Seq = false>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots,
@@ -876,6 +945,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   constexpr bool kDirect = Mode == 2;
   static_assert(Cap % 64 == 0 && Cap <= 4032, "11 B of LDS per staged byte and the masks (Narrow: 9 B); wl[] and the word list hold 16-bit indices");
   static_assert(!Narrow || (Mode == 0 && Packed && !Ordered), "the narrow form: running text, a packed table, FastBPE's order");
+  static_assert(!Seq || Narrow, "Seq says where the narrow form's rounds get the merged code from");
   static_assert(!Narrow || kLaneCap != 512 || sizeof(LaneLds<Cap, true>) + sizeof(LaneShared<true>) <= sizeof(LaneLds<kLaneCap>) + sizeof(LaneShared<false>),
                 "the narrow kernel's chunk is sized to the LDS of the wide one, so that as many waves reside");
   using Slot = typename LaneSym<Narrow>::Slot;
@@ -916,9 +986,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1);
     wave_sync();
     // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
-    const LaneWord W = lane_rounds<Packed, Proper, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank);
+    const LaneWord W = lane_rounds<Packed, Proper, Seq, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank, D);
     const unsigned long long BUSY = __ballot(W.n != 0u);
-    if (BUSY != 0ull) lane_tail<Packed, 4, Cap>(L, W, BUSY, lane, tab, sh, merged_of_rank);
+    if (BUSY != 0ull) lane_tail<Packed, 4, Seq, Cap>(L, W, BUSY, lane, tab, sh, merged_of_rank, D);
     wave_sync();
     lane_emit<Cap, Mode>(L, D, sent_off, T, C, lane, sent_local, uslot, rec, drec, direct);
     if (C.last) break;
@@ -970,7 +1040,7 @@ struct swt_bpe_table {
   // 16-bit symbol codes (swt_bpe_narrow.h) for the narrow form of the running-text kernel; empty unless narrow.eligible
   NarrowTable narrow;
   NarrowSlot *d_nslots = nullptr;
-  uint32_t *d_ncodes = nullptr;  // code_of_cp, then cp_of_code
+  uint32_t *d_ncodes = nullptr;  // code_of_cp, then cp_of_code, then (a table that is not sequential) code_of_rank
   NarrowDir *d_ndir = nullptr;
 };
 
@@ -982,6 +1052,8 @@ static int bpe_upload_narrow(swt_bpe_table *t) {
   std::vector<uint32_t> codes = n.code_of_cp(host_class_table());
   const uint32_t n_cps = (uint32_t)codes.size();
   codes.insert(codes.end(), n.cp_of_code.begin(), n.cp_of_code.end());
+  const size_t at_ranks = codes.size();
+  if (!n.sequential) codes.insert(codes.end(), n.code_of_rank.begin(), n.code_of_rank.end());
   NarrowSlot *d_nslots = nullptr;
   uint32_t *d_ncodes = nullptr;
   NarrowDir *d_ndir = nullptr;
@@ -989,7 +1061,7 @@ static int bpe_upload_narrow(swt_bpe_table *t) {
   if (e == hipSuccess) e = hipMemcpy(d_nslots, n.slots.data(), n.slots.size() * sizeof(NarrowSlot), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void **)&d_ncodes, (codes.size() + 1) * 4);
   if (e == hipSuccess) e = hipMemcpy(d_ncodes, codes.data(), codes.size() * 4, hipMemcpyHostToDevice);
-  const NarrowDir dir{t->d_slots, d_ncodes, d_ncodes + n_cps, 32u - t->bits, n_cps, n.letters(), 0u};
+  const NarrowDir dir{t->d_slots, d_ncodes, d_ncodes + n_cps, n.sequential ? nullptr : d_ncodes + at_ranks, 32u - t->bits, n_cps, n.letters(), 0u};
   if (e == hipSuccess) e = hipMalloc((void **)&d_ndir, sizeof dir);
   if (e == hipSuccess) e = hipMemcpy(d_ndir, &dir, sizeof dir, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -1063,6 +1135,7 @@ static bool lane_narrow(swt_bpe_table *t, bool ordered, uint64_t n_bytes) {
   return t->opt_lane_narrow == 2 || n_bytes >= (uint64_t)kLaneTile * lane_slots(t, false, false);
 }
 static LaneKernel lane_kernel_narrow(const swt_bpe_table *t) {
+  if (t->narrow.sequential) return t->proper ? bpe_lane_kernel<true, true, kNarrowCap, 0, false, true, true> : bpe_lane_kernel<true, false, kNarrowCap, 0, false, true, true>;
   return t->proper ? bpe_lane_kernel<true, true, kNarrowCap, 0, false, true> : bpe_lane_kernel<true, false, kNarrowCap, 0, false, true>;
 }
 // The largest tile of a running-text call.  The narrow kernel's own geometry has kNarrowTile; a call whose geometry is SET
@@ -1082,13 +1155,15 @@ extern "C" {
 // FastBPE's order take the NARROW kernel -- 0 none (not eligible, or SWT_OPT_LANE_NARROW = 1), 1 those of a chip-full of tiles
 // and more (the library's choice), 2 all (SWT_OPT_LANE_NARROW = 2), 8: eligible for it (packed and letters + merges <= 0x7FFD),
 // 9: letters of its alphabet (0 when not eligible), 11: the kernel the LAST running-text launch of this handle took, written where
-// the launch picks it -- 1 the narrow kernel, 0 a wide one, -1 no such launch yet
+// the launch picks it -- 1 the narrow kernel, 0 a wide one, -1 no such launch yet, 12: the narrow kernel's rounds get the merged
+// code as letters + rank (1: NarrowTable::sequential, the Seq kernels) or read it from code_of_rank (0; also when not eligible)
 int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   if (!t) return -1;
   if (which == 7) return !t->narrow.eligible || t->opt_lane_narrow == 1 ? 0 : t->opt_lane_narrow == 2 ? 2 : 1;
   if (which == 8) return t->narrow.eligible ? 1 : 0;
   if (which == 9) return (int)t->narrow.letters();
   if (which == 11) return t->last_lane_narrow;
+  if (which == 12) return t->narrow.eligible && t->narrow.sequential ? 1 : 0;
   if (which == 0) return (int)t->bits;
   if (which == 1) return t->packed ? 1 : 0;
   if (which == 2) return t->proper ? 1 : 0;
@@ -1113,6 +1188,17 @@ int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   return which == 3 ? (int)n : (placed ? 1 : 0);
 } SWT_API_CATCH
 
+#ifdef SWT_SCAN_TRIPS
+// diagnostic builds only: copies the three trip counts out (take, after a round, tail) and clears them
+int swt_debug_scan_trips(unsigned long long *out) try {
+  void *d = nullptr;
+  SWT_HIP(hipDeviceSynchronize());
+  SWT_HIP(hipGetSymbolAddress(&d, HIP_SYMBOL(g_scan_trips)));
+  SWT_HIP(hipMemcpy(out, d, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost));
+  SWT_HIP(hipMemset(d, 0, sizeof(unsigned long long) * 3));
+  return SWT_OK;
+} SWT_API_CATCH
+#endif
 #ifdef SWT_STAMPS
 // diagnostic builds only: copies the stamps of the last Mode 0 launch out (2 * swt_debug_lane_stamp_count() values) and clears them
 int swt_debug_lane_stamp_count() { return (int)kLaneStamps; }

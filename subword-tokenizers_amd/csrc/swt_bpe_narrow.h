@@ -11,6 +11,11 @@
 // The rank table of the codes is the same two-choice cuckoo table as the one of the ids (bpe_hash, two slots a pair), keyed on
 // l << 16 | r, exact in 32 bits: a slot is {key, value} in 8 bytes, value = rank << 16 | code of the merged symbol.
 //
+// The kernel's val[] entry of a pair is the round's KEY, rank << 16 | the slot's index in its word (slot_key, swt_bpe_encode.hip):
+// only the rank half of a table value gets there, and a round learns the merged code from the rank.  Where the list's live merge i
+// produces the symbol SWT_SYM_BASE + i (any list whose merged strings are all new ones, every trained list) that is one add,
+// letters + rank (NarrowTable::sequential); any other eligible list reads code_of_rank[rank].
+//
 // Nothing from HIP is included here: a CPU test compiles this header with g++ (tests/test_lane_narrow.py).
 #pragma once
 
@@ -50,8 +55,13 @@ constexpr uint32_t kNarrowMinCps = 1024;  // code_of_cp covers at least the code
 struct NarrowSlot { uint32_t key, value; };
 SWT_NARROW_HD uint32_t narrow_key(uint32_t l, uint32_t r) { return (l << 16) | r; }
 
+// Every eligible table runs the narrow kernel with keys in val[].  `sequential` only says how a round gets the merged code from
+// the rank: letters + rank, or (a list that spells a merged string before the merge producing it, or twice) code_of_rank[rank],
+// which the device reads from memory.  No table loses its eligibility to the keys and the value form of a slot stays what it was.
 struct NarrowTable {
   bool eligible = false;
+  bool sequential = false;             // code(merged[i]) == letters + i for every live merge i
+  std::vector<uint32_t> code_of_rank;  // [n_merges] code(merged[i]) of a live merge, kNarrowDead of any other
   std::vector<uint32_t> cp_of_code;  // the alphabet, ascending
   std::vector<NarrowSlot> slots;
   uint32_t bits = 0;
@@ -130,8 +140,15 @@ inline void narrow_build(const uint32_t *left, const uint32_t *right, const uint
   t.cp_of_code.erase(std::unique(t.cp_of_code.begin(), t.cp_of_code.end()), t.cp_of_code.end());
   if ((uint64_t)t.letters() + top > kNarrowMaxCodes) { t = NarrowTable(); return; }
   std::vector<NarrowSlot> entries;
+  t.code_of_rank.assign(n_merges, kNarrowDead);
+  t.sequential = true;
   for (uint32_t i = 0; i < n_merges; i++)
-    if (live[i]) entries.push_back(NarrowSlot{narrow_key(t.code(left[i]), t.code(right[i])), (i << 16) | t.code(merged[i])});
+    if (live[i]) {
+      const uint32_t g = t.code(merged[i]);
+      entries.push_back(NarrowSlot{narrow_key(t.code(left[i]), t.code(right[i])), (i << 16) | g});
+      t.code_of_rank[i] = g;
+      if (g != t.letters() + i) t.sequential = false;
+    }
   if (!narrow_place(entries, t.slots, t.bits)) { t = NarrowTable(); return; }
   t.eligible = true;
 }
