@@ -857,6 +857,45 @@ def wp_length_table(tokens):
     return out
 
 
+def _encode_out(n_ids, n_sent, status):
+    """the outputs every host encode fills: room for n_ids ids, the offsets, the statuses (or None) and the id count"""
+    return (np.empty(max(n_ids, 1), dtype=np.uint32), np.zeros(n_sent + 1, dtype=np.uint64),
+            np.zeros(max(n_sent, 1), dtype=np.uint8) if status else None, C.c_uint64())
+
+
+def _encode_host(entry, handle, text_u8, sent_off, status=False, flags=None, spans=None):
+    """One host-buffer encode of include/swt.h: lowercased packed text and its offsets in, arrays trimmed to the id count out
+    -> (ids uint32, offsets uint64[n+1]), then status uint8[n] for an entry that has per-sentence statuses, then (spans
+    uint32[n, 2], word uint32[n]) for one that takes a span flag word (`spans`).  flags: the trailing flag word of the BPE entries."""
+    n_sent = int(sent_off.size - 1)
+    out, out_off, st, nt = _encode_out(int(sent_off[-1]), n_sent, status)
+    args = [handle, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size, ptr(out_off, u64p)]
+    args += [ptr(st, u8p), C.byref(nt)] if status else [C.byref(nt)]
+    if flags is not None:
+        args.append(flags)
+    if spans is not None:
+        sp, word = np.zeros((out.size, 2), dtype=np.uint32), np.zeros(out.size, dtype=np.uint32)
+        args += [spans, ptr(sp, u32p), ptr(word, u32p)]
+    check(getattr(lib(), entry)(*args))
+    n = nt.value
+    return (out[:n], out_off) + ((st[:n_sent],) if status else ()) + ((sp[:n], word[:n]) if spans is not None else ())
+
+
+def _encode_joined(entry, handle, joined, n_sent, status=False, flags=None):
+    """The same for the `_joined` entries: join_texts' bytes in (not lowercased), the prepared text staying on the device;
+    None when a sentence needs the host's str.lower() (the entry leaves UINT64_MAX for the count)."""
+    out, out_off, st, nt = _encode_out(int(joined.size), n_sent, status)
+    need = np.zeros(max(n_sent, 1), dtype=np.uint8)
+    args = [handle, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size, ptr(out_off, u64p)]
+    args += [ptr(st, u8p), C.byref(nt), ptr(need, u8p)] if status else [C.byref(nt), ptr(need, u8p)]
+    if flags is not None:
+        args.append(flags)
+    check(getattr(lib(), entry)(*args))
+    if nt.value == 0xFFFFFFFFFFFFFFFF:
+        return None
+    return (out[:nt.value], out_off) + ((st[:n_sent],) if status else ())
+
+
 class BpeTable:
     """Device merge-rank table (swt_bpe_table)."""
 
@@ -888,27 +927,12 @@ class BpeTable:
 
     def encode(self, text_u8, sent_off, flags=0, _entry="swt_bpe_encode"):
         """host buffers in -> (ids uint32, offsets uint64[n+1])"""
-        n_sent = int(sent_off.size - 1)
-        n_bytes = int(sent_off[-1])
-        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        nt = C.c_uint64()
-        check(getattr(lib(), _entry)(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
-                                     ptr(out_off, u64p), C.byref(nt), flags))
-        return out[:nt.value], out_off
+        return _encode_host(_entry, self._h, text_u8, sent_off, flags=flags)
 
     def encode_joined(self, joined, n_sent, flags=0, _entry="swt_bpe_encode_joined"):
         """join_texts' bytes in (not lowercased) -> (ids, offsets), the prepared text staying on the device; None when a sentence
         needs the host's str.lower() (the caller goes pack_and_lower -> encode)"""
-        out = np.empty(max(int(joined.size), 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        need = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(getattr(lib(), _entry)(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
-                                     ptr(out_off, u64p), C.byref(nt), ptr(need, u8p), flags))
-        if nt.value == 0xFFFFFFFFFFFFFFFF:
-            return None
-        return out[:nt.value], out_off
+        return _encode_joined(_entry, self._h, joined, n_sent, flags=flags)
 
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags=0, stream=0):
         """device pointers (ints) in; enqueues on `stream` and returns"""
@@ -978,28 +1002,11 @@ class WpTrie:
         return bytes(buf[:n.value]).decode("utf-32-le", "surrogatepass")
 
     def encode(self, text_u8, sent_off):
-        n_sent = int(sent_off.size - 1)
-        n_bytes = int(sent_off[-1])
-        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(lib().swt_wp_encode(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
-                                  ptr(out_off, u64p), ptr(status, u8p), C.byref(nt)))
-        return out[:nt.value], out_off, status[:n_sent]
+        return _encode_host("swt_wp_encode", self._h, text_u8, sent_off, status=True)
 
     def encode_joined(self, joined, n_sent):
         """join_texts' bytes in (not lowercased) -> (ids, offsets, status), or None when a sentence needs the host's str.lower()"""
-        out = np.empty(max(int(joined.size), 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        need = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(lib().swt_wp_encode_joined(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
-                                         ptr(out_off, u64p), ptr(status, u8p), C.byref(nt), ptr(need, u8p)))
-        if nt.value == 0xFFFFFFFFFFFFFFFF:
-            return None
-        return out[:nt.value], out_off, status[:n_sent]
+        return _encode_joined("swt_wp_encode_joined", self._h, joined, n_sent, status=True)
 
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
@@ -1008,18 +1015,7 @@ class WpTrie:
         """encode() with, per token, where it came from (swt_wp_encode_spans) -> (ids, offsets, status, spans uint32[n, 2] = start
         and end inside the sentence in code points or bytes, word uint32[n] = index of the token's segment among those of its
         sentence that emit a token)"""
-        n_sent = int(sent_off.size - 1)
-        n_bytes = int(sent_off[-1])
-        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
-        spans = np.zeros((out.size, 2), dtype=np.uint32)
-        word = np.zeros(out.size, dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(lib().swt_wp_encode_spans(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
-                                        ptr(out_off, u64p), ptr(status, u8p), C.byref(nt), SPAN_CODEPOINTS if codepoints else 0,
-                                        ptr(spans, u32p), ptr(word, u32p)))
-        return out[:nt.value], out_off, status[:n_sent], spans[:nt.value], word[:nt.value]
+        return _encode_host("swt_wp_encode_spans", self._h, text_u8, sent_off, status=True, spans=SPAN_CODEPOINTS if codepoints else 0)
 
     def encode_spans_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, d_spans, d_word, codepoints=True,
                          stream=0):
@@ -1035,28 +1031,11 @@ class WpTrie:
 
     def encode_naive(self, text_u8, sent_off):
         """NaiveWP.tokenize over lowercased packed text -> (ids, offsets, status)"""
-        n_sent = int(sent_off.size - 1)
-        n_bytes = int(sent_off[-1])
-        out = np.empty(max(n_bytes, 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(lib().swt_wp_encode_naive(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size,
-                                        ptr(out_off, u64p), ptr(status, u8p), C.byref(nt)))
-        return out[:nt.value], out_off, status[:n_sent]
+        return _encode_host("swt_wp_encode_naive", self._h, text_u8, sent_off, status=True)
 
     def encode_naive_joined(self, joined, n_sent):
         """join_texts' bytes in (not lowercased) -> (ids, offsets, status), or None when a sentence needs the host's str.lower()"""
-        out = np.empty(max(int(joined.size), 1), dtype=np.uint32)
-        out_off = np.zeros(n_sent + 1, dtype=np.uint64)
-        status = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        need = np.zeros(max(n_sent, 1), dtype=np.uint8)
-        nt = C.c_uint64()
-        check(lib().swt_wp_encode_naive_joined(self._h, ptr(joined, u8p), int(joined.size), n_sent, ptr(out, u32p), out.size,
-                                               ptr(out_off, u64p), ptr(status, u8p), C.byref(nt), ptr(need, u8p)))
-        if nt.value == 0xFFFFFFFFFFFFFFFF:
-            return None
-        return out[:nt.value], out_off, status[:n_sent]
+        return _encode_joined("swt_wp_encode_naive_joined", self._h, joined, n_sent, status=True)
 
     def encode_naive_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_naive_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))

@@ -151,31 +151,26 @@ def unique_words_packed(corpus: List[str]):
 
 def _encode_packed(tokenizer, text_u8, off):
     """ids + offsets of a packed (already lowercased) batch through the tokenizer's device handle"""
-    if hasattr(tokenizer, "_trie") and tokenizer._trie is not None:  # FastWP
-        ids, ooff, status = tokenizer._trie.encode(text_u8, off)
-        bad = np.flatnonzero(status)
+    enc = tokenizer._enc
+    got = getattr(enc.handle(), enc.host)(text_u8, off)
+    ids, ooff = got[:2]
+    if enc.complain is not None:
+        bad = np.flatnonzero(got[2])
         if bad.size:
             i = int(bad[0])
-            tokenizer._raise_for_status(int(status[i]), text_u8[int(off[i]):int(off[i + 1])].tobytes().decode("utf-8", "replace"))
-        n_vocab = len(tokenizer._tokens)
-        if ids.size and int(ids.max()) > n_vocab + 1:
-            raise NotImplementedError("a multi-token NaiveWP.encode_word('##') corner (wordpiece.py:260-261) is not counted on the device")
-        return ids, ooff, n_vocab + 3
-    if hasattr(tokenizer, "_naive_trie") and not hasattr(tokenizer, "_trie"):  # NaiveWP
-        ids, ooff, status = tokenizer._ensure_naive_trie().encode_naive(text_u8, off)
-        bad = np.flatnonzero(status)
-        if bad.size:
-            i = int(bad[0])
-            tokenizer._raise_naive_status(int(status[i]), text_u8[int(off[i]):int(off[i + 1])].tobytes().decode("utf-8", "replace"))
-        return ids, ooff, len(tokenizer._naive_tokens) + 2
-    table = tokenizer._ensure_table()  # FastBPE
-    ids, ooff = table.encode(text_u8, off)
-    return ids, ooff, N.SYM_BASE + len(tokenizer._syms.strings) + 1
+            enc.complain(int(got[2][i]), text_u8[int(off[i]):int(off[i + 1])].tobytes().decode("utf-8", "replace"))
+    if enc.corner and ids.size and int(ids.max()) > len(enc.spelling()) + 1:
+        raise NotImplementedError("a multi-token NaiveWP.encode_word('##') corner (wordpiece.py:260-261) is not counted on the device")
+    return ids, ooff, enc.id_cap()
 
 
 def quality_metrics(tokenizer, test_corpus: List[str]) -> Dict[str, Any]:
     """Every tokenization metric of benchmarks() (benchmarks.py:331-346 and 354-357) for a FastBPE / NaiveWP / FastWP of this package:
     two batched encodes and one device histogram instead of a Python call per sentence and per unique word."""
+    from . import tokenizers as T
+
+    if not isinstance(tokenizer, (T.FastBPE, T.NaiveWP, T.FastWP)):  # (NaiveBPE has never been counted here)
+        raise TypeError("quality_metrics takes a FastBPE, NaiveWP or FastWP, not a %s" % type(tokenizer).__name__)
     if not isinstance(test_corpus, list) or not all(isinstance(s, str) for s in test_corpus):
         raise TypeError("Text must be a string.")
     n_sent = len(test_corpus)
@@ -289,25 +284,14 @@ def _canonical_map(tokenizer, canon: _Canon):
     BPE: 2 * n_sym entries over the merged symbols; [k] = strip(string_k) for an id without SWT_BPE_CONT, [n_sym + k] = string_k
     for an id with it (the token is "##" + string_k, which strips back to string_k); one-code-point symbols are their own
     canonical id, map_base = SYM_BASE.  WordPiece: strip(token) in id order, then "['UNK']", then "[UNK]"; map_base = 0."""
-    from . import tokenizers as T
-
-    intern = canon.intern
-    if isinstance(tokenizer, T.NaiveBPE):
-        if isinstance(tokenizer, T.FastBPE):
-            tokenizer._ensure_table()
-            strings = tokenizer._syms.strings
-        else:
-            tokenizer._ensure_naive_table()
-            strings = tokenizer._naive_syms.strings
+    intern, enc = canon.intern, tokenizer._enc
+    enc.handle()
+    if enc.flagged:
+        strings = enc.spelling().strings
         cmap = [intern(_strip1(s)) for s in strings] + [intern(s) for s in strings]
-        return np.array(cmap, dtype=np.uint32), N.SYM_BASE, True
-    if isinstance(tokenizer, T.FastWP):
-        tokens = tokenizer._tokens
     else:
-        tokenizer._ensure_naive_trie()
-        tokens = tokenizer._naive_tokens
-    cmap = [intern(_strip1(t)) for t in tokens] + [intern("['UNK']"), intern("[UNK]")]
-    return np.array(cmap, dtype=np.uint32), 0, False
+        cmap = [intern(_strip1(t)) for t in enc.names()]
+    return np.array(cmap, dtype=np.uint32), enc.len_base, enc.flagged
 
 
 def _encode_ids(tokenizer, texts: List[str]):
@@ -317,21 +301,16 @@ def _encode_ids(tokenizer, texts: List[str]):
         if not isinstance(texts, list):
             raise TypeError("Text must be a string.")
         return np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
-    from . import tokenizers as T
-
-    got = tokenizer.encode_ids_batch(texts)
-    if isinstance(tokenizer, T.NaiveBPE):
+    got, enc = tokenizer.encode_ids_batch(texts), tokenizer._enc
+    if enc.complain is None:
         return got
     ids, off, status = got
     bad = np.flatnonzero(status)
-    if isinstance(tokenizer, T.FastWP):
-        if bad.size:
-            tokenizer._raise_for_status(int(status[int(bad[0])]), texts[int(bad[0])])
-            raise RuntimeError("FastWP.encode_ids_batch: unknown status %d" % int(status[int(bad[0])]))
-        if ids.size and int(ids.max()) > len(tokenizer._tokens) + 1:
-            return None
-    elif bad.size:
-        tokenizer._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
+    if bad.size:
+        enc.complain(int(status[int(bad[0])]), texts[int(bad[0])])
+        raise RuntimeError("FastWP.encode_ids_batch: unknown status %d" % int(status[int(bad[0])]))  # (NaiveWP's always raises)
+    if enc.corner and ids.size and int(ids.max()) > len(enc.spelling()) + 1:
+        return None
     return ids, off
 
 

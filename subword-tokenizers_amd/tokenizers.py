@@ -16,6 +16,7 @@ is no CPU fallback -- without a GPU the compute calls raise `NoDeviceError`.
 """
 import json
 import os
+import weakref
 from collections import Counter
 from typing import Dict, List, Optional, Tuple
 
@@ -76,8 +77,8 @@ class SubwordTokenizer:
     def vocab_length(self, corpus: List[str]) -> int:
         return len({symbol for example in corpus for symbol in example})
 
-    # -- model-ready batches (not in the reference; batching.py).  A class supplies _batch_vocabulary,
-    # encode_ids_batch, _batch_encode_spans and _batch_encode_dev.
+    # -- model-ready batches (not in the reference; batching.py).  A class supplies its _Encoder as `_enc` and
+    # encode_ids_batch; the hooks of batching.py are at the end of this class.
     def vocab_list(self) -> List[str]:
         """The token strings in dense-id order: row i of a model's embedding table belongs to vocab_list()[i].  It depends on
         nothing but what save_resources keeps."""
@@ -179,8 +180,14 @@ class SubwordTokenizer:
             return ""
         return batching.decode_batch(self, ids.reshape(1, -1), None, skip_special_tokens)[0]
 
+    def _batch_vocabulary(self):
+        return self._enc.vocabulary()
+
     def _batch_encode_spans(self, texts):
         return self.encode_spans_batch(texts)
+
+    def _batch_encode_dev(self, *args):
+        return _encode_dev(self._enc, *args)
 
 
 _CLS_CACHE: Dict[str, int] = {}
@@ -225,6 +232,157 @@ def _raise_span_mismatch(status: int, i: int, text: str) -> None:
 _PLAIN_INTERN = _SymbolTable.intern  # (a test swaps intern() for another to force the collision replay: then the Python loop runs)
 
 
+# ------------------------------------------------------------------------------------------------------
+# The batch calls: one body per operation, written against what a class says about its encoder
+
+class _Encoder:
+    """What the batch calls of one tokenizer class differ in (the Python side of csrc/swt_tile.h's HostEncoder).  A tokenizer
+    makes one in __init__ and keeps it as `_enc`.  The record owns nothing but its caches: the handle and what spells its ids
+    stay the tokenizer's attributes, read by name every time, and are built, rebuilt and closed where they always were.
+
+    ensure: the tokenizer's method that returns the live N.BpeTable / N.WpTrie; spelling: its attribute that spells the ids,
+    a _SymbolTable (BPE) or the token list (WordPiece); naive: the `encode_naive*` entries instead of `encode*`; complain:
+    what raises for a sentence's status (WordPiece; None: BPE, which has no statuses); corner: an id past "[UNK]" stands for
+    the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE)."""
+
+    def __init__(self, tok, ensure, spelling, naive, error="Text to tokenize must be a string.", complain=None, corner=False,
+                 first=False):
+        self._tok, self._ensure, self._spelling = weakref.proxy(tok), ensure, spelling  # (no cycle: a tokenizer dies with its last name)
+        self.host = "encode_naive" if naive else "encode"  # the three call forms on the handle, by name
+        self.joined, self.dev = self.host + "_joined", self.host + "_dev"
+        self.error, self.complain, self.corner, self.first = error, complain, corner, first
+        self.flagged = complain is None  # BPE ids carry SWT_BPE_CONT over SYM_BASE + k; WordPiece ids index the token list
+        self.len_base = N.SYM_BASE if self.flagged else 0
+        self._cache: dict = {}
+
+    def handle(self):
+        return getattr(self._tok, self._ensure)()
+
+    def spelling(self):
+        """as the last handle() left it"""
+        return getattr(self._tok, self._spelling)
+
+    def names(self) -> List[str]:
+        """WordPiece: the token of every id below the corner's"""
+        return self.spelling() + ["['UNK']", "[UNK]"]
+
+    def id_cap(self) -> int:
+        """one past the largest id (without SWT_BPE_CONT) an encode can return"""
+        sp = self.spelling()
+        return N.SYM_BASE + len(sp.strings) + 1 if self.flagged else len(sp) + 2 + self.corner
+
+    def _cached(self, what, make, spelling=None, *more):
+        """make(spelling) once per spelling object and its length: a rebuilt handle comes with a new one"""
+        sp = self.spelling() if spelling is None else spelling
+        key = (len(sp.strings) if self.flagged else len(sp),) + more
+        hit = self._cache.get(what)
+        if hit is None or hit[0] is not sp or hit[1] != key:
+            hit = self._cache[what] = (sp, key, make(sp))
+        return hit[2]
+
+    def lengths(self, spelling=None) -> np.ndarray:
+        """the length table of swt_token_spans for ids spelled by `spelling` (None: this encoder's own)"""
+        return self._cached("lengths", (lambda sp: N.bpe_length_table(sp.strings)) if self.flagged else N.wp_length_table, spelling)
+
+    def vocabulary(self):
+        """the dense ids of batching.py over the live handle's ids"""
+        self.handle()
+        if not self.flagged:
+            return self._cached("vocabulary", batching.wp_vocabulary)
+        merges = self._tok.merges_list
+        return self._cached("vocabulary", lambda sp: batching.bpe_vocabulary(merges, sp), None, len(merges))
+
+
+def _raise_flagged(enc: _Encoder, status, texts) -> None:
+    """what tokenize() raises for the first text with a status; a status FastWP's complain does not know passes"""
+    for i in np.flatnonzero(status):
+        enc.complain(int(status[i]), texts[int(i)])
+
+
+def _encode_ids(enc: _Encoder, texts):
+    """encode_ids_batch of every class: the argument checks in the class's order, then the route -- past 64 texts the joined
+    call (strings -> joined bytes -> ids: the device splits, lowercases (utils.py:27) and encodes, the prepared
+    text never comes back); texts with U+0000 inside, or that only str.lower() lowercases, and small batches go the long way"""
+    if not isinstance(texts, list):
+        raise TypeError(enc.error)
+    if enc.first:
+        handle = enc.handle()
+    few = len(texts) <= 64  # past that join_texts raises for an item that is no str, on its way through them
+    if few and not all(isinstance(t, str) for t in texts):
+        raise TypeError(enc.error)
+    if not enc.first:
+        try:
+            handle = enc.handle()
+        except AttributeError:  # FastWP before load/train, as the reference: but the argument's TypeError goes first
+            if not all(isinstance(t, str) for t in texts):
+                raise TypeError(enc.error) from None
+            raise
+    if not few:
+        joined, n_nul = N.join_texts(texts, enc.error)
+        if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
+            got = getattr(handle, enc.joined)(joined, len(texts))
+            if got is not None:
+                return got
+    text, off = N.pack_and_lower(texts)  # utils.py:27 / wordpiece.py:248 lower()
+    return getattr(handle, enc.host)(text, off)
+
+
+def _bpe_tokens(enc: _Encoder, ids, off=None):
+    """BPE ids -> their token strings, one list per sentence of `off` (None: one flat list)"""
+    st = enc.spelling()
+    ids = np.asarray(ids, dtype=np.uint32)
+    if ids.size < 4096:
+        toks = [("##" + st.string(t)) if t & N.BPE_CONT else st.string(t) for t in map(int, ids)]
+        return toks if off is None else [toks[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
+    # large outputs: spell each DISTINCT id once (found by a presence map over the id space, not a sort), then hand out references
+    # (the per-token Python loop was 1.5 s per 2 M tokens)
+    key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit
+    spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
+    cap = 2 * (N.SYM_BASE + len(st.strings))
+    if off is None:
+        return N.nested_lists_by_key(key, cap, spell, np.array([0, ids.size], dtype=np.uint64))[0]
+    return N.nested_lists_by_key(key, cap, spell, off)
+
+
+def _encode_spans(enc: _Encoder, texts):
+    """encode_spans_batch by tiling (NaiveBPE, FastBPE, NaiveWP): the host encode's results with (spans, word ids) behind them.
+    The text is packed once and sent to the device twice, for the encode and for swt_token_spans."""
+    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+        raise TypeError("Text to tokenize must be a string.")
+    handle = enc.handle()
+    text, off = N.pack_and_lower(texts)
+    got = getattr(handle, enc.host)(text, off)
+    if enc.complain is not None:
+        _raise_flagged(enc, got[2], texts)
+    spans, word, status = N.token_spans(text, off, got[0], got[1], enc.lengths(), enc.len_base, enc.flagged)
+    if status.any():
+        _raise_span_mismatch(1, int(np.flatnonzero(status)[0]), "")
+    return got + (spans, word)
+
+
+def _encode_dev(enc: _Encoder, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
+    """the `_dev` encode on the caller's torch buffers, then swt_token_spans_dev when spans are wanted
+    -> [(status tensor, what to raise for a status)]"""
+    import torch
+    call, checks = getattr(enc.handle(), enc.dev), []
+    if enc.complain is None:
+        call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
+    else:
+        d_status = empty(n_sent + 8, torch.uint8)
+        call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
+        checks.append((d_status, lambda st, i, text: enc.complain(st, text)))
+    if d_spans is not None:
+        lengths = enc.lengths()
+        d_len = empty(lengths.size + 4, torch.int32)
+        d_len[:lengths.size].copy_(torch.from_numpy(lengths.view(np.int32)))
+        d_span_status = empty(n_sent + 8, torch.uint8)
+        N.check(N.lib().swt_token_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_len.data_ptr(), enc.len_base,
+                                            int(lengths.size), int(enc.flagged), N.SPAN_CODEPOINTS, d_spans, d_word,
+                                            d_span_status.data_ptr(), stream))
+        checks.append((d_span_status, _raise_span_mismatch))
+    return checks
+
+
 class NaiveBPE(SubwordTokenizer):
     """Byte-Pair Encoding (bpe.py:9-189).  `train` runs on the device; `encode_word`/`tokenize` keep the
     reference's didactic O(merges x length) loop in Python (out of the GPU scope, SURVEY.md section 2 row 11);
@@ -242,6 +400,7 @@ class NaiveBPE(SubwordTokenizer):
         self._naive_syms = _SymbolTable()
         self._naive_merges: Optional[list] = None  # the list the handle was built from
         self._train_merges: Optional[list] = None  # the merges _train_ids name (merges_list itself may be changed later)
+        self._enc = _Encoder(self, "_ensure_naive_table", "_naive_syms", naive=True)
 
     # -- bpe.py:25-48
     def _replace_pair(self, pair: Tuple[str, str], word: List[str]) -> List[str]:
@@ -400,59 +559,28 @@ class NaiveBPE(SubwordTokenizer):
     def encode_ids_batch(self, texts: List[str]) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
         over this object's own symbol table (decode_ids spells them)."""
-        if not isinstance(texts, list) or (len(texts) <= 64 and not all(isinstance(t, str) for t in texts)):
-            raise TypeError("Text to tokenize must be a string.")
-        table = self._ensure_naive_table()
-        if len(texts) > 64:
-            joined, n_nul = N.join_texts(texts, "Text to tokenize must be a string.")  # as FastBPE.encode_ids_batch
-            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
-                got = table.encode_naive_joined(joined, len(texts))
-                if got is not None:
-                    return got
-        text, off = N.pack_and_lower(texts)  # utils.py:27 lower()
-        return table.encode_naive(text, off)
+        return _encode_ids(self._enc, texts)
 
     def decode_ids(self, ids) -> List[str]:
-        st = self._naive_syms
-        return [("##" + st.string(t)) if t & N.BPE_CONT else st.string(t) for t in map(int, np.asarray(ids, dtype=np.uint32))]
+        return _bpe_tokens(self._enc, ids)
 
     def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
         """[tokenize(t) for t in texts]"""
-        ids, off = self.encode_ids_batch(texts)
-        if ids.size < 4096:
-            toks = self.decode_ids(ids)
-            return [toks[int(off[i]):int(off[i + 1])] for i in range(len(texts))]
-        st = self._naive_syms
-        key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit: each DISTINCT id is spelled once
-        spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
-        return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, off)
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts))
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
     def _span_parts(self):
         """-> (the host-buffer encode of this class, the symbol table its ids are spelled from)"""
-        table = self._ensure_naive_table()
-        return table.encode_naive, self._naive_syms
+        return getattr(self._enc.handle(), self._enc.host), self._enc.spelling()
 
-    def _span_lengths(self, syms) -> np.ndarray:
-        # rebuilt whenever the table it belongs to was: a rebuild makes a new _SymbolTable
-        cached = getattr(self, "_span_len", None)
-        if cached is None or cached[0] is not syms or cached[1] != len(syms.strings):
-            cached = self._span_len = (syms, len(syms.strings), N.bpe_length_table(syms.strings))
-        return cached[2]
+    def _span_lengths(self, spelling=None) -> np.ndarray:
+        return self._enc.lengths(spelling)
 
     def encode_spans_batch(self, texts: List[str]):
         """texts -> (ids, offsets, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its (start, end) in
         code points of text.lower() -- preprocessing's convention (utils.py:27-29) -- and the index of its word in the sentence.
         The text is packed once and sent to the device twice, for the encode and for swt_token_spans."""
-        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
-            raise TypeError("Text to tokenize must be a string.")
-        encode, syms = self._span_parts()
-        text, off = N.pack_and_lower(texts)
-        ids, tok_off = encode(text, off)
-        spans, word, status = N.token_spans(text, off, ids, tok_off, self._span_lengths(syms), N.SYM_BASE, True)
-        if status.any():
-            raise RuntimeError("token spans: the tokens of text %d do not tile it (a bug in this library)" % int(np.flatnonzero(status)[0]))
-        return ids, tok_off, spans, word
+        return _encode_spans(self._enc, texts)
 
     def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
         """[(token, (start, end)), ...]: tokenize(text) in the shape of one preprocessing row"""
@@ -460,33 +588,6 @@ class NaiveBPE(SubwordTokenizer):
             raise TypeError("Text to tokenize must be a string.")
         ids, _, spans, _ = self.encode_spans_batch([text])
         return [(tok, (int(s), int(e))) for tok, (s, e) in zip(self.decode_ids(ids), spans.tolist())]
-
-    # -- model-ready batches: the hooks of SubwordTokenizer.encode_batch
-    def _batch_vocabulary(self):
-        _, syms = self._span_parts()
-        key = (len(syms.strings), len(self.merges_list))
-        cached = getattr(self, "_batch_voc", None)
-        if cached is None or cached[0] is not syms or cached[1] != key:  # a rebuilt table has a new _SymbolTable
-            cached = self._batch_voc = (syms, key, batching.bpe_vocabulary(self.merges_list, syms))
-        return cached[2]
-
-    def _batch_dev_call(self):
-        return self._ensure_naive_table().encode_naive_dev
-
-    def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
-        """the `_dev` encode on the caller's torch buffers, then swt_token_spans_dev when spans are wanted
-        -> [(status tensor, what to raise for a status)]"""
-        import torch
-        self._batch_dev_call()(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
-        if d_spans is None:
-            return []
-        lengths = self._span_lengths(self._span_parts()[1])
-        d_len = empty(lengths.size + 4, torch.int32)
-        d_len[:lengths.size].copy_(torch.from_numpy(lengths.view(np.int32)))
-        d_status = empty(n_sent + 8, torch.uint8)
-        N.check(N.lib().swt_token_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_len.data_ptr(), N.SYM_BASE, int(lengths.size),
-                                            1, N.SPAN_CODEPOINTS, d_spans, d_word, d_status.data_ptr(), stream))
-        return [(d_status, _raise_span_mismatch)]
 
     # -- bpe.py:160-164
     def reset(self) -> None:
@@ -520,6 +621,7 @@ class FastBPE(NaiveBPE):
         self._bpe_ranks: Dict[Tuple[str, str], int] = {}
         self._table: Optional[N.BpeTable] = None
         self._syms = _SymbolTable()
+        self._enc = _Encoder(self, "_ensure_table", "_syms", naive=False, error="Text must be a string.", first=True)
 
     def _build_table(self) -> None:
         # bpe.py:200 / :257
@@ -559,51 +661,15 @@ class FastBPE(NaiveBPE):
         return {(seq[i], seq[i + 1]) for i in range(len(seq) - 1)}
 
     def decode_ids(self, ids) -> List[str]:
-        st = self._syms
-        one = lambda t: ("##" + st.string(t)) if t & N.BPE_CONT else st.string(t)
-        ids = np.asarray(ids, dtype=np.uint32)
-        if ids.size < 4096:
-            return [one(t) for t in map(int, ids)]
-        # large outputs: spell each DISTINCT id once, then hand out references (the per-token Python loop was 1.5 s per 2 M tokens)
-        key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit
-        spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
-        return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, np.array([0, ids.size], dtype=np.uint64))[0]
+        return _bpe_tokens(self._enc, ids)
 
-    # -- batch entry points (not in the reference)
+    # -- batch entry points (not in the reference); FastBPE's own, like the reference's methods of the same class
     def encode_ids_batch(self, texts: List[str]) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]); ids as defined in include/swt.h."""
-        if not isinstance(texts, list):
-            raise TypeError("Text must be a string.")
-        table = self._ensure_table()
-        if len(texts) > 64:
-            # strings -> joined bytes -> ids: the device splits, lowercases (utils.py:27; SURVEY.md 8f-2) and encodes, the
-            # prepared text never comes back.  Texts with U+0000 inside, or that only str.lower() lowercases, go the long way.
-            joined, n_nul = N.join_texts(texts)  # TypeError for an item that is no str
-            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
-                got = table.encode_joined(joined, len(texts))
-                if got is not None:
-                    return got
-        elif not all(isinstance(t, str) for t in texts):
-            raise TypeError("Text must be a string.")
-        text, off = N.pack_and_lower(texts)
-        return table.encode(text, off)
+        return _encode_ids(self._enc, texts)
 
     def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
-        ids, off = self.encode_ids_batch(texts)
-        if ids.size < 4096:
-            toks = self.decode_ids(ids)
-            return [toks[int(off[i]):int(off[i + 1])] for i in range(len(texts))]
-        # spell each DISTINCT id once (found by a presence map over the id space, not a sort), then hand out references
-        st = self._syms
-        key = (ids << np.uint32(1)) | (ids >> np.uint32(31))  # symbol * 2 + the BPE_CONT bit
-        spell = lambda k: ("##" + st.string(k >> 1)) if k & 1 else st.string(k >> 1)
-        return N.nested_lists_by_key(key, 2 * (N.SYM_BASE + len(st.strings)), spell, off)
-
-    def _span_parts(self):
-        return self._ensure_table().encode, self._syms
-
-    def _batch_dev_call(self):
-        return self._ensure_table().encode_dev
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts))
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -670,6 +736,8 @@ class NaiveWP(SubwordTokenizer):
         self._naive_trie: Optional[N.WpTrie] = None  # built from sorted(vocab) on the first batch call
         self._naive_tokens: List[str] = []
         self._naive_vocab: Optional[frozenset] = None  # the vocabulary the handle was built from
+        # (FastWP puts its own in `_enc`; the methods it inherits that answer with NaiveWP's tokens keep to `_naive_enc`)
+        self._enc = self._naive_enc = _Encoder(self, "_ensure_naive_trie", "_naive_tokens", naive=True, complain=self._raise_naive_status)
 
     # -- wordpiece.py:29-103: the merge loop, on the device
     def train(self, corpus, max_vocab: int = 30_000):
@@ -794,34 +862,18 @@ class NaiveWP(SubwordTokenizer):
     def encode_ids_batch(self, texts: List[str]):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]): tokenize() of every text on the device.  ids index
         sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns."""
-        if not isinstance(texts, list) or (len(texts) <= 64 and not all(isinstance(t, str) for t in texts)):
-            raise TypeError("Text to tokenize must be a string.")
-        trie = self._ensure_naive_trie()
-        if len(texts) > 64:
-            joined, n_nul = N.join_texts(texts, "Text to tokenize must be a string.")
-            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
-                got = trie.encode_naive_joined(joined, len(texts))
-                if got is not None:
-                    return got
-        text, off = N.pack_and_lower(texts)  # utils.py:27 lower(), on the device
-        return trie.encode_naive(text, off)
+        return _encode_ids(self._enc, texts)
 
     def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
         """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
         deviation: the reference hangs)."""
         ids, off, status = self.encode_ids_batch(texts)
-        bad = np.flatnonzero(status)
-        if bad.size:
-            self._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
-        return N.nested_lists(self._naive_tokens + ["['UNK']", "[UNK]"], ids, off)
+        _raise_flagged(self._enc, status, texts)
+        return N.nested_lists(self._enc.names(), ids, off)
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
-    def _span_lengths(self) -> np.ndarray:
-        # rebuilt whenever the trie was: _ensure_naive_trie makes a new token list
-        cached = getattr(self, "_span_len", None)
-        if cached is None or cached[0] is not self._naive_tokens:
-            cached = self._span_len = (self._naive_tokens, N.wp_length_table(self._naive_tokens))
-        return cached[1]
+    def _span_lengths(self, spelling=None) -> np.ndarray:
+        return self._naive_enc.lengths(spelling)
 
     def encode_spans_batch(self, texts: List[str]):
         """texts -> (ids, offsets, status, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its
@@ -829,18 +881,7 @@ class NaiveWP(SubwordTokenizer):
         the sentence.  A text on which the reference never returns raises as in tokenize_batch.  The text is packed once and sent
         to the device twice, for the encode and for swt_token_spans.  FastWP inherits this method unchanged: called on a FastWP
         it answers with NaiveWP's tokens over the same vocabulary; FastWP's own tokens come from fast_encode_spans_batch."""
-        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
-            raise TypeError("Text to tokenize must be a string.")
-        trie = self._ensure_naive_trie()
-        text, off = N.pack_and_lower(texts)
-        ids, tok_off, status = trie.encode_naive(text, off)
-        bad = np.flatnonzero(status)
-        if bad.size:
-            self._raise_naive_status(int(status[int(bad[0])]), texts[int(bad[0])])
-        spans, word, st = N.token_spans(text, off, ids, tok_off, self._span_lengths(), 0, False)
-        if st.any():
-            raise RuntimeError("token spans: the tokens of text %d do not tile it (a bug in this library)" % int(np.flatnonzero(st)[0]))
-        return ids, tok_off, status, spans, word
+        return _encode_spans(self._naive_enc, texts)
 
     def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
         """[(token, (start, end)), ...]: NaiveWP.tokenize(text) in the shape of one preprocessing row (on a FastWP too, which
@@ -848,35 +889,8 @@ class NaiveWP(SubwordTokenizer):
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
         ids, _, _, spans, _ = self.encode_spans_batch([text])
-        names = self._naive_tokens + ["['UNK']", "[UNK]"]
+        names = self._naive_enc.names()
         return [(names[i], (int(s), int(e))) for i, (s, e) in zip(ids.tolist(), spans.tolist())]
-
-    # -- model-ready batches: the hooks of SubwordTokenizer.encode_batch
-    def _batch_tokens(self) -> List[str]:
-        self._ensure_naive_trie()
-        return self._naive_tokens
-
-    def _batch_vocabulary(self):
-        tokens = self._batch_tokens()
-        cached = getattr(self, "_batch_voc", None)
-        if cached is None or cached[0] is not tokens:  # a rebuilt trie has a new token list
-            cached = self._batch_voc = (tokens, batching.wp_vocabulary(tokens))
-        return cached[1]
-
-    def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
-        import torch
-        d_status = empty(n_sent + 8, torch.uint8)
-        self._ensure_naive_trie().encode_naive_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
-        checks = [(d_status, lambda st, i, text: self._raise_naive_status(st, text))]
-        if d_spans is not None:
-            lengths = self._span_lengths()
-            d_len = empty(lengths.size + 4, torch.int32)
-            d_len[:lengths.size].copy_(torch.from_numpy(lengths.view(np.int32)))
-            d_span_status = empty(n_sent + 8, torch.uint8)
-            N.check(N.lib().swt_token_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_len.data_ptr(), 0, int(lengths.size), 0,
-                                                N.SPAN_CODEPOINTS, d_spans, d_word, d_span_status.data_ptr(), stream))
-            checks.append((d_span_status, _raise_span_mismatch))
-        return checks
 
     @staticmethod
     def _raise_naive_status(st: int, text: str) -> None:
@@ -977,6 +991,12 @@ class FastWP(NaiveWP):
         self._tokens: List[str] = []
         self._corner: Optional[List[str]] = None
         self.vocab_trie: Optional[TrieView] = None
+        self._enc = _Encoder(self, "_ensure_trie", "_tokens", naive=False, complain=self._raise_for_status, corner=True)
+
+    def _ensure_trie(self) -> N.WpTrie:
+        if self._trie is None:
+            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")  # as the reference before load/train
+        return self._trie
 
     def _build_trie(self) -> None:
         # utils.py:75-85; ids = position in the sorted vocabulary (vocab.json order is arbitrary, wordpiece.py:196)
@@ -1017,27 +1037,11 @@ class FastWP(NaiveWP):
     # -- batch entry points (not in the reference)
     def encode_ids_batch(self, texts: List[str]):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status."""
-        if not isinstance(texts, list):
-            raise TypeError("Text to tokenize must be a string.")
-        if len(texts) <= 64 and not all(isinstance(t, str) for t in texts):
-            raise TypeError("Text to tokenize must be a string.")
-        if self._trie is None:
-            if not all(isinstance(t, str) for t in texts):
-                raise TypeError("Text to tokenize must be a string.")
-            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")  # as the reference before load/train
-        if len(texts) > 64:
-            joined, n_nul = N.join_texts(texts, "Text to tokenize must be a string.")  # as FastBPE.encode_ids_batch
-            if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
-                got = self._trie.encode_joined(joined, len(texts))
-                if got is not None:
-                    return got
-        text, off = N.pack_and_lower(texts)  # wordpiece.py:248 lower(), on the device; the " " is implicit
-        return self._trie.encode(text, off)
+        return _encode_ids(self._enc, texts)
 
     def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
         ids, off, status = self.encode_ids_batch(texts)
-        for i in np.flatnonzero(status):
-            self._raise_for_status(int(status[i]), texts[int(i)])
+        _raise_flagged(self._enc, status, texts)
         if ids.size and int(ids.max()) <= len(self._tokens) + 1:  # no multi-token corner: one table, references handed out
             if ids.size < 4096:
                 toks = self._decode(ids)
@@ -1058,12 +1062,10 @@ class FastWP(NaiveWP):
         return from raises as in tokenize_batch.  One pack, one trip to the device."""
         if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
             raise TypeError("Text to tokenize must be a string.")
-        if self._trie is None:
-            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")
+        trie = self._ensure_trie()
         text, off = N.pack_and_lower(texts)
-        ids, tok_off, status, spans, word = self._trie.encode_spans(text, off, codepoints=True)
-        for i in np.flatnonzero(status):
-            self._raise_for_status(int(status[i]), texts[int(i)])
+        ids, tok_off, status, spans, word = trie.encode_spans(text, off, codepoints=True)
+        _raise_flagged(self._enc, status, texts)
         return ids, tok_off, status, spans, word
 
     def fast_tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
@@ -1078,22 +1080,16 @@ class FastWP(NaiveWP):
         return out
 
     # -- model-ready batches: FastWP's own ids and, with offsets, the spans of its trie walk
-    def _batch_tokens(self) -> List[str]:
-        if self._trie is None:
-            raise AttributeError("'FastWP' object has no attribute 'vocab_trie'")
-        return self._tokens
-
     def _batch_encode_spans(self, texts):
         return self.fast_encode_spans_batch(texts)
 
     def _batch_encode_dev(self, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
         import torch
-        d_status = empty(n_sent + 8, torch.uint8)
+        trie, d_status = self._ensure_trie(), empty(n_sent + 8, torch.uint8)
         if d_spans is None:
-            self._trie.encode_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
+            trie.encode_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
         else:
-            self._trie.encode_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, d_spans, d_word,
-                                        True, stream)
+            trie.encode_spans_dev(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, d_spans, d_word, True, stream)
         return [(d_status, lambda st, i, text: self._raise_for_status(st, text))]
 
     @staticmethod
