@@ -756,6 +756,95 @@ int swt_decode_rows_dev(const void *d_ids, const uint8_t *d_mask, uint64_t rows,
                         const uint32_t *d_tok_off, const uint8_t *d_tok_flags, uint32_t n_tok, uint32_t flags, const uint64_t *d_text_off,
                         uint8_t *d_out_text, uint64_t text_cap, void *stream);
 int swt_decode_capacity(uint32_t *cols_per_step, uint32_t *scan_group);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fine-tuning labels: over the finished rows of the batch calls above -- word[rows, width] (out_word), seq[rows, width] (int8,
+ * the pair rows' out_seq), spans[rows, width, 2] (out_spans), sample[rows] (out_sample) and len[rows] (out_len) -- the labels of
+ * token classification and of extractive question answering, and the best answer span from a model's logits.  The reference has
+ * nothing of the sort; tests/label_cases.py holds these semantics and the kernels equal it element by element.
+ *
+ * A TOKEN COLUMN of row r is a column c that holds a token of the side in question: seq[r, c] == side (0 or 1) when seq is given,
+ * word[r, c] != 0xFFFFFFFF when seq is NULL (single-sentence rows).  sample[r] names the row's text; NULL: row r is text r.  A row
+ * with sample[r] >= n_samples gets the "nothing" result of the call and is counted in info where info has a place for it.
+ * Labels and positions are int32, int64 with SWT_LABEL_IDS64.
+ *
+ * 1. swt_label_words: the labels lab[lab_off[s] .. lab_off[s + 1]) (int32; lab_off uint64[n_samples + 1], non-decreasing, ending
+ * at or below n_lab) of the words of text s onto its rows.  For column c of row r, s = sample[r], k = word[r, c]:
+ *   no token column, or a row of no text: ignore;
+ *   k >= lab_off[s + 1] - lab_off[s]: ignore, the column counts in info[2] and out_status[r] (uint8[rows], may be NULL) is 1,
+ *     else 0;
+ *   c is the FIRST column of its word in this row -- c == 0, or column c - 1 is no token column, or word[r, c - 1] != k:
+ *     l = lab[lab_off[s] + k].  A word cut by a window's edge is labelled again in the next window, as the usual recipe does
+ *     and as the masked-LM rule treats a cut word;
+ *   any other column of the word: ignore; with SWT_LABEL_ALL_TOKENS l, and where inside (int32[n_inside], may be NULL) is given
+ *     and 0 <= l < n_inside, inside[l] -- the B-x to I-x map of BIO tagging.
+ * info[4] (may be NULL): columns given a label, token columns left at ignore as non-first, token columns whose word has no
+ * label, rows of no text (their columns are in none of the first three).
+ *
+ * 2. swt_answer_positions: the answer's characters ans[s] = (a, e) (uint32[n_samples, 2], in the unit of spans; a == 0xFFFFFFFF
+ * or a >= e: the text has no answer) as start and end columns.  C: the token columns of the row in order, c0 the first, c1 the
+ * last.  The row HOLDS the answer iff C is not empty, the text has an answer, spans[c0].start <= a and spans[c1].end >= e; then
+ * start = max{c in C: spans[c].start <= a}, end = min{c in C: spans[c].end >= e} and out_has[r] = 1.  Otherwise both positions
+ * are the NOTHING COLUMN and out_has[r] = 0: with SWT_ANSWER_CLS the [CLS] column -- 0, or with SWT_ANSWER_PAD_LEFT (which needs
+ * len) width - len[r], 0 where len[r] is 0 or above the width -- and `ignore` without.  This is the recipe of the usual QA preprocessing with its
+ * two scans confined to C; the recipe's first loop runs on into [SEP] and the padding, whose offsets are (0, 0), when the answer
+ * starts in the window's last token: that quirk is not reproduced.  out_has (uint8[rows]) and out_hit (uint8[n_samples]; zeroed
+ * by the call, 1 where some row holds the text's answer) may be NULL.  info[3] (may be NULL): rows that hold their answer, rows
+ * of a text that do not, rows of no text.
+ *
+ * 3. swt_answer_best: from start_logit and end_logit (float32[rows, width]) the best span of every row and of every text.  The
+ * candidates of a row are the pairs of token columns (i, j), i <= j < i + max_len (max_len >= 1; a larger value acts as width);
+ * the score is the float32 sum start_logit[i] + end_logit[j], one IEEE addition; a candidate whose score is a NaN is none.  The
+ * order: higher score, then smaller i, then smaller j -- total, so that the result does not depend on how it is reduced.  A
+ * row's result (out_row_score, out_row_start, out_row_end; each may be NULL) is its first candidate, (-inf, -1, -1) without one;
+ * a candidate at -inf is one.  `sample` must not decrease: a text's rows are contiguous, as the window plans emit them (the host
+ * form checks; the `_dev` form then leaves which run of such a text is reported undefined, and writes nothing out of place).
+ * Per text (all required when n_samples > 0): the first of its rows' results in the order (higher score, smaller row) as
+ * out_score, out_row, out_start_col, out_end_col, out_char_start = spans[row, start_col].start, out_char_end =
+ * spans[row, end_col].end; (-inf, -1, -1, -1, 0, 0) for a text with no row or no candidate.  out_null_score: with SWT_ANSWER_CLS
+ * the least start_logit[cls] + end_logit[cls] over the text's rows that is no NaN (the [CLS] column as in 2.), +inf without such
+ * a row or without the flag.  info[2] (may be NULL): rows with a candidate, texts with one.  Fewer than 2^31 rows.
+ *
+ * SWT_ERR_INVALID, swt_last_error naming the argument: a NULL array that is not optional (word may be NULL in 2. and 3. when seq
+ * is given); width == 0 with rows > 0; 2^32 rows or more; 2^31 columns or more; 2^32 texts or more; a side that is not 0 or 1
+ * with seq; an unknown flag; an array that is not aligned to its element type; an output that shares a byte with another array;
+ * max_len == 0; in the host forms a lab_off that decreases or runs past n_lab, and a sample that decreases in 3.
+ * rows == 0 succeeds: info and out_hit zeroed, every text's "nothing" record written.  The host forms check everything before
+ * anything touches the device and need none for rows == 0.  The `_dev` forms take device pointers (16-byte alignment lets them
+ * take the wide loads and stores), enqueue on the stream and do not synchronise; they write every element of every output given
+ * and nothing else.  With d_info (and swt_answer_best_dev always) they keep counts and rows' results between their launches in a
+ * workspace of the process: no two such calls at once on different streams.
+ * swt_label_capacity: the columns of a row one step covers, and the rows of one workgroup of the reduction over a text's rows
+ * (csrc/swt_labels.hip). */
+#define SWT_LABEL_ALL_TOKENS 1u
+#define SWT_LABEL_IDS64 4u /* the value of SWT_BATCH_IDS64 */
+#define SWT_ANSWER_CLS 1u
+#define SWT_ANSWER_PAD_LEFT 2u
+int swt_label_words(const uint32_t *word, const int8_t *seq, int32_t side, const uint32_t *sample, uint64_t rows, uint32_t width,
+                    const uint64_t *lab_off, const int32_t *lab, uint64_t n_lab, uint64_t n_samples, const int32_t *inside, uint32_t n_inside,
+                    int32_t ignore, uint32_t flags, void *out_labels, uint8_t *out_status, uint64_t *info);
+int swt_label_words_dev(const uint32_t *d_word, const int8_t *d_seq, int32_t side, const uint32_t *d_sample, uint64_t rows, uint32_t width,
+                        const uint64_t *d_lab_off, const int32_t *d_lab, uint64_t n_lab, uint64_t n_samples, const int32_t *d_inside,
+                        uint32_t n_inside, int32_t ignore, uint32_t flags, void *d_out_labels, uint8_t *d_out_status, uint64_t *d_info,
+                        void *stream);
+int swt_answer_positions(const uint32_t *spans, const uint32_t *word, const int8_t *seq, int32_t side, const uint32_t *sample, uint64_t rows,
+                         uint32_t width, const uint32_t *ans, uint64_t n_samples, const uint32_t *len, int32_t ignore, uint32_t flags,
+                         void *out_start, void *out_end, uint8_t *out_has, uint8_t *out_hit, uint64_t *info);
+int swt_answer_positions_dev(const uint32_t *d_spans, const uint32_t *d_word, const int8_t *d_seq, int32_t side, const uint32_t *d_sample,
+                             uint64_t rows, uint32_t width, const uint32_t *d_ans, uint64_t n_samples, const uint32_t *d_len, int32_t ignore,
+                             uint32_t flags, void *d_out_start, void *d_out_end, uint8_t *d_out_has, uint8_t *d_out_hit, uint64_t *d_info,
+                             void *stream);
+int swt_answer_best(const float *start_logit, const float *end_logit, const uint32_t *spans, const uint32_t *word, const int8_t *seq, int32_t side,
+                    const uint32_t *sample, uint64_t rows, uint32_t width, uint64_t n_samples, uint32_t max_len, const uint32_t *len,
+                    uint32_t flags, float *out_score, float *out_null_score, int32_t *out_row, int32_t *out_start_col, int32_t *out_end_col,
+                    uint32_t *out_char_start, uint32_t *out_char_end, float *out_row_score, int32_t *out_row_start, int32_t *out_row_end,
+                    uint64_t *info);
+int swt_answer_best_dev(const float *d_start_logit, const float *d_end_logit, const uint32_t *d_spans, const uint32_t *d_word, const int8_t *d_seq,
+                        int32_t side, const uint32_t *d_sample, uint64_t rows, uint32_t width, uint64_t n_samples, uint32_t max_len,
+                        const uint32_t *d_len, uint32_t flags, float *d_out_score, float *d_out_null_score, int32_t *d_out_row,
+                        int32_t *d_out_start_col, int32_t *d_out_end_col, uint32_t *d_out_char_start, uint32_t *d_out_char_end,
+                        float *d_out_row_score, int32_t *d_out_row_start, int32_t *d_out_row_end, uint64_t *d_info, void *stream);
+int swt_label_capacity(uint32_t *cols_per_step, uint32_t *scan_rows);
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,19 @@ SIGNATURES = {
     "swt_decode_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "swt_decode_capacity": (C.c_int, [u32p, u32p]),
+    "swt_label_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32] + [C.c_void_p] * 3),
+    "swt_label_words_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_uint64, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4),
+    "swt_answer_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 5),
+    "swt_answer_positions_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                           C.c_uint64, C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 6),
+    "swt_answer_best": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                  C.c_uint32] + [C.c_void_p] * 11),
+    "swt_answer_best_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                      C.c_uint32] + [C.c_void_p] * 12),
+    "swt_label_capacity": (C.c_int, [u32p, u32p]),
 }
 
 
@@ -841,6 +854,111 @@ def decode_rows(ids, mask, tok_bytes, tok_off, tok_flags, n_tok, text_off, skip_
     check(lib().swt_decode_rows(_vp(ids) or _vp(one), _vp(mask), rows, width, _vp(tok_bytes) or _vp(one), _vp(tok_off), _vp(tok_flags), n_tok,
                                 flags, _vp(text_off), _vp(text) or _vp(one), cap))
     return text
+
+
+LABEL_ALL_TOKENS, LABEL_IDS64 = 1, 4  # the flags of swt_label_words; IDS64 also of swt_answer_positions
+ANSWER_CLS, ANSWER_PAD_LEFT = 1, 2  # the flags of swt_answer_positions and swt_answer_best
+LABEL_IGNORE = -100  # what the Python layer passes as `ignore`
+NO_ANSWER = 0xFFFFFFFF  # ans[s, 0] of a text without an answer
+LABEL_COUNTS, ANSWER_COUNTS, BEST_COUNTS = 4, 3, 2  # the entries of info of the three calls
+
+
+def label_capacity():
+    """-> (cols_per_step, scan_rows): the columns of a row one step of the label kernels covers, the rows of one workgroup of the
+    reduction over a text's rows (csrc/swt_labels.hip)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_label_capacity(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _as_u32(a):
+    """an array of 32-bit integers as contiguous uint32, whatever its sign (-1 is 0xFFFFFFFF); None stays None"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype in (np.int32, np.uint32) else a.astype(np.uint32)
+
+
+def _label_rows(shape_of, word, seq, sample, spans=None, length=None):
+    """the row arrays of the label calls as the C ABI takes them, each held to the shape of `shape_of` [rows, width]"""
+    rows, width = shape_of.shape[:2]
+    word, sample, spans, length = _as_u32(word), _as_u32(sample), _as_u32(spans), _as_u32(length)
+    seq = None if seq is None else np.ascontiguousarray(seq, dtype=np.int8)
+    for name, a, shape in (("word", word, (rows, width)), ("seq", seq, (rows, width)), ("sample", sample, (rows,)),
+                           ("spans", spans, (rows, width, 2)), ("length", length, (rows,))):
+        if a is not None and a.shape != shape:
+            raise ValueError("%s has the shape %s, the rows want %s" % (name, a.shape, shape))
+    return int(rows), int(width), word, seq, sample, spans, length
+
+
+_ONE = np.zeros(4, dtype=np.uint64)  # an array of no element still needs an address
+
+
+def _at(a):
+    return None if a is None else _vp(a) if a.size else _vp(_ONE)
+
+
+def label_words(word, lab_off, lab, seq=None, side=0, sample=None, inside=None, all_tokens=False, ids64=False, ignore=LABEL_IGNORE,
+                status=True, info=True):
+    """Word labels onto token rows (swt_label_words).  word [rows, width] (int32 or uint32), lab_off uint64[n + 1], lab int32.
+    -> dict: labels int32 or int64 [rows, width], status uint8[rows] (or None), info uint64[4] (or None)"""
+    if not isinstance(word, np.ndarray) or word.ndim != 2:
+        raise TypeError("word: a 2-D array")
+    rows, width, word, seq, sample, _, _ = _label_rows(word, word, seq, sample)
+    lab_off, lab = np.ascontiguousarray(lab_off, dtype=np.uint64), np.ascontiguousarray(lab, dtype=np.int32)
+    if lab_off.size < 1:
+        raise ValueError("lab_off holds n_samples + 1 entries")
+    inside = None if inside is None else np.ascontiguousarray(inside, dtype=np.int32)
+    out = {"labels": np.zeros((rows, width), dtype=np.int64 if ids64 else np.int32), "status": np.zeros(rows, dtype=np.uint8) if status else None,
+           "info": np.zeros(LABEL_COUNTS, dtype=np.uint64) if info else None}
+    check(lib().swt_label_words(_at(word), _at(seq), int(side), _at(sample), rows, width, _at(lab_off), _at(lab), int(lab.size),
+                                int(lab_off.size) - 1, _at(inside), 0 if inside is None else int(inside.size), int(ignore),
+                                (LABEL_ALL_TOKENS if all_tokens else 0) | (LABEL_IDS64 if ids64 else 0), _at(out["labels"]), _at(out["status"]),
+                                _at(out["info"])))
+    return out
+
+
+def answer_positions(spans, ans, word=None, seq=None, side=0, sample=None, length=None, cls=False, pad_left=False, ids64=False,
+                     ignore=LABEL_IGNORE, has=True, hit=True, info=True):
+    """Answer character spans to start and end columns (swt_answer_positions).  spans [rows, width, 2], ans uint32[n, 2].
+    -> dict: start, end int32 or int64 [rows], has uint8[rows], hit uint8[n], info uint64[3] (each of the last three or None)"""
+    if not isinstance(spans, np.ndarray) or spans.ndim != 3:
+        raise TypeError("spans: a 3-D array [rows, width, 2]")
+    rows, width, word, seq, sample, spans, length = _label_rows(spans, word, seq, sample, spans, length)
+    ans = np.ascontiguousarray(ans, dtype=np.uint32).reshape(-1, 2)
+    t = np.int64 if ids64 else np.int32
+    out = {"start": np.zeros(rows, dtype=t), "end": np.zeros(rows, dtype=t), "has": np.zeros(rows, dtype=np.uint8) if has else None,
+           "hit": np.zeros(ans.shape[0], dtype=np.uint8) if hit else None, "info": np.zeros(ANSWER_COUNTS, dtype=np.uint64) if info else None}
+    flags = (ANSWER_CLS if cls else 0) | (ANSWER_PAD_LEFT if pad_left else 0) | (LABEL_IDS64 if ids64 else 0)
+    check(lib().swt_answer_positions(_at(spans), _at(word), _at(seq), int(side), _at(sample), rows, width, _at(ans), int(ans.shape[0]), _at(length),
+                                     int(ignore), flags, _at(out["start"]), _at(out["end"]), _at(out["has"]), _at(out["hit"]), _at(out["info"])))
+    return out
+
+
+BEST_TEXT = (("score", np.float32), ("null_score", np.float32), ("row", np.int32), ("start_col", np.int32), ("end_col", np.int32),
+             ("char_start", np.uint32), ("char_end", np.uint32))
+BEST_ROW = (("row_score", np.float32), ("row_start", np.int32), ("row_end", np.int32))
+
+
+def answer_best(start_logit, end_logit, spans, n_samples, word=None, seq=None, side=0, sample=None, max_len=30, length=None, cls=False,
+                pad_left=False, per_row=True, info=True):
+    """The best span per row and per text from start and end logits (swt_answer_best).  The logits are float32 [rows, width].
+    -> dict: per text score, null_score float32, row, start_col, end_col int32, char_start, char_end uint32 [n_samples]; per row
+    row_score, row_start, row_end (or None); info uint64[2] (or None)"""
+    for name, a in (("start_logit", start_logit), ("end_logit", end_logit)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or not a.flags.c_contiguous:
+            raise TypeError("%s: a 2-D C-contiguous array of float32" % name)
+    if end_logit.shape != start_logit.shape:
+        raise ValueError("end_logit has the shape of start_logit")
+    rows, width, word, seq, sample, spans, length = _label_rows(start_logit, word, seq, sample, spans, length)
+    out = {name: np.zeros(int(n_samples), dtype=t) for name, t in BEST_TEXT}
+    out.update((name, np.zeros(rows, dtype=t) if per_row else None) for name, t in BEST_ROW)
+    out["info"] = np.zeros(BEST_COUNTS, dtype=np.uint64) if info else None
+    flags = (ANSWER_CLS if cls else 0) | (ANSWER_PAD_LEFT if pad_left else 0)
+    check(lib().swt_answer_best(_at(start_logit), _at(end_logit), _at(spans), _at(word), _at(seq), int(side), _at(sample), rows, width,
+                                int(n_samples), int(max_len), _at(length), flags, *[_at(out[name]) for name, _ in BEST_TEXT + BEST_ROW],
+                                _at(out["info"])))
+    return out
 
 
 def bpe_length_table(strings):

@@ -5,7 +5,9 @@ encoder's ids to dense ids) and its encode calls (`encode_ids_batch`, `_batch_en
 pads, truncates or windows the rows on the device -- through the host forms of the C ABI into NumPy arrays, or with
 `device=True` on torch tensors without the ids ever leaving the device.  `mask_tokens` masks such rows for the masked-LM
 objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident.  `decode_batch`
-spells rows of dense ids back as text (swt_decode_plan / swt_decode_rows)."""
+spells rows of dense ids back as text (swt_decode_plan / swt_decode_rows).  `align_word_labels`,
+`answer_positions` and `best_answers` make the labels of token classification and extractive QA, and a QA model's best spans,
+from the rows of a batch (swt_label_words, swt_answer_positions, swt_answer_best)."""
 import collections
 import ctypes as C
 import re
@@ -516,6 +518,239 @@ def mask_tokens(tok, input_ids, probability=0.15, whole_word=True, seed=0, epoch
     if return_selected:
         res["selected"] = out["selected"]
     res.update((name, int(x)) for name, x in zip(MLM_COUNTS, info))
+    return res
+
+
+class _LabelRows:
+    """What the label calls read of an encode_batch(..., return_offsets=True) result: NumPy arrays (the host forms) or torch
+    tensors on the GPU (the `_dev` forms on the current stream), the side whose columns are token columns, and the layout of the
+    rows -- whether they carry specials and on which side they are padded -- taken from the rows themselves."""
+
+    def __init__(self, batch, side, pair_default):
+        if not isinstance(batch, dict) or "input_ids" not in batch:
+            raise TypeError("batch: a result of encode_batch(..., return_offsets=True)")
+        if "word_ids" not in batch or "offset_mapping" not in batch:
+            if "sample_ids" in batch:
+                raise ValueError("packed batches have no word_ids: labels go with padded rows or windows")
+            raise ValueError("the batch has no word_ids and offset_mapping: encode_batch(..., return_offsets=True) makes them")
+        ids = batch["input_ids"]
+        self.torch = None
+        if not isinstance(ids, np.ndarray):
+            import torch
+            if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
+                raise TypeError("batch: NumPy arrays, or torch tensors on the GPU")
+            self.torch = torch
+        kind = np.ndarray if self.torch is None else self.torch.Tensor
+        self.rows, self.width = int(ids.shape[0]), int(ids.shape[1])
+        self.ids64 = "int64" in str(ids.dtype)
+        self.word, self.spans, self.length, self.mask = batch["word_ids"], batch["offset_mapping"], batch["length"], batch["attention_mask"]
+        self.seq, self.sample = batch.get("sequence_ids"), batch.get("overflow_to_sample_mapping")
+        for a in (self.word, self.spans, self.length, self.mask, self.seq, self.sample):
+            if a is not None and not isinstance(a, kind):
+                raise TypeError("batch: every array a NumPy array, or every one a torch tensor on the GPU")
+        if self.seq is None:
+            if side not in (None, 0):
+                raise ValueError("side: single rows have side 0 alone")
+            self.side = 0
+        else:
+            if side is None:
+                side = pair_default
+            if side not in (0, 1):
+                raise ValueError("side is 0 or 1: pair rows need to be told whose words the labels are")
+            self.side = int(side)
+
+    def layout(self):
+        """-> (specials, pad_left), from attention_mask, word_ids and length: rows are padded on the left when a row shorter
+        than the width starts with padding, and carry specials when a row's first column of content holds no word"""
+        if not self.rows or not self.width:
+            return False, False
+        if self.torch is None:
+            n = self.length.astype(np.int64)
+            short = (n > 0) & (n < self.width)
+            pad_left = bool(((self.mask[:, 0] == 0) & short).any())
+            first = np.where(n > 0, self.width - n, 0) if pad_left else np.zeros(self.rows, dtype=np.int64)
+            head = self.word[np.arange(self.rows), first]
+            return bool(((head.astype(np.int64) & 0xFFFFFFFF == 0xFFFFFFFF) & (n > 0)).any()), pad_left
+        n = self.length.long()
+        short = (n > 0) & (n < self.width)
+        pad_left = bool(((self.mask[:, 0] == 0) & short).any())
+        first = self.torch.where(n > 0, self.width - n, 0) if pad_left else self.torch.zeros_like(n)
+        head = self.word.gather(1, first.unsqueeze(1)).squeeze(1)
+        return bool(((head == -1) & (n > 0)).any()), pad_left
+
+    def upload(self, a):
+        """a NumPy array of 32- or 64-bit integers as a tensor on the rows' device"""
+        signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype)
+        return self.torch.from_numpy(np.ascontiguousarray(a.view(signed) if signed else a)).to(self.word.device)
+
+    def ptr(self, a, spare):
+        """the address of a tensor; `spare`'s for one of no element; None for no tensor"""
+        return None if a is None else a.data_ptr() or spare.data_ptr()
+
+
+def _word_labels(word_labels):
+    """-> (lab_off uint64[n + 1], lab int32): a list of int lists, one per text, or (values, offsets) arrays"""
+    if isinstance(word_labels, tuple) and len(word_labels) == 2:
+        lab, off = np.ascontiguousarray(word_labels[0], dtype=np.int32), np.ascontiguousarray(word_labels[1], dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1 or lab.ndim != 1 or (np.diff(off.astype(np.int64)) < 0).any() or int(off[-1]) > lab.size:
+            raise ValueError("word_labels: offsets hold n_texts + 1 entries that do not decrease and end inside the values")
+        return off, lab
+    if not isinstance(word_labels, list) or not all(isinstance(x, (list, tuple, np.ndarray)) for x in word_labels):
+        raise TypeError("word_labels: a list of int lists, one per text, or (values, offsets) arrays")
+    off = np.zeros(len(word_labels) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in word_labels], dtype=np.uint64)
+    lab = np.fromiter((int(v) for x in word_labels for v in x), dtype=np.int32, count=int(off[-1]))
+    return off, lab
+
+
+def align_word_labels(batch, word_labels, label_all_tokens=False, inside=None, side=None, ignore_index=N.LABEL_IGNORE):
+    """SubwordTokenizer.align_word_labels: NumPy arrays through swt_label_words, torch tensors on the GPU through
+    swt_label_words_dev on the current device and stream, with `info` the only read-back of a batch that is in order."""
+    rows = _LabelRows(batch, side, None)
+    lab_off, lab = _word_labels(word_labels)
+    if inside is not None:
+        inside = np.ascontiguousarray(inside, dtype=np.int32)
+        if inside.ndim != 1:
+            raise ValueError("inside: one label per label")
+    n_texts = int(lab_off.size) - 1
+    if rows.torch is None:
+        out = N.label_words(rows.word, lab_off, lab, rows.seq, rows.side, rows.sample, inside, label_all_tokens, rows.ids64, ignore_index)
+        labels, info, status, sample = out["labels"], out["info"], out["status"], rows.sample
+    else:
+        torch = rows.torch
+        with torch.cuda.device(rows.word.device):
+            d_off, d_lab, d_inside = rows.upload(lab_off), rows.upload(lab), None if inside is None else rows.upload(inside)
+            labels = torch.empty((rows.rows, rows.width), dtype=torch.int64 if rows.ids64 else torch.int32, device=rows.word.device)
+            d_status = torch.empty(max(rows.rows, 1), dtype=torch.uint8, device=rows.word.device)
+            d_info = torch.empty(N.LABEL_COUNTS, dtype=torch.int64, device=rows.word.device)
+            word, seq, sample = rows.word.contiguous(), None if rows.seq is None else rows.seq.contiguous(), rows.sample
+            p = lambda a: rows.ptr(a, d_info)
+            N.check(N.lib().swt_label_words_dev(p(word), p(seq), rows.side, p(sample), rows.rows, rows.width, p(d_off), p(d_lab), int(lab.size),
+                                                n_texts, p(d_inside), 0 if inside is None else int(inside.size), int(ignore_index),
+                                                (N.LABEL_ALL_TOKENS if label_all_tokens else 0) | (N.LABEL_IDS64 if rows.ids64 else 0),
+                                                p(labels), d_status.data_ptr(), d_info.data_ptr(), torch.cuda.current_stream().cuda_stream))
+            info = d_info.cpu().numpy()
+            status = d_status[:rows.rows].cpu().numpy() if info[2] else None
+            sample = sample.cpu().numpy() if info[2] and sample is not None else None
+    if info[3]:
+        raise ValueError("align_word_labels: %d rows name a text beyond the %d of word_labels" % (int(info[3]), n_texts))
+    if info[2]:
+        row = int(np.flatnonzero(status)[0])
+        text = row if sample is None else int(sample[row])
+        raise ValueError("align_word_labels: row %d names a word beyond the %d labels of text %d"
+                         % (row, int(lab_off[text + 1]) - int(lab_off[text]), text))
+    return {"labels": labels, "n_labelled": int(info[0]), "n_continuation": int(info[1])}
+
+
+def _lower_positions(text, positions):
+    """indices into `text` as indices into text.lower(): the running sum of len(ch.lower())"""
+    at = np.zeros(len(text) + 1, dtype=np.int64)
+    at[1:] = np.cumsum([len(ch.lower()) for ch in text])
+    return [int(at[min(max(int(p), 0), len(text))]) for p in positions]
+
+
+def _answers(answers, texts):
+    """-> uint32[n, 2]: (a, e) per text in the unit of offset_mapping, (NO_ANSWER, NO_ANSWER) for None or a negative start"""
+    if isinstance(answers, np.ndarray):
+        answers = answers.tolist()
+    if not isinstance(answers, (list, tuple)):
+        raise TypeError("answers: one (start, end) per text, None or (-1, -1) for a text without an answer")
+    if texts is not None and (not isinstance(texts, list) or len(texts) != len(answers) or not all(isinstance(t, str) for t in texts)):
+        raise ValueError("texts holds one string for every answer")
+    ans = np.full((len(answers), 2), N.NO_ANSWER, dtype=np.uint32)
+    for i, x in enumerate(answers):
+        if x is None:
+            continue
+        if len(x) != 2:
+            raise ValueError("answers: one (start, end) per text")
+        a, e = int(x[0]), int(x[1])
+        if a < 0 or e < 0:
+            continue
+        if texts is not None and len(texts[i].lower()) != len(texts[i]):
+            a, e = _lower_positions(texts[i], (a, e))
+        if a >= N.NO_ANSWER or e > N.NO_ANSWER:
+            raise ValueError("answers: a position of 2^32 - 1 or more")
+        ans[i] = (a, e)
+    return ans
+
+
+def answer_positions(batch, answers, side=None, texts=None, ignore_index=N.LABEL_IGNORE):
+    """SubwordTokenizer.answer_positions: NumPy arrays through swt_answer_positions, torch tensors on the GPU through its `_dev`
+    form on the current device and stream; `info` and the rows' layout are the read-backs."""
+    rows = _LabelRows(batch, side, 1)
+    ans = _answers(answers, texts)
+    specials, pad_left = rows.layout()
+    pad_left = pad_left and specials  # without [CLS] the nothing column is ignore_index on either side
+    if rows.torch is None:
+        out = N.answer_positions(rows.spans, ans, rows.word, rows.seq, rows.side, rows.sample, rows.length, specials, pad_left, rows.ids64,
+                                 ignore_index)
+        info = out["info"]
+    else:
+        torch = rows.torch
+        dev = rows.word.device
+        with torch.cuda.device(dev):
+            t = torch.int64 if rows.ids64 else torch.int32
+            out = {"start": torch.empty(rows.rows, dtype=t, device=dev), "end": torch.empty(rows.rows, dtype=t, device=dev),
+                   "has": torch.empty(rows.rows, dtype=torch.uint8, device=dev), "hit": torch.empty(ans.shape[0], dtype=torch.uint8, device=dev)}
+            d_info, d_ans = torch.empty(N.ANSWER_COUNTS, dtype=torch.int64, device=dev), rows.upload(ans)
+            p = lambda a: rows.ptr(a, d_info)
+            seq = None if rows.seq is None else rows.seq.contiguous()
+            flags = (N.ANSWER_CLS if specials else 0) | (N.ANSWER_PAD_LEFT if pad_left else 0) | (N.LABEL_IDS64 if rows.ids64 else 0)
+            N.check(N.lib().swt_answer_positions_dev(p(rows.spans.contiguous()), p(rows.word.contiguous()), p(seq), rows.side, p(rows.sample),
+                                                     rows.rows, rows.width, p(d_ans), int(ans.shape[0]), p(rows.length.contiguous()),
+                                                     int(ignore_index), flags, p(out["start"]), p(out["end"]), p(out["has"]), p(out["hit"]),
+                                                     d_info.data_ptr(), torch.cuda.current_stream().cuda_stream))
+            info = d_info.cpu().numpy()
+    if info[2]:
+        raise ValueError("answer_positions: %d rows name a text beyond the %d of answers" % (int(info[2]), ans.shape[0]))
+    return {"start_positions": out["start"], "end_positions": out["end"], "has_answer": out["has"], "sample_has_answer_row": out["hit"],
+            "n_with": int(info[0]), "n_without": int(info[1])}
+
+
+def best_answers(batch, start_logits, end_logits, max_answer_length=30, side=None, texts=None):
+    """SubwordTokenizer.best_answers: NumPy arrays through swt_answer_best, torch tensors on the GPU through its `_dev` form on
+    the current device and stream; the rows' layout and, without `texts`, the last row's text are the read-backs."""
+    rows = _LabelRows(batch, side, 1)
+    kind, f32 = (np.ndarray, np.float32) if rows.torch is None else (rows.torch.Tensor, rows.torch.float32)
+    for name, a in (("start_logits", start_logits), ("end_logits", end_logits)):
+        if not isinstance(a, kind) or a.dtype != f32 or (rows.torch is not None and not a.is_cuda):
+            raise TypeError("%s: float32, a NumPy array or a torch tensor on the GPU as the batch is" % name)
+        if tuple(a.shape) != (rows.rows, rows.width):
+            raise ValueError("%s has the shape of input_ids" % name)
+    if int(max_answer_length) < 1:
+        raise ValueError("max_answer_length is 1 or more")
+    if texts is not None and (not isinstance(texts, list) or not all(isinstance(t, str) for t in texts)):
+        raise TypeError("texts: the strings of that side, one per text")
+    if texts is not None:
+        n_texts = len(texts)
+    elif rows.sample is None or not rows.rows:
+        n_texts = rows.rows
+    else:
+        n_texts = int(rows.sample[-1]) + 1
+    specials, pad_left = rows.layout()
+    pad_left = pad_left and specials
+    max_len = min(int(max_answer_length), 0xFFFFFFFF)
+    if rows.torch is None:
+        out = N.answer_best(np.ascontiguousarray(start_logits), np.ascontiguousarray(end_logits), rows.spans, n_texts, rows.word, rows.seq,
+                            rows.side, rows.sample, max_len, rows.length, specials, pad_left, per_row=False, info=False)
+    else:
+        torch = rows.torch
+        dev = rows.word.device
+        with torch.cuda.device(dev):
+            types = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32}
+            out = {name: torch.empty(n_texts, dtype=types[t], device=dev) for name, t in N.BEST_TEXT}
+            spare = torch.empty(2, dtype=torch.int64, device=dev)
+            p = lambda a: rows.ptr(a, spare)
+            seq = None if rows.seq is None else rows.seq.contiguous()
+            flags = (N.ANSWER_CLS if specials else 0) | (N.ANSWER_PAD_LEFT if pad_left else 0)
+            N.check(N.lib().swt_answer_best_dev(p(start_logits.contiguous()), p(end_logits.contiguous()), p(rows.spans.contiguous()),
+                                                p(rows.word.contiguous()), p(seq), rows.side, p(rows.sample), rows.rows, rows.width, n_texts,
+                                                max_len, p(rows.length.contiguous()), flags, *[p(out[name]) for name, _ in N.BEST_TEXT],
+                                                None, None, None, None, torch.cuda.current_stream().cuda_stream))
+    res = {name: out[name] for name, _ in N.BEST_TEXT}
+    if texts is not None:
+        cs, ce = (x if rows.torch is None else x.cpu().numpy() for x in (out["char_start"], out["char_end"]))
+        res["text"] = [t.lower()[int(a):int(b)] for t, a, b in zip(texts, cs.astype(np.int64), ce.astype(np.int64))]
     return res
 
 

@@ -149,6 +149,51 @@ class SubwordTokenizer:
         [0, 1], mask_share + random_share > 1, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
         return batching.mask_tokens(self, input_ids, probability, whole_word, seed, epoch, mask_share, random_share, return_selected)
 
+    # -- fine-tuning labels (not in the reference; batching.py, DESIGN.md 4.14).  They read a batch and no encoder state.
+    def align_word_labels(self, batch: dict, word_labels, label_all_tokens: bool = False, inside=None, side: Optional[int] = None,
+                          ignore_index: int = -100) -> dict:
+        """The labels of a token-classification task (NER, POS) on the rows of `batch`, a result of
+        encode_batch(..., return_offsets=True), on the device (swt_label_words).  word_labels: a list of int lists, one per text
+        and one label per word of it (the words of pre_tokenize, which "word_ids" count), or (values, offsets) arrays.  The
+        first token of a word in its row takes the word's label -- a word cut by a window's edge is labelled again in the next
+        window --, every other token ignore_index, or with label_all_tokens the label too; where `inside` is given, such a token
+        takes inside[label] for 0 <= label < len(inside): the B-x to I-x map of BIO tagging.  Specials, padding and the other
+        side of a pair get ignore_index.  side: whose words the labels are, 0 or 1; required for pair rows.
+        batch: NumPy arrays, or torch tensors on the GPU (labelled on the current stream, nothing leaving the device but the
+        counts); anything else raises TypeError.  A packed batch has no word_ids: ValueError.
+        -> {"labels" [rows, width] of the dtype of input_ids, "n_labelled", "n_continuation": the tokens left at ignore_index as
+        no first token}.  ValueError, naming the first such row and its text: a row that names a word beyond its text's labels."""
+        return batching.align_word_labels(batch, word_labels, label_all_tokens, inside, side, ignore_index)
+
+    def answer_positions(self, batch: dict, answers, side: Optional[int] = None, texts: Optional[List[str]] = None,
+                         ignore_index: int = -100) -> dict:
+        """The start and end columns of an extractive-QA answer in every row of `batch`, a result of
+        encode_batch(..., return_offsets=True), on the device (swt_answer_positions).  answers: [n_texts, 2], the (start, end)
+        of each text's answer, None or (-1, -1) for none, in the unit of "offset_mapping" -- code points of text.lower().  With
+        texts, the original strings of that side, the positions are indices into the original string: where
+        len(t.lower()) != len(t) ("İ") they are mapped on the host by the running sum of len(ch.lower()).  side: where the
+        answer lies, 1 (the context) by default for pair rows.
+        A row holds the answer when its first token of that side starts at or before it and its last ends at or behind it: then
+        the start position is the last token that starts at or before the answer's start, the end position the first that ends
+        at or behind its end.  Every other row gets the [CLS] column twice when the rows have specials (wherever the padding
+        is), ignore_index when not.  The usual recipe lets its first scan run on into [SEP] and the padding when the answer
+        starts in a window's last token; this does not.
+        -> {"start_positions", "end_positions" [rows] of the dtype of input_ids, "has_answer" uint8[rows],
+        "sample_has_answer_row" uint8[n_texts], "n_with", "n_without"}.  TypeError and ValueError as align_word_labels."""
+        return batching.answer_positions(batch, answers, side, texts, ignore_index)
+
+    def best_answers(self, batch: dict, start_logits, end_logits, max_answer_length: int = 30, side: Optional[int] = None,
+                     texts: Optional[List[str]] = None) -> dict:
+        """One best answer span per text from a QA model's start and end logits ([rows, width], float32, NumPy or torch on the
+        GPU as `batch` is; another dtype raises TypeError) over the rows of `batch`, on the device (swt_answer_best).  A span is
+        a pair of token columns (i, j) of that side in one row, i <= j < i + max_answer_length; its score start_logits[i] +
+        end_logits[j] in float32; a NaN score is no span.  The best: higher score, then smaller i, then smaller j, and between
+        the windows of a text the earlier row.
+        -> per text {"score" (-inf without a span), "null_score" (the least [CLS] score of the text's rows when the rows have
+        specials, +inf when not), "row", "start_col", "end_col" (-1 without a span), "char_start", "char_end" (the span in
+        "offset_mapping"'s unit)}, and with texts "text": texts[i].lower()[char_start:char_end], sliced on the host."""
+        return batching.best_answers(batch, start_logits, end_logits, max_answer_length, side, texts)
+
     def decode_batch_bytes(self, input_ids, attention_mask=None, skip_special_tokens: bool = True):
         """Rows of dense ids (any "input_ids" of encode_batch or mask_tokens, a model's output) back to text on the device
         (swt_decode_plan / swt_decode_rows), as the reference's recover_sentence (utils.py:141-154) spells the rows' tokens: '##'
