@@ -71,6 +71,9 @@ int swt_device_info(int *n_cu, char *name, size_t name_cap);
 /* Kernel timing for bench.py's roofline line (state of the CALLING THREAD, like the error text).  on = 1: every launch of a path's DOMINANT kernel (bpe_lane_kernel,
  * wp_encode_kernel, the training apply/argmax pair) is bracketed by two HIP events on the stream it is launched on;
  * on = 2: the bracket spans all kernels of one call instead (first launch .. last launch); 0 = off.
+ * on = 3 (a diagnostic): the bracket is the first kernel of the word-level dedup's front half alone (wordref_kernel), and nothing
+ * else is bracketed, so the number of brackets is the number of dedup pipelines that ran on this thread: one per FastBPE or
+ * FastWP encode call that took the dedup path, none for a call that went the direct way.
  * swt_profile_read waits for the events, returns the summed elapsed milliseconds and the number of brackets since
  * the last read, and clears the list. */
 int swt_profile_enable(int on);

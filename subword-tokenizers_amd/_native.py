@@ -256,7 +256,9 @@ DEDUP_AUTO, DEDUP_NEVER, DEDUP_ALWAYS = 0, 1, 2
 
 
 def profile_enable(on=True):
-    """True/1 = time the dominant kernel of each path, 2 = time all kernels of a call, False/0 = off"""
+    """True/1 = time the dominant kernel of each path, 2 = time all kernels of a call, 3 = bracket only the wordref_kernel launch
+    of the word-level dedup (profile_read then counts the dedup pipelines that ran: one per encode call that took that path, none
+    for a direct one), False/0 = off"""
     check(lib().swt_profile_enable(int(on)))
 
 

@@ -24,9 +24,10 @@ certify a wrong answer is the state a true candidate starts from and the bytes i
 root has no edge for is one "['UNK']" behind a letter-class character and never returns behind punctuation: the straddlers ".z"
 and ".中" put that pair across every seam), the sentence bounds taken from `sbits`, the clipping of a character at `ce`, the
 territory a lane writes, and everything behind phase C: statuses, compaction, offsets, the walk in global memory.  wp_naive_kernel
-has no second walk: there every mask bit is output.  Nothing tells from outside whether the dedup pipeline ran or how many tiles
-its unique pass took (the library has no call for it); test_fast_wp_seams checks the one condition under which it is skipped
-without a word, and the dedup family sweeps 200 .. 330 unique bytes across kWpUTile.
+has no second walk: there every mask bit is output.  Whether the dedup pipeline ran does tell from outside: profile level 3
+brackets exactly the wordref_kernel launch of dedup_front, and check_fast asserts one bracket for its dedup leg and none for its
+direct leg; how many tiles the unique pass took does not (the library has no call for it).  test_fast_wp_seams also checks the
+one condition under which the pipeline is skipped without a word, and the dedup family sweeps 200 .. 330 unique bytes across kWpUTile.
 
 Measured on an MI355X, one mask-only mutation per library, this file and the WordPiece tests from before it (test_gpu_parity.py
 -k wp, test_gpu_naive_wp.py): `prev_pu = false` at the end of wp_encode_kernel's block loop and `& ~SS` dropped from `before_pu`
@@ -468,8 +469,13 @@ def check_fast(dev, tok, orc, name, sents):
     try:
         for path, mode in (("direct", dev.DEDUP_NEVER), ("dedup", dev.DEDUP_ALWAYS)):
             tok._trie.set_option(dev.OPT_DEDUP, mode)
-            same(tok.encode_ids_batch(sents), want, "FastWP %s, %s" % (path, name), sents)
+            dev.profile_enable(3)  # level 3 brackets the wordref_kernel launch of dedup_front and nothing else
+            dev.profile_read()
+            got = tok.encode_ids_batch(sents)
+            assert dev.profile_read()[1] == (1 if path == "dedup" else 0), "dedup pipelines that ran (FastWP %s, %s)" % (path, name)
+            same(got, want, "FastWP %s, %s" % (path, name), sents)
     finally:
+        dev.profile_enable(0)
         tok._trie.set_option(dev.OPT_DEDUP, dev.DEDUP_AUTO)
     for i, t in enumerate(sents[:3]):
         tag = "FastWP tokenize, sentence %d of %s: 1 sentence, %d bytes" % (i, name, nbytes(t))
