@@ -848,6 +848,91 @@ int swt_answer_best_dev(const float *d_start_logit, const float *d_end_logit, co
                         int32_t *d_out_start_col, int32_t *d_out_end_col, uint32_t *d_out_char_start, uint32_t *d_out_char_end,
                         float *d_out_row_score, int32_t *d_out_row_start, int32_t *d_out_row_end, uint64_t *d_info, void *stream);
 int swt_label_capacity(uint32_t *cols_per_step, uint32_t *scan_rows);
+
+/* ------------------------------------------------------------------------------------------------
+ * Token-classification inference: from a model's logits (float32[rows, width, n_labels], C-contiguous, n_labels >= 1, fewer
+ * than 2^40 elements) over the same finished rows, one label and score per WORD of every text and the words' BIO grouping into
+ * entities.  The conventions are those of the labels block above: token columns of `side`, sample (NULL: row r is text r; a row
+ * with sample[r] >= n_samples is a row of no text), the argument checks, the `_dev` forms.  The reference has nothing of the
+ * sort; tests/tag_cases.py holds these semantics.
+ *
+ * A RUN of row r is a maximal set of consecutive token columns with the same word id k: the first-column rule of
+ * swt_label_words, continued to the right.  `sample` must not decrease (as in swt_answer_best; the host forms check, the `_dev`
+ * forms then leave the affected texts' results undefined and write nothing out of place).
+ *
+ * 1. swt_word_plan: n_words[s] = 1 + the greatest word[r, c] over the token columns of the rows of text s, 0 for a text with no
+ * token column; out_word_off (uint64[n_samples + 1]) is its exclusive prefix sum.  info[2] (required): out_word_off[n_samples],
+ * rows of no text.  The plan half of a plan / rows pair, as swt_decode_plan: the caller reads the total back and sizes the
+ * per-word arrays of 2. and 3. with it.
+ *
+ * 2. swt_word_predict: per word, at index w = word_off[s] + k of arrays of n_words elements (word_off as 1. made it, or any
+ * other that does not decrease and ends at or below n_words), each of which may be NULL: out_label (int32), out_score (float32),
+ * out_row, out_col, out_ncols (int32), out_char_start, out_char_end (uint32), out_logits (float32[n_words, n_labels]).
+ *   WHICH RUN SPEAKS FOR A WORD.  The context of a run is min(token columns of the side left of its first column, token columns
+ *   of the side right of its last column), both in its row -- the "max context" of the original BERT span code.  Among the runs
+ *   of (s, k) over all rows of s the winner has the greater context, then the smaller row, then the smaller first column: a
+ *   total order, so that the result does not depend on how it is reduced.  A word cut by a window's edge has context 0 there.
+ *   A run of a row of no text, and a run with k >= word_off[s + 1] - word_off[s] or word_off[s] + k >= n_words, takes no part
+ *   and counts in info[3].
+ *   THE WORD'S VECTOR v[0, n_labels) from the winner's columns c_0 < ... < c_{n-1}, x = logits[row]:
+ *     SWT_TAG_FIRST  v_l = x[c_0, l]
+ *     SWT_TAG_MEAN   v_l = (((x[c_0, l] + x[c_1, l]) + ...) + x[c_{n-1}, l]) / float32(n): float32 IEEE additions in column
+ *                    order, then one IEEE division -- the order is part of the contract
+ *     SWT_TAG_MAX    v_l = the greatest x[c_i, l] that is no NaN, NaN if all are
+ *   out_label: the smallest l whose v_l is no NaN and >= every entry that is no NaN; -1 if all are NaN.  Exact.
+ *   out_score: with m = v[label], 1 / sum over l in order of expf(v_l - m), in float32: the softmax probability of the label.
+ *   NaN and +-inf go through as IEEE has them: a NaN entry makes the score NaN while the label stands; label -1 has score NaN.
+ *   out_row, out_col = c_0, out_ncols = n; out_char_start = spans[row, c_0].start, out_char_end = spans[row, c_{n-1}].end;
+ *   out_logits = v.
+ *   A WORD WITH NO RUN: label -1, score 0, row, col and ncols -1, characters (0, 0), out_logits all NaN.
+ * info[4] (may be NULL): words with a run, words without, runs that lost to another row's run, runs that take no part.
+ * Fewer than 2^31 rows; n_words * n_labels below 2^40; SWT_ERR_INVALID where bits(width) * 2 + bits(rows - 1) exceeds 64 (a
+ * run's context, row and column make one 64-bit key): with fewer than 2^40 logits that needs a width of 2^21 columns or more.
+ *
+ * 3. swt_entity_spans: over the word arrays of 2. (label, score, char_start, char_end; n_words each) and the label scheme etype
+ * (int32[n_labels]; -1: outside) and begins (uint8[n_labels]).  Word w of text s (word_off[s] <= w < word_off[s + 1]; a word at
+ * or beyond word_off[n_samples] is of no text and of no entity) has the type t_w = etype[label_w], -1 for a label outside
+ * [0, n_labels).  It HEADS an entity iff t_w >= 0 and it is the first word of its text, or t_{w-1} != t_w, or begins[label_w];
+ * the entity runs through the following words of the text that have the same type and are no heads.  Records, n_words of each
+ * (all required when n_words > 0), in the order of the heads: ent_text, ent_type, ent_first_word, ent_last_word (int32; the
+ * words as indices in the text), ent_char_start of the head, ent_char_end of the last word (uint32), ent_score (float32): the
+ * words' scores added in order from the first, float32 IEEE additions, divided by float32(count).  Every record at or beyond
+ * the count is (-1, -1, -1, -1, 0, 0, 0.0).  info[2] (may be NULL): entities, words inside entities.
+ *
+ * SWT_ERR_INVALID also for: a NULL array that is not optional (seq, sample and the outputs of 2. are), the shapes the labels
+ * block refuses, n_labels == 0, an unknown strategy, misalignment to the element type, an output sharing a byte with another
+ * array; in the host forms a sample or word_off that decreases, and a word_off that ends beyond n_words.  rows == 0 (n_words
+ * == 0 in 3.) succeeds without a device: the offsets and info zeroed, every word's "nothing" record written.  The `_dev` forms
+ * enqueue on the stream, do not synchronise, write every element of every output given and nothing else; they keep keys,
+ * flags and counts in a workspace of the process, and 1. and 3. scan in the workspace of the plans: no two such calls at once on
+ * different streams.
+ * swt_tag_capacity: the columns of a row one step covers, the rows of one workgroup of the reduction over a text's rows (also
+ * the words of one workgroup of the per-word kernels), and the words of one group of the entity scan (csrc/swt_tags.hip). */
+#define SWT_TAG_FIRST 0u
+#define SWT_TAG_MEAN 1u
+#define SWT_TAG_MAX 2u
+int swt_word_plan(const uint32_t *word, const int8_t *seq, int32_t side, const uint32_t *sample, uint64_t rows, uint32_t width,
+                  uint64_t n_samples, uint64_t *out_word_off, uint64_t *info);
+int swt_word_plan_dev(const uint32_t *d_word, const int8_t *d_seq, int32_t side, const uint32_t *d_sample, uint64_t rows, uint32_t width,
+                      uint64_t n_samples, uint64_t *d_out_word_off, uint64_t *d_info, void *stream);
+int swt_word_predict(const float *logits, const uint32_t *word, const int8_t *seq, int32_t side, const uint32_t *sample, const uint32_t *spans,
+                     uint64_t rows, uint32_t width, uint32_t n_labels, const uint64_t *word_off, uint64_t n_samples, uint64_t n_words,
+                     uint32_t strategy, int32_t *out_label, float *out_score, int32_t *out_row, int32_t *out_col, int32_t *out_ncols,
+                     uint32_t *out_char_start, uint32_t *out_char_end, float *out_logits, uint64_t *info);
+int swt_word_predict_dev(const float *d_logits, const uint32_t *d_word, const int8_t *d_seq, int32_t side, const uint32_t *d_sample,
+                         const uint32_t *d_spans, uint64_t rows, uint32_t width, uint32_t n_labels, const uint64_t *d_word_off,
+                         uint64_t n_samples, uint64_t n_words, uint32_t strategy, int32_t *d_out_label, float *d_out_score, int32_t *d_out_row,
+                         int32_t *d_out_col, int32_t *d_out_ncols, uint32_t *d_out_char_start, uint32_t *d_out_char_end, float *d_out_logits,
+                         uint64_t *d_info, void *stream);
+int swt_entity_spans(const int32_t *label, const float *score, const uint32_t *char_start, const uint32_t *char_end, const uint64_t *word_off,
+                     uint64_t n_samples, uint64_t n_words, const int32_t *etype, const uint8_t *begins, uint32_t n_labels, int32_t *ent_text,
+                     int32_t *ent_type, int32_t *ent_first_word, int32_t *ent_last_word, uint32_t *ent_char_start, uint32_t *ent_char_end,
+                     float *ent_score, uint64_t *info);
+int swt_entity_spans_dev(const int32_t *d_label, const float *d_score, const uint32_t *d_char_start, const uint32_t *d_char_end,
+                         const uint64_t *d_word_off, uint64_t n_samples, uint64_t n_words, const int32_t *d_etype, const uint8_t *d_begins,
+                         uint32_t n_labels, int32_t *d_ent_text, int32_t *d_ent_type, int32_t *d_ent_first_word, int32_t *d_ent_last_word,
+                         uint32_t *d_ent_char_start, uint32_t *d_ent_char_end, float *d_ent_score, uint64_t *d_info, void *stream);
+int swt_tag_capacity(uint32_t *cols_per_step, uint32_t *text_rows, uint32_t *scan_words);
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,15 @@ SIGNATURES = {
     "swt_answer_best_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
                                       C.c_uint32] + [C.c_void_p] * 12),
     "swt_label_capacity": (C.c_int, [u32p, u32p]),
+    "swt_word_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "swt_word_plan_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64] + [C.c_void_p] * 3),
+    "swt_word_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32] + [C.c_void_p] * 9),
+    "swt_word_predict_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32] + [C.c_void_p] * 10),
+    "swt_entity_spans": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8),
+    "swt_entity_spans_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 9),
+    "swt_tag_capacity": (C.c_int, [u32p, u32p, u32p]),
 }
 
 
@@ -960,6 +969,72 @@ def answer_best(start_logit, end_logit, spans, n_samples, word=None, seq=None, s
     check(lib().swt_answer_best(_at(start_logit), _at(end_logit), _at(spans), _at(word), _at(seq), int(side), _at(sample), rows, width,
                                 int(n_samples), int(max_len), _at(length), flags, *[_at(out[name]) for name, _ in BEST_TEXT + BEST_ROW],
                                 _at(out["info"])))
+    return out
+
+
+TAG_FIRST, TAG_MEAN, TAG_MAX = 0, 1, 2  # the strategies of swt_word_predict
+TAG_STRATEGIES = {"first": TAG_FIRST, "mean": TAG_MEAN, "max": TAG_MAX}
+PLAN_COUNTS, PREDICT_COUNTS, ENTITY_COUNTS = 2, 4, 2  # the entries of info of the three calls
+WORD_OUT = (("label", np.int32), ("score", np.float32), ("row", np.int32), ("col", np.int32), ("n_tokens", np.int32),
+            ("char_start", np.uint32), ("char_end", np.uint32))
+ENTITY_OUT = (("text_index", np.int32), ("type", np.int32), ("first_word", np.int32), ("last_word", np.int32), ("char_start", np.uint32),
+              ("char_end", np.uint32), ("score", np.float32))
+
+
+def tag_capacity():
+    """-> (cols_per_step, text_rows, scan_words): the columns of a row one step of the tag kernels covers, the rows of one
+    workgroup of the reduction over a text's rows, the words of one group of the entity scan (csrc/swt_tags.hip)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_tag_capacity(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def word_plan(word, n_samples, seq=None, side=0, sample=None):
+    """How many words each text has (swt_word_plan).  word [rows, width] -> (word_off uint64[n_samples + 1], info uint64[2])"""
+    if not isinstance(word, np.ndarray) or word.ndim != 2:
+        raise TypeError("word: a 2-D array")
+    rows, width, word, seq, sample, _, _ = _label_rows(word, word, seq, sample)
+    word_off, info = np.zeros(int(n_samples) + 1, dtype=np.uint64), np.zeros(PLAN_COUNTS, dtype=np.uint64)
+    check(lib().swt_word_plan(_at(word), _at(seq), int(side), _at(sample), rows, width, int(n_samples), _at(word_off), _at(info)))
+    return word_off, info
+
+
+def word_predict(logits, word, spans, word_off, seq=None, side=0, sample=None, strategy=TAG_FIRST, n_words=None, word_logits=False,
+                 info=True):
+    """One label and score per word from logits float32 [rows, width, n_labels] (swt_word_predict).  n_words: the capacity of the
+    per-word arrays, word_off[-1] by default -> dict: label, score, row, col, n_tokens, char_start, char_end [n_words], logits
+    [n_words, n_labels] (or None), info uint64[4] (or None)"""
+    if not isinstance(logits, np.ndarray) or logits.dtype != np.float32 or logits.ndim != 3 or not logits.flags.c_contiguous:
+        raise TypeError("logits: a 3-D C-contiguous array of float32")
+    rows, width, word, seq, sample, spans, _ = _label_rows(logits, word, seq, sample, spans)
+    word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+    if word_off.size < 1:
+        raise ValueError("word_off holds n_samples + 1 entries")
+    n_words = int(word_off[-1]) if n_words is None else int(n_words)
+    n_labels = int(logits.shape[2])
+    out = {name: np.zeros(n_words, dtype=t) for name, t in WORD_OUT}
+    out["logits"] = np.zeros((n_words, n_labels), dtype=np.float32) if word_logits else None
+    out["info"] = np.zeros(PREDICT_COUNTS, dtype=np.uint64) if info else None
+    check(lib().swt_word_predict(_at(logits), _at(word), _at(seq), int(side), _at(sample), _at(spans), rows, width, n_labels, _at(word_off),
+                                 int(word_off.size) - 1, n_words, int(strategy), *[_at(out[name]) for name, _ in WORD_OUT], _at(out["logits"]),
+                                 _at(out["info"])))
+    return out
+
+
+def entity_spans(label, score, char_start, char_end, word_off, etype, begins, info=True):
+    """The BIO grouping of the words of word_predict (swt_entity_spans) -> dict: text_index, type, first_word, last_word,
+    char_start, char_end, score [n_words] (the records at or beyond the count are "nothing"), info uint64[2] (or None)"""
+    label, score = np.ascontiguousarray(label, dtype=np.int32), np.ascontiguousarray(score, dtype=np.float32)
+    char_start, char_end = _as_u32(char_start), _as_u32(char_end)
+    word_off, etype = np.ascontiguousarray(word_off, dtype=np.uint64), np.ascontiguousarray(etype, dtype=np.int32)
+    begins = np.ascontiguousarray(begins, dtype=np.uint8)
+    n_words = int(label.size)
+    if not (score.shape == char_start.shape == char_end.shape == label.shape == (n_words,)) or begins.shape != etype.shape or word_off.size < 1:
+        raise ValueError("label, score, char_start and char_end hold one entry per word, etype and begins one per label")
+    out = {name: np.zeros(n_words, dtype=t) for name, t in ENTITY_OUT}
+    out["info"] = np.zeros(ENTITY_COUNTS, dtype=np.uint64) if info else None
+    check(lib().swt_entity_spans(_at(label), _at(score), _at(char_start), _at(char_end), _at(word_off), int(word_off.size) - 1, n_words,
+                                 _at(etype), _at(begins), int(etype.size), *[_at(out[name]) for name, _ in ENTITY_OUT], _at(out["info"])))
     return out
 
 

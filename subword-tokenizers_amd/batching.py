@@ -754,6 +754,123 @@ def best_answers(batch, start_logits, end_logits, max_answer_length=30, side=Non
     return res
 
 
+def _n_texts(rows, n_texts):
+    """the texts of a batch: what the caller says, else one per row, or with windows the last row's text + 1 (a read-back)"""
+    if n_texts is not None:
+        return int(n_texts)
+    if rows.sample is None or not rows.rows:
+        return rows.rows
+    return int(rows.sample[-1]) + 1
+
+
+def word_predictions(batch, logits, strategy="first", side=None, return_logits=False, n_texts=None):
+    """SubwordTokenizer.word_predictions: NumPy arrays through swt_word_plan / swt_word_predict, torch tensors on the GPU through
+    their `_dev` forms on the current device and stream; the word total and `info` are the read-backs."""
+    rows = _LabelRows(batch, side, None)
+    kind, f32 = (np.ndarray, np.float32) if rows.torch is None else (rows.torch.Tensor, rows.torch.float32)
+    if not isinstance(logits, kind) or logits.dtype != f32 or (rows.torch is not None and not logits.is_cuda):
+        raise TypeError("logits: float32, a NumPy array or a torch tensor on the GPU as the batch is")
+    if len(logits.shape) != 3 or tuple(logits.shape[:2]) != (rows.rows, rows.width) or int(logits.shape[2]) < 1:
+        raise ValueError("logits has the shape [rows, width, n_labels] over the rows of input_ids")
+    if strategy not in N.TAG_STRATEGIES:
+        raise ValueError("strategy is 'first', 'mean' or 'max'")
+    n_texts, n_labels = _n_texts(rows, n_texts), int(logits.shape[2])
+    if rows.torch is None:
+        word_off, plan = N.word_plan(rows.word, n_texts, rows.seq, rows.side, rows.sample)
+        out = N.word_predict(np.ascontiguousarray(logits), rows.word, rows.spans, word_off, rows.seq, rows.side, rows.sample,
+                             N.TAG_STRATEGIES[strategy], word_logits=return_logits)
+        info = out["info"]
+    else:
+        torch = rows.torch
+        dev = rows.word.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            d_off = torch.empty(n_texts + 1, dtype=torch.int64, device=dev)
+            d_plan, d_info = torch.empty(N.PLAN_COUNTS, dtype=torch.int64, device=dev), torch.empty(N.PREDICT_COUNTS, dtype=torch.int64, device=dev)
+            p = lambda a: rows.ptr(a, d_info)
+            word, seq = rows.word.contiguous(), None if rows.seq is None else rows.seq.contiguous()
+            N.check(N.lib().swt_word_plan_dev(p(word), p(seq), rows.side, p(rows.sample), rows.rows, rows.width, n_texts, d_off.data_ptr(),
+                                              d_plan.data_ptr(), stream))
+            plan = d_plan.cpu().numpy()  # the one read-back before the words: how many there are
+            n_words = int(plan[0])
+            types = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32}
+            out = {name: torch.empty(n_words, dtype=types[t], device=dev) for name, t in N.WORD_OUT}
+            out["logits"] = torch.empty((n_words, n_labels), dtype=torch.float32, device=dev) if return_logits else None
+            N.check(N.lib().swt_word_predict_dev(p(logits.contiguous()), p(word), p(seq), rows.side, p(rows.sample), p(rows.spans.contiguous()),
+                                                 rows.rows, rows.width, n_labels, d_off.data_ptr(), n_texts, n_words,
+                                                 N.TAG_STRATEGIES[strategy], *[p(out[name]) for name, _ in N.WORD_OUT], p(out["logits"]),
+                                                 d_info.data_ptr(), stream))
+            info = d_info.cpu().numpy()
+            word_off = d_off.view(torch.uint64)
+    if plan[1]:
+        raise ValueError("word_predictions: %d rows name a text beyond the %d of the batch" % (int(plan[1]), n_texts))
+    res = {"word_offsets": word_off}
+    res.update((name, out[name]) for name, _ in N.WORD_OUT)
+    if return_logits:
+        res["logits"] = out["logits"]
+    res.update({"n_words": int(info[0]), "n_missing": int(info[1])})
+    return res
+
+
+def _label_scheme(id2label):
+    """-> (etype int32[L], begins uint8[L], type_names): "B-x" and "I-x" are of type x and "B-x" begins; "O" is outside; any
+    other name is its own type and never begins"""
+    if not isinstance(id2label, (list, tuple)) or not id2label or not all(isinstance(x, str) for x in id2label):
+        raise TypeError("id2label: a list of label names, the name of label i at index i")
+    names, etype, begins = [], np.full(len(id2label), -1, dtype=np.int32), np.zeros(len(id2label), dtype=np.uint8)
+    for i, name in enumerate(id2label):
+        if name == "O":
+            continue
+        kind = name[2:] if name[:2] in ("B-", "I-") and len(name) > 2 else name
+        if kind not in names:
+            names.append(kind)
+        etype[i], begins[i] = names.index(kind), name[:2] == "B-" and len(name) > 2
+    return etype, begins, names
+
+
+def entities(words, id2label, texts=None):
+    """SubwordTokenizer.entities: the word arrays of word_predictions through swt_entity_spans (NumPy) or its `_dev` form (torch
+    tensors on the GPU, on the current device and stream); the count is the read-back that cuts the arrays."""
+    need = ("word_offsets", "label", "score", "char_start", "char_end")
+    if not isinstance(words, dict) or not all(k in words for k in need):
+        raise TypeError("words: a result of word_predictions")
+    etype, begins, names = _label_scheme(id2label)
+    if texts is not None and (not isinstance(texts, list) or not all(isinstance(t, str) for t in texts)):
+        raise TypeError("texts: the strings of that side, one per text")
+    label = words["label"]
+    n_texts = int(words["word_offsets"].shape[0]) - 1
+    if texts is not None and len(texts) != n_texts:
+        raise ValueError("texts holds one string for every text of the words")
+    if isinstance(label, np.ndarray):
+        out = N.entity_spans(label, words["score"], words["char_start"], words["char_end"], words["word_offsets"], etype, begins)
+        info = out["info"]
+        n = int(info[0])
+        res = {name: out[name][:n] for name, _ in N.ENTITY_OUT}
+    else:
+        import torch
+        if not isinstance(label, torch.Tensor) or not label.is_cuda:
+            raise TypeError("words: NumPy arrays, or torch tensors on the GPU")
+        dev = label.device
+        with torch.cuda.device(dev):
+            n_words = int(label.shape[0])
+            types = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32}
+            out = {name: torch.empty(n_words, dtype=types[t], device=dev) for name, t in N.ENTITY_OUT}
+            d_info = torch.empty(N.ENTITY_COUNTS, dtype=torch.int64, device=dev)
+            d_etype, d_begins = torch.from_numpy(etype).to(dev), torch.from_numpy(begins).to(dev)
+            p = lambda a: a.data_ptr() or d_info.data_ptr()
+            N.check(N.lib().swt_entity_spans_dev(*[p(words[k].contiguous()) for k in need[1:]], p(words["word_offsets"].contiguous()), n_texts,
+                                                 n_words, p(d_etype), p(d_begins), int(etype.size), *[p(out[name]) for name, _ in N.ENTITY_OUT],
+                                                 d_info.data_ptr(), torch.cuda.current_stream().cuda_stream))
+            info = d_info.cpu().numpy()
+            n = int(info[0])
+            res = {name: out[name][:n] for name, _ in N.ENTITY_OUT}
+    res.update({"type_names": names, "n_entities": n, "n_entity_words": int(info[1])})
+    if texts is not None:
+        ti, cs, ce = (x if isinstance(x, np.ndarray) else x.cpu().numpy() for x in (res["text_index"], res["char_start"], res["char_end"]))
+        res["text"] = [texts[int(i)].lower()[int(a):int(b)] for i, a, b in zip(ti, cs.astype(np.int64), ce.astype(np.int64))]
+    return res
+
+
 def _raise_decode_status(status, row):
     """the ValueError of a plan whose info counts reported rows: the first such row and its cause"""
     causes = [text for bit, text in ((N.DECODE_BAD_ID, "an id outside the vocabulary on a kept column"),

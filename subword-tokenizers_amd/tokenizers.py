@@ -194,6 +194,35 @@ class SubwordTokenizer:
         "offset_mapping"'s unit)}, and with texts "text": texts[i].lower()[char_start:char_end], sliced on the host."""
         return batching.best_answers(batch, start_logits, end_logits, max_answer_length, side, texts)
 
+    # -- token-classification inference (not in the reference; batching.py, DESIGN.md 4.15)
+    def word_predictions(self, batch: dict, logits, strategy: str = "first", side: Optional[int] = None, return_logits: bool = False,
+                         n_texts: Optional[int] = None) -> dict:
+        """One label and softmax score per word of every text from a token-classification model's logits ([rows, width,
+        n_labels], float32, NumPy or torch on the GPU as `batch` is; another dtype or kind raises TypeError, another shape
+        ValueError) over the rows of `batch`, a result of encode_batch(..., return_offsets=True), on the device (swt_word_plan,
+        swt_word_predict): the way back from align_word_labels.  A word's tokens in a row are a run of columns; where a word
+        shows up in several overlapping windows, the run with the most context speaks for it -- min(tokens to its left, tokens
+        to its right) in its row, then the earlier row --, so that a word cut by a window's edge is read from its whole copy.
+        strategy: "first" takes the logits of the run's first token, "mean" their float32 mean over the run in column order,
+        "max" their maximum.  The label is the first argmax, the score its softmax probability.  side: whose words, 0 or 1;
+        required for pair rows.  n_texts: the texts of the batch; by default one per row, or with windows the last row's + 1.
+        -> {"word_offsets" uint64[n_texts + 1]: the words of text s are [word_offsets[s], word_offsets[s + 1]); per word "label"
+        (-1 for a word no row holds), "score", "row", "col", "n_tokens" (where the run lies; -1), "char_start", "char_end" (the
+        word in "offset_mapping"'s unit); "n_words": the words with a run, "n_missing": those without}, and with return_logits
+        "logits" [words, n_labels], the word's vector.  A packed batch raises ValueError.  With torch tensors everything stays
+        on the device and the current stream; the word total and the counts are read back."""
+        return batching.word_predictions(batch, logits, strategy, side, return_logits, n_texts)
+
+    def entities(self, words: dict, id2label, texts: Optional[List[str]] = None) -> dict:
+        """The words of word_predictions grouped into entities on the device (swt_entity_spans).  id2label: the label names by
+        id, as "O", "B-PER", "I-PER": "B-x" and "I-x" are of type x, "O" is outside, any other name is a type of its own that
+        never begins.  A word heads an entity when it has a type and is its text's first word, follows a word of another type
+        (or none), or its label begins; the entity runs on over the words of the same type that head none.
+        -> per entity, in order, {"text_index", "type" (an index into "type_names"), "first_word", "last_word" (in the text),
+        "char_start", "char_end", "score": the float32 mean of the words' scores}, "type_names", "n_entities",
+        "n_entity_words", and with texts (one string per text) "text": texts[i].lower()[char_start:char_end], sliced on the host."""
+        return batching.entities(words, id2label, texts)
+
     def decode_batch_bytes(self, input_ids, attention_mask=None, skip_special_tokens: bool = True):
         """Rows of dense ids (any "input_ids" of encode_batch or mask_tokens, a model's output) back to text on the device
         (swt_decode_plan / swt_decode_rows), as the reference's recover_sentence (utils.py:141-154) spells the rows' tokens: '##'
