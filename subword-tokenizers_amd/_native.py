@@ -454,14 +454,20 @@ def pack_utf32(strings):
     return blob, off
 
 
-def token_histogram(ids, id_cap):
-    """uint32 token ids -> uint64 counts[2 * id_cap] (second half: ids carrying BPE_CONT), counted on the device"""
+def token_histogram_counts(ids, id_cap):
+    """swt_token_histogram as it is: -> (uint64 counts[2 * id_cap], how many ids lie outside [0, id_cap): they are counted nowhere)"""
     ids = np.ascontiguousarray(ids, dtype=np.uint32)
     counts = np.zeros(2 * int(id_cap), dtype=np.uint64)
     oor = C.c_uint64()
     check(lib().swt_token_histogram(ptr(ids, u32p) if ids.size else None, int(ids.size), int(id_cap), ptr(counts, u64p), C.byref(oor)))
-    if oor.value:
-        raise ValueError("%d token ids are outside [0, %d)" % (oor.value, id_cap))
+    return counts, oor.value
+
+
+def token_histogram(ids, id_cap):
+    """uint32 token ids -> uint64 counts[2 * id_cap] (second half: ids carrying BPE_CONT), counted on the device"""
+    counts, oor = token_histogram_counts(ids, id_cap)
+    if oor:
+        raise ValueError("%d token ids are outside [0, %d)" % (oor, id_cap))
     return counts
 
 
