@@ -202,6 +202,38 @@ int swt_bpe_encode_naive_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n
                              uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * BPE-dropout (Provilkov et al. 2020; not in the reference): swt_bpe_encode with every candidate merge skipped with a given
+ * probability at every merge step, so that the same text comes out in another segmentation per (seed, epoch).  Arguments, ids,
+ * flags and capacities as swt_bpe_encode / swt_bpe_encode_dev, plus the draw: drop_below in [0, 2^32] (from a probability p,
+ * round(p * 2^32); above 2^32: SWT_ERR_INVALID), a 64-bit seed and a 32-bit epoch.  No floating point on the device.
+ *
+ * Pre-tokenisation is swt_bpe_encode's; a word of one symbol is that symbol.  A word of symbols s[0..n) (its code points) has
+ * the key (i, b): i = the index of its sentence in this call's sent_off, b = the byte offset of the word's first byte from
+ * sent_off[i] in the text the call is given (for Python's entry points pack_and_lower(texts)), both mod 2^32.  Then
+ *     t = 0
+ *     while n >= 2:
+ *         live = the k in [0, n - 1) whose pair (s[k], s[k+1]) has a rank and is not dropped(t, k)
+ *         if there is none: stop
+ *         m = the smallest rank among the pairs at live
+ *         left to right (source/bpe.py:221-235): at k, if k is live and its pair has rank m, emit the merged symbol and go on
+ *         at k + 2, else emit s[k] and go on at k + 1
+ *         s, n = what was emitted; t += 1
+ * dropped(t, k): x = Philox4x32-10 (the function and constants of swt_mlm_mask) of the counter
+ * (((t << 16) + (k >> 2)) mod 2^32, b, i, epoch) under the key (seed & 0xFFFFFFFF, seed >> 32); the pair is dropped iff
+ * x[k & 3] < drop_below.  k indexes the word's sequence as it stands at the start of round t.
+ * So: a sentence's ids depend on (seed, epoch, i) and its own bytes, not on tiles, chunks, the route of the call or the other
+ * sentences; drop_below = 0 is swt_bpe_encode for any table; drop_below = 2^32 leaves every word as its code points; the loop
+ * stops in the first round in which every ranked pair is dropped (the paper's rule).  Two occurrences of a word must be able to
+ * differ, so the word-level dedup pipeline is never taken, whatever SWT_OPT_DEDUP says.  With SWT_BPE_RAW_WORDS every sentence
+ * is one word and b = 0.  One lane per word through the literal loop (csrc/swt_bpe_encode.hip, dropout_word). */
+int swt_bpe_encode_dropout(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                           uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags,
+                           uint64_t drop_below, uint64_t seed, uint32_t epoch);
+int swt_bpe_encode_dropout_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                               uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens,
+                               uint32_t flags, uint64_t drop_below, uint64_t seed, uint32_t epoch, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * FastWP encode: replaces WPTrie_E2E (source/utils.py:66-139: insert + precompute, built on the host
  * and flattened into device arrays) and FastWP.tokenize/matchloop/iswdbndry/ispunc
  * (source/wordpiece.py:233-316).

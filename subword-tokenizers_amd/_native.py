@@ -79,6 +79,10 @@ SIGNATURES = {
     "swt_bpe_encode_naive_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u64p, u8p, C.c_uint32]),
     "swt_bpe_encode_naive_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_void_p]),
+    "swt_bpe_encode_dropout": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u64p, C.c_uint32, C.c_uint64, C.c_uint64,
+                                         C.c_uint32]),
+    "swt_bpe_encode_dropout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
     "swt_wp_trie_create": (C.c_int, [u32p, u64p, C.c_uint32, vpp]),
     "swt_wp_trie_destroy": (None, [C.c_void_p]),
     "swt_wp_trie_stats": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
@@ -1064,16 +1068,18 @@ def _encode_out(n_ids, n_sent, status):
             np.zeros(max(n_sent, 1), dtype=np.uint8) if status else None, C.c_uint64())
 
 
-def _encode_host(entry, handle, text_u8, sent_off, status=False, flags=None, spans=None):
+def _encode_host(entry, handle, text_u8, sent_off, status=False, flags=None, spans=None, draw=()):
     """One host-buffer encode of include/swt.h: lowercased packed text and its offsets in, arrays trimmed to the id count out
     -> (ids uint32, offsets uint64[n+1]), then status uint8[n] for an entry that has per-sentence statuses, then (spans
-    uint32[n, 2], word uint32[n]) for one that takes a span flag word (`spans`).  flags: the trailing flag word of the BPE entries."""
+    uint32[n, 2], word uint32[n]) for one that takes a span flag word (`spans`).  flags: the trailing flag word of the BPE entries;
+    draw: (drop_below, seed, epoch) behind it, for the dropout entry."""
     n_sent = int(sent_off.size - 1)
     out, out_off, st, nt = _encode_out(int(sent_off[-1]), n_sent, status)
     args = [handle, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(out, u32p), out.size, ptr(out_off, u64p)]
     args += [ptr(st, u8p), C.byref(nt)] if status else [C.byref(nt)]
     if flags is not None:
         args.append(flags)
+    args += draw
     if spans is not None:
         sp, word = np.zeros((out.size, 2), dtype=np.uint32), np.zeros(out.size, dtype=np.uint32)
         args += [spans, ptr(sp, u32p), ptr(word, u32p)]
@@ -1138,6 +1144,13 @@ class BpeTable:
     def encode_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags=0, stream=0):
         """device pointers (ints) in; enqueues on `stream` and returns"""
         check(lib().swt_bpe_encode_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags, stream))
+
+    # BPE-dropout (swt_bpe_encode_dropout, include/swt.h): draw = (drop_below in [0, 2^32], seed, epoch)
+    def encode_dropout(self, text_u8, sent_off, draw, flags=0):
+        return _encode_host("swt_bpe_encode_dropout", self._h, text_u8, sent_off, flags=flags, draw=list(draw))
+
+    def encode_dropout_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, draw, flags=0, stream=0):
+        check(lib().swt_bpe_encode_dropout_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, flags, *draw, stream))
 
     # the merges in LIST order (NaiveBPE.encode_word, bpe.py:114-134): same arguments and results as the three above
     def encode_naive(self, text_u8, sent_off, flags=0):

@@ -205,20 +205,20 @@ def _pair_result(out, overflowing, offsets, token_types, special_mask):
     return res
 
 
-def _encode_host(tok, texts, offsets):
+def _encode_host(tok, texts, offsets, dropout=None):
     """one encode through the host forms -> (ids, tok_off, spans, word); spans and word are None without offsets"""
     if offsets:
-        got = tok._batch_encode_spans(texts)
+        got = tok._batch_encode_spans(texts) if dropout is None else tok._batch_encode_spans(texts, dropout)
         return got[0], got[1], got[-2], got[-1]
-    got = tok.encode_ids_batch(texts)
+    got = tok._batch_encode_ids(texts, dropout)
     return got[0], got[1], None, None
 
 
 def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
-                  int64, truncation, token_types, special_mask):
+                  int64, truncation, token_types, special_mask, dropout=None):
     """pairs through the host forms: ONE encode of texts + text_pairs, whose offsets from len(texts) on are those of the B sides"""
     n, strategy, n_special = len(texts), STRATEGIES[truncation], 3 if add_special_tokens else 0
-    ids, tok_off, spans, word = _encode_host(tok, texts + text_pairs, offsets)
+    ids, tok_off, spans, word = _encode_host(tok, texts + text_pairs, offsets, dropout)
     tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
     off_a, off_b = tok_off[:n + 1], tok_off[n:]
     longest = int(N.batch_pair_plan(off_a, off_b, N.batch_spec(0), strategy)[2][1])
@@ -234,23 +234,26 @@ def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, mult
 def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_to_multiple_of=None, add_special_tokens=True,
                  padding_side="right", return_overflowing=False, return_offsets=False, int64=False, device=False, text_pairs=None,
                  truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False, packing=None, drop_last=False,
-                 mlm=None):
+                 mlm=None, dropout=None):
+    if dropout is not None:
+        tok._enc.draw(dropout)  # refused before anything is encoded: a class without BPE-dropout, arguments that give no draw
     if mlm is None:
         return _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                              return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                             return_special_tokens_mask, packing, drop_last)
+                             return_special_tokens_mask, packing, drop_last, dropout)
     if not isinstance(mlm, dict):
         raise TypeError("mlm is None or a dict of mask_tokens keywords")
     _mlm_thresholds(**{k: v for k, v in mlm.items() if k != "return_selected"})  # refused before anything is encoded
     res = _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing,
                         return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing,
-                        drop_last)
+                        drop_last, dropout)
     res.update(mask_tokens(tok, res["input_ids"], **mlm))
     return res
 
 
 def _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing,
-                  return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing, drop_last):
+                  return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing, drop_last,
+                  dropout=None):
     _check(texts, max_length, stride, return_overflowing)
     _check_pairs(texts, text_pairs, truncation, return_overflowing, return_token_type_ids, return_special_tokens_mask)
     voc = tok._batch_vocabulary()
@@ -258,18 +261,18 @@ def _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, a
         mode = _pack_mode(packing, drop_last, max_length, stride, padding_side, return_overflowing, return_offsets, text_pairs)
         width = _width(0, 0, max_length, "max_length", pad_to_multiple_of)
         spec = _spec(tok, voc, width, 0, False, add_special_tokens, "right", int64)
-        return (_pack_device if device else _pack_host)(tok, voc, texts, spec, mode)
+        return (_pack_device if device else _pack_host)(tok, voc, texts, spec, mode, dropout)
     geometry = (max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing, return_offsets, int64)
     if text_pairs is not None:
         token_types, special_mask = return_token_type_ids is None or bool(return_token_type_ids), bool(return_special_tokens_mask)
         if not device:
-            return _encode_pairs(tok, voc, texts, text_pairs, *geometry, truncation, token_types, special_mask)
-        out = _encode_device(tok, voc, texts + text_pairs, len(texts), *geometry, (truncation, token_types, special_mask))
+            return _encode_pairs(tok, voc, texts, text_pairs, *geometry, truncation, token_types, special_mask, dropout)
+        out = _encode_device(tok, voc, texts + text_pairs, len(texts), *geometry, (truncation, token_types, special_mask), dropout)
         return _pair_result(out, return_overflowing, return_offsets, token_types, special_mask)
     if device:
-        out = _encode_device(tok, voc, texts, len(texts), *geometry)
+        out = _encode_device(tok, voc, texts, len(texts), *geometry, None, dropout)
         return _result(out, return_overflowing, return_offsets, int(out["info"][2]))
-    ids, tok_off, spans, word = _encode_host(tok, texts, return_offsets)
+    ids, tok_off, spans, word = _encode_host(tok, texts, return_offsets, dropout)
     _, longest = N.batch_plan(tok_off, N.batch_spec(0))
     width = _width(longest, 2 if add_special_tokens else 0, max_length, padding, pad_to_multiple_of)
     spec = _spec(tok, voc, width, stride, return_overflowing, add_special_tokens, padding_side, int64)
@@ -313,8 +316,8 @@ def _pack_result(out, slot, tok_off, spec, mode, info, plan_info, xp):
             "density": float(min(int(plan_info[3]), rows * width)) / (rows * width) if rows else 0.0}
 
 
-def _pack_host(tok, voc, texts, spec, mode):
-    ids, tok_off = tok.encode_ids_batch(texts)[:2]
+def _pack_host(tok, voc, texts, spec, mode, dropout=None):
+    ids, tok_off = tok._batch_encode_ids(texts, dropout)[:2]
     tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
     slot, row_first, plan_info = N.pack_plan(tok_off, spec, mode)
     out = N.pack_rows(ids, tok_off, spec, mode, slot, row_first, voc.cmap, voc.n_map, voc.flagged, rows_cap=int(plan_info[0]))
@@ -324,7 +327,7 @@ def _pack_host(tok, voc, texts, spec, mode):
 Encoded = collections.namedtuple("Encoded", "stream empty ids tok_off spans word checks")
 
 
-def _encode_on_device(tok, voc, texts, offsets=False):
+def _encode_on_device(tok, voc, texts, offsets=False, dropout=None):
     """The front half of the device paths, on the current device and stream: ONE upload of the lowercased texts and one `_dev`
     encode (with offsets its span form) into torch-owned buffers, and voc.d_cmap on that device.  -> Encoded: empty(shape, dtype,
     wanted=True) allocates on the device; spans and word are None without offsets; checks: the (statuses, complain) pairs of the
@@ -349,20 +352,20 @@ def _encode_on_device(tok, voc, texts, offsets=False):
         d_ntok = torch.zeros(1, dtype=torch.int64, device=dev)
         checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
                                        d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None,
-                                       stream, empty)
+                                       stream, empty, **({} if dropout is None else {"dropout": dropout}))
     if voc.d_cmap is None or voc.d_cmap.device != dev:
         voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
     return Encoded(stream, empty, d_ids, d_tok_off, d_spans, d_word, checks)
 
 
-def _pack_device(tok, voc, texts, spec, mode):
+def _pack_device(tok, voc, texts, spec, mode, dropout=None):
     """as _encode_device: one upload of the texts, one `_dev` encode, the packing plan and rows on torch-owned buffers on the
     current stream; the plan's info (for the rows to allocate) and the rows' info are all that comes back"""
     import torch
     n_rows, width = len(texts), int(spec.width)
     lib, check = N.lib(), N.check
     idt = torch.int64 if spec.flags & N.BATCH_IDS64 else torch.int32
-    enc = _encode_on_device(tok, voc, texts)
+    enc = _encode_on_device(tok, voc, texts, False, dropout)
     stream, empty, d_ids, d_tok_off = enc.stream, enc.empty, enc.ids, enc.tok_off
     d_slot, d_first, d_info = empty(n_rows + 1, torch.int64), empty(n_rows + 1, torch.int64), empty(8, torch.int64)
     check(lib.swt_pack_plan_dev(d_tok_off.data_ptr(), n_rows, C.byref(spec), mode, d_slot.data_ptr(), d_first.data_ptr(), d_info.data_ptr(),
@@ -392,7 +395,7 @@ def _result(out, overflowing, offsets, n_unknown):
 
 
 def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
-                   int64, pair=None):
+                   int64, pair=None, dropout=None):
     """The same on torch tensors, on the current device and stream: ONE upload of the lowercased texts, one `_dev` encode (or its
     span form), the plan and the rows call on torch-owned buffers; `info`, the token count and, of a batch that holds a refused
     pair, the statuses are all that comes back.  texts: every text of the call -- of pairs the A sides and then the B sides,
@@ -404,7 +407,7 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
     n_special, n_info = ((3 if pair else 2) if add_special_tokens else 0), (5 if pair else 3)
     lib, check = N.lib(), N.check
     idt = torch.int64 if int64 else torch.int32
-    stream, empty, d_ids, d_tok_off, d_spans, d_word, checks = _encode_on_device(tok, voc, texts, offsets)
+    stream, empty, d_ids, d_tok_off, d_spans, d_word, checks = _encode_on_device(tok, voc, texts, offsets, dropout)
     p_spans, p_word = (d_spans.data_ptr(), d_word.data_ptr()) if offsets else (None, None)
 
     def outputs(rows, width):
@@ -459,6 +462,27 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
         check(lib.swt_batch_rows_dev(*head, d_row_base.data_ptr() if overflowing else None, rows, p["input_ids"], p["attention_mask"], *tail))
     out["info"] = d_info[:n_info].cpu().numpy()
     return out
+
+
+def dropout_draw(dropout):
+    """A `dropout` argument of the encode calls -> None, or (drop_below, seed, epoch) of swt_bpe_encode_dropout: drop_below =
+    round(probability * 2^32), seed and epoch 0 unless given.  TypeError for what is neither None nor a dict, ValueError for a
+    probability that is missing, a NaN or outside [0, 1], an unknown key, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
+    if dropout is None:
+        return None
+    if not isinstance(dropout, dict):
+        raise TypeError("dropout is None or a dict of 'probability', 'seed' and 'epoch'")
+    unknown = set(dropout) - {"probability", "seed", "epoch"}
+    if unknown or "probability" not in dropout:
+        raise ValueError("dropout takes 'probability' and, if wanted, 'seed' and 'epoch'")
+    p, seed, epoch = float(dropout["probability"]), int(dropout.get("seed", 0)), int(dropout.get("epoch", 0))
+    if not 0.0 <= p <= 1.0:  # (false for a NaN)
+        raise ValueError("dropout: probability lies in [0, 1]")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("dropout: seed lies in [0, 2^64)")
+    if not 0 <= epoch < 1 << 32:
+        raise ValueError("dropout: epoch lies in [0, 2^32)")
+    return int(round(p * 4294967296.0)), seed, epoch
 
 
 MLM_COUNTS = ("n_eligible", "n_selected", "n_masked", "n_random", "n_kept")

@@ -23,11 +23,13 @@
 // costs 0.418 ms per call against FastBPE's 0.153 (2.7 x), 2 % more than the FastBPE kernel on the same improper table
 // (slow_word): DESIGN.md section 4.2d.
 #include <cstring>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 
 #include "swt_bpe_narrow.h"
 #include "swt_dedup.h"
+#include "swt_philox.h"
 #include "swt_tile.h"
 #include "swt_words.h"
 
@@ -192,15 +194,70 @@ __device__ uint32_t merge_word_ordered(uint32_t *s, uint32_t n, const BpeSlot *_
   return n;
 }
 
+// ---- BPE-dropout (include/swt.h, swt_bpe_encode_dropout): the loop of merge_word with every candidate pair of a round skipped
+// when its draw says so.  The draw of pair k in round t of the word with the key (i, b) -- its sentence and its first byte's
+// offset in it -- is word k & 3 of Philox at the counter ((t << 16) + (k >> 2), b, i, epoch): one call serves four neighbours.
+struct DropDraw {  // what a dropout launch draws with: kernel arguments of the dropout kernels, and of no other
+  unsigned long long drop_below;  // 0 .. 2^32
+  uint32_t key0, key1, epoch;
+};
+struct NoDrop {};  // what every other kernel carries in their place
+struct DropWord { uint32_t i, b; };
+// the draws of one round of one word, asked for in any order of k; the last call's four words are kept
+struct DropRound {
+  const DropDraw &dd;
+  const DropWord w;
+  const uint32_t t16;
+  uint32_t group = 0xFFFFFFFFu;  // k >> 2 of the call `x` holds (a word has fewer than 2^32 symbols: no group is all ones)
+  Philox x{};
+  __device__ __forceinline__ DropRound(const DropDraw &d, const DropWord &word, uint32_t t) : dd(d), w(word), t16(t << 16) {}
+  __device__ __forceinline__ bool dropped(uint32_t k) {
+    if ((k >> 2) != group) {
+      group = k >> 2;
+      x = philox4x32_10(t16 + group, w.b, w.i, dd.epoch, dd.key0, dd.key1);
+    }
+    const uint32_t q = k & 3u;
+    const uint32_t v = q == 0u ? x.x[0] : q == 1u ? x.x[1] : q == 2u ? x.x[2] : x.x[3];
+    return v < dd.drop_below;
+  }
+};
+
+// The serial form for the one-lane fallback (a word longer than a chunk), as merge_word.  Returns the new length.
+__device__ uint32_t merge_word_dropout(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh, const DropDraw &dd,
+                                       const DropWord &w) {
+  for (uint32_t t = 0; n >= 2; t++) {
+    DropRound R(dd, w, t);
+    uint32_t best = kNoRank, bm = 0, bl = 0, br = 0;
+    uint32_t a = s[0];
+    for (uint32_t k = 0; k + 1 < n; k++) {
+      const uint32_t b = s[k + 1];
+      uint32_t rk, mg;
+      // (a pair that does not beat the minimum so far cannot change it: its draw is not needed)
+      if (slot_lookup(slots, sh, a, b, rk, mg) && rk < best && !R.dropped(k)) { best = rk; bm = mg; bl = a; br = b; }
+      a = b;
+    }
+    if (best == kNoRank) break;
+    uint32_t j = 0, i = 0;  // i counts in the round's sequence, which is what a draw is indexed by; j <= i
+    while (i < n) {
+      const uint32_t x = s[i];
+      if (i + 1 < n && x == bl && s[i + 1] == br && !R.dropped(i)) { s[j++] = bm; i += 2; }
+      else { s[j++] = x; i++; }
+    }
+    n = j;
+  }
+  return n;
+}
+
 struct GiantResult { uint64_t end; uint32_t ntok; };
 
 // One lane, global memory only: the word (or single separator) starting at byte `pos`, bounded by
 // `send` (end of its sentence).  Tokens go to `out` (which doubles as the symbol workspace).
 // Ordered: the merges in list order (merge_word_ordered; `info` is its chain, unused otherwise).
-template <bool Packed, bool Ordered>
+// Draw = DropDraw: BPE-dropout with the draws `draw` and the word's key `w` (merge_word_dropout); NoDrop in every other kernel.
+template <bool Packed, bool Ordered, class Draw>
 __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos, uint64_t send,
                                   const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                  const uint32_t *__restrict__ info, uint32_t *out) {
+                                  const uint32_t *__restrict__ info, uint32_t *out, const Draw &draw, const DropWord &w) {
   GiantResult r{pos, 0};
   uint32_t n = 0;
   bool first = true;
@@ -220,7 +277,8 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
     r.end += len;
     first = false;
   }
-  n = Ordered ? merge_word_ordered<Packed>(out, n, slots, sh, info) : merge_word(out, n, slots, sh);
+  if constexpr (std::is_same_v<Draw, DropDraw>) n = merge_word_dropout(out, n, slots, sh, draw, w);
+  else n = Ordered ? merge_word_ordered<Packed>(out, n, slots, sh, info) : merge_word(out, n, slots, sh);
   for (uint32_t i = 1; i < n; i++) out[i] |= SWT_BPE_CONT;
   r.ntok = n;
   return r;
@@ -273,6 +331,10 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //          lane_tail) are plain minima, 6 vector instructions and 2 ds_read2_b32 per four slots where building the keys from the
 //          values took 15 and 4 (profiles/lane_keys.txt).  The merged code comes from the key's rank (narrow_merged): letters + rank
 //          in the kernel of a sequential table (template parameter Seq), code_of_rank[rank] in that of any other.
+//   Dropout: BPE-dropout (swt_bpe_encode_dropout*, include/swt.h): every multi-symbol word goes through dropout_word() /
+//          merge_word_dropout(), one lane per word, with the candidate pairs of every round dropped by their Philox draws.  Wide
+//          symbols, Modes 0 and 2 (two occurrences of a word may differ: no unique-word pass).  The draws are arguments of these
+//          instantiations alone (DirectDrop); the others carry a NoDrop and test nothing.  DESIGN.md section 4.2e.
 template <bool Narrow>
 struct LaneSym {  // how a symbol stands in LDS
   using type = uint32_t;
@@ -408,6 +470,42 @@ __device__ void ordered_word(uint32_t *S, uint32_t *V, const uint32_t n0, const 
     for (uint32_t k = 0; k + 1 < n; k++)
       if (V[k] == kDirtyVal)
         V[k] = ordered_value<Packed>(slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT), floor, info);
+  }
+  for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
+}
+
+// BPE-dropout on the same layout, modelled on slow_word: a round's minimum runs over the pairs that are not dropped, the merge
+// takes the occurrences of the winning pair that are not dropped, and t counts the rounds.  A cached value stays the pair's
+// rank whatever was dropped around it, so only the pairs a merge created are probed again.  The compaction reads slot i (the
+// index a draw goes by) and writes slot j <= i.
+template <bool Packed>
+__device__ void dropout_word(uint32_t *S, uint32_t *V, const uint32_t n0, const BpeSlot *__restrict__ slots, uint32_t sh,
+                             const uint32_t *__restrict__ merged_of_rank, const DropDraw &dd, const DropWord &w) {
+  uint32_t n = n0;
+  for (uint32_t t = 0;; t++) {
+    DropRound R(dd, w, t);
+    uint32_t m = kNoRank;
+    for (uint32_t k = 0; k + 1 < n; k++) {
+      const uint32_t v = V[k];
+      if (v < m && !R.dropped(k)) m = v;  // (a pair that does not beat the minimum so far cannot change it: no draw)
+    }
+    if (m == kNoRank) break;
+    const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+    uint32_t i = 0, j = 0;
+    while (i < n) {
+      const uint32_t vi = V[i];
+      const bool take = i + 1 < n && vi == m && !R.dropped(i);
+      const uint32_t s = take ? mg : (S[i] & ~SWT_BPE_CONT);
+      if (take && j) V[j - 1] = kDirtyVal;
+      S[j] = j ? (s | SWT_BPE_CONT) : s;
+      V[j] = take ? kDirtyVal : vi;
+      i += take ? 2u : 1u;
+      j++;
+    }
+    n = j;
+    V[n - 1] = kNoRank;
+    for (uint32_t k = 0; k + 1 < n; k++)
+      if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT);
   }
   for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
 }
@@ -582,12 +680,13 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
 
 // ---- the end of a chunk that does not end the tile: one word longer than the staged bytes goes to the one-lane walker (and the
 // chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list and moves T.cb past the chunk.
-template <int Cap, int Mode, bool Packed, bool Ordered, bool Narrow>
+// Draw: the draws of a dropout kernel (DropDraw; the word then goes through merge_word_dropout), NoDrop in every other.
+template <int Cap, int Mode, bool Packed, bool Ordered, bool Narrow, class Draw>
 __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap, Narrow> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
                                                const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
                                                const uint32_t *__restrict__ merged_of_rank, LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
                                                const uint32_t *__restrict__ uslot, unsigned long long *__restrict__ rec,
-                                               unsigned long long *__restrict__ drec, const DirectOut &direct) {
+                                               unsigned long long *__restrict__ drec, const DirectOut &direct, const Draw &draw) {
   constexpr bool kDirect = Mode == 2, kRec = Mode == 1;
   if (!C.last) {
     if (C.cut < 0) {
@@ -596,7 +695,10 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap, Narrow> &L, GiantRes
         uint64_t s = T.s_next;
         while (s < T.s_hi && sent_off[s] <= T.cb) s++;
         const uint64_t send = sent_off[s];  // s <= s_hi and sent_off[s_hi] = span_end > cb
-        giant = giant_word<Packed, Ordered>(text, T.cb, send, cls_tab, slots, sh, merged_of_rank, T.tile_out + T.run);
+        // dropout: the word's sentence is the last that starts at or before it, s - 1 (the tile's first starts at span_base <= cb: s > s_lo)
+        DropWord w{0u, 0u};
+        if constexpr (std::is_same_v<Draw, DropDraw>) w = DropWord{(uint32_t)(s - 1), (uint32_t)(T.cb - sent_off[s - 1])};
+        giant = giant_word<Packed, Ordered>(text, T.cb, send, cls_tab, slots, sh, merged_of_rank, T.tile_out + T.run, draw, w);
       }
       wave_sync();
       const GiantResult g = giant;
@@ -801,11 +903,42 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
   }
 }
 
+// BPE-dropout: what a lane needs beside the draws to find the key (i, b) of the word it takes -- the chunk's place in the text
+// and the tile's sentences.  A kernel without dropout carries a NoDrop in its place.
+struct DropSite {
+  DropDraw dd;
+  const uint64_t *sent_off;
+  uint64_t s_lo, s_hi;  // the tile's sentences: sent_off[s_lo] <= every byte of the tile < sent_off[s_hi]
+  uint64_t abase;       // LaneChunk::abase
+  uint32_t nblk;        // LaneChunk::nblk
+};
+// The key of the word whose first symbol is symbol `where` of the chunk.  Symbol -> byte is the inverse of the split's byte ->
+// symbol maps: the block whose sympre is the last at or below `where`, then that many set bits into its symmask.  Byte -> sentence
+// is a search of the tile's sentence offsets for the last at or below the byte (empty sentences share an offset with the next
+// sentence that has bytes, which is the last of them).
+template <int Cap>
+__device__ __forceinline__ DropWord drop_word_at(const LaneLds<Cap, false> &L, const DropSite &site, uint32_t where) {
+  uint32_t blk = 0;
+  while (blk + 1 < site.nblk && L.sympre[blk + 1] <= where) blk++;
+  unsigned long long m = L.symmask[blk];
+  for (uint32_t r = where - L.sympre[blk]; r != 0u && m != 0ull; r--) m &= m - 1ull;
+  const uint64_t pos = site.abase + (uint64_t)blk * 64u + (m ? (uint32_t)__builtin_ctzll(m) : 0u);
+  uint64_t lo = site.s_lo, hi = site.s_hi;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (site.sent_off[mid] <= pos) lo = mid; else hi = mid;
+  }
+  return DropWord{(uint32_t)lo, (uint32_t)(pos - site.sent_off[lo])};
+}
+
 // The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
-template <bool Packed, bool Proper, bool Seq, int Cap, bool Ordered, bool Narrow>
+// Site: DropSite in a dropout kernel, where every multi-symbol word goes through dropout_word(); NoDrop in every other.
+template <bool Packed, bool Proper, bool Seq, int Cap, bool Ordered, bool Narrow, class Site>
 __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const uint16_t *list, uint32_t n_list, int lane,
                                                 const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
-                                                const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D) {
+                                                const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D, const Site &site) {
+  constexpr bool Dropout = std::is_same_v<Site, DropSite>;
+  static_assert(!(Dropout && (Narrow || Ordered)), "the dropout form: wide symbols, FastBPE's ranks");
   static_assert(!(Narrow && (Ordered || !Packed)), "the narrow form is that of a packed table in FastBPE's order");
   constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
@@ -827,7 +960,10 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
         S = &L.sym[where];
         V = &L.val[where];
         alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
-        if constexpr (Ordered) {
+        if constexpr (Dropout) {
+          dropout_word<Packed>(S, V, n, slots, sh, merged_of_rank, site.dd, drop_word_at(L, site, where));
+          n = 0u;
+        } else if constexpr (Ordered) {
           ordered_word<Packed>(S, V, n, slots, sh, merged_of_rank);
           n = 0u;
         } else if (!Proper || n > 32u) {
@@ -935,19 +1071,27 @@ __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 #endif
 
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
-template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false, bool Seq = false>
+// The DROPOUT form (swt_bpe_encode_dropout*, include/swt.h; template parameter Dropout): the same wave over the same staging,
+// split, emit, scan and gather, every multi-symbol word through dropout_word() -- one lane per word, as the ordered form -- and
+// a word longer than a chunk through merge_word_dropout().  Wide symbols, Mode 0 or 2.  Its draws travel behind the DirectOut in
+// its last argument (DirectDrop); every other instantiation has the arguments it always had, carries a NoDrop and tests nothing.
+struct DirectDrop : DirectOut { DropDraw draw; };
+template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false, bool Seq = false, bool Dropout = false>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots,
     uint32_t sh, const uint32_t *__restrict__ merged_of_rank, uint32_t *__restrict__ scratch,
     uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, const uint32_t *__restrict__ uslot,
-    unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec, DirectOut direct) {
+    unsigned long long *__restrict__ rec, unsigned long long *__restrict__ drec, std::conditional_t<Dropout, DirectDrop, DirectOut> direct) {
   constexpr bool kDirect = Mode == 2;
   static_assert(Cap % 64 == 0 && Cap <= 4032, "11 B of LDS per staged byte and the masks (Narrow: 9 B); wl[] and the word list hold 16-bit indices");
   static_assert(!Narrow || (Mode == 0 && Packed && !Ordered), "the narrow form: running text, a packed table, FastBPE's order");
   static_assert(!Seq || Narrow, "Seq says where the narrow form's rounds get the merged code from");
   static_assert(!Narrow || kLaneCap != 512 || sizeof(LaneLds<Cap, true>) + sizeof(LaneShared<true>) <= sizeof(LaneLds<kLaneCap>) + sizeof(LaneShared<false>),
                 "the narrow kernel's chunk is sized to the LDS of the wide one, so that as many waves reside");
+  static_assert(!Dropout || (Mode != 1 && !Narrow && !Ordered && !Proper), "the dropout form: running text or the single workgroup, wide symbols, FastBPE's ranks");
+  std::conditional_t<Dropout, DropDraw, NoDrop> draw{};
+  if constexpr (Dropout) draw = direct.draw;
   using Slot = typename LaneSym<Narrow>::Slot;
   __shared__ LaneLds<Cap, Narrow> L;
   __shared__ LaneShared<Narrow> SH;
@@ -979,14 +1123,17 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     lane_split(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
     // (the one-lane walker of a word longer than a chunk works on ids, whatever the kernel's symbols are)
     lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, Narrow ? D.wide_slots : slots, Narrow ? D.wide_sh : sh, merged_of_rank, T, C,
-                                               lane, sent_local, uslot, rec, drec, direct);
+                                               lane, sent_local, uslot, rec, drec, direct, draw);
     if (C.giant) continue;
     uint32_t c2, c1, c0;
     lane_words_count(L, C.nw, lane, c2, c1, c0);
     lane_words_write(L, C.nw, lane, list, 0u, c2, c2 + c1);
     wave_sync();
     // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
-    const LaneWord W = lane_rounds<Packed, Proper, Seq, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank, D);
+    // (dropout: every word is finished where its lane takes it, and nothing is left for the tail)
+    std::conditional_t<Dropout, DropSite, NoDrop> site{};
+    if constexpr (Dropout) site = DropSite{draw, sent_off, T.s_lo, T.s_hi, C.abase, C.nblk};
+    const LaneWord W = lane_rounds<Packed, Proper, Seq, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank, D, site);
     const unsigned long long BUSY = __ballot(W.n != 0u);
     if (BUSY != 0ull) lane_tail<Packed, 4, Seq, Cap>(L, W, BUSY, lane, tab, sh, merged_of_rank, D);
     wave_sync();
@@ -1036,7 +1183,7 @@ struct swt_bpe_table {
   int opt_lane_slots = 0;   // SWT_OPT_LANE_SLOTS
   int opt_lane_narrow = 0;  // SWT_OPT_LANE_NARROW
   int last_lane_narrow = -1;  // what the last running-text launch took: 1 the narrow kernel, 0 a wide one, -1 none yet (diagnostics)
-  uint64_t lane_slots[3] = {0, 0, 0};  // wave slots of the device for the running-text kernel of this table ([1]: its ordered form, [2]: its narrow form)
+  uint64_t lane_slots[4] = {0, 0, 0, 0};  // wave slots of the device for the running-text kernel of this table ([1]: its ordered form, [2]: its narrow form, [3]: its dropout form)
   // 16-bit symbol codes (swt_bpe_narrow.h) for the narrow form of the running-text kernel; empty unless narrow.eligible
   NarrowTable narrow;
   NarrowSlot *d_nslots = nullptr;
@@ -1129,10 +1276,16 @@ static LaneKernel lane_kernel(const swt_bpe_table *t, bool ordered, int cap = kL
 // narrow kernel, 2.5 MB gains 5).  SWT_OPT_LANE_NARROW = 1 keeps the wide kernel, 2 takes the narrow one at every size.  The
 // unique-word pass and the single workgroup stay wide: their chunks are sized by their tiles (128 to 512 bytes of words, one
 // short call), not by the LDS, so 16-bit symbols would buy them nothing.
-static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow);
+static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow, bool dropout = false);
 static bool lane_narrow(swt_bpe_table *t, bool ordered, uint64_t n_bytes) {
   if (!t->narrow.eligible || ordered || t->opt_lane_narrow == 1) return false;
   return t->opt_lane_narrow == 2 || n_bytes >= (uint64_t)kLaneTile * lane_slots(t, false, false);
+}
+// The dropout form (bpe_lane_kernel's Dropout): running text or the single workgroup, by the table's values alone.
+using DropoutKernel = decltype(&bpe_lane_kernel<true, false, kLaneCap, 0, false, false, false, true>);
+template <int Mode>
+static DropoutKernel lane_kernel_dropout(const swt_bpe_table *t) {
+  return t->packed ? bpe_lane_kernel<true, false, kLaneCap, Mode, false, false, false, true> : bpe_lane_kernel<false, false, kLaneCap, Mode, false, false, false, true>;
 }
 static LaneKernel lane_kernel_narrow(const swt_bpe_table *t) {
   if (t->narrow.sequential) return t->proper ? bpe_lane_kernel<true, true, kNarrowCap, 0, false, true, true> : bpe_lane_kernel<true, false, kNarrowCap, 0, false, true, true>;
@@ -1401,12 +1554,14 @@ static void launch_encode_kernel(swt_bpe_table *t, uint64_t n_tiles, const TileW
 static uint32_t lane_span(const swt_bpe_table *t) { return t->opt_lane_span ? (uint32_t)t->opt_lane_span : 1u; }
 
 // Wave slots of the device for the running-text kernel this table gets: CUs x resident workgroups per CU, asked once per handle.
-static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow) {
+static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow, bool dropout) {
   if (t->opt_lane_slots) return (uint64_t)t->opt_lane_slots;
-  uint64_t &slots = t->lane_slots[narrow ? 2 : ordered ? 1 : 0];
+  uint64_t &slots = t->lane_slots[dropout ? 3 : narrow ? 2 : ordered ? 1 : 0];
   if (!slots) {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow ? lane_kernel_narrow(t) : lane_kernel<0>(t, ordered), 64, 0) != hipSuccess || per_cu < 1) {
+    const hipError_t e = dropout ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lane_kernel_dropout<0>(t), 64, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, narrow ? lane_kernel_narrow(t) : lane_kernel<0>(t, ordered), 64, 0);
+    if (e != hipSuccess || per_cu < 1) {
       (void)hipGetLastError();
       per_cu = 24;  // what the stamps show resident on gfx950
     }
@@ -1420,13 +1575,14 @@ static uint64_t lane_slots(swt_bpe_table *t, bool ordered, bool narrow) {
 // then 256, 192 and 128 bytes by the same rule (tilemap_taper), so that the waves started last have short lives.  A short tile
 // is dear (a wave's life is ~12 us + 0.047 us per byte), so the taper is short: c = 3/8 and no tile under 192 bytes unless
 // SWT_OPT_LANE_TAPER says otherwise (profiles/lane_taper.txt section 2: c = 1 down to 128 bytes LOSES 6 us to tiles of one size).
-static TileMap lane_map(swt_bpe_table *t, uint64_t n_bytes, bool ordered) {
+// dropout: the call runs the dropout form, a wide kernel with wave slots of its own.
+static TileMap lane_map(swt_bpe_table *t, uint64_t n_bytes, bool ordered, bool dropout = false) {
   const uint32_t span = lane_span(t);
-  const bool wide = !lane_narrow_tiles(t, ordered, n_bytes);
+  const bool wide = dropout || !lane_narrow_tiles(t, ordered, n_bytes);
   const uint32_t tile = wide ? (uint32_t)kLaneTile : (uint32_t)kNarrowTile;
   const int v = t->opt_lane_taper ? t->opt_lane_taper : wide ? kTaperDefault : kNarrowTaperDefault;
   if (span > 1 || v == 1 || tile <= 256) return tilemap_uniform(n_bytes, tile * span);
-  const uint64_t slots = lane_slots(t, ordered, lane_narrow(t, ordered, n_bytes));
+  const uint64_t slots = lane_slots(t, ordered, !dropout && lane_narrow(t, ordered, n_bytes), dropout);
   // The floor of the library's own choice: a text under two chip-fulls of full tiles keeps tiles of one size (2.5 MB measured
   // 2.2 us slower tapered, profiles/lane_taper.txt section 3).  An explicit SWT_OPT_LANE_TAPER tapers whatever the size.
   // The narrow kernel's tiles taper wherever the library's own choice runs it, from one chip-full of kLaneTile-byte tiles (its
@@ -1456,11 +1612,11 @@ int swt_debug_bpe_tile_map(swt_bpe_table *t, uint64_t n_bytes, uint64_t *out) tr
 
 static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, const uint8_t *d_cls,
-                             hipStream_t st, bool ordered) {
+                             hipStream_t st, bool ordered, const DropDraw *drop = nullptr) {
   // plan, scan and gather see a span as one tile of K * kLaneTile bytes (plan[j] of that size IS plan[j * K] of the tiles), and so
   // does the kernel: its chunk loop walks the span kLaneCap bytes at a time.  None of them learns a tile's size: the map goes to
   // the plan and everything behind it reads plan[t] and plan[t + 1].
-  const TileMap map = n_bytes <= kDirectBytes && n_sent <= kDirectSents ? tilemap_uniform(n_bytes, kLaneTile) : lane_map(t, n_bytes, ordered);
+  const TileMap map = n_bytes <= kDirectBytes && n_sent <= kDirectSents ? tilemap_uniform(n_bytes, kLaneTile) : lane_map(t, n_bytes, ordered, drop != nullptr);
   const uint64_t n_tiles = map.n_tiles;
   if (n_tiles > 0x7FFFFFFFull)
     return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
@@ -1469,9 +1625,14 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
     // a sentence or a few: one workgroup, one launch, the caller's arrays written by the kernel (DirectOut)
     if ((rc = ws.reserve(64, 0, 1))) return rc;
     const BpeView v = bpe_view(t, ordered);
-    hipLaunchKernelGGL(lane_kernel<2>(t, ordered), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots,
-                       v.sh, v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
-                       (unsigned long long *)nullptr, (unsigned long long *)nullptr, DirectOut{d_out_off, d_n_tokens, n_sent});
+    if (drop)
+      hipLaunchKernelGGL(lane_kernel_dropout<2>(t), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots,
+                         v.sh, v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
+                         (unsigned long long *)nullptr, (unsigned long long *)nullptr, DirectDrop{{d_out_off, d_n_tokens, n_sent}, *drop});
+    else
+      hipLaunchKernelGGL(lane_kernel<2>(t, ordered), dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, v.slots,
+                         v.sh, v.merged, d_out_ids, ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(), (const uint32_t *)nullptr,
+                         (unsigned long long *)nullptr, (unsigned long long *)nullptr, DirectOut{d_out_off, d_n_tokens, n_sent});
     SWT_HIP(hipGetLastError());
     return SWT_OK;
   }
@@ -1479,7 +1640,13 @@ static int bpe_encode_direct(swt_bpe_table *t, TileWorkspace &ws, const uint8_t 
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, map, ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st, ordered);
+  if (drop) {
+    const BpeView v = bpe_view(t, false);
+    hipLaunchKernelGGL(lane_kernel_dropout<0>(t), dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off, ws.plan.as<uint64_t>(), d_cls,
+                       v.slots, v.sh, v.merged, ws.scratch.as<uint32_t>(), ws.sent_local.as<uint32_t>(), ws.tile_tok.as<uint32_t>(),
+                       (const uint32_t *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr, DirectDrop{{nullptr, nullptr, 0}, *drop});
+  } else
+    launch_encode_kernel(t, n_tiles, ws, d_text, n_bytes, d_sent_off, d_cls, nullptr, nullptr, nullptr, st, ordered);
   prof_end(st);
   launch_scan_gather(d_sent_off, n_sent, n_tiles, ws, d_out_ids, d_out_off, d_n_tokens, st);
   prof_end(st, 2);
@@ -1526,7 +1693,7 @@ static bool bpe_ordered(const swt_bpe_table *t) { return t && !t->order_equivale
 
 static int bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                           uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
-                          void *stream, bool ordered) {
+                          void *stream, bool ordered, const DropDraw *drop = nullptr) {
   if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_bytes && (!d_text || !d_out_ids)))
     return fail(SWT_ERR_INVALID, "null argument");
   int rc = bpe_upload(t);
@@ -1542,29 +1709,33 @@ static int bpe_encode_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_by
   }
   const bool raw = (flags & SWT_BPE_RAW_WORDS) != 0;
   // debug knob 1: bit 0 = never dedup, bit 1 = dedup whatever the batch size (tests)
-  if (!raw && !(flags & SWT_BPE_NO_DEDUP) && t->dd.opt_mode != 1 &&
+  // (a dropout call never dedups: two occurrences of a word may come out differently)
+  if (!drop && !raw && !(flags & SWT_BPE_NO_DEDUP) && t->dd.opt_mode != 1 &&
       (t->dd.opt_mode == 2 || (n_bytes >= kDedupMinBytes && t->dd.pays(n_bytes)))) {
     rc = bpe_encode_dedup(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, d_cls, st, ordered);
     if (rc == 0 && t->dd.opt_mode == 0) t->dd.note(n_bytes, st);
     if (rc <= 0) return rc;  // done, or a real error
   }
   // raw-word mode: no classes, so nothing splits and nothing is dropped
-  return bpe_encode_direct(t, t->ws, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, raw ? nullptr : d_cls, st, ordered);
+  return bpe_encode_direct(t, t->ws, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, raw ? nullptr : d_cls, st, ordered, drop);
 }
 
 // What the host-call layer (swt_tile.h) needs to know of this encoder, in either order.
-static HostEncoder bpe_host(swt_bpe_table *t, uint32_t flags, bool ordered) {
+// drop: the draws of a dropout call (copied: the encoder may outlive the caller's), null for every other.
+static HostEncoder bpe_host(swt_bpe_table *t, uint32_t flags, bool ordered, const DropDraw *drop = nullptr) {
+  const bool dropout = drop != nullptr;
+  const DropDraw dd = drop ? *drop : DropDraw{};
   return HostEncoder{[t] { return bpe_upload(t); },
-                     [t, flags, ordered](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent, uint32_t *d_ids,
-                                         uint64_t *d_out_off, uint8_t *, uint64_t *d_n_tokens) {
-                       return bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, d_ids, d_out_off, d_n_tokens, flags, nullptr, ordered);
+                     [t, flags, ordered, dropout, dd](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n_sent, uint32_t *d_ids,
+                                                      uint64_t *d_out_off, uint8_t *, uint64_t *d_n_tokens) {
+                       return bpe_encode_dev(t, d_text, n_bytes, d_off, n_sent, d_ids, d_out_off, d_n_tokens, flags, nullptr, ordered, dropout ? &dd : nullptr);
                      },
                      kDirectBytes, kDirectSents, false};
 }
 static int bpe_encode_host(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
-                           uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered) {
+                           uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, bool ordered, const DropDraw *drop = nullptr) {
   if (!t) return fail(SWT_ERR_INVALID, "null argument");
-  return host_encode(t->stage, bpe_host(t, flags, ordered), text, sent_off, n_sent, out_ids, out_cap, out_off, nullptr, n_tokens);
+  return host_encode(t->stage, bpe_host(t, flags, ordered, drop), text, sent_off, n_sent, out_ids, out_cap, out_off, nullptr, n_tokens);
 }
 static int bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
                              uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags, bool ordered) {
@@ -1588,6 +1759,30 @@ int swt_bpe_encode(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_o
 int swt_bpe_encode_joined(swt_bpe_table *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids, uint64_t out_cap,
                           uint64_t *out_off, uint64_t *n_tokens, uint8_t *need_host, uint32_t flags) try {
   return bpe_encode_joined(t, joined, n_joined, n_sent, out_ids, out_cap, out_off, n_tokens, need_host, flags, false);
+} SWT_API_CATCH
+
+// BPE-dropout (include/swt.h): the encode above with every candidate merge dropped by its Philox draw.  The draws of a call, or
+// the refusal of a threshold above 2^32.
+static int bpe_drop_draw(uint64_t drop_below, uint64_t seed, uint32_t epoch, DropDraw &out) {
+  if (drop_below > (1ull << 32)) return fail(SWT_ERR_INVALID, "drop_below is above 2^32");
+  out = DropDraw{drop_below, (uint32_t)seed, (uint32_t)(seed >> 32), epoch};
+  return SWT_OK;
+}
+
+int swt_bpe_encode_dropout_dev(swt_bpe_table *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                               uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint64_t *d_n_tokens, uint32_t flags,
+                               uint64_t drop_below, uint64_t seed, uint32_t epoch, void *stream) try {
+  DropDraw dd;
+  if (int rc = bpe_drop_draw(drop_below, seed, epoch, dd)) return rc;
+  return bpe_encode_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, flags, stream, false, &dd);
+} SWT_API_CATCH
+
+int swt_bpe_encode_dropout(swt_bpe_table *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                           uint64_t out_cap, uint64_t *out_off, uint64_t *n_tokens, uint32_t flags, uint64_t drop_below, uint64_t seed,
+                           uint32_t epoch) try {
+  DropDraw dd;
+  if (int rc = bpe_drop_draw(drop_below, seed, epoch, dd)) return rc;
+  return bpe_encode_host(t, text, sent_off, n_sent, out_ids, out_cap, out_off, n_tokens, flags, false, &dd);
 } SWT_API_CATCH
 
 // NaiveBPE.tokenize (bpe.py:136-158: the split of utils.py:26-29, then encode_word, bpe.py:114-134, per word) for a batch: the

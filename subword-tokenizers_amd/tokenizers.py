@@ -98,7 +98,8 @@ class SubwordTokenizer:
                      return_overflowing: bool = False, return_offsets: bool = False, int64: bool = False, device: bool = False,
                      text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
                      return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False,
-                     packing: Optional[str] = None, drop_last: bool = False, mlm: Optional[dict] = None) -> dict:
+                     packing: Optional[str] = None, drop_last: bool = False, mlm: Optional[dict] = None,
+                     dropout: Optional[dict] = None) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
@@ -124,10 +125,14 @@ class SubwordTokenizer:
         and left padding do not go with packing: ValueError.
 
         mlm, a dict of mask_tokens keywords ({} for its defaults), masks the finished rows of any of these forms for the masked-LM
-        objective: "input_ids" are the masked ids and the result gains "labels" and the five counts of mask_tokens."""
+        objective: "input_ids" are the masked ids and the result gains "labels" and the five counts of mask_tokens.
+
+        dropout = {"probability": p, "seed": 0, "epoch": 0} (FastBPE; any other class raises ValueError) encodes with BPE-dropout,
+        as FastBPE.encode_ids_batch: every form above -- pairs, windows, offsets, packing, mlm, device -- then works on those ids.
+        The sentence index of the draws is the text's index, and len(texts) + j for text_pairs[j]."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                                     return_special_tokens_mask, packing, drop_last, mlm)
+                                     return_special_tokens_mask, packing, drop_last, mlm, dropout)
 
     def mask_id(self) -> int:
         """The dense id of "[MASK]": its index where the vocabulary holds the string, else len(vocab_list()), one past the end,
@@ -257,11 +262,14 @@ class SubwordTokenizer:
     def _batch_vocabulary(self):
         return self._enc.vocabulary()
 
-    def _batch_encode_spans(self, texts):
-        return self.encode_spans_batch(texts)
+    def _batch_encode_ids(self, texts, dropout=None):
+        return self.encode_ids_batch(texts) if dropout is None else self.encode_ids_batch(texts, dropout=dropout)
 
-    def _batch_encode_dev(self, *args):
-        return _encode_dev(self._enc, *args)
+    def _batch_encode_spans(self, texts, dropout=None):
+        return self.encode_spans_batch(texts) if dropout is None else _encode_spans(self._enc, texts, dropout)
+
+    def _batch_encode_dev(self, *args, dropout=None):
+        return _encode_dev(self._enc, *args, dropout=dropout)
 
 
 _CLS_CACHE: Dict[str, int] = {}
@@ -317,13 +325,17 @@ class _Encoder:
     ensure: the tokenizer's method that returns the live N.BpeTable / N.WpTrie; spelling: its attribute that spells the ids,
     a _SymbolTable (BPE) or the token list (WordPiece); naive: the `encode_naive*` entries instead of `encode*`; complain:
     what raises for a sentence's status (WordPiece; None: BPE, which has no statuses); corner: an id past "[UNK]" stands for
-    the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE)."""
+    the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE);
+    dropout: the handle has the `encode_dropout*` entries, a third set beside the two (FastBPE)."""
 
     def __init__(self, tok, ensure, spelling, naive, error="Text to tokenize must be a string.", complain=None, corner=False,
-                 first=False):
+                 first=False, dropout=False):
         self._tok, self._ensure, self._spelling = weakref.proxy(tok), ensure, spelling  # (no cycle: a tokenizer dies with its last name)
         self.host = "encode_naive" if naive else "encode"  # the three call forms on the handle, by name
         self.joined, self.dev = self.host + "_joined", self.host + "_dev"
+        # BPE-dropout: a host and a `_dev` form, no joined one -- a word's draws go by its byte offset in pack_and_lower's text,
+        # so every dropout call takes the long way
+        self.drop_host, self.drop_dev = ("encode_dropout", "encode_dropout_dev") if dropout else (None, None)
         self.error, self.complain, self.corner, self.first = error, complain, corner, first
         self.flagged = complain is None  # BPE ids carry SWT_BPE_CONT over SYM_BASE + k; WordPiece ids index the token list
         self.len_base = N.SYM_BASE if self.flagged else 0
@@ -335,6 +347,15 @@ class _Encoder:
     def spelling(self):
         """as the last handle() left it"""
         return getattr(self._tok, self._spelling)
+
+    def draw(self, dropout):
+        """a `dropout` argument -> None, or the (drop_below, seed, epoch) of this encoder's dropout entries; ValueError for an
+        encoder that has none, and for arguments that give no draw (batching.dropout_draw)"""
+        if dropout is None:
+            return None
+        if self.drop_host is None:
+            raise ValueError("dropout: only FastBPE drops merges (BPE-dropout); this tokenizer takes dropout=None")
+        return batching.dropout_draw(dropout)
 
     def names(self) -> List[str]:
         """WordPiece: the token of every id below the corner's"""
@@ -373,10 +394,12 @@ def _raise_flagged(enc: _Encoder, status, texts) -> None:
         enc.complain(int(status[i]), texts[int(i)])
 
 
-def _encode_ids(enc: _Encoder, texts):
+def _encode_ids(enc: _Encoder, texts, dropout=None):
     """encode_ids_batch of every class: the argument checks in the class's order, then the route -- past 64 texts the joined
     call (strings -> joined bytes -> ids: the device splits, lowercases (utils.py:27) and encodes, the prepared
-    text never comes back); texts with U+0000 inside, or that only str.lower() lowercases, and small batches go the long way"""
+    text never comes back); texts with U+0000 inside, or that only str.lower() lowercases, and small batches go the long way.
+    dropout (FastBPE; None: everything above, untouched): BPE-dropout through the encoder's dropout entry, always the long way."""
+    draw = enc.draw(dropout)
     if not isinstance(texts, list):
         raise TypeError(enc.error)
     if enc.first:
@@ -393,11 +416,13 @@ def _encode_ids(enc: _Encoder, texts):
             raise
     if not few:
         joined, n_nul = N.join_texts(texts, enc.error)
-        if n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
+        if draw is None and n_nul == 0 and joined.size + 1 != len(texts) and N.device_lower_ok():
             got = getattr(handle, enc.joined)(joined, len(texts))
             if got is not None:
                 return got
     text, off = N.pack_and_lower(texts)  # utils.py:27 / wordpiece.py:248 lower()
+    if draw is not None:
+        return getattr(handle, enc.drop_host)(text, off, draw)
     return getattr(handle, enc.host)(text, off)
 
 
@@ -418,14 +443,16 @@ def _bpe_tokens(enc: _Encoder, ids, off=None):
     return N.nested_lists_by_key(key, cap, spell, off)
 
 
-def _encode_spans(enc: _Encoder, texts):
+def _encode_spans(enc: _Encoder, texts, dropout=None):
     """encode_spans_batch by tiling (NaiveBPE, FastBPE, NaiveWP): the host encode's results with (spans, word ids) behind them.
-    The text is packed once and sent to the device twice, for the encode and for swt_token_spans."""
+    The text is packed once and sent to the device twice, for the encode and for swt_token_spans.  dropout: as _encode_ids --
+    any segmentation of a word tiles it, so the spans need nothing more."""
+    draw = enc.draw(dropout)
     if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
         raise TypeError("Text to tokenize must be a string.")
     handle = enc.handle()
     text, off = N.pack_and_lower(texts)
-    got = getattr(handle, enc.host)(text, off)
+    got = getattr(handle, enc.host)(text, off) if draw is None else getattr(handle, enc.drop_host)(text, off, draw)
     if enc.complain is not None:
         _raise_flagged(enc, got[2], texts)
     spans, word, status = N.token_spans(text, off, got[0], got[1], enc.lengths(), enc.len_base, enc.flagged)
@@ -434,12 +461,15 @@ def _encode_spans(enc: _Encoder, texts):
     return got + (spans, word)
 
 
-def _encode_dev(enc: _Encoder, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty):
-    """the `_dev` encode on the caller's torch buffers, then swt_token_spans_dev when spans are wanted
+def _encode_dev(enc: _Encoder, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, d_spans, d_word, stream, empty, dropout=None):
+    """the `_dev` encode on the caller's torch buffers (dropout: its dropout form), then swt_token_spans_dev when spans are wanted
     -> [(status tensor, what to raise for a status)]"""
     import torch
+    draw = enc.draw(dropout)
     call, checks = getattr(enc.handle(), enc.dev), []
-    if enc.complain is None:
+    if draw is not None:
+        getattr(enc.handle(), enc.drop_dev)(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, draw, 0, stream)
+    elif enc.complain is None:
         call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
     else:
         d_status = empty(n_sent + 8, torch.uint8)
@@ -630,17 +660,17 @@ class NaiveBPE(SubwordTokenizer):
             self._naive_table, self._naive_syms, self._naive_merges = N.BpeTable(left, right, merged), syms, merges
         return self._naive_table
 
-    def encode_ids_batch(self, texts: List[str]) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
-        over this object's own symbol table (decode_ids spells them)."""
-        return _encode_ids(self._enc, texts)
+        over this object's own symbol table (decode_ids spells them).  dropout: None; anything else is FastBPE's (ValueError)."""
+        return _encode_ids(self._enc, texts, dropout)
 
     def decode_ids(self, ids) -> List[str]:
         return _bpe_tokens(self._enc, ids)
 
-    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts]"""
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts))
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout))
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
     def _span_parts(self):
@@ -695,7 +725,7 @@ class FastBPE(NaiveBPE):
         self._bpe_ranks: Dict[Tuple[str, str], int] = {}
         self._table: Optional[N.BpeTable] = None
         self._syms = _SymbolTable()
-        self._enc = _Encoder(self, "_ensure_table", "_syms", naive=False, error="Text must be a string.", first=True)
+        self._enc = _Encoder(self, "_ensure_table", "_syms", naive=False, error="Text must be a string.", first=True, dropout=True)
 
     def _build_table(self) -> None:
         # bpe.py:200 / :257
@@ -738,12 +768,19 @@ class FastBPE(NaiveBPE):
         return _bpe_tokens(self._enc, ids)
 
     # -- batch entry points (not in the reference); FastBPE's own, like the reference's methods of the same class
-    def encode_ids_batch(self, texts: List[str]) -> Tuple[np.ndarray, np.ndarray]:
-        """texts -> (token ids uint32, sentence offsets uint64[n+1]); ids as defined in include/swt.h."""
-        return _encode_ids(self._enc, texts)
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """texts -> (token ids uint32, sentence offsets uint64[n+1]); ids as defined in include/swt.h.
 
-    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts))
+        dropout = {"probability": p, "seed": 0, "epoch": 0}: BPE-dropout (Provilkov et al. 2020) on the device
+        (swt_bpe_encode_dropout, where the rule stands in full).  At every merge step of a word each candidate merge is skipped
+        with probability p, so a text gets another segmentation per (seed, epoch) -- and the same one for the same (seed, epoch,
+        index in `texts`), whatever the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain
+        encode, p = 1 leaves every word as its characters.  ValueError: a probability outside [0, 1] or a NaN, a seed outside
+        [0, 2^64), an epoch outside [0, 2^32), an unknown key."""
+        return _encode_ids(self._enc, texts, dropout)
+
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout))
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -755,10 +792,10 @@ class FastBPE(NaiveBPE):
         return self.decode_ids(ids)
 
     # -- bpe.py:245-249
-    def tokenize(self, text: str) -> List[str]:
+    def tokenize(self, text: str, dropout: Optional[dict] = None) -> List[str]:
         if not isinstance(text, str):
             raise TypeError("Text must be a string.")
-        return self.tokenize_batch([text])[0]
+        return self.tokenize_batch([text], dropout)[0]
 
     # -- bpe.py:251-263
     def load_resources(self, path: str) -> None:
@@ -933,15 +970,16 @@ class NaiveWP(SubwordTokenizer):
             self._naive_trie = N.WpTrie(self._naive_tokens)
         return self._naive_trie
 
-    def encode_ids_batch(self, texts: List[str]):
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]): tokenize() of every text on the device.  ids index
-        sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns."""
-        return _encode_ids(self._enc, texts)
+        sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns.
+        dropout: None; anything else is FastBPE's (ValueError)."""
+        return _encode_ids(self._enc, texts, dropout)
 
-    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
         deviation: the reference hangs)."""
-        ids, off, status = self.encode_ids_batch(texts)
+        ids, off, status = self.encode_ids_batch(texts, dropout)
         _raise_flagged(self._enc, status, texts)
         return N.nested_lists(self._enc.names(), ids, off)
 
@@ -1109,12 +1147,13 @@ class FastWP(NaiveWP):
         self._build_trie()
 
     # -- batch entry points (not in the reference)
-    def encode_ids_batch(self, texts: List[str]):
-        """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status."""
-        return _encode_ids(self._enc, texts)
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None):
+        """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status.
+        dropout: None; anything else is FastBPE's (ValueError)."""
+        return _encode_ids(self._enc, texts, dropout)
 
-    def tokenize_batch(self, texts: List[str]) -> List[List[str]]:
-        ids, off, status = self.encode_ids_batch(texts)
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
+        ids, off, status = self.encode_ids_batch(texts, dropout)
         _raise_flagged(self._enc, status, texts)
         if ids.size and int(ids.max()) <= len(self._tokens) + 1:  # no multi-token corner: one table, references handed out
             if ids.size < 4096:
