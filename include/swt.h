@@ -965,6 +965,68 @@ int swt_entity_spans_dev(const int32_t *d_label, const float *d_score, const uin
                          uint32_t n_labels, int32_t *d_ent_text, int32_t *d_ent_type, int32_t *d_ent_first_word, int32_t *d_ent_last_word,
                          uint32_t *d_ent_char_start, uint32_t *d_ent_char_end, float *d_ent_score, uint64_t *d_info, void *stream);
 int swt_tag_capacity(uint32_t *cols_per_step, uint32_t *text_rows, uint32_t *scan_words);
+
+/* ------------------------------------------------------------------------------------------------
+ * Masked-LM inference: from a model's logits (float32[rows, width, n_vocab], C-contiguous, aligned to 4 bytes and no more) the
+ * scores of SELECTED cells only -- the counterpart of the masked-LM block above, which makes the masked rows and their labels.
+ * A cell is named by its flat index row * width + col.  The reference has nothing of the sort; tests/fill_cases.py holds these
+ * semantics.  The argument checks and the `_dev` forms follow the labels block.
+ *
+ * 1. swt_mlm_positions: over ids[rows, width] (int32, int64 with SWT_FILL_IDS64; any input_ids or labels of the calls above) the
+ * cells with ids == value (SWT_FILL_EQUAL: input_ids == [MASK]) or ids != value (SWT_FILL_NOT_EQUAL: labels != -100); the compare
+ * is signed, of the id widened to 64 bits.  out_pos (uint64[rows * width]): the flat indices of the selected cells in ascending
+ * order, every element from the count on UINT64_MAX.  info[2] (required): the count, the cells looked at.  The plan half of a
+ * plan / rows pair: the caller reads the count back and sizes the arrays of 2. with it.  Fewer than 2^32 cells.
+ *
+ * 2. swt_mlm_predict: for position p < n_pos the row x[0, n_vocab) = logits[pos[p]] is read, and nothing of any other cell.
+ * labels[rows, width] (int32, int64 with SWT_FILL_IDS64) may be NULL, and then the three label outputs must be; 0 <= k <= 64,
+ * and k == 0 needs out_top_id and out_top_logit NULL.  Every output may be NULL.
+ *   THE ORDER of the entries of a row that are no NaN: the greater logit first (-0.0 == 0.0), among equal logits the smaller
+ *   index.  It is total, so that nothing below depends on how it is reduced.  A NaN is never in it.
+ *   out_lse[p] (float32) = m + logf(S), m = max x_i, S = sum of expf(x_i - m), in float32.  NaN when any entry is a NaN, -inf
+ *   when m is -inf, +inf when m is +inf.  The order of the additions is the kernel's own and THE ONLY THING HERE THAT IS NOT
+ *   EXACT: with s = floats_per_step of swt_fill_capacity a term expf(x_i - m) passes at most
+ *       chain(V) = min(V - 1, ceil(V / s) + 8)
+ *   float32 additions with another nonzero term -- ceil(V / s) in its lane (a sum per column of the lane's quad, one addition a
+ *   step, and a lane has ceil(quads / 64) <= ceil(V / s) steps; the first sum starts from the lane's float of the peeled head
+ *   or tail, which costs no addition), 2 to add the lane's four sums, 6 over the wavefront; V - 1 is what any order is held to.
+ *   There is no rescaling: m is the exact maximum from a pass before.  x_i - m is one IEEE subtraction, expf and logf are
+ *   libm's (1 ulp).  tests/fill_cases.py makes its tolerance of exactly this.
+ *   out_top_id[p, k] (int32), out_top_logit[p, k] (float32, a bit copy of the input): the first k entries in the order; the
+ *   slots beyond the number of entries that are no NaN hold id -1 and logit NaN.
+ *   out_label_id[p] (int32): l = labels[pos[p]] where 0 <= l < n_vocab, else -1.  out_label_logit[p] (float32, a bit copy):
+ *   x[l], NaN for a label out of range.  out_label_rank[p] (int32): the entries that come before (x[l], l) in the order -- 0
+ *   for the argmax of the smallest index; -1 for a label out of range or one whose logit is a NaN.
+ *   info[5] (may be NULL): positions, labels of rank 0, labels of rank 0 <= r < max(k, 1), positions whose row holds a NaN,
+ *   labels out of range.  Without labels the second, third and fifth are 0.
+ *   A pos[p] >= rows * width is SWT_ERR_INVALID in the host form.  The `_dev` form gives such a position the "nothing" record --
+ *   lse NaN, ids -1, logits NaN, rank -1 -- counts it as a position and in nothing else, and reads neither logits nor labels.
+ * Log-probabilities and probabilities are top_logit - lse and its exp over n_pos * k elements: the callers make them.
+ *
+ * SWT_ERR_INVALID, swt_last_error naming the argument: NULL ids, out_pos, info (1.), logits, pos (2.); width == 0 with rows > 0;
+ * 2^32 rows or more; 2^31 columns or more; an unknown mode or flag; n_vocab == 0 or >= 2^31; k > 64; rows * width * n_vocab
+ * >= 2^62; 2^32 positions or more; top outputs with k == 0; label outputs without labels; an array that is not aligned to its
+ * element type; an output that shares a byte with another array.  Zero rows (1.) and zero positions (2.) succeed without a
+ * device, info zeroed.  The host forms check everything before anything touches the device.  The `_dev` forms take device
+ * pointers, enqueue on the stream and do not synchronise; they write every element of every output given and nothing else,
+ * whatever the inputs hold.  They keep the workgroups' counts in a workspace of the process, and 1. scans in the workspace of
+ * the plans: no two such calls at once on different streams.
+ * swt_fill_capacity: the floats of a row one step of a wavefront covers (s above), the positions of one workgroup of 2., the
+ * greatest k, and the cells of one scan group of 1. (csrc/swt_fill.hip). */
+#define SWT_FILL_EQUAL 0u
+#define SWT_FILL_NOT_EQUAL 1u
+#define SWT_FILL_IDS64 4u /* the value of SWT_BATCH_IDS64 */
+int swt_mlm_positions(const void *ids, uint64_t rows, uint32_t width, int64_t value, uint32_t mode, uint32_t flags, uint64_t *out_pos,
+                      uint64_t *info);
+int swt_mlm_positions_dev(const void *d_ids, uint64_t rows, uint32_t width, int64_t value, uint32_t mode, uint32_t flags, uint64_t *d_out_pos,
+                          uint64_t *d_info, void *stream);
+int swt_mlm_predict(const float *logits, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *pos, uint64_t n_pos, const void *labels,
+                    uint32_t flags, uint32_t k, float *out_lse, int32_t *out_top_id, float *out_top_logit, int32_t *out_label_id,
+                    float *out_label_logit, int32_t *out_label_rank, uint64_t *info);
+int swt_mlm_predict_dev(const float *d_logits, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *d_pos, uint64_t n_pos,
+                        const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id, float *d_out_top_logit,
+                        int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info, void *stream);
+int swt_fill_capacity(uint32_t *floats_per_step, uint32_t *positions_per_workgroup, uint32_t *k_max, uint32_t *scan_cells);
 #ifdef __cplusplus
 }
 #endif

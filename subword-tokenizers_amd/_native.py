@@ -197,6 +197,13 @@ SIGNATURES = {
     "swt_entity_spans": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8),
     "swt_entity_spans_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 9),
     "swt_tag_capacity": (C.c_int, [u32p, u32p, u32p]),
+    "swt_mlm_positions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "swt_mlm_positions_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
+    "swt_mlm_predict": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32] +
+                        [C.c_void_p] * 7),
+    "swt_mlm_predict_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                      C.c_uint32] + [C.c_void_p] * 8),
+    "swt_fill_capacity": (C.c_int, [u32p, u32p, u32p, u32p]),
 }
 
 
@@ -1045,6 +1052,61 @@ def entity_spans(label, score, char_start, char_end, word_off, etype, begins, in
     out["info"] = np.zeros(ENTITY_COUNTS, dtype=np.uint64) if info else None
     check(lib().swt_entity_spans(_at(label), _at(score), _at(char_start), _at(char_end), _at(word_off), int(word_off.size) - 1, n_words,
                                  _at(etype), _at(begins), int(etype.size), *[_at(out[name]) for name, _ in ENTITY_OUT], _at(out["info"])))
+    return out
+
+
+FILL_EQUAL, FILL_NOT_EQUAL, FILL_IDS64 = 0, 1, 4  # the modes of swt_mlm_positions, the flag of both calls
+POSITION_COUNTS, FILL_COUNTS = 2, 5  # the entries of info of the two calls
+FILL_OUT = (("lse", np.float32, False), ("top_id", np.int32, True), ("top_logit", np.float32, True), ("label_id", np.int32, False),
+            ("label_logit", np.float32, False), ("label_rank", np.int32, False))  # name, type, [n, k] instead of [n]
+
+
+def fill_capacity():
+    """-> (floats_per_step, positions_per_workgroup, k_max, scan_cells): the floats of a row one step of a wavefront covers, the
+    positions of one workgroup of swt_mlm_predict, the greatest k, the cells of one scan group of swt_mlm_positions
+    (csrc/swt_fill.hip)"""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_fill_capacity(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def _fill_ids(name, a):
+    if not isinstance(a, np.ndarray) or a.dtype not in (np.int32, np.int64) or a.ndim != 2 or not a.flags.c_contiguous:
+        raise TypeError("%s: a 2-D C-contiguous array of int32 or int64" % name)
+    return int(a.shape[0]), int(a.shape[1]), FILL_IDS64 if a.dtype == np.int64 else 0
+
+
+def mlm_positions(ids, value, not_equal=False):
+    """The flat indices of the cells of ids [rows, width] that equal `value` (or do not), ascending (swt_mlm_positions).
+    -> (pos uint64[rows * width], UINT64_MAX from the count on; info uint64[2]: the count, the cells looked at)"""
+    rows, width, flags = _fill_ids("ids", ids)
+    pos, info = np.zeros(rows * width, dtype=np.uint64), np.zeros(POSITION_COUNTS, dtype=np.uint64)
+    check(lib().swt_mlm_positions(_at(ids), rows, width, int(value), FILL_NOT_EQUAL if not_equal else FILL_EQUAL, flags, _at(pos), _at(info)))
+    return pos, info
+
+
+def mlm_predict(logits, pos, labels=None, k=0, lse=True, info=True):
+    """The scores of the rows logits[pos[p]] of float32 logits [rows, width, V] (swt_mlm_predict).  -> dict: lse float32[n] (or
+    None), top_id int32, top_logit float32 [n, k] (None with k == 0), label_id, label_logit, label_rank [n] (None without labels),
+    info uint64[5] (or None)"""
+    if not isinstance(logits, np.ndarray) or logits.dtype != np.float32 or logits.ndim != 3 or not logits.flags.c_contiguous:
+        raise TypeError("logits: a 3-D C-contiguous array of float32")
+    rows, width, n_vocab = (int(x) for x in logits.shape)
+    flags = 0
+    if labels is not None:
+        lr, lw, flags = _fill_ids("labels", labels)
+        if (lr, lw) != (rows, width):
+            raise ValueError("labels has the shape %s, the logits want %s" % (labels.shape, (rows, width)))
+    pos = np.ascontiguousarray(pos, dtype=np.uint64)
+    if pos.ndim != 1:
+        raise ValueError("pos: a 1-D array of flat cell indices")
+    n, k = int(pos.size), int(k)
+    wanted = {"lse": lse, "top_id": k > 0, "top_logit": k > 0, "label_id": labels is not None, "label_logit": labels is not None,
+              "label_rank": labels is not None}
+    out = {name: np.zeros((n, k) if per_k else n, dtype=t) if wanted[name] else None for name, t, per_k in FILL_OUT}
+    out["info"] = np.zeros(FILL_COUNTS, dtype=np.uint64) if info else None
+    check(lib().swt_mlm_predict(_at(logits), rows, width, n_vocab, _at(pos), n, _at(labels), flags, k,
+                                *[_at(out[name]) for name, _, _ in FILL_OUT], _at(out["info"])))
     return out
 
 

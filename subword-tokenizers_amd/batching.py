@@ -895,6 +895,112 @@ def entities(words, id2label, texts=None):
     return res
 
 
+def _fill_predict(ids, value, not_equal, logits, labels, top_k, what):
+    """What fill_mask and mlm_scores share: the cells of `ids` that equal `value` (or do not) through swt_mlm_positions, the scores
+    of their rows of logits through swt_mlm_predict -- NumPy arrays through the host forms, torch tensors on the GPU through the
+    `_dev` forms on the current device and stream, the position count and `info` the only read-backs.
+    -> (dict: row, col, lse, top_id, top_logit, logprob, score, label_id, label_logit, label_rank; info)"""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 64:
+        raise ValueError("top_k lies in 1 .. 64")
+    k = int(top_k)
+    if isinstance(ids, np.ndarray):
+        torch = None
+        ok = ids.dtype in (np.int32, np.int64) and ids.ndim == 2 and ids.flags.c_contiguous
+        logits_ok = isinstance(logits, np.ndarray) and logits.dtype == np.float32
+    else:
+        import torch
+        ok = isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype in (torch.int32, torch.int64) and ids.dim() == 2 and ids.is_contiguous()
+        logits_ok = isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32
+    if not ok:
+        raise TypeError("%s: a 2-D C-contiguous NumPy array, or torch tensor on the GPU, of int32 or int64" % what)
+    if not logits_ok:
+        raise TypeError("logits: float32, a NumPy array or a torch tensor on the GPU as %s is" % what)
+    rows, width = int(ids.shape[0]), int(ids.shape[1])
+    if len(logits.shape) != 3 or tuple(logits.shape[:2]) != (rows, width) or int(logits.shape[2]) < 1:
+        raise ValueError("logits has the shape [rows, width, V] over the rows of %s" % what)
+    if not (logits.flags.c_contiguous if torch is None else logits.is_contiguous()):
+        raise ValueError("logits is C-contiguous: a copy of it is what these calls are there to avoid")
+    if torch is None:
+        pos, plan = N.mlm_positions(ids, value, not_equal)
+        pos = pos[:int(plan[0])]
+        out = N.mlm_predict(logits, pos, labels, k)
+        info = out["info"]
+        cell = pos.astype(np.int64)
+        xp_exp = np.exp
+    else:
+        dev = ids.device
+        if logits.device != dev:
+            raise TypeError("logits: a torch tensor on the device of %s" % what)
+        ids64 = ids.dtype == torch.int64
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            d_plan, d_info = torch.empty(N.POSITION_COUNTS, dtype=torch.int64, device=dev), torch.empty(N.FILL_COUNTS, dtype=torch.int64, device=dev)
+            d_pos = torch.empty(rows * width, dtype=torch.int64, device=dev)
+            d_spare = torch.empty(2, dtype=torch.int64, device=dev)  # a tensor of no element still needs an address
+            p = lambda a: None if a is None else a.data_ptr() or d_spare.data_ptr()
+            N.check(N.lib().swt_mlm_positions_dev(p(ids), rows, width, int(value), N.FILL_NOT_EQUAL if not_equal else N.FILL_EQUAL,
+                                                  N.FILL_IDS64 if ids64 else 0, p(d_pos), d_plan.data_ptr(), stream))
+            n = int(d_plan.cpu().numpy()[0])  # the one read-back before the scores: how many positions there are
+            types = {np.float32: torch.float32, np.int32: torch.int32}
+            wanted = [name for name, _, _ in N.FILL_OUT if labels is not None or not name.startswith("label")]
+            out = {name: torch.empty((n, k) if per_k else n, dtype=types[t], device=dev) if name in wanted else None
+                   for name, t, per_k in N.FILL_OUT}
+            N.check(N.lib().swt_mlm_predict_dev(p(logits), rows, width, int(logits.shape[2]), p(d_pos), n, p(labels),
+                                                N.FILL_IDS64 if ids64 else 0, k, *[p(out[name]) for name, _, _ in N.FILL_OUT],
+                                                d_info.data_ptr(), stream))
+            info = d_info.cpu().numpy()
+            cell = d_pos[:n]
+            xp_exp = torch.exp
+    out["row"], out["col"] = cell // width, cell % width
+    out["logprob"] = out["top_logit"] - out["lse"][:, None]
+    out["score"] = xp_exp(out["logprob"])
+    return out, info
+
+
+def _kept_sum(keep, x):
+    """the sum of x where keep holds, as a 0-d tensor: what is not kept, a NaN included, adds nothing"""
+    return x.where(keep, x.new_zeros(())).sum()
+
+
+def _fill_top(out):
+    return {"token_ids": out["top_id"], "logit": out["top_logit"], "logprob": out["logprob"], "score": out["score"], "lse": out["lse"]}
+
+
+def fill_mask(tok, input_ids, logits, top_k=5, tokens=False):
+    """SubwordTokenizer.fill_mask: the columns with input_ids == mask_id()."""
+    voc = tok._batch_vocabulary()
+    out, info = _fill_predict(input_ids, voc.mask_id, False, logits, None, top_k, "input_ids")
+    res = {"row": out["row"], "col": out["col"]}
+    res.update(_fill_top(out))
+    res["n_positions"] = int(info[0])
+    if tokens:
+        ids = out["top_id"] if isinstance(out["top_id"], np.ndarray) else out["top_id"].cpu().numpy()
+        names = list(voc.tokens) + ([MASK] if voc.mask_id == len(voc.tokens) else [])
+        res["tokens"] = [[names[i] if 0 <= i < len(names) else None for i in row] for row in ids.tolist()]
+    return res
+
+
+def mlm_scores(logits, labels, top_k=1):
+    """SubwordTokenizer.mlm_scores: the columns with labels != -100."""
+    out, info = _fill_predict(labels, N.LABEL_IGNORE, True, logits, labels, top_k, "labels")
+    res = {"row": out["row"], "col": out["col"], "label": out["label_id"], "label_logprob": out["label_logit"] - out["lse"],
+           "label_rank": out["label_rank"]}
+    res.update(_fill_top(out))
+    n, n_in = int(info[0]), int(info[0]) - int(info[4])
+    lp, known = res["label_logprob"], out["label_id"] >= 0  # a masked sum: no gather, and on the device no read-back
+    if isinstance(lp, np.ndarray):
+        loss = float(np.where(known, -lp.astype(np.float64), 0.0).sum() / n_in) if n_in else float("nan")
+        perplexity = float(np.exp(loss))
+    else:
+        neg = -lp.double()
+        loss = _kept_sum(known, neg) / n_in if n_in else neg.new_full((), float("nan"))
+        perplexity = loss.exp()
+    res.update({"loss": loss, "perplexity": perplexity, "accuracy": int(info[1]) / n if n else float("nan"),
+                "accuracy_at_k": int(info[2]) / n if n else float("nan"), "n_positions": n, "n_correct": int(info[1]),
+                "n_correct_at_k": int(info[2]), "n_nan": int(info[3]), "n_out_of_range": int(info[4])})
+    return res
+
+
 def _raise_decode_status(status, row):
     """the ValueError of a plan whose info counts reported rows: the first such row and its cause"""
     causes = [text for bit, text in ((N.DECODE_BAD_ID, "an id outside the vocabulary on a kept column"),

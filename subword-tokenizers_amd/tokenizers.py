@@ -228,6 +228,32 @@ class SubwordTokenizer:
         "n_entity_words", and with texts (one string per text) "text": texts[i].lower()[char_start:char_end], sliced on the host."""
         return batching.entities(words, id2label, texts)
 
+    # -- masked-LM inference (not in the reference; batching.py, DESIGN.md 4.16)
+    def fill_mask(self, input_ids, logits, top_k: int = 5, tokens: bool = False) -> dict:
+        """The top_k best tokens of every [MASK] column -- input_ids == mask_id() -- from a masked-LM's logits ([rows, width, V],
+        float32), on the device (swt_mlm_positions, swt_mlm_predict), which reads the logits of those columns and of no other
+        and makes no copy of them.  The order: the greater logit, then the smaller id; a NaN logit is no candidate.
+        input_ids: a 2-D C-contiguous int32 or int64 NumPy array, or such a torch tensor on the GPU, and C-contiguous logits of
+        the same kind (then everything stays on the device and the current stream; the number of columns and the counts are
+        read back); logits that are not float32 or not of that kind raise TypeError; a shape other than [rows, width, V],
+        logits that are not contiguous or a top_k outside 1 .. 64 ValueError.
+        -> per [MASK] column, in row-major order, {"row", "col", "token_ids" [n, top_k] (-1 where the row has fewer entries
+        that are no NaN), "logit", "logprob" (logit - the row's log-sum-exp), "score" (exp(logprob)), "lse"}, "n_positions",
+        and with tokens=True "tokens": per column a list of vocab_list() strings made on the host, "[MASK]" for mask_id() past
+        the list's end and None for -1."""
+        return batching.fill_mask(self, input_ids, logits, top_k, tokens)
+
+    def mlm_scores(self, logits, labels, top_k: int = 1) -> dict:
+        """A masked-LM's logits ([rows, width, V], float32) scored against `labels` of encode_batch(..., mlm=...) or mask_tokens
+        at the columns with labels != -100, on the device (swt_mlm_positions, swt_mlm_predict).  Kinds, TypeError and
+        ValueError as fill_mask.
+        -> per such column {"row", "col", "label" (-1 for a label outside [0, V)), "label_logprob", "label_rank" (the entries
+        that come before the label's: 0 for the argmax; -1 for a label out of range or with a NaN logit), "lse", and the top_k
+        as fill_mask gives them}; "loss": the mean of -label_logprob over the labels in range, "perplexity" = exp(loss),
+        "accuracy" and "accuracy_at_k" over all columns, "n_positions", "n_correct", "n_correct_at_k", "n_nan" (columns whose
+        logits hold a NaN), "n_out_of_range"."""
+        return batching.mlm_scores(logits, labels, top_k)
+
     def decode_batch_bytes(self, input_ids, attention_mask=None, skip_special_tokens: bool = True):
         """Rows of dense ids (any "input_ids" of encode_batch or mask_tokens, a model's output) back to text on the device
         (swt_decode_plan / swt_decode_rows), as the reference's recover_sentence (utils.py:141-154) spells the rows' tokens: '##'
