@@ -282,6 +282,41 @@ int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_by
                             uint64_t *d_n_tokens, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MaxMatch-Dropout (Hiraoka, COLING 2022; not in the reference): swt_wp_encode_naive with a vocabulary match of the
+ * longest-match search thrown away with a given probability, so that the search falls back to a shorter piece and the same text
+ * comes out in another segmentation per (seed, epoch).  Arguments, ids, statuses, capacities (out_cap >= n_bytes) and refusals
+ * (SWT_ERR_UNSUPPORTED for a '###x' vocabulary included) as swt_wp_encode_naive / _dev, plus the draw, exactly as
+ * swt_bpe_encode_dropout carries it: drop_below in [0, 2^32] (from a probability p, round(p * 2^32); above 2^32:
+ * SWT_ERR_INVALID), a 64-bit seed and a 32-bit epoch.  No floating point on the device.
+ *
+ * The split is swt_wp_encode_naive's.  A word is walked as NaiveWP.encode_word walks it (source/wordpiece.py:131-158): the state
+ * is the string "#" * L + word[p:], L = 0 at the word's start.  In one step
+ *     the candidates are the prefixes of the state that are vocabulary tokens;
+ *     a candidate TAKES c code points when it reaches c code points beyond the L leading '#' (c = 0: it ends inside them);
+ *     a candidate with c >= 2 is dropped iff x[c & 3] < drop_below, x = Philox4x32-10 (the function and constants of
+ *       swt_mlm_mask) of the counter (c >> 2, a, i, epoch), all mod 2^32, under the key (seed & 0xFFFFFFFF, seed >> 32), where
+ *       i = the index of the sentence in this call's sent_off and a = the byte offset from sent_off[i] of the word byte the state
+ *       starts at (p), in the text the call is given (for Python's entry points pack_and_lower(texts));
+ *     candidates with c <= 1 are never dropped;
+ *     the step takes the longest candidate that is not dropped; when there is none the whole word is one "[UNK]" and the pieces
+ *       stored so far are discarded (wordpiece.py:148-149); everything else is the plain walk.
+ * So: a draw depends on (seed, epoch, i, a, c) and on nothing else -- not on L, the step, tiles, chunks, the route of the call or
+ * the other sentences; one Philox call serves four consecutive c.  drop_below = 0 is swt_wp_encode_naive on any vocabulary;
+ * drop_below = 2^32 leaves every word as its code points wherever each is a token in its position.  At a fixed p the step is the
+ * plain step over a vocabulary with some tokens removed, never a '#'-only one, so the bound of sharp_depth + 2 steps at one p
+ * still decides SWT_WP_NONTERMINATING -- and a sentence's status is that of the thinned walk, so IT CAN DEPEND ON THE DRAW: under
+ * {"a", "##", "##bc"} the word "abc" is a ##bc when "##bc" survives and never returns when it is dropped (the plain step at
+ * "##bc" then takes "##" for ever); under {"a", "##bc"} it is "[UNK]" instead.  The paper's rule to our reading, except that a
+ * single code point is never dropped here, so that p = 1 gives the characters.  There is no joined form: a is
+ * an offset in the text the call is given.  One lane per word (csrc/swt_wp.hip, naive_word with a WpDraw). */
+int swt_wp_encode_naive_dropout(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                                uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens,
+                                uint64_t drop_below, uint64_t seed, uint32_t epoch);
+int swt_wp_encode_naive_dropout_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                                    uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status,
+                                    uint64_t *d_n_tokens, uint64_t drop_below, uint64_t seed, uint32_t epoch, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's
  * zipf_distribution (source/benchmarks.py:240-253), over ids -- a '##' token and the same token without the prefix are
  * different strings and different ids.  counts has 2 * id_cap entries: counts[id & 0x7FFFFFFF] for ids without SWT_BPE_CONT,

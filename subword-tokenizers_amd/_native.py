@@ -97,6 +97,10 @@ SIGNATURES = {
     "swt_wp_encode_naive_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, u8p]),
     "swt_wp_encode_naive_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_wp_encode_naive_dropout": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, C.c_uint64, C.c_uint64,
+                                              C.c_uint32]),
+    "swt_wp_encode_naive_dropout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -1315,6 +1319,14 @@ class WpTrie:
 
     def encode_naive_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_naive_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
+
+    # MaxMatch-Dropout (swt_wp_encode_naive_dropout, include/swt.h): draw = (drop_below in [0, 2^32], seed, epoch)
+    def encode_naive_dropout(self, text_u8, sent_off, draw):
+        return _encode_host("swt_wp_encode_naive_dropout", self._h, text_u8, sent_off, status=True, draw=list(draw))
+
+    def encode_naive_dropout_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, draw, stream=0):
+        check(lib().swt_wp_encode_naive_dropout_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, *draw,
+                                                    stream))
 
 
 class BpeTrainer:

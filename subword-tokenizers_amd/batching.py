@@ -236,7 +236,7 @@ def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_t
                  truncation="longest_first", return_token_type_ids=None, return_special_tokens_mask=False, packing=None, drop_last=False,
                  mlm=None, dropout=None):
     if dropout is not None:
-        tok._enc.draw(dropout)  # refused before anything is encoded: a class without BPE-dropout, arguments that give no draw
+        tok._enc.draw(dropout)  # refused before anything is encoded: a class without that dropout, arguments that give no draw
     if mlm is None:
         return _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                              return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
@@ -464,24 +464,34 @@ def _encode_device(tok, voc, texts, n_rows, max_length, stride, padding, multipl
     return out
 
 
-def dropout_draw(dropout):
-    """A `dropout` argument of the encode calls -> None, or (drop_below, seed, epoch) of swt_bpe_encode_dropout: drop_below =
-    round(probability * 2^32), seed and epoch 0 unless given.  TypeError for what is neither None nor a dict, ValueError for a
-    probability that is missing, a NaN or outside [0, 1], an unknown key, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
+class MaxMatch:
+    """A `maxmatch_dropout` argument on its way through the calls below: they carry one `dropout` value from the public call to the
+    encoder record (tokenizers._Encoder.draw), a dict for BPE-dropout as it was given, or this around the dict of MaxMatch-Dropout."""
+    __slots__ = ("spec",)
+
+    def __init__(self, spec):
+        self.spec = spec
+
+
+def dropout_draw(dropout, name="dropout"):
+    """A `dropout` (or, by `name`, `maxmatch_dropout`) argument of the encode calls -> None, or (drop_below, seed, epoch) of
+    swt_bpe_encode_dropout / swt_wp_encode_naive_dropout: drop_below = round(probability * 2^32), seed and epoch 0 unless given.
+    TypeError for what is neither None nor a dict, ValueError for a probability that is missing, a NaN or outside [0, 1], an
+    unknown key, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
     if dropout is None:
         return None
     if not isinstance(dropout, dict):
-        raise TypeError("dropout is None or a dict of 'probability', 'seed' and 'epoch'")
+        raise TypeError(name + " is None or a dict of 'probability', 'seed' and 'epoch'")
     unknown = set(dropout) - {"probability", "seed", "epoch"}
     if unknown or "probability" not in dropout:
-        raise ValueError("dropout takes 'probability' and, if wanted, 'seed' and 'epoch'")
+        raise ValueError(name + " takes 'probability' and, if wanted, 'seed' and 'epoch'")
     p, seed, epoch = float(dropout["probability"]), int(dropout.get("seed", 0)), int(dropout.get("epoch", 0))
     if not 0.0 <= p <= 1.0:  # (false for a NaN)
-        raise ValueError("dropout: probability lies in [0, 1]")
+        raise ValueError(name + ": probability lies in [0, 1]")
     if not 0 <= seed < 1 << 64:
-        raise ValueError("dropout: seed lies in [0, 2^64)")
+        raise ValueError(name + ": seed lies in [0, 2^64)")
     if not 0 <= epoch < 1 << 32:
-        raise ValueError("dropout: epoch lies in [0, 2^32)")
+        raise ValueError(name + ": epoch lies in [0, 2^32)")
     return int(round(p * 4294967296.0)), seed, epoch
 
 

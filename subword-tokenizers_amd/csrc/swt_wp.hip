@@ -12,9 +12,11 @@
 //   pops   token ids of every failure_pops list, concatenated
 // Node ids: 0 = root, 1 = root_p (detached, childless), 2.. in creation order; root_sharp is the node of "##".
 #include <cstring>
+#include <type_traits>
 #include <unordered_map>
 
 #include "swt_dedup.h"
+#include "swt_philox.h"
 #include "swt_tile.h"
 #include "swt_words.h"
 
@@ -386,7 +388,8 @@ __device__ __forceinline__ bool wp_mark(WpTileLds &L, const WpTile &tile, WpChun
   return true;
 }
 
-// One sentence longer than the LDS chunk: lane 0 walks it in global memory (walk(b, e, out, status) -> token count).  The empty
+// One sentence longer than the LDS chunk: lane 0 walks it in global memory (walk(b, e, out, status, s) -> token count; s: the
+// sentence's index in sent_off).  The empty
 // sentences that also start at cb come first and get no tokens and `empty_status`.  True: the tile ends with it.
 template <class Walk>
 __device__ __forceinline__ bool wp_giant(WpTileLds &L, WpTile &tile, const uint64_t *__restrict__ sent_off, const WpOut &out,
@@ -396,7 +399,7 @@ __device__ __forceinline__ bool wp_giant(WpTileLds &L, WpTile &tile, const uint6
     while (s + 1 < tile.s_hi && sent_off[s + 1] <= tile.cb) s++;  // the last sentence that starts at cb
     int stt;
     const uint64_t e = sent_off[s + 1];
-    const uint32_t n = walk(tile.cb, e, tile.tile_out + tile.run, stt);
+    const uint32_t n = walk(tile.cb, e, tile.tile_out + tile.run, stt, s);
     for (uint64_t z = tile.s_next; z <= s; z++) {
       out.off(z, tile.run);
       out.status[z] = (uint8_t)empty_status;
@@ -581,7 +584,7 @@ __global__ __launch_bounds__(64) void wp_encode_kernel(
     }
     __syncthreads();
     if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t) {
         if constexpr (Lds::spans) {
           WpSpanSink sink{sa.tab, tile_sp + 2 * (o - tile.tile_out), tile_wd + (o - tile.tile_out), nullptr, 0, b, 0, 0, true};
           return wp_sentence(TxtSrc{text, nullptr, cls_tab}, b, e, o, T, stt, sink);
@@ -866,9 +869,46 @@ struct WpNaiveDev {
   uint32_t max_steps;  // sharp_depth + 2
 };
 
+// ---- MaxMatch-Dropout (include/swt.h, swt_wp_encode_naive_dropout): the same walk with a vocabulary match
+// thrown away when its draw says so.  A candidate that takes c >= 2 code points of the word from byte a of sentence i is dropped
+// when word c & 3 of Philox at the counter (c >> 2, a, i, epoch) is below drop_below: one call serves four consecutive c.  The
+// candidates of one step come in rising c, so the last call's four words are all that is kept.
+// Termination: the draws at one p are functions of (a, c) alone, the same in every step there, so the steps at a fixed p are the
+// plain steps over a vocabulary with some tokens removed -- never a '#'-only one (c = 0), never a single code point (c = 1).  The
+// bound above speaks of the '#' chain of the trie alone, which is whole: more than sharp_depth + 2 steps at one p still mean that
+// the (thinned) reference walk never returns.  And a word that terminates still makes no step inside the leading '#' (such a step
+// from L = 2 comes back to L = 2 at the same p or never below it), so its tokens are at most its code points: room is not passed.
+struct WpDrawArgs {  // what a dropout launch draws with: arguments of the dropout kernel, and of no other
+  unsigned long long drop_below;  // 0 .. 2^32
+  uint32_t key0, key1, epoch;
+};
+struct WpNoDraw {
+  static constexpr bool on = false;
+};
+struct WpDraw {
+  static constexpr bool on = true;
+  const WpDrawArgs &d;
+  const uint32_t i, a0;  // the word's sentence in the call's sent_off; the byte offset of the word in that sentence (both mod 2^32)
+  uint32_t group = 0xFFFFFFFFu, at = 0;  // c >> 2 and a of the call `x` holds (c counts code points of a text: no group is all ones)
+  Philox x{};
+  __device__ __forceinline__ WpDraw(const WpDrawArgs &args, uint32_t sent, uint32_t word_at) : d(args), i(sent), a0(word_at) {}
+  __device__ __forceinline__ bool dropped(uint32_t a, uint32_t c) {
+    if ((c >> 2) != group || a != at) {
+      group = c >> 2;
+      at = a;
+      x = philox4x32_10(group, a, i, d.epoch, d.key0, d.key1);
+    }
+    const uint32_t q = c & 3u;
+    const uint32_t v = q == 0u ? x.x[0] : q == 1u ? x.x[1] : q == 2u ? x.x[2] : x.x[3];
+    return v < d.drop_below;
+  }
+};
+
 // One word [wb, we) of txt: its ids to out[0..room), the count returned.  nonterm = true: the reference never returns (count 0).
+// draw: WpNoDraw, the plain walk and not an instruction more, or the word's WpDraw.
+template <class Draw>
 __device__ uint32_t naive_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpNaiveDev &N, uint32_t *out, uint32_t room,
-                               bool &nonterm) {
+                               bool &nonterm, Draw &draw) {
   uint32_t nt = 0, L = 0, steps = 0;
   uint64_t p = wb;
   for (;;) {
@@ -876,6 +916,7 @@ __device__ uint32_t naive_word(const uint8_t *txt, uint64_t wb, uint64_t we, con
     int32_t best = -1;
     uint64_t best_end = p;
     uint32_t k = 0;
+    [[maybe_unused]] uint32_t taken = 0;  // code points of the word that the candidate at hand takes (c of the rule)
     for (; k < L; k++) {
       const int32_t c = edge_lookup(N.T, node, '#');
       if (c < 0) break;
@@ -899,6 +940,10 @@ __device__ uint32_t naive_word(const uint8_t *txt, uint64_t wb, uint64_t we, con
         if (c < 0) break;
         node = (uint32_t)c;
         const int32_t v = N.tok[node];
+        if constexpr (Draw::on) {
+          taken++;
+          if (v >= 0 && taken >= 2 && draw.dropped(draw.a0 + (uint32_t)(p - wb), taken)) continue;
+        }
         if (v >= 0) { best = v; best_sh = L; best_end = q; }
       }
     }
@@ -926,9 +971,14 @@ __device__ __forceinline__ uint8_t bert_class(const uint8_t *cls_tab, uint32_t c
 }
 
 // A whole sentence [b, e) by one lane (sentences longer than a chunk): split as SubwordTokenizer._split, each word's tokens
-// within that word's bytes of out.  Returns the count (0 when status != OK).
+// within that word's bytes of out.  Returns the count (0 when status != OK).  Dropout: the sentence is number i of the call, and
+// its words draw by their offsets from b -- the key the tiled walk gives the same word.
+template <bool Dropout>
+using WpDrawOf = std::conditional_t<Dropout, WpDrawArgs, WpNoDraw>;
+template <bool Dropout>
 __device__ uint32_t naive_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
-                                   const WpNaiveDev &N, int &status) {
+                                   const WpNaiveDev &N, int &status, [[maybe_unused]] const WpDrawOf<Dropout> &args,
+                                   [[maybe_unused]] uint64_t i) {
   TxtSrc src{txt, nullptr, cls_tab};
   uint32_t nt = 0;
   status = SWT_WP_OK;
@@ -947,7 +997,13 @@ __device__ uint32_t naive_sentence(const uint8_t *txt, const uint8_t *cls_tab, u
       }
     }
     bool nonterm = false;
-    nt += naive_word(txt, p, q, N, out + nt, (uint32_t)(q - p), nonterm);
+    if constexpr (Dropout) {
+      WpDraw draw(args, (uint32_t)i, (uint32_t)(p - b));
+      nt += naive_word(txt, p, q, N, out + nt, (uint32_t)(q - p), nonterm, draw);
+    } else {
+      WpNoDraw none;
+      nt += naive_word(txt, p, q, N, out + nt, (uint32_t)(q - p), nonterm, none);
+    }
     if (nonterm) { status = SWT_WP_NONTERMINATING; return 0; }
     p = q;
   }
@@ -966,10 +1022,20 @@ struct alignas(16) WpNaiveLds : WpTileLds {
 //   C  one lane per word runs the MaxMatch walk, writing its ids into the word's own bytes of tok[] (a terminating word of n
 //      bytes has at most n tokens: swt_wp_encode_naive_dev refuses the vocabularies for which that does not hold)
 //   D  a sentence with a word that never returns gets status SWT_WP_NONTERMINATING and no tokens
+// Two instantiations: wp_naive_kernel<false>, the plain walk with the arguments, resources and instructions it always had, and
+// wp_naive_kernel<true>, MaxMatch-Dropout (swt_wp_encode_naive_dropout*): the draws travel behind the DirectOut in the last
+// argument, and in C every lane looks up the key of its word -- a = its offset from wp_sentence_start, i = the last sentence of
+// sent_off[s_next .. s_hi) that starts at or before it (empty sentences share their offset with the next one that has bytes, and
+// that one it is).  The one-lane walk in global memory has both at hand and draws by the same key.
+struct WpDirectDrop : DirectOut { WpDrawArgs draw; };
+template <bool Dropout>
 __global__ __launch_bounds__(64) void wp_naive_kernel(
     const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
     const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpNaiveDev N, uint32_t *__restrict__ scratch,
-    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status,
+    std::conditional_t<Dropout, WpDirectDrop, DirectOut> direct) {
+  WpDrawOf<Dropout> draw_args{};
+  if constexpr (Dropout) draw_args = direct.draw;
   __shared__ WpNaiveLds L;
   const int lane = threadIdx.x;
   const unsigned long long lt = (1ull << lane) - 1ull;
@@ -983,7 +1049,9 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
     if (lane <= kWpBlocks) L.nonterm[lane] = 0ull;
     __syncthreads();
     if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt) { return naive_sentence(text, cls_tab, b, e, o, N, stt); };
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t s) {
+        return naive_sentence<Dropout>(text, cls_tab, b, e, o, N, stt, draw_args, s);
+      };
       if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
       continue;
     }
@@ -1030,7 +1098,20 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
         if (we > ch.ce) we = ch.ce;
       }
       bool nt_word = false;
-      naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word);
+      if constexpr (Dropout) {
+        const uint32_t s0 = wp_sentence_start(L, ch, p0);
+        const uint64_t g = ch.abase + p0;
+        uint64_t lo = tile.s_next, hi = tile.s_hi;  // sent_off[lo] <= g (the chunk begins at a sentence start) < sent_off[hi]
+        while (hi - lo > 1) {
+          const uint64_t mid = lo + ((hi - lo) >> 1);
+          if (sent_off[mid] <= g) lo = mid; else hi = mid;
+        }
+        WpDraw draw(draw_args, (uint32_t)lo, p0 - s0);
+        naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word, draw);
+      } else {
+        WpNoDraw none;
+        naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word, none);
+      }
       if (nt_word) {
         const uint32_t s0 = wp_sentence_start(L, ch, p0);
         atomicOr(&L.nonterm[s0 >> 6], 1ull << (s0 & 63));
@@ -1321,8 +1402,12 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
   return SWT_OK;
 } SWT_API_CATCH
 
-int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
-                            uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
+}  // extern "C"
+
+// swt_wp_encode_naive_dev, and with `draw` swt_wp_encode_naive_dropout_dev: the same routes with the dropout instantiation
+static int wp_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                        uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, const WpDrawArgs *draw,
+                        void *stream) {
   if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_sent && !d_status) || (n_bytes && (!d_text || !d_out_ids)))
     return fail(SWT_ERR_INVALID, "null argument");
   if (t->H.naive_excess)
@@ -1349,25 +1434,51 @@ int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_by
   N.tok = t->d_tok;
   N.unk_id = t->H.n_vocab + 1;
   N.max_steps = t->H.sharp_depth + 2;
+  const auto launch = [&](unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
+    if (draw)
+      hipLaunchKernelGGL(wp_naive_kernel<true>, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, N, ids,
+                         t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, WpDirectDrop{direct, *draw});
+    else
+      hipLaunchKernelGGL(wp_naive_kernel<false>, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, N, ids,
+                         t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, direct);
+  };
   if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents) {
     // one workgroup, one launch, the caller's arrays written by the kernel (DirectOut, swt_tile.h)
-    hipLaunchKernelGGL(wp_naive_kernel, dim3(1), dim3(64), 0, st, d_text, n_bytes, d_sent_off, (const uint64_t *)nullptr, d_cls, N,
-                       d_out_ids, t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status,
-                       DirectOut{d_out_off, d_n_tokens, n_sent});
+    launch(1, nullptr, d_out_ids, DirectOut{d_out_off, d_n_tokens, n_sent});
     SWT_HIP(hipGetLastError());
     return SWT_OK;
   }
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  hipLaunchKernelGGL(wp_naive_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                     t->ws.plan.as<uint64_t>(), d_cls, N, t->ws.scratch.as<uint32_t>(), t->ws.sent_local.as<uint32_t>(),
-                     t->ws.tile_tok.as<uint32_t>(), d_status, DirectOut{nullptr, nullptr, 0});
+  launch((unsigned)n_tiles, t->ws.plan.as<uint64_t>(), t->ws.scratch.as<uint32_t>(), DirectOut{nullptr, nullptr, 0});
   prof_end(st);
   launch_scan_gather(d_sent_off, n_sent, n_tiles, t->ws, d_out_ids, d_out_off, d_n_tokens, st);
   prof_end(st, 2);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
+}
+
+// the draw of a dropout call from its three arguments
+static int wp_draw_args(uint64_t drop_below, uint64_t seed, uint32_t epoch, WpDrawArgs &d) {
+  if (drop_below > (1ull << 32)) return fail(SWT_ERR_INVALID, "drop_below lies in [0, 2^32] (round(p * 2^32))");
+  d = WpDrawArgs{drop_below, (uint32_t)seed, (uint32_t)(seed >> 32), epoch};
+  return SWT_OK;
+}
+
+extern "C" {
+
+int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                            uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
+  return wp_naive_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_status, d_n_tokens, nullptr, stream);
+} SWT_API_CATCH
+
+int swt_wp_encode_naive_dropout_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                                    uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint64_t drop_below,
+                                    uint64_t seed, uint32_t epoch, void *stream) try {
+  WpDrawArgs d;
+  if (int rc = wp_draw_args(drop_below, seed, epoch, d)) return rc;
+  return wp_naive_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_status, d_n_tokens, &d, stream);
 } SWT_API_CATCH
 
 // FastWP with token spans: swt_wp_encode_dev's direct and tiled paths with the span instantiation of the kernel, the spans and
@@ -1474,6 +1585,22 @@ int swt_wp_encode_spans(swt_wp_trie *t, const uint8_t *text, const uint64_t *sen
 int swt_wp_encode_naive(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
                         uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
   return wp_encode_host(swt_wp_encode_naive_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+} SWT_API_CATCH
+
+// MaxMatch-Dropout, host buffers: the one host-call layer with the dropout `_dev` form behind it.  No joined form: a draw goes by
+// a byte offset in the text the call is given.
+int swt_wp_encode_naive_dropout(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                                uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint64_t drop_below,
+                                uint64_t seed, uint32_t epoch) try {
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  WpDrawArgs d;
+  if (int rc = wp_draw_args(drop_below, seed, epoch, d)) return rc;
+  HostEncoder enc = wp_host(t, swt_wp_encode_naive_dev);
+  enc.dev = [t, d](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n, uint32_t *d_ids, uint64_t *d_out_off,
+                   uint8_t *d_status, uint64_t *d_n_tokens) {
+    return wp_naive_dev(t, d_text, n_bytes, d_off, n, d_ids, d_out_off, d_status, d_n_tokens, &d, nullptr);
+  };
+  return host_encode(t->stage, enc, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
 } SWT_API_CATCH
 
 // list[str] joined with U+0000 -> ids, the prepared text staying on the device (see swt_bpe_encode_joined).

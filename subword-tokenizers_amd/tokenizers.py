@@ -99,7 +99,7 @@ class SubwordTokenizer:
                      text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
                      return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False,
                      packing: Optional[str] = None, drop_last: bool = False, mlm: Optional[dict] = None,
-                     dropout: Optional[dict] = None) -> dict:
+                     dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
@@ -129,10 +129,13 @@ class SubwordTokenizer:
 
         dropout = {"probability": p, "seed": 0, "epoch": 0} (FastBPE; any other class raises ValueError) encodes with BPE-dropout,
         as FastBPE.encode_ids_batch: every form above -- pairs, windows, offsets, packing, mlm, device -- then works on those ids.
-        The sentence index of the draws is the text's index, and len(texts) + j for text_pairs[j]."""
+        The sentence index of the draws is the text's index, and len(texts) + j for text_pairs[j].
+
+        maxmatch_dropout, a dict of the same three keys (NaiveWP; any other class raises ValueError), encodes with MaxMatch-Dropout
+        as NaiveWP.encode_ids_batch does, with the same reach and the same sentence indices."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                                     return_special_tokens_mask, packing, drop_last, mlm, dropout)
+                                     return_special_tokens_mask, packing, drop_last, mlm, self._enc.channel(dropout, maxmatch_dropout))
 
     def mask_id(self) -> int:
         """The dense id of "[MASK]": its index where the vocabulary holds the string, else len(vocab_list()), one past the end,
@@ -289,7 +292,7 @@ class SubwordTokenizer:
         return self._enc.vocabulary()
 
     def _batch_encode_ids(self, texts, dropout=None):
-        return self.encode_ids_batch(texts) if dropout is None else self.encode_ids_batch(texts, dropout=dropout)
+        return self.encode_ids_batch(texts) if dropout is None else _encode_ids(self._enc, texts, dropout)
 
     def _batch_encode_spans(self, texts, dropout=None):
         return self.encode_spans_batch(texts) if dropout is None else _encode_spans(self._enc, texts, dropout)
@@ -352,16 +355,21 @@ class _Encoder:
     a _SymbolTable (BPE) or the token list (WordPiece); naive: the `encode_naive*` entries instead of `encode*`; complain:
     what raises for a sentence's status (WordPiece; None: BPE, which has no statuses); corner: an id past "[UNK]" stands for
     the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE);
-    dropout: the handle has the `encode_dropout*` entries, a third set beside the two (FastBPE)."""
+    dropout: the handle has the `encode_dropout*` entries, a third set beside the two (FastBPE); maxmatch: that third set is
+    `encode_naive_dropout*`, MaxMatch-Dropout (NaiveWP).  Either way the set is reached through drop_host / drop_dev, and the
+    argument travels through one channel: a `dropout=` dict as it is, a `maxmatch_dropout=` dict inside a batching.MaxMatch."""
 
     def __init__(self, tok, ensure, spelling, naive, error="Text to tokenize must be a string.", complain=None, corner=False,
-                 first=False, dropout=False):
+                 first=False, dropout=False, maxmatch=False):
         self._tok, self._ensure, self._spelling = weakref.proxy(tok), ensure, spelling  # (no cycle: a tokenizer dies with its last name)
         self.host = "encode_naive" if naive else "encode"  # the three call forms on the handle, by name
         self.joined, self.dev = self.host + "_joined", self.host + "_dev"
         # BPE-dropout: a host and a `_dev` form, no joined one -- a word's draws go by its byte offset in pack_and_lower's text,
         # so every dropout call takes the long way
         self.drop_host, self.drop_dev = ("encode_dropout", "encode_dropout_dev") if dropout else (None, None)
+        if maxmatch:  # MaxMatch-Dropout: the same two forms, for the same reason
+            self.drop_host, self.drop_dev = self.host + "_dropout", self.host + "_dropout_dev"
+        self.bpe_dropout, self.maxmatch = bool(dropout), bool(maxmatch)
         self.error, self.complain, self.corner, self.first = error, complain, corner, first
         self.flagged = complain is None  # BPE ids carry SWT_BPE_CONT over SYM_BASE + k; WordPiece ids index the token list
         self.len_base = N.SYM_BASE if self.flagged else 0
@@ -379,9 +387,22 @@ class _Encoder:
         encoder that has none, and for arguments that give no draw (batching.dropout_draw)"""
         if dropout is None:
             return None
-        if self.drop_host is None:
+        if isinstance(dropout, batching.MaxMatch):
+            if not self.maxmatch:
+                raise ValueError("maxmatch_dropout: only NaiveWP drops matches (MaxMatch-Dropout); this tokenizer takes "
+                                 "maxmatch_dropout=None")
+            return batching.dropout_draw(dropout.spec, "maxmatch_dropout")
+        if not self.bpe_dropout:
             raise ValueError("dropout: only FastBPE drops merges (BPE-dropout); this tokenizer takes dropout=None")
         return batching.dropout_draw(dropout)
+
+    def channel(self, dropout, maxmatch_dropout):
+        """the two keywords of the public calls -> what travels on as `dropout`.  Both given: whichever this class does not have
+        raises, and no class has both."""
+        if maxmatch_dropout is None:
+            return dropout
+        self.draw(dropout)
+        return batching.MaxMatch(maxmatch_dropout)
 
     def names(self) -> List[str]:
         """WordPiece: the token of every id below the corner's"""
@@ -493,13 +514,17 @@ def _encode_dev(enc: _Encoder, d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off,
     import torch
     draw = enc.draw(dropout)
     call, checks = getattr(enc.handle(), enc.dev), []
-    if draw is not None:
-        getattr(enc.handle(), enc.drop_dev)(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, draw, 0, stream)
-    elif enc.complain is None:
-        call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
+    if enc.complain is None:
+        if draw is not None:
+            getattr(enc.handle(), enc.drop_dev)(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, draw, 0, stream)
+        else:
+            call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_ntok, 0, stream)
     else:
         d_status = empty(n_sent + 8, torch.uint8)
-        call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
+        if draw is not None:
+            getattr(enc.handle(), enc.drop_dev)(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, draw, stream)
+        else:
+            call(d_text, n_bytes, d_off, n_sent, d_ids, d_tok_off, d_status.data_ptr(), d_ntok, stream)
         checks.append((d_status, lambda st, i, text: enc.complain(st, text)))
     if d_spans is not None:
         lengths = enc.lengths()
@@ -686,17 +711,20 @@ class NaiveBPE(SubwordTokenizer):
             self._naive_table, self._naive_syms, self._naive_merges = N.BpeTable(left, right, merged), syms, merges
         return self._naive_table
 
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None,
+                         maxmatch_dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
-        over this object's own symbol table (decode_ids spells them).  dropout: None; anything else is FastBPE's (ValueError)."""
-        return _encode_ids(self._enc, texts, dropout)
+        over this object's own symbol table (decode_ids spells them).  dropout: None; anything else is FastBPE's (ValueError).
+        maxmatch_dropout: None; anything else is NaiveWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
     def decode_ids(self, ids) -> List[str]:
         return _bpe_tokens(self._enc, ids)
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
+                       maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts]"""
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout))
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout))
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
     def _span_parts(self):
@@ -794,7 +822,8 @@ class FastBPE(NaiveBPE):
         return _bpe_tokens(self._enc, ids)
 
     # -- batch entry points (not in the reference); FastBPE's own, like the reference's methods of the same class
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None,
+                         maxmatch_dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]); ids as defined in include/swt.h.
 
         dropout = {"probability": p, "seed": 0, "epoch": 0}: BPE-dropout (Provilkov et al. 2020) on the device
@@ -802,11 +831,12 @@ class FastBPE(NaiveBPE):
         with probability p, so a text gets another segmentation per (seed, epoch) -- and the same one for the same (seed, epoch,
         index in `texts`), whatever the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain
         encode, p = 1 leaves every word as its characters.  ValueError: a probability outside [0, 1] or a NaN, a seed outside
-        [0, 2^64), an epoch outside [0, 2^32), an unknown key."""
-        return _encode_ids(self._enc, texts, dropout)
+        [0, 2^64), an epoch outside [0, 2^32), an unknown key.  maxmatch_dropout: None; anything else is NaiveWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout))
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
+                       maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout))
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -818,10 +848,10 @@ class FastBPE(NaiveBPE):
         return self.decode_ids(ids)
 
     # -- bpe.py:245-249
-    def tokenize(self, text: str, dropout: Optional[dict] = None) -> List[str]:
+    def tokenize(self, text: str, dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[str]:
         if not isinstance(text, str):
             raise TypeError("Text must be a string.")
-        return self.tokenize_batch([text], dropout)[0]
+        return self.tokenize_batch([text], dropout, maxmatch_dropout)[0]
 
     # -- bpe.py:251-263
     def load_resources(self, path: str) -> None:
@@ -874,7 +904,8 @@ class NaiveWP(SubwordTokenizer):
         self._naive_tokens: List[str] = []
         self._naive_vocab: Optional[frozenset] = None  # the vocabulary the handle was built from
         # (FastWP puts its own in `_enc`; the methods it inherits that answer with NaiveWP's tokens keep to `_naive_enc`)
-        self._enc = self._naive_enc = _Encoder(self, "_ensure_naive_trie", "_naive_tokens", naive=True, complain=self._raise_naive_status)
+        self._enc = self._naive_enc = _Encoder(self, "_ensure_naive_trie", "_naive_tokens", naive=True, complain=self._raise_naive_status,
+                                                   maxmatch=True)
 
     # -- wordpiece.py:29-103: the merge loop, on the device
     def train(self, corpus, max_vocab: int = 30_000):
@@ -973,9 +1004,12 @@ class NaiveWP(SubwordTokenizer):
         return pieces
 
     # -- wordpiece.py:161-181
-    def tokenize(self, text):
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
+        """maxmatch_dropout: as encode_ids_batch, on the device, `text` being sentence 0; None: the reference's walk, here"""
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
+        if maxmatch_dropout is not None:
+            return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
         out = []
         for w, _ in self.preprocessing([text])[0]:
             out.extend(self.encode_word(w))
@@ -996,16 +1030,24 @@ class NaiveWP(SubwordTokenizer):
             self._naive_trie = N.WpTrie(self._naive_tokens)
         return self._naive_trie
 
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None):
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]): tokenize() of every text on the device.  ids index
         sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns.
-        dropout: None; anything else is FastBPE's (ValueError)."""
-        return _encode_ids(self._enc, texts, dropout)
+        dropout: None; anything else is FastBPE's (ValueError).
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
+        maxmatch_dropout = {"probability": p, "seed": 0, "epoch": 0}: MaxMatch-Dropout (Hiraoka 2022) on the device
+        (swt_wp_encode_naive_dropout, where the rule stands in full).  In the longest-match search a vocabulary match of two or
+        more characters of the word is thrown away with probability p, so the search falls back to a shorter piece and a text
+        gets another segmentation per (seed, epoch) -- and the same one for the same (seed, epoch, index in `texts`), whatever
+        the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain encode, p = 1 leaves every word
+        as its characters where each is a token in its position.  A word whose every match is dropped or missing is "[UNK]", and
+        the status of a text is that of the thinned walk: over an odd vocabulary it can depend on the draw.  Errors as dropout's."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
+
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
         deviation: the reference hangs)."""
-        ids, off, status = self.encode_ids_batch(texts, dropout)
+        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout)
         _raise_flagged(self._enc, status, texts)
         return N.nested_lists(self._enc.names(), ids, off)
 
@@ -1173,13 +1215,14 @@ class FastWP(NaiveWP):
         self._build_trie()
 
     # -- batch entry points (not in the reference)
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None):
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status.
-        dropout: None; anything else is FastBPE's (ValueError)."""
-        return _encode_ids(self._enc, texts, dropout)
+        dropout: None; anything else is FastBPE's (ValueError).  maxmatch_dropout: None; anything else is NaiveWP's (ValueError:
+        this class walks failure links, not MaxMatch -- a NaiveWP over the same vocabulary gives this class's ids)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None) -> List[List[str]]:
-        ids, off, status = self.encode_ids_batch(texts, dropout)
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
+        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout)
         _raise_flagged(self._enc, status, texts)
         if ids.size and int(ids.max()) <= len(self._tokens) + 1:  # no multi-token corner: one table, references handed out
             if ids.size < 4096:
@@ -1240,10 +1283,10 @@ class FastWP(NaiveWP):
             raise IndexError("string index out of range")  # wordpiece.py:285 with i == len(seq)
 
     # -- wordpiece.py:233-270
-    def tokenize(self, text):
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
-        return self.tokenize_batch([text])[0]
+        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
 
     # -- wordpiece.py:318-330
     def load_resources(self, path: str) -> None:
