@@ -71,7 +71,7 @@ constexpr uint64_t kDirectBytes = 1024, kDirectSents = 64;  // up to here one wo
 // slot h2, so a lookup is two independent 16-byte loads and two compares -- no probe loop, and a wave never goes round
 // again because one of its lanes met a collision.  The hashes are 24-bit multiplies (full-rate v_mul_u32_u24; symbol ids
 // are below 2^24 for any table under five million merges, larger ids only hash worse) with one xor-shift between them.
-// (BpeHash, kHash1, kHash2, bpe_hash: swt_bpe_narrow.h, which the table of 16-bit codes shares them with.)
+// (BpeHash, kHash1, kHash2, bpe_hash: swt_bpe_narrow.h, beside narrow_hash, the hash pair of the table of 16-bit codes.)
 static_assert(kNarrowSymBase == SWT_SYM_BASE, "swt_bpe_narrow.h numbers the merged symbols from SWT_SYM_BASE");
 static_assert((kNarrowCont << 16) == SWT_BPE_CONT, "the emit moves the continuation bit of a code to that of an id");
 
@@ -94,10 +94,21 @@ __device__ __forceinline__ uint32_t slot_value(const BpeSlot *__restrict__ slots
   const uint32_t b = (r2.x == r && r2.y == l) ? r2.z : kNoRank;
   return a & b;
 }
+// Pointers the kernel reads out of a record in memory (NarrowDir) are generic to the compiler, and a load through one is a flat
+// load: it counts against the LDS counter too and cannot take a scalar base.  They all point into device-global memory.
+template <class T>
+using GlobalPtr = const __attribute__((address_space(1))) T *;
+template <class T>
+__device__ __forceinline__ GlobalPtr<T> global_ptr(const T *p) { return (GlobalPtr<T>)p; }
 // The same over the table of 16-bit codes (swt_bpe_narrow.h): two 8-byte loads, one compare each.  l and r without kNarrowCont.
+// Both slots come from one multiply chain (narrow_hash), and a slot's address is the table's base -- a scalar -- and a 32-bit
+// byte offset (a table has at most 2^28 slots), so no 64-bit add is made per slot.
 __device__ __forceinline__ uint32_t slot_value(const NarrowSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r) {
-  const uint2 r1 = *reinterpret_cast<const uint2 *>(&slots[bpe_hash(l, r, sh, kHash1)]);
-  const uint2 r2 = *reinterpret_cast<const uint2 *>(&slots[bpe_hash(l, r, sh, kHash2)]);
+  const NarrowHash h = narrow_hash(l, r, sh);
+  const GlobalPtr<char> base = global_ptr(reinterpret_cast<const char *>(slots));
+  typedef uint32_t Pair __attribute__((ext_vector_type(2)));  // {key, value}: one 8-byte load
+  const Pair r1 = *reinterpret_cast<GlobalPtr<Pair>>(base + (h.h1 << 3));
+  const Pair r2 = *reinterpret_cast<GlobalPtr<Pair>>(base + (h.h2 << 3));
   const uint32_t key = narrow_key(l, r);
   const uint32_t a = r1.x == key ? r1.y : kNoRank;
   const uint32_t b = r2.x == key ? r2.y : kNoRank;
@@ -121,7 +132,7 @@ __device__ __forceinline__ uint32_t slot_key(uint32_t v, uint32_t slot) { return
 // launch and 1.6 % of the step in registers spilled around the rounds (profiles/lane_keys.txt section 6)
 template <bool Seq>
 __device__ __forceinline__ uint32_t narrow_merged(const NarrowDir &D, uint32_t rank) {
-  if constexpr (Seq) return D.letters + rank; else return D.code_of_rank[rank];
+  if constexpr (Seq) return D.letters + rank; else return global_ptr(D.code_of_rank)[rank];
 }
 
 // FastBPE.encode_word on a symbol array (bpe.py:210-238), serial form for the one-lane fallback: repeat { lowest-rank
@@ -400,6 +411,16 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Lane masks without a detour through a vector register.  lane_ballot: the mask of a predicate straight from the compare that
+// makes it (__ballot turns the bool into an int and compares that again: a v_cndmask and a v_cmp_ne per mask).  lane_bit: this
+// lane's bit of a mask that is the same in every lane, as a predicate (the mask itself serves as the condition; (m >> lane) & 1
+// is two 64-bit vector operations and a compare).  lanes_below: base + the set bits of such a mask below this lane (v_mbcnt).
+__device__ __forceinline__ unsigned long long lane_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool lane_bit(unsigned long long uniform_mask) { return __builtin_amdgcn_inverse_ballot_w64(uniform_mask); }
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long uniform_mask, uint32_t base) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(uniform_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)uniform_mask, base));
+}
+
 constexpr uint32_t kDirtyVal = 0xFFFFFFFEu;  // above every table value (ranks stay below 2^32 - 2), below kNoRank
 
 // bpe.py:210-238 on one word whose symbols S[0..n) and pair values V[0..n) (V[n-1] = kNoRank) live in LDS: every round merges
@@ -536,7 +557,6 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
                                            int lane) {
   constexpr int Blocks = Cap / 64;
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont;
-  const unsigned long long lt = (1ull << lane) - 1ull;  // lanes below me
   const unsigned long long le = (2ull << lane) - 1ull;  // me and below
   const uint64_t abase = T.cb & ~15ull;
   const uint32_t off0 = (uint32_t)(T.cb - abase);
@@ -563,18 +583,31 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
   }
   wave_sync();
 
-  // ---- B/C.  Scalars carried from block to block:
+  // ---- B/C.  Scalars carried from block to block (the two flags as integers: a bool that lives across the loop is kept as a
+  // lane mask, and every use of it in scalar logic went through a v_cndmask and a v_readfirstlane):
   uint32_t nsym = 0, nw = 0;  // symbols and words so far
-  bool prev_wb = true;        // the byte before this block belongs to a whitespace/punctuation char (or chunk start)
-  bool pend_open = false;     // the last symbol of the previous block may have its successor in this one
+  unsigned long long prev_wb = 1ull;  // 1: the byte before this block belongs to a whitespace/punctuation char (or chunk start)
+  uint32_t pend_shut = 1u;    // 0: the last symbol of the previous block may have its successor in this one
   uint32_t pend_cp = 0;
-  uint32_t wbase = 0;         // Narrow: the symbol at which the word that is open at the block boundary began
   int cut = -1;               // last word boundary (for a span longer than the chunk)
+  // Every mask of a block comes from ONE vector compare, taken where the compare stands (lane_ballot; a predicate that first
+  // crosses a branch is made into a register and compared again), and is combined with the others as a scalar.  With
+  // d = p - off0: off0 <= p < staged is d < n_in (off0 < staged), and off0 < p && p + 4 <= staged is d - 1 < n_cut.
+  const uint32_t n_in = staged - off0, n_cut = max(n_in, 4u) - 4u;
+  // The class of a lane is tested where it lies: Narrow, bits 16 and 17 of the code_of_cp entry; a lane outside the chunk, which
+  // behaves as whitespace, holds kClsOut there.  The masks are scalars (no class table: nothing in the chunk has a class).
+  constexpr uint32_t kClsAt = Narrow ? 16u : 0u, kClsOut = 4u << kClsAt;
+  const uint32_t ws_bits = Narrow ? ((cls_tab ? kClsWs << kClsAt : 0u) | kClsOut) : kClsWs;
+  const uint32_t pn_bits = Narrow ? (cls_tab ? kClsPunct << kClsAt : 0u) : kClsPunct;
   for (uint32_t blk = 0; blk < nblk; blk++) {
     const uint32_t p = blk * 64 + lane;
-    const bool inr = p >= off0 && p < staged;
+    const uint32_t d = p - off0;
+    const bool inr = d < n_in;
+    const unsigned long long INR = lane_ballot(inr);
+    const unsigned long long CUTR = lane_ballot(d - 1u < n_cut);
     const uint8_t b = inr ? L.txt[p] : (uint8_t)' ';
     const bool lead = !utf8_is_cont(b);
+    const unsigned long long LEAD = lane_ballot(lead);
     uint32_t cp = b;
     if (b >= 0xC0) {
       int len = utf8_len(b);
@@ -584,63 +617,72 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
         for (int i = 1; i < len; i++) cp = (cp << 6) | (L.txt[p + i] & 0x3F);
       }
     }
-    uint32_t c = kClsWs;  // bytes outside the chunk behave as whitespace
+    uint32_t c = Narrow ? kClsOut : kClsWs;  // bytes outside the chunk behave as whitespace
     uint32_t sy = cp;     // the symbol: the code point, or (Narrow) its code
     if constexpr (Narrow) {
       sy = kNarrowForeign;
       if (inr && lead) {
         if (cp < D.n_cps) {
-          const uint32_t e = D.code_of_cp[cp];
-          sy = e & 0xFFFFu;
-          c = cls_tab ? (e >> 16) : 0u;
+          c = global_ptr(D.code_of_cp)[cp];  // (the code below the class: no test reads it)
+          sy = c & 0xFFFFu;
         } else {
-          c = (cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u;
+          c = (cls_tab && cp < kNumCodePoints) ? (uint32_t)(cls_tab[cp] & 3u) << kClsAt : 0u;
           // an ill-formed sequence that decodes past U+10FFFF reads as the symbol id it equals, as it does in the wide kernel
           if (cp >= SWT_SYM_BASE && cp - SWT_SYM_BASE + D.letters < kNarrowMaxCodes) sy = cp - SWT_SYM_BASE + D.letters;
         }
       }
     } else if (inr && lead)
       c = cp < 1024u ? ((cls2[cp >> 4] >> ((cp & 15u) << 1)) & 3u) : ((cls_tab && cp < kNumCodePoints) ? (cls_tab[cp] & 3u) : 0u);
-    const unsigned long long INR = __ballot(inr);
-    const unsigned long long LEAD = __ballot(lead);
-    const unsigned long long WSm = __ballot(lead && (c & kClsWs));
-    const unsigned long long PNm = __ballot(lead && (c & kClsPunct));
+    const unsigned long long WSm = lane_ballot((c & ws_bits) != 0u) & LEAD;
+    const unsigned long long PNm = lane_ballot((c & pn_bits) != 0u) & LEAD;
     const unsigned long long CONT = ~LEAD;
-    unsigned long long WB = WSm | PNm | ((prev_wb && (CONT & 1ull)) ? 1ull : 0ull);
+    unsigned long long WB = WSm | PNm | (prev_wb & CONT);  // (prev_wb is bit 0 alone)
     WB |= (WB << 1) & CONT;
     WB |= (WB << 1) & CONT;
     WB |= (WB << 1) & CONT;
     const unsigned long long SS = L.sbits[blk];
     const unsigned long long first_bit = blk == 0 ? (1ull << off0) : 0ull;  // off0 < 16
-    const unsigned long long before = (WB << 1) | (prev_wb ? 1ull : 0ull) | SS | first_bit;
+    const unsigned long long before = (WB << 1) | prev_wb | SS | first_bit;
     const unsigned long long SYM = LEAD & ~WSm & INR;
     const unsigned long long WSTART = SYM & (PNm | before);
     {
-      const unsigned long long CUT = LEAD & (WSm | PNm | SS) & __ballot(inr && p > off0 && p + 4 <= staged);
+      const unsigned long long CUT = LEAD & (WSm | PNm | SS) & CUTR;
       if (CUT) cut = (int)(blk * 64 + 63 - __builtin_clzll(CUT));
     }
-    const bool is_sym = (SYM >> lane) & 1ull;
-    const bool wstart = (WSTART >> lane) & 1ull;
+    const bool is_sym = lane_bit(SYM);
+    const bool wstart = lane_bit(WSTART);
     const unsigned long long after = SYM & ~le;
     const uint32_t q = after ? (uint32_t)__builtin_ctzll(after) : 64u;
-    const bool hasnext = is_sym && q < 64 && !((WSTART >> (q & 63)) & 1ull);
+    // HASNEXT: the symbols whose next symbol in the block continues their word, as a scalar.  In bit-reversed order the next
+    // symbol of a lane lies BELOW it: a one added above every continuing symbol to the mask of the non-symbol lanes carries up
+    // through them and sets exactly the symbol it belongs to (a symbol lane is a zero there and takes at most that one carry).
+    const unsigned long long rsym = __builtin_bitreverse64(SYM);
+    const unsigned long long HASNEXT = __builtin_bitreverse64((~rsym + (__builtin_bitreverse64(SYM & ~WSTART) << 1)) & rsym);
+    const bool hasnext = lane_bit(HASNEXT);
     const uint32_t f = SYM ? (uint32_t)__builtin_ctzll(SYM) : 64u;
-    const bool joins = pend_open && f < 64 && !((WSTART >> (f & 63)) & 1ull);
-    const uint32_t si = nsym + (uint32_t)__popcll(SYM & lt);
+    const bool joins = pend_shut == 0u && f < 64 && !((WSTART >> (f & 63)) & 1ull);
+    const uint32_t si = lanes_below(SYM, nsym);
     const uint32_t cpn = __shfl(sy, (int)(q & 63));
     // lane 63 never has a successor inside the block: it probes the pair that straddles the block boundary (Narrow: not behind a
     // FOREIGN symbol, whose entry is taken)
-    const bool jp = joins && lane == 63 && !(Narrow && pend_cp == kNarrowForeign);
+    const unsigned long long JP = (joins && !(Narrow && pend_cp == kNarrowForeign)) ? 1ull << 63 : 0ull;
+    const bool jp = lane_bit(JP);
     const uint32_t cpf = __builtin_amdgcn_readlane(sy, (int)(f & 63));
-    const bool want = hasnext || jp;
+    const bool want = lane_bit(HASNEXT | JP);
+    if (wstart) L.wl[lanes_below(WSTART, nw)] = (uint16_t)si;
     uint32_t v = kNoRank;
-    if (want) v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn);
     if constexpr (Narrow) {
-      // the value goes in as the key of its slot (slot_key): the symbol's place in its word, counted from the word start at or
-      // below this lane -- whose lane knows its symbol index -- or, when the block has none down there, from wbase
-      const unsigned long long ws = WSTART & le;
-      const uint32_t first = __shfl(si, ws ? 63 - __builtin_clzll(ws) : 0);
-      v = slot_key(v, jp ? nsym - 1u - wbase : si - (ws ? first : wbase));
+      // the value goes in as the key of its slot (slot_key): the symbol's place in its word, counted from the word's first
+      // symbol, which the word list holds by now -- this block's word starts were written just above, and a lane's word is
+      // the last that starts at or below it (the straddling pair's: the last of the blocks before).  A symbol that has a
+      // successor has a word: the first symbol of a chunk starts one.
+      wave_sync();
+      if (want) {
+        const uint32_t first = L.wl[jp ? nw - 1u : lanes_below(WSTART >> 1, nw - 1u + (uint32_t)(WSTART & 1ull))];
+        v = slot_key(slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn), (jp ? nsym - 1u : si) - first);
+      }
+    } else if (want) {
+      v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn);
     }
     if (is_sym) {
       L.sym[si] = wstart ? sy : (sy | kCont);
@@ -649,21 +691,20 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
     if (want) L.val[jp ? nsym - 1 : si] = v;
     if constexpr (Narrow) {
       if (is_sym && sy == kNarrowForeign) L.val[si] = kNarrowNoPair | (cp & kNarrowCpMask);
-      if (WSTART) wbase = nsym + (uint32_t)__popcll(SYM & ((1ull << (63 - __builtin_clzll(WSTART))) - 1ull));
     }
-    if (wstart) L.wl[nw + (uint32_t)__popcll(WSTART & lt)] = (uint16_t)si;
     if (lane == 0) { L.symmask[blk] = SYM; L.sympre[blk] = nsym; }
     nw += (uint32_t)__popcll(WSTART);
     nsym += (uint32_t)__popcll(SYM);
     if (SYM) {
       const int li = 63 - __builtin_clzll(SYM);
       const unsigned long long tail = li == 63 ? 0ull : ~((2ull << li) - 1ull);
-      pend_open = ((WSm | PNm | SS) & tail) == 0ull && !((PNm >> li) & 1ull);
+      const unsigned long long shut = ((WSm | PNm | SS) & tail) | (PNm & (1ull << li));
+      pend_shut = (uint32_t)shut | (uint32_t)(shut >> 32);
       pend_cp = __builtin_amdgcn_readlane(sy, li);
     } else {
-      pend_open = false;  // a block without symbols holds whitespace: every word ended
+      pend_shut = 1u;  // a block without symbols holds whitespace: every word ended
     }
-    prev_wb = (WB >> 63) & 1ull;
+    prev_wb = WB >> 63;
   }
   wave_sync();
   C.abase = abase;
@@ -1031,7 +1072,7 @@ __device__ __forceinline__ void lane_emit(LaneLds<Cap, Narrow> &L, const NarrowD
     if constexpr (Narrow) {
       const uint32_t c = sv & ~kNarrowCont;  // (a dead slot's code is neither a letter nor FOREIGN: it reads nothing)
       id = c + (SWT_SYM_BASE - D.letters);
-      if (c < D.letters) id = D.cp_of_code[c];
+      if (c < D.letters) id = global_ptr(D.cp_of_code)[c];
       if (c == kNarrowForeign) id = L.val[j] & kNarrowCpMask;
       id |= (sv & kNarrowCont) << 16;
     }
@@ -1122,6 +1163,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     LaneChunk C;
     lane_split(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
     // (the one-lane walker of a word longer than a chunk works on ids, whatever the kernel's symbols are)
+    // (Narrow: their table comes out of the directory as a generic pointer and stays one: the walker's three loads of a slot are
+    // the kernel's only flat loads, and marking the table global cost the kernel 0.5 M vector instructions a launch in registers
+    // moved about, profiles/lane_diet.txt section 4)
     lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, Narrow ? D.wide_slots : slots, Narrow ? D.wide_sh : sh, merged_of_rank, T, C,
                                                lane, sent_local, uslot, rec, drec, direct, draw);
     if (C.giant) continue;
@@ -1309,7 +1353,8 @@ extern "C" {
 // and more (the library's choice), 2 all (SWT_OPT_LANE_NARROW = 2), 8: eligible for it (packed and letters + merges <= 0x7FFD),
 // 9: letters of its alphabet (0 when not eligible), 11: the kernel the LAST running-text launch of this handle took, written where
 // the launch picks it -- 1 the narrow kernel, 0 a wide one, -1 no such launch yet, 12: the narrow kernel's rounds get the merged
-// code as letters + rank (1: NarrowTable::sequential, the Seq kernels) or read it from code_of_rank (0; also when not eligible)
+// code as letters + rank (1: NarrowTable::sequential, the Seq kernels) or read it from code_of_rank (0; also when not eligible),
+// 13: log2 of the slots of the table of the codes (0 when not eligible)
 int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   if (!t) return -1;
   if (which == 7) return !t->narrow.eligible || t->opt_lane_narrow == 1 ? 0 : t->opt_lane_narrow == 2 ? 2 : 1;
@@ -1317,6 +1362,7 @@ int swt_debug_bpe_table_info(const swt_bpe_table *t, int which) try {
   if (which == 9) return (int)t->narrow.letters();
   if (which == 11) return t->last_lane_narrow;
   if (which == 12) return t->narrow.eligible && t->narrow.sequential ? 1 : 0;
+  if (which == 13) return (int)t->narrow.bits;
   if (which == 0) return (int)t->bits;
   if (which == 1) return t->packed ? 1 : 0;
   if (which == 2) return t->proper ? 1 : 0;

@@ -8,8 +8,9 @@
 //   0x7FFE      FOREIGN: a code point outside the alphabet.  No pair holds it, so it never merges
 //   0x7FFF      a consumed slot
 //   bit 15      SWT_BPE_CONT
-// The rank table of the codes is the same two-choice cuckoo table as the one of the ids (bpe_hash, two slots a pair), keyed on
-// l << 16 | r, exact in 32 bits: a slot is {key, value} in 8 bytes, value = rank << 16 | code of the merged symbol.
+// The rank table of the codes is a two-choice cuckoo table as the one of the ids is (two slots a pair), keyed on l << 16 | r, exact
+// in 32 bits: a slot is {key, value} in 8 bytes, value = rank << 16 | code of the merged symbol.  Its two hashes are its own
+// (narrow_hash): they share their first stage, which 15-bit codes allow and the ids of the wide table (bpe_hash) do not.
 //
 // The kernel's val[] entry of a pair is the round's KEY, rank << 16 | the slot's index in its word (slot_key, swt_bpe_encode.hip):
 // only the rank half of a table value gets there, and a round learns the merged code from the rank.  Where the list's live merge i
@@ -33,7 +34,7 @@
 
 namespace swt {
 
-// The hashes of both rank tables: 24-bit multiplies (full-rate v_mul_u32_u24; symbol ids are below 2^24 for any table under five
+// The hashes of the rank table of the IDS (and of NaiveBPE's table of first positions): 24-bit multiplies (full-rate v_mul_u32_u24; symbol ids are below 2^24 for any table under five
 // million merges, larger ids only hash worse) with one xor-shift between them.
 struct BpeHash { uint32_t a, b, c; };
 constexpr BpeHash kHash1{0x9E3779u, 0x85EBCBu, 0xC2B2AFu}, kHash2{0x27D4EBu, 0x165667u, 0x9E3779u};
@@ -54,6 +55,17 @@ constexpr uint32_t kNarrowMinCps = 1024;  // code_of_cp covers at least the code
 
 struct NarrowSlot { uint32_t key, value; };
 SWT_NARROW_HD uint32_t narrow_key(uint32_t l, uint32_t r) { return (l << 16) | r; }
+
+// The two slots of a pair of CODES.  One multiply chain serves both: x = l * A + r * B (a v_mul_u32_u24 and a v_mad_u32_u24),
+// the first slot is the top of x, the second the top of x's low 24 bits times C -- five vector instructions where two calls of
+// bpe_hash take ten.  Codes are below 2^15 and differ in few bits, so the top bits of one odd multiply spread them as well as
+// bpe_hash's xor-shift did: the pretrained lists settle in tables of the same size (tests/test_narrow_hash.py).  sh = 32 - log2(slots).
+struct NarrowHash { uint32_t h1, h2; };
+constexpr uint32_t kNarrowHashA = 0x9E3779u, kNarrowHashB = 0x85EBCBu, kNarrowHashC = 0xC2B2AFu;
+SWT_NARROW_HD NarrowHash narrow_hash(uint32_t l, uint32_t r, uint32_t sh) {
+  const uint32_t x = (l & 0xFFFFFFu) * kNarrowHashA + (r & 0xFFFFFFu) * kNarrowHashB;
+  return NarrowHash{x >> sh, ((x & 0xFFFFFFu) * kNarrowHashC) >> sh};
+}
 
 // Every eligible table runs the narrow kernel with keys in val[].  `sequential` only says how a round gets the merged code from
 // the rank: letters + rank, or (a list that spells a merged string before the merge producing it, or twice) code_of_rank[rank],
@@ -84,12 +96,13 @@ struct NarrowTable {
   // the value of the pair of CODES (l, r) as a device lookup finds it, all ones when the table has no such pair
   uint32_t find(uint32_t l, uint32_t r) const {
     const uint32_t sh = 32u - bits, key = narrow_key(l, r);
-    const NarrowSlot &a = slots[bpe_hash(l, r, sh, kHash1)], &b = slots[bpe_hash(l, r, sh, kHash2)];
+    const NarrowHash h = narrow_hash(l, r, sh);
+    const NarrowSlot &a = slots[h.h1], &b = slots[h.h2];
     return (a.key == key ? a.value : 0xFFFFFFFFu) & (b.key == key ? b.value : 0xFFFFFFFFu);
   }
 };
 
-// Two-choice cuckoo placement, as place_slots (swt_bpe_encode.hip) does it for the ids: first slot, second slot, else evict (but
+// Two-choice cuckoo placement over narrow_hash, as place_slots (swt_bpe_encode.hip) does it for the ids: first slot, second slot, else evict (but
 // not from the slot the entry was just evicted from); a table that does not settle gets twice the slots.
 inline bool narrow_place(const std::vector<NarrowSlot> &entries, std::vector<NarrowSlot> &slots, uint32_t &bits_out) {
   uint32_t bits = 4;
@@ -106,7 +119,8 @@ inline bool narrow_place(const std::vector<NarrowSlot> &entries, std::vector<Nar
       ok = false;
       for (int kick = 0; kick < 2000; kick++) {
         const uint32_t l = cur.key >> 16, r = cur.key & 0xFFFFu;
-        const uint32_t h1 = bpe_hash(l, r, sh, kHash1), h2 = bpe_hash(l, r, sh, kHash2);
+        const NarrowHash h = narrow_hash(l, r, sh);
+        const uint32_t h1 = h.h1, h2 = h.h2;
         if (slots[h1].key == kNarrowEmptyKey) { slots[h1] = cur; ok = true; break; }
         if (slots[h2].key == kNarrowEmptyKey) { slots[h2] = cur; ok = true; break; }
         const uint32_t j = h1 == avoid ? h2 : h1;
