@@ -19,9 +19,14 @@
 // /root/reference/source/bpe.py:114-134: the merges applied in LIST order (bpe.py:126-127 over _replace_pair, bpe.py:25-48), which
 // differs from FastBPE's lowest-rank-first on lists that repeat a pair or rank a pair below a merge producing one of its symbols.
 // Only such lists take it (any trained list is order-equivalent and runs the FastBPE kernels as they are), so it is written for
-// correctness, not speed: ONE LANE PER WORD through ordered_word(), no one-occurrence rounds, no four-lane tail.  On S85k-open it
-// costs 0.418 ms per call against FastBPE's 0.153 (2.7 x), 2 % more than the FastBPE kernel on the same improper table
-// (slow_word): DESIGN.md section 4.2d.
+// correctness, not speed: ONE LANE PER WORD through the literal rounds, no one-occurrence rounds, no four-lane tail.  On S85k-open
+// it costs 0.418 ms per call against FastBPE's 0.153 (2.7 x), 2 % more than the FastBPE kernel on the same improper table, which
+// takes the same rounds: DESIGN.md section 4.2d.
+//
+// The literal form of a merge round -- the best adjacent pair, its occurrences merged left to right, the word compacted -- is
+// written twice, once per storage: literal_rounds() for a word in LDS with its cached pair values, walker_rounds() for one lane
+// over global memory (a word longer than a chunk).  Both run under a MERGE RULE (RankRule, ListRule, DropRule, below), which says
+// what FastBPE's rank order, NaiveBPE's list order and BPE-dropout do differently in a round.
 #include <cstring>
 #include <type_traits>
 #include <unordered_map>
@@ -135,126 +140,132 @@ __device__ __forceinline__ uint32_t narrow_merged(const NarrowDir &D, uint32_t r
   if constexpr (Seq) return D.letters + rank; else return global_ptr(D.code_of_rank)[rank];
 }
 
-// FastBPE.encode_word on a symbol array (bpe.py:210-238), serial form for the one-lane fallback: repeat { lowest-rank
-// adjacent pair; replace all of its occurrences left to right, non-overlapping }.  Returns the new length.
-__device__ uint32_t merge_word(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh) {
-  while (n >= 2) {
-    uint32_t best = 0xFFFFFFFFu, bm = 0, bl = 0, br = 0;
-    uint32_t a = s[0];
-    for (uint32_t i = 0; i + 1 < n; i++) {
-      const uint32_t b = s[i + 1];
-      uint32_t rk, mg;
-      if (slot_lookup(slots, sh, a, b, rk, mg) && rk < best) { best = rk; bm = mg; bl = a; br = b; }
-      a = b;
-    }
-    if (best == 0xFFFFFFFFu) break;
-    uint32_t j = 0, i = 0;
-    while (i < n) {
-      const uint32_t x = s[i];
-      if (i + 1 < n && x == bl && s[i + 1] == br) { s[j++] = bm; i += 2; }
-      else { s[j++] = x; i++; }
-    }
-    n = j;
+// ---- The MERGE RULES.  The literal form of a round (literal_rounds, walker_rounds) is one loop; a rule answers what the three
+// orders do differently in it:
+//   value(v)    the table value of a pair -> the value a round compares (kNoRank: the pair does not merge);
+//   takes(k)    whether the pair at slot k of the round's sequence takes part in this round.  Asked only of a pair that beats the
+//               minimum so far, and in the merge of an occurrence of the winning pair;
+//   next(rank)  the round that merged the pair of `rank` is over: what the next round starts from;
+//   begin()     a round begins: what takes() keeps within a round starts empty (a draw does not outlive its round; kept across
+//               rounds in the rule, the four draws and their group cost the dropout form 1.5 % of its time);
+//   lookup()    the walker's probe of a pair: its value(), and the merged symbol where the slot holds the round's.
+// kChain: a value may stand for a later list position than the table's, so the merged symbol is the position's (info[2 * rank]).
+// A rule is the rule of ONE word.  What travels from the kernel to the word routines makes it: of(L, where) for the word whose
+// first symbol is symbol `where` of the chunk in L, of(s, pos) for the word at byte `pos` of the text, in sentence s.
+
+template <bool Packed>
+__device__ __forceinline__ uint32_t value_rank(uint32_t v) { return Packed ? (v >> 16) : v; }  // the rank (list position) half of a table value
+
+// FastBPE's rank order (bpe.py:210-238): lowest rank first.  Every answer is a constant: its rounds test nothing and draw nothing.
+struct RankRule {
+  static constexpr bool kChain = false;
+  __device__ __forceinline__ uint32_t value(uint32_t v) const { return v; }
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ bool takes(uint32_t) const { return true; }
+  __device__ __forceinline__ void next(uint32_t) {}
+  // the walker's probe of a pair: its value and, from the slot, its merged symbol; false when the pair does not merge
+  __device__ __forceinline__ bool lookup(const BpeSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r, uint32_t &v, uint32_t &mg) const {
+    return slot_lookup(slots, sh, l, r, v, mg);
   }
-  return n;
-}
+  template <class Lds>
+  __device__ __forceinline__ RankRule of(const Lds &, uint32_t) const { return *this; }  // every word's rule: in a chunk,
+  __device__ __forceinline__ RankRule of(uint64_t, uint64_t) const { return *this; }     // and at a byte of the text
+};
 
-// ---- NaiveBPE's list order (bpe.py:126-127) as a RISING FLOOR f: a round takes the smallest list position >= f over the
-// word's adjacent pairs, merges all occurrences of that pair left to right (bpe.py:25-48) and sets f = position + 1.  That is the
-// literal loop: the merges below f have been applied or found nothing to apply to, and no position between f and the minimum
-// has an occurrence in the word.  A pair listed several times has several positions; the ordered table (swt_bpe_table::h_oslots)
-// holds the FIRST, and info[2 * i + 1] chains position i to the next position of the same pair (kNoRank at the end);
-// info[2 * i] is the merged symbol of position i.
-// v = the table value of a pair -> the value of its first position >= floor, kNoRank when there is none.
+// NaiveBPE's list order (bpe.py:126-127) as a RISING FLOOR: a round takes the smallest list position >= floor over the word's
+// adjacent pairs, merges all occurrences of that pair left to right (bpe.py:25-48) and sets floor = position + 1.  That is the
+// literal loop: the merges below the floor have been applied or found nothing to apply to, and no position between the floor and
+// the minimum has an occurrence in the word.  A pair listed several times has several positions; the ordered table
+// (swt_bpe_table::h_oslots) holds the FIRST, and info[2 * i + 1] chains position i to the next position of the same pair (kNoRank
+// at the end); info[2 * i] is the merged symbol of position i.
 template <bool Packed>
-__device__ __forceinline__ uint32_t ordered_value(uint32_t v, uint32_t floor, const uint32_t *__restrict__ info) {
-  if (v == kNoRank) return v;
-  uint32_t r = Packed ? (v >> 16) : v;
-  if (r >= floor) return v;
-  do r = info[2 * r + 1]; while (r != kNoRank && r < floor);
-  if (r == kNoRank) return kNoRank;
-  return Packed ? ((r << 16) | (info[2 * r] - SWT_SYM_BASE)) : r;
-}
-
-// NaiveBPE.encode_word on a symbol array (bpe.py:124-127), serial form for the one-lane fallback.  Returns the new length.
-template <bool Packed>
-__device__ uint32_t merge_word_ordered(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                       const uint32_t *__restrict__ info) {
+struct ListRule {
+  static constexpr bool kChain = true;
+  const uint32_t *__restrict__ info;
   uint32_t floor = 0;
-  while (n >= 2) {
-    uint32_t best = kNoRank, bl = 0, br = 0;
-    uint32_t a = s[0];
-    for (uint32_t i = 0; i + 1 < n; i++) {
-      const uint32_t b = s[i + 1];
-      const uint32_t v = ordered_value<Packed>(slot_value(slots, sh, a, b), floor, info);
-      if (v < best) { best = v; bl = a; br = b; }
-      a = b;
-    }
-    if (best == kNoRank) break;
-    const uint32_t rank = Packed ? (best >> 16) : best;
-    const uint32_t bm = info[2 * rank];
-    uint32_t j = 0, i = 0;
-    while (i < n) {
-      const uint32_t x = s[i];
-      if (i + 1 < n && x == bl && s[i + 1] == br) { s[j++] = bm; i += 2; }
-      else { s[j++] = x; i++; }
-    }
-    n = j;
-    floor = rank + 1u;
+  // the value of the pair's first position >= floor, kNoRank when there is none
+  __device__ __forceinline__ uint32_t value(uint32_t v) const {
+    if (v == kNoRank) return v;
+    uint32_t r = value_rank<Packed>(v);
+    if (r >= floor) return v;
+    do r = info[2 * r + 1]; while (r < floor);  // (the end of the chain, kNoRank, is below no floor)
+    if (r == kNoRank) return kNoRank;
+    return Packed ? ((r << 16) | (info[2 * r] - SWT_SYM_BASE)) : r;
   }
-  return n;
-}
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ bool takes(uint32_t) const { return true; }
+  __device__ __forceinline__ void next(uint32_t rank) { floor = rank + 1u; }
+  // (the merged symbol is the winning position's, which the walker reads from info once the round's pair is known)
+  __device__ __forceinline__ bool lookup(const BpeSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r, uint32_t &v, uint32_t &mg) const {
+    v = value(slot_value(slots, sh, l, r));
+    mg = 0;
+    return true;
+  }
+  template <class Lds>
+  __device__ __forceinline__ ListRule of(const Lds &, uint32_t) const { return *this; }  // every word's rule, the floor at 0
+  __device__ __forceinline__ ListRule of(uint64_t, uint64_t) const { return *this; }
+};
 
-// ---- BPE-dropout (include/swt.h, swt_bpe_encode_dropout): the loop of merge_word with every candidate pair of a round skipped
-// when its draw says so.  The draw of pair k in round t of the word with the key (i, b) -- its sentence and its first byte's
-// offset in it -- is word k & 3 of Philox at the counter ((t << 16) + (k >> 2), b, i, epoch): one call serves four neighbours.
+// BPE-dropout (include/swt.h, swt_bpe_encode_dropout): FastBPE's order with every candidate pair of a round skipped when its
+// draw says so.  The draw of pair k in round t of the word with the key (i, b) -- its sentence and its first byte's offset in
+// it -- is word k & 3 of Philox at the counter ((t << 16) + (k >> 2), b, i, epoch): one call serves four neighbours.  A pair
+// that does not beat the minimum so far cannot change it, so the loops do not ask for its draw: which calls are made is theirs.
 struct DropDraw {  // what a dropout launch draws with: kernel arguments of the dropout kernels, and of no other
   unsigned long long drop_below;  // 0 .. 2^32
   uint32_t key0, key1, epoch;
 };
-struct NoDrop {};  // what every other kernel carries in their place
 struct DropWord { uint32_t i, b; };
-// the draws of one round of one word, asked for in any order of k; the last call's four words are kept
-struct DropRound {
+struct DropRule {
+  static constexpr bool kChain = false;
   const DropDraw &dd;
   const DropWord w;
-  const uint32_t t16;
+  uint32_t t = 0, t16 = 0;       // the rounds begun, and the round at hand << 16
   uint32_t group = 0xFFFFFFFFu;  // k >> 2 of the call `x` holds (a word has fewer than 2^32 symbols: no group is all ones)
-  Philox x{};
-  __device__ __forceinline__ DropRound(const DropDraw &d, const DropWord &word, uint32_t t) : dd(d), w(word), t16(t << 16) {}
-  __device__ __forceinline__ bool dropped(uint32_t k) {
+  Philox x{};                    // the draws are asked for in any order of k; the last call's four words are kept
+  __device__ __forceinline__ DropRule(const DropDraw &d, const DropWord &word) : dd(d), w(word) {}
+  __device__ __forceinline__ uint32_t value(uint32_t v) const { return v; }
+  __device__ __forceinline__ bool takes(uint32_t k) {
     if ((k >> 2) != group) {
       group = k >> 2;
       x = philox4x32_10(t16 + group, w.b, w.i, dd.epoch, dd.key0, dd.key1);
     }
     const uint32_t q = k & 3u;
     const uint32_t v = q == 0u ? x.x[0] : q == 1u ? x.x[1] : q == 2u ? x.x[2] : x.x[3];
-    return v < dd.drop_below;
+    return v >= dd.drop_below;
+  }
+  __device__ __forceinline__ void begin() { t16 = t++ << 16; group = 0xFFFFFFFFu; x = Philox{}; }  // (no draw outlives its round)
+  __device__ __forceinline__ void next(uint32_t) {}  // (begin() counts the rounds)
+  // the walker's probe of a pair: its value and, from the slot, its merged symbol; false when the pair does not merge
+  __device__ __forceinline__ bool lookup(const BpeSlot *__restrict__ slots, uint32_t sh, uint32_t l, uint32_t r, uint32_t &v, uint32_t &mg) const {
+    return slot_lookup(slots, sh, l, r, v, mg);
   }
 };
 
-// The serial form for the one-lane fallback (a word longer than a chunk), as merge_word.  Returns the new length.
-__device__ uint32_t merge_word_dropout(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh, const DropDraw &dd,
-                                       const DropWord &w) {
-  for (uint32_t t = 0; n >= 2; t++) {
-    DropRound R(dd, w, t);
+// The literal rounds on a symbol array in global memory, the one-lane fallback for a word longer than a chunk (bpe.py:210-238
+// under RankRule, bpe.py:124-127 under ListRule): repeat { the best adjacent pair; replace all of its occurrences left to right,
+// non-overlapping }.  Returns the new length.
+template <bool Packed, class Rule>
+__device__ uint32_t walker_rounds(uint32_t *s, uint32_t n, const BpeSlot *__restrict__ slots, uint32_t sh, Rule rule) {
+  while (n >= 2) {
+    rule.begin();
     uint32_t best = kNoRank, bm = 0, bl = 0, br = 0;
     uint32_t a = s[0];
     for (uint32_t k = 0; k + 1 < n; k++) {
       const uint32_t b = s[k + 1];
-      uint32_t rk, mg;
-      // (a pair that does not beat the minimum so far cannot change it: its draw is not needed)
-      if (slot_lookup(slots, sh, a, b, rk, mg) && rk < best && !R.dropped(k)) { best = rk; bm = mg; bl = a; br = b; }
+      uint32_t v, mg;
+      if (rule.lookup(slots, sh, a, b, v, mg) && v < best && rule.takes(k)) { best = v; bm = mg; bl = a; br = b; }
       a = b;
     }
     if (best == kNoRank) break;
-    uint32_t j = 0, i = 0;  // i counts in the round's sequence, which is what a draw is indexed by; j <= i
+    if constexpr (Rule::kChain) bm = rule.info[2 * value_rank<Packed>(best)];
+    uint32_t j = 0, i = 0;  // i counts in the round's sequence, which is what takes() goes by; j <= i
     while (i < n) {
       const uint32_t x = s[i];
-      if (i + 1 < n && x == bl && s[i + 1] == br && !R.dropped(i)) { s[j++] = bm; i += 2; }
+      if (i + 1 < n && x == bl && s[i + 1] == br && rule.takes(i)) { s[j++] = bm; i += 2; }
       else { s[j++] = x; i++; }
     }
     n = j;
+    rule.next(value_rank<Packed>(best));
   }
   return n;
 }
@@ -263,12 +274,11 @@ struct GiantResult { uint64_t end; uint32_t ntok; };
 
 // One lane, global memory only: the word (or single separator) starting at byte `pos`, bounded by
 // `send` (end of its sentence).  Tokens go to `out` (which doubles as the symbol workspace).
-// Ordered: the merges in list order (merge_word_ordered; `info` is its chain, unused otherwise).
-// Draw = DropDraw: BPE-dropout with the draws `draw` and the word's key `w` (merge_word_dropout); NoDrop in every other kernel.
-template <bool Packed, bool Ordered, class Draw>
+// `rule`: the word's merge rule (walker_rounds).
+template <bool Packed, class Rule>
 __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos, uint64_t send,
-                                  const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                  const uint32_t *__restrict__ info, uint32_t *out, const Draw &draw, const DropWord &w) {
+                                  const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh, uint32_t *out,
+                                  const Rule &rule) {
   GiantResult r{pos, 0};
   uint32_t n = 0;
   bool first = true;
@@ -288,8 +298,7 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
     r.end += len;
     first = false;
   }
-  if constexpr (std::is_same_v<Draw, DropDraw>) n = merge_word_dropout(out, n, slots, sh, draw, w);
-  else n = Ordered ? merge_word_ordered<Packed>(out, n, slots, sh, info) : merge_word(out, n, slots, sh);
+  n = walker_rounds<Packed>(out, n, slots, sh, rule);
   for (uint32_t i = 1; i < n; i++) out[i] |= SWT_BPE_CONT;
   r.ntok = n;
   return r;
@@ -309,8 +318,8 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //        word is finished takes the next word of the list.  On a PROPER table (every pair ranks above the merges that produce
 //        its symbols: any trained table) merging one occurrence per round is the reference's "all occurrences of the best
 //        pair, left to right" (bpe.py:221-235) -- what is left of the pair is still the minimum and is found leftmost-first
-//        in the next round.  Tables without that property, and words beyond 32 symbols, take slow_word(): the same loop in
-//        its literal form (all occurrences per round, compaction), one lane per word.
+//        in the next round.  Tables without that property, and words beyond 32 symbols, take literal_rounds(): the same loop
+//        in its literal form (all occurrences per round, compaction), one lane per word, under the kernel's merge rule.
 //   E/F  order-preserving ballot compaction over the SYMBOL space to the tile's output run; the tile-local token offset of
 //        every sentence, through the split's symbol masks.
 // Template parameters:
@@ -325,7 +334,7 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //          each form keeps only its own arguments in scalar registers (one kernel for all three spilled 44 of them).
 //   Ordered: NaiveBPE's list order (bpe.py:126-127) instead of lowest rank first: `slots` is the table of FIRST list positions,
 //          `merged_of_rank` the interleaved (merged symbol, next position of the same pair) array, and every multi-symbol word
-//          goes through ordered_word() / merge_word_ordered(), one lane per word.  Launched only for a table that is not
+//          goes through the literal rounds under a ListRule, one lane per word.  Launched only for a table that is not
 //          order-equivalent (swt_bpe_table::order_equivalent), where the two orders can disagree.
 // Measured and dropped (profiles/r03_experiments/bpe_lane_*.txt): one wave running the rounds for the words of four tiles
 // (fewer instructions, but three waves of four idle meanwhile: 0.229 against 0.200 ms), tiles that place their own output by a
@@ -342,10 +351,13 @@ __device__ GiantResult giant_word(const uint8_t *__restrict__ text, uint64_t pos
 //          lane_tail) are plain minima, 6 vector instructions and 2 ds_read2_b32 per four slots where building the keys from the
 //          values took 15 and 4 (profiles/lane_keys.txt).  The merged code comes from the key's rank (narrow_merged): letters + rank
 //          in the kernel of a sequential table (template parameter Seq), code_of_rank[rank] in that of any other.
-//   Dropout: BPE-dropout (swt_bpe_encode_dropout*, include/swt.h): every multi-symbol word goes through dropout_word() /
-//          merge_word_dropout(), one lane per word, with the candidate pairs of every round dropped by their Philox draws.  Wide
+//   Dropout: BPE-dropout (swt_bpe_encode_dropout*, include/swt.h): every multi-symbol word goes through the literal rounds
+//          under a DropRule, one lane per word, with the candidate pairs of every round dropped by their Philox draws.  Wide
 //          symbols, Modes 0 and 2 (two occurrences of a word may differ: no unique-word pass).  The draws are arguments of these
-//          instantiations alone (DirectDrop); the others carry a NoDrop and test nothing.  DESIGN.md section 4.2e.
+//          instantiations alone (DirectDrop).  DESIGN.md section 4.2e.
+// Ordered and Dropout stop at the kernel: it makes one thing of them (lane_rules) -- a RankRule, a ListRule, or the DropSite that
+// makes every word its DropRule -- and that is what lane_chunk_end, giant_word and lane_rounds take.  A RankRule is empty and its
+// answers are constants, so the kernels of FastBPE's order carry nothing for the other two and test nothing.
 template <bool Narrow>
 struct LaneSym {  // how a symbol stands in LDS
   using type = uint32_t;
@@ -423,27 +435,39 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long uniform_mask,
 
 constexpr uint32_t kDirtyVal = 0xFFFFFFFEu;  // above every table value (ranks stay below 2^32 - 2), below kNoRank
 
-// bpe.py:210-238 on one word whose symbols S[0..n) and pair values V[0..n) (V[n-1] = kNoRank) live in LDS: every round merges
-// ALL occurrences of the best pair left to right, compacts the word and probes only the pairs that changed.
+// The literal rounds (bpe.py:210-238 under RankRule, bpe.py:124-127 under ListRule) on one word whose symbols S[0..n) and pair
+// values V[0..n) (V[n-1] = kNoRank) live in LDS: every round merges ALL occurrences of the best pair left to right, compacts the
+// word and probes only the pairs that changed.  A cached value outlives the round under every rule: it stays the pair's rank
+// whatever was dropped around it (DropRule), and one above the round's minimum is a position >= the new floor, so it stays the
+// pair's first such position (ListRule; the values the split left come from the table of first positions and are valid at
+// floor 0).  All slots of the winning pair hold the same value, so V[i] == m finds them.  The compaction reads slot i -- the index
+// takes() goes by -- and writes slot j <= i.
 // Narrow: S holds 16-bit codes.  A FOREIGN symbol's V entry is its code point (>= kNarrowNoPair, so it is never the minimum); it
 // moves with the symbol when the word is compacted and is neither marked dirty nor reset.  The pair entries come in as keys
 // (slot_key) and are read by their RANK half alone: the word is finished here, so the low half -- the split's slot, stale once the
 // word is compacted, or the code of a value looked up here -- is never read as a slot.
-template <bool Packed, bool Narrow = false, bool Seq = false>
-__device__ void slow_word(typename LaneSym<Narrow>::type *S, uint32_t *V, const uint32_t n0, const typename LaneSym<Narrow>::Slot *__restrict__ slots,
-                          uint32_t sh, const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D) {
+template <bool Packed, bool Narrow = false, bool Seq = false, class Rule>
+__device__ void literal_rounds(typename LaneSym<Narrow>::type *S, uint32_t *V, const uint32_t n0, const typename LaneSym<Narrow>::Slot *__restrict__ slots,
+                               uint32_t sh, const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D, Rule rule) {
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   uint32_t n = n0;
   for (;;) {
+    rule.begin();
     uint32_t m = kNoRank;
-    for (uint32_t i = 0; i + 1 < n; i++) m = min(m, V[i]);
+    for (uint32_t k = 0; k + 1 < n; k++) {
+      const uint32_t v = V[k];
+      if (m > v && rule.takes(k)) m = v;  // (a pair that does not beat the minimum so far cannot change it: it is not asked about)
+    }
     if (Narrow ? m >= kNarrowNoPair : m == kNoRank) break;
+    const uint32_t rank = Packed ? (m >> 16) : m;
     uint32_t mg;
-    if constexpr (Narrow) mg = narrow_merged<Seq>(D, m >> 16); else mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
+    if constexpr (Narrow) mg = narrow_merged<Seq>(D, rank);
+    else mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[Rule::kChain ? 2 * rank : rank];
     uint32_t i = 0, j = 0;
     while (i < n) {
       const uint32_t vi = V[i];
-      const bool take = i + 1 < n && (Narrow ? (vi >> 16) == (m >> 16) : vi == m);  // (no other kind of entry has a rank's high half)
+      // (Narrow: no other kind of entry has a rank's high half)
+      const bool take = i + 1 < n && (Narrow ? (vi >> 16) == (m >> 16) : vi == m) && rule.takes(i);
       const uint32_t s = take ? mg : (S[i] & ~kCont);
       if (take && j && !(Narrow && (S[j - 1] & ~kCont) == kNarrowForeign)) V[j - 1] = kDirtyVal;
       S[j] = j ? (s | kCont) : s;
@@ -452,83 +476,12 @@ __device__ void slow_word(typename LaneSym<Narrow>::type *S, uint32_t *V, const 
       j++;
     }
     n = j;
+    rule.next(rank);
     if (!(Narrow && (S[n - 1] & ~kCont) == kNarrowForeign)) V[n - 1] = kNoRank;
     for (uint32_t k = 0; k + 1 < n; k++)
-      if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~kCont, S[k + 1] & ~kCont);
+      if (V[k] == kDirtyVal) V[k] = rule.value(slot_value(slots, sh, S[k] & ~kCont, S[k + 1] & ~kCont));
   }
   for (uint32_t k = n; k < n0; k++) S[k] = kDead;
-}
-
-// NaiveBPE.encode_word (bpe.py:124-127) on the same layout, modelled on slow_word: a round merges all occurrences of the pair
-// with the smallest list position >= floor and raises the floor past it.  The values the split left come from the table of
-// first positions, so they are valid at floor 0; a cached value above the round's minimum is a position >= the new floor and
-// stays the pair's first such position, so only the pairs a merge created are probed again -- and walk the chain of their
-// pair's positions up to the floor (ordered_value).  All slots of the winning pair hold the same value, so V[i] == m finds them.
-template <bool Packed>
-__device__ void ordered_word(uint32_t *S, uint32_t *V, const uint32_t n0, const BpeSlot *__restrict__ slots, uint32_t sh,
-                             const uint32_t *__restrict__ info) {
-  uint32_t n = n0;
-  for (;;) {
-    uint32_t m = kNoRank;
-    for (uint32_t i = 0; i + 1 < n; i++) m = min(m, V[i]);
-    if (m == kNoRank) break;
-    const uint32_t rank = Packed ? (m >> 16) : m;
-    const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : info[2 * rank];
-    const uint32_t floor = rank + 1u;
-    uint32_t i = 0, j = 0;
-    while (i < n) {
-      const uint32_t vi = V[i];
-      const bool take = i + 1 < n && vi == m;
-      const uint32_t s = take ? mg : (S[i] & ~SWT_BPE_CONT);
-      if (take && j) V[j - 1] = kDirtyVal;
-      S[j] = j ? (s | SWT_BPE_CONT) : s;
-      V[j] = take ? kDirtyVal : vi;
-      i += take ? 2u : 1u;
-      j++;
-    }
-    n = j;
-    V[n - 1] = kNoRank;
-    for (uint32_t k = 0; k + 1 < n; k++)
-      if (V[k] == kDirtyVal)
-        V[k] = ordered_value<Packed>(slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT), floor, info);
-  }
-  for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
-}
-
-// BPE-dropout on the same layout, modelled on slow_word: a round's minimum runs over the pairs that are not dropped, the merge
-// takes the occurrences of the winning pair that are not dropped, and t counts the rounds.  A cached value stays the pair's
-// rank whatever was dropped around it, so only the pairs a merge created are probed again.  The compaction reads slot i (the
-// index a draw goes by) and writes slot j <= i.
-template <bool Packed>
-__device__ void dropout_word(uint32_t *S, uint32_t *V, const uint32_t n0, const BpeSlot *__restrict__ slots, uint32_t sh,
-                             const uint32_t *__restrict__ merged_of_rank, const DropDraw &dd, const DropWord &w) {
-  uint32_t n = n0;
-  for (uint32_t t = 0;; t++) {
-    DropRound R(dd, w, t);
-    uint32_t m = kNoRank;
-    for (uint32_t k = 0; k + 1 < n; k++) {
-      const uint32_t v = V[k];
-      if (v < m && !R.dropped(k)) m = v;  // (a pair that does not beat the minimum so far cannot change it: no draw)
-    }
-    if (m == kNoRank) break;
-    const uint32_t mg = Packed ? (SWT_SYM_BASE + (m & 0xFFFFu)) : merged_of_rank[m];
-    uint32_t i = 0, j = 0;
-    while (i < n) {
-      const uint32_t vi = V[i];
-      const bool take = i + 1 < n && vi == m && !R.dropped(i);
-      const uint32_t s = take ? mg : (S[i] & ~SWT_BPE_CONT);
-      if (take && j) V[j - 1] = kDirtyVal;
-      S[j] = j ? (s | SWT_BPE_CONT) : s;
-      V[j] = take ? kDirtyVal : vi;
-      i += take ? 2u : 1u;
-      j++;
-    }
-    n = j;
-    V[n - 1] = kNoRank;
-    for (uint32_t k = 0; k + 1 < n; k++)
-      if (V[k] == kDirtyVal) V[k] = slot_value(slots, sh, S[k] & ~SWT_BPE_CONT, S[k + 1] & ~SWT_BPE_CONT);
-  }
-  for (uint32_t k = n; k < n0; k++) S[k] = kInvalidTok;
 }
 
 // classes of the first 1,024 code points: 16 per lane, two bits each (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)
@@ -721,13 +674,13 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
 
 // ---- the end of a chunk that does not end the tile: one word longer than the staged bytes goes to the one-lane walker (and the
 // chunk is done: C.giant), anything else is cut at its last word boundary.  Closes the word list and moves T.cb past the chunk.
-// Draw: the draws of a dropout kernel (DropDraw; the word then goes through merge_word_dropout), NoDrop in every other.
-template <int Cap, int Mode, bool Packed, bool Ordered, bool Narrow, class Draw>
+// rules: what makes the long word its merge rule (lane_rules).
+template <int Cap, int Mode, bool Packed, bool Narrow, class Rules>
 __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap, Narrow> &L, GiantResult &giant, const uint8_t *__restrict__ text, const uint64_t *__restrict__ sent_off,
                                                const uint8_t *__restrict__ cls_tab, const BpeSlot *__restrict__ slots, uint32_t sh,
-                                               const uint32_t *__restrict__ merged_of_rank, LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
+                                               LaneTile &T, LaneChunk &C, int lane, uint32_t *__restrict__ sent_local,
                                                const uint32_t *__restrict__ uslot, unsigned long long *__restrict__ rec,
-                                               unsigned long long *__restrict__ drec, const DirectOut &direct, const Draw &draw) {
+                                               unsigned long long *__restrict__ drec, const DirectOut &direct, const Rules &rules) {
   constexpr bool kDirect = Mode == 2, kRec = Mode == 1;
   if (!C.last) {
     if (C.cut < 0) {
@@ -736,10 +689,8 @@ __device__ __forceinline__ void lane_chunk_end(LaneLds<Cap, Narrow> &L, GiantRes
         uint64_t s = T.s_next;
         while (s < T.s_hi && sent_off[s] <= T.cb) s++;
         const uint64_t send = sent_off[s];  // s <= s_hi and sent_off[s_hi] = span_end > cb
-        // dropout: the word's sentence is the last that starts at or before it, s - 1 (the tile's first starts at span_base <= cb: s > s_lo)
-        DropWord w{0u, 0u};
-        if constexpr (std::is_same_v<Draw, DropDraw>) w = DropWord{(uint32_t)(s - 1), (uint32_t)(T.cb - sent_off[s - 1])};
-        giant = giant_word<Packed, Ordered>(text, T.cb, send, cls_tab, slots, sh, merged_of_rank, T.tile_out + T.run, draw, w);
+        // the word's sentence is the last that starts at or before it, s - 1 (the tile's first starts at span_base <= cb: s > s_lo)
+        giant = giant_word<Packed>(text, T.cb, send, cls_tab, slots, sh, T.tile_out + T.run, rules.of(s - 1, T.cb));
       }
       wave_sync();
       const GiantResult g = giant;
@@ -944,43 +895,52 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
   }
 }
 
-// BPE-dropout: what a lane needs beside the draws to find the key (i, b) of the word it takes -- the chunk's place in the text
-// and the tile's sentences.  A kernel without dropout carries a NoDrop in its place.
+// BPE-dropout: what makes a word its DropRule -- the draws, and what a lane needs to find the key (i, b) of the word it takes,
+// the chunk's place in the text and the tile's sentences.
 struct DropSite {
   DropDraw dd;
   const uint64_t *sent_off;
   uint64_t s_lo, s_hi;  // the tile's sentences: sent_off[s_lo] <= every byte of the tile < sent_off[s_hi]
   uint64_t abase;       // LaneChunk::abase
   uint32_t nblk;        // LaneChunk::nblk
-};
-// The key of the word whose first symbol is symbol `where` of the chunk.  Symbol -> byte is the inverse of the split's byte ->
-// symbol maps: the block whose sympre is the last at or below `where`, then that many set bits into its symmask.  Byte -> sentence
-// is a search of the tile's sentence offsets for the last at or below the byte (empty sentences share an offset with the next
-// sentence that has bytes, which is the last of them).
-template <int Cap>
-__device__ __forceinline__ DropWord drop_word_at(const LaneLds<Cap, false> &L, const DropSite &site, uint32_t where) {
-  uint32_t blk = 0;
-  while (blk + 1 < site.nblk && L.sympre[blk + 1] <= where) blk++;
-  unsigned long long m = L.symmask[blk];
-  for (uint32_t r = where - L.sympre[blk]; r != 0u && m != 0ull; r--) m &= m - 1ull;
-  const uint64_t pos = site.abase + (uint64_t)blk * 64u + (m ? (uint32_t)__builtin_ctzll(m) : 0u);
-  uint64_t lo = site.s_lo, hi = site.s_hi;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (site.sent_off[mid] <= pos) lo = mid; else hi = mid;
+  __device__ __forceinline__ DropRule of(uint64_t s, uint64_t pos) const { return DropRule(dd, DropWord{(uint32_t)s, (uint32_t)(pos - sent_off[s])}); }
+  // Symbol -> byte is the inverse of the split's byte -> symbol maps: the block whose sympre is the last at or below `where`, then
+  // that many set bits into its symmask.  Byte -> sentence is a search of the tile's sentence offsets for the last at or below the
+  // byte (empty sentences share an offset with the next sentence that has bytes, which is the last of them).
+  template <int Cap>
+  __device__ __forceinline__ DropRule of(const LaneLds<Cap, false> &L, uint32_t where) const {
+    uint32_t blk = 0;
+    while (blk + 1 < nblk && L.sympre[blk + 1] <= where) blk++;
+    unsigned long long m = L.symmask[blk];
+    for (uint32_t r = where - L.sympre[blk]; r != 0u && m != 0ull; r--) m &= m - 1ull;
+    const uint64_t pos = abase + (uint64_t)blk * 64u + (m ? (uint32_t)__builtin_ctzll(m) : 0u);
+    uint64_t lo = s_lo, hi = s_hi;
+    while (hi - lo > 1) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (sent_off[mid] <= pos) lo = mid; else hi = mid;
+    }
+    return of(lo, pos);
   }
-  return DropWord{(uint32_t)lo, (uint32_t)(pos - site.sent_off[lo])};
+};
+// The one thing a kernel makes of Ordered and Dropout, once per tile: what gives every word its merge rule (a DropSite learns
+// the place of every chunk from the kernel).
+template <bool Packed, bool Ordered, bool Dropout, class Direct>
+__device__ __forceinline__ auto lane_rules(const uint32_t *__restrict__ info, const Direct &direct, const uint64_t *__restrict__ sent_off, const LaneTile &T) {
+  if constexpr (Dropout) return DropSite{direct.draw, sent_off, T.s_lo, T.s_hi, 0u, 0u};
+  else if constexpr (Ordered) return ListRule<Packed>{info};
+  else return RankRule{};
 }
 
 // The rounds proper: until the list is empty and at most 16 words are still merging, which are returned for the tail.
-// Site: DropSite in a dropout kernel, where every multi-symbol word goes through dropout_word(); NoDrop in every other.
-template <bool Packed, bool Proper, bool Seq, int Cap, bool Ordered, bool Narrow, class Site>
+// rules: what makes a word its merge rule (lane_rules).  Only under a RankRule are there rounds proper; under the other two
+// every multi-symbol word is finished in the literal rounds where its lane takes it.
+template <bool Packed, bool Proper, bool Seq, int Cap, bool Narrow, class Rules>
 __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const uint16_t *list, uint32_t n_list, int lane,
                                                 const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh,
-                                                const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D, const Site &site) {
-  constexpr bool Dropout = std::is_same_v<Site, DropSite>;
-  static_assert(!(Dropout && (Narrow || Ordered)), "the dropout form: wide symbols, FastBPE's ranks");
-  static_assert(!(Narrow && (Ordered || !Packed)), "the narrow form is that of a packed table in FastBPE's order");
+                                                const uint32_t *__restrict__ merged_of_rank, const NarrowDir &D, const Rules &rules) {
+  constexpr bool Ranked = std::is_same_v<Rules, RankRule>;
+  static_assert(Ranked || !(Narrow || Proper), "list order and dropout: wide symbols, the literal rounds alone");
+  static_assert(!(Narrow && !Packed), "the narrow form is that of a packed table");
   constexpr uint32_t kNoKey = Narrow ? kNarrowNoPair : Packed ? 0xFFFF0000u : 0xFFFFFFE0u;  // keys from here up: no pair
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont, kDead = LaneSym<Narrow>::kDead;
   const unsigned long long lt = (1ull << lane) - 1ull;
@@ -1001,14 +961,8 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
         S = &L.sym[where];
         V = &L.val[where];
         alive = n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u;
-        if constexpr (Dropout) {
-          dropout_word<Packed>(S, V, n, slots, sh, merged_of_rank, site.dd, drop_word_at(L, site, where));
-          n = 0u;
-        } else if constexpr (Ordered) {
-          ordered_word<Packed>(S, V, n, slots, sh, merged_of_rank);
-          n = 0u;
-        } else if (!Proper || n > 32u) {
-          slow_word<Packed, Narrow, Seq>(S, V, n, slots, sh, merged_of_rank, D);
+        if (!Proper || n > 32u) {
+          literal_rounds<Packed, Narrow, Seq>(S, V, n, slots, sh, merged_of_rank, D, rules.of(L, where));
           n = 0u;
         } else {
           if constexpr (Narrow) { ks = KeyScan(n); key = scan_keys<0>(V, n, ks); } else key = scan_key<Packed>(V, n);
@@ -1018,7 +972,7 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
     }
     const unsigned long long BUSY = __ballot(n != 0u);
     if (next >= n_list && __popcll(BUSY) <= 16) break;  // the last few (long) words: several lanes each, lane_tail
-    if (BUSY == 0ull) continue;  // every word just taken went through slow_word: take the next ones
+    if (BUSY == 0ull) continue;  // every word just taken went through the literal rounds: take the next ones
     if (n != 0u) {
       // slot im merges with the next live slot r; pl / rr = the live slots either side of the pair
       const uint32_t im = key & 31u;
@@ -1113,9 +1067,9 @@ __device__ unsigned long long g_lane_stamp[2 * kLaneStamps];
 
 // One wave per tile: running text (Mode 0), the unique words of the dedup path (Mode 1), the single-workgroup call (Mode 2).
 // The DROPOUT form (swt_bpe_encode_dropout*, include/swt.h; template parameter Dropout): the same wave over the same staging,
-// split, emit, scan and gather, every multi-symbol word through dropout_word() -- one lane per word, as the ordered form -- and
-// a word longer than a chunk through merge_word_dropout().  Wide symbols, Mode 0 or 2.  Its draws travel behind the DirectOut in
-// its last argument (DirectDrop); every other instantiation has the arguments it always had, carries a NoDrop and tests nothing.
+// split, emit, scan and gather, every multi-symbol word through the literal rounds under a DropRule -- one lane per word, as the
+// ordered form.  Wide symbols, Mode 0 or 2.  Its draws travel behind the DirectOut in its last argument (DirectDrop); every other
+// instantiation has the arguments it always had.
 struct DirectDrop : DirectOut { DropDraw draw; };
 template <bool Packed, bool Proper, int Cap, int Mode, bool Ordered = false, bool Narrow = false, bool Seq = false, bool Dropout = false>
 __global__ __launch_bounds__(64) void bpe_lane_kernel(
@@ -1131,8 +1085,6 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   static_assert(!Narrow || kLaneCap != 512 || sizeof(LaneLds<Cap, true>) + sizeof(LaneShared<true>) <= sizeof(LaneLds<kLaneCap>) + sizeof(LaneShared<false>),
                 "the narrow kernel's chunk is sized to the LDS of the wide one, so that as many waves reside");
   static_assert(!Dropout || (Mode != 1 && !Narrow && !Ordered && !Proper), "the dropout form: running text or the single workgroup, wide symbols, FastBPE's ranks");
-  std::conditional_t<Dropout, DropDraw, NoDrop> draw{};
-  if constexpr (Dropout) draw = direct.draw;
   using Slot = typename LaneSym<Narrow>::Slot;
   __shared__ LaneLds<Cap, Narrow> L;
   __shared__ LaneShared<Narrow> SH;
@@ -1159,6 +1111,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   T.s_next = T.s_lo;
   T.cb = T.span_base;
   uint16_t *const list = reinterpret_cast<uint16_t *>(L.txt);  // the staged bytes are not read again once the split is done
+  auto rules = lane_rules<Packed, Ordered, Dropout>(merged_of_rank, direct, sent_off, T);
   for (;;) {
     LaneChunk C;
     lane_split(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
@@ -1166,8 +1119,9 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     // (Narrow: their table comes out of the directory as a generic pointer and stays one: the walker's three loads of a slot are
     // the kernel's only flat loads, and marking the table global cost the kernel 0.5 M vector instructions a launch in registers
     // moved about, profiles/lane_diet.txt section 4)
-    lane_chunk_end<Cap, Mode, Packed, Ordered>(L, SH.giant, text, sent_off, cls_tab, Narrow ? D.wide_slots : slots, Narrow ? D.wide_sh : sh, merged_of_rank, T, C,
-                                               lane, sent_local, uslot, rec, drec, direct, draw);
+    if constexpr (Dropout) { rules.abase = C.abase; rules.nblk = C.nblk; }
+    lane_chunk_end<Cap, Mode, Packed>(L, SH.giant, text, sent_off, cls_tab, Narrow ? D.wide_slots : slots, Narrow ? D.wide_sh : sh, T, C, lane, sent_local, uslot,
+                                      rec, drec, direct, rules);
     if (C.giant) continue;
     uint32_t c2, c1, c0;
     lane_words_count(L, C.nw, lane, c2, c1, c0);
@@ -1175,9 +1129,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
     wave_sync();
     // the rounds, then four lanes a word once the list is empty and 16 words are left (lane_tail)
     // (dropout: every word is finished where its lane takes it, and nothing is left for the tail)
-    std::conditional_t<Dropout, DropSite, NoDrop> site{};
-    if constexpr (Dropout) site = DropSite{draw, sent_off, T.s_lo, T.s_hi, C.abase, C.nblk};
-    const LaneWord W = lane_rounds<Packed, Proper, Seq, Cap, Ordered>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank, D, site);
+    const LaneWord W = lane_rounds<Packed, Proper, Seq, Cap>(L, list, c2 + c1 + c0, lane, tab, sh, merged_of_rank, D, rules);
     const unsigned long long BUSY = __ballot(W.n != 0u);
     if (BUSY != 0ull) lane_tail<Packed, 4, Seq, Cap>(L, W, BUSY, lane, tab, sh, merged_of_rank, D);
     wave_sync();
@@ -1297,7 +1249,7 @@ static BpeView bpe_view(const swt_bpe_table *t, bool ordered) {
 
 // Which bpe_lane_kernel a launch gets.  Mode (the kernel's: 0 tiles of running text, 1 the unique words of the dedup path, 2 the
 // single workgroup) is the caller's; from the table come Packed and Proper, from the entry point Ordered (which has no Proper
-// form: every word goes through ordered_word), from the tile size of the launch the chunk size -- `cap` bytes where the tiled
+// form: every word goes through the literal rounds), from the tile size of the launch the chunk size -- `cap` bytes where the tiled
 // forms have it (128, 256), kLaneCap otherwise; the single workgroup exists at kLaneCap only.
 using LaneKernel = decltype(&bpe_lane_kernel<true, true, kLaneCap, 0>);
 template <int Cap, int Mode>
@@ -1489,7 +1441,7 @@ int swt_bpe_table_create(const uint32_t *left, const uint32_t *right, const uint
     if (merged[i] < SWT_SYM_BASE || merged[i] - SWT_SYM_BASE >= 0xFFFFu) t->packed = false;
   // NaiveBPE applies the list in order (bpe.py:126-127), every position of a repeated pair in its turn.  Without repeats and
   // on a proper table that is FastBPE's result and nothing more is built; otherwise the ordered form of the kernel gets the
-  // first position of every pair and the chain through its later ones (ordered_value).
+  // first position of every pair and the chain through its later ones (ListRule::value).
   t->order_equivalent = t->proper && last.size() == n_merges;
   if (!t->order_equivalent) {
     std::unordered_map<uint64_t, uint32_t> first, seen;

@@ -110,7 +110,7 @@ def characters(split, texts):
 PROPER = [("a", "b"), ("c", "d"), ("ab", "cd"), ("x", "y"), ("ż", "ó"), ("żó", "ł"), ("q", "q"), ("abcd", "abcd"), ("qq", "qq"),
           ("abcdabcd", "abcd"), ("xy", "xy"), ("ó", "ł"), ("\U0001F600", "\U0001F600"), ("€", "a"), ("b", "a"), ("ab", "ab")]
 # improper: ("ab", "c") ranks BELOW ("a", "b"), which makes its left symbol, ("a", "a") is listed twice and ("aa", "a") sits
-# between its two positions -- the device takes slow_word's literal rounds for such a table, and so must the dropout form
+# between its two positions -- the device takes the literal rounds (literal_rounds) for such a table, and so must the dropout form
 IMPROPER = [("ab", "c"), ("a", "a"), ("a", "b"), ("aa", "a"), ("c", "d"), ("abc", "d"), ("a", "a"), ("x", "y"), ("xy", "x"),
             ("q", "q"), ("qq", "q"), ("b", "a")]
 

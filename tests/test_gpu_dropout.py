@@ -1,4 +1,4 @@
-"""BPE-dropout on the device (swt_bpe_encode_dropout*, the Dropout form of bpe_lane_kernel: dropout_word, merge_word_dropout)
+"""BPE-dropout on the device (swt_bpe_encode_dropout*, the Dropout form of bpe_lane_kernel: the literal rounds under a DropRule)
 against the plain-Python model of tests/dropout_cases.py: ids and sentence offsets equal element by element, at the smallest
 shapes that reach each seam of the kernel -- the single workgroup and the tiles, tile boundaries moved by SWT_OPT_LANE_SPAN and
 SWT_OPT_LANE_TAPER, a word across a chunk's end, words beyond the 32-slot mask, a word longer than a chunk (one lane, global

@@ -12,7 +12,7 @@ cases run through the narrow kernel and once more through the wide one, which co
 The table of the 16-bit codes has a hash pair of its own: both slots from one multiply chain, addresses as a scalar base and a
 32-bit offset.  Its cases: every ordered pair of 90 letters as a merge (every pair of the text hits, every pair of a round
 misses; the builder doubles that table twice), a table whose merged codes are read from memory (the Seq = false kernel), an
-improper table (slow_word), and a word longer than a chunk, which the one-lane walker merges over the WIDE table.
+improper table (literal_rounds), and a word longer than a chunk, which the one-lane walker merges over the WIDE table.
 
 Every call through run() asks for the kernel it means and asserts that the launch took it (swt_debug_bpe_table_info 11).  All
 texts are built from a fixed seed; nothing here reads a file outside the repository.  Needs a real MI355X: `-m gpu`."""
@@ -189,7 +189,7 @@ def test_square_table(swt, oracle, dev):
 
 
 def test_tables_with_other_kernels(swt, oracle, dev, pre):
-    """the kernel of a table whose merged codes come from memory (Seq = false), an improper table (every word through slow_word),
+    """the kernel of a table whose merged codes come from memory (Seq = false), an improper table (every word through literal_rounds),
     and a word longer than a chunk, which the one-lane walker merges over the wide table of the ids"""
     rng = random.Random(0xD1EE)
     tok, orc = make(swt, oracle, REPEATED)

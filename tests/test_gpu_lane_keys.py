@@ -6,7 +6,7 @@ writes the slot (counted across its 64-byte blocks), a round writes two entries 
 two reads of two entries off one clamped base.  What can go wrong is what these tests aim at: a scan that reads past or before its
 word (words of every group edge, a word without a pair beside one of a very low rank), a slot that is counted wrongly (words
 across block boundaries and the chunk cut), equal ranks in one word (the leftmost one has to win), entries that are no keys
-(FOREIGN symbols, dead slots), the tail of the rounds with few words, slow_word on the same entries (an improper table, words
+(FOREIGN symbols, dead slots), the tail of the rounds with few words, literal_rounds on the same entries (an improper table, words
 beyond 32 symbols), and a table whose merged codes are not letters + rank (a merged string spelled twice: code_of_rank).
 
 Every call asks for the narrow kernel at every size (SWT_OPT_LANE_NARROW = 2) and asserts that the launch took it
@@ -172,7 +172,7 @@ def test_few_words(dev, pre):
 
 
 def test_improper_table(swt, oracle, dev):
-    """every word through slow_word on the keys; the table spells "ab" before the merge that produces it, so its merged codes are
+    """every word through literal_rounds on the keys; the table spells "ab" before the merge that produces it, so its merged codes are
     not letters + rank and come from code_of_rank"""
     tok, orc = make(swt, oracle, IMPROPER)
     h = tok._table

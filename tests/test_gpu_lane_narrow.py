@@ -88,7 +88,7 @@ def pre(swt, oracle, dev):
 
 def test_chunk_and_tile_seams(dev, pre):
     """texts and sentence starts at CAP - 1 .. CAP + 1, 2 CAP +- 1 and TILE +- 1 bytes; a word across the cut; a word longer than
-    a chunk (the one-lane walker); a word of 33 symbols (slow_word)"""
+    a chunk (the one-lane walker); a word of 33 symbols (literal_rounds)"""
     tok, orc, short, multibyte, cat = pre
     rng = random.Random(640)
     sizes = (CAP - 1, CAP, CAP + 1, 2 * CAP - 1, 2 * CAP, 2 * CAP + 1, TILE - 1, TILE, TILE + 1)
@@ -194,7 +194,7 @@ def test_eligibility_edge(swt, oracle, dev):
 
 
 def test_improper_table(swt, oracle, dev):
-    """a table that is not proper: every word goes through slow_word, with 16-bit symbols and foreign letters among them"""
+    """a table that is not proper: every word goes through literal_rounds, with 16-bit symbols and foreign letters among them"""
     tok, orc = make(swt, oracle, IMPROPER)
     assert info(dev, tok._table, 2) == 0 and info(dev, tok._table, 8) == 1
     rng = random.Random(512640)

@@ -34,7 +34,7 @@ def test_constants_are_the_kernels():
 PROPER = [("a", "b"), ("c", "d"), ("ab", "cd"), ("e", "e"), ("ee", "e"), ("abcd", "ab"), ("x", "y"), ("xy", "xy"),
           ("ab", "ab"), ("d", "a"), ("ż", "ó"), ("żó", "ł"), ("b", "c"), ("abcdab", "cd"), ("y", "x"), ("abcd", "abcd"),
           ("abcdabcd", "abcdabcd")]
-# not proper: (ab, c) ranks BELOW the merge that makes ab, and (aa, a) below (a, a): every word goes through slow_word
+# not proper: (ab, c) ranks BELOW the merge that makes ab, and (aa, a) below (a, a): every word goes through literal_rounds
 IMPROPER = [("ab", "c"), ("a", "b"), ("aa", "a"), ("a", "a"), ("c", "d"), ("x", "y"), ("b", "c")]
 
 
@@ -120,7 +120,7 @@ def seam_texts(rng, short, longs, multibyte, giant_unit):
 
 
 def test_pipeline_seams_handmade_tables(swt, oracle, dev):
-    """the proper table (one occurrence of the best pair per round) and the improper one (every word through slow_word)"""
+    """the proper table (one occurrence of the best pair per round) and the improper one (every word through literal_rounds)"""
     short = ["ab", "cd", "abcd", "xyxy", "eee", "abab", "abcdabcd", "da", "xyx"]
     longs = long_words("abcd", (25, 28, 31, 32)) + long_words("abcd", (33, 40, 64)) + ["e" * 32, "xy" * 16, "xy" * 17]
     multibyte = ["żół", "żółżół", "óż", "łłł"]

@@ -19,7 +19,7 @@ CAP = 512     # staged bytes per chunk: SWT_LANE_CAP (tests/test_gpu_lane_pipeli
 TILE = 384    # bytes of sentence starts per tile: SWT_LANE_TILE
 SPANS = (1, 2, 3, 4, 8, 0)  # 0 last: the library's own choice, which is also what the handle is left with
 
-# not proper: (ab, c) ranks BELOW the merge that makes ab, and (aa, a) below (a, a): every word goes through slow_word
+# not proper: (ab, c) ranks BELOW the merge that makes ab, and (aa, a) below (a, a): every word goes through literal_rounds
 IMPROPER = [("ab", "c"), ("a", "b"), ("aa", "a"), ("a", "a"), ("c", "d"), ("x", "y"), ("b", "c"), ("ż", "ó"), ("żó", "ł")]
 
 
@@ -130,7 +130,7 @@ def span_batches(rng, short, longs, multibyte):
 
 
 def test_span_seams_improper_table(swt, oracle, dev):
-    """a hand-made improper table: every word of every span goes through slow_word"""
+    """a hand-made improper table: every word of every span goes through literal_rounds"""
     tok, orc = make(swt, oracle, IMPROPER)
     lib = dev.lib()
     lib.swt_debug_bpe_table_info.restype = ctypes.c_int

@@ -195,7 +195,7 @@ def seam_suite(dev, tok, orc, short, longs, multibyte, seed):
 
 
 def test_taper_seams_improper_table(swt, oracle, dev):
-    """a hand-made improper table: every word goes through slow_word"""
+    """a hand-made improper table: every word goes through literal_rounds"""
     tok, orc = make(swt, oracle, IMPROPER)
     short = ["ab", "abc", "aaa", "aaaa", "cd", "xy", "abcabc", "bc", "aab", "xyxy"]
     longs = ["abc" * 9, "a" * 31, "abcd" * 9, "aab" * 14]

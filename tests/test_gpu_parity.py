@@ -967,10 +967,10 @@ def test_sharded_training_over_rccl_world1(swt, oracle, dev, corpora, shard_mode
 @pytest.mark.gpu
 def test_bpe_word_lane_kernel_boundaries(swt, oracle, dev, bpe, bpe_orc):
     """the shapes bpe_lane_kernel (csrc/swt_bpe_encode.hip) has of its own: words around the 32-slot live mask (longer ones take
-    slow_word), more multi-symbol words in a chunk than a wave has lanes (the lanes take a next word), words and multi-byte
+    literal_rounds), more multi-symbol words in a chunk than a wave has lanes (the lanes take a next word), words and multi-byte
     characters straddling the 64-byte blocks of the split and the 512-byte chunks, pairs that recur inside a word, and the same
     texts under a PROPER table (one occurrence of the best pair per round) and under tables that are not (every word through
-    slow_word: all occurrences per round, bpe.py:221-235)."""
+    literal_rounds: all occurrences per round, bpe.py:221-235)."""
     def table(merges):
         tok = swt.FastBPE()
         tok.merges_list = list(merges)

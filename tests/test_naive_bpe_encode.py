@@ -1,6 +1,6 @@
 """NaiveBPE.tokenize (bpe.py:114-158: the merges applied in list order) against the reference's own output
 (tests/golden/naivebpe.json, made by make_golden_naivebpe.py), through the rising-floor model the device runs
-(csrc/swt_bpe_encode.hip, ordered_word) and through the package's Python loop.  The device encoder
+(csrc/swt_bpe_encode.hip, literal_rounds under a ListRule) and through the package's Python loop.  The device encoder
 (tests/test_gpu_naive_bpe.py) is checked against the same fixture and model.  No GPU needed here."""
 import ctypes
 import json

@@ -9,6 +9,9 @@ one process, HIP events around enough back-to-back calls for 0.2 s each:
                    tree's), when one is given: the number that must not move, held to the spread measured in this same run
   dropout_draws    swt_bpe_encode_dropout_dev at drop_below = 1: every draw made, effectively none dropped
   dropout_p10      the same at p = 0.1
+  dropout_draws_parent, dropout_p10_parent   the two dropout legs through the parent's library (--parent-lib), their ids compared
+                   with this tree's first.  "dropout_against_parent": a leg passes when this tree's median does not exceed the
+                   parent's by more than the parent's own spread (max - min) in this run
 Before the timing the dropout ids at drop_below = 0 are compared with the plain ids on the whole text, and those at p = 0.1
 with the model of tests/dropout_cases.py on the first --check sentences.  Prints one JSON line; --out FILE appends it."""
 import argparse
@@ -24,7 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SEED, EPOCH = 2024, 0
-NEEDED = ("swt_init", "swt_last_error", "swt_bpe_table_create", "swt_bpe_table_destroy", "swt_bpe_table_set_option", "swt_bpe_encode_dev")
+NEEDED = ("swt_init", "swt_last_error", "swt_bpe_table_create", "swt_bpe_table_destroy", "swt_bpe_table_set_option", "swt_bpe_encode_dev",
+          "swt_bpe_encode_dropout_dev")
 
 
 def main():
@@ -85,14 +89,19 @@ def main():
         h_parent = table(parent)
         legs["plain_parent"] = plain_of(parent, h_parent)
 
-    def dropout_of(below, out=d_ids, n=n_sent, nb=n_bytes):
+    def dropout_of(below, out=d_ids, n=n_sent, nb=n_bytes, lib=here, h=h_here):
         def call():
-            N.check(here.swt_bpe_encode_dropout_dev(h_here, d_text.data_ptr(), nb, d_off.data_ptr(), n, out.data_ptr(), d_tok_off.data_ptr(),
-                                                    d_ntok.data_ptr(), 0, below, SEED, EPOCH, stream))
+            rc = lib.swt_bpe_encode_dropout_dev(h, d_text.data_ptr(), nb, d_off.data_ptr(), n, out.data_ptr(), d_tok_off.data_ptr(),
+                                                d_ntok.data_ptr(), 0, below, SEED, EPOCH, stream)
+            if rc:
+                raise RuntimeError("swt_bpe_encode_dropout_dev: %d %s" % (rc, lib.swt_last_error().decode()))
         return call
 
-    legs["dropout_draws"] = dropout_of(1)
-    legs["dropout_p10"] = dropout_of(D.drop_below(0.1))
+    drops = {"dropout_draws": 1, "dropout_p10": D.drop_below(0.1)}
+    for name, below in drops.items():
+        legs[name] = dropout_of(below)
+        if "plain_parent" in legs:
+            legs[name + "_parent"] = dropout_of(below, lib=parent, h=h_parent)
 
     # ---- the checks
     legs["plain"]()
@@ -108,10 +117,15 @@ def main():
         if int(d_ntok.item()) != n_plain or not torch.equal(d_ids[:n_plain], d_ids2[:n_plain]):
             raise AssertionError("the plain encode differs from the parent's")
     tokens = {}
-    for name in ("dropout_draws", "dropout_p10"):
+    for name, below in drops.items():
         legs[name]()
         torch.cuda.synchronize()
         tokens[name] = int(d_ntok.item())
+        if "plain_parent" in legs:
+            dropout_of(below, d_ids2, lib=parent, h=h_parent)()
+            torch.cuda.synchronize()
+            if int(d_ntok.item()) != tokens[name] or not torch.equal(d_ids[:tokens[name]], d_ids2[:tokens[name]]):
+                raise AssertionError("%s differs from the parent's" % name)
     k = min(args.check, n_sent)
     d_off_k = d_off[:k + 1].clone()  # the first k sentences as a call of their own: same indices, same bytes, same ids
     N.check(here.swt_bpe_encode_dropout_dev(h_here, d_text.data_ptr(), int(off[k]), d_off_k.data_ptr(), k, d_ids2.data_ptr(), d_tok_off.data_ptr(),
@@ -151,6 +165,12 @@ def main():
         p = out["legs"]["plain_parent"]
         out["plain_against_parent"] = {"ratio": round(base / p["median_ms"], 4),
                                        "margin": round(max(p["spread"], out["legs"]["plain"]["spread"]), 4)}
+        out["dropout_against_parent"] = {}
+        for name in drops:
+            theirs = ms[name + "_parent"]
+            over = statistics.median(ms[name]) - statistics.median(theirs)
+            out["dropout_against_parent"][name] = {"over_parent_ms": round(over, 4), "parent_spread_ms": round(max(theirs) - min(theirs), 4),
+                                                   "passes": bool(over <= max(theirs) - min(theirs))}
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:

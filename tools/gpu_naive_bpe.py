@@ -8,12 +8,17 @@ region bracketed by a device synchronisation on both sides (bench.py's encode_co
   b  swt_bpe_encode_naive_dev on the same table           order-equivalent: must launch the same kernels as a
   c  swt_bpe_encode_naive_dev on the table with two       not order-equivalent: the ordered form of bpe_lane_kernel
      dependent merges swapped
-  d  swt_bpe_encode_dev on the table of c                 FastBPE on an improper table (slow_word), for scale
+  d  swt_bpe_encode_dev on the table of c                 FastBPE on an improper table (the literal rounds), for scale
 
 Prints one JSON line: ms per step of every repeat, median, spread ((max - min) / median), the ratios to a, the time of the
 dominant kernel alone, and whether b's output equals a's.  --leg a|b|c|d runs ONE leg once without the timing (for a kernel trace).
+
+--parent-lib FILE loads the parent commit's libswt_hip.so beside this tree's and adds "against_parent": legs c and d through both
+libraries on the same table, alternating repeat after repeat in this one process, the ids compared first.  A leg passes when this
+tree's median does not exceed the parent's by more than the parent's own spread (max - min) in this run.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -38,12 +43,65 @@ def swap_dependent(merges, at):
     raise SystemExit("no dependent pair of merges")
 
 
+def against_parent(args, N, torch, bad, step, result, call_args):
+    """legs c and d through this tree's library and the parent's, alternating"""
+    d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, stream = call_args
+    parent = C.CDLL(os.path.abspath(args.parent_lib))
+    entries = {"c": "swt_bpe_encode_naive_dev", "d": "swt_bpe_encode_dev"}
+    for name in ("swt_init", "swt_last_error", "swt_bpe_table_create", "swt_bpe_table_destroy") + tuple(entries.values()):
+        fn = getattr(parent, name)
+        fn.restype, fn.argtypes = N.SIGNATURES[name]
+    if parent.swt_init(0):
+        raise RuntimeError("the parent's library does not initialise")
+    syms = type(bad._naive_syms)()
+    tri = np.array([x for l, r in bad.merges_list for x in (syms.intern(l), syms.intern(r), syms.intern(l + r))], dtype=np.uint32).reshape(-1, 3)
+    left, right, merged = (np.ascontiguousarray(tri[:, k]) for k in range(3))
+    h = C.c_void_p()
+    if parent.swt_bpe_table_create(N.ptr(left, N.u32p), N.ptr(right, N.u32p), N.ptr(merged, N.u32p), len(left), C.byref(h)):
+        raise RuntimeError("the parent's table: %s" % parent.swt_last_error().decode())
+
+    def parent_step(leg):
+        rc = getattr(parent, entries[leg])(h, d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_out.data_ptr(), d_out_off.data_ptr(),
+                                           d_ntok.data_ptr(), 0, stream)
+        if rc:
+            raise RuntimeError("%s (parent): %d %s" % (entries[leg], rc, parent.swt_last_error().decode()))
+
+    runs = {"c": lambda: step("c"), "c_parent": lambda: parent_step("c"), "d": lambda: step("d"), "d_parent": lambda: parent_step("d")}
+    for leg in "cd":  # the same ids from both libraries, before any timing
+        here = result(leg)
+        parent_step(leg)
+        torch.cuda.synchronize()
+        n = int(d_ntok.item())
+        if n != here[0].size or not np.array_equal(d_out[:n].cpu().numpy(), here[0]) or not np.array_equal(d_out_off.cpu().numpy(), here[1]):
+            raise AssertionError("leg %s: the ids differ from the parent's" % leg)
+    ms = {name: [] for name in runs}
+    for r in range(2 + args.repeats):  # two warm-up rounds
+        for name, fn in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            if r >= 2:
+                ms[name].append((time.perf_counter() - t0) / args.steps * 1e3)
+    parent.swt_bpe_table_destroy(h)
+    res = {"ids_equal": True}
+    for leg in "cd":
+        mine, theirs = ms[leg], ms[leg + "_parent"]
+        res[leg] = {"ms_per_step": [round(x, 4) for x in mine], "median": round(statistics.median(mine), 4),
+                    "parent_ms_per_step": [round(x, 4) for x in theirs], "parent_median": round(statistics.median(theirs), 4),
+                    "parent_spread_ms": round(max(theirs) - min(theirs), 4)}
+        res[leg]["passes"] = bool(statistics.median(mine) - statistics.median(theirs) <= max(theirs) - min(theirs))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--leg", choices="abcd", default=None)
+    ap.add_argument("--parent-lib", default=None)
     args = ap.parse_args()
     import torch
 
@@ -111,6 +169,8 @@ def main():
                             "mb_s": round(n_bytes / 1e3 / med, 1), "dominant_kernel_us": round(k_ms * 1e3 / max(launches, 1), 1)}
     a = out["legs"]["a"]["median"]
     out["ratio_to_a"] = {leg: round(out["legs"][leg]["median"] / a, 3) for leg in "bcd"}
+    if args.parent_lib:
+        out["against_parent"] = against_parent(args, N, torch, bad, step, result, (d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_ntok, stream))
     print(json.dumps(out))
     return 0
 
