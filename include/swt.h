@@ -1062,6 +1062,65 @@ int swt_mlm_predict_dev(const float *d_logits, uint64_t rows, uint32_t width, ui
                         const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id, float *d_out_top_logit,
                         int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info, void *stream);
 int swt_fill_capacity(uint32_t *floats_per_step, uint32_t *positions_per_workgroup, uint32_t *k_max, uint32_t *scan_cells);
+
+/* ------------------------------------------------------------------------------------------------
+ * Added and special tokens written in the text ("[MASK]", "[SEP]", "<user>", a domain term kept whole): one stage in front of the
+ * encoders, which finds them and hides them from the pre-tokenizer, and one behind, which splices them into the encoders'
+ * streams.  No encoder and no row kernel knows of them.  The reference has nothing of the sort; the `tokenizers` wheel calls it
+ * the added vocabulary.  tests/added_cases.py holds these semantics as plain Python.
+ *
+ * PATTERNS.  A handle holds n patterns (1 .. 4096), pattern k the bytes [pat_off[k], pat_off[k + 1]) of pat_bytes: 1 .. 64 bytes
+ * of strict UTF-8 -- no surrogate, no code point past U+FFFF, no U+0000, no code point of class SWT_CLS_BERT_WS -- and no
+ * pattern twice; anything else is SWT_ERR_INVALID, swt_last_error saying why.  The caller lowercases: the patterns are matched
+ * against the text the encoders see (the lowercased UTF-8 of the callers).  swt_added_create needs no device; the tables go up
+ * with the first find.  The handle keeps a byte trie with a table of the root's children by first byte in front (the
+ * first-byte reject): the work of a text position is bounded by the longest pattern, not by the number of patterns
+ * (csrc/swt_added.h, where the lookup "the longest pattern that matches here" is one function for host and device).
+ *
+ * 1. swt_added_find: over the texts [sent_off[s], sent_off[s + 1]) of `text`.
+ *   THE MATCHES of a text: among the patterns that match at a byte position the longest wins; scanning from the left, a match
+ *   is taken at the first position that has one and does not lie inside the match before it, and the scan goes on at the
+ *   match's end: leftmost-longest, non-overlapping.  A match never crosses a text's end.  Matches may lie inside a word.
+ *   out_text (n_bytes, a buffer of its own): the text with every code point of every match overwritten by a whitespace code
+ *   point of the same UTF-8 length -- U+0020, U+00A0, U+2003 -- so that the byte and code-point offsets of everything else stay
+ *   what they were; every other byte is a copy.
+ *   m_off (uint64[n_sent + 1]): the matches of text s are [m_off[s], m_off[s + 1]), in text order.  m_pat (uint32): the pattern.
+ *   m_span (uint32[2] per match): the match's (start, end) in code points inside its text, the unit of SWT_SPAN_CODEPOINTS; a
+ *   code point is a byte that is no continuation byte (10xxxxxx), which on well-formed UTF-8 is the count of the span calls.
+ *   info[3] (required): matches, texts with a match, bytes blanked.
+ *   SIZES.  A match takes a byte at least, so a call has no more matches than bytes: the `_dev` form takes m_pat of n_bytes and
+ *   m_span of 2 * n_bytes elements and needs no plan call.  Between its kernels the matches stand in a grow-only workspace of
+ *   the handle (12 bytes per text byte), as swt_token_spans_dev keeps one: no two calls on one handle at once on different
+ *   streams; the counts are scanned in the workspace of the plans.  The host form takes m_cap, the matches m_pat and m_span
+ *   have room for; with more matches it returns SWT_ERR_CAPACITY, out_text, m_off and info written.
+ *
+ * 2. swt_added_splice: the matches into the four streams of a span call over the blanked text (ids, tok_off, spans in code
+ * points, word).  With j = the matches of its text that start before a token's span, the token moves j slots up and its word
+ * index grows by j; with i = the tokens of its text that start before a match, match k of the text takes slot i + k of the
+ * text's new run, its span is m_span, its id added_base + m_pat (never flagged with SWT_BPE_CONT), and it is a word of its own:
+ * the word after that of the token before it, the first where there is none, plus k.  out_tok_off[s] = tok_off[s] + m_off[s].
+ * The outputs are arrays of their own with room for tok_off[n_sent] + m_off[n_sent] tokens, which is no more than n_bytes.
+ * Spans that do not ascend inside a text give an arrangement that is not defined, inside the text's own run.
+ *
+ * The `_dev` forms take device pointers, enqueue on the stream and do not synchronise.  n_sent == 0, and for 1. n_bytes == 0,
+ * succeed with the offsets and info zeroed.  Fewer than 2^32 texts, each of fewer than 2^32 bytes: the host form refuses a longer
+ * one, the `_dev` form takes it for an empty text.
+ * swt_added_capacity: the bytes of one step of a wavefront's walk through a text, the bytes of halo staged behind a step (a match
+ * may straddle a step), the bytes of one tile, the greatest number of patterns and of bytes of a pattern (csrc/swt_added.hip). */
+typedef struct swt_added swt_added;
+int swt_added_create(const uint8_t *pat_bytes, const uint64_t *pat_off, uint32_t n, swt_added **out);
+void swt_added_destroy(swt_added *h);
+int swt_added_find(swt_added *h, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint8_t *out_text, uint64_t *m_off,
+                   uint32_t *m_pat, uint32_t *m_span, uint64_t m_cap, uint64_t *info);
+int swt_added_find_dev(swt_added *h, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, uint8_t *d_out_text,
+                       uint64_t *d_m_off, uint32_t *d_m_pat, uint32_t *d_m_span, uint64_t *d_info, void *stream);
+int swt_added_splice(const uint32_t *ids, const uint64_t *tok_off, const uint32_t *spans, const uint32_t *word, uint64_t n_sent,
+                     const uint64_t *m_off, const uint32_t *m_pat, const uint32_t *m_span, uint32_t added_base, uint32_t *out_ids,
+                     uint64_t *out_tok_off, uint32_t *out_spans, uint32_t *out_word);
+int swt_added_splice_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, const uint32_t *d_spans, const uint32_t *d_word, uint64_t n_sent,
+                         const uint64_t *d_m_off, const uint32_t *d_m_pat, const uint32_t *d_m_span, uint32_t added_base, uint32_t *d_out_ids,
+                         uint64_t *d_out_tok_off, uint32_t *d_out_spans, uint32_t *d_out_word, void *stream);
+int swt_added_capacity(uint32_t *step_bytes, uint32_t *halo_bytes, uint32_t *tile_bytes, uint32_t *max_patterns, uint32_t *max_pattern_bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libswt_hip.so")
-SOURCES = ["swt_core.hip", "swt_tile.hip", "swt_dedup.hip", "swt_bpe_encode.hip", "swt_wp.hip", "swt_words.hip", "swt_bpe_train.hip", "swt_dist.hip", "swt_lower.hip", "swt_metrics.hip", "swt_spans.hip", "swt_batch.hip", "swt_pack.hip", "swt_mlm.hip", "swt_decode.hip", "swt_labels.hip", "swt_tags.hip", "swt_fill.hip"]
-HEADERS = ["swt_common.h", "swt_philox.h", "swt_tile.h", "swt_tilemap.h", "swt_bpe_narrow.h", "swt_dedup.h", "swt_words.h", "swt_train.h", "swt_batch.h", "swt_rows.h", "swt_labels.h", "unicode_classes.inc", "unicode_lower.inc", os.path.join("..", "..", "include", "swt.h")]
+SOURCES = ["swt_core.hip", "swt_tile.hip", "swt_dedup.hip", "swt_bpe_encode.hip", "swt_wp.hip", "swt_words.hip", "swt_bpe_train.hip", "swt_dist.hip", "swt_lower.hip", "swt_metrics.hip", "swt_spans.hip", "swt_batch.hip", "swt_pack.hip", "swt_mlm.hip", "swt_decode.hip", "swt_labels.hip", "swt_tags.hip", "swt_fill.hip", "swt_added.hip"]
+HEADERS = ["swt_common.h", "swt_philox.h", "swt_tile.h", "swt_tilemap.h", "swt_bpe_narrow.h", "swt_dedup.h", "swt_words.h", "swt_train.h", "swt_batch.h", "swt_rows.h", "swt_labels.h", "swt_added.h", "unicode_classes.inc", "unicode_lower.inc", os.path.join("..", "..", "include", "swt.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # diagnostic builds (tools/ only): SWT_EXTRA_FLAGS="-DSWT_STAMPS"; the flags are part of the build stamp
 FLAGS += os.environ.get("SWT_EXTRA_FLAGS", "").split()

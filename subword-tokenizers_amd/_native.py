@@ -208,6 +208,13 @@ SIGNATURES = {
     "swt_mlm_predict_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                       C.c_uint32] + [C.c_void_p] * 8),
     "swt_fill_capacity": (C.c_int, [u32p, u32p, u32p, u32p]),
+    "swt_added_create": (C.c_int, [u8p, u64p, C.c_uint32, vpp]),
+    "swt_added_destroy": (None, [C.c_void_p]),
+    "swt_added_find": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u8p, u64p, u32p, u32p, C.c_uint64, u64p]),
+    "swt_added_find_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
+    "swt_added_splice": (C.c_int, [u32p, u64p, u32p, u32p, C.c_uint64, u64p, u32p, u32p, C.c_uint32, u32p, u64p, u32p, u32p]),
+    "swt_added_splice_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 5),
+    "swt_added_capacity": (C.c_int, [u32p] * 5),
 }
 
 
@@ -1112,6 +1119,70 @@ def mlm_predict(logits, pos, labels=None, k=0, lse=True, info=True):
     check(lib().swt_mlm_predict(_at(logits), rows, width, n_vocab, _at(pos), n, _at(labels), flags, k,
                                 *[_at(out[name]) for name, _, _ in FILL_OUT], _at(out["info"])))
     return out
+
+
+ADDED_COUNTS = 3  # the entries of info of swt_added_find: matches, texts with a match, bytes blanked
+
+
+def added_capacity():
+    """-> (step_bytes, halo_bytes, tile_bytes, max_patterns, max_pattern_bytes): the bytes of one step of a wavefront's walk
+    through a text, the halo staged behind a step, the bytes of a tile, the limits of a handle (csrc/swt_added.hip)"""
+    v = [C.c_uint32() for _ in range(5)]
+    check(lib().swt_added_capacity(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+class AddedPatterns:
+    """The patterns of the added tokens (swt_added): `patterns` are bytes objects, lowercased UTF-8.  Needs no device until the
+    first find."""
+
+    def __init__(self, patterns):
+        self.n = len(patterns)
+        blob = np.frombuffer(b"".join(patterns) + b"\0", dtype=np.uint8)
+        off = np.zeros(self.n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(p) for p in patterns], dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib().swt_added_create(ptr(blob, u8p), ptr(off, u64p), self.n, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.swt_added_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def find(self, text_u8, sent_off):
+        """host buffers in -> (blanked text uint8, m_off uint64[n + 1], m_pat uint32[m], m_span uint32[m, 2], info uint64[3])"""
+        n_sent, n_bytes = int(sent_off.size - 1), int(sent_off[-1]) if sent_off.size else 0
+        text_u8, sent_off = np.ascontiguousarray(text_u8, dtype=np.uint8), np.ascontiguousarray(sent_off, dtype=np.uint64)
+        blank, m_off = np.zeros(max(n_bytes, 1), dtype=np.uint8), np.zeros(n_sent + 1, dtype=np.uint64)
+        m_pat, m_span = np.zeros(max(n_bytes, 1), dtype=np.uint32), np.zeros((max(n_bytes, 1), 2), dtype=np.uint32)
+        info = np.zeros(ADDED_COUNTS, dtype=np.uint64)
+        check(lib().swt_added_find(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, ptr(blank, u8p), ptr(m_off, u64p), ptr(m_pat, u32p),
+                                   ptr(m_span, u32p), n_bytes, ptr(info, u64p)))
+        m = int(info[0])
+        return blank[:n_bytes], m_off, m_pat[:m], m_span[:m], info
+
+    def find_dev(self, d_text, n_bytes, d_off, n_sent, d_out_text, d_m_off, d_m_pat, d_m_span, d_info, stream=0):
+        """device pointers (ints) in; enqueues on `stream` and returns"""
+        check(lib().swt_added_find_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out_text, d_m_off, d_m_pat, d_m_span, d_info, stream))
+
+
+def added_splice(ids, tok_off, spans, word, m_off, m_pat, m_span, added_base):
+    """The matches of AddedPatterns.find into the streams of a span call over the blanked text (swt_added_splice)
+    -> (ids uint32, tok_off uint64[n + 1], spans uint32[n, 2], word uint32[n])"""
+    ids, word, m_pat = (np.ascontiguousarray(a, dtype=np.uint32) for a in (ids, word, m_pat))
+    spans, m_span = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 2) for a in (spans, m_span))
+    tok_off, m_off = np.ascontiguousarray(tok_off, dtype=np.uint64), np.ascontiguousarray(m_off, dtype=np.uint64)
+    n_sent = int(tok_off.size - 1)
+    n = int(ids.size + m_pat.size)
+    out_ids, out_off = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(n_sent + 1, dtype=np.uint64)
+    out_spans, out_word = np.zeros((max(n, 1), 2), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    check(lib().swt_added_splice(ptr(ids, u32p), ptr(tok_off, u64p), ptr(spans, u32p), ptr(word, u32p), n_sent, ptr(m_off, u64p),
+                                 ptr(m_pat, u32p), ptr(m_span, u32p), int(added_base), ptr(out_ids, u32p), ptr(out_off, u64p),
+                                 ptr(out_spans, u32p), ptr(out_word, u32p)))
+    return out_ids[:n], out_off, out_spans[:n], out_word[:n]
 
 
 def bpe_length_table(strings):

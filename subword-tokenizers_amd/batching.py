@@ -37,14 +37,18 @@ class Vocabulary:
         self.d_mlm = None  # (device, cls_tab, rand_ids) as torch tensors, made by the first device call of mask_tokens
         self._decode = None
         self.d_decode = None  # (device, tok_bytes, tok_off, tok_flags) as torch tensors, made by the first device call of decode_batch
+        # added tokens (with_added): the encoder-side id of the first, the dense id of each, the strings of the special and of
+        # the ordinary ones
+        self.added_base, self.added_dense, self.added_special, self.added_ordinary = None, (), frozenset(), frozenset()
 
     @property
     def cls_tab(self):
-        """uint8 per dense id: 0 starts a word, 1 continues one ('##' and more), 2 is never masked (the specials and [MASK])"""
+        """uint8 per dense id: 0 starts a word, 1 continues one ('##' and more), 2 is never masked (the specials, [MASK] and
+        the special added tokens); an ordinary added token that was appended starts a word, one the vocabulary held keeps its class"""
         if self._cls_tab is None:
-            never = set(SPECIALS) | {MASK}
-            self._cls_tab = np.fromiter((2 if t in never else 1 if len(t) > 2 and t.startswith("##") else 0 for t in self.tokens),
-                                        dtype=np.uint8, count=len(self.tokens))
+            never, word = set(SPECIALS) | {MASK} | self.added_special, self.added_ordinary
+            self._cls_tab = np.fromiter((2 if t in never else 0 if t in word else 1 if len(t) > 2 and t.startswith("##") else 0
+                                         for t in self.tokens), dtype=np.uint8, count=len(self.tokens))
         return self._cls_tab
 
     @property
@@ -66,7 +70,9 @@ class Vocabulary:
             if total >= 1 << 23:
                 raise ValueError("decode: the vocabulary's tokens take %d bytes, swt_decode_* takes fewer than 2^23" % total)
             off[1:] = np.cumsum([len(b) for b in raw], dtype=np.uint64)
-            flags = np.fromiter((_decode_flags(t) for t in tokens), dtype=np.uint8, count=len(tokens))
+            special = self.added_special
+            flags = np.fromiter((_decode_flags(t) | (N.TOK_SPECIAL if t in special else 0) for t in tokens), dtype=np.uint8,
+                                count=len(tokens))
             self._decode = (np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8), off, flags, len(tokens))
         return self._decode
 
@@ -132,6 +138,66 @@ def wp_vocabulary(sorted_tokens):
     n = len(sorted_tokens)
     cmap = np.concatenate([np.arange(n, dtype=np.uint32), np.array([index["[UNK]"], index["[UNK]"], N.BATCH_NONE], dtype=np.uint32)])
     return Vocabulary(tokens, index, cmap, n + 3, False)
+
+
+def with_added(voc, added):
+    """`voc` (of bpe_vocabulary / wp_vocabulary) with the added tokens `added`, a list of (content, special), behind it: a new
+    Vocabulary in which no dense id of `voc` has moved.  The string of an added token -- content for a special one,
+    content.lower() for an ordinary one -- takes its index where `voc` holds the string, mask_id where it is "[MASK]", and else
+    the next free id from max(len(voc.tokens), voc.mask_id + 1) on, in the order of addition; once an id is handed out, the
+    token list runs to the highest id, with "[MASK]" at its reserved slot.  The encoder-side id of added token k is added_base
+    + k, past every id of the encoder, and the map grows by those entries in the convention it has (flagged or plain)."""
+    if not added:
+        return voc
+    tokens, index = list(voc.tokens), dict(voc.index)
+    dense, special, ordinary = [], set(), set()
+    for content, is_special in added:
+        s = content if is_special else content.lower()
+        if is_special:
+            special.add(s)
+        elif s not in voc.index:  # an ordinary token the vocabulary holds keeps the class it has there ('##x' goes on continuing)
+            ordinary.add(s)
+        if s in index:
+            d = index[s]
+        elif s == MASK:
+            d = voc.mask_id
+        else:
+            if len(tokens) == voc.mask_id:  # the reserved slot is spelled before anything goes behind it
+                index[MASK] = len(tokens)
+                tokens.append(MASK)
+            d = index[s] = len(tokens)
+            tokens.append(s)
+        dense.append(d)
+    dense = np.array(dense, dtype=np.uint32)
+    if voc.flagged:  # [plain | flagged], each n_map long; n_map itself is the encoder's id of a symbol it cannot spell
+        base = voc.n_map + 1
+        n_map = base + len(dense)
+        cmap = np.full(2 * n_map, N.BATCH_NONE, dtype=np.uint32)
+        cmap[:voc.n_map], cmap[n_map:n_map + voc.n_map] = voc.cmap[:voc.n_map], voc.cmap[voc.n_map:]
+        cmap[base:n_map] = dense
+    else:
+        base, n_map = voc.n_map, voc.n_map + len(dense)
+        cmap = np.concatenate([voc.cmap, dense])
+    out = Vocabulary(tokens, index, cmap, n_map, voc.flagged)
+    assert out.mask_id == voc.mask_id and out.special == voc.special
+    out.added_base, out.added_dense, out.added_special, out.added_ordinary = base, dense, frozenset(special), frozenset(ordinary - special)
+    return out
+
+
+def check_added_token(token, n_so_far):
+    """the ValueError of add_tokens for a token that cannot be added (include/swt.h states the limits), naming it"""
+    if not isinstance(token, str):
+        raise TypeError("an added token is a string")
+    if token == "":
+        raise ValueError("added token %r: the empty string" % token)
+    if any(N.class_of(ord(ch)) & N.CLS_BERT_WS or ch.isspace() for ch in token + token.lower()):
+        raise ValueError("added token %r: whitespace inside" % token)
+    if any(ord(ch) > 0xFFFF or ord(ch) == 0 or 0xD800 <= ord(ch) < 0xE000 for ch in token + token.lower()):
+        raise ValueError("added token %r: a code point past U+FFFF, a surrogate or U+0000" % token)
+    if len(token.lower().encode("utf-8")) > 64:
+        raise ValueError("added token %r: its pattern takes more than 64 bytes" % token)
+    if n_so_far >= 4096:
+        raise ValueError("added token %r: more than 4096 added tokens" % token)
 
 
 def _width(longest, n_special, max_length, padding, multiple):
@@ -207,11 +273,25 @@ def _pair_result(out, overflowing, offsets, token_types, special_mask):
 
 def _encode_host(tok, texts, offsets, dropout=None):
     """one encode through the host forms -> (ids, tok_off, spans, word); spans and word are None without offsets"""
+    if tok._added:
+        return _encode_host_added(tok, texts, offsets, dropout)
     if offsets:
         got = tok._batch_encode_spans(texts) if dropout is None else tok._batch_encode_spans(texts, dropout)
         return got[0], got[1], got[-2], got[-1]
     got = tok._batch_encode_ids(texts, dropout)
     return got[0], got[1], None, None
+
+
+def _encode_host_added(tok, texts, offsets, dropout=None):
+    """_encode_host of a tokenizer with added tokens: the texts are packed and lowercased once, the added tokens found and
+    blanked (swt_added_find), the blanked text encoded by the class's span call -- the spans are needed whether or not the caller
+    wants offsets -- and the matches spliced into its streams (swt_added_splice)"""
+    patterns, voc = tok._added_patterns(), tok._batch_vocabulary()
+    text, off = N.pack_and_lower(texts)
+    blank, m_off, m_pat, m_span, _ = patterns.find(text, off)
+    got = tok._batch_encode_spans_packed(blank, off, texts, dropout)
+    ids, tok_off, spans, word = N.added_splice(got[0], got[1], got[-2], got[-1], m_off, m_pat, m_span, voc.added_base)
+    return (ids, tok_off, spans, word) if offsets else (ids, tok_off, None, None)
 
 
 def _encode_pairs(tok, voc, texts, text_pairs, max_length, stride, padding, multiple, add_special_tokens, padding_side, overflowing, offsets,
@@ -317,7 +397,7 @@ def _pack_result(out, slot, tok_off, spec, mode, info, plan_info, xp):
 
 
 def _pack_host(tok, voc, texts, spec, mode, dropout=None):
-    ids, tok_off = tok._batch_encode_ids(texts, dropout)[:2]
+    ids, tok_off = _encode_host(tok, texts, False, dropout)[:2]
     tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
     slot, row_first, plan_info = N.pack_plan(tok_off, spec, mode)
     out = N.pack_rows(ids, tok_off, spec, mode, slot, row_first, voc.cmap, voc.n_map, voc.flagged, rows_cap=int(plan_info[0]))
@@ -341,8 +421,10 @@ def _encode_on_device(tok, voc, texts, offsets=False, dropout=None):
 
     text, off = N.pack_utf8([t.lower() for t in texts])
     n_bytes, n_sent = int(text.size), len(texts)
+    added = tok._added_patterns() if tok._added else None  # with added tokens the span form runs whether or not offsets are wanted
+    spans = offsets or added is not None
     d_ids, d_tok_off = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64)
-    d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, offsets), empty(n_bytes + 64, torch.int32, offsets)
+    d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, spans), empty(n_bytes + 64, torch.int32, spans)
     checks = []
     if n_bytes == 0:
         d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
@@ -350,12 +432,27 @@ def _encode_on_device(tok, voc, texts, offsets=False, dropout=None):
         d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
         d_off = torch.from_numpy(off.view(np.int64)).to(dev)
         d_ntok = torch.zeros(1, dtype=torch.int64, device=dev)
+        if added is not None:  # the added tokens found and blanked in a copy of the text, which the encoder then reads
+            d_seen = empty(n_bytes + 64, torch.uint8)
+            d_seen[n_bytes:].zero_()
+            d_m_off, d_m_pat, d_m_span = empty(n_sent + 1, torch.int64), empty(n_bytes, torch.int32), empty(2 * n_bytes, torch.int32)
+            d_m_info = empty(4, torch.int64)
+            added.find_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_seen.data_ptr(), d_m_off.data_ptr(), d_m_pat.data_ptr(),
+                           d_m_span.data_ptr(), d_m_info.data_ptr(), stream)
+            d_text = d_seen
         checks = tok._batch_encode_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
-                                       d_ntok.data_ptr(), d_spans.data_ptr() if offsets else None, d_word.data_ptr() if offsets else None,
+                                       d_ntok.data_ptr(), d_spans.data_ptr() if spans else None, d_word.data_ptr() if spans else None,
                                        stream, empty, **({} if dropout is None else {"dropout": dropout}))
+        if added is not None:  # and spliced into the encoder's streams: a text has no more tokens and matches than bytes
+            before = d_ids, d_tok_off, d_spans, d_word
+            d_ids, d_tok_off = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64)
+            d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32), empty(n_bytes + 64, torch.int32)
+            N.check(N.lib().swt_added_splice_dev(*(a.data_ptr() for a in before), n_sent, d_m_off.data_ptr(), d_m_pat.data_ptr(),
+                                                 d_m_span.data_ptr(), voc.added_base, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                                 d_spans.data_ptr(), d_word.data_ptr(), stream))
     if voc.d_cmap is None or voc.d_cmap.device != dev:
         voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
-    return Encoded(stream, empty, d_ids, d_tok_off, d_spans, d_word, checks)
+    return Encoded(stream, empty, d_ids, d_tok_off, d_spans if offsets else None, d_word if offsets else None, checks)
 
 
 def _pack_device(tok, voc, texts, spec, mode, dropout=None):

@@ -50,6 +50,9 @@ class SubwordTokenizer:
         if tokenizer is not None and not _is_bert_pretokenizer(tokenizer):
             raise ValueError("only a BertPreTokenizer-backed tokenizer (the reference's default, cli.py:85) is supported")
         self.tokenizer = tokenizer
+        self._added: List[Tuple[str, bool]] = []  # the added tokens (content, special) in the order of addition
+        self._added_gen = 0  # counts the changes of the list: part of the vocabulary's cache key
+        self._added_handle: Optional[N.AddedPatterns] = None
 
     # -- utils.py:15-29
     def preprocessing(self, corpus: List[str]) -> List[List[Tuple[str, Tuple[int, int]]]]:
@@ -136,6 +139,69 @@ class SubwordTokenizer:
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
                                      return_special_tokens_mask, packing, drop_last, mlm, self._enc.channel(dropout, maxmatch_dropout))
+
+    # -- added and special tokens written in the text (not in the reference; include/swt.h)
+    def add_tokens(self, tokens: List[str], special: bool = False) -> int:
+        """Registers strings that encode_batch keeps whole wherever they stand in a text -- "<user>", a domain term; with
+        special=True (add_special_tokens) a control token such as "[MASK]" or "[SEP]".  They are found on the device in the
+        lowercased text the encoders see (swt_added_find: leftmost-longest, not overlapping, also inside a word), hidden from the
+        encoder and spliced into its output (swt_added_splice), each a word of its own.  The text is lowercased before anything
+        else (utils.py:27), so a token is recognised in any case: "[mask]" in a text is "[MASK]".
+        The dense id of a token -- its string is `content` for a special one, content.lower() for an ordinary one -- is the
+        string's index where the vocabulary holds it (a typed "[SEP]" is [SEP]), mask_id() for "[MASK]", and else the next free id
+        from max(len(vocab_list()), mask_id() + 1) on; no other dense id moves and vocab_list() grows by the appended ones.  A
+        special token is never masked nor a random replacement (mask_tokens) and is skipped by decode_batch(...,
+        skip_special_tokens=True); an ordinary one is a word like any other.
+        -> the number of tokens newly added; one whose lowercased form is registered already is not new.  ValueError, naming the
+        token: the empty string, whitespace inside, a code point past U+FFFF, a lowercased form of more than 64 bytes, more than
+        4096 tokens; on a FastWP whose vocabulary holds a token with whitespace, any token.  The list survives train,
+        load_resources and reset (the dense ids follow the new vocabulary); save_resources does not write it: re-add after loading.
+        tokenize, tokenize_batch, encode_ids_batch, encode_spans_batch and fast_encode_spans_batch keep the reference's behaviour
+        and do not see added tokens."""
+        if isinstance(tokens, str) or not isinstance(tokens, (list, tuple)):
+            raise TypeError("tokens: a list of strings")
+        self._refuse_added()
+        staged, have, new = list(self._added), {content.lower() for content, _ in self._added}, 0
+        for token in tokens:
+            batching.check_added_token(token, 0)
+            if token.lower() in have:
+                continue
+            batching.check_added_token(token, len(staged))
+            staged.append((token, bool(special)))
+            have.add(token.lower())
+            new += 1
+        if new:
+            self._set_added(staged)
+        return new
+
+    def add_special_tokens(self, tokens: List[str]) -> int:
+        """add_tokens(tokens, special=True)"""
+        return self.add_tokens(tokens, special=True)
+
+    def added_tokens(self) -> List[Tuple[str, bool]]:
+        """[(content, special)] in the order of addition"""
+        return list(self._added)
+
+    def clear_added_tokens(self) -> None:
+        """forgets every added token: encode_batch and vocab_list() are what they were before the first add_tokens"""
+        if self._added:
+            self._set_added([])
+
+    def _set_added(self, added) -> None:
+        self._added, self._added_gen = added, self._added_gen + 1
+        if self._added_handle is not None:
+            self._added_handle.close()
+        self._added_handle = None
+
+    def _added_patterns(self) -> N.AddedPatterns:
+        """the device handle of the list's patterns, content.lower() as UTF-8, built on first use"""
+        self._refuse_added()
+        if self._added_handle is None:
+            self._added_handle = N.AddedPatterns([content.lower().encode("utf-8") for content, _ in self._added])
+        return self._added_handle
+
+    def _refuse_added(self) -> None:
+        """a class that cannot take added tokens over its present vocabulary raises ValueError here (FastWP)"""
 
     def mask_id(self) -> int:
         """The dense id of "[MASK]": its index where the vocabulary holds the string, else len(vocab_list()), one past the end,
@@ -297,6 +363,10 @@ class SubwordTokenizer:
     def _batch_encode_spans(self, texts, dropout=None):
         return self.encode_spans_batch(texts) if dropout is None else _encode_spans(self._enc, texts, dropout)
 
+    def _batch_encode_spans_packed(self, text, off, texts, dropout=None):
+        """_batch_encode_spans over a packed, lowercased text the caller has made (and may have blanked); texts: for the errors"""
+        return _encode_spans_packed(self._enc, text, off, texts, self._enc.draw(dropout))
+
     def _batch_encode_dev(self, *args, dropout=None):
         return _encode_dev(self._enc, *args, dropout=dropout)
 
@@ -427,12 +497,17 @@ class _Encoder:
         return self._cached("lengths", (lambda sp: N.bpe_length_table(sp.strings)) if self.flagged else N.wp_length_table, spelling)
 
     def vocabulary(self):
-        """the dense ids of batching.py over the live handle's ids"""
+        """the dense ids of batching.py over the live handle's ids, the added tokens behind them"""
         self.handle()
         if not self.flagged:
-            return self._cached("vocabulary", batching.wp_vocabulary)
-        merges = self._tok.merges_list
-        return self._cached("vocabulary", lambda sp: batching.bpe_vocabulary(merges, sp), None, len(merges))
+            base = self._cached("base_vocabulary", batching.wp_vocabulary)
+        else:
+            merges = self._tok.merges_list
+            base = self._cached("base_vocabulary", lambda sp: batching.bpe_vocabulary(merges, sp), None, len(merges))
+        added = self._tok._added
+        if not added:
+            return base
+        return self._cached("vocabulary", lambda sp: batching.with_added(base, added), None, id(base), self._tok._added_gen)
 
 
 def _raise_flagged(enc: _Encoder, status, texts) -> None:
@@ -497,8 +572,12 @@ def _encode_spans(enc: _Encoder, texts, dropout=None):
     draw = enc.draw(dropout)
     if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
         raise TypeError("Text to tokenize must be a string.")
+    return _encode_spans_packed(enc, *N.pack_and_lower(texts), texts, draw)
+
+
+def _encode_spans_packed(enc: _Encoder, text, off, texts, draw=None):
+    """_encode_spans from the packed text on: `text` is lowercased UTF-8, `off` its offsets, `texts` what the errors quote"""
     handle = enc.handle()
-    text, off = N.pack_and_lower(texts)
     got = getattr(handle, enc.host)(text, off) if draw is None else getattr(handle, enc.drop_host)(text, off, draw)
     if enc.complain is not None:
         _raise_flagged(enc, got[2], texts)
@@ -715,7 +794,7 @@ class NaiveBPE(SubwordTokenizer):
                          maxmatch_dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
         over this object's own symbol table (decode_ids spells them).  dropout: None; anything else is FastBPE's (ValueError).
-        maxmatch_dropout: None; anything else is NaiveWP's (ValueError)."""
+        maxmatch_dropout: None; anything else is NaiveWP's (ValueError).  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
     def decode_ids(self, ids) -> List[str]:
@@ -723,7 +802,7 @@ class NaiveBPE(SubwordTokenizer):
 
     def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
                        maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
-        """[tokenize(t) for t in texts]"""
+        """[tokenize(t) for t in texts].  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout))
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
@@ -737,7 +816,7 @@ class NaiveBPE(SubwordTokenizer):
     def encode_spans_batch(self, texts: List[str]):
         """texts -> (ids, offsets, spans uint32[n, 2], word_ids uint32[n]): encode_ids_batch plus, per token, its (start, end) in
         code points of text.lower() -- preprocessing's convention (utils.py:27-29) -- and the index of its word in the sentence.
-        The text is packed once and sent to the device twice, for the encode and for swt_token_spans."""
+        The text is packed once and sent to the device twice, for the encode and for swt_token_spans.  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_spans(self._enc, texts)
 
     def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
@@ -831,7 +910,8 @@ class FastBPE(NaiveBPE):
         with probability p, so a text gets another segmentation per (seed, epoch) -- and the same one for the same (seed, epoch,
         index in `texts`), whatever the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain
         encode, p = 1 leaves every word as its characters.  ValueError: a probability outside [0, 1] or a NaN, a seed outside
-        [0, 2^64), an epoch outside [0, 2^32), an unknown key.  maxmatch_dropout: None; anything else is NaiveWP's (ValueError)."""
+        [0, 2^64), an epoch outside [0, 2^32), an unknown key.  maxmatch_dropout: None; anything else is NaiveWP's (ValueError).
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
     def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
@@ -1005,7 +1085,8 @@ class NaiveWP(SubwordTokenizer):
 
     # -- wordpiece.py:161-181
     def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
-        """maxmatch_dropout: as encode_ids_batch, on the device, `text` being sentence 0; None: the reference's walk, here"""
+        """maxmatch_dropout: as encode_ids_batch, on the device, `text` being sentence 0; None: the reference's walk, here.
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
         if maxmatch_dropout is not None:
@@ -1041,12 +1122,13 @@ class NaiveWP(SubwordTokenizer):
         gets another segmentation per (seed, epoch) -- and the same one for the same (seed, epoch, index in `texts`), whatever
         the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain encode, p = 1 leaves every word
         as its characters where each is a token in its position.  A word whose every match is dropped or missing is "[UNK]", and
-        the status of a text is that of the thinned walk: over an odd vocabulary it can depend on the draw.  Errors as dropout's."""
+        the status of a text is that of the thinned walk: over an odd vocabulary it can depend on the draw.  Errors as dropout's.
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
     def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
-        deviation: the reference hangs)."""
+        deviation: the reference hangs).  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout)
         _raise_flagged(self._enc, status, texts)
         return N.nested_lists(self._enc.names(), ids, off)
@@ -1060,7 +1142,8 @@ class NaiveWP(SubwordTokenizer):
         (start, end) in code points of text.lower() (utils.py:27-29; "[UNK]" spans its whole word) and the index of its word in
         the sentence.  A text on which the reference never returns raises as in tokenize_batch.  The text is packed once and sent
         to the device twice, for the encode and for swt_token_spans.  FastWP inherits this method unchanged: called on a FastWP
-        it answers with NaiveWP's tokens over the same vocabulary; FastWP's own tokens come from fast_encode_spans_batch."""
+        it answers with NaiveWP's tokens over the same vocabulary; FastWP's own tokens come from fast_encode_spans_batch.
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_spans(self._naive_enc, texts)
 
     def tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
@@ -1218,7 +1301,8 @@ class FastWP(NaiveWP):
     def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status.
         dropout: None; anything else is FastBPE's (ValueError).  maxmatch_dropout: None; anything else is NaiveWP's (ValueError:
-        this class walks failure links, not MaxMatch -- a NaiveWP over the same vocabulary gives this class's ids)."""
+        this class walks failure links, not MaxMatch -- a NaiveWP over the same vocabulary gives this class's ids).
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
 
     def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
@@ -1241,14 +1325,22 @@ class FastWP(NaiveWP):
         (start, end) in code points of text.lower() and the index of its segment among those of the sentence that emit a token
         (include/swt.h: a valid segment's tokens cover a prefix of it, "['UNK']" reaches to the next boundary, the '##' corner
         covers two).  A multi-token corner is one id (len(vocab) + 2) with the corner's span.  A text the reference does not
-        return from raises as in tokenize_batch.  One pack, one trip to the device."""
+        return from raises as in tokenize_batch.  One pack, one trip to the device.  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
             raise TypeError("Text to tokenize must be a string.")
-        trie = self._ensure_trie()
-        text, off = N.pack_and_lower(texts)
-        ids, tok_off, status, spans, word = trie.encode_spans(text, off, codepoints=True)
+        return self._batch_encode_spans_packed(*N.pack_and_lower(texts), texts)
+
+    def _batch_encode_spans_packed(self, text, off, texts, dropout=None):
+        self._enc.draw(dropout)  # (this class has none: anything but None raises)
+        ids, tok_off, status, spans, word = self._ensure_trie().encode_spans(text, off, codepoints=True)
         _raise_flagged(self._enc, status, texts)
         return ids, tok_off, status, spans, word
+
+    def _refuse_added(self) -> None:
+        # A token with whitespace inside is matched across the words of a text by this class's walk (wordpiece.py:233-270 runs
+        # over the whole text): the blanks that hide an added token would become part of such a match.
+        if self._trie is not None and self._enc._cached("ws_token", lambda sp: any(_class_of(ch) & N.CLS_BERT_WS for t in sp for ch in t)):
+            raise ValueError("FastWP: the vocabulary holds a token with whitespace inside, which added tokens do not go with")
 
     def fast_tokenize_with_offsets(self, text: str) -> List[Tuple[str, Tuple[int, int]]]:
         """[(token, (start, end)), ...]: FastWP.tokenize(text) with the code points of text.lower() every token covers; a
