@@ -1121,6 +1121,73 @@ int swt_added_splice_dev(const uint32_t *d_ids, const uint64_t *d_tok_off, const
                          const uint64_t *d_m_off, const uint32_t *d_m_pat, const uint32_t *d_m_span, uint32_t added_base, uint32_t *d_out_ids,
                          uint64_t *d_out_tok_off, uint32_t *d_out_spans, uint32_t *d_out_word, void *stream);
 int swt_added_capacity(uint32_t *step_bytes, uint32_t *halo_bytes, uint32_t *tile_bytes, uint32_t *max_patterns, uint32_t *max_pattern_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * The normalizer: what the `tokenizers` wheel's BertNormalizer does to a text before a BERT checkpoint's tokenizer splits it, on
+ * raw UTF-8 on the device, with the alignment of every output code point back to the text.  The reference only lowercases
+ * (utils.py:27); swt_utf8_lower rewrites in place what keeps its length and leaves the rest to the host.  This changes lengths
+ * and has no host part.  tests/normalizer_cases.py holds these semantics as plain Python.
+ *
+ * THE RULE.  Per code point c of the text, in this order, each step under its own flag:
+ *   1. SWT_NORMALIZE_CLEAN_TEXT: c is dropped if it is U+0000 or U+FFFD, or its general category begins with C (Cc, Cf, Cs, Co,
+ *      Cn) and it is not \t, \n or \r.  Else c becomes U+0020 if it is \t, \n or \r, or its category is Zs, Zl or Zp.
+ *   2. SWT_NORMALIZE_CHINESE_CHARS: c in BERT's fixed ideograph ranges -- 4E00-9FFF, 3400-4DBF, 20000-2A6DF, 2A700-2B73F,
+ *      2B740-2B81F, 2B820-2CEAF, F900-FAFF, 2F800-2FA1F -- becomes U+0020 c U+0020.
+ *   3. SWT_NORMALIZE_STRIP_ACCENTS: c becomes the code points of its canonical decomposition (NFD of c alone, a Hangul syllable's
+ *      jamo included) without those of category Mn; a c that is Mn itself vanishes.  Without the flag nothing is decomposed.
+ *   4. SWT_NORMALIZE_LOWERCASE: every resulting code point d becomes its lowercase, taken per code point: U+03A3 is always
+ *      U+03C3 (no final-sigma form), U+0130 without step 3 is U+0069 U+0307 (with it, U+0049's U+0069).
+ * The spaces of step 2 stand around whatever steps 3 and 4 make of c.  Categories, decompositions and lowercases are those of
+ * Unicode SWT_UNIDATA_VERSION (swt_unidata_version), generated by tools/gen_normalize_table.py into csrc/unicode_normalize.inc,
+ * which also states the longest expansion of one code point (swt_normalize_capacity).
+ * NOT reproduced: the canonical reordering of marks.  The wheel decomposes the whole string, which sorts neighbouring marks by
+ * combining class; here every code point is decomposed by itself, so marks that survive step 3 (categories Mc and Me) and are
+ * carried by different source code points keep the order the text has them in.
+ * Bytes that are not well-formed UTF-8 are copied through: a lead byte without all its continuation bytes (or 0xF8 and above, a
+ * value past U+10FFFF, or an overlong form such as C1 81) with the continuation bytes it has, as one code point; any other
+ * continuation byte as no code point.  The three bytes of a surrogate are generalised UTF-8 here as elsewhere in this library:
+ * they decode, and step 1 drops them as category Cs.
+ * A CODE POINT of the text, here as in the span calls, is a byte that is no continuation byte.
+ *
+ * THE ALIGNMENT.  Every output code point remembers the index of the source code point it came from, counted over the whole
+ * text; the spaces of step 2 point at their ideograph.  src_cp_off[s] is the index of sentence s's first code point, so
+ * out_align[out_cp_off[s] + k] - src_cp_off[s] is where code point k of the normalised sentence s stood in the original one.
+ *
+ * 1. swt_normalize_plan: one wavefront per tile of 1 KiB of text counts the tile's output bytes, output code points and source
+ *   code points; scans make bases of them.  info[3]: the bytes and the code points of the normalised text, the code points of
+ *   the source -- what the caller sizes out_text and out_align by.  sent_off is sorted and sent_off[n_sent] == n_bytes.
+ * 2. swt_normalize_rows: out_text, the normalised text; out_off (uint64[n_sent + 1]), where sentence s begins in it.  With
+ *   SWT_NORMALIZE_ALIGN also out_cp_off and src_cp_off (uint64[n_sent + 1]) and out_align (uint32 per output code point); without
+ *   it these three are not looked at.  The `_dev` form reads the bases the last swt_normalize_plan_dev left in a workspace of
+ *   the process: the same arguments, the same stream, no other plan in between -- else SWT_ERR_INVALID -- and it writes nothing
+ *   past text_cap bytes and align_cap code points.  The host form plans by itself and returns SWT_ERR_CAPACITY for outputs that
+ *   are too small, nothing written.
+ * 3. swt_normalize_spans: token spans over the normalised text (spans: uint32[2] per token in code points inside its sentence, as
+ *   the span calls leave them; tok_off: uint64[n_sent + 1]) become spans over the original, in place: [a, b) becomes
+ *   [align[a], align[b - 1] + 1) relative to the sentence, an empty span a = b = align[a], at the sentence's end its source's
+ *   length.  The `_dev` form covers the tokens below min(n_cap, d_tok_off[n_sent]).
+ *
+ * Fewer than 2^31 bytes and sentences per call (SWT_ERR_UNSUPPORTED).  The `_dev` forms take device pointers, enqueue on the
+ * stream and do not synchronise; no two plans at once on different streams.  n_bytes == 0 succeeds with the offsets and info
+ * zeroed.  swt_normalize_capacity: the bytes of a tile and of a lane, the most code points and bytes one code point becomes. */
+#define SWT_NORMALIZE_CLEAN_TEXT 1u
+#define SWT_NORMALIZE_CHINESE_CHARS 2u
+#define SWT_NORMALIZE_STRIP_ACCENTS 4u
+#define SWT_NORMALIZE_LOWERCASE 8u
+#define SWT_NORMALIZE_ALIGN 16u /* swt_normalize_rows: write out_cp_off, src_cp_off and out_align */
+int swt_normalize_plan(const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t flags, uint64_t *info);
+int swt_normalize_plan_dev(const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, uint32_t flags,
+                           uint64_t *d_info, void *stream);
+int swt_normalize_rows(const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t flags, uint8_t *out_text, uint64_t text_cap,
+                       uint64_t *out_off, uint64_t *out_cp_off, uint64_t *src_cp_off, uint32_t *out_align, uint64_t align_cap);
+int swt_normalize_rows_dev(const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, uint32_t flags,
+                           uint8_t *d_out_text, uint64_t text_cap, uint64_t *d_out_off, uint64_t *d_out_cp_off, uint64_t *d_src_cp_off,
+                           uint32_t *d_out_align, uint64_t align_cap, void *stream);
+int swt_normalize_spans(uint32_t *spans, const uint64_t *tok_off, uint64_t n_sent, const uint32_t *align, const uint64_t *cp_off,
+                        const uint64_t *src_cp_off);
+int swt_normalize_spans_dev(uint32_t *d_spans, uint64_t n_cap, const uint64_t *d_tok_off, uint64_t n_sent, const uint32_t *d_align,
+                            const uint64_t *d_cp_off, const uint64_t *d_src_cp_off, void *stream);
+int swt_normalize_capacity(uint32_t *tile_bytes, uint32_t *lane_bytes, uint32_t *max_cps, uint32_t *max_bytes);
 #ifdef __cplusplus
 }
 #endif

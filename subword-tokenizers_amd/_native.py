@@ -215,6 +215,14 @@ SIGNATURES = {
     "swt_added_splice": (C.c_int, [u32p, u64p, u32p, u32p, C.c_uint64, u64p, u32p, u32p, C.c_uint32, u32p, u64p, u32p, u32p]),
     "swt_added_splice_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 5),
     "swt_added_capacity": (C.c_int, [u32p] * 5),
+    "swt_normalize_plan": (C.c_int, [u8p, u64p, C.c_uint64, C.c_uint32, u64p]),
+    "swt_normalize_plan_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "swt_normalize_rows": (C.c_int, [u8p, u64p, C.c_uint64, C.c_uint32, u8p, C.c_uint64, u64p, u64p, u64p, u32p, C.c_uint64]),
+    "swt_normalize_rows_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64] +
+                               [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p]),
+    "swt_normalize_spans": (C.c_int, [u32p, u64p, C.c_uint64, u32p, u64p, u64p]),
+    "swt_normalize_spans_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "swt_normalize_capacity": (C.c_int, [u32p] * 4),
 }
 
 
@@ -1183,6 +1191,64 @@ def added_splice(ids, tok_off, spans, word, m_off, m_pat, m_span, added_base):
                                  ptr(m_pat, u32p), ptr(m_span, u32p), int(added_base), ptr(out_ids, u32p), ptr(out_off, u64p),
                                  ptr(out_spans, u32p), ptr(out_word, u32p)))
     return out_ids[:n], out_off, out_spans[:n], out_word[:n]
+
+
+# the normalizer (swt_normalize_*): the flags of a setting, the host form and the device form
+NORMALIZE_CLEAN_TEXT, NORMALIZE_CHINESE_CHARS, NORMALIZE_STRIP_ACCENTS, NORMALIZE_LOWERCASE, NORMALIZE_ALIGN = 1, 2, 4, 8, 16
+NORMALIZE_KEYS = (("clean_text", NORMALIZE_CLEAN_TEXT), ("handle_chinese_chars", NORMALIZE_CHINESE_CHARS),
+                  ("strip_accents", NORMALIZE_STRIP_ACCENTS), ("lowercase", NORMALIZE_LOWERCASE))
+
+
+def normalize_capacity():
+    """-> (tile_bytes, lane_bytes, max_cps, max_bytes): the bytes of a tile and of a lane, the most code points and bytes one
+    code point becomes (csrc/swt_normalize.hip, csrc/unicode_normalize.inc)"""
+    v = [C.c_uint32() for _ in range(4)]
+    check(lib().swt_normalize_capacity(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def normalize(text_u8, sent_off, flags, align=False):
+    """host buffers in -> (normalised text uint8, off uint64[n + 1], cp_off, src_cp_off, align uint32); the last three are None
+    without align (swt_normalize_plan, swt_normalize_rows)"""
+    text_u8, sent_off = np.ascontiguousarray(text_u8, dtype=np.uint8), np.ascontiguousarray(sent_off, dtype=np.uint64)
+    n_sent = int(sent_off.size - 1)
+    info = np.zeros(3, dtype=np.uint64)
+    check(lib().swt_normalize_plan(ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, flags, ptr(info, u64p)))
+    n_bytes, n_cps = int(info[0]), int(info[1])
+    out, off = np.zeros(max(n_bytes, 1), dtype=np.uint8), np.zeros(n_sent + 1, dtype=np.uint64)
+    cp_off, src_off, al = ((np.zeros(n_sent + 1, dtype=np.uint64), np.zeros(n_sent + 1, dtype=np.uint64), np.zeros(max(n_cps, 1), dtype=np.uint32))
+                           if align else (None, None, None))
+    check(lib().swt_normalize_rows(ptr(text_u8, u8p), ptr(sent_off, u64p), n_sent, flags | (NORMALIZE_ALIGN if align else 0), ptr(out, u8p),
+                                   n_bytes, ptr(off, u64p), *((ptr(cp_off, u64p), ptr(src_off, u64p), ptr(al, u32p), n_cps) if align
+                                                              else (None, None, None, 0))))
+    return out[:n_bytes], off, cp_off, src_off, al[:n_cps] if align else None
+
+
+def normalize_dev(d_text, n_bytes, d_off, n_sent, flags, align, empty, stream=0):
+    """device tensors in (text uint8 with n_bytes bytes, off int64[n_sent + 1]); plan, the one read-back of the totals, rows into
+    tensors of empty(shape, dtype) -> (text uint8 with 64 zero bytes behind it, n_bytes, off, cp_off, src_cp_off, align); the
+    last three None without align"""
+    import torch
+    d_info = empty(3, torch.int64)
+    check(lib().swt_normalize_plan_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, flags, d_info.data_ptr(), stream))
+    out_bytes, out_cps = (int(x) for x in d_info[:2].cpu())
+    d_out, d_out_off = empty(out_bytes + 64, torch.uint8), empty(n_sent + 1, torch.int64)
+    d_out[out_bytes:].zero_()
+    d_cp_off, d_src_off, d_align = ((empty(n_sent + 1, torch.int64), empty(n_sent + 1, torch.int64), empty(out_cps + 1, torch.int32)) if align
+                                    else (None, None, None))
+    check(lib().swt_normalize_rows_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, flags | (NORMALIZE_ALIGN if align else 0),
+                                       d_out.data_ptr(), out_bytes, d_out_off.data_ptr(), *((d_cp_off.data_ptr(), d_src_off.data_ptr(),
+                                       d_align.data_ptr(), out_cps) if align else (None, None, None, 0)), stream))
+    return d_out, out_bytes, d_out_off, d_cp_off, d_src_off, d_align
+
+
+def normalize_spans(spans, tok_off, align, cp_off, src_cp_off):
+    """spans uint32[n, 2] over the normalised texts -> over the originals (swt_normalize_spans); a new array"""
+    spans = np.array(spans, dtype=np.uint32).reshape(-1, 2)
+    tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    check(lib().swt_normalize_spans(ptr(spans, u32p), ptr(tok_off, u64p), int(tok_off.size - 1), ptr(np.ascontiguousarray(align), u32p),
+                                    ptr(cp_off, u64p), ptr(src_cp_off, u64p)))
+    return spans
 
 
 def bpe_length_table(strings):

@@ -271,8 +271,86 @@ def _pair_result(out, overflowing, offsets, token_types, special_mask):
     return res
 
 
+BERT_NORMALIZER = {"clean_text": True, "handle_chinese_chars": True, "strip_accents": None, "lowercase": True}
+
+
+def normalizer_setting(normalizer):
+    """a set_normalizer argument -> None, or the four flags as a dict of bools (strip_accents=None follows lowercase)"""
+    if normalizer is None:
+        return None
+    if normalizer == "bert":
+        normalizer = BERT_NORMALIZER
+    if not isinstance(normalizer, dict):
+        raise TypeError("normalizer is None, 'bert' or a dict of clean_text, handle_chinese_chars, strip_accents, lowercase")
+    unknown = sorted(set(normalizer) - set(BERT_NORMALIZER))
+    if unknown:
+        raise ValueError("normalizer: unknown key %r" % unknown[0])
+    setting = dict(BERT_NORMALIZER, **normalizer)
+    for key, value in setting.items():
+        if not isinstance(value, bool) and not (key == "strip_accents" and value is None):
+            raise TypeError("normalizer: %s is True or False%s" % (key, ", or None to follow lowercase" if key == "strip_accents" else ""))
+    if setting["strip_accents"] is None:
+        setting["strip_accents"] = setting["lowercase"]
+    return setting
+
+
+def normalizer_flags(setting):
+    """the SWT_NORMALIZE_* bits of a setting"""
+    return sum(bit for key, bit in N.NORMALIZE_KEYS if setting[key])
+
+
+def normalize_batch(tok, texts, return_alignment=False, device=False):
+    """SubwordTokenizer.normalize_batch: the texts packed as they are and normalised on the device (swt_normalize_plan,
+    swt_normalize_rows), through the host form or on torch tensors on the current device and stream"""
+    if tok._normalizer is None:
+        raise ValueError("normalize_batch needs a normalizer: set_normalizer('bert')")
+    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
+        raise TypeError("texts: a list of strings")
+    flags, n = normalizer_flags(tok._normalizer), len(texts)
+    text, off = N.pack_utf8(texts)
+    if device:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+        d_out, n_bytes, d_out_off, d_cp_off, d_src_off, d_align = N.normalize_dev(d_text, int(text.size), d_off, n, flags, True, empty,
+                                                                                  torch.cuda.current_stream().cuda_stream)
+        return {"text": d_out[:n_bytes], "offsets": d_out_off, "cp_offsets": d_cp_off, "source_cp_offsets": d_src_off,
+                "alignment": d_align[:-1]}
+    out, out_off, cp_off, src_off, align = N.normalize(text, off, flags, return_alignment)
+    data = out.tobytes()
+    strings = [data[int(out_off[i]):int(out_off[i + 1])].decode("utf-8", "surrogatepass") for i in range(n)]
+    if not return_alignment:
+        return strings
+    align = align.astype(np.int64)
+    return strings, [align[int(cp_off[i]):int(cp_off[i + 1])] - int(src_off[i]) for i in range(n)]
+
+
+def _encode_host_normalized(tok, texts, offsets, dropout=None):
+    """_encode_host of a tokenizer with a normalizer: the texts are packed as they are -- no str.lower() -- and normalised on the
+    device; the added tokens, if any, are found in the normalised text; the class's packed span call encodes it, and with
+    offsets the spans go back to code points of the original texts (swt_normalize_spans)"""
+    text, off, cp_off, src_off, align = N.normalize(*N.pack_utf8(texts), normalizer_flags(tok._normalizer), offsets)
+    if tok._added:
+        blank, m_off, m_pat, m_span, _ = tok._added_patterns().find(text, off)
+        got = tok._batch_encode_spans_packed(blank, off, texts, dropout)
+        ids, tok_off, spans, word = N.added_splice(got[0], got[1], got[-2], got[-1], m_off, m_pat, m_span, tok._batch_vocabulary().added_base)
+    elif not offsets:  # the ids alone, as the plain path: no span call
+        got = tok._batch_encode_ids_packed(text, off, dropout)
+        return got[0], got[1], None, None
+    else:
+        got = tok._batch_encode_spans_packed(text, off, texts, dropout)
+        ids, tok_off, spans, word = got[0], got[1], got[-2], got[-1]
+    if not offsets:
+        return ids, tok_off, None, None
+    return ids, tok_off, N.normalize_spans(spans, tok_off, align, cp_off, src_off), word
+
+
 def _encode_host(tok, texts, offsets, dropout=None):
     """one encode through the host forms -> (ids, tok_off, spans, word); spans and word are None without offsets"""
+    if tok._normalizer is not None:
+        return _encode_host_normalized(tok, texts, offsets, dropout)
     if tok._added:
         return _encode_host_added(tok, texts, offsets, dropout)
     if offsets:
@@ -317,17 +395,17 @@ def encode_batch(tok, texts, max_length=None, stride=0, padding="longest", pad_t
                  mlm=None, dropout=None):
     if dropout is not None:
         tok._enc.draw(dropout)  # refused before anything is encoded: a class without that dropout, arguments that give no draw
-    if mlm is None:
-        return _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
-                             return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                             return_special_tokens_mask, packing, drop_last, dropout)
-    if not isinstance(mlm, dict):
-        raise TypeError("mlm is None or a dict of mask_tokens keywords")
-    _mlm_thresholds(**{k: v for k, v in mlm.items() if k != "return_selected"})  # refused before anything is encoded
+    if mlm is not None:
+        if not isinstance(mlm, dict):
+            raise TypeError("mlm is None or a dict of mask_tokens keywords")
+        _mlm_thresholds(**{k: v for k, v in mlm.items() if k != "return_selected"})  # refused before anything is encoded
     res = _encode_batch(tok, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side, return_overflowing,
                         return_offsets, int64, device, text_pairs, truncation, return_token_type_ids, return_special_tokens_mask, packing,
                         drop_last, dropout)
-    res.update(mask_tokens(tok, res["input_ids"], **mlm))
+    if tok._normalizer is not None and return_offsets:
+        res["offset_unit"] = "original"  # offset_mapping counts code points of the texts as given, not of text.lower()
+    if mlm is not None:
+        res.update(mask_tokens(tok, res["input_ids"], **mlm))
     return res
 
 
@@ -419,18 +497,23 @@ def _encode_on_device(tok, voc, texts, offsets=False, dropout=None):
     def empty(shape, dtype, wanted=True):
         return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
 
-    text, off = N.pack_utf8([t.lower() for t in texts])
+    norm = tok._normalizer
+    text, off = N.pack_utf8(texts if norm is not None else [t.lower() for t in texts])
     n_bytes, n_sent = int(text.size), len(texts)
     added = tok._added_patterns() if tok._added else None  # with added tokens the span form runs whether or not offsets are wanted
     spans = offsets or added is not None
+    if n_bytes:
+        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+        if norm is not None:  # the raw text normalised on the device: the encoder reads that, and the spans go back through d_align
+            d_text, n_bytes, d_off, d_cp_off, d_src_off, d_align = N.normalize_dev(d_text, n_bytes, d_off, n_sent, normalizer_flags(norm),
+                                                                                   offsets, empty, stream)
     d_ids, d_tok_off = empty(n_bytes + 64, torch.int32), empty(n_sent + 1, torch.int64)
     d_spans, d_word = empty(2 * (n_bytes + 64), torch.int32, spans), empty(n_bytes + 64, torch.int32, spans)
     checks = []
     if n_bytes == 0:
         d_tok_off.zero_()  # nothing but empty texts: every row is specials and padding
     else:
-        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
-        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
         d_ntok = torch.zeros(1, dtype=torch.int64, device=dev)
         if added is not None:  # the added tokens found and blanked in a copy of the text, which the encoder then reads
             d_seen = empty(n_bytes + 64, torch.uint8)
@@ -450,6 +533,9 @@ def _encode_on_device(tok, voc, texts, offsets=False, dropout=None):
             N.check(N.lib().swt_added_splice_dev(*(a.data_ptr() for a in before), n_sent, d_m_off.data_ptr(), d_m_pat.data_ptr(),
                                                  d_m_span.data_ptr(), voc.added_base, d_ids.data_ptr(), d_tok_off.data_ptr(),
                                                  d_spans.data_ptr(), d_word.data_ptr(), stream))
+        if norm is not None and offsets:
+            N.check(N.lib().swt_normalize_spans_dev(d_spans.data_ptr(), n_bytes + 64, d_tok_off.data_ptr(), n_sent, d_align.data_ptr(),
+                                                    d_cp_off.data_ptr(), d_src_off.data_ptr(), stream))
     if voc.d_cmap is None or voc.d_cmap.device != dev:
         voc.d_cmap = torch.from_numpy(voc.cmap.view(np.int32)).to(dev)
     return Encoded(stream, empty, d_ids, d_tok_off, d_spans if offsets else None, d_word if offsets else None, checks)
@@ -805,11 +891,16 @@ def _answers(answers, texts):
     return ans
 
 
+def _original_unit(batch):
+    """the offsets of this batch, or of these words, count code points of the texts as given (a normalizer made them)"""
+    return isinstance(batch, dict) and batch.get("offset_unit") == "original"
+
+
 def answer_positions(batch, answers, side=None, texts=None, ignore_index=N.LABEL_IGNORE):
     """SubwordTokenizer.answer_positions: NumPy arrays through swt_answer_positions, torch tensors on the GPU through its `_dev`
     form on the current device and stream; `info` and the rows' layout are the read-backs."""
     rows = _LabelRows(batch, side, 1)
-    ans = _answers(answers, texts)
+    ans = _answers(answers, None if _original_unit(batch) else texts)
     specials, pad_left = rows.layout()
     pad_left = pad_left and specials  # without [CLS] the nothing column is ignore_index on either side
     if rows.torch is None:
@@ -881,7 +972,8 @@ def best_answers(batch, start_logits, end_logits, max_answer_length=30, side=Non
     res = {name: out[name] for name, _ in N.BEST_TEXT}
     if texts is not None:
         cs, ce = (x if rows.torch is None else x.cpu().numpy() for x in (out["char_start"], out["char_end"]))
-        res["text"] = [t.lower()[int(a):int(b)] for t, a, b in zip(texts, cs.astype(np.int64), ce.astype(np.int64))]
+        lower = (lambda t: t) if _original_unit(batch) else str.lower
+        res["text"] = [lower(t)[int(a):int(b)] for t, a, b in zip(texts, cs.astype(np.int64), ce.astype(np.int64))]
     return res
 
 
@@ -940,6 +1032,8 @@ def word_predictions(batch, logits, strategy="first", side=None, return_logits=F
     if return_logits:
         res["logits"] = out["logits"]
     res.update({"n_words": int(info[0]), "n_missing": int(info[1])})
+    if _original_unit(batch):
+        res["offset_unit"] = "original"
     return res
 
 
@@ -998,7 +1092,8 @@ def entities(words, id2label, texts=None):
     res.update({"type_names": names, "n_entities": n, "n_entity_words": int(info[1])})
     if texts is not None:
         ti, cs, ce = (x if isinstance(x, np.ndarray) else x.cpu().numpy() for x in (res["text_index"], res["char_start"], res["char_end"]))
-        res["text"] = [texts[int(i)].lower()[int(a):int(b)] for i, a, b in zip(ti, cs.astype(np.int64), ce.astype(np.int64))]
+        lower = (lambda t: t) if _original_unit(words) else str.lower
+        res["text"] = [lower(texts[int(i)])[int(a):int(b)] for i, a, b in zip(ti, cs.astype(np.int64), ce.astype(np.int64))]
     return res
 
 

@@ -82,7 +82,9 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     if "uncased" not in args.normalize_with or "bert" not in args.normalize_with:
-        parser.error("--normalize_with: only BERT-style uncased normalization (lowercase + BertPreTokenizer) is built in")
+        parser.error("--normalize_with: this command line tokenizes and trains as the reference does, on str.lower() and the built-in "
+                     "BertPreTokenizer split, so it takes the name of an uncased BERT only; the full BertNormalizer of an uncased or "
+                     "cased checkpoint is set_normalizer() of the classes and acts in encode_batch (nothing is downloaded)")
 
     # cli.py:166-188
     if args.reset:

@@ -53,6 +53,7 @@ class SubwordTokenizer:
         self._added: List[Tuple[str, bool]] = []  # the added tokens (content, special) in the order of addition
         self._added_gen = 0  # counts the changes of the list: part of the vocabulary's cache key
         self._added_handle: Optional[N.AddedPatterns] = None
+        self._normalizer: Optional[Dict[str, bool]] = None  # the four flags of set_normalizer; None: str.lower() alone
 
     # -- utils.py:15-29
     def preprocessing(self, corpus: List[str]) -> List[List[Tuple[str, Tuple[int, int]]]]:
@@ -140,6 +141,40 @@ class SubwordTokenizer:
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
                                      return_special_tokens_mask, packing, drop_last, mlm, self._enc.channel(dropout, maxmatch_dropout))
 
+    # -- the BERT normalizer (not in the reference, which only lowercases; include/swt.h)
+    def set_normalizer(self, normalizer) -> None:
+        """What encode_batch does to a text before it is split.  None (the default): str.lower(), as the reference (utils.py:27).
+        "bert": what the `tokenizers` wheel's BertNormalizer does for an uncased BERT checkpoint -- clean_text (control
+        characters dropped, every whitespace a space), handle_chinese_chars (spaces around every CJK ideograph), strip_accents
+        (canonical decomposition, marks of category Mn dropped) and lowercase -- on the device, on the raw UTF-8 of the texts,
+        with no str.lower() on the host (swt_normalize_plan / swt_normalize_rows; the rule in full: include/swt.h).  A dict
+        of these four names sets each flag (a missing one as in "bert"); strip_accents=None follows lowercase, so
+        {"lowercase": False} is the normalizer of a cased checkpoint.  With lowercase=False nothing lowercases.
+        With a normalizer every form of encode_batch works on the normalised text; "offset_mapping" then counts code points of
+        the texts AS GIVEN -- the result says so with "offset_unit": "original" -- and answer_positions, best_answers,
+        word_predictions and entities read that key: positions and slices are the original string's.  Added tokens are found in
+        the normalised text, their patterns normalised by the same rule.  tokenize, train and the other calls of the
+        reference's surface stay on str.lower(): pass them normalize_batch(corpus)."""
+        setting = batching.normalizer_setting(normalizer)
+        if setting != self._normalizer:
+            self._normalizer = setting
+            if self._added_handle is not None:  # its patterns were spelled under the setting before
+                self._added_handle.close()
+            self._added_handle = None
+
+    def normalizer(self) -> Optional[Dict[str, bool]]:
+        """the current setting: None, or the four flags"""
+        return None if self._normalizer is None else dict(self._normalizer)
+
+    def normalize_batch(self, texts: List[str], return_alignment: bool = False, device: bool = False):
+        """The texts under the normalizer that is set, made on the device -> a list of str; with return_alignment also one int64
+        array per text: for every code point of the normalised text the index of the code point of the original it came from
+        (the spaces around an ideograph point at it).  device=True: a dict of torch tensors on the current device and stream --
+        "text" (uint8, UTF-8), "offsets" (where text i starts), "cp_offsets" and "source_cp_offsets" (the same in code points of
+        the normalised and of the original texts), "alignment" (int32 per code point, counted over all texts: subtract
+        source_cp_offsets[i]).  ValueError without a normalizer."""
+        return batching.normalize_batch(self, texts, return_alignment, device)
+
     # -- added and special tokens written in the text (not in the reference; include/swt.h, DESIGN.md 4.17)
     def add_tokens(self, tokens: List[str], special: bool = False) -> int:
         """Registers strings that encode_batch keeps whole wherever they stand in a text -- "<user>", a domain term; with
@@ -194,10 +229,17 @@ class SubwordTokenizer:
         self._added_handle = None
 
     def _added_patterns(self) -> N.AddedPatterns:
-        """the device handle of the list's patterns, content.lower() as UTF-8, built on first use"""
+        """the device handle of the list's patterns, built on first use: content.lower() as UTF-8, or with a normalizer what it
+        makes of the content, as it makes it of the texts"""
         self._refuse_added()
         if self._added_handle is None:
-            self._added_handle = N.AddedPatterns([content.lower().encode("utf-8") for content, _ in self._added])
+            contents = [content for content, _ in self._added]
+            spelled = [c.lower() for c in contents] if self._normalizer is None else batching.normalize_batch(self, contents)
+            for content, pattern in zip(contents, spelled):
+                if not pattern or any(ch.isspace() for ch in pattern):
+                    raise ValueError("added token %r: under the normalizer that is set it is %r, which is empty or holds whitespace"
+                                     % (content, pattern))
+            self._added_handle = N.AddedPatterns([p.encode("utf-8") for p in spelled])
         return self._added_handle
 
     def _refuse_added(self) -> None:
@@ -243,7 +285,8 @@ class SubwordTokenizer:
                          ignore_index: int = -100) -> dict:
         """The start and end columns of an extractive-QA answer in every row of `batch`, a result of
         encode_batch(..., return_offsets=True), on the device (swt_answer_positions).  answers: [n_texts, 2], the (start, end)
-        of each text's answer, None or (-1, -1) for none, in the unit of "offset_mapping" -- code points of text.lower().  With
+        of each text's answer, None or (-1, -1) for none, in the unit of "offset_mapping" -- code points of text.lower(), or of the text as given when the batch was made with a normalizer
+        (then `texts` maps nothing).  With
         texts, the original strings of that side, the positions are indices into the original string: where
         len(t.lower()) != len(t) ("İ") they are mapped on the host by the running sum of len(ch.lower()).  side: where the
         answer lies, 1 (the context) by default for pair rows.
@@ -265,7 +308,8 @@ class SubwordTokenizer:
         the windows of a text the earlier row.
         -> per text {"score" (-inf without a span), "null_score" (the least [CLS] score of the text's rows when the rows have
         specials, +inf when not), "row", "start_col", "end_col" (-1 without a span), "char_start", "char_end" (the span in
-        "offset_mapping"'s unit)}, and with texts "text": texts[i].lower()[char_start:char_end], sliced on the host."""
+        "offset_mapping"'s unit)}, and with texts "text": texts[i].lower()[char_start:char_end], sliced on the host (texts[i][char_start:char_end] for
+        a batch made with a normalizer)."""
         return batching.best_answers(batch, start_logits, end_logits, max_answer_length, side, texts)
 
     # -- token-classification inference (not in the reference; batching.py, DESIGN.md 4.15)
@@ -294,7 +338,8 @@ class SubwordTokenizer:
         (or none), or its label begins; the entity runs on over the words of the same type that head none.
         -> per entity, in order, {"text_index", "type" (an index into "type_names"), "first_word", "last_word" (in the text),
         "char_start", "char_end", "score": the float32 mean of the words' scores}, "type_names", "n_entities",
-        "n_entity_words", and with texts (one string per text) "text": texts[i].lower()[char_start:char_end], sliced on the host."""
+        "n_entity_words", and with texts (one string per text) "text": texts[i].lower()[char_start:char_end], sliced on the host (texts[i][char_start:char_end] for words of a
+        batch made with a normalizer)."""
         return batching.entities(words, id2label, texts)
 
     # -- masked-LM inference (not in the reference; batching.py, DESIGN.md 4.16)
@@ -366,6 +411,11 @@ class SubwordTokenizer:
     def _batch_encode_spans_packed(self, text, off, texts, dropout=None):
         """_batch_encode_spans over a packed, lowercased text the caller has made (and may have blanked); texts: for the errors"""
         return _encode_spans_packed(self._enc, text, off, texts, self._enc.draw(dropout))
+
+    def _batch_encode_ids_packed(self, text, off, dropout=None):
+        """_batch_encode_ids over a packed text the caller has made: nothing is lowercased here, no status raises"""
+        draw, handle = self._enc.draw(dropout), self._enc.handle()
+        return getattr(handle, self._enc.host)(text, off) if draw is None else getattr(handle, self._enc.drop_host)(text, off, draw)
 
     def _batch_encode_dev(self, *args, dropout=None):
         return _encode_dev(self._enc, *args, dropout=dropout)
