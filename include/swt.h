@@ -125,7 +125,10 @@ int swt_utf8_lower_dev(uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent
  *                             with 384-byte tiles once, tapering from there up; the 512-byte tiles in the library's own
  *                             geometry only (a SWT_OPT_LANE_TAPER or SWT_OPT_LANE_SPAN that is set counts from 384); 1: never;
  *                             2: at every size (tiles of one size under that floor), and the tile sizes fall from 512 under a
- *                             set SWT_OPT_LANE_TAPER / SWT_OPT_LANE_SPAN too */
+ *                             set SWT_OPT_LANE_TAPER / SWT_OPT_LANE_SPAN too
+ * And one that is part of a rule, not of a path:
+ *   SWT_OPT_MAX_WORD_CHARS    (swt_wp_encode_viterbi) a word of more code points is one "[UNK]": 1..1024, default 100 (BERT's
+ *                             max_input_chars_per_word) */
 #define SWT_OPT_DEDUP 1
 #define SWT_OPT_DEDUP_TABLE_BITS 2
 #define SWT_OPT_UNIQUE_TILE 3
@@ -133,6 +136,7 @@ int swt_utf8_lower_dev(uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent
 #define SWT_OPT_LANE_TAPER 5
 #define SWT_OPT_LANE_SLOTS 6
 #define SWT_OPT_LANE_NARROW 7
+#define SWT_OPT_MAX_WORD_CHARS 8
 
 /* Code-point classes compiled into the library (fixture data probed from the wheel/interpreter the
  * reference runs on; tools/gen_unicode_tables.py).  bit0 pre-tokenizer whitespace, bit1 pre-tokenizer
@@ -315,6 +319,38 @@ int swt_wp_encode_naive_dropout(swt_wp_trie *t, const uint8_t *text, const uint6
 int swt_wp_encode_naive_dropout_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
                                     uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status,
                                     uint64_t *d_n_tokens, uint64_t drop_below, uint64_t seed, uint32_t epoch, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * UnigramWP (the unigram language model of Kudo 2018 over a WordPiece vocabulary; not in the reference): every vocabulary token
+ * carries a score, and a word comes out in the segmentation with the best total.  Arguments, ids, capacities (out_cap >= n_bytes)
+ * and the three forms as the swt_wp_encode_naive trio; ids index the vocabulary as there, "[UNK]" = n_vocab + 1.  Every sentence's
+ * status is SWT_WP_OK: there is no walk that never returns, and a '###x' vocabulary is not refused.
+ *
+ * swt_wp_trie_set_scores gives the trie one finite float32 per vocabulary id: n must be n_vocab (SWT_ERR_INVALID), a NaN or an
+ * infinity is SWT_ERR_INVALID, a vocabulary of more than 2^21 tokens SWT_ERR_UNSUPPORTED.  The scores go to the device once, with
+ * the first encode after the call.  Without scores the three encode entries return SWT_ERR_STATE.
+ *
+ * The text is prepared and split as for swt_wp_encode_naive.  For a word of n code points c[0..n):
+ *     piece(i, j), 0 <= i < j <= n, is the vocabulary token spelled c[i..j) when i == 0 and "##" + c[i..j) otherwise; nothing else
+ *       is a piece (the "#" * L states of NaiveWP.encode_word are not reproduced, so the search always ends);
+ *     reached[0] = true, best[0] = +0.0f;
+ *     for j = 1..n, for i = 0..j-1 in rising order: if reached[i] and piece(i, j) exists, cand = best[i] + score[piece] -- one
+ *       float32 round-to-nearest add, nothing fused -- replaces best[j] (and i, the piece become the way back from j) when j is
+ *       not yet reached or cand > best[j] strictly: on equal totals the smaller i, the longer last piece, stays;
+ *     (the same in push form: the starts i in rising order, every reached one walking the trie forward from c[i] and relaxing
+ *       each token end j it meets; this is what the kernel does;)
+ *     the word's tokens are the pieces on the way back from n, first to last;
+ *     n not reached: the word is one "[UNK]"; n > SWT_OPT_MAX_WORD_CHARS: one "[UNK]" too, nothing is searched.
+ * A total that overflows float32 becomes an infinity and compares as one.  One lane per word, the state in LDS (csrc/swt_wp.hip,
+ * wp_viterbi_kernel). */
+int swt_wp_trie_set_scores(swt_wp_trie *t, const float *scores, uint32_t n);
+int swt_wp_encode_viterbi(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                          uint32_t *out_ids, uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens);
+int swt_wp_encode_viterbi_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                                 uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host);
+int swt_wp_encode_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                              uint64_t n_sent, uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status,
+                              uint64_t *d_n_tokens, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's

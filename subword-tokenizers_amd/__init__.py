@@ -4,6 +4,6 @@ The directory name carries a hyphen (it mirrors the reference's repository name)
 alias package `subword_tokenizers_amd` at the repository root.
 """
 from ._native import NoDeviceError, SwtError  # noqa: F401
-from .tokenizers import FastBPE, FastWP, NaiveBPE, NaiveWP, SubwordTokenizer, TrieView  # noqa: F401
+from .tokenizers import FastBPE, FastWP, NaiveBPE, NaiveWP, SubwordTokenizer, TrieView, UnigramWP  # noqa: F401
 
-__all__ = ["SubwordTokenizer", "NaiveBPE", "FastBPE", "NaiveWP", "FastWP", "TrieView", "SwtError", "NoDeviceError"]
+__all__ = ["SubwordTokenizer", "NaiveBPE", "FastBPE", "NaiveWP", "FastWP", "UnigramWP", "TrieView", "SwtError", "NoDeviceError"]

@@ -101,6 +101,11 @@ SIGNATURES = {
                                               C.c_uint32]),
     "swt_wp_encode_naive_dropout_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "swt_wp_trie_set_scores": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
+    "swt_wp_encode_viterbi": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p]),
+    "swt_wp_encode_viterbi_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, u8p]),
+    "swt_wp_encode_viterbi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -291,6 +296,7 @@ def init(device=0):
 
 
 OPT_DEDUP, OPT_DEDUP_TABLE_BITS, OPT_UNIQUE_TILE, OPT_LANE_SPAN, OPT_LANE_TAPER, OPT_LANE_SLOTS = 1, 2, 3, 4, 5, 6
+OPT_MAX_WORD_CHARS = 8  # swt_wp_encode_viterbi: a word of more code points is one "[UNK]" (1..1024, default 100)
 DEDUP_AUTO, DEDUP_NEVER, DEDUP_ALWAYS = 0, 1, 2
 
 
@@ -1464,6 +1470,20 @@ class WpTrie:
     def encode_naive_dropout_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, draw, stream=0):
         check(lib().swt_wp_encode_naive_dropout_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, *draw,
                                                     stream))
+
+    # UnigramWP (swt_wp_encode_viterbi, include/swt.h): one float32 score per vocabulary id, then the three forms
+    def set_scores(self, scores):
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        check(lib().swt_wp_trie_set_scores(self._h, ptr(scores, C.POINTER(C.c_float)) if scores.size else None, int(scores.size)))
+
+    def encode_viterbi(self, text_u8, sent_off):
+        return _encode_host("swt_wp_encode_viterbi", self._h, text_u8, sent_off, status=True)
+
+    def encode_viterbi_joined(self, joined, n_sent):
+        return _encode_joined("swt_wp_encode_viterbi_joined", self._h, joined, n_sent, status=True)
+
+    def encode_viterbi_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
+        check(lib().swt_wp_encode_viterbi_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
 
 
 class BpeTrainer:

@@ -11,6 +11,7 @@
 //   nodes  16 bytes each {failure link, pop offset, pop count, flags}
 //   pops   token ids of every failure_pops list, concatenated
 // Node ids: 0 = root, 1 = root_p (detached, childless), 2.. in creation order; root_sharp is the node of "##".
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <unordered_map>
@@ -1016,6 +1017,56 @@ struct alignas(16) WpNaiveLds : WpTileLds {
   unsigned long long nonterm[kWpBlocks + 1]; // per sentence-start position: a word of the sentence never returns
 };
 
+// ---- B of wp_viterbi_kernel, which is wp_naive_kernel's (that kernel keeps its own text, and with it its instructions: as a
+// caller of this function it came out 12 instructions longer and the plain call 1.2 % slower): 64 bytes per step, BERT white-space / punctuation ballots -> the
+// word starts in cand[] (their count is returned), stop and pbits, tok[] cleared.  The caller synchronises.
+template <class Lds>
+__device__ __forceinline__ uint32_t wp_words(Lds &L, const WpChunk &ch, const uint8_t *__restrict__ cls_tab, int lane) {
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  uint32_t nc = 0;
+  bool prev_stop = true;  // the char owning the byte before this block is white space or punctuation
+  for (uint32_t blk = 0; blk < ch.nblk; blk++) {
+    const uint32_t p = blk * 64 + lane;
+    bool inr, lead;
+    const uint32_t cp = wp_decode(L, ch, p, inr, lead);
+    uint8_t c = SWT_CLS_BERT_WS;  // bytes outside the chunk behave as white space
+    if (inr && lead) c = cp < (uint32_t)kWpClsLds ? (uint8_t)(L.cls_lo[cp] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)) : bert_class(cls_tab, cp);
+    const unsigned long long INR = __ballot(inr);
+    const unsigned long long LEAD = __ballot(lead);
+    const unsigned long long WSm = __ballot(lead && (c & SWT_CLS_BERT_WS));
+    const unsigned long long PUm = __ballot(lead && (c & SWT_CLS_BERT_PUNCT) && !(c & SWT_CLS_BERT_WS));
+    const unsigned long long CONT = ~LEAD;
+    unsigned long long STb = WSm | PUm | ((prev_stop && (CONT & 1ull)) ? 1ull : 0ull);
+    STb |= (STb << 1) & CONT; STb |= (STb << 1) & CONT; STb |= (STb << 1) & CONT;
+    const unsigned long long SS = L.sbits[blk] & INR;
+    const unsigned long long before = ((STb << 1) | (prev_stop ? 1ull : 0ull)) & ~SS;  // no context across a sentence start
+    const unsigned long long CAND = INR & LEAD & ~WSm & (SS | before | PUm);
+    if (lane == 0) { L.stop[blk] = WSm | PUm | SS | ~INR; L.pbits[blk] = PUm & INR; }
+    if ((CAND >> lane) & 1ull) L.cand[nc + __popcll(CAND & lt)] = (uint16_t)p;
+    nc += __popcll(CAND);
+    L.tok[p] = kInvalidTok;
+    prev_stop = (STb >> 63) & 1ull;
+  }
+  return nc;
+}
+
+// where the word that starts at byte p0 of the chunk ends: a punctuation character is a word of its own
+template <class Lds>
+__device__ __forceinline__ uint32_t wp_word_end(const Lds &L, const WpChunk &ch, uint32_t p0) {
+  uint32_t we;
+  if (wbit(L.pbits, p0)) {
+    we = p0 + 1;
+    while (we < ch.ce && utf8_is_cont(L.txt[we])) we++;
+  } else {
+    int w = (int)(p0 >> 6);
+    unsigned long long m = (p0 & 63) == 63 ? 0ull : (L.stop[w] & ~((2ull << (p0 & 63)) - 1ull));
+    while (!m && w + 1 < (int)ch.nblk) m = L.stop[++w];
+    we = m ? (uint32_t)(w * 64 + __builtin_ctzll(m)) : ch.ce;
+    if (we > ch.ce) we = ch.ce;
+  }
+  return we;
+}
+
 // The skeleton of wp_encode_kernel (wp_tile_begin .. wp_tile_end) with these phases.  Word boundaries do not depend on the
 // vocabulary here, so there is nothing to speculate about:
 //   B  64 bytes per step: BERT white-space / punctuation ballots -> word starts and word ends
@@ -1138,6 +1189,193 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
   wp_tile_end(tile, tile_tok, direct, lane);
 }
 
+// ---- UnigramWP: the best-scoring segmentation of every word (include/swt.h, swt_wp_encode_viterbi) -------------
+//
+// The pieces of a word of n code points are the trie paths from the root over c[0..j) and from root_sharp over c[i..j), i > 0,
+// that end in a node with a vocabulary id.  The state of boundary j (1..n) is one word of dp[] and one of best[], both at index
+// j - 1: a word of b bytes has at most b code points, so a lane keeps its whole programme in its word's own b slots of tok[] and
+// of best[] and no two lanes of a chunk touch the same slot.  dp[j - 1] = id | i << 21 of the best piece that ends at j (ids are
+// below 2^21: swt_wp_trie_set_scores refuses larger vocabularies; i < n <= max_chars <= 1,024), kInvalidTok while j is not reached.
+struct WpViterbiDev {
+  WpDev T;              // edges and root_sharp
+  const int32_t *tok;   // node -> vocabulary id, -1 for none
+  const float *score;   // vocabulary id -> score
+  uint32_t unk_id;      // "[UNK]"
+  uint32_t max_chars;   // 1 .. kWpCap: a longer word is one "[UNK]"
+};
+constexpr uint32_t kVitIdBits = 21, kVitIdMask = (1u << kVitIdBits) - 1u;
+constexpr uint32_t kVitMaxChars = kWpCap;
+
+// the code point at q of the word that ends at we, as naive_word reads it; q moves past it
+__device__ __forceinline__ uint32_t wp_next_cp(const uint8_t *txt, uint64_t &q, uint64_t we) {
+  const uint8_t b = txt[q];
+  int n = utf8_len(b);
+  if (q + n > we) n = (int)(we - q);
+  uint32_t cp = b;
+  if (b >= 0x80 && n > 1) {
+    cp = b & (0xFF >> (n + 1));
+    for (int i = 1; i < n; i++) cp = (cp << 6) | (txt[q + i] & 0x3F);
+  }
+  q += n;
+  while (q < we && utf8_is_cont(txt[q])) q++;
+  return cp;
+}
+
+// One word [wb, we) of txt: its ids to out[0..), the count returned (never more than the word's code points).  dp and best hold
+// as many words as the word has code points, at most max_chars.  InPlace: out is dp, and the slots behind the ids end as
+// kInvalidTok.
+//   forward   starts i in rising order; a reached one walks the edge hash from the root (i = 0) or root_sharp and relaxes every
+//             boundary at which the node has an id: cand = best[i] + score, one float32 add.  Strictly greater replaces, so on
+//             equal totals the smaller i -- the longer last piece -- stays.
+//   backward  the chain from n is turned round in place (every dp word on it gets the NEXT boundary for the previous one) and
+//             counted, then followed from the front: piece k is read at its end boundary, which is never before slot k, and
+//             written to slot k.  (From the last piece down the ids would land in the same slots, but the id of piece k would
+//             overwrite the state of an earlier piece that ends on boundary k + 1: "ab ##c ##d" puts "##c" where "ab" is kept.)
+template <bool InPlace>
+__device__ __forceinline__ uint32_t viterbi_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpViterbiDev &V, uint32_t *dp,
+                                                 float *best, uint32_t *out) {
+  uint32_t n = 0;
+  for (uint64_t q = wb; q < we && n <= V.max_chars; n++) (void)wp_next_cp(txt, q, we);
+  if (n > V.max_chars) {
+    out[0] = V.unk_id;
+    return 1;
+  }
+  for (uint32_t k = 0; k < n; k++) dp[k] = kInvalidTok;
+  uint64_t pi = wb;
+  for (uint32_t i = 0; i < n; i++) {
+    if (i == 0 || dp[i - 1] != kInvalidTok) {
+      const float bi = i ? best[i - 1] : 0.0f;
+      uint32_t node = i ? V.T.root_sharp : kWpRoot;
+      uint64_t q = pi;
+      for (uint32_t j = i; q < we; j++) {  // j: the slot of boundary j + 1
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(V.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = V.tok[node];
+        if (v < 0) continue;
+        const float cand = __fadd_rn(bi, V.score[v]);
+        if (dp[j] == kInvalidTok || cand > best[j]) {
+          best[j] = cand;
+          dp[j] = (uint32_t)v | (i << kVitIdBits);
+        }
+      }
+    }
+    (void)wp_next_cp(txt, pi, we);
+  }
+  uint32_t m = 0;
+  if (dp[n - 1] == kInvalidTok) {
+    out[0] = V.unk_id;
+    m = 1;
+  } else {
+    uint32_t cur = n, nxt = 0;
+    while (cur) {
+      const uint32_t e = dp[cur - 1];
+      dp[cur - 1] = (e & kVitIdMask) | (nxt << kVitIdBits);
+      nxt = cur;
+      cur = e >> kVitIdBits;
+      m++;
+    }
+    for (uint32_t k = 0, q = nxt;; k++) {
+      const uint32_t e = dp[q - 1];
+      out[k] = e & kVitIdMask;
+      if (q == n) break;
+      q = e >> kVitIdBits;
+    }
+  }
+  if constexpr (InPlace)
+    for (uint32_t k = m; k < n; k++) dp[k] = kInvalidTok;
+  return m;
+}
+
+// A whole sentence [b, e) by one lane (sentences longer than a chunk): naive_sentence's split, every word through the
+// programme above with its state in dp[] and best[] -- the wave's LDS arrays, idle while its one lane walks.
+__device__ uint32_t viterbi_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
+                                     const WpViterbiDev &V, uint32_t *dp, float *best) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint32_t nt = 0;
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    nt += viterbi_word<false>(txt, p, q, V, dp, best, out + nt);
+    p = q;
+  }
+  return nt;
+}
+
+struct alignas(16) WpViterbiLds : WpTileLds {
+  unsigned long long stop[kWpBlocks + 1];   // as WpNaiveLds
+  unsigned long long pbits[kWpBlocks + 1];
+  float best[kWpCap];                       // per boundary of a word, in the word's own bytes: the best total that reaches it
+};
+
+// wp_naive_kernel's skeleton and its B; C is the programme above, one lane per word, the state in the word's own slots of tok[]
+// and best[]; D has one status to write.  12,944 bytes of LDS: 4 more per staged byte than wp_naive_kernel.  The one kernel of this
+// file with float32 arithmetic is compiled without packed float32 operations, a precaution of this project on gfx950: its code has
+// none today either way, so no result depends on it, and as an attribute it leaves the other kernels as they were.
+#ifdef __HIP_DEVICE_COMPILE__
+#define SWT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SWT_NO_PACKED_F32  // (the host's stub has no such feature)
+#endif
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_viterbi_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpViterbiDev V, uint32_t *__restrict__ scratch,
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+  __shared__ WpViterbiLds L;
+  const int lane = threadIdx.x;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
+  const WpOut out{sent_local, status, direct};
+
+  for (;;) {
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    __syncthreads();
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t) {
+        stt = SWT_WP_OK;
+        return viterbi_sentence(text, cls_tab, b, e, o, V, L.tok, L.best);
+      };
+      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
+      continue;
+    }
+
+    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
+    __syncthreads();
+
+    // ---- C. one lane per word
+    for (uint32_t k = lane; k < nc; k += 64) {
+      const uint32_t p0 = L.cand[k];
+      const uint32_t we = wp_word_end(L, ch, p0);
+      viterbi_word<true>(L.txt, p0, we, V, &L.tok[p0], &L.best[p0], &L.tok[p0]);
+    }
+    __syncthreads();
+
+    // ---- D. every sentence is SWT_WP_OK
+    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+      const uint64_t rel = sent_off[s] - ch.abase;
+      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+      status[s] = (uint8_t)SWT_WP_OK;
+    }
+    __syncthreads();
+
+    if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
+  }
+  wp_tile_end(tile, tile_tok, direct, lane);
+}
+
 }  // namespace swt
 
 using namespace swt;
@@ -1154,6 +1392,11 @@ struct swt_wp_trie {
   WpNode *d_nodes = nullptr;
   uint32_t *d_pops = nullptr;
   int32_t *d_tok = nullptr;  // node -> vocabulary id (NaiveWP encode), uploaded on its first call
+  // UnigramWP (swt_wp_trie_set_scores): a score per vocabulary id, uploaded by the first Viterbi call after they were set
+  std::vector<float> h_score;
+  float *d_score = nullptr;
+  bool score_fresh = false;  // h_score is newer than d_score
+  uint32_t max_word_chars = 100;  // SWT_OPT_MAX_WORD_CHARS
   TileWorkspace ws;
   HostStage stage;  // the host entry points (host_encode*, swt_tile.h)
   // word-level dedup inside one call (swt_dedup.h): possible when no vocabulary token holds a str.isspace character
@@ -1201,6 +1444,15 @@ static int wp_upload_naive(swt_wp_trie *t) {
   if (rc || t->d_tok) return rc;
   SWT_HIP(hipMalloc((void **)&t->d_tok, t->H.tok.size() * 4));
   SWT_HIP(hipMemcpy(t->d_tok, t->H.tok.data(), t->H.tok.size() * 4, hipMemcpyHostToDevice));
+  return SWT_OK;
+}
+
+static int wp_upload_viterbi(swt_wp_trie *t) {
+  int rc = wp_upload_naive(t);
+  if (rc || !t->score_fresh) return rc;
+  if (!t->d_score) SWT_HIP(hipMalloc((void **)&t->d_score, (t->h_score.size() + 1) * 4));
+  if (!t->h_score.empty()) SWT_HIP(hipMemcpy(t->d_score, t->h_score.data(), t->h_score.size() * 4, hipMemcpyHostToDevice));
+  t->score_fresh = false;
   return SWT_OK;
 }
 
@@ -1272,6 +1524,10 @@ int swt_wp_trie_set_option(swt_wp_trie *t, int option, int value) try {
       if (value != 0 && (value < 4 || value > 24)) return fail(SWT_ERR_INVALID, "SWT_OPT_DEDUP_TABLE_BITS takes 0 or 4..24");
       t->dd.opt_table_bits = (uint32_t)value;
       return SWT_OK;
+    case SWT_OPT_MAX_WORD_CHARS:
+      if (value < 1 || value > (int)kVitMaxChars) return fail(SWT_ERR_INVALID, "SWT_OPT_MAX_WORD_CHARS takes 1..%u", kVitMaxChars);
+      t->max_word_chars = (uint32_t)value;
+      return SWT_OK;
   }
   return fail(SWT_ERR_INVALID, "no such option");
 } SWT_API_CATCH
@@ -1283,6 +1539,7 @@ void swt_wp_trie_destroy(swt_wp_trie *t) try {
   if (t->d_pops) (void)hipFree(t->d_pops);
   if (t->d_tok) (void)hipFree(t->d_tok);
   if (t->d_len) (void)hipFree(t->d_len);
+  if (t->d_score) (void)hipFree(t->d_score);
   t->sp_scratch.release();
   t->wd_scratch.release();
   t->ws.release();
@@ -1404,6 +1661,40 @@ int swt_wp_encode_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, c
 
 }  // extern "C"
 
+// The routes of the kernels that give a word to a lane, after the tables are on the device: one workgroup that writes the
+// caller's arrays, or the plan, the tiles and the gather.  launch(classes, blocks, plan, ids, direct) enqueues the kernel.
+template <class Launch>
+static int wp_word_routes(swt_wp_trie *t, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, uint32_t *d_out_ids,
+                          uint64_t *d_out_off, uint64_t *d_n_tokens, hipStream_t st, Launch launch) {
+  int rc;
+  const uint8_t *d_cls = nullptr;
+  if ((rc = device_class_table(&d_cls))) return rc;
+  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
+  if (n_tiles > 0x7FFFFFFFull)
+    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
+  if ((rc = t->ws.reserve(n_bytes, n_sent, n_tiles))) return rc;
+  if (n_sent == 0) {
+    SWT_HIP(hipMemsetAsync(d_out_off, 0, 8, st));
+    SWT_HIP(hipMemsetAsync(d_n_tokens, 0, 8, st));
+    return SWT_OK;
+  }
+  if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents) {
+    // one workgroup, one launch, the caller's arrays written by the kernel (DirectOut, swt_tile.h)
+    launch(d_cls, 1, nullptr, d_out_ids, DirectOut{d_out_off, d_n_tokens, n_sent});
+    SWT_HIP(hipGetLastError());
+    return SWT_OK;
+  }
+  prof_begin(st, 2);
+  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
+  prof_begin(st);
+  launch(d_cls, (unsigned)n_tiles, t->ws.plan.as<uint64_t>(), t->ws.scratch.as<uint32_t>(), DirectOut{nullptr, nullptr, 0});
+  prof_end(st);
+  launch_scan_gather(d_sent_off, n_sent, n_tiles, t->ws, d_out_ids, d_out_off, d_n_tokens, st);
+  prof_end(st, 2);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+}
+
 // swt_wp_encode_naive_dev, and with `draw` swt_wp_encode_naive_dropout_dev: the same routes with the dropout instantiation
 static int wp_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                         uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, const WpDrawArgs *draw,
@@ -1416,17 +1707,6 @@ static int wp_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes,
   int rc = wp_upload_naive(t);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const uint8_t *d_cls = nullptr;
-  if ((rc = device_class_table(&d_cls))) return rc;
-  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
-  if (n_tiles > 0x7FFFFFFFull)
-    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
-  if ((rc = t->ws.reserve(n_bytes, n_sent, n_tiles))) return rc;
-  if (n_sent == 0) {
-    SWT_HIP(hipMemsetAsync(d_out_off, 0, 8, st));
-    SWT_HIP(hipMemsetAsync(d_n_tokens, 0, 8, st));
-    return SWT_OK;
-  }
   WpNaiveDev N;
   N.T = WpDev{};
   N.T.edges = t->d_edges;
@@ -1434,29 +1714,45 @@ static int wp_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes,
   N.tok = t->d_tok;
   N.unk_id = t->H.n_vocab + 1;
   N.max_steps = t->H.sharp_depth + 2;
-  const auto launch = [&](unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
+  return wp_word_routes(t, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, st,
+                        [&](const uint8_t *d_cls, unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
     if (draw)
       hipLaunchKernelGGL(wp_naive_kernel<true>, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, N, ids,
                          t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, WpDirectDrop{direct, *draw});
     else
       hipLaunchKernelGGL(wp_naive_kernel<false>, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, N, ids,
                          t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, direct);
-  };
-  if (n_bytes <= kWpDirectBytes && n_sent <= kWpDirectSents) {
-    // one workgroup, one launch, the caller's arrays written by the kernel (DirectOut, swt_tile.h)
-    launch(1, nullptr, d_out_ids, DirectOut{d_out_off, d_n_tokens, n_sent});
-    SWT_HIP(hipGetLastError());
-    return SWT_OK;
-  }
-  prof_begin(st, 2);
-  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
-  prof_begin(st);
-  launch((unsigned)n_tiles, t->ws.plan.as<uint64_t>(), t->ws.scratch.as<uint32_t>(), DirectOut{nullptr, nullptr, 0});
-  prof_end(st);
-  launch_scan_gather(d_sent_off, n_sent, n_tiles, t->ws, d_out_ids, d_out_off, d_n_tokens, st);
-  prof_end(st, 2);
-  SWT_HIP(hipGetLastError());
-  return SWT_OK;
+  });
+}
+
+static int wp_scores_set(const swt_wp_trie *t) {
+  if (t->h_score.size() == t->H.n_vocab && (t->d_score || t->score_fresh)) return SWT_OK;
+  return fail(SWT_ERR_STATE, "the trie has no scores: swt_wp_trie_set_scores comes before the Viterbi encode");
+}
+
+// swt_wp_encode_viterbi_dev: the same two routes with wp_viterbi_kernel
+static int wp_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                          uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) {
+  if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_sent && !d_status) || (n_bytes && (!d_text || !d_out_ids)))
+    return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_scores_set(t)) return rc;
+  int rc = wp_upload_viterbi(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  WpViterbiDev V;
+  V.T = WpDev{};
+  V.T.edges = t->d_edges;
+  V.T.edge_bits = t->edge_bits;
+  V.T.root_sharp = t->H.root_sharp;
+  V.tok = t->d_tok;
+  V.score = t->d_score;
+  V.unk_id = t->H.n_vocab + 1;
+  V.max_chars = t->max_word_chars;
+  return wp_word_routes(t, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, st,
+                        [&](const uint8_t *d_cls, unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
+    hipLaunchKernelGGL(wp_viterbi_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, V, ids,
+                       t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, direct);
+  });
 }
 
 // the draw of a dropout call from its three arguments
@@ -1467,6 +1763,22 @@ static int wp_draw_args(uint64_t drop_below, uint64_t seed, uint32_t epoch, WpDr
 }
 
 extern "C" {
+
+int swt_wp_trie_set_scores(swt_wp_trie *t, const float *scores, uint32_t n) try {
+  if (!t || (n && !scores)) return fail(SWT_ERR_INVALID, "null argument");
+  if (n != t->H.n_vocab) return fail(SWT_ERR_INVALID, "%u scores for a vocabulary of %u tokens", n, t->H.n_vocab);
+  if (n > kVitIdMask + 1) return fail(SWT_ERR_UNSUPPORTED, "the Viterbi encode takes vocabularies of up to %u tokens", kVitIdMask + 1);
+  for (uint32_t v = 0; v < n; v++)
+    if (!std::isfinite(scores[v])) return fail(SWT_ERR_INVALID, "the score of token %u is not finite", v);
+  t->h_score.assign(scores, scores + n);
+  t->score_fresh = true;
+  return SWT_OK;
+} SWT_API_CATCH
+
+int swt_wp_encode_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                              uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
+  return wp_viterbi_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_status, d_n_tokens, stream);
+} SWT_API_CATCH
 
 int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                             uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
@@ -1613,6 +1925,22 @@ int swt_wp_encode_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joine
 int swt_wp_encode_naive_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
                                uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) try {
   return wp_encode_joined(swt_wp_encode_naive_dev, t, joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
+} SWT_API_CATCH
+
+// UnigramWP, host buffers and joined strings: the one host-call layer with the Viterbi `_dev` form behind it.  The scores are
+// asked for here, before the layer looks for a device.
+int swt_wp_encode_viterbi(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                          uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens) try {
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_scores_set(t)) return rc;
+  return wp_encode_host(swt_wp_encode_viterbi_dev, t, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+} SWT_API_CATCH
+
+int swt_wp_encode_viterbi_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t n_joined, uint64_t n_sent, uint32_t *out_ids,
+                                 uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint8_t *need_host) try {
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_scores_set(t)) return rc;
+  return wp_encode_joined(swt_wp_encode_viterbi_dev, t, joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
 } SWT_API_CATCH
 
 }  // extern "C"

@@ -27,7 +27,7 @@ import numpy as np
 from . import _native as N
 from . import batching
 
-__all__ = ["SubwordTokenizer", "NaiveBPE", "FastBPE", "NaiveWP", "FastWP", "TrieView"]
+__all__ = ["SubwordTokenizer", "NaiveBPE", "FastBPE", "NaiveWP", "FastWP", "UnigramWP", "TrieView"]
 
 
 def _is_bert_pretokenizer(tokenizer) -> bool:
@@ -475,14 +475,15 @@ class _Encoder:
     a _SymbolTable (BPE) or the token list (WordPiece); naive: the `encode_naive*` entries instead of `encode*`; complain:
     what raises for a sentence's status (WordPiece; None: BPE, which has no statuses); corner: an id past "[UNK]" stands for
     the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE);
+    entry: another set of the three forms altogether (UnigramWP: `encode_viterbi*`);
     dropout: the handle has the `encode_dropout*` entries, a third set beside the two (FastBPE); maxmatch: that third set is
     `encode_naive_dropout*`, MaxMatch-Dropout (NaiveWP).  Either way the set is reached through drop_host / drop_dev, and the
     argument travels through one channel: a `dropout=` dict as it is, a `maxmatch_dropout=` dict inside a batching.MaxMatch."""
 
     def __init__(self, tok, ensure, spelling, naive, error="Text to tokenize must be a string.", complain=None, corner=False,
-                 first=False, dropout=False, maxmatch=False):
+                 first=False, dropout=False, maxmatch=False, entry=None):
         self._tok, self._ensure, self._spelling = weakref.proxy(tok), ensure, spelling  # (no cycle: a tokenizer dies with its last name)
-        self.host = "encode_naive" if naive else "encode"  # the three call forms on the handle, by name
+        self.host = entry or ("encode_naive" if naive else "encode")  # the three call forms on the handle, by name
         self.joined, self.dev = self.host + "_joined", self.host + "_dev"
         # BPE-dropout: a host and a `_dev` form, no joined one -- a word's draws go by its byte offset in pack_and_lower's text,
         # so every dropout call takes the long way
@@ -1228,6 +1229,127 @@ class NaiveWP(SubwordTokenizer):
             with open(vocab_file, "r", encoding="utf-8") as f:
                 self.vocab = set(json.load(f))
             self._drop_naive_trie()
+
+
+class UnigramWP(NaiveWP):
+    """A WordPiece vocabulary whose tokens carry a score, and per word the segmentation with the best total (the unigram language
+    model of Kudo 2018; not in the reference).  The rule stands in full in include/swt.h (swt_wp_encode_viterbi): the pieces of a
+    word are its vocabulary tokens in their positions ('##' inside the word), totals are float32 sums, on equal totals the longer
+    last piece wins, a word no segmentation reaches or of more than `max_word_chars` code points is one "[UNK]".  Ids index
+    sorted(vocab) as NaiveWP's, so every batch call, encode_batch in all its forms and decode_batch are NaiveWP's bodies over the
+    Viterbi entries.  Scores come from set_scores, fit_scores (hard EM on the device) or load_resources; encoding without them
+    raises ValueError.  encode_word stays NaiveWP's longest-match loop; tokenize runs the batch call on one text."""
+
+    def __init__(self, tokenizer=None, max_word_chars: int = 100):
+        super().__init__(tokenizer)
+        if not isinstance(max_word_chars, int) or not 1 <= max_word_chars <= 1024:
+            raise ValueError("max_word_chars: an int in 1..1024")
+        self.max_word_chars = max_word_chars
+        self._scores: Optional[Dict[str, float]] = None
+        self._scored_trie: Optional[N.WpTrie] = None  # the handle the scores were last given to
+        self._enc = self._naive_enc = _Encoder(self, "_ensure_scored_trie", "_naive_tokens", naive=True, entry="encode_viterbi",
+                                               complain=self._raise_naive_status)
+
+    def set_scores(self, scores) -> None:
+        """scores: token -> float for every token of `vocab` (more are ignored); kept as float32"""
+        kept = {}
+        for token in self.vocab:
+            if token not in scores:
+                raise ValueError("set_scores: no score for the token %r" % token)
+            with np.errstate(over="ignore"):
+                value = float(np.float32(scores[token]))
+            if not np.isfinite(value):
+                raise ValueError("set_scores: the score of the token %r is not a finite float32: %r" % (token, scores[token]))
+            kept[token] = value
+        self._scores, self._scored_trie = kept, None
+
+    def scores(self) -> Optional[Dict[str, float]]:
+        return None if self._scores is None else dict(self._scores)
+
+    def _ensure_scored_trie(self) -> N.WpTrie:
+        trie = self._ensure_naive_trie()
+        if trie is not self._scored_trie:
+            if self._scores is None:
+                raise ValueError("UnigramWP has no scores: set_scores, fit_scores, train or load_resources come before an encode")
+            for token in self._naive_tokens:
+                if token not in self._scores:
+                    raise ValueError("UnigramWP: the vocabulary has changed and the token %r has no score" % token)
+            trie.set_scores(np.array([self._scores[t] for t in self._naive_tokens], dtype=np.float32))
+            self._scored_trie = trie
+        trie.set_option(N.OPT_MAX_WORD_CHARS, self.max_word_chars)  # (every time: the attribute may have been changed since)
+        return trie
+
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
+        if not isinstance(text, str):
+            raise TypeError("Text to tokenize must be a string.")
+        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
+
+    def fit_scores(self, corpus: List[str], iterations: int = 2, alpha: float = 1.0) -> List[int]:
+        """Hard EM on the device: segment the corpus, count every token (swt_token_histogram_dev), set
+        score = float32(log((count + alpha) / (total + alpha * len(vocab)))) -- the log taken here in float64, total = the
+        corpus's tokens with a vocabulary id -- and again.  Iteration 0 segments with NaiveWP's longest match, the later ones with
+        the best total under the scores of the one before.  The text goes to the device once and the ids never leave it.
+        -> the number of tokens (with "[UNK]"s) of every iteration's segmentation."""
+        import math
+
+        import torch
+        if not isinstance(corpus, list) or not all(isinstance(t, str) for t in corpus):
+            raise TypeError("corpus must be a list of strings.")
+        if not isinstance(iterations, int) or iterations < 1:
+            raise ValueError("iterations: an int of at least 1")
+        if not alpha > 0 or not math.isfinite(alpha):
+            raise ValueError("alpha: a positive float")
+        text, off = N.pack_and_lower(corpus) if self._normalizer is None else N.pack_utf8(self.normalize_batch(corpus))
+        n_bytes, n_sent, size = int(text.size), len(corpus), len(self.vocab)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stream = torch.cuda.current_stream().cuda_stream
+        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+        d_ids, d_tok_off = torch.empty(n_bytes + 64, dtype=torch.int32, device=dev), torch.empty(n_sent + 1, dtype=torch.int64, device=dev)
+        d_status, d_ntok = torch.empty(n_sent + 8, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+        d_counts, d_oor = torch.empty(2 * (size + 2), dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+        totals = []
+        for it in range(iterations):
+            if it == 0:
+                trie = self._ensure_naive_trie()
+                trie.encode_naive_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                      d_status.data_ptr(), d_ntok.data_ptr(), stream)
+                for i in torch.nonzero(d_status[:n_sent]).flatten().tolist():
+                    self._raise_naive_status(int(d_status[i]), corpus[i])
+            else:
+                self._ensure_scored_trie().encode_viterbi_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(),
+                                                              d_tok_off.data_ptr(), d_status.data_ptr(), d_ntok.data_ptr(), stream)
+            totals.append(int(d_ntok.item()))
+            N.check(N.lib().swt_token_histogram_dev(d_ids.data_ptr(), totals[-1], size + 2, d_counts.data_ptr(), d_oor.data_ptr(), stream))
+            counts = d_counts[:size].cpu().numpy()
+            norm = float(counts.sum()) + alpha * size
+            self.set_scores({t: math.log((int(c) + alpha) / norm) for t, c in zip(self._naive_tokens, counts)})
+        return totals
+
+    def train(self, corpus, max_vocab: int = 30_000):
+        """NaiveWP.train, then fit_scores(corpus)"""
+        super().train(corpus, max_vocab)
+        self.fit_scores(corpus)
+
+    def reset(self) -> None:
+        super().reset()
+        self._scores, self._scored_trie = None, None
+
+    def save_resources(self, path: str) -> None:
+        """NaiveWP's vocab.json, and scores.json: [[token, score], ...] (when there are scores)"""
+        super().save_resources(path)
+        if self._scores is not None:
+            with open(os.path.join(path, "scores.json"), "w", encoding="utf-8") as f:
+                json.dump(sorted(self._scores.items()), f, ensure_ascii=False)
+
+    def load_resources(self, path: str) -> None:
+        """vocab.json and scores.json; without the second the scores stay unset"""
+        super().load_resources(path)
+        self._scores, self._scored_trie = None, None
+        scores_file = os.path.join(path, "scores.json")
+        if os.path.isfile(scores_file):
+            with open(scores_file, "r", encoding="utf-8") as f:
+                self.set_scores({token: score for token, score in json.load(f)})
 
 
 class TrieNodeView:
