@@ -353,6 +353,49 @@ int swt_wp_encode_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_
                               uint64_t *d_n_tokens, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * UnigramWP, sampled (subword regularisation, Kudo 2018): a word comes out in a segmentation drawn with probability proportional
+ * to the product of its pieces' weights, instead of always the best one.  Arguments, capacities, ids and the two routes as the
+ * Viterbi pair; every sentence's status is SWT_WP_OK.  There is no joined form: a draw goes by a byte offset in the text the call
+ * is given, as for swt_wp_encode_naive_dropout.
+ *
+ * Weights.  swt_wp_trie_set_weights gives the trie one float32 per vocabulary id (for alpha and scores, exp(alpha * score): the
+ * caller computes it).  n must be n_vocab, and every w finite, normal, positive and within [2^-64, 2^64]: anything else is
+ * SWT_ERR_INVALID.  A vocabulary of more than 2^21 tokens is SWT_ERR_UNSUPPORTED.  The weights go to the device with the next
+ * sampling call; without weights the encode entries return SWT_ERR_STATE.
+ *
+ * Arithmetic.  Every lattice value is a "wide float32": 0, or f * 2^E with f a float32 in [1, 2) and E an int32.  (x) and (+) are
+ * multiplication and addition of non-negative values, each rounded to nearest-even to 24 significant bits with no bound on the
+ * exponent: float32 arithmetic that never underflows or overflows (100 pieces at weight 2^-64 total 2^-6400).  On the device (x)
+ * is one float32 multiply of the significand by the weight -- the product is always a normal float32 -- whose exponent bits then
+ * move into E; (+) scales the operand of the smaller exponent by 2^-d, exactly, and uses one float32 add; for d > 25 the larger
+ * operand is the result (the smaller one is below half an ulp).  Nothing is fused, and there is no exp or log on the device.
+ *
+ * Backward sums.  The text is prepared and split as for swt_wp_encode_viterbi; piece(i, j) and SWT_OPT_MAX_WORD_CHARS as there.
+ * For a word of n code points c[0..n):
+ *     b[n] = 1;
+ *     for i = n-1 down to 0: b[i] = the (+)-sum, in rising j and starting from 0, of w[piece(i, j)] (x) b[j] over the j for which
+ *       piece(i, j) exists; 0 when there is none.  (Start i walks the trie forward from c[i], from the root for i = 0 and from
+ *       root_sharp otherwise, as the Viterbi push form does; every start walks, reached or not.)
+ *     b[0] == 0 or n > SWT_OPT_MAX_WORD_CHARS: the word is one "[UNK]".
+ *
+ * The draw.  From i = 0, until i == n:
+ *     u = (x >> 8) * 2^-24, x = word 0 of Philox4x32-10 (the function and constants of swt_mlm_mask) at the counter
+ *       (0, a, s, epoch) under the key (seed & 0xFFFFFFFF, seed >> 32); s = the index of the sentence in this call's sent_off,
+ *       a = the byte offset from sent_off[s] of the first byte of c[i] in the text the call is given (both mod 2^32);
+ *     t = u (x) b[i];
+ *     the walk from c[i] again, the same terms in the same order, cum = cum (+) term from cum = 0: the piece taken is the first
+ *       piece(i, j) with cum > t, and i = j.
+ * The last cum is b[i] bit for bit and t < b[i] strictly (u <= 1 - 2^-24), so a piece is always taken; a term of 0 is a dead end
+ * and is never taken.  A draw depends on (seed, epoch, s, a) and on nothing else: not on tiles, chunks, the route of the call or
+ * the other sentences.  One lane per word, the state in LDS (csrc/swt_wp.hip, wp_sample_kernel). */
+int swt_wp_trie_set_weights(swt_wp_trie *t, const float *w, uint32_t n);
+int swt_wp_encode_sample(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                         uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint64_t seed, uint32_t epoch);
+int swt_wp_encode_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                             uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint64_t seed,
+                             uint32_t epoch, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's
  * zipf_distribution (source/benchmarks.py:240-253), over ids -- a '##' token and the same token without the prefix are
  * different strings and different ids.  counts has 2 * id_cap entries: counts[id & 0x7FFFFFFF] for ids without SWT_BPE_CONT,

@@ -106,6 +106,10 @@ SIGNATURES = {
     "swt_wp_encode_viterbi_joined": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, u8p]),
     "swt_wp_encode_viterbi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_wp_trie_set_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
+    "swt_wp_encode_sample": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, C.c_uint64, C.c_uint32]),
+    "swt_wp_encode_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -1381,6 +1385,7 @@ class WpTrie:
         h = C.c_void_p()
         check(lib().swt_wp_trie_create(ptr(blob, u32p) if blob.size else None, ptr(off, u64p), self.n_vocab, C.byref(h)))
         self._h = h
+        self._scores, self._alpha = None, None  # set_scores' array, and the alpha the trie's weights were made of it at (encode_sample)
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1475,6 +1480,7 @@ class WpTrie:
     def set_scores(self, scores):
         scores = np.ascontiguousarray(scores, dtype=np.float32)
         check(lib().swt_wp_trie_set_scores(self._h, ptr(scores, C.POINTER(C.c_float)) if scores.size else None, int(scores.size)))
+        self._scores, self._alpha = scores, None  # (encode_sample's weights come from these)
 
     def encode_viterbi(self, text_u8, sent_off):
         return _encode_host("swt_wp_encode_viterbi", self._h, text_u8, sent_off, status=True)
@@ -1484,6 +1490,38 @@ class WpTrie:
 
     def encode_viterbi_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream=0):
         check(lib().swt_wp_encode_viterbi_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, stream))
+
+    # UnigramWP, sampled (swt_wp_encode_sample, include/swt.h): one float32 weight per vocabulary id, then the two forms;
+    # draw = (alpha, seed, epoch), the weights being those of set_scores' scores at alpha: given to the trie once per (scores, alpha)
+    def set_weights(self, weights):
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        check(lib().swt_wp_trie_set_weights(self._h, ptr(weights, C.POINTER(C.c_float)) if weights.size else None, int(weights.size)))
+        self._alpha = None
+
+    def _at_alpha(self, alpha):
+        if alpha is None:  # the weights as set_weights left them
+            return
+        if self._scores is None:
+            raise ValueError("the trie has no scores: set_scores comes before encode_sample")
+        if self._alpha != alpha:
+            self.set_weights(sample_weights(self._scores, alpha))
+            self._alpha = alpha
+
+    def encode_sample(self, text_u8, sent_off, draw):
+        self._at_alpha(draw[0])
+        return _encode_host("swt_wp_encode_sample", self._h, text_u8, sent_off, status=True, draw=list(draw[1:]))
+
+    def encode_sample_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, draw, stream=0):
+        self._at_alpha(draw[0])
+        check(lib().swt_wp_encode_sample_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, *draw[1:], stream))
+
+
+def sample_weights(scores, alpha):
+    """float32(exp(alpha * score)) per score, the exponential taken in float64 and clamped into [2^-64, 2^64] before it is rounded:
+    the weights of swt_wp_trie_set_weights"""
+    with np.errstate(over="ignore", under="ignore"):
+        w = np.exp(float(alpha) * np.asarray(scores, dtype=np.float64))
+    return np.clip(w, 2.0 ** -64, 2.0 ** 64).astype(np.float32)
 
 
 class BpeTrainer:

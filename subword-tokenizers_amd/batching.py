@@ -656,6 +656,32 @@ class MaxMatch:
         self.spec = spec
 
 
+class Sample:
+    """The same around a `sample` argument (UnigramWP)."""
+    __slots__ = ("spec",)
+
+    def __init__(self, spec):
+        self.spec = spec
+
+
+def sample_draw(sample):
+    """A `sample` argument of the encode calls -> (alpha, seed, epoch) of N.WpTrie.encode_sample: alpha 0.1, seed and epoch 0
+    unless given.  TypeError for what is no dict, ValueError for an alpha that is negative, infinite or a NaN, an unknown key, a
+    seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
+    if not isinstance(sample, dict):
+        raise TypeError("sample is None or a dict of 'alpha', 'seed' and 'epoch'")
+    if set(sample) - {"alpha", "seed", "epoch"}:
+        raise ValueError("sample takes 'alpha', 'seed' and 'epoch'")
+    alpha, seed, epoch = float(sample.get("alpha", 0.1)), int(sample.get("seed", 0)), int(sample.get("epoch", 0))
+    if not 0.0 <= alpha < float("inf"):  # (false for a NaN)
+        raise ValueError("sample: alpha is finite and not negative")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("sample: seed lies in [0, 2^64)")
+    if not 0 <= epoch < 1 << 32:
+        raise ValueError("sample: epoch lies in [0, 2^32)")
+    return alpha, seed, epoch
+
+
 def dropout_draw(dropout, name="dropout"):
     """A `dropout` (or, by `name`, `maxmatch_dropout`) argument of the encode calls -> None, or (drop_below, seed, epoch) of
     swt_bpe_encode_dropout / swt_wp_encode_naive_dropout: drop_below = round(probability * 2^32), seed and epoch 0 unless given.

@@ -1376,6 +1376,213 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_viterbi_kernel(
   wp_tile_end(tile, tile_tok, direct, lane);
 }
 
+// ---- UnigramWP, sampled: a segmentation of every word drawn with probability proportional to the product of its pieces'
+// weights (include/swt.h, swt_wp_encode_sample) -----------------------------------------------------------------
+//
+// The state of boundary i (0..n-1; b[n] = 1 is not kept) is slot i of the word's own slots: the significand of b[i] in best[],
+// its exponent in tok[].  Before the backward pass slot i of tok[] holds the byte offset of c[i] in the word, written by the pass
+// that counts the code points: the backward pass reads it on its way down and puts the exponent in its place, so no cursor ever
+// steps back through the bytes.
+struct WpSampleDev {
+  WpDev T;                    // edges and root_sharp
+  const int32_t *tok;         // node -> vocabulary id, -1 for none
+  const float *weight;        // vocabulary id -> weight, within [2^-64, 2^64]
+  uint32_t unk_id;            // "[UNK]"
+  uint32_t max_chars;         // 1 .. kWpCap: a longer word is one "[UNK]"
+  uint32_t key0, key1, epoch; // the draw
+};
+
+// Wide float32: 0 (f == 0) or f * 2^e with f in [1, 2).  Every operation is one float32 operation on significands whose result
+// is 0 or a normal number, and the exponent bits of that result then move into e: float32 that never underflows or overflows.
+struct Wide {
+  float f;
+  int32_t e;
+};
+__device__ __forceinline__ Wide wide_norm(float r, int32_t e) {  // r: 0, or normal and positive
+  const uint32_t bits = __float_as_uint(r);
+  if (bits == 0u) return Wide{0.0f, 0};
+  return Wide{__uint_as_float((bits & 0x007FFFFFu) | 0x3F800000u), e + (int32_t)(bits >> 23) - 127};
+}
+// a * w, w = 0 or in [2^-64, 2^64]: the product of the significand is 0 or normal
+__device__ __forceinline__ Wide wide_mul(const Wide &a, float w) { return wide_norm(__fmul_rn(a.f, w), a.e); }
+// a + b: the operand of the smaller exponent scaled by 2^-d, exactly (d <= 25: a normal number), then one add; for d > 25 it lies
+// below half an ulp of the larger one, which is the rounded sum
+__device__ __forceinline__ Wide wide_add(const Wide &a, const Wide &b) {
+  if (a.f == 0.0f) return b;
+  if (b.f == 0.0f) return a;
+  const bool swap = a.e < b.e;
+  const Wide hi = swap ? b : a, lo = swap ? a : b;
+  const int32_t d = hi.e - lo.e;
+  if (d > 25) return hi;
+  return wide_norm(__fadd_rn(hi.f, __fmul_rn(lo.f, __uint_as_float((uint32_t)(127 - d) << 23))), hi.e);
+}
+__device__ __forceinline__ bool wide_gt(const Wide &a, const Wide &b) {
+  if (a.f == 0.0f) return false;
+  if (b.f == 0.0f) return true;
+  return a.e != b.e ? a.e > b.e : a.f > b.f;
+}
+
+// One word [wb, we) of txt, which starts at byte a0 of sentence `sent` of the call: its ids to out[0..), the count returned
+// (never more than the word's code points).  se and sf hold as many words as the word has code points, at most max_chars.
+// InPlace: out is se, and the slots behind the ids end as kInvalidTok.
+//   count     the code points, the byte offset of each into se[]
+//   backward  starts i from n - 1 down: the walk from c[i] (from the root for i = 0, from root_sharp otherwise) adds
+//             weight[piece] * b[j] for every token end j it meets, in rising j, and the sum is b[i]
+//   draw      from i = 0: t = u * b[i], the same walk with the same sums, and the first piece whose running sum exceeds t is
+//             taken.  Piece k goes to slot k, which is never ahead of slot i: b[i] is read before the walk.
+template <bool InPlace>
+__device__ __forceinline__ uint32_t sample_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpSampleDev &S, uint32_t sent,
+                                                uint32_t a0, uint32_t *se, float *sf, uint32_t *out) {
+  uint32_t n = 0;
+  for (uint64_t q = wb; q < we && n <= S.max_chars; n++) {
+    if (n < S.max_chars) se[n] = (uint32_t)(q - wb);
+    (void)wp_next_cp(txt, q, we);
+  }
+  const uint32_t used = n < S.max_chars ? n : S.max_chars;  // slots written so far
+  bool unk = n > S.max_chars;
+  if (!unk) {
+    for (uint32_t i = n; i-- > 0;) {
+      uint32_t node = i ? S.T.root_sharp : kWpRoot;
+      uint64_t q = wb + se[i];
+      Wide b{0.0f, 0};
+      for (uint32_t j = i + 1; q < we; j++) {
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(S.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = S.tok[node];
+        if (v < 0) continue;
+        const Wide bj = q == we ? Wide{1.0f, 0} : Wide{sf[j], (int32_t)se[j]};
+        b = wide_add(b, wide_mul(bj, S.weight[v]));
+      }
+      sf[i] = b.f;
+      se[i] = (uint32_t)b.e;
+    }
+    unk = sf[0] == 0.0f;
+  }
+  uint32_t m = 0;
+  if (!unk) {
+    uint64_t p = wb;
+    for (uint32_t i = 0; p < we;) {
+      const Wide bi{sf[i], (int32_t)se[i]};
+      const uint32_t x = philox4x32_10(0u, a0 + (uint32_t)(p - wb), sent, S.epoch, S.key0, S.key1).x[0];
+      const Wide t = wide_mul(bi, __fmul_rn((float)(x >> 8), 0x1p-24f));
+      uint32_t node = i ? S.T.root_sharp : kWpRoot, j = i;
+      uint64_t q = p;
+      Wide cum{0.0f, 0};
+      int32_t taken = -1;
+      while (q < we) {
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(S.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        j++;
+        const int32_t v = S.tok[node];
+        if (v < 0) continue;
+        const Wide bj = q == we ? Wide{1.0f, 0} : Wide{sf[j], (int32_t)se[j]};
+        cum = wide_add(cum, wide_mul(bj, S.weight[v]));
+        if (wide_gt(cum, t)) { taken = v; break; }
+      }
+      if (taken < 0) { unk = true; break; }  // (not reached: the last cum is b[i], and t < b[i])
+      out[m++] = (uint32_t)taken;
+      p = q;
+      i = j;
+    }
+  }
+  if (unk) {
+    out[0] = S.unk_id;
+    m = 1;
+  }
+  if constexpr (InPlace)
+    for (uint32_t k = m; k < used; k++) se[k] = kInvalidTok;
+  return m;
+}
+
+// A whole sentence [b, e), number `sent` of the call, by one lane (sentences longer than a chunk): viterbi_sentence's split,
+// every word through the programme above with its state in se[] and sf[] -- the wave's LDS arrays, idle while its one lane walks.
+__device__ uint32_t sample_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
+                                    const WpSampleDev &S, uint32_t sent, uint32_t *se, float *sf) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint32_t nt = 0;
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    nt += sample_word<false>(txt, p, q, S, sent, (uint32_t)(p - b), se, sf, out + nt);
+    p = q;
+  }
+  return nt;
+}
+
+// wp_viterbi_kernel's skeleton, B, D and LDS (12,944 bytes); C is the programme above, one lane per word, which looks up the key
+// of its word as wp_naive_kernel<true> does: a0 = its offset from wp_sentence_start, sent = the last sentence of
+// sent_off[s_next .. s_hi) that starts at or before it.  The LDS is WpViterbiLds under a name of its own, so that wp_words and
+// wp_word_end are instantiated for this kernel apart: sharing the instances moved six instructions of wp_viterbi_kernel.
+struct alignas(16) WpSampleLds : WpViterbiLds {};
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_sample_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpSampleDev S, uint32_t *__restrict__ scratch,
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+  __shared__ WpSampleLds L;
+  const int lane = threadIdx.x;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
+  const WpOut out{sent_local, status, direct};
+
+  for (;;) {
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    __syncthreads();
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t s) {
+        stt = SWT_WP_OK;
+        return sample_sentence(text, cls_tab, b, e, o, S, (uint32_t)s, L.tok, L.best);
+      };
+      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
+      continue;
+    }
+
+    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
+    __syncthreads();
+
+    // ---- C. one lane per word
+    for (uint32_t k = lane; k < nc; k += 64) {
+      const uint32_t p0 = L.cand[k];
+      const uint32_t we = wp_word_end(L, ch, p0);
+      const uint32_t s0 = wp_sentence_start(L, ch, p0);
+      const uint64_t g = ch.abase + p0;
+      uint64_t lo = tile.s_next, hi = tile.s_hi;  // sent_off[lo] <= g (the chunk begins at a sentence start) < sent_off[hi]
+      while (hi - lo > 1) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (sent_off[mid] <= g) lo = mid; else hi = mid;
+      }
+      sample_word<true>(L.txt, p0, we, S, (uint32_t)lo, p0 - s0, &L.tok[p0], &L.best[p0], &L.tok[p0]);
+    }
+    __syncthreads();
+
+    // ---- D. every sentence is SWT_WP_OK
+    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+      const uint64_t rel = sent_off[s] - ch.abase;
+      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+      status[s] = (uint8_t)SWT_WP_OK;
+    }
+    __syncthreads();
+
+    if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
+  }
+  wp_tile_end(tile, tile_tok, direct, lane);
+}
+
 }  // namespace swt
 
 using namespace swt;
@@ -1397,6 +1604,10 @@ struct swt_wp_trie {
   float *d_score = nullptr;
   bool score_fresh = false;  // h_score is newer than d_score
   uint32_t max_word_chars = 100;  // SWT_OPT_MAX_WORD_CHARS
+  // UnigramWP, sampled (swt_wp_trie_set_weights): a weight per vocabulary id, uploaded by the first sampling call after they were set
+  std::vector<float> h_weight;
+  float *d_weight = nullptr;
+  bool weight_fresh = false;  // h_weight is newer than d_weight
   TileWorkspace ws;
   HostStage stage;  // the host entry points (host_encode*, swt_tile.h)
   // word-level dedup inside one call (swt_dedup.h): possible when no vocabulary token holds a str.isspace character
@@ -1453,6 +1664,15 @@ static int wp_upload_viterbi(swt_wp_trie *t) {
   if (!t->d_score) SWT_HIP(hipMalloc((void **)&t->d_score, (t->h_score.size() + 1) * 4));
   if (!t->h_score.empty()) SWT_HIP(hipMemcpy(t->d_score, t->h_score.data(), t->h_score.size() * 4, hipMemcpyHostToDevice));
   t->score_fresh = false;
+  return SWT_OK;
+}
+
+static int wp_upload_sample(swt_wp_trie *t) {
+  int rc = wp_upload_naive(t);
+  if (rc || !t->weight_fresh) return rc;
+  if (!t->d_weight) SWT_HIP(hipMalloc((void **)&t->d_weight, (t->h_weight.size() + 1) * 4));
+  if (!t->h_weight.empty()) SWT_HIP(hipMemcpy(t->d_weight, t->h_weight.data(), t->h_weight.size() * 4, hipMemcpyHostToDevice));
+  t->weight_fresh = false;
   return SWT_OK;
 }
 
@@ -1540,6 +1760,7 @@ void swt_wp_trie_destroy(swt_wp_trie *t) try {
   if (t->d_tok) (void)hipFree(t->d_tok);
   if (t->d_len) (void)hipFree(t->d_len);
   if (t->d_score) (void)hipFree(t->d_score);
+  if (t->d_weight) (void)hipFree(t->d_weight);
   t->sp_scratch.release();
   t->wd_scratch.release();
   t->ws.release();
@@ -1755,6 +1976,40 @@ static int wp_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_byte
   });
 }
 
+static int wp_weights_set(const swt_wp_trie *t) {
+  if (t->h_weight.size() == t->H.n_vocab && (t->d_weight || t->weight_fresh)) return SWT_OK;
+  return fail(SWT_ERR_STATE, "the trie has no weights: swt_wp_trie_set_weights comes before the sampling encode");
+}
+
+// swt_wp_encode_sample_dev: the same two routes with wp_sample_kernel
+static int wp_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                         uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint64_t seed,
+                         uint32_t epoch, void *stream) {
+  if (!t || !d_sent_off || !d_out_off || !d_n_tokens || (n_sent && !d_status) || (n_bytes && (!d_text || !d_out_ids)))
+    return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_weights_set(t)) return rc;
+  int rc = wp_upload_sample(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  WpSampleDev S;
+  S.T = WpDev{};
+  S.T.edges = t->d_edges;
+  S.T.edge_bits = t->edge_bits;
+  S.T.root_sharp = t->H.root_sharp;
+  S.tok = t->d_tok;
+  S.weight = t->d_weight;
+  S.unk_id = t->H.n_vocab + 1;
+  S.max_chars = t->max_word_chars;
+  S.key0 = (uint32_t)seed;
+  S.key1 = (uint32_t)(seed >> 32);
+  S.epoch = epoch;
+  return wp_word_routes(t, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, st,
+                        [&](const uint8_t *d_cls, unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
+    hipLaunchKernelGGL(wp_sample_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, S, ids,
+                       t->ws.sent_local.as<uint32_t>(), t->ws.tile_tok.as<uint32_t>(), d_status, direct);
+  });
+}
+
 // the draw of a dropout call from its three arguments
 static int wp_draw_args(uint64_t drop_below, uint64_t seed, uint32_t epoch, WpDrawArgs &d) {
   if (drop_below > (1ull << 32)) return fail(SWT_ERR_INVALID, "drop_below lies in [0, 2^32] (round(p * 2^32))");
@@ -1778,6 +2033,23 @@ int swt_wp_trie_set_scores(swt_wp_trie *t, const float *scores, uint32_t n) try 
 int swt_wp_encode_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                               uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, void *stream) try {
   return wp_viterbi_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_status, d_n_tokens, stream);
+} SWT_API_CATCH
+
+int swt_wp_trie_set_weights(swt_wp_trie *t, const float *w, uint32_t n) try {
+  if (!t || (n && !w)) return fail(SWT_ERR_INVALID, "null argument");
+  if (n != t->H.n_vocab) return fail(SWT_ERR_INVALID, "%u weights for a vocabulary of %u tokens", n, t->H.n_vocab);
+  if (n > kVitIdMask + 1) return fail(SWT_ERR_UNSUPPORTED, "the sampling encode takes vocabularies of up to %u tokens", kVitIdMask + 1);
+  for (uint32_t v = 0; v < n; v++)
+    if (!(w[v] >= 0x1p-64f && w[v] <= 0x1p64f)) return fail(SWT_ERR_INVALID, "the weight of token %u lies outside [2^-64, 2^64]", v);
+  t->h_weight.assign(w, w + n);
+  t->weight_fresh = true;
+  return SWT_OK;
+} SWT_API_CATCH
+
+int swt_wp_encode_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                             uint32_t *d_out_ids, uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens, uint64_t seed,
+                             uint32_t epoch, void *stream) try {
+  return wp_sample_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_status, d_n_tokens, seed, epoch, stream);
 } SWT_API_CATCH
 
 int swt_wp_encode_naive_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
@@ -1941,6 +2213,20 @@ int swt_wp_encode_viterbi_joined(swt_wp_trie *t, const uint8_t *joined, uint64_t
   if (!t) return fail(SWT_ERR_INVALID, "null argument");
   if (int rc = wp_scores_set(t)) return rc;
   return wp_encode_joined(swt_wp_encode_viterbi_dev, t, joined, n_joined, n_sent, out_ids, out_cap, out_off, status, n_tokens, need_host);
+} SWT_API_CATCH
+
+// UnigramWP sampled, host buffers: the one host-call layer with the sampling `_dev` form behind it; the weights are asked for
+// before the layer looks for a device.  No joined form: a draw goes by a byte offset in the text the call is given.
+int swt_wp_encode_sample(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint32_t *out_ids,
+                         uint64_t out_cap, uint64_t *out_off, uint8_t *status, uint64_t *n_tokens, uint64_t seed, uint32_t epoch) try {
+  if (!t) return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_weights_set(t)) return rc;
+  HostEncoder enc = wp_host(t, swt_wp_encode_naive_dev);
+  enc.dev = [t, seed, epoch](const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_off, uint64_t n, uint32_t *d_ids,
+                             uint64_t *d_out_off, uint8_t *d_status, uint64_t *d_n_tokens) {
+    return wp_sample_dev(t, d_text, n_bytes, d_off, n, d_ids, d_out_off, d_status, d_n_tokens, seed, epoch, nullptr);
+  };
+  return host_encode(t->stage, enc, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
 } SWT_API_CATCH
 
 }  // extern "C"

@@ -103,7 +103,7 @@ class SubwordTokenizer:
                      text_pairs: Optional[List[str]] = None, truncation: str = "longest_first",
                      return_token_type_ids: Optional[bool] = None, return_special_tokens_mask: bool = False,
                      packing: Optional[str] = None, drop_last: bool = False, mlm: Optional[dict] = None,
-                     dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> dict:
+                     dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None, sample: Optional[dict] = None) -> dict:
         """texts -> {"input_ids" [rows, width], "attention_mask", "length", "n_unknown"} with dense ids (vocab_list), [CLS] and
         [SEP] around every row and [PAD] up to the width, made on the device (swt_batch_rows).  padding="longest": width =
         min(max_length, longest row + specials); "max_length": max_length; both rounded up to pad_to_multiple_of.  A longer row
@@ -136,10 +136,14 @@ class SubwordTokenizer:
         The sentence index of the draws is the text's index, and len(texts) + j for text_pairs[j].
 
         maxmatch_dropout, a dict of the same three keys (NaiveWP; any other class raises ValueError), encodes with MaxMatch-Dropout
-        as NaiveWP.encode_ids_batch does, with the same reach and the same sentence indices."""
+        as NaiveWP.encode_ids_batch does, with the same reach and the same sentence indices.
+
+        sample = {"alpha": a, "seed": 0, "epoch": 0} (UnigramWP; any other class raises ValueError) encodes with a segmentation
+        drawn per word as UnigramWP.encode_ids_batch does, with the same reach and the same sentence indices."""
         return batching.encode_batch(self, texts, max_length, stride, padding, pad_to_multiple_of, add_special_tokens, padding_side,
                                      return_overflowing, return_offsets, int64, device, text_pairs, truncation, return_token_type_ids,
-                                     return_special_tokens_mask, packing, drop_last, mlm, self._enc.channel(dropout, maxmatch_dropout))
+                                     return_special_tokens_mask, packing, drop_last, mlm,
+                                     self._enc.channel(dropout, maxmatch_dropout, sample))
 
     # -- the BERT normalizer (not in the reference, which only lowercases; include/swt.h, DESIGN.md 4.18)
     def set_normalizer(self, normalizer) -> None:
@@ -477,11 +481,12 @@ class _Encoder:
     the several tokens of encode_word("##") (FastWP); first: the handle is built before the items are looked at (FastBPE);
     entry: another set of the three forms altogether (UnigramWP: `encode_viterbi*`);
     dropout: the handle has the `encode_dropout*` entries, a third set beside the two (FastBPE); maxmatch: that third set is
-    `encode_naive_dropout*`, MaxMatch-Dropout (NaiveWP).  Either way the set is reached through drop_host / drop_dev, and the
-    argument travels through one channel: a `dropout=` dict as it is, a `maxmatch_dropout=` dict inside a batching.MaxMatch."""
+    `encode_naive_dropout*`, MaxMatch-Dropout (NaiveWP); sample: it is `encode_sample*`, drawn segmentations (UnigramWP).  In
+    every case the set is reached through drop_host / drop_dev, and the argument travels through one channel: a `dropout=` dict
+    as it is, a `maxmatch_dropout=` dict inside a batching.MaxMatch, a `sample=` dict inside a batching.Sample."""
 
     def __init__(self, tok, ensure, spelling, naive, error="Text to tokenize must be a string.", complain=None, corner=False,
-                 first=False, dropout=False, maxmatch=False, entry=None):
+                 first=False, dropout=False, maxmatch=False, entry=None, sample=False):
         self._tok, self._ensure, self._spelling = weakref.proxy(tok), ensure, spelling  # (no cycle: a tokenizer dies with its last name)
         self.host = entry or ("encode_naive" if naive else "encode")  # the three call forms on the handle, by name
         self.joined, self.dev = self.host + "_joined", self.host + "_dev"
@@ -490,7 +495,9 @@ class _Encoder:
         self.drop_host, self.drop_dev = ("encode_dropout", "encode_dropout_dev") if dropout else (None, None)
         if maxmatch:  # MaxMatch-Dropout: the same two forms, for the same reason
             self.drop_host, self.drop_dev = self.host + "_dropout", self.host + "_dropout_dev"
-        self.bpe_dropout, self.maxmatch = bool(dropout), bool(maxmatch)
+        if sample:  # drawn segmentations: the same two forms, for the same reason
+            self.drop_host, self.drop_dev = "encode_sample", "encode_sample_dev"
+        self.bpe_dropout, self.maxmatch, self.sample = bool(dropout), bool(maxmatch), bool(sample)
         self.error, self.complain, self.corner, self.first = error, complain, corner, first
         self.flagged = complain is None  # BPE ids carry SWT_BPE_CONT over SYM_BASE + k; WordPiece ids index the token list
         self.len_base = N.SYM_BASE if self.flagged else 0
@@ -513,13 +520,21 @@ class _Encoder:
                 raise ValueError("maxmatch_dropout: only NaiveWP drops matches (MaxMatch-Dropout); this tokenizer takes "
                                  "maxmatch_dropout=None")
             return batching.dropout_draw(dropout.spec, "maxmatch_dropout")
+        if isinstance(dropout, batching.Sample):
+            if not self.sample:
+                raise ValueError("sample: only UnigramWP draws segmentations; this tokenizer takes sample=None")
+            return batching.sample_draw(dropout.spec)
         if not self.bpe_dropout:
             raise ValueError("dropout: only FastBPE drops merges (BPE-dropout); this tokenizer takes dropout=None")
         return batching.dropout_draw(dropout)
 
-    def channel(self, dropout, maxmatch_dropout):
-        """the two keywords of the public calls -> what travels on as `dropout`.  Both given: whichever this class does not have
-        raises, and no class has both."""
+    def channel(self, dropout, maxmatch_dropout, sample=None):
+        """the three keywords of the public calls -> what travels on as `dropout`.  More than one given: whichever this class does
+        not have raises, and no class has two."""
+        if sample is not None:
+            self.draw(dropout)
+            self.draw(None if maxmatch_dropout is None else batching.MaxMatch(maxmatch_dropout))
+            return batching.Sample(sample)
         if maxmatch_dropout is None:
             return dropout
         self.draw(dropout)
@@ -841,20 +856,21 @@ class NaiveBPE(SubwordTokenizer):
             self._naive_table, self._naive_syms, self._naive_merges = N.BpeTable(left, right, merged), syms, merges
         return self._naive_table
 
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None,
-                         maxmatch_dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                         sample: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]): tokenize() of every text; ids as defined in include/swt.h
         over this object's own symbol table (decode_ids spells them).  dropout: None; anything else is FastBPE's (ValueError).
-        maxmatch_dropout: None; anything else is NaiveWP's (ValueError).  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
+        maxmatch_dropout: None; anything else is NaiveWP's (ValueError).  Added tokens (add_tokens) are not looked for here: only encode_batch honours them.
+        sample: None; anything else is UnigramWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout, sample))
 
     def decode_ids(self, ids) -> List[str]:
         return _bpe_tokens(self._enc, ids)
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
-                       maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                       sample: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts].  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout))
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout, sample))
 
     # -- token spans (not in the reference): preprocessing's (start, end) carried on from the words to their tokens
     def _span_parts(self):
@@ -952,8 +968,8 @@ class FastBPE(NaiveBPE):
         return _bpe_tokens(self._enc, ids)
 
     # -- batch entry points (not in the reference); FastBPE's own, like the reference's methods of the same class
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None,
-                         maxmatch_dropout: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                         sample: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
         """texts -> (token ids uint32, sentence offsets uint64[n+1]); ids as defined in include/swt.h.
 
         dropout = {"probability": p, "seed": 0, "epoch": 0}: BPE-dropout (Provilkov et al. 2020) on the device
@@ -962,12 +978,13 @@ class FastBPE(NaiveBPE):
         index in `texts`), whatever the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain
         encode, p = 1 leaves every word as its characters.  ValueError: a probability outside [0, 1] or a NaN, a seed outside
         [0, 2^64), an epoch outside [0, 2^32), an unknown key.  maxmatch_dropout: None; anything else is NaiveWP's (ValueError).
-        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them.
+        sample: None; anything else is UnigramWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout, sample))
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None,
-                       maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
-        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout))
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                       sample: Optional[dict] = None) -> List[List[str]]:
+        return _bpe_tokens(self._enc, *self.encode_ids_batch(texts, dropout, maxmatch_dropout, sample))
 
     # -- bpe.py:205-243, one word = one device "sentence" with the pre-tokenizer split switched off
     def encode_word(self, word: str) -> List[str]:
@@ -979,10 +996,11 @@ class FastBPE(NaiveBPE):
         return self.decode_ids(ids)
 
     # -- bpe.py:245-249
-    def tokenize(self, text: str, dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[str]:
+    def tokenize(self, text: str, dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                 sample: Optional[dict] = None) -> List[str]:
         if not isinstance(text, str):
             raise TypeError("Text must be a string.")
-        return self.tokenize_batch([text], dropout, maxmatch_dropout)[0]
+        return self.tokenize_batch([text], dropout, maxmatch_dropout, sample)[0]
 
     # -- bpe.py:251-263
     def load_resources(self, path: str) -> None:
@@ -1135,13 +1153,14 @@ class NaiveWP(SubwordTokenizer):
         return pieces
 
     # -- wordpiece.py:161-181
-    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None, sample: Optional[dict] = None):
         """maxmatch_dropout: as encode_ids_batch, on the device, `text` being sentence 0; None: the reference's walk, here.
+        sample: None; anything else is UnigramWP's (ValueError).
         Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
-        if maxmatch_dropout is not None:
-            return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
+        if maxmatch_dropout is not None or sample is not None:
+            return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout, sample=sample)[0]
         out = []
         for w, _ in self.preprocessing([text])[0]:
             out.extend(self.encode_word(w))
@@ -1162,7 +1181,8 @@ class NaiveWP(SubwordTokenizer):
             self._naive_trie = N.WpTrie(self._naive_tokens)
         return self._naive_trie
 
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None):
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                         sample: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]): tokenize() of every text on the device.  ids index
         sorted(vocab); len(vocab) + 1 is "[UNK]"; status WP_NONTERMINATING marks a text on which the reference never returns.
         dropout: None; anything else is FastBPE's (ValueError).
@@ -1174,13 +1194,15 @@ class NaiveWP(SubwordTokenizer):
         the other texts are.  The draws are Philox4x32-10, as mask_tokens'.  p = 0 is the plain encode, p = 1 leaves every word
         as its characters where each is a token in its position.  A word whose every match is dropped or missing is "[UNK]", and
         the status of a text is that of the thinned walk: over an odd vocabulary it can depend on the draw.  Errors as dropout's.
-        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them.
+        sample: None; anything else is UnigramWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout, sample))
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                       sample: Optional[dict] = None) -> List[List[str]]:
         """[tokenize(t) for t in texts], except that a text on which the reference never returns raises RuntimeError (documented
         deviation: the reference hangs).  Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout)
+        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout, sample)
         _raise_flagged(self._enc, status, texts)
         return N.nested_lists(self._enc.names(), ids, off)
 
@@ -1238,7 +1260,15 @@ class UnigramWP(NaiveWP):
     last piece wins, a word no segmentation reaches or of more than `max_word_chars` code points is one "[UNK]".  Ids index
     sorted(vocab) as NaiveWP's, so every batch call, encode_batch in all its forms and decode_batch are NaiveWP's bodies over the
     Viterbi entries.  Scores come from set_scores, fit_scores (hard EM on the device) or load_resources; encoding without them
-    raises ValueError.  encode_word stays NaiveWP's longest-match loop; tokenize runs the batch call on one text."""
+    raises ValueError.  encode_word stays NaiveWP's longest-match loop; tokenize runs the batch call on one text.
+
+    sample = {"alpha": 0.1, "seed": 0, "epoch": 0} on encode_ids_batch, tokenize_batch, tokenize and encode_batch: subword
+    regularisation (Kudo 2018) on the device (swt_wp_encode_sample, where the rule stands in full).  Every word comes out in a
+    segmentation drawn with probability proportional to the product of exp(alpha * score) over its pieces, so a text gets another
+    segmentation per (seed, epoch) -- and the same one for the same (seed, epoch, index in `texts`), whatever the other texts
+    are.  alpha = 0 makes every segmentation equally likely; a large alpha approaches the best one.  The draws are Philox4x32-10,
+    as mask_tokens'.  ValueError: an alpha that is negative, infinite or a NaN, a seed outside [0, 2^64), an epoch outside
+    [0, 2^32), an unknown key."""
 
     def __init__(self, tokenizer=None, max_word_chars: int = 100):
         super().__init__(tokenizer)
@@ -1248,7 +1278,7 @@ class UnigramWP(NaiveWP):
         self._scores: Optional[Dict[str, float]] = None
         self._scored_trie: Optional[N.WpTrie] = None  # the handle the scores were last given to
         self._enc = self._naive_enc = _Encoder(self, "_ensure_scored_trie", "_naive_tokens", naive=True, entry="encode_viterbi",
-                                               complain=self._raise_naive_status)
+                                               complain=self._raise_naive_status, sample=True)
 
     def set_scores(self, scores) -> None:
         """scores: token -> float for every token of `vocab` (more are ignored); kept as float32"""
@@ -1279,10 +1309,10 @@ class UnigramWP(NaiveWP):
         trie.set_option(N.OPT_MAX_WORD_CHARS, self.max_word_chars)  # (every time: the attribute may have been changed since)
         return trie
 
-    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None, sample: Optional[dict] = None):
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
-        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
+        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout, sample=sample)[0]
 
     def fit_scores(self, corpus: List[str], iterations: int = 2, alpha: float = 1.0) -> List[int]:
         """Hard EM on the device: segment the corpus, count every token (swt_token_histogram_dev), set
@@ -1470,15 +1500,18 @@ class FastWP(NaiveWP):
         self._build_trie()
 
     # -- batch entry points (not in the reference)
-    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None):
+    def encode_ids_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                         sample: Optional[dict] = None):
         """texts -> (ids uint32, offsets uint64[n+1], status uint8[n]); see include/swt.h for ids and status.
         dropout: None; anything else is FastBPE's (ValueError).  maxmatch_dropout: None; anything else is NaiveWP's (ValueError:
         this class walks failure links, not MaxMatch -- a NaiveWP over the same vocabulary gives this class's ids).
-        Added tokens (add_tokens) are not looked for here: only encode_batch honours them."""
-        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout))
+        Added tokens (add_tokens) are not looked for here: only encode_batch honours them.
+        sample: None; anything else is UnigramWP's (ValueError)."""
+        return _encode_ids(self._enc, texts, self._enc.channel(dropout, maxmatch_dropout, sample))
 
-    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None) -> List[List[str]]:
-        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout)
+    def tokenize_batch(self, texts: List[str], dropout: Optional[dict] = None, maxmatch_dropout: Optional[dict] = None,
+                       sample: Optional[dict] = None) -> List[List[str]]:
+        ids, off, status = self.encode_ids_batch(texts, dropout, maxmatch_dropout, sample)
         _raise_flagged(self._enc, status, texts)
         if ids.size and int(ids.max()) <= len(self._tokens) + 1:  # no multi-token corner: one table, references handed out
             if ids.size < 4096:
@@ -1547,10 +1580,10 @@ class FastWP(NaiveWP):
             raise IndexError("string index out of range")  # wordpiece.py:285 with i == len(seq)
 
     # -- wordpiece.py:233-270
-    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None):
+    def tokenize(self, text, maxmatch_dropout: Optional[dict] = None, sample: Optional[dict] = None):
         if not isinstance(text, str):
             raise TypeError("Text to tokenize must be a string.")
-        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout)[0]
+        return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout, sample=sample)[0]
 
     # -- wordpiece.py:318-330
     def load_resources(self, path: str) -> None:
