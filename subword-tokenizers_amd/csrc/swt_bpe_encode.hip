@@ -115,9 +115,8 @@ __device__ __forceinline__ uint32_t slot_value(const NarrowSlot *__restrict__ sl
   const Pair r1 = *reinterpret_cast<GlobalPtr<Pair>>(base + (h.h1 << 3));
   const Pair r2 = *reinterpret_cast<GlobalPtr<Pair>>(base + (h.h2 << 3));
   const uint32_t key = narrow_key(l, r);
-  const uint32_t a = r1.x == key ? r1.y : kNoRank;
-  const uint32_t b = r2.x == key ? r2.y : kNoRank;
-  return a & b;
+  // a key sits in at most one of its two slots: a select of a select (both loads are issued above, whatever the selects wait for)
+  return r1.x == key ? r1.y : (r2.x == key ? r2.y : kNoRank);
 }
 // What the narrow kernel reads beside its rank table, one record per handle in device memory (the kernel's merged_of_rank
 // argument, which a packed table does not use, points at it).
@@ -502,15 +501,16 @@ __device__ __forceinline__ void lane_classes(LaneShared<false> &L, const uint8_t
 // ---- A + B/C of one chunk: stage the bytes, then 64 bytes per step: classes, word structure from ballot masks, the dense
 // symbols, the list of word starts, and the table value of every adjacent pair of a word.
 // Narrow: the symbols are codes, read with the class from D.code_of_cp (cls2 is not there); a FOREIGN symbol's val[] entry gets
-// its code point.
-template <int Cap, bool Narrow>
+// its code point.  NextLds: a symbol's successor in its block is read back from sym[] (the kernels with rounds proper on codes).
+template <bool NextLds, int Cap, bool Narrow>
 __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32_t *cls2, const NarrowDir &D, const uint8_t *__restrict__ text,
                                            uint64_t n_bytes, const uint64_t *__restrict__ sent_off, const uint8_t *__restrict__ cls_tab,
                                            const typename LaneSym<Narrow>::Slot *__restrict__ slots, uint32_t sh, const LaneTile &T, LaneChunk &C,
                                            int lane) {
+  static_assert(!NextLds || Narrow, "the successor is read back from sym[] in the form of the narrow kernels alone (the wide form has no wave_sync in front of its lookup)");
   constexpr int Blocks = Cap / 64;
   constexpr uint32_t kCont = LaneSym<Narrow>::kCont;
-  const unsigned long long le = (2ull << lane) - 1ull;  // me and below
+  [[maybe_unused]] const unsigned long long le = (2ull << lane) - 1ull;  // me and below (the wide form's next symbol)
   const uint64_t abase = T.cb & ~15ull;
   const uint32_t off0 = (uint32_t)(T.cb - abase);
   const uint64_t avail = T.span_end - abase;
@@ -604,8 +604,8 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
     }
     const bool is_sym = lane_bit(SYM);
     const bool wstart = lane_bit(WSTART);
-    const unsigned long long after = SYM & ~le;
-    const uint32_t q = after ? (uint32_t)__builtin_ctzll(after) : 64u;
+    [[maybe_unused]] const unsigned long long after = SYM & ~le;
+    [[maybe_unused]] const uint32_t q = after ? (uint32_t)__builtin_ctzll(after) : 64u;  // the lane of the next symbol (the wide form)
     // HASNEXT: the symbols whose next symbol in the block continues their word, as a scalar.  In bit-reversed order the next
     // symbol of a lane lies BELOW it: a one added above every continuing symbol to the mask of the non-symbol lanes carries up
     // through them and sets exactly the symbol it belongs to (a symbol lane is a zero there and takes at most that one carry).
@@ -615,7 +615,12 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
     const uint32_t f = SYM ? (uint32_t)__builtin_ctzll(SYM) : 64u;
     const bool joins = pend_shut == 0u && f < 64 && !((WSTART >> (f & 63)) & 1ull);
     const uint32_t si = lanes_below(SYM, nsym);
-    const uint32_t cpn = __shfl(sy, (int)(q & 63));
+    // without NextLds the next symbol of the block is fetched from its lane (with it, it is read back from sym[], below).  That
+    // form has fewer vector instructions in every instantiation, but only the kernels with rounds proper gained by it: the
+    // kernels that finish every word in the literal rounds -- ordered, dropout, FastBPE on an improper table -- ran 1.3 to 3 %
+    // slower with it (profiles/lane_rounds_diet.txt section 4)
+    [[maybe_unused]] uint32_t cpn_lane = 0;
+    if constexpr (!NextLds) cpn_lane = __shfl(sy, (int)(q & 63));
     // lane 63 never has a successor inside the block: it probes the pair that straddles the block boundary (Narrow: not behind a
     // FOREIGN symbol, whose entry is taken)
     const unsigned long long JP = (joins && !(Narrow && pend_cp == kNarrowForeign)) ? 1ull << 63 : 0ull;
@@ -624,6 +629,13 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
     const bool want = lane_bit(HASNEXT | JP);
     if (wstart) L.wl[lanes_below(WSTART, nw)] = (uint16_t)si;
     uint32_t v = kNoRank;
+    // NextLds: the symbols are dense, so the next symbol of the block stands at sym[si + 1]: it is read back from there once the
+    // block's symbols are written, at a constant offset from the address the lane stores to (finding the lane of the next
+    // symbol and fetching from it cost a 64-bit find-first-set per lane and a ds_bpermute).  Only a lane of HASNEXT uses what
+    // it reads, and its successor is a symbol of this block that continues the word: it was stored with kCont.
+    if constexpr (NextLds) {
+      if (is_sym) L.sym[si] = wstart ? sy : (sy | kCont);
+    }
     if constexpr (Narrow) {
       // the value goes in as the key of its slot (slot_key): the symbol's place in its word, counted from the word's first
       // symbol, which the word list holds by now -- this block's word starts were written just above, and a lane's word is
@@ -631,14 +643,16 @@ __device__ __forceinline__ void lane_split(LaneLds<Cap, Narrow> &L, const uint32
       // successor has a word: the first symbol of a chunk starts one.
       wave_sync();
       if (want) {
+        uint32_t cpn = cpn_lane;
+        if constexpr (NextLds) cpn = (uint32_t)L.sym[si + 1] & ~kCont;
         const uint32_t first = L.wl[jp ? nw - 1u : lanes_below(WSTART >> 1, nw - 1u + (uint32_t)(WSTART & 1ull))];
         v = slot_key(slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn), (jp ? nsym - 1u : si) - first);
       }
     } else if (want) {
-      v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn);
+      v = slot_value(slots, sh, jp ? pend_cp : sy, jp ? cpf : cpn_lane);
     }
     if (is_sym) {
-      L.sym[si] = wstart ? sy : (sy | kCont);
+      if constexpr (!NextLds) L.sym[si] = wstart ? sy : (sy | kCont);
       if (!hasnext) L.val[si] = kNoRank;
     }
     if (want) L.val[jp ? nsym - 1 : si] = v;
@@ -797,22 +811,34 @@ struct KeyScan {
 // [0] when a lane takes a word, [1] after a round, [2] in the tail
 __device__ unsigned long long g_scan_trips[3];
 #endif
+// (the trip that starts at entry i0, a multiple of 4, reads at the byte offsets min(4 i0, lim4) and that + d4)
+// The rounds' form of that scan, over the same groups of entries in the same order of trips.  Only a word's LAST trip is clamped
+// and has its second read at a distance of its own: with K = (n - 2) / 4 trips before it, their bases 16 k stay below lim4 - 4
+// (4 K <= n - 2) and belong to a word of six symbols or more, whose second read lies 8 bytes on.  So the word keeps the two read
+// addresses of its last trip, and a trip before it is two reads off one address that steps: two min3, an add and the compare.
+struct KeyWalk {
+  const uint32_t *last, *last_b;
+  __device__ __forceinline__ KeyWalk() : last(nullptr), last_b(nullptr) {}
+  __device__ __forceinline__ KeyWalk(const uint32_t *V, uint32_t n) {
+    const KeyScan ks(n);
+    last = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(V) + min(16u * ((n - 2u) >> 2), ks.lim4));
+    last_b = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(last) + ks.d4);
+  }
+};
 template <int Which>
-__device__ __forceinline__ uint32_t scan_trip(const uint32_t *V, uint32_t i0, const KeyScan &ks, uint32_t key) {  // i0: a multiple of 4
+__device__ __forceinline__ uint32_t walk_keys(const uint32_t *V, const KeyWalk &kw) {
+  uint32_t key = 0xFFFFFFFFu;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)  // (a minimum is a reduction: the loop was interleaved by two)
+  for (const uint32_t *a = V; a < kw.last; a += 4) {
+#ifdef SWT_SCAN_TRIPS
+    if (threadIdx.x == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_scan_trips[Which], 1ull);
+#endif
+    key = min(min(min(min(key, a[0]), a[1]), a[2]), a[3]);
+  }
 #ifdef SWT_SCAN_TRIPS
   if (threadIdx.x == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_scan_trips[Which], 1ull);
 #endif
-  const uint32_t o = min(4u * i0, ks.lim4);
-  const char *const v0 = reinterpret_cast<const char *>(V);
-  const uint32_t *a = reinterpret_cast<const uint32_t *>(v0 + o), *b = reinterpret_cast<const uint32_t *>(v0 + ks.d4 + o);
-  return min(min(min(min(key, a[0]), a[1]), b[0]), b[1]);
-}
-template <int Which>
-__device__ __forceinline__ uint32_t scan_keys(const uint32_t *V, uint32_t n, const KeyScan &ks) {
-  const uint32_t nm1 = n - 1u;
-  uint32_t key = 0xFFFFFFFFu;
-  for (uint32_t i0 = 0; i0 < nm1; i0 += 4) key = scan_trip<Which>(V, i0, ks, key);
-  return key;
+  return min(min(min(min(key, kw.last[0]), kw.last[1]), kw.last_b[0]), kw.last_b[1]);
 }
 // A lane's word as the rounds hand it to their tail.
 struct LaneWord {
@@ -842,19 +868,39 @@ __device__ __forceinline__ void lane_tail(LaneLds<Cap, Narrow> &L, const LaneWor
   typename LaneSym<Narrow>::type *const S = L.sym + t_w;
   uint32_t *const V = L.val + t_w;
   uint32_t n = have ? t_n : 0u, alive = t_alive;
-  [[maybe_unused]] const KeyScan ks(max(n, 2u));
+  // Narrow: a word keeps its length through the tail, so the read addresses of this lane's trips over its share of the (at most
+  // 32) slots are made once: those of a trip (KeyScan) where the share holds a pair, else entries n - 2 and n - 1 of the word twice --
+  // its own last pair, which is part of the group's minimum anyway -- so that a round makes no clamp, no add and no branch.
+  constexpr uint32_t kTrips = 32u / TL / 4u;
+  static_assert(!Narrow || ((32u / TL) % 4u == 0u && kTrips >= 1u), "a lane's share of the 32 slots is a whole number of trips of four");
+  [[maybe_unused]] const uint32_t *ta[kTrips], *tb[kTrips];
+  if constexpr (Narrow) {
+    const uint32_t n2 = max(n, 2u);
+    const KeyScan ks(n2);
+#pragma unroll
+    for (uint32_t q = 0; q < kTrips; q++) {
+      const uint32_t i0 = (32u / TL) * j + 4u * q;
+      const bool in = i0 < n2 - 1u;
+      ta[q] = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(V) + (in ? min(4u * i0, ks.lim4) : 4u * (n2 - 2u)));
+      tb[q] = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(ta[q]) + (in ? ks.d4 : 0u));
+    }
+  }
   for (;;) {
     if (__ballot(n != 0u) == 0ull) break;
     if (n != 0u) {
-      const uint32_t nm1 = n - 1u;
+      [[maybe_unused]] const uint32_t nm1 = n - 1u;
       uint32_t k = 0xFFFFFFFFu;
+      if constexpr (Narrow) {
+#ifdef SWT_SCAN_TRIPS
+        if (threadIdx.x == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_scan_trips[2], (unsigned long long)kTrips);
+#endif
 #pragma unroll
-      for (uint32_t q0 = 0; q0 < 32u / TL; q0 += 4) {  // this lane's share of the (at most 32) slots
-        const uint32_t i0 = (32u / TL) * j + q0;
-        if (i0 < nm1) {
-          if constexpr (Narrow) {
-            k = scan_trip<2>(V, i0, ks, k);
-          } else {
+        for (uint32_t q = 0; q < kTrips; q++) k = min(min(min(min(k, ta[q][0]), ta[q][1]), tb[q][0]), tb[q][1]);
+      } else {
+#pragma unroll
+        for (uint32_t q0 = 0; q0 < 32u / TL; q0 += 4) {  // this lane's share of the (at most 32) slots
+          const uint32_t i0 = (32u / TL) * j + q0;
+          if (i0 < nm1) {
             const uint32_t i1 = min(i0 + 1u, nm1), i2 = min(i0 + 2u, nm1), i3 = min(i0 + 3u, nm1);
             k = min(k, min(min(rank_key<Packed>(V[i0], i0), rank_key<Packed>(V[i1], i1)), min(rank_key<Packed>(V[i2], i2), rank_key<Packed>(V[i3], i3))));
           }
@@ -947,7 +993,7 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
   uint32_t next = 0;  // first word of the list no lane has taken (the same in every lane)
   uint32_t n = 0, alive = 0, where = 0;  // this lane's word: symbols (0: none), live slots, first slot
   uint32_t key = 0xFFFFFFFFu;            // its smallest rank | the slot that holds it
-  [[maybe_unused]] KeyScan ks(2u);       // Narrow: what a scan of its entries needs, kept with the word
+  [[maybe_unused]] KeyWalk kw;           // Narrow: what a scan of its entries needs, kept with the word
   typename LaneSym<Narrow>::type *S = L.sym;
   uint32_t *V = L.val;
   for (;;) {
@@ -965,7 +1011,7 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
           literal_rounds<Packed, Narrow, Seq>(S, V, n, slots, sh, merged_of_rank, D, rules.of(L, where));
           n = 0u;
         } else {
-          if constexpr (Narrow) { ks = KeyScan(n); key = scan_keys<0>(V, n, ks); } else key = scan_key<Packed>(V, n);
+          if constexpr (Narrow) { kw = KeyWalk(V, n); key = walk_keys<0>(V, kw); } else key = scan_key<Packed>(V, n);
         }
       }
       next += (uint32_t)__popcll(IDLE);
@@ -993,10 +1039,12 @@ __device__ __forceinline__ LaneWord lane_rounds(LaneLds<Cap, Narrow> &L, const u
         S[im] = im ? (mg | kCont) : mg;
         S[r] = kDead;
         V[r] = kNoRank;
+        // (v1 is looked up whether or not the word has a left neighbour: under a guard like v2's the narrow kernel executed 0.2 M
+        // MORE vector instructions a launch, profiles/lane_rounds_diet.txt section 4)
         const uint32_t v1 = slot_value(slots, sh, sl, mg), v2 = has_rr ? slot_value(slots, sh, mg, sr) : kNoRank;
         if (has_pl && !(Narrow && sl == kNarrowForeign)) V[pl] = Narrow ? slot_key(v1, pl) : v1;  // a FOREIGN symbol's entry is its code point
         V[im] = Narrow ? slot_key(v2, im) : v2;
-        if constexpr (Narrow) key = scan_keys<1>(V, n, ks); else key = scan_key<Packed>(V, n);
+        if constexpr (Narrow) key = walk_keys<1>(V, kw); else key = scan_key<Packed>(V, n);
       }
     }
   }
@@ -1114,7 +1162,7 @@ __global__ __launch_bounds__(64) void bpe_lane_kernel(
   auto rules = lane_rules<Packed, Ordered, Dropout>(merged_of_rank, direct, sent_off, T);
   for (;;) {
     LaneChunk C;
-    lane_split(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
+    lane_split<Narrow && Proper>(L, SH.cls2, D, text, n_bytes, sent_off, cls_tab, tab, sh, T, C, lane);
     // (the one-lane walker of a word longer than a chunk works on ids, whatever the kernel's symbols are)
     // (Narrow: their table comes out of the directory as a generic pointer and stays one: the walker's three loads of a slot are
     // the kernel's only flat loads, and marking the table global cost the kernel 0.5 M vector instructions a launch in registers
