@@ -396,6 +396,40 @@ int swt_wp_encode_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_b
                              uint32_t epoch, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * UnigramWP, expected counts (the E-step of soft EM, Kudo 2018): every piece of a word's lattice gets its posterior probability
+ * -- the share of the word's total weight that runs through it -- summed over the text, and the text gets its log-likelihood.
+ * counts has n_vocab entries, indexed as the vocabulary is; stats has three.  The weights are swt_wp_trie_set_weights': without
+ * them both entries return SWT_ERR_STATE; a vocabulary of more than 2^21 tokens is SWT_ERR_UNSUPPORTED.  The `_dev` form takes
+ * device pointers and zeroes its outputs itself.  There is no joined form.
+ *
+ * Text preparation, splitting, piece(i, j), SWT_OPT_MAX_WORD_CHARS, the weights w and the operations (x) and (+) are exactly those
+ * of swt_wp_encode_sample.  (/) is the quotient of two non-zero wide values, rounded to nearest-even to 24 significant bits with no
+ * bound on the exponent: on the device one correctly rounded float32 division of the significands (the quotient lies in (1/2, 2))
+ * whose exponent bits move into E; the definition is the rounding, not the instruction.  For a word of n code points c[0..n):
+ *   1. Backward.  b[] exactly as in the sampling rule: the same terms in the same order.  b[0] == 0 or
+ *      n > SWT_OPT_MAX_WORD_CHARS: the word is an UNK word; it adds 1 to stats[1] and nothing else.
+ *   2. Forward, push form.  a[0] = 1 and a[j] = 0 elsewhere.  The starts i go in rising order; a start with a[i] == 0 is skipped;
+ *      another one walks the trie from c[i] (from the root for i = 0, from root_sharp otherwise), and for each piece(i, j), in
+ *      rising j: term = a[i] (x) w[piece], then a[j] = a[j] (+) term.  So for a fixed j the additions into a[j] arrive in rising i,
+ *      and a[i] is complete when start i reads it.
+ *   3. Posterior.  In the same visit, if b[j] != 0 (b[n] = 1): p = (term (x) b[j]) (/) b[0].  With p = M * 2^e,
+ *      2^23 <= M < 2^24, the fixed-point count is q = min(floor(M * 2^(e + 32)), 2^32) -- a shift of M, 0 when it shifts out --
+ *      and counts[id(piece)] += q as an unsigned 64-bit integer.  (b[j] == 0: a dead end, no segmentation runs through it.)
+ *   4. Likelihood.  With b[0] = M * 2^e: L = ((e + 23) << 24) + frac24(M), log2(b[0]) in units of 2^-24.  frac24: m = M << 7; 24
+ *      times m = (m * m) >> 30, and if m >= 2^31 the next bit (most significant first) is 1 and m >>= 1, otherwise it is 0.
+ *      Everything fits in 64-bit integers; there is no log on the device.  frac24(M) * 2^-24 - log2(M * 2^-23) lies in
+ *      [-1.02 * 2^-24, 0] over all 2^23 significands.  stats[2] += L as a signed 64-bit integer, stats[0] += 1.
+ * So stats[0] counts the words with a segmentation, stats[1] the UNK words, and stats[2] * 2^-24 is the log2-likelihood of the
+ * former; counts * 2^-32 are the expected counts.  Every accumulation is an integer addition: the result does not depend on the
+ * order of lanes, waves or tiles, and equals the rule's exactly.  Capacity: q <= 2^32 per piece occurrence, so the counts of a
+ * call are exact below 2^31 words; |L| <= (65 n + 1) * 2^24 for a word of n code points at the extreme weights (under 2^25 for a
+ * word whose weight lies within [2^-1, 2]), and stats[2] is exact while the sum stays below 2^63.  One lane per word, both sums in LDS (csrc/swt_wp.hip, wp_marginal_kernel). */
+int swt_wp_expected_counts(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *counts,
+                           uint64_t *stats);
+int swt_wp_expected_counts_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                               uint64_t *d_counts, uint64_t *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's
  * zipf_distribution (source/benchmarks.py:240-253), over ids -- a '##' token and the same token without the prefix are
  * different strings and different ids.  counts has 2 * id_cap entries: counts[id & 0x7FFFFFFF] for ids without SWT_BPE_CONT,

@@ -110,6 +110,8 @@ SIGNATURES = {
     "swt_wp_encode_sample": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u64p, u8p, u64p, C.c_uint64, C.c_uint32]),
     "swt_wp_encode_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "swt_wp_expected_counts": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u64p, u64p]),
+    "swt_wp_expected_counts_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -1514,6 +1516,19 @@ class WpTrie:
     def encode_sample_dev(self, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, draw, stream=0):
         self._at_alpha(draw[0])
         check(lib().swt_wp_encode_sample_dev(self._h, d_text, n_bytes, d_off, n_sent, d_out, d_out_off, d_status, d_ntok, *draw[1:], stream))
+
+    # UnigramWP, expected counts (swt_wp_expected_counts, include/swt.h) under the weights of set_scores' scores at `alpha` (None:
+    # as set_weights left them) -> (counts uint64[n_vocab] in units of 2^-32, stats: words, UNK words, log2-likelihood in 2^-24)
+    def expected_counts(self, text_u8, sent_off, alpha=None):
+        self._at_alpha(alpha)
+        counts, stats = np.zeros(self.n_vocab, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
+        check(lib().swt_wp_expected_counts(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), int(sent_off.size - 1),
+                                           ptr(counts, u64p) if counts.size else None, ptr(stats, u64p)))
+        return counts, stats.view(np.int64)
+
+    def expected_counts_dev(self, d_text, n_bytes, d_off, n_sent, d_counts, d_stats, alpha=None, stream=0):
+        self._at_alpha(alpha)
+        check(lib().swt_wp_expected_counts_dev(self._h, d_text, n_bytes, d_off, n_sent, d_counts, d_stats, stream))
 
 
 def sample_weights(scores, alpha):

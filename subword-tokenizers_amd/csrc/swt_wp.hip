@@ -391,9 +391,10 @@ __device__ __forceinline__ bool wp_mark(WpTileLds &L, const WpTile &tile, WpChun
 
 // One sentence longer than the LDS chunk: lane 0 walks it in global memory (walk(b, e, out, status, s) -> token count; s: the
 // sentence's index in sent_off).  The empty
-// sentences that also start at cb come first and get no tokens and `empty_status`.  True: the tile ends with it.
-template <class Walk>
-__device__ __forceinline__ bool wp_giant(WpTileLds &L, WpTile &tile, const uint64_t *__restrict__ sent_off, const WpOut &out,
+// sentences that also start at cb come first and get no tokens and `empty_status`.  True: the tile ends with it.  Out: WpOut, or
+// WpNoOut in a kernel that has no per-sentence results.
+template <class Walk, class Out>
+__device__ __forceinline__ bool wp_giant(WpTileLds &L, WpTile &tile, const uint64_t *__restrict__ sent_off, const Out &out,
                                          uint32_t empty_status, Walk walk, int lane) {
   if (lane == 0) {
     uint64_t s = tile.s_next;
@@ -1583,6 +1584,253 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_sample_kernel(
   wp_tile_end(tile, tile_tok, direct, lane);
 }
 
+// ---- UnigramWP, expected counts: every piece of a word's lattice with its posterior probability, summed over the text, and the
+// text's log-likelihood (include/swt.h, swt_wp_expected_counts) --------------------------------------------------
+//
+// Boundary j of a word (0..n-1) has b[j] AND a[j] alive at once, in slot j of the word's own slots.  A wide value packs into 48
+// bits -- its significand as the 24-bit integer M (0 for zero) and 24 bits of exponent, of which a word of 1,024 pieces at
+// 2^+-64 needs 18 -- so the two take three words per slot and not four:
+//     sb[j] = M(b) | (E(b) & 0xFF) << 24      (tok[], which holds no ids here)
+//     sa[j] = M(a) | (E(a) & 0xFF) << 24
+//     sx[j] = (E(b) >> 8 & 0xFFFF) | (E(a) >> 8) << 16
+// Before the backward pass sa[i] holds the byte offset of c[i], as sample_word's se[] does; the forward pass has its own cursor.
+struct WpMarginalDev {
+  WpDev T;                      // edges and root_sharp
+  const int32_t *tok;           // node -> vocabulary id, -1 for none
+  const float *weight;          // vocabulary id -> weight, within [2^-64, 2^64]
+  uint32_t max_chars;           // 1 .. kWpCap: a longer word is an UNK word
+  unsigned long long *counts;   // vocabulary id -> the sum of q
+  unsigned long long *stats;    // words, UNK words, the sum of L
+};
+// what a lane has met so far: added to stats[] once, at the end of its tile
+struct WpTally {
+  long long like;
+  uint32_t words, unk;
+};
+
+// The adds into the tables that the whole grid shares, and the wave's sums before them, spelled with the builtins: as calls of the
+// library's wrappers they stayed calls in this kernel, one in the innermost loop.
+__device__ __forceinline__ void wp_tally_add(unsigned long long *p, unsigned long long v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t wp_wave_sum(uint32_t v, int lane) {
+  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)v);
+  return v;
+}
+
+__device__ __forceinline__ Wide wide_unpack(uint32_t m, uint32_t x16) {  // x16: the upper 16 bits of the exponent, in the low half
+  if ((m & 0x00FFFFFFu) == 0u) return Wide{0.0f, 0};
+  return Wide{__uint_as_float((m & 0x007FFFFFu) | 0x3F800000u), (int32_t)((x16 << 16) | ((m >> 24) << 8)) >> 8};
+}
+__device__ __forceinline__ uint32_t wide_pack(const Wide &v) {  // the word of sb[] or sa[]; (uint32_t)v.e >> 8 goes to sx[]
+  if (v.f == 0.0f) return 0u;
+  return (__float_as_uint(v.f) & 0x007FFFFFu) | 0x00800000u | ((uint32_t)v.e << 24);
+}
+// a * b, both wide: the product of the significands lies in [1, 4)
+__device__ __forceinline__ Wide wide_mul2(const Wide &a, const Wide &b) { return wide_norm(__fmul_rn(a.f, b.f), a.e + b.e); }
+// a / b, neither 0: the quotient of the significands lies in (1/2, 2), one correctly rounded float32 division
+__device__ __forceinline__ Wide wide_div(const Wide &a, const Wide &b) { return wide_norm(__fdiv_rn(a.f, b.f), a.e - b.e); }
+// floor(p * 2^32), at most 2^32: a shift of the significand
+__device__ __forceinline__ unsigned long long wide_fixed32(const Wide &p) {
+  const unsigned long long m = (__float_as_uint(p.f) & 0x007FFFFFu) | 0x00800000u;
+  const int32_t s = p.e + 9;  // M * 2^(e - 23 + 32)
+  if (s >= 9) return 1ull << 32;
+  if (s >= 0) return m << s;
+  return s > -24 ? m >> -s : 0ull;
+}
+// log2 of a non-zero wide value in units of 2^-24, rounded down bit by bit: squaring the significand doubles its logarithm, and
+// every carry into [2, 4) is the next bit.  Integers only: m stays in [2^30, 2^31) between the steps, m * m below 2^62.
+__device__ __forceinline__ long long wide_log2_fixed24(const Wide &v) {
+  unsigned long long m = (unsigned long long)((__float_as_uint(v.f) & 0x007FFFFFu) | 0x00800000u) << 7;
+  uint32_t frac = 0;
+  for (int k = 0; k < 24; k++) {
+    m = (m * m) >> 30;
+    frac <<= 1;
+    if (m >> 31) { frac |= 1u; m >>= 1; }
+  }
+  return (long long)v.e * (1ll << 24) + (long long)frac;
+}
+
+// One word [wb, we) of txt.  sb, sa and sx hold as many words as the word has code points, at most max_chars.
+//   count     the code points, the byte offset of each into sa[]
+//   backward  sample_word's, b[i] into sb[i] and the low half of sx[i]
+//   forward   a[1..n) = 0; the starts i in rising order, a reached one walks as the backward pass did: every piece adds
+//             term = a[i] * w to a[j] (a[n] is never read and is not kept) and, where b[j] != 0, floor(2^32 * term * b[j] / b[0])
+//             to counts[id] -- a global 64-bit atomic: integer sums come out the same in any order
+__device__ __forceinline__ void marginal_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpMarginalDev &M, uint32_t *sb,
+                                              uint32_t *sa, uint32_t *sx, WpTally &tally) {
+  uint32_t n = 0;
+  for (uint64_t q = wb; q < we && n <= M.max_chars; n++) {
+    if (n < M.max_chars) sa[n] = (uint32_t)(q - wb);
+    (void)wp_next_cp(txt, q, we);
+  }
+  Wide b0{0.0f, 0};
+  if (n <= M.max_chars) {
+    for (uint32_t i = n; i-- > 0;) {
+      uint32_t node = i ? M.T.root_sharp : kWpRoot;
+      uint64_t q = wb + sa[i];
+      Wide b{0.0f, 0};
+      for (uint32_t j = i + 1; q < we; j++) {
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(M.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = M.tok[node];
+        if (v < 0) continue;
+        const Wide bj = q == we ? Wide{1.0f, 0} : wide_unpack(sb[j], sx[j]);
+        b = wide_add(b, wide_mul(bj, M.weight[v]));
+      }
+      sb[i] = wide_pack(b);
+      sx[i] = ((uint32_t)b.e >> 8) & 0xFFFFu;
+      b0 = b;
+    }
+  }
+  if (b0.f == 0.0f) {
+    tally.unk++;
+    return;
+  }
+  tally.words++;
+  tally.like += wide_log2_fixed24(b0);
+  for (uint32_t k = 1; k < n; k++) sa[k] = 0u;
+  uint64_t pi = wb;
+  for (uint32_t i = 0; i < n; i++) {
+    const Wide ai = i ? wide_unpack(sa[i], sx[i] >> 16) : Wide{1.0f, 0};
+    if (ai.f != 0.0f) {
+      uint32_t node = i ? M.T.root_sharp : kWpRoot;
+      uint64_t q = pi;
+      for (uint32_t j = i + 1; q < we; j++) {
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(M.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = M.tok[node];
+        if (v < 0) continue;
+        const Wide term = wide_mul(ai, M.weight[v]);
+        Wide bj{1.0f, 0};
+        if (q < we) {
+          const uint32_t x = sx[j];
+          const Wide aj = wide_add(wide_unpack(sa[j], x >> 16), term);
+          sa[j] = wide_pack(aj);
+          sx[j] = (x & 0xFFFFu) | (((uint32_t)aj.e >> 8) << 16);
+          bj = wide_unpack(sb[j], x & 0xFFFFu);
+        }
+        if (bj.f == 0.0f) continue;  // a dead end
+        const unsigned long long fx = wide_fixed32(wide_div(wide_mul2(term, bj), b0));
+        if (fx) wp_tally_add(&M.counts[v], fx);
+      }
+    }
+    (void)wp_next_cp(txt, pi, we);
+  }
+}
+
+// A whole sentence [b, e) by one lane (sentences longer than a chunk): sample_sentence's split, every word through the programme
+// above with its state in the wave's LDS arrays, idle while its one lane walks.
+__device__ void marginal_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, const WpMarginalDev &M,
+                                  uint32_t *sb, uint32_t *sa, uint32_t *sx, WpTally &tally) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    marginal_word(txt, p, q, M, sb, sa, sx, tally);
+    p = q;
+  }
+}
+
+// 17,040 bytes of LDS: WpViterbiLds with two words per staged byte in the place of best[].  A type of its own, so that wp_words
+// and wp_word_end are instantiated for this kernel apart (as WpSampleLds).
+struct alignas(16) WpMarginalLds : WpTileLds {
+  unsigned long long stop[kWpBlocks + 1];   // as WpNaiveLds
+  unsigned long long pbits[kWpBlocks + 1];
+  uint32_t sa[kWpCap];                      // per boundary of a word, in the word's own bytes: a[], and
+  uint32_t sx[kWpCap];                      // the upper exponent bits of b[] and a[]
+};
+// a kernel without per-sentence results hands this to wp_giant
+struct WpNoOut {
+  struct Sink {
+    __device__ __forceinline__ Sink operator[](uint64_t) const { return Sink{}; }
+    __device__ __forceinline__ void operator=(uint8_t) const {}
+  };
+  Sink status;
+  __device__ __forceinline__ void off(uint64_t, uint32_t) const {}
+};
+
+// The chunk is done and nothing is emitted: what wp_emit does to the tile beyond its output.  True: that was the last chunk.
+__device__ __forceinline__ bool wp_advance(WpTile &tile, const WpChunk &ch, const uint64_t *__restrict__ sent_off, int lane) {
+  if (ch.last) return true;
+  uint32_t mine = 0;
+  for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+    const uint64_t rel = sent_off[s] - ch.abase;
+    if (rel >= ch.ce) break;
+    mine++;
+  }
+  tile.s_next += wp_wave_sum(mine, lane);
+  tile.cb = ch.abase + ch.ce;
+  return false;
+}
+
+// wp_sample_kernel's skeleton and B; C is the programme above, one lane per word.  There is no D, E or F: the kernel emits
+// nothing, so it is launched over the plan alone -- no scratch, no per-sentence arrays, no scan or gather behind it (tile_tok is
+// where wp_tile_begin notes a tile without a sentence).  A lane keeps its words' likelihood and the two word counts in registers;
+// the wave adds them up once, at the end of its tile, for one atomic each.
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_marginal_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpMarginalDev M, uint32_t *__restrict__ tile_tok) {
+  __shared__ WpMarginalLds L;
+  const int lane = threadIdx.x;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, nullptr, tile_tok, DirectOut{nullptr, nullptr, 0}, lane)) return;
+  WpTally tally{0, 0u, 0u};
+
+  for (;;) {
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    __syncthreads();
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *, int &stt, uint64_t) {
+        stt = SWT_WP_OK;
+        marginal_sentence(text, cls_tab, b, e, M, L.tok, L.sa, L.sx, tally);
+        return 0u;
+      };
+      if (wp_giant(L, tile, sent_off, WpNoOut{}, SWT_WP_OK, walk, lane)) break;
+      continue;
+    }
+
+    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
+    __syncthreads();
+
+    // ---- C. one lane per word
+    for (uint32_t k = lane; k < nc; k += 64) {
+      const uint32_t p0 = L.cand[k];
+      const uint32_t we = wp_word_end(L, ch, p0);
+      marginal_word(L.txt, p0, we, M, &L.tok[p0], &L.sa[p0], &L.sx[p0], tally);
+    }
+    __syncthreads();
+
+    if (wp_advance(tile, ch, sent_off, lane)) break;
+  }
+  unsigned long long like = (unsigned long long)tally.like;  // (two's complement: the sum is read as signed)
+  for (int d = 32; d >= 1; d >>= 1)
+    like += (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)like) |
+            (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)(like >> 32)) << 32;
+  const uint32_t words = wp_wave_sum(tally.words, lane), unk = wp_wave_sum(tally.unk, lane);
+  if (lane == 0) {
+    if (words) wp_tally_add(&M.stats[0], words);
+    if (unk) wp_tally_add(&M.stats[1], unk);
+    if (like) wp_tally_add(&M.stats[2], like);
+  }
+}
+
 }  // namespace swt
 
 using namespace swt;
@@ -2010,6 +2258,47 @@ static int wp_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes
   });
 }
 
+// swt_wp_expected_counts_dev: the outputs zeroed, the plan, and wp_marginal_kernel over its tiles -- one route at every size, and
+// of the tile workspace only the plan and tile_tok
+static int wp_marginal_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                           uint64_t *d_counts, uint64_t *d_stats, void *stream) {
+  if (!t || !d_sent_off || !d_stats || (t->H.n_vocab && !d_counts) || (n_bytes && !d_text)) return fail(SWT_ERR_INVALID, "null argument");
+  if (t->H.n_vocab > kVitIdMask + 1)
+    return fail(SWT_ERR_UNSUPPORTED, "the expected counts take vocabularies of up to %u tokens", kVitIdMask + 1);
+  if (int rc = wp_weights_set(t)) return rc;
+  int rc = wp_upload_sample(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t *d_cls = nullptr;
+  if ((rc = device_class_table(&d_cls))) return rc;
+  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
+  if (n_tiles > 0x7FFFFFFFull)
+    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
+  if ((rc = t->ws.plan.reserve((n_tiles + 1) * 8)) || (rc = t->ws.tile_tok.reserve((n_tiles + 1) * 4))) return rc;
+  if (t->H.n_vocab) SWT_HIP(hipMemsetAsync(d_counts, 0, (size_t)t->H.n_vocab * 8, st));
+  SWT_HIP(hipMemsetAsync(d_stats, 0, 3 * 8, st));
+  if (n_sent == 0) return SWT_OK;
+  WpMarginalDev M;
+  M.T = WpDev{};
+  M.T.edges = t->d_edges;
+  M.T.edge_bits = t->edge_bits;
+  M.T.root_sharp = t->H.root_sharp;
+  M.tok = t->d_tok;
+  M.weight = t->d_weight;
+  M.max_chars = t->max_word_chars;
+  M.counts = reinterpret_cast<unsigned long long *>(d_counts);
+  M.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  prof_begin(st, 2);
+  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
+  prof_begin(st);
+  hipLaunchKernelGGL(wp_marginal_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                     t->ws.plan.as<uint64_t>(), d_cls, M, t->ws.tile_tok.as<uint32_t>());
+  prof_end(st);
+  prof_end(st, 2);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+}
+
 // the draw of a dropout call from its three arguments
 static int wp_draw_args(uint64_t drop_below, uint64_t seed, uint32_t epoch, WpDrawArgs &d) {
   if (drop_below > (1ull << 32)) return fail(SWT_ERR_INVALID, "drop_below lies in [0, 2^32] (round(p * 2^32))");
@@ -2227,6 +2516,41 @@ int swt_wp_encode_sample(swt_wp_trie *t, const uint8_t *text, const uint64_t *se
     return wp_sample_dev(t, d_text, n_bytes, d_off, n, d_ids, d_out_off, d_status, d_n_tokens, seed, epoch, nullptr);
   };
   return host_encode(t->stage, enc, text, sent_off, n_sent, out_ids, out_cap, out_off, status, n_tokens);
+} SWT_API_CATCH
+
+int swt_wp_expected_counts_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                               uint64_t *d_counts, uint64_t *d_stats, void *stream) try {
+  return wp_marginal_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_counts, d_stats, stream);
+} SWT_API_CATCH
+
+// Host buffers: nothing of the host-call layer fits a call without ids, so the text and the offsets go up through the handle's
+// staging buffers, and the stats with the table behind them come back from one block of its out_off.  The weights are asked for before a device is.
+int swt_wp_expected_counts(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *counts,
+                           uint64_t *stats) try {
+  if (!t || !sent_off || !stats || (t->H.n_vocab && !counts)) return fail(SWT_ERR_INVALID, "null argument");
+  if (t->H.n_vocab > kVitIdMask + 1)
+    return fail(SWT_ERR_UNSUPPORTED, "the expected counts take vocabularies of up to %u tokens", kVitIdMask + 1);
+  if (int rc = wp_weights_set(t)) return rc;
+  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
+  for (uint64_t s = 0; s < n_sent; s++)
+    if (sent_off[s] > sent_off[s + 1])
+      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
+  const uint64_t n_bytes = sent_off[n_sent];
+  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
+  int rc = wp_upload_sample(t);
+  if (rc) return rc;
+  HostStage &hs = t->stage;
+  const size_t n_out = 3 + (size_t)t->H.n_vocab;
+  if ((rc = hs.in_text.reserve(n_bytes + 64)) || (rc = hs.in_off.reserve((n_sent + 1) * 8)) || (rc = hs.out_off.reserve(n_out * 8)))
+    return rc;
+  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
+  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
+  uint64_t *d_out = hs.out_off.as<uint64_t>();
+  if ((rc = wp_marginal_dev(t, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, d_out + 3, d_out, nullptr))) return rc;
+  SWT_HIP(hipStreamSynchronize(nullptr));
+  SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
+  if (t->H.n_vocab) SWT_HIP(hipMemcpy(counts, d_out + 3, (size_t)t->H.n_vocab * 8, hipMemcpyDeviceToHost));
+  return SWT_OK;
 } SWT_API_CATCH
 
 }  // extern "C"

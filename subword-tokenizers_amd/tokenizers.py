@@ -1259,7 +1259,7 @@ class UnigramWP(NaiveWP):
     word are its vocabulary tokens in their positions ('##' inside the word), totals are float32 sums, on equal totals the longer
     last piece wins, a word no segmentation reaches or of more than `max_word_chars` code points is one "[UNK]".  Ids index
     sorted(vocab) as NaiveWP's, so every batch call, encode_batch in all its forms and decode_batch are NaiveWP's bodies over the
-    Viterbi entries.  Scores come from set_scores, fit_scores (hard EM on the device) or load_resources; encoding without them
+    Viterbi entries.  Scores come from set_scores, fit_scores (hard or soft EM on the device) or load_resources; encoding without them
     raises ValueError.  encode_word stays NaiveWP's longest-match loop; tokenize runs the batch call on one text.
 
     sample = {"alpha": 0.1, "seed": 0, "epoch": 0} on encode_ids_batch, tokenize_batch, tokenize and encode_batch: subword
@@ -1314,27 +1314,72 @@ class UnigramWP(NaiveWP):
             raise TypeError("Text to tokenize must be a string.")
         return self.tokenize_batch([text], maxmatch_dropout=maxmatch_dropout, sample=sample)[0]
 
-    def fit_scores(self, corpus: List[str], iterations: int = 2, alpha: float = 1.0) -> List[int]:
-        """Hard EM on the device: segment the corpus, count every token (swt_token_histogram_dev), set
-        score = float32(log((count + alpha) / (total + alpha * len(vocab)))) -- the log taken here in float64, total = the
-        corpus's tokens with a vocabulary id -- and again.  Iteration 0 segments with NaiveWP's longest match, the later ones with
-        the best total under the scores of the one before.  The text goes to the device once and the ids never leave it.
-        -> the number of tokens (with "[UNK]"s) of every iteration's segmentation."""
-        import math
-
+    def _resident(self, corpus):
+        """the prepared corpus on the current device -> (d_text, its bytes, d_off, the device, the current stream)"""
         import torch
         if not isinstance(corpus, list) or not all(isinstance(t, str) for t in corpus):
             raise TypeError("corpus must be a list of strings.")
+        text, off = N.pack_and_lower(corpus) if self._normalizer is None else N.pack_utf8(self.normalize_batch(corpus))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
+        return d_text, int(text.size), torch.from_numpy(off.view(np.int64)).to(dev), dev, torch.cuda.current_stream().cuda_stream
+
+    def _expected(self, resident, n_sent):
+        """one E-step over a resident corpus -> (the raw counts tensor, words, UNK words, log2-likelihood)"""
+        import torch
+        d_text, n_bytes, d_off, dev, stream = resident
+        trie = self._ensure_scored_trie()
+        d_counts = torch.empty(trie.n_vocab + 3, dtype=torch.int64, device=dev)  # the stats first, the table behind them
+        trie.expected_counts_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_counts[3:].data_ptr(), d_counts.data_ptr(), 1.0, stream)
+        words, unk, like = d_counts[:3].tolist()
+        return d_counts[3:], words, unk, like * 2.0 ** -24
+
+    def expected_counts(self, corpus: List[str], device: bool = False) -> dict:
+        """The E-step of soft EM on the device (swt_wp_expected_counts, where the rule stands in full): every piece of every
+        word's lattice with its posterior probability under the weights exp(score) -- clamped to [2^-64, 2^64], the weights of
+        sample= at alpha 1 -- summed over the corpus.
+        -> {"counts": float64[len(vocab)] in the order of sorted(vocab) (device=True: the uint64 tensor of the device, in units of
+        2^-32, as int64), "words": the words that have a segmentation, "unk_words": those that have none or are longer than
+        max_word_chars, "log2_likelihood": the sum of log2 of the former's total weights}.  ValueError without scores."""
+        if self._scores is None:
+            raise ValueError("UnigramWP has no scores: set_scores, fit_scores, train or load_resources come before expected_counts")
+        counts, words, unk, like = self._expected(self._resident(corpus), len(corpus))
+        return {"counts": counts if device else counts.cpu().numpy().view(np.uint64).astype(np.float64) * 2.0 ** -32,
+                "words": words, "unk_words": unk, "log2_likelihood": like}
+
+    def fit_scores(self, corpus: List[str], iterations: int = 2, alpha: float = 1.0, method: str = "hard") -> list:
+        """EM on the device.  method="hard": segment the corpus, count every token (swt_token_histogram_dev), set
+        score = float32(log((count + alpha) / (total + alpha * len(vocab)))) -- the log taken here in float64, total = the
+        corpus's tokens with a vocabulary id -- and again.  Iteration 0 segments with NaiveWP's longest match, the later ones with
+        the best total under the scores of the one before.  The text goes to the device once and the ids never leave it.
+        -> the number of tokens (with "[UNK]"s) of every iteration's segmentation.
+        method="soft" (Kudo 2018): the count of a token is its expected count (expected_counts) under the scores of the iteration
+        before, the same formula makes the scores of it; without scores one hard iteration 0 seeds them and is not counted.
+        -> the log2-likelihood of the corpus at the start of every iteration (with alpha > 0 it is the smoothed objective that EM
+        cannot lower, not this number)."""
+        import math
+
+        import torch
+        if method not in ("hard", "soft"):
+            raise ValueError('method: "hard" or "soft"')
         if not isinstance(iterations, int) or iterations < 1:
             raise ValueError("iterations: an int of at least 1")
         if not alpha > 0 or not math.isfinite(alpha):
             raise ValueError("alpha: a positive float")
-        text, off = N.pack_and_lower(corpus) if self._normalizer is None else N.pack_utf8(self.normalize_batch(corpus))
-        n_bytes, n_sent, size = int(text.size), len(corpus), len(self.vocab)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        stream = torch.cuda.current_stream().cuda_stream
-        d_text = torch.from_numpy(np.concatenate([text, np.zeros(64, dtype=np.uint8)])).to(dev)
-        d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+        resident = self._resident(corpus)
+        d_text, n_bytes, d_off, dev, stream = resident
+        n_sent, size = len(corpus), len(self.vocab)
+        if method == "soft":
+            if self._scores is None:
+                self.fit_scores(corpus, 1, alpha)
+            likelihoods = []
+            for _ in range(iterations):
+                d_counts, _, _, like = self._expected(resident, n_sent)
+                counts = d_counts.cpu().numpy().view(np.uint64).astype(np.float64) * 2.0 ** -32
+                norm = float(counts.sum()) + alpha * size
+                self.set_scores({t: math.log((float(c) + alpha) / norm) for t, c in zip(self._naive_tokens, counts)})
+                likelihoods.append(like)
+            return likelihoods
         d_ids, d_tok_off = torch.empty(n_bytes + 64, dtype=torch.int32, device=dev), torch.empty(n_sent + 1, dtype=torch.int64, device=dev)
         d_status, d_ntok = torch.empty(n_sent + 8, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
         d_counts, d_oor = torch.empty(2 * (size + 2), dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
