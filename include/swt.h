@@ -430,6 +430,44 @@ int swt_wp_expected_counts_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n
                                uint64_t *d_counts, uint64_t *d_stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * UnigramWP, removal losses (the pruning step of Kudo 2018's trainer): for every piece, what the text's best total loses when the
+ * piece leaves the vocabulary -- exactly, for the Viterbi objective, every word searched again in its own context.  table has
+ * 3 * n_vocab entries, each third indexed as the vocabulary is: counts, then losses, then orphans.  stats has three.  The scores
+ * are swt_wp_trie_set_scores': without them both entries return SWT_ERR_STATE; a vocabulary of more than 2^21 tokens is
+ * SWT_ERR_UNSUPPORTED.  The `_dev` form takes device pointers and zeroes its outputs itself.  There is no joined form.
+ *
+ * Text preparation, splitting, piece(i, j), SWT_OPT_MAX_WORD_CHARS, the scores, the float32 forward pass with its one round-to-
+ * nearest add per candidate, the tie rule and the way back are exactly those of swt_wp_encode_viterbi.  For a word of n code
+ * points:
+ *   1. UNK word.  n > SWT_OPT_MAX_WORD_CHARS, or boundary n is not reached: stats[1] += 1 and nothing else.
+ *   2. Word with a path.  Otherwise B = best[n] and P = the pieces on the way back from n.  stats[0] += 1; stats[2] += fix(B) as a
+ *      signed 64-bit integer; counts[id] += 1 for every piece of P, a piece that stands twice counted twice.
+ *   3. Barred pass.  For every DISTINCT id t on P, once: the forward pass again, from boundary 0, with every candidate whose piece
+ *      has the id t skipped -- at every position where it turns up, not only where it stands on P.  Only the total matters; no way
+ *      back is kept.  A_t is what it leaves at boundary n.  Not reached: orphans[t] += 1 (the word would become an UNK word).
+ *      Reached: losses[t] += ufix(B, A_t).
+ *   4. Fixed point, in units of 2^-20.  ufix(B, A) = 0 when B == A compares equal (two equal infinities too); otherwise d = B - A,
+ *      one float32 round-to-nearest subtraction, and ufix = min(floor(d * 2^20), 2^40) (an infinite d gives 2^40).  fix(B) is
+ *      B * 2^20 truncated toward zero and clamped to +-2^40.  The scaling by 2^20 is exact in float32 wherever the clamp does not
+ *      apply: it moves the exponent only.
+ * A_t <= B always: the barred pass sees a subset of the candidates, and rounding to nearest is monotone -- x <= y gives
+ * x + s <= y + s after rounding -- so by induction over the boundaries no barred best[] exceeds the unbarred one, and a boundary
+ * the barred pass reaches the unbarred one reached.  So d >= 0 and the losses are unsigned.  (A loss of 0 is common: another
+ * segmentation ties, or the difference is below 2^-20.)
+ * So stats[0] counts the words with a segmentation, stats[1] the UNK words, stats[2] * 2^-20 is the text's Viterbi total, and
+ * removing t alone -- the other scores kept -- turns orphans[t] words into UNK words and lowers the sum of the other words'
+ * totals by losses[t] * 2^-20, up to the floor of each word's share (exactly, where all float sums are exact).  Every
+ * accumulation is a 64-bit integer atomic addition: the result does not depend on the order of lanes, waves or tiles, nor on the
+ * route of the call, and equals the rule's exactly.  Capacity: a word adds at most 2^40 to a loss or, in magnitude, to stats[2],
+ * so each sum is exact while it stays below 2^63: 2^23 clamped words at the least, and for words whose totals stay within +-2^11
+ * more than 2^31 of them.  One lane per word, the path and two barred lattices in LDS (csrc/swt_wp.hip, wp_prune_kernel;
+ * DESIGN.md 4.3h). */
+int swt_wp_removal_losses(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *table,
+                          int64_t *stats);
+int swt_wp_removal_losses_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                              uint64_t *d_table, int64_t *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's
  * zipf_distribution (source/benchmarks.py:240-253), over ids -- a '##' token and the same token without the prefix are
  * different strings and different ids.  counts has 2 * id_cap entries: counts[id & 0x7FFFFFFF] for ids without SWT_BPE_CONT,

@@ -112,6 +112,8 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "swt_wp_expected_counts": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u64p, u64p]),
     "swt_wp_expected_counts_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "swt_wp_removal_losses": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u64p, i64p]),
+    "swt_wp_removal_losses_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "swt_lower_of": (C.c_uint32, [C.c_uint32]),
     "swt_unidata_version": (C.c_char_p, []),
     "swt_utf8_lower": (C.c_int, [u8p, u64p, C.c_uint64, u8p]),
@@ -1529,6 +1531,17 @@ class WpTrie:
     def expected_counts_dev(self, d_text, n_bytes, d_off, n_sent, d_counts, d_stats, alpha=None, stream=0):
         self._at_alpha(alpha)
         check(lib().swt_wp_expected_counts_dev(self._h, d_text, n_bytes, d_off, n_sent, d_counts, d_stats, stream))
+
+    # UnigramWP, removal losses (swt_wp_removal_losses, include/swt.h) under set_scores' scores -> (table uint64[3, n_vocab]:
+    # counts, losses in units of 2^-20, orphans; stats int64[3]: words, UNK words, the Viterbi total in 2^-20)
+    def removal_losses(self, text_u8, sent_off):
+        table, stats = np.zeros((3, self.n_vocab), dtype=np.uint64), np.zeros(3, dtype=np.int64)
+        check(lib().swt_wp_removal_losses(self._h, ptr(text_u8, u8p), ptr(sent_off, u64p), int(sent_off.size - 1),
+                                          ptr(table, u64p) if table.size else None, ptr(stats, i64p)))
+        return table, stats
+
+    def removal_losses_dev(self, d_text, n_bytes, d_off, n_sent, d_table, d_stats, stream=0):
+        check(lib().swt_wp_removal_losses_dev(self._h, d_text, n_bytes, d_off, n_sent, d_table, d_stats, stream))
 
 
 def sample_weights(scores, alpha):

@@ -1618,6 +1618,20 @@ __device__ __forceinline__ uint32_t wp_wave_sum(uint32_t v, int lane) {
   return v;
 }
 
+// The end of a tile: the wave's sums of what its lanes have met, one atomic each into stats[0..3).
+__device__ __forceinline__ void wp_tally_flush(const WpTally &tally, unsigned long long *stats, int lane) {
+  unsigned long long like = (unsigned long long)tally.like;  // (two's complement: the sum is read as signed)
+  for (int d = 32; d >= 1; d >>= 1)
+    like += (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)like) |
+            (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)(like >> 32)) << 32;
+  const uint32_t words = wp_wave_sum(tally.words, lane), unk = wp_wave_sum(tally.unk, lane);
+  if (lane == 0) {
+    if (words) wp_tally_add(&stats[0], words);
+    if (unk) wp_tally_add(&stats[1], unk);
+    if (like) wp_tally_add(&stats[2], like);
+  }
+}
+
 __device__ __forceinline__ Wide wide_unpack(uint32_t m, uint32_t x16) {  // x16: the upper 16 bits of the exponent, in the low half
   if ((m & 0x00FFFFFFu) == 0u) return Wide{0.0f, 0};
   return Wide{__uint_as_float((m & 0x007FFFFFu) | 0x3F800000u), (int32_t)((x16 << 16) | ((m >> 24) << 8)) >> 8};
@@ -1819,16 +1833,191 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_marginal_kernel(
 
     if (wp_advance(tile, ch, sent_off, lane)) break;
   }
-  unsigned long long like = (unsigned long long)tally.like;  // (two's complement: the sum is read as signed)
-  for (int d = 32; d >= 1; d >>= 1)
-    like += (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)like) |
-            (unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)(uint32_t)(like >> 32)) << 32;
-  const uint32_t words = wp_wave_sum(tally.words, lane), unk = wp_wave_sum(tally.unk, lane);
-  if (lane == 0) {
-    if (words) wp_tally_add(&M.stats[0], words);
-    if (unk) wp_tally_add(&M.stats[1], unk);
-    if (like) wp_tally_add(&M.stats[2], like);
+  wp_tally_flush(tally, M.stats, lane);
+}
+
+// ---- UnigramWP, removal losses: what the text's best total loses when a piece leaves the vocabulary, per piece (include/swt.h,
+// swt_wp_removal_losses) -----------------------------------------------------------------------------------------
+//
+// A word's first pass is viterbi_word's, its path written to path[] -- a third array of the word's own slots, which outlives the
+// barred passes.  A barred pass keeps no way back, so a boundary needs one word and not two: tok[] and best[] of the word are
+// free once the path stands in path[], and each takes the totals of ONE barred piece.  One walk of the trie from a start -- the
+// probes of the edge hash in global memory, which are what a pass costs -- therefore relaxes two barred lattices at once, and a
+// word of D distinct pieces takes 1 + ceil(D / 2) walks over its starts and not 1 + D.  A slot holds the bits of a float32 total,
+// kInvalidTok (a NaN no sum of finite scores makes) while its boundary is not reached.
+struct WpPruneDev {
+  WpViterbiDev V;
+  unsigned long long *table;  // counts, losses, orphans: n_vocab entries each
+  unsigned long long *stats;  // words with a path, UNK words, the sum of fix(B)
+  uint32_t n_vocab;
+};
+constexpr double kPruneOne = 1048576.0, kPruneClamp = 1099511627776.0;  // 2^20, the fixed point's unit; 2^40, its clamp
+
+// fix(B): B * 2^20 toward zero, within +-2^40 (the product is exact in a double, as it is in float32 wherever it fits)
+__device__ __forceinline__ long long prune_fix(float b) {
+  const double x = (double)b * kPruneOne;
+  return x >= kPruneClamp ? 1ll << 40 : x <= -kPruneClamp ? -(1ll << 40) : (long long)x;
+}
+// ufix(B, A), A <= B: 0 when they compare equal (two equal infinities too), else floor((B - A) * 2^20), at most 2^40
+__device__ __forceinline__ unsigned long long prune_ufix(float b, float a) {
+  if (b == a) return 0ull;
+  const double d = (double)__fsub_rn(b, a) * kPruneOne;
+  return d >= kPruneClamp ? 1ull << 40 : d > 0.0 ? (unsigned long long)d : 0ull;
+}
+
+// one candidate into slot j of a barred lattice
+__device__ __forceinline__ void prune_relax(uint32_t *f, uint32_t j, float cand) {
+  const uint32_t cur = f[j];
+  if (cur == kInvalidTok || cand > __uint_as_float(cur)) f[j] = __float_as_uint(cand);
+}
+
+// The forward pass of a word of n code points with the piece t0 barred in fa[] and, if `two`, t1 in fb[]: viterbi_word's starts,
+// walks and adds, every candidate whose id is the lattice's barred one skipped, at whatever start it turns up.  A start walks when
+// either lattice has reached it.  The totals of boundary n end in fa[n - 1] and fb[n - 1].
+__device__ __forceinline__ void prune_barred(const uint8_t *txt, uint64_t wb, uint64_t we, const WpViterbiDev &V, uint32_t n,
+                                             uint32_t t0, uint32_t t1, bool two, uint32_t *fa, uint32_t *fb) {
+  for (uint32_t k = 0; k < n; k++) fa[k] = fb[k] = kInvalidTok;
+  uint64_t pi = wb;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t ua = i ? fa[i - 1] : 0u, ub = !two ? kInvalidTok : i ? fb[i - 1] : 0u;  // (0: the bits of +0.0f)
+    if (ua != kInvalidTok || ub != kInvalidTok) {
+      uint32_t node = i ? V.T.root_sharp : kWpRoot;
+      uint64_t q = pi;
+      for (uint32_t j = i; q < we; j++) {  // j: the slot of boundary j + 1
+        const uint32_t cp = wp_next_cp(txt, q, we);
+        const int32_t c = edge_lookup(V.T, node, cp);
+        if (c < 0) break;
+        node = (uint32_t)c;
+        const int32_t v = V.tok[node];
+        if (v < 0) continue;
+        const float s = V.score[v];
+        if (ua != kInvalidTok && (uint32_t)v != t0) prune_relax(fa, j, __fadd_rn(__uint_as_float(ua), s));
+        if (ub != kInvalidTok && (uint32_t)v != t1) prune_relax(fb, j, __fadd_rn(__uint_as_float(ub), s));
+      }
+    }
+    (void)wp_next_cp(txt, pi, we);
   }
+}
+
+// what a barred lattice says of its piece: the word is lost without it, or poorer by ufix
+__device__ __forceinline__ void prune_settle(const WpPruneDev &P, uint32_t t, float b, uint32_t a) {
+  if (a == kInvalidTok) {
+    wp_tally_add(&P.table[2ull * P.n_vocab + t], 1ull);
+  } else if (const unsigned long long u = prune_ufix(b, __uint_as_float(a))) {
+    wp_tally_add(&P.table[(uint64_t)P.n_vocab + t], u);
+  }
+}
+
+// One word [wb, we) of txt; dp, best and path hold as many words as the word has code points, at most max_chars.  Each distinct
+// id of the path gets one add of its occurrences into counts[], and waits in `held` for a second one to share a barred pass with.
+__device__ __forceinline__ void prune_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpPruneDev &P, uint32_t *dp,
+                                           float *best, uint32_t *path, WpTally &tally) {
+  uint32_t n = 0;
+  for (uint64_t q = wb; q < we && n <= P.V.max_chars; n++) (void)wp_next_cp(txt, q, we);
+  if (n > P.V.max_chars) {
+    tally.unk++;
+    return;
+  }
+  const uint32_t m = viterbi_word<false>(txt, wb, we, P.V, dp, best, path);
+  if (path[0] == P.V.unk_id) {  // (no id of the vocabulary: boundary n was not reached)
+    tally.unk++;
+    return;
+  }
+  const float b = best[n - 1];
+  tally.words++;
+  tally.like += prune_fix(b);
+  uint32_t *fa = dp, *fb = reinterpret_cast<uint32_t *>(best);
+  uint32_t held = kInvalidTok;
+  for (uint32_t k = 0; k < m; k++) {
+    const uint32_t t = path[k];
+    uint32_t seen = 0, occ = 1;
+    for (uint32_t e = 0; e < k; e++) seen |= path[e] == t;
+    if (seen) continue;  // handled where it first stood
+    for (uint32_t e = k + 1; e < m; e++) occ += path[e] == t;
+    wp_tally_add(&P.table[t], occ);
+    if (held == kInvalidTok) {
+      held = t;
+      continue;
+    }
+    prune_barred(txt, wb, we, P.V, n, held, t, true, fa, fb);
+    prune_settle(P, held, b, fa[n - 1]);
+    prune_settle(P, t, b, fb[n - 1]);
+    held = kInvalidTok;
+  }
+  if (held != kInvalidTok) {
+    prune_barred(txt, wb, we, P.V, n, held, kInvalidTok, false, fa, fb);
+    prune_settle(P, held, b, fa[n - 1]);
+  }
+}
+
+// A whole sentence [b, e) by one lane (sentences longer than a chunk): viterbi_sentence's split, every word through the programme
+// above with its state in the wave's LDS arrays, idle while its one lane walks.
+__device__ void prune_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, const WpPruneDev &P, uint32_t *dp,
+                               float *best, uint32_t *path, WpTally &tally) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    prune_word(txt, p, q, P, dp, best, path, tally);
+    p = q;
+  }
+}
+
+// 17,040 bytes of LDS, as WpMarginalLds: WpViterbiLds and the path.  A type of its own, so that wp_words and wp_word_end are
+// instantiated for this kernel apart.
+struct alignas(16) WpPruneLds : WpViterbiLds {
+  uint32_t path[kWpCap];  // per piece of a word's best path, in the word's own bytes: its id
+};
+
+// wp_marginal_kernel's skeleton, B and end; C is the programme above, one lane per word.  Launched over the plan alone.
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_prune_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpPruneDev P, uint32_t *__restrict__ tile_tok) {
+  __shared__ WpPruneLds L;
+  const int lane = threadIdx.x;
+  WpTile tile;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, nullptr, tile_tok, DirectOut{nullptr, nullptr, 0}, lane)) return;
+  WpTally tally{0, 0u, 0u};
+
+  for (;;) {
+    WpChunk ch;
+    wp_stage(L, tile, ch, text, n_bytes, lane);
+    __syncthreads();
+    if (!wp_mark(L, tile, ch, sent_off, lane)) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *, int &stt, uint64_t) {
+        stt = SWT_WP_OK;
+        prune_sentence(text, cls_tab, b, e, P, L.tok, L.best, L.path, tally);
+        return 0u;
+      };
+      if (wp_giant(L, tile, sent_off, WpNoOut{}, SWT_WP_OK, walk, lane)) break;
+      continue;
+    }
+
+    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
+    __syncthreads();
+
+    // ---- C. one lane per word
+    for (uint32_t k = lane; k < nc; k += 64) {
+      const uint32_t p0 = L.cand[k];
+      const uint32_t we = wp_word_end(L, ch, p0);
+      prune_word(L.txt, p0, we, P, &L.tok[p0], &L.best[p0], &L.path[p0], tally);
+    }
+    __syncthreads();
+
+    if (wp_advance(tile, ch, sent_off, lane)) break;
+  }
+  wp_tally_flush(tally, P.stats, lane);
 }
 
 }  // namespace swt
@@ -2299,6 +2488,48 @@ static int wp_marginal_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_byt
   return SWT_OK;
 }
 
+// swt_wp_removal_losses_dev: wp_marginal_dev's route with wp_prune_kernel, under the scores
+static int wp_prune_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                        uint64_t *d_table, int64_t *d_stats, void *stream) {
+  if (!t || !d_sent_off || !d_stats || (t->H.n_vocab && !d_table) || (n_bytes && !d_text)) return fail(SWT_ERR_INVALID, "null argument");
+  if (t->H.n_vocab > kVitIdMask + 1)
+    return fail(SWT_ERR_UNSUPPORTED, "the removal losses take vocabularies of up to %u tokens", kVitIdMask + 1);
+  if (int rc = wp_scores_set(t)) return rc;
+  int rc = wp_upload_viterbi(t);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t *d_cls = nullptr;
+  if ((rc = device_class_table(&d_cls))) return rc;
+  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
+  if (n_tiles > 0x7FFFFFFFull)
+    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
+  if ((rc = t->ws.plan.reserve((n_tiles + 1) * 8)) || (rc = t->ws.tile_tok.reserve((n_tiles + 1) * 4))) return rc;
+  if (t->H.n_vocab) SWT_HIP(hipMemsetAsync(d_table, 0, (size_t)t->H.n_vocab * 3 * 8, st));
+  SWT_HIP(hipMemsetAsync(d_stats, 0, 3 * 8, st));
+  if (n_sent == 0) return SWT_OK;
+  WpPruneDev P;
+  P.V.T = WpDev{};
+  P.V.T.edges = t->d_edges;
+  P.V.T.edge_bits = t->edge_bits;
+  P.V.T.root_sharp = t->H.root_sharp;
+  P.V.tok = t->d_tok;
+  P.V.score = t->d_score;
+  P.V.unk_id = t->H.n_vocab + 1;
+  P.V.max_chars = t->max_word_chars;
+  P.table = reinterpret_cast<unsigned long long *>(d_table);
+  P.stats = reinterpret_cast<unsigned long long *>(d_stats);
+  P.n_vocab = t->H.n_vocab;
+  prof_begin(st, 2);
+  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
+  prof_begin(st);
+  hipLaunchKernelGGL(wp_prune_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
+                     t->ws.plan.as<uint64_t>(), d_cls, P, t->ws.tile_tok.as<uint32_t>());
+  prof_end(st);
+  prof_end(st, 2);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+}
+
 // the draw of a dropout call from its three arguments
 static int wp_draw_args(uint64_t drop_below, uint64_t seed, uint32_t epoch, WpDrawArgs &d) {
   if (drop_below > (1ull << 32)) return fail(SWT_ERR_INVALID, "drop_below lies in [0, 2^32] (round(p * 2^32))");
@@ -2550,6 +2781,41 @@ int swt_wp_expected_counts(swt_wp_trie *t, const uint8_t *text, const uint64_t *
   SWT_HIP(hipStreamSynchronize(nullptr));
   SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
   if (t->H.n_vocab) SWT_HIP(hipMemcpy(counts, d_out + 3, (size_t)t->H.n_vocab * 8, hipMemcpyDeviceToHost));
+  return SWT_OK;
+} SWT_API_CATCH
+
+int swt_wp_removal_losses_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
+                              uint64_t *d_table, int64_t *d_stats, void *stream) try {
+  return wp_prune_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_table, d_stats, stream);
+} SWT_API_CATCH
+
+// Host buffers, as swt_wp_expected_counts: up through the handle's staging buffers, the stats and the table back from one block.
+int swt_wp_removal_losses(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *table,
+                          int64_t *stats) try {
+  if (!t || !sent_off || !stats || (t->H.n_vocab && !table)) return fail(SWT_ERR_INVALID, "null argument");
+  if (t->H.n_vocab > kVitIdMask + 1)
+    return fail(SWT_ERR_UNSUPPORTED, "the removal losses take vocabularies of up to %u tokens", kVitIdMask + 1);
+  if (int rc = wp_scores_set(t)) return rc;
+  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
+  for (uint64_t s = 0; s < n_sent; s++)
+    if (sent_off[s] > sent_off[s + 1])
+      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
+  const uint64_t n_bytes = sent_off[n_sent];
+  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
+  int rc = wp_upload_viterbi(t);
+  if (rc) return rc;
+  HostStage &hs = t->stage;
+  const size_t n_table = 3 * (size_t)t->H.n_vocab;
+  if ((rc = hs.in_text.reserve(n_bytes + 64)) || (rc = hs.in_off.reserve((n_sent + 1) * 8)) || (rc = hs.out_off.reserve((3 + n_table) * 8)))
+    return rc;
+  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
+  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
+  uint64_t *d_out = hs.out_off.as<uint64_t>();
+  if ((rc = wp_prune_dev(t, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, d_out + 3, reinterpret_cast<int64_t *>(d_out), nullptr)))
+    return rc;
+  SWT_HIP(hipStreamSynchronize(nullptr));
+  SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
+  if (n_table) SWT_HIP(hipMemcpy(table, d_out + 3, n_table * 8, hipMemcpyDeviceToHost));
   return SWT_OK;
 } SWT_API_CATCH
 

@@ -1406,6 +1406,95 @@ class UnigramWP(NaiveWP):
         super().train(corpus, max_vocab)
         self.fit_scores(corpus)
 
+    def removal_losses(self, corpus: List[str], device: bool = False) -> dict:
+        """The pruning step's question on the device (swt_wp_removal_losses, where the rule stands in full): for every piece,
+        what the corpus's best total loses when the piece alone leaves the vocabulary, every word that uses it searched again in
+        its own context.
+        -> {"counts": int64[len(vocab)] in the order of sorted(vocab), the pieces of the best segmentations; "loss": float64 in
+        nats, the sum over the words that keep a segmentation; "orphaned": int64, the words that would become "[UNK]"; "words",
+        "unk_words" and "viterbi_total" (nats) of the corpus as it is}.  device=True: the three arrays are int64 tensors of the
+        device, "loss" in units of 2^-20.  ValueError without scores."""
+        import torch
+        if self._scores is None:
+            raise ValueError("UnigramWP has no scores: set_scores, fit_scores, train or load_resources come before removal_losses")
+        d_text, n_bytes, d_off, dev, stream = self._resident(corpus)
+        trie = self._ensure_scored_trie()
+        size = trie.n_vocab
+        d_out = torch.empty(3 + 3 * size, dtype=torch.int64, device=dev)  # the stats first, the table behind them
+        trie.removal_losses_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), len(corpus), d_out[3:].data_ptr(), d_out.data_ptr(), stream)
+        words, unk, total = d_out[:3].tolist()
+        counts, loss, orphaned = d_out[3:].view(3, size) if device else d_out[3:].cpu().numpy().reshape(3, size)
+        return {"counts": counts, "loss": loss if device else loss.astype(np.float64) * 2.0 ** -20, "orphaned": orphaned,
+                "words": words, "unk_words": unk, "viterbi_total": total * 2.0 ** -20}
+
+    def _mandatory(self, token: str) -> bool:
+        return token in ("[UNK]", "[CLS]", "[SEP]", "[PAD]", "[MASK]") or len(token) == 1 or (len(token) == 3 and token.startswith("##"))
+
+    def prune(self, corpus: List[str], max_vocab: int, losses: Optional[dict] = None) -> List[str]:
+        """Drop the pieces the corpus misses least until `max_vocab` are left (Kudo 2018's pruning step, with removal_losses'
+        exact figures; `losses`: its result for this corpus, vocabulary and scores, taken here when None).  Always kept: the
+        special tokens the vocabulary holds, every piece of one code point ('x' and '##x'), every piece with orphaned > 0.  The
+        rest rank by loss (greater first), then count (greater first), then token; if the mandatory ones alone exceed max_vocab,
+        exactly they stay.  The removed tokens leave `vocab` and the scores, the tries are dropped, the surviving scores stay as
+        they are (fit_scores refits them).  -> the removed tokens, sorted."""
+        if not isinstance(max_vocab, int) or isinstance(max_vocab, bool) or max_vocab < 1:
+            raise ValueError("max_vocab: an int of at least 1")
+        if losses is None:
+            losses = self.removal_losses(corpus)
+        if self._scores is None:
+            raise ValueError("UnigramWP has no scores: set_scores, fit_scores, train or load_resources come before prune")
+        tokens = sorted(self.vocab)
+        loss, counts, orphaned = (np.asarray(losses[k]) for k in ("loss", "counts", "orphaned"))
+        if not loss.shape == counts.shape == orphaned.shape == (len(tokens),):
+            raise ValueError("losses: not removal_losses' result for this vocabulary")
+        rest = [k for k, t in enumerate(tokens) if not self._mandatory(t) and not orphaned[k]]
+        rest.sort(key=lambda k: (-loss[k], -counts[k], tokens[k]))
+        removed = sorted(tokens[k] for k in rest[max(0, max_vocab - (len(tokens) - len(rest))):])
+        self.vocab -= set(removed)
+        self._scores = {t: s for t, s in self._scores.items() if t in self.vocab}
+        self._drop_naive_trie()
+        self._scored_trie = None
+        return removed
+
+    def train_unigram(self, corpus: List[str], max_vocab: int, seed_vocab=None, seed_factor: int = 4, shrink: float = 0.75,
+                      iterations: int = 2, alpha: float = 1.0, method: str = "soft") -> list:
+        """Kudo 2018's trainer: a seed vocabulary -- `seed_vocab`, or NaiveWP.train(corpus, seed_factor * max_vocab) -- fitted
+        with fit_scores(corpus, iterations, alpha, method), then, while it is larger than max_vocab: removal_losses, prune to
+        max(max_vocab, floor(shrink * len(vocab))), fit_scores again.  It ends early when only what prune always keeps is left.
+        -> per round (the vocabulary's size, viterbi_total, unk_words) as its removal_losses found them, before the round's
+        prune; the final size is len(vocab).  The arguments are checked before any device work."""
+        import math
+        if not isinstance(corpus, list) or not all(isinstance(t, str) for t in corpus):
+            raise TypeError("corpus must be a list of strings.")
+        if not isinstance(max_vocab, int) or isinstance(max_vocab, bool) or max_vocab < 1:
+            raise ValueError("max_vocab: an int of at least 1")
+        if seed_vocab is not None and (isinstance(seed_vocab, str) or not all(isinstance(t, str) for t in seed_vocab)):
+            raise TypeError("seed_vocab: tokens as strings")
+        if not isinstance(seed_factor, int) or isinstance(seed_factor, bool) or seed_factor < 1:
+            raise ValueError("seed_factor: an int of at least 1")
+        if not isinstance(shrink, float) or not 0.0 < shrink < 1.0:
+            raise ValueError("shrink: a float in (0, 1)")
+        if method not in ("hard", "soft"):
+            raise ValueError('method: "hard" or "soft"')
+        if not isinstance(iterations, int) or iterations < 1:
+            raise ValueError("iterations: an int of at least 1")
+        if not alpha > 0 or not math.isfinite(alpha):
+            raise ValueError("alpha: a positive float")
+        if seed_vocab is None:
+            NaiveWP.train(self, corpus, seed_factor * max_vocab)
+        else:
+            self.reset()
+            self.vocab = set(seed_vocab)
+        self.fit_scores(corpus, iterations, alpha, method)
+        rounds = []
+        while len(self.vocab) > max_vocab:
+            losses = self.removal_losses(corpus)
+            rounds.append((len(self.vocab), losses["viterbi_total"], losses["unk_words"]))
+            if not self.prune(corpus, max(max_vocab, int(math.floor(shrink * len(self.vocab)))), losses):
+                break
+            self.fit_scores(corpus, iterations, alpha, method)
+        return rounds
+
     def reset(self) -> None:
         super().reset()
         self._scores, self._scored_trie = None, None
