@@ -45,7 +45,8 @@ extern "C" {
 #define SWT_ERR_HIP (-4)          /* a HIP call failed */
 #define SWT_ERR_UNSUPPORTED (-5)
 #define SWT_ERR_STATE (-6)        /* call out of order, or an internal capacity check failed (the handle is unusable) */
-#define SWT_ERR_NOMEM (-7)        /* host memory exhausted (std::bad_alloc / std::length_error inside the library) */
+#define SWT_ERR_NOMEM (-7)        /* host memory exhausted (std::bad_alloc / std::length_error inside the library); a table the
+                                     caller sized is full (swt_substring_counts) */
 #define SWT_ERR_INTERNAL (-8)     /* any other C++ exception stopped at the ABI boundary */
 
 #define SWT_SYM_BASE 0x110000u
@@ -466,6 +467,49 @@ int swt_wp_removal_losses(swt_wp_trie *t, const uint8_t *text, const uint64_t *s
                           int64_t *stats);
 int swt_wp_removal_losses_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                               uint64_t *d_table, int64_t *d_stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * UnigramWP, seed pieces: the substrings of the corpus's words with their frequencies, counted on the device -- the candidates
+ * Kudo 2018's trainer starts from (UnigramWP.seed_substrings ranks them by count x length).
+ *
+ * Input.  The unique words as code points: sym, word_off[n_words + 1] (word_off[0] = 0, non-decreasing) and freq[n_words], the
+ * arrays swt_bpe_train_create_words takes and the device's word census makes.
+ * Parameters.  max_chars L in 2..32; min_count >= 1; max_word: 0, or 1..1024 -- a word of more code points contributes nothing
+ * (UnigramWP spells it "[UNK]" whatever the vocabulary is); table_bits: 0 (the library sizes the table) or 4..30.  Anything else
+ * is SWT_ERR_INVALID.
+ * Counting.  For a word c[0..n) of frequency f that max_word lets through: for every start i in [0, n) and every length l in
+ * [2, min(L, n - i)] the key is (i > 0, c[i..i+l)) and count[key] += f, in unsigned 64-bit integers.  Overlapping occurrences
+ * in one word each count: in "aaaa" the key (1, "aa") gets 2 f and the key (0, "aa") gets f.  The flag is the '##' of the
+ * WordPiece spelling: "ab" and "##ab" are different keys.  Pieces of one code point are not counted (the trainer's base symbols
+ * cover them); a word of frequency 0 and an empty word add nothing.
+ * Output.  Every key with count >= min_count, once each, in no particular order: entry k is out_flag[k], out_count[k] and the code
+ * points out_cps[out_off[k] .. out_off[k + 1]); out_off[0] = 0.  *n_out entries and *n_cps code points.  out_off has room for
+ * out_cap + 1 values, out_flag and out_count for out_cap, out_cps for cps_cap; when *n_out > out_cap or *n_cps > cps_cap the call
+ * returns SWT_ERR_CAPACITY with both numbers set to what is needed, and has written nothing at or past a capacity (a capacity of
+ * 0 with NULL outputs asks for the numbers).
+ * The table.  2^table_bits slots, which must stay MORE than the distinct keys (of any count): otherwise the call returns
+ * SWT_ERR_NOMEM with a message and no output -- for a full table or one with no slot left, whatever the order of the insertions.
+ * table_bits = 0 counts the insertions first and takes the power of two from 2 * insertions + 16 up (1,024 at the least; more
+ * than 2^30: SWT_ERR_UNSUPPORTED), which the distinct keys cannot fill.
+ * Every accumulation is an integer atomic addition, so the counts do not depend on the order of lanes, waves or tiles.  Sums are
+ * exact below 2^64.  The `_dev` form takes device pointers for the arrays (n_out and n_cps stay host pointers), trusts word_off
+ * to be non-decreasing, works on the stream and synchronises it before it returns.  The `_text_dev` form takes prepared text as the
+ * encoders' `_dev` entries do, runs the word census of swt_bpe_train_create_text on it and the same kernels on the word list,
+ * which never leaves the device; base_out[0 .. min(*n_base, base_cap)) receives the distinct code points of the words, ascending
+ * (host memory; may be NULL with base_cap = 0).  swt_substring_counts_capacity: the start positions of one wavefront's tile, the
+ * positions staged behind it, and the largest max_chars (csrc/swt_seed.hip). */
+int swt_substring_counts(const uint32_t *sym, const uint64_t *word_off, const uint32_t *freq, uint64_t n_words, uint32_t max_chars,
+                         uint64_t min_count, uint32_t max_word, uint32_t table_bits, uint64_t *out_off, uint32_t *out_cps, uint8_t *out_flag,
+                         uint64_t *out_count, uint64_t out_cap, uint64_t cps_cap, uint64_t *n_out, uint64_t *n_cps);
+int swt_substring_counts_dev(const uint32_t *d_sym, const uint64_t *d_word_off, const uint32_t *d_freq, uint64_t n_words, uint32_t max_chars,
+                             uint64_t min_count, uint32_t max_word, uint32_t table_bits, uint64_t *d_out_off, uint32_t *d_out_cps,
+                             uint8_t *d_out_flag, uint64_t *d_out_count, uint64_t out_cap, uint64_t cps_cap, uint64_t *n_out, uint64_t *n_cps,
+                             void *stream);
+int swt_substring_counts_text_dev(const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent, uint32_t max_chars,
+                                  uint64_t min_count, uint32_t max_word, uint32_t table_bits, uint64_t *d_out_off, uint32_t *d_out_cps,
+                                  uint8_t *d_out_flag, uint64_t *d_out_count, uint64_t out_cap, uint64_t cps_cap, uint64_t *n_out,
+                                  uint64_t *n_cps, uint32_t *base_out, uint32_t base_cap, uint32_t *n_base, void *stream);
+int swt_substring_counts_capacity(uint32_t *tile, uint32_t *halo, uint32_t *max_chars);
 
 /* ------------------------------------------------------------------------------------------------
  * Token-id histogram on the device: the Counter over token strings of the reference's

@@ -127,6 +127,13 @@ SIGNATURES = {
     "swt_token_equivalence_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "swt_substring_counts": (C.c_int, [u32p, u64p, u32p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, u64p, u32p, u8p, u64p,
+                                       C.c_uint64, C.c_uint64, u64p, u64p]),
+    "swt_substring_counts_dev": (C.c_int, [C.c_void_p] * 3 + [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 +
+                                 [C.c_uint64, C.c_uint64, u64p, u64p, C.c_void_p]),
+    "swt_substring_counts_text_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32] +
+                                      [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, u64p, u64p, u32p, C.c_uint32, u32p, C.c_void_p]),
+    "swt_substring_counts_capacity": (C.c_int, [u32p, u32p, u32p]),
     "swt_token_equivalence_capacity": (C.c_int, [u32p, u32p]),
     "swt_token_spans": (C.c_int, [u8p, u64p, C.c_uint64, u32p, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u32p, u32p, u8p]),
     "swt_token_spans_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -513,6 +520,53 @@ def token_histogram(ids, id_cap):
     if oor:
         raise ValueError("%d token ids are outside [0, %d)" % (oor, id_cap))
     return counts
+
+
+def substring_counts_capacity():
+    """-> (tile, halo, max_chars): the start positions one wavefront of swt_substring_counts takes, the positions it stages behind
+    them, and the largest max_chars (csrc/swt_seed.hip)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_substring_counts_capacity(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def substring_counts_into(sym, word_off, freq, max_chars, min_count, max_word, table_bits, out_off, out_cps, out_flag, out_count,
+                          out_cap=None, cps_cap=None):
+    """swt_substring_counts as it is, into the caller's arrays (None = NULL with a capacity of 0; the capacities are the sizes of
+    out_flag and out_cps unless given): -> (status, entries, code points)"""
+    sym, word_off = np.ascontiguousarray(sym, dtype=np.uint32), np.ascontiguousarray(word_off, dtype=np.uint64)
+    freq = np.ascontiguousarray(freq, dtype=np.uint32)
+    n, m = C.c_uint64(), C.c_uint64()
+    rc = lib().swt_substring_counts(ptr(sym, u32p) if sym.size else None, ptr(word_off, u64p), ptr(freq, u32p) if freq.size else None,
+                                    int(word_off.size - 1), max_chars, min_count, max_word, table_bits,
+                                    None if out_off is None else ptr(out_off, u64p), None if out_cps is None else ptr(out_cps, u32p),
+                                    None if out_flag is None else ptr(out_flag, u8p), None if out_count is None else ptr(out_count, u64p),
+                                    out_cap if out_cap is not None else 0 if out_flag is None else int(out_flag.size),
+                                    cps_cap if cps_cap is not None else 0 if out_cps is None else int(out_cps.size), C.byref(n), C.byref(m))
+    return rc, n.value, m.value
+
+
+def substring_counts(sym, word_off, freq, max_chars, min_count=1, max_word=0, table_bits=0):
+    """The substring census of include/swt.h (swt_substring_counts) over a host word list -> (off uint64[n + 1], cps uint32, flag
+    uint8[n], count uint64[n]), the entries in no particular order.  The numbers are asked for first, then the call is made again."""
+    rc, n, m = substring_counts_into(sym, word_off, freq, max_chars, min_count, max_word, table_bits, None, None, None, None)
+    if rc not in (0, ERR_CAPACITY):
+        check(rc)
+    off, cps = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(m, 1), dtype=np.uint32)
+    flag, count = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        check(substring_counts_into(sym, word_off, freq, max_chars, min_count, max_word, table_bits, off, cps, flag, count)[0])
+    return off, cps[:m], flag[:n], count[:n]
+
+
+def substring_counts_text_dev(d_text, n_bytes, d_off, n_sent, max_chars, min_count, max_word, d_out, out_cap, cps_cap, base_cap=0, stream=None):
+    """swt_substring_counts_text_dev over prepared resident text, table_bits = 0; d_out = the device pointers (off, cps, flag, count)
+    -> (status, entries, code points, the words' distinct code points uint32 or None when base_cap is too small)"""
+    n, m, nb = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    base = np.zeros(max(base_cap, 1), dtype=np.uint32)
+    rc = lib().swt_substring_counts_text_dev(d_text, n_bytes, d_off, n_sent, max_chars, min_count, max_word, 0, *d_out, out_cap, cps_cap,
+                                             C.byref(n), C.byref(m), ptr(base, u32p), base_cap, C.byref(nb), stream)
+    return rc, n.value, m.value, base[:nb.value] if nb.value <= base_cap else None
 
 
 def token_equivalence_capacity():

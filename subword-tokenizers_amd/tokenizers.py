@@ -1456,9 +1456,56 @@ class UnigramWP(NaiveWP):
         self._scored_trie = None
         return removed
 
+    def seed_substrings(self, corpus: List[str], size: int, max_piece_chars: int = 16, min_count: int = 2, return_counts: bool = False):
+        """Kudo 2018's seed vocabulary from the corpus's most frequent substrings, counted on the device (swt_substring_counts,
+        where the rule stands in full): every token NaiveWP.train starts from before its first merge -- each code point of the
+        corpus's words as 'c' and '##c' -- and then the pieces of 2..max_piece_chars code points that occur min_count times or
+        more ('##' for a piece that does not start its word), in the order (greater count x length, greater count, smaller token)
+        until `size` tokens are reached.  Words of more than max_word_chars code points are not counted.  The corpus goes through
+        the normalizer as for fit_scores; the word list never leaves the device, the entries are ranked here with NumPy.
+        -> the sorted tokens; return_counts=True: (the tokens, {piece: count} of the pieces among them).  The vocabulary and the
+        scores stay as they are.  The arguments are checked before any device work."""
+        import torch
+        if not isinstance(corpus, list) or not all(isinstance(t, str) for t in corpus):
+            raise TypeError("corpus must be a list of strings.")
+        for name, value, low, high in (("size", size, 1, 1 << 62), ("max_piece_chars", max_piece_chars, 2, 32), ("min_count", min_count, 1, 1 << 62)):
+            if not isinstance(value, int) or isinstance(value, bool) or not low <= value <= high:
+                raise ValueError("%s: an int in %d..%d" % (name, low, high))
+        d_text, n_bytes, d_off, dev, stream = self._resident(corpus)
+        out_cap = min(n_bytes // 2 + 1024, 1 << 23)  # a guess; when it is too small the call says what it takes
+        cps_cap = 6 * out_cap
+        for _ in range(2):
+            d_o, d_c = torch.empty(out_cap + 1, dtype=torch.int64, device=dev), torch.empty(cps_cap + 1, dtype=torch.int32, device=dev)
+            d_f, d_n = torch.empty(out_cap + 1, dtype=torch.uint8, device=dev), torch.empty(out_cap + 1, dtype=torch.int64, device=dev)
+            rc, n, m, base = N.substring_counts_text_dev(d_text.data_ptr(), n_bytes, d_off.data_ptr(), len(corpus), max_piece_chars, min_count,
+                                                         self.max_word_chars, [t.data_ptr() for t in (d_o, d_c, d_f, d_n)], out_cap, cps_cap,
+                                                         0x110000, stream)
+            if rc != N.ERR_CAPACITY:
+                break
+            out_cap, cps_cap = n, m
+        N.check(rc)
+        tokens = {chr(int(c)) for c in base} | {"##" + chr(int(c)) for c in base}
+        off, count = d_o[:n + 1].cpu().numpy().astype(np.int64), d_n[:n].cpu().numpy().view(np.uint64)
+        cps, flag = d_c[:m].cpu().numpy().view(np.uint32), d_f[:n].cpu().numpy()
+        score, want = count * (off[1:] - off[:-1]).astype(np.uint64), max(0, size - len(tokens))
+        def spell(k):
+            return "##" * int(flag[k]) + cps[off[k]:off[k + 1]].tobytes().decode("utf-32-le", "surrogatepass")
+
+        rank = np.lexsort((~count, ~score))[:want if want else 0]  # greater first: ~x = 2^64 - 1 - x
+        if 0 < want < n:
+            # the entries that tie with the last one taken rank by their spelling; the ones before them are in whatever it is
+            k = rank[-1]
+            tie = np.nonzero((score == score[k]) & (count == count[k]))[0]
+            head = rank[(score[rank] != score[k]) | (count[rank] != count[k])]
+            rank = np.concatenate([head, np.array(sorted(tie.tolist(), key=spell)[:want - head.size], dtype=rank.dtype)])
+        pieces = {spell(k): int(count[k]) for k in rank.tolist()}
+        tokens = sorted(tokens | set(pieces))
+        return (tokens, pieces) if return_counts else tokens
+
     def train_unigram(self, corpus: List[str], max_vocab: int, seed_vocab=None, seed_factor: int = 4, shrink: float = 0.75,
-                      iterations: int = 2, alpha: float = 1.0, method: str = "soft") -> list:
-        """Kudo 2018's trainer: a seed vocabulary -- `seed_vocab`, or NaiveWP.train(corpus, seed_factor * max_vocab) -- fitted
+                      iterations: int = 2, alpha: float = 1.0, method: str = "soft", seed: str = "merges") -> list:
+        """Kudo 2018's trainer: a seed vocabulary -- `seed_vocab`, or NaiveWP.train(corpus, seed_factor * max_vocab), or with
+        seed="substrings" seed_substrings(corpus, seed_factor * max_vocab) -- fitted
         with fit_scores(corpus, iterations, alpha, method), then, while it is larger than max_vocab: removal_losses, prune to
         max(max_vocab, floor(shrink * len(vocab))), fit_scores again.  It ends early when only what prune always keeps is left.
         -> per round (the vocabulary's size, viterbi_total, unk_words) as its removal_losses found them, before the round's
@@ -1480,7 +1527,14 @@ class UnigramWP(NaiveWP):
             raise ValueError("iterations: an int of at least 1")
         if not alpha > 0 or not math.isfinite(alpha):
             raise ValueError("alpha: a positive float")
-        if seed_vocab is None:
+        if seed not in ("merges", "substrings"):
+            raise ValueError('seed: "merges" or "substrings"')
+        if seed == "substrings" and seed_vocab is not None:
+            raise ValueError('seed="substrings" makes the seed vocabulary: seed_vocab must be None')
+        if seed == "substrings":
+            self.reset()
+            self.vocab = set(self.seed_substrings(corpus, seed_factor * max_vocab))
+        elif seed_vocab is None:
             NaiveWP.train(self, corpus, seed_factor * max_vocab)
         else:
             self.reset()
