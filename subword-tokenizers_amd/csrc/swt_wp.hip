@@ -451,6 +451,19 @@ __device__ __forceinline__ uint32_t wp_sentence_start(const WpTileLds &L, const 
   return m ? (uint32_t)(w * 64 + 63 - __builtin_clzll(m)) : ch.off0;
 }
 
+// the sentence around byte p0 of the chunk, as an index of sent_off: the last of the tile's sentences not done yet that starts at
+// or before it (empty sentences share their offset with the next one that has bytes, and that one it is)
+__device__ __forceinline__ uint64_t wp_sentence_index(const WpTile &tile, const WpChunk &ch, const uint64_t *__restrict__ sent_off,
+                                                      uint32_t p0) {
+  const uint64_t g = ch.abase + p0;
+  uint64_t lo = tile.s_next, hi = tile.s_hi;  // sent_off[lo] <= g (the chunk begins at a sentence start) < sent_off[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (sent_off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // ---- E. compaction, F. sentence offsets.  Advances the tile; true: that was its last chunk.  extra(p, k): what else travels with
 // the token at byte p of the chunk to slot k of the tile's run (the span form; WpNoExtra for ids alone).
 struct WpNoExtra {
@@ -1018,11 +1031,17 @@ struct alignas(16) WpNaiveLds : WpTileLds {
   unsigned long long nonterm[kWpBlocks + 1]; // per sentence-start position: a word of the sentence never returns
 };
 
-// ---- B of wp_viterbi_kernel, which is wp_naive_kernel's (that kernel keeps its own text, and with it its instructions: as a
-// caller of this function it came out 12 instructions longer and the plain call 1.2 % slower): 64 bytes per step, BERT white-space / punctuation ballots -> the
-// word starts in cand[] (their count is returned), stop and pbits, tok[] cleared.  The caller synchronises.
-template <class Lds>
-__device__ __forceinline__ uint32_t wp_words(Lds &L, const WpChunk &ch, const uint8_t *__restrict__ cls_tab, int lane) {
+// What the UnigramWP kernels keep of a chunk's words; each puts its lattice state behind it.
+struct alignas(16) WpWordLds : WpTileLds {
+  unsigned long long stop[kWpBlocks + 1];    // as WpNaiveLds
+  unsigned long long pbits[kWpBlocks + 1];
+};
+
+// ---- B of the UnigramWP kernels, which is wp_naive_kernel's (that kernel keeps its own text: as a caller of this function it
+// came out 12 instructions longer and the plain call 1.2 % slower): 64 bytes per step, BERT white-space /
+// punctuation ballots -> the word starts in cand[] (their count is returned), stop and pbits, tok[] cleared.  The caller
+// synchronises.
+__device__ __forceinline__ uint32_t wp_words(WpWordLds &L, const WpChunk &ch, const uint8_t *__restrict__ cls_tab, int lane) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   uint32_t nc = 0;
   bool prev_stop = true;  // the char owning the byte before this block is white space or punctuation
@@ -1031,7 +1050,12 @@ __device__ __forceinline__ uint32_t wp_words(Lds &L, const WpChunk &ch, const ui
     bool inr, lead;
     const uint32_t cp = wp_decode(L, ch, p, inr, lead);
     uint8_t c = SWT_CLS_BERT_WS;  // bytes outside the chunk behave as white space
-    if (inr && lead) c = cp < (uint32_t)kWpClsLds ? (uint8_t)(L.cls_lo[cp] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT)) : bert_class(cls_tab, cp);
+    if (inr && lead) {
+      // The LDS read comes first and alone: as one arm of a choice between cls_lo and cls_tab the two loads were merged into
+      // one flat load of either table, which cost the sampled encode 0.5 % (profiles/unigram_refactor.txt).
+      c = (uint8_t)(L.cls_lo[cp & (uint32_t)(kWpClsLds - 1)] & (SWT_CLS_BERT_WS | SWT_CLS_BERT_PUNCT));
+      if (cp >= (uint32_t)kWpClsLds) c = bert_class(cls_tab, cp);
+    }
     const unsigned long long INR = __ballot(inr);
     const unsigned long long LEAD = __ballot(lead);
     const unsigned long long WSm = __ballot(lead && (c & SWT_CLS_BERT_WS));
@@ -1052,8 +1076,7 @@ __device__ __forceinline__ uint32_t wp_words(Lds &L, const WpChunk &ch, const ui
 }
 
 // where the word that starts at byte p0 of the chunk ends: a punctuation character is a word of its own
-template <class Lds>
-__device__ __forceinline__ uint32_t wp_word_end(const Lds &L, const WpChunk &ch, uint32_t p0) {
+__device__ __forceinline__ uint32_t wp_word_end(const WpWordLds &L, const WpChunk &ch, uint32_t p0) {
   uint32_t we;
   if (wbit(L.pbits, p0)) {
     we = p0 + 1;
@@ -1152,13 +1175,7 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
       bool nt_word = false;
       if constexpr (Dropout) {
         const uint32_t s0 = wp_sentence_start(L, ch, p0);
-        const uint64_t g = ch.abase + p0;
-        uint64_t lo = tile.s_next, hi = tile.s_hi;  // sent_off[lo] <= g (the chunk begins at a sentence start) < sent_off[hi]
-        while (hi - lo > 1) {
-          const uint64_t mid = lo + ((hi - lo) >> 1);
-          if (sent_off[mid] <= g) lo = mid; else hi = mid;
-        }
-        WpDraw draw(draw_args, (uint32_t)lo, p0 - s0);
+        WpDraw draw(draw_args, (uint32_t)wp_sentence_index(tile, ch, sent_off, p0), p0 - s0);
         naive_word(L.txt, p0, we, N, &L.tok[p0], we - p0, nt_word, draw);
       } else {
         WpNoDraw none;
@@ -1197,12 +1214,15 @@ __global__ __launch_bounds__(64) void wp_naive_kernel(
 // j - 1: a word of b bytes has at most b code points, so a lane keeps its whole programme in its word's own b slots of tok[] and
 // of best[] and no two lanes of a chunk touch the same slot.  dp[j - 1] = id | i << 21 of the best piece that ends at j (ids are
 // below 2^21: swt_wp_trie_set_scores refuses larger vocabularies; i < n <= max_chars <= 1,024), kInvalidTok while j is not reached.
-struct WpViterbiDev {
+// What all four UnigramWP kernels (Viterbi, sampling, expected counts, removal losses) know of the vocabulary; each adds its own.
+struct WpLatticeDev {
   WpDev T;              // edges and root_sharp
   const int32_t *tok;   // node -> vocabulary id, -1 for none
-  const float *score;   // vocabulary id -> score
   uint32_t unk_id;      // "[UNK]"
-  uint32_t max_chars;   // 1 .. kWpCap: a longer word is one "[UNK]"
+  uint32_t max_chars;   // 1 .. kWpCap: a longer word is one "[UNK]" (an UNK word where nothing is emitted)
+};
+struct WpViterbiDev : WpLatticeDev {
+  const float *score;   // vocabulary id -> score
 };
 constexpr uint32_t kVitIdBits = 21, kVitIdMask = (1u << kVitIdBits) - 1u;
 constexpr uint32_t kVitMaxChars = kWpCap;
@@ -1220,6 +1240,47 @@ __device__ __forceinline__ uint32_t wp_next_cp(const uint8_t *txt, uint64_t &q, 
   q += n;
   while (q < we && utf8_is_cont(txt[q])) q++;
   return cp;
+}
+
+// The pieces of the word that ends at we which start at byte q: the edge hash is followed from the root, or from root_sharp when
+// the start is not the word's first (from_sharp), and f(steps, id, q) is called at every node with a vocabulary id -- steps: the
+// code points taken so far, q: the byte behind them.  f returns true to end the walk there.  The walks over wide values call it
+// (wp_backward, the draw, the forward pass of the expected counts); viterbi_word and prune_barred spell the same loop out.
+template <class F>
+__device__ __forceinline__ void wp_pieces(const uint8_t *txt, uint64_t q, uint64_t we, const WpLatticeDev &D, bool from_sharp, F f) {
+  uint32_t node = from_sharp ? D.T.root_sharp : kWpRoot;
+  for (uint32_t steps = 1; q < we; steps++) {
+    const uint32_t cp = wp_next_cp(txt, q, we);
+    const int32_t c = edge_lookup(D.T, node, cp);
+    if (c < 0) break;
+    node = (uint32_t)c;
+    const int32_t v = D.tok[node];
+    if (v < 0) continue;
+    if (f(steps, (uint32_t)v, q)) break;
+  }
+}
+
+// A sentence [b, e) of txt in global memory, split as SubwordTokenizer._split (naive_sentence's loop): f(p, q) for every word.
+template <class F>
+__device__ __forceinline__ void wp_split_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, F f) {
+  TxtSrc src{txt, nullptr, cls_tab};
+  uint64_t p = b;
+  while (p < e) {
+    uint32_t cp, cc, len;
+    src.load(p, e, cp, cc, len);
+    const uint8_t c = bert_class(cls_tab, cp);
+    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
+    uint64_t q = p + len;
+    if (!(c & SWT_CLS_BERT_PUNCT)) {
+      while (q < e) {
+        src.load(q, e, cp, cc, len);
+        if (bert_class(cls_tab, cp)) break;
+        q += len;
+      }
+    }
+    f(p, q);
+    p = q;
+  }
 }
 
 // One word [wb, we) of txt: its ids to out[0..), the count returned (never more than the word's code points).  dp and best hold
@@ -1248,7 +1309,7 @@ __device__ __forceinline__ uint32_t viterbi_word(const uint8_t *txt, uint64_t wb
       const float bi = i ? best[i - 1] : 0.0f;
       uint32_t node = i ? V.T.root_sharp : kWpRoot;
       uint64_t q = pi;
-      for (uint32_t j = i; q < we; j++) {  // j: the slot of boundary j + 1
+      for (uint32_t j = i; q < we; j++) {  // wp_pieces' walk, written out (as a caller of it the encode was 1.2 % slower)
         const uint32_t cp = wp_next_cp(txt, q, we);
         const int32_t c = edge_lookup(V.T, node, cp);
         if (c < 0) break;
@@ -1256,7 +1317,7 @@ __device__ __forceinline__ uint32_t viterbi_word(const uint8_t *txt, uint64_t wb
         const int32_t v = V.tok[node];
         if (v < 0) continue;
         const float cand = __fadd_rn(bi, V.score[v]);
-        if (dp[j] == kInvalidTok || cand > best[j]) {
+        if (dp[j] == kInvalidTok || cand > best[j]) {  // j: the slot of boundary j + 1
           best[j] = cand;
           dp[j] = (uint32_t)v | (i << kVitIdBits);
         }
@@ -1289,94 +1350,6 @@ __device__ __forceinline__ uint32_t viterbi_word(const uint8_t *txt, uint64_t wb
   return m;
 }
 
-// A whole sentence [b, e) by one lane (sentences longer than a chunk): naive_sentence's split, every word through the
-// programme above with its state in dp[] and best[] -- the wave's LDS arrays, idle while its one lane walks.
-__device__ uint32_t viterbi_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
-                                     const WpViterbiDev &V, uint32_t *dp, float *best) {
-  TxtSrc src{txt, nullptr, cls_tab};
-  uint32_t nt = 0;
-  uint64_t p = b;
-  while (p < e) {
-    uint32_t cp, cc, len;
-    src.load(p, e, cp, cc, len);
-    const uint8_t c = bert_class(cls_tab, cp);
-    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
-    uint64_t q = p + len;
-    if (!(c & SWT_CLS_BERT_PUNCT)) {
-      while (q < e) {
-        src.load(q, e, cp, cc, len);
-        if (bert_class(cls_tab, cp)) break;
-        q += len;
-      }
-    }
-    nt += viterbi_word<false>(txt, p, q, V, dp, best, out + nt);
-    p = q;
-  }
-  return nt;
-}
-
-struct alignas(16) WpViterbiLds : WpTileLds {
-  unsigned long long stop[kWpBlocks + 1];   // as WpNaiveLds
-  unsigned long long pbits[kWpBlocks + 1];
-  float best[kWpCap];                       // per boundary of a word, in the word's own bytes: the best total that reaches it
-};
-
-// wp_naive_kernel's skeleton and its B; C is the programme above, one lane per word, the state in the word's own slots of tok[]
-// and best[]; D has one status to write.  12,944 bytes of LDS: 4 more per staged byte than wp_naive_kernel.  The one kernel of this
-// file with float32 arithmetic is compiled without packed float32 operations, a precaution of this project on gfx950: its code has
-// none today either way, so no result depends on it, and as an attribute it leaves the other kernels as they were.
-#ifdef __HIP_DEVICE_COMPILE__
-#define SWT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define SWT_NO_PACKED_F32  // (the host's stub has no such feature)
-#endif
-SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_viterbi_kernel(
-    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
-    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpViterbiDev V, uint32_t *__restrict__ scratch,
-    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
-  __shared__ WpViterbiLds L;
-  const int lane = threadIdx.x;
-  WpTile tile;
-  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
-  const WpOut out{sent_local, status, direct};
-
-  for (;;) {
-    WpChunk ch;
-    wp_stage(L, tile, ch, text, n_bytes, lane);
-    __syncthreads();
-    if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t) {
-        stt = SWT_WP_OK;
-        return viterbi_sentence(text, cls_tab, b, e, o, V, L.tok, L.best);
-      };
-      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
-      continue;
-    }
-
-    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
-    __syncthreads();
-
-    // ---- C. one lane per word
-    for (uint32_t k = lane; k < nc; k += 64) {
-      const uint32_t p0 = L.cand[k];
-      const uint32_t we = wp_word_end(L, ch, p0);
-      viterbi_word<true>(L.txt, p0, we, V, &L.tok[p0], &L.best[p0], &L.tok[p0]);
-    }
-    __syncthreads();
-
-    // ---- D. every sentence is SWT_WP_OK
-    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
-      const uint64_t rel = sent_off[s] - ch.abase;
-      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
-      status[s] = (uint8_t)SWT_WP_OK;
-    }
-    __syncthreads();
-
-    if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
-  }
-  wp_tile_end(tile, tile_tok, direct, lane);
-}
-
 // ---- UnigramWP, sampled: a segmentation of every word drawn with probability proportional to the product of its pieces'
 // weights (include/swt.h, swt_wp_encode_sample) -----------------------------------------------------------------
 //
@@ -1384,12 +1357,8 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_viterbi_kernel(
 // its exponent in tok[].  Before the backward pass slot i of tok[] holds the byte offset of c[i] in the word, written by the pass
 // that counts the code points: the backward pass reads it on its way down and puts the exponent in its place, so no cursor ever
 // steps back through the bytes.
-struct WpSampleDev {
-  WpDev T;                    // edges and root_sharp
-  const int32_t *tok;         // node -> vocabulary id, -1 for none
+struct WpSampleDev : WpLatticeDev {
   const float *weight;        // vocabulary id -> weight, within [2^-64, 2^64]
-  uint32_t unk_id;            // "[UNK]"
-  uint32_t max_chars;         // 1 .. kWpCap: a longer word is one "[UNK]"
   uint32_t key0, key1, epoch; // the draw
 };
 
@@ -1423,71 +1392,79 @@ __device__ __forceinline__ bool wide_gt(const Wide &a, const Wide &b) {
   return a.e != b.e ? a.e > b.e : a.f > b.f;
 }
 
+// The backward pass of a word [wb, we) over wide values, which sample_word and marginal_word share.  `slots` keeps b[i] in slot i
+// of the word's own slots, as many as the word has code points and at most max_chars, in the caller's form (WideSlots,
+// WidePackedSlots): get(j), put(i, b), and offset(i) / set_offset(i, o) for the byte offset of c[i], which stands in slot i until
+// b[i] takes its place.
+//   count     the code points (n; more than max_chars: nothing else is done), the byte offset of each into its slot
+//   backward  starts i from n - 1 down: the walk from c[i] adds weight[piece] * b[j] for every token end j it meets, in rising j
+//             (b[n] = 1 is not kept), and the sum is b[i]
+// Returns b[0], 0 for a word of too many code points.
+template <class Slots>
+__device__ __forceinline__ Wide wp_backward(const uint8_t *txt, uint64_t wb, uint64_t we, const WpLatticeDev &D, const float *weight,
+                                            const Slots &slots, uint32_t &n) {
+  n = 0;
+  for (uint64_t q = wb; q < we && n <= D.max_chars; n++) {
+    if (n < D.max_chars) slots.set_offset(n, (uint32_t)(q - wb));
+    (void)wp_next_cp(txt, q, we);
+  }
+  Wide b{0.0f, 0};
+  if (n > D.max_chars) return b;
+  for (uint32_t i = n; i-- > 0;) {
+    b = Wide{0.0f, 0};
+    wp_pieces(txt, wb + slots.offset(i), we, D, i != 0, [&](uint32_t steps, uint32_t v, uint64_t q) {
+      const Wide bj = q == we ? Wide{1.0f, 0} : slots.get(i + steps);
+      b = wide_add(b, wide_mul(bj, weight[v]));
+      return false;
+    });
+    slots.put(i, b);
+  }
+  return b;
+}
+
+// a wide value in two words: the significand in sf[], the exponent in se[], which holds the byte offsets before it
+struct WideSlots {
+  float *sf;
+  uint32_t *se;
+  __device__ __forceinline__ Wide get(uint32_t j) const { return Wide{sf[j], (int32_t)se[j]}; }
+  __device__ __forceinline__ void put(uint32_t i, const Wide &b) const { sf[i] = b.f; se[i] = (uint32_t)b.e; }
+  __device__ __forceinline__ uint32_t offset(uint32_t i) const { return se[i]; }
+  __device__ __forceinline__ void set_offset(uint32_t i, uint32_t o) const { se[i] = o; }
+};
+
 // One word [wb, we) of txt, which starts at byte a0 of sentence `sent` of the call: its ids to out[0..), the count returned
 // (never more than the word's code points).  se and sf hold as many words as the word has code points, at most max_chars.
 // InPlace: out is se, and the slots behind the ids end as kInvalidTok.
-//   count     the code points, the byte offset of each into se[]
-//   backward  starts i from n - 1 down: the walk from c[i] (from the root for i = 0, from root_sharp otherwise) adds
-//             weight[piece] * b[j] for every token end j it meets, in rising j, and the sum is b[i]
+//   backward  wp_backward over se[] and sf[]
 //   draw      from i = 0: t = u * b[i], the same walk with the same sums, and the first piece whose running sum exceeds t is
 //             taken.  Piece k goes to slot k, which is never ahead of slot i: b[i] is read before the walk.
 template <bool InPlace>
 __device__ __forceinline__ uint32_t sample_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpSampleDev &S, uint32_t sent,
                                                 uint32_t a0, uint32_t *se, float *sf, uint32_t *out) {
-  uint32_t n = 0;
-  for (uint64_t q = wb; q < we && n <= S.max_chars; n++) {
-    if (n < S.max_chars) se[n] = (uint32_t)(q - wb);
-    (void)wp_next_cp(txt, q, we);
-  }
+  const WideSlots slots{sf, se};
+  uint32_t n;
+  bool unk = wp_backward(txt, wb, we, S, S.weight, slots, n).f == 0.0f;
   const uint32_t used = n < S.max_chars ? n : S.max_chars;  // slots written so far
-  bool unk = n > S.max_chars;
-  if (!unk) {
-    for (uint32_t i = n; i-- > 0;) {
-      uint32_t node = i ? S.T.root_sharp : kWpRoot;
-      uint64_t q = wb + se[i];
-      Wide b{0.0f, 0};
-      for (uint32_t j = i + 1; q < we; j++) {
-        const uint32_t cp = wp_next_cp(txt, q, we);
-        const int32_t c = edge_lookup(S.T, node, cp);
-        if (c < 0) break;
-        node = (uint32_t)c;
-        const int32_t v = S.tok[node];
-        if (v < 0) continue;
-        const Wide bj = q == we ? Wide{1.0f, 0} : Wide{sf[j], (int32_t)se[j]};
-        b = wide_add(b, wide_mul(bj, S.weight[v]));
-      }
-      sf[i] = b.f;
-      se[i] = (uint32_t)b.e;
-    }
-    unk = sf[0] == 0.0f;
-  }
   uint32_t m = 0;
   if (!unk) {
     uint64_t p = wb;
     for (uint32_t i = 0; p < we;) {
-      const Wide bi{sf[i], (int32_t)se[i]};
+      const Wide bi = slots.get(i);
       const uint32_t x = philox4x32_10(0u, a0 + (uint32_t)(p - wb), sent, S.epoch, S.key0, S.key1).x[0];
       const Wide t = wide_mul(bi, __fmul_rn((float)(x >> 8), 0x1p-24f));
-      uint32_t node = i ? S.T.root_sharp : kWpRoot, j = i;
-      uint64_t q = p;
       Wide cum{0.0f, 0};
       int32_t taken = -1;
-      while (q < we) {
-        const uint32_t cp = wp_next_cp(txt, q, we);
-        const int32_t c = edge_lookup(S.T, node, cp);
-        if (c < 0) break;
-        node = (uint32_t)c;
-        j++;
-        const int32_t v = S.tok[node];
-        if (v < 0) continue;
-        const Wide bj = q == we ? Wide{1.0f, 0} : Wide{sf[j], (int32_t)se[j]};
+      wp_pieces(txt, p, we, S, i != 0, [&](uint32_t steps, uint32_t v, uint64_t q) {
+        const Wide bj = q == we ? Wide{1.0f, 0} : slots.get(i + steps);
         cum = wide_add(cum, wide_mul(bj, S.weight[v]));
-        if (wide_gt(cum, t)) { taken = v; break; }
-      }
+        if (!wide_gt(cum, t)) return false;
+        taken = (int32_t)v;
+        p = q;
+        i += steps;
+        return true;
+      });
       if (taken < 0) { unk = true; break; }  // (not reached: the last cum is b[i], and t < b[i])
       out[m++] = (uint32_t)taken;
-      p = q;
-      i = j;
     }
   }
   if (unk) {
@@ -1497,91 +1474,6 @@ __device__ __forceinline__ uint32_t sample_word(const uint8_t *txt, uint64_t wb,
   if constexpr (InPlace)
     for (uint32_t k = m; k < used; k++) se[k] = kInvalidTok;
   return m;
-}
-
-// A whole sentence [b, e), number `sent` of the call, by one lane (sentences longer than a chunk): viterbi_sentence's split,
-// every word through the programme above with its state in se[] and sf[] -- the wave's LDS arrays, idle while its one lane walks.
-__device__ uint32_t sample_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, uint32_t *out,
-                                    const WpSampleDev &S, uint32_t sent, uint32_t *se, float *sf) {
-  TxtSrc src{txt, nullptr, cls_tab};
-  uint32_t nt = 0;
-  uint64_t p = b;
-  while (p < e) {
-    uint32_t cp, cc, len;
-    src.load(p, e, cp, cc, len);
-    const uint8_t c = bert_class(cls_tab, cp);
-    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
-    uint64_t q = p + len;
-    if (!(c & SWT_CLS_BERT_PUNCT)) {
-      while (q < e) {
-        src.load(q, e, cp, cc, len);
-        if (bert_class(cls_tab, cp)) break;
-        q += len;
-      }
-    }
-    nt += sample_word<false>(txt, p, q, S, sent, (uint32_t)(p - b), se, sf, out + nt);
-    p = q;
-  }
-  return nt;
-}
-
-// wp_viterbi_kernel's skeleton, B, D and LDS (12,944 bytes); C is the programme above, one lane per word, which looks up the key
-// of its word as wp_naive_kernel<true> does: a0 = its offset from wp_sentence_start, sent = the last sentence of
-// sent_off[s_next .. s_hi) that starts at or before it.  The LDS is WpViterbiLds under a name of its own, so that wp_words and
-// wp_word_end are instantiated for this kernel apart: sharing the instances moved six instructions of wp_viterbi_kernel.
-struct alignas(16) WpSampleLds : WpViterbiLds {};
-SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_sample_kernel(
-    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
-    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpSampleDev S, uint32_t *__restrict__ scratch,
-    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
-  __shared__ WpSampleLds L;
-  const int lane = threadIdx.x;
-  WpTile tile;
-  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
-  const WpOut out{sent_local, status, direct};
-
-  for (;;) {
-    WpChunk ch;
-    wp_stage(L, tile, ch, text, n_bytes, lane);
-    __syncthreads();
-    if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t s) {
-        stt = SWT_WP_OK;
-        return sample_sentence(text, cls_tab, b, e, o, S, (uint32_t)s, L.tok, L.best);
-      };
-      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
-      continue;
-    }
-
-    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
-    __syncthreads();
-
-    // ---- C. one lane per word
-    for (uint32_t k = lane; k < nc; k += 64) {
-      const uint32_t p0 = L.cand[k];
-      const uint32_t we = wp_word_end(L, ch, p0);
-      const uint32_t s0 = wp_sentence_start(L, ch, p0);
-      const uint64_t g = ch.abase + p0;
-      uint64_t lo = tile.s_next, hi = tile.s_hi;  // sent_off[lo] <= g (the chunk begins at a sentence start) < sent_off[hi]
-      while (hi - lo > 1) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (sent_off[mid] <= g) lo = mid; else hi = mid;
-      }
-      sample_word<true>(L.txt, p0, we, S, (uint32_t)lo, p0 - s0, &L.tok[p0], &L.best[p0], &L.tok[p0]);
-    }
-    __syncthreads();
-
-    // ---- D. every sentence is SWT_WP_OK
-    for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
-      const uint64_t rel = sent_off[s] - ch.abase;
-      if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
-      status[s] = (uint8_t)SWT_WP_OK;
-    }
-    __syncthreads();
-
-    if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
-  }
-  wp_tile_end(tile, tile_tok, direct, lane);
 }
 
 // ---- UnigramWP, expected counts: every piece of a word's lattice with its posterior probability, summed over the text, and the
@@ -1594,11 +1486,8 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_sample_kernel(
 //     sa[j] = M(a) | (E(a) & 0xFF) << 24
 //     sx[j] = (E(b) >> 8 & 0xFFFF) | (E(a) >> 8) << 16
 // Before the backward pass sa[i] holds the byte offset of c[i], as sample_word's se[] does; the forward pass has its own cursor.
-struct WpMarginalDev {
-  WpDev T;                      // edges and root_sharp
-  const int32_t *tok;           // node -> vocabulary id, -1 for none
+struct WpMarginalDev : WpLatticeDev {
   const float *weight;          // vocabulary id -> weight, within [2^-64, 2^64]
-  uint32_t max_chars;           // 1 .. kWpCap: a longer word is an UNK word
   unsigned long long *counts;   // vocabulary id -> the sum of q
   unsigned long long *stats;    // words, UNK words, the sum of L
 };
@@ -1665,40 +1554,24 @@ __device__ __forceinline__ long long wide_log2_fixed24(const Wide &v) {
   return (long long)v.e * (1ll << 24) + (long long)frac;
 }
 
+// b[] as the backward pass keeps it here: packed into sb[] and the low half of sx[], the byte offsets in sa[] before a[] is there
+struct WidePackedSlots {
+  uint32_t *sb, *sa, *sx;
+  __device__ __forceinline__ Wide get(uint32_t j) const { return wide_unpack(sb[j], sx[j]); }
+  __device__ __forceinline__ void put(uint32_t i, const Wide &b) const { sb[i] = wide_pack(b); sx[i] = ((uint32_t)b.e >> 8) & 0xFFFFu; }
+  __device__ __forceinline__ uint32_t offset(uint32_t i) const { return sa[i]; }
+  __device__ __forceinline__ void set_offset(uint32_t i, uint32_t o) const { sa[i] = o; }
+};
+
 // One word [wb, we) of txt.  sb, sa and sx hold as many words as the word has code points, at most max_chars.
-//   count     the code points, the byte offset of each into sa[]
-//   backward  sample_word's, b[i] into sb[i] and the low half of sx[i]
+//   backward  wp_backward over the packed slots
 //   forward   a[1..n) = 0; the starts i in rising order, a reached one walks as the backward pass did: every piece adds
 //             term = a[i] * w to a[j] (a[n] is never read and is not kept) and, where b[j] != 0, floor(2^32 * term * b[j] / b[0])
 //             to counts[id] -- a global 64-bit atomic: integer sums come out the same in any order
 __device__ __forceinline__ void marginal_word(const uint8_t *txt, uint64_t wb, uint64_t we, const WpMarginalDev &M, uint32_t *sb,
                                               uint32_t *sa, uint32_t *sx, WpTally &tally) {
-  uint32_t n = 0;
-  for (uint64_t q = wb; q < we && n <= M.max_chars; n++) {
-    if (n < M.max_chars) sa[n] = (uint32_t)(q - wb);
-    (void)wp_next_cp(txt, q, we);
-  }
-  Wide b0{0.0f, 0};
-  if (n <= M.max_chars) {
-    for (uint32_t i = n; i-- > 0;) {
-      uint32_t node = i ? M.T.root_sharp : kWpRoot;
-      uint64_t q = wb + sa[i];
-      Wide b{0.0f, 0};
-      for (uint32_t j = i + 1; q < we; j++) {
-        const uint32_t cp = wp_next_cp(txt, q, we);
-        const int32_t c = edge_lookup(M.T, node, cp);
-        if (c < 0) break;
-        node = (uint32_t)c;
-        const int32_t v = M.tok[node];
-        if (v < 0) continue;
-        const Wide bj = q == we ? Wide{1.0f, 0} : wide_unpack(sb[j], sx[j]);
-        b = wide_add(b, wide_mul(bj, M.weight[v]));
-      }
-      sb[i] = wide_pack(b);
-      sx[i] = ((uint32_t)b.e >> 8) & 0xFFFFu;
-      b0 = b;
-    }
-  }
+  uint32_t n;
+  const Wide b0 = wp_backward(txt, wb, we, M, M.weight, WidePackedSlots{sb, sa, sx}, n);
   if (b0.f == 0.0f) {
     tally.unk++;
     return;
@@ -1710,15 +1583,8 @@ __device__ __forceinline__ void marginal_word(const uint8_t *txt, uint64_t wb, u
   for (uint32_t i = 0; i < n; i++) {
     const Wide ai = i ? wide_unpack(sa[i], sx[i] >> 16) : Wide{1.0f, 0};
     if (ai.f != 0.0f) {
-      uint32_t node = i ? M.T.root_sharp : kWpRoot;
-      uint64_t q = pi;
-      for (uint32_t j = i + 1; q < we; j++) {
-        const uint32_t cp = wp_next_cp(txt, q, we);
-        const int32_t c = edge_lookup(M.T, node, cp);
-        if (c < 0) break;
-        node = (uint32_t)c;
-        const int32_t v = M.tok[node];
-        if (v < 0) continue;
+      wp_pieces(txt, pi, we, M, i != 0, [&](uint32_t steps, uint32_t v, uint64_t q) {
+        const uint32_t j = i + steps;
         const Wide term = wide_mul(ai, M.weight[v]);
         Wide bj{1.0f, 0};
         if (q < we) {
@@ -1728,47 +1594,16 @@ __device__ __forceinline__ void marginal_word(const uint8_t *txt, uint64_t wb, u
           sx[j] = (x & 0xFFFFu) | (((uint32_t)aj.e >> 8) << 16);
           bj = wide_unpack(sb[j], x & 0xFFFFu);
         }
-        if (bj.f == 0.0f) continue;  // a dead end
+        if (bj.f == 0.0f) return false;  // a dead end
         const unsigned long long fx = wide_fixed32(wide_div(wide_mul2(term, bj), b0));
         if (fx) wp_tally_add(&M.counts[v], fx);
-      }
+        return false;
+      });
     }
     (void)wp_next_cp(txt, pi, we);
   }
 }
 
-// A whole sentence [b, e) by one lane (sentences longer than a chunk): sample_sentence's split, every word through the programme
-// above with its state in the wave's LDS arrays, idle while its one lane walks.
-__device__ void marginal_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, const WpMarginalDev &M,
-                                  uint32_t *sb, uint32_t *sa, uint32_t *sx, WpTally &tally) {
-  TxtSrc src{txt, nullptr, cls_tab};
-  uint64_t p = b;
-  while (p < e) {
-    uint32_t cp, cc, len;
-    src.load(p, e, cp, cc, len);
-    const uint8_t c = bert_class(cls_tab, cp);
-    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
-    uint64_t q = p + len;
-    if (!(c & SWT_CLS_BERT_PUNCT)) {
-      while (q < e) {
-        src.load(q, e, cp, cc, len);
-        if (bert_class(cls_tab, cp)) break;
-        q += len;
-      }
-    }
-    marginal_word(txt, p, q, M, sb, sa, sx, tally);
-    p = q;
-  }
-}
-
-// 17,040 bytes of LDS: WpViterbiLds with two words per staged byte in the place of best[].  A type of its own, so that wp_words
-// and wp_word_end are instantiated for this kernel apart (as WpSampleLds).
-struct alignas(16) WpMarginalLds : WpTileLds {
-  unsigned long long stop[kWpBlocks + 1];   // as WpNaiveLds
-  unsigned long long pbits[kWpBlocks + 1];
-  uint32_t sa[kWpCap];                      // per boundary of a word, in the word's own bytes: a[], and
-  uint32_t sx[kWpCap];                      // the upper exponent bits of b[] and a[]
-};
 // a kernel without per-sentence results hands this to wp_giant
 struct WpNoOut {
   struct Sink {
@@ -1791,49 +1626,6 @@ __device__ __forceinline__ bool wp_advance(WpTile &tile, const WpChunk &ch, cons
   tile.s_next += wp_wave_sum(mine, lane);
   tile.cb = ch.abase + ch.ce;
   return false;
-}
-
-// wp_sample_kernel's skeleton and B; C is the programme above, one lane per word.  There is no D, E or F: the kernel emits
-// nothing, so it is launched over the plan alone -- no scratch, no per-sentence arrays, no scan or gather behind it (tile_tok is
-// where wp_tile_begin notes a tile without a sentence).  A lane keeps its words' likelihood and the two word counts in registers;
-// the wave adds them up once, at the end of its tile, for one atomic each.
-SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_marginal_kernel(
-    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
-    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpMarginalDev M, uint32_t *__restrict__ tile_tok) {
-  __shared__ WpMarginalLds L;
-  const int lane = threadIdx.x;
-  WpTile tile;
-  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, nullptr, tile_tok, DirectOut{nullptr, nullptr, 0}, lane)) return;
-  WpTally tally{0, 0u, 0u};
-
-  for (;;) {
-    WpChunk ch;
-    wp_stage(L, tile, ch, text, n_bytes, lane);
-    __syncthreads();
-    if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *, int &stt, uint64_t) {
-        stt = SWT_WP_OK;
-        marginal_sentence(text, cls_tab, b, e, M, L.tok, L.sa, L.sx, tally);
-        return 0u;
-      };
-      if (wp_giant(L, tile, sent_off, WpNoOut{}, SWT_WP_OK, walk, lane)) break;
-      continue;
-    }
-
-    const uint32_t nc = wp_words(L, ch, cls_tab, lane);  // B
-    __syncthreads();
-
-    // ---- C. one lane per word
-    for (uint32_t k = lane; k < nc; k += 64) {
-      const uint32_t p0 = L.cand[k];
-      const uint32_t we = wp_word_end(L, ch, p0);
-      marginal_word(L.txt, p0, we, M, &L.tok[p0], &L.sa[p0], &L.sx[p0], tally);
-    }
-    __syncthreads();
-
-    if (wp_advance(tile, ch, sent_off, lane)) break;
-  }
-  wp_tally_flush(tally, M.stats, lane);
 }
 
 // ---- UnigramWP, removal losses: what the text's best total loses when a piece leaves the vocabulary, per piece (include/swt.h,
@@ -1883,7 +1675,7 @@ __device__ __forceinline__ void prune_barred(const uint8_t *txt, uint64_t wb, ui
     if (ua != kInvalidTok || ub != kInvalidTok) {
       uint32_t node = i ? V.T.root_sharp : kWpRoot;
       uint64_t q = pi;
-      for (uint32_t j = i; q < we; j++) {  // j: the slot of boundary j + 1
+      for (uint32_t j = i; q < we; j++) {  // viterbi_word's walk, written out for the same reason (1.0 % of this call)
         const uint32_t cp = wp_next_cp(txt, q, we);
         const int32_t c = edge_lookup(V.T, node, cp);
         if (c < 0) break;
@@ -1950,44 +1742,88 @@ __device__ __forceinline__ void prune_word(const uint8_t *txt, uint64_t wb, uint
   }
 }
 
-// A whole sentence [b, e) by one lane (sentences longer than a chunk): viterbi_sentence's split, every word through the programme
-// above with its state in the wave's LDS arrays, idle while its one lane walks.
-__device__ void prune_sentence(const uint8_t *txt, const uint8_t *cls_tab, uint64_t b, uint64_t e, const WpPruneDev &P, uint32_t *dp,
-                               float *best, uint32_t *path, WpTally &tally) {
-  TxtSrc src{txt, nullptr, cls_tab};
-  uint64_t p = b;
-  while (p < e) {
-    uint32_t cp, cc, len;
-    src.load(p, e, cp, cc, len);
-    const uint8_t c = bert_class(cls_tab, cp);
-    if (c & SWT_CLS_BERT_WS) { p += len; continue; }
-    uint64_t q = p + len;
-    if (!(c & SWT_CLS_BERT_PUNCT)) {
-      while (q < e) {
-        src.load(q, e, cp, cc, len);
-        if (bert_class(cls_tab, cp)) break;
-        q += len;
-      }
-    }
-    prune_word(txt, p, q, P, dp, best, path, tally);
-    p = q;
-  }
-}
-
-// 17,040 bytes of LDS, as WpMarginalLds: WpViterbiLds and the path.  A type of its own, so that wp_words and wp_word_end are
-// instantiated for this kernel apart.
+// ---- The four UnigramWP kernels: one body (wp_lattice_tiles) under a policy each ------------------------------------------------
+//
+// The lattice state of a word stands in the word's own slots of tok[] and of what the kernel's LDS puts behind WpWordLds.
+struct alignas(16) WpViterbiLds : WpWordLds {
+  float best[kWpCap];      // Viterbi: the best total that reaches a boundary; sampling: the significand of b[]
+};
+struct alignas(16) WpMarginalLds : WpWordLds {
+  uint32_t sa[kWpCap];     // a[], and
+  uint32_t sx[kWpCap];     // the upper exponent bits of b[] and a[]
+};
 struct alignas(16) WpPruneLds : WpViterbiLds {
-  uint32_t path[kWpCap];  // per piece of a word's best path, in the word's own bytes: its id
+  uint32_t path[kWpCap];   // per piece of a word's best path: its id
+};
+static_assert(sizeof(WpViterbiLds) == 12944, "4 bytes per staged byte more than wp_naive_kernel: 3 waves per SIMD by LDS");
+static_assert(sizeof(WpMarginalLds) == 17040 && sizeof(WpPruneLds) == 17040, "two words per staged byte: still 3 waves per SIMD");
+
+// A policy names the kernel's LDS, says whether the kernel emits ids (phase D, wp_emit and wp_tile_end; otherwise wp_advance and
+// one wp_tally_flush into stats()) and whether a word needs its draw key, and runs one word [wb, we) of txt with its state in slot
+// `at` of the LDS arrays: InPlace, a word of the chunk at its own byte, or a word of a giant sentence at slot 0 with the ids to out.
+struct WpKey { uint32_t sent, a0; };  // the word's sentence in the call's sent_off, its byte offset in that sentence
+struct WpViterbiWords {
+  using Lds = WpViterbiLds;
+  static constexpr bool emits = true, keyed = false;
+  const WpViterbiDev &V;
+  template <bool InPlace>
+  __device__ __forceinline__ uint32_t word(const uint8_t *txt, uint64_t wb, uint64_t we, Lds &L, uint32_t at, uint32_t *out, WpKey,
+                                           WpTally &) const {
+    return viterbi_word<InPlace>(txt, wb, we, V, &L.tok[at], &L.best[at], out);
+  }
+};
+struct WpSampleWords {
+  using Lds = WpViterbiLds;
+  static constexpr bool emits = true, keyed = true;
+  const WpSampleDev &S;
+  template <bool InPlace>
+  __device__ __forceinline__ uint32_t word(const uint8_t *txt, uint64_t wb, uint64_t we, Lds &L, uint32_t at, uint32_t *out, WpKey key,
+                                           WpTally &) const {
+    return sample_word<InPlace>(txt, wb, we, S, key.sent, key.a0, &L.tok[at], &L.best[at], out);
+  }
+};
+struct WpMarginalWords {
+  using Lds = WpMarginalLds;
+  static constexpr bool emits = false, keyed = false;
+  const WpMarginalDev &M;
+  template <bool InPlace>
+  __device__ __forceinline__ uint32_t word(const uint8_t *txt, uint64_t wb, uint64_t we, Lds &L, uint32_t at, uint32_t *, WpKey,
+                                           WpTally &tally) const {
+    marginal_word(txt, wb, we, M, &L.tok[at], &L.sa[at], &L.sx[at], tally);
+    return 0;
+  }
+  __device__ __forceinline__ unsigned long long *stats() const { return M.stats; }
+};
+struct WpPruneWords {
+  using Lds = WpPruneLds;
+  static constexpr bool emits = false, keyed = false;
+  const WpPruneDev &P;
+  template <bool InPlace>
+  __device__ __forceinline__ uint32_t word(const uint8_t *txt, uint64_t wb, uint64_t we, Lds &L, uint32_t at, uint32_t *, WpKey,
+                                           WpTally &tally) const {
+    prune_word(txt, wb, we, P, &L.tok[at], &L.best[at], &L.path[at], tally);
+    return 0;
+  }
+  __device__ __forceinline__ unsigned long long *stats() const { return P.stats; }
 };
 
-// wp_marginal_kernel's skeleton, B and end; C is the programme above, one lane per word.  Launched over the plan alone.
-SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_prune_kernel(
-    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
-    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpPruneDev P, uint32_t *__restrict__ tile_tok) {
-  __shared__ WpPruneLds L;
+// wp_naive_kernel's skeleton with wp_words as its B; C is the policy's word, one lane per word; D has one status to write.  A
+// sentence longer than a chunk goes word by word through one lane, its state in the wave's LDS arrays, idle while that lane walks.
+// A kernel that emits nothing is launched over the plan alone -- no scratch, no per-sentence arrays, no scan or gather behind it
+// (tile_tok is where wp_tile_begin notes a tile without a sentence): a lane keeps its words' likelihood and the two word counts
+// in registers, and the wave adds them up once, at the end of its tile, for one atomic each.
+template <class Words>
+__device__ __forceinline__ void wp_lattice_tiles(typename Words::Lds &L, const Words &words, const uint8_t *__restrict__ text,
+                                                 uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+                                                 const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab,
+                                                 uint32_t *__restrict__ scratch, uint32_t *__restrict__ sent_local,
+                                                 uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, const DirectOut &direct) {
   const int lane = threadIdx.x;
   WpTile tile;
-  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, nullptr, tile_tok, DirectOut{nullptr, nullptr, 0}, lane)) return;
+  if (!wp_tile_begin(L, tile, sent_off, plan, cls_tab, scratch, tile_tok, direct, lane)) return;
+  const std::conditional_t<Words::emits, WpOut, WpNoOut> out = [&] {
+    if constexpr (Words::emits) return WpOut{sent_local, status, direct}; else return WpNoOut{};
+  }();
   WpTally tally{0, 0u, 0u};
 
   for (;;) {
@@ -1995,12 +1831,15 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_prune_kernel(
     wp_stage(L, tile, ch, text, n_bytes, lane);
     __syncthreads();
     if (!wp_mark(L, tile, ch, sent_off, lane)) {
-      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *, int &stt, uint64_t) {
+      const auto walk = [&](uint64_t b, uint64_t e, uint32_t *o, int &stt, uint64_t s) {
         stt = SWT_WP_OK;
-        prune_sentence(text, cls_tab, b, e, P, L.tok, L.best, L.path, tally);
-        return 0u;
+        uint32_t nt = 0;
+        wp_split_sentence(text, cls_tab, b, e, [&](uint64_t p, uint64_t q) {
+          nt += words.template word<false>(text, p, q, L, 0, o + nt, WpKey{(uint32_t)s, (uint32_t)(p - b)}, tally);
+        });
+        return nt;
       };
-      if (wp_giant(L, tile, sent_off, WpNoOut{}, SWT_WP_OK, walk, lane)) break;
+      if (wp_giant(L, tile, sent_off, out, SWT_WP_OK, walk, lane)) break;
       continue;
     }
 
@@ -2011,13 +1850,65 @@ SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_prune_kernel(
     for (uint32_t k = lane; k < nc; k += 64) {
       const uint32_t p0 = L.cand[k];
       const uint32_t we = wp_word_end(L, ch, p0);
-      prune_word(L.txt, p0, we, P, &L.tok[p0], &L.best[p0], &L.path[p0], tally);
+      WpKey key{0u, 0u};
+      if constexpr (Words::keyed)
+        key = WpKey{(uint32_t)wp_sentence_index(tile, ch, sent_off, p0), p0 - wp_sentence_start(L, ch, p0)};
+      words.template word<true>(L.txt, p0, we, L, p0, &L.tok[p0], key, tally);
     }
     __syncthreads();
 
-    if (wp_advance(tile, ch, sent_off, lane)) break;
+    if constexpr (Words::emits) {
+      // ---- D. every sentence is SWT_WP_OK
+      for (uint64_t s = tile.s_next + lane; s < tile.s_hi; s += 64) {
+        const uint64_t rel = sent_off[s] - ch.abase;
+        if (rel > ch.ce || (rel == ch.ce && !ch.last)) break;
+        status[s] = (uint8_t)SWT_WP_OK;
+      }
+      __syncthreads();
+      if (wp_emit(L, tile, ch, sent_off, out, lane, WpNoExtra{})) break;
+    } else {
+      if (wp_advance(tile, ch, sent_off, lane)) break;
+    }
   }
-  wp_tally_flush(tally, P.stats, lane);
+  if constexpr (Words::emits) wp_tile_end(tile, tile_tok, direct, lane);
+  else wp_tally_flush(tally, words.stats(), lane);
+}
+
+// The kernels of this file with float32 arithmetic are compiled without packed float32 operations, a precaution of this project
+// on gfx950: their code has none today either way, so no result depends on it, and as an attribute it leaves the other kernels as
+// they were.
+#ifdef __HIP_DEVICE_COMPILE__
+#define SWT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SWT_NO_PACKED_F32  // (the host's stub has no such feature)
+#endif
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_viterbi_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpViterbiDev V, uint32_t *__restrict__ scratch,
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+  __shared__ WpViterbiLds L;
+  wp_lattice_tiles(L, WpViterbiWords{V}, text, n_bytes, sent_off, plan, cls_tab, scratch, sent_local, tile_tok, status, direct);
+}
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_sample_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpSampleDev S, uint32_t *__restrict__ scratch,
+    uint32_t *__restrict__ sent_local, uint32_t *__restrict__ tile_tok, uint8_t *__restrict__ status, DirectOut direct) {
+  __shared__ WpViterbiLds L;
+  wp_lattice_tiles(L, WpSampleWords{S}, text, n_bytes, sent_off, plan, cls_tab, scratch, sent_local, tile_tok, status, direct);
+}
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_marginal_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpMarginalDev M, uint32_t *__restrict__ tile_tok) {
+  __shared__ WpMarginalLds L;
+  wp_lattice_tiles(L, WpMarginalWords{M}, text, n_bytes, sent_off, plan, cls_tab, nullptr, nullptr, tile_tok, nullptr,
+                   DirectOut{nullptr, nullptr, 0});
+}
+SWT_NO_PACKED_F32 __global__ __launch_bounds__(64) void wp_prune_kernel(
+    const uint8_t *__restrict__ text, uint64_t n_bytes, const uint64_t *__restrict__ sent_off,
+    const uint64_t *__restrict__ plan, const uint8_t *__restrict__ cls_tab, WpPruneDev P, uint32_t *__restrict__ tile_tok) {
+  __shared__ WpPruneLds L;
+  wp_lattice_tiles(L, WpPruneWords{P}, text, n_bytes, sent_off, plan, cls_tab, nullptr, nullptr, tile_tok, nullptr,
+                   DirectOut{nullptr, nullptr, 0});
 }
 
 }  // namespace swt
@@ -2095,22 +1986,29 @@ static int wp_upload_naive(swt_wp_trie *t) {
   return SWT_OK;
 }
 
-static int wp_upload_viterbi(swt_wp_trie *t) {
+// the tables of the NaiveWP walk, and a float per vocabulary id (the scores or the weights) where the host's copy is the newer
+static int wp_upload_floats(swt_wp_trie *t, const std::vector<float> &h, float *&d, bool &fresh) {
   int rc = wp_upload_naive(t);
-  if (rc || !t->score_fresh) return rc;
-  if (!t->d_score) SWT_HIP(hipMalloc((void **)&t->d_score, (t->h_score.size() + 1) * 4));
-  if (!t->h_score.empty()) SWT_HIP(hipMemcpy(t->d_score, t->h_score.data(), t->h_score.size() * 4, hipMemcpyHostToDevice));
-  t->score_fresh = false;
+  if (rc || !fresh) return rc;
+  if (!d) SWT_HIP(hipMalloc((void **)&d, (h.size() + 1) * 4));
+  if (!h.empty()) SWT_HIP(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+  fresh = false;
   return SWT_OK;
 }
+static int wp_upload_viterbi(swt_wp_trie *t) { return wp_upload_floats(t, t->h_score, t->d_score, t->score_fresh); }
+static int wp_upload_sample(swt_wp_trie *t) { return wp_upload_floats(t, t->h_weight, t->d_weight, t->weight_fresh); }
 
-static int wp_upload_sample(swt_wp_trie *t) {
-  int rc = wp_upload_naive(t);
-  if (rc || !t->weight_fresh) return rc;
-  if (!t->d_weight) SWT_HIP(hipMalloc((void **)&t->d_weight, (t->h_weight.size() + 1) * 4));
-  if (!t->h_weight.empty()) SWT_HIP(hipMemcpy(t->d_weight, t->h_weight.data(), t->h_weight.size() * 4, hipMemcpyHostToDevice));
-  t->weight_fresh = false;
-  return SWT_OK;
+// what the UnigramWP kernels know of the vocabulary, once the tables are on the device
+static WpLatticeDev wp_lattice_dev(const swt_wp_trie *t) {
+  WpLatticeDev D;
+  D.T = WpDev{};
+  D.T.edges = t->d_edges;
+  D.T.edge_bits = t->edge_bits;
+  D.T.root_sharp = t->H.root_sharp;
+  D.tok = t->d_tok;
+  D.unk_id = t->H.n_vocab + 1;
+  D.max_chars = t->max_word_chars;
+  return D;
 }
 
 static int wp_upload_spans(swt_wp_trie *t) {
@@ -2397,15 +2295,7 @@ static int wp_viterbi_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_byte
   int rc = wp_upload_viterbi(t);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  WpViterbiDev V;
-  V.T = WpDev{};
-  V.T.edges = t->d_edges;
-  V.T.edge_bits = t->edge_bits;
-  V.T.root_sharp = t->H.root_sharp;
-  V.tok = t->d_tok;
-  V.score = t->d_score;
-  V.unk_id = t->H.n_vocab + 1;
-  V.max_chars = t->max_word_chars;
+  const WpViterbiDev V{wp_lattice_dev(t), t->d_score};
   return wp_word_routes(t, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, st,
                         [&](const uint8_t *d_cls, unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
     hipLaunchKernelGGL(wp_viterbi_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, V, ids,
@@ -2428,18 +2318,7 @@ static int wp_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes
   int rc = wp_upload_sample(t);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  WpSampleDev S;
-  S.T = WpDev{};
-  S.T.edges = t->d_edges;
-  S.T.edge_bits = t->edge_bits;
-  S.T.root_sharp = t->H.root_sharp;
-  S.tok = t->d_tok;
-  S.weight = t->d_weight;
-  S.unk_id = t->H.n_vocab + 1;
-  S.max_chars = t->max_word_chars;
-  S.key0 = (uint32_t)seed;
-  S.key1 = (uint32_t)(seed >> 32);
-  S.epoch = epoch;
+  const WpSampleDev S{wp_lattice_dev(t), t->d_weight, (uint32_t)seed, (uint32_t)(seed >> 32), epoch};
   return wp_word_routes(t, n_bytes, d_sent_off, n_sent, d_out_ids, d_out_off, d_n_tokens, st,
                         [&](const uint8_t *d_cls, unsigned blocks, const uint64_t *plan, uint32_t *ids, const DirectOut &direct) {
     hipLaunchKernelGGL(wp_sample_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, plan, d_cls, S, ids,
@@ -2447,16 +2326,48 @@ static int wp_sample_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes
   });
 }
 
-// swt_wp_expected_counts_dev: the outputs zeroed, the plan, and wp_marginal_kernel over its tiles -- one route at every size, and
-// of the tile workspace only the plan and tile_tok
-static int wp_marginal_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
-                           uint64_t *d_counts, uint64_t *d_stats, void *stream) {
-  if (!t || !d_sent_off || !d_stats || (t->H.n_vocab && !d_counts) || (n_bytes && !d_text)) return fail(SWT_ERR_INVALID, "null argument");
+// The two calls that fill a table and three stats and emit no ids: swt_wp_expected_counts* (one column per vocabulary id, under
+// the weights) and swt_wp_removal_losses* (three, under the scores).
+struct WpTableCall {
+  const char *what;
+  uint32_t columns;
+  int (*ready)(const swt_wp_trie *);
+  int (*upload)(swt_wp_trie *);
+  // the kernel over `blocks` tiles of the plan in t->ws
+  void (*launch)(swt_wp_trie *t, unsigned blocks, hipStream_t st, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                 const uint8_t *d_cls, unsigned long long *table, unsigned long long *stats);
+};
+static const WpTableCall kWpExpectedCounts{
+    "expected counts", 1, wp_weights_set, wp_upload_sample,
+    [](swt_wp_trie *t, unsigned blocks, hipStream_t st, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+       const uint8_t *d_cls, unsigned long long *table, unsigned long long *stats) {
+      const WpMarginalDev M{wp_lattice_dev(t), t->d_weight, table, stats};
+      hipLaunchKernelGGL(wp_marginal_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, t->ws.plan.as<uint64_t>(), d_cls,
+                         M, t->ws.tile_tok.as<uint32_t>());
+    }};
+static const WpTableCall kWpRemovalLosses{
+    "removal losses", 3, wp_scores_set, wp_upload_viterbi,
+    [](swt_wp_trie *t, unsigned blocks, hipStream_t st, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+       const uint8_t *d_cls, unsigned long long *table, unsigned long long *stats) {
+      const WpPruneDev P{WpViterbiDev{wp_lattice_dev(t), t->d_score}, table, stats, t->H.n_vocab};
+      hipLaunchKernelGGL(wp_prune_kernel, dim3(blocks), dim3(64), 0, st, d_text, n_bytes, d_sent_off, t->ws.plan.as<uint64_t>(), d_cls, P,
+                         t->ws.tile_tok.as<uint32_t>());
+    }};
+
+// what both forms of such a call ask before anything is uploaded
+static int wp_table_ready(const swt_wp_trie *t, const WpTableCall &call) {
   if (t->H.n_vocab > kVitIdMask + 1)
-    return fail(SWT_ERR_UNSUPPORTED, "the expected counts take vocabularies of up to %u tokens", kVitIdMask + 1);
-  if (int rc = wp_weights_set(t)) return rc;
-  int rc = wp_upload_sample(t);
-  if (rc) return rc;
+    return fail(SWT_ERR_UNSUPPORTED, "the %s take vocabularies of up to %u tokens", call.what, kVitIdMask + 1);
+  return call.ready(t);
+}
+
+// The device form: the outputs zeroed, the plan, and the kernel over its tiles -- one route at every size, and of the tile
+// workspace only the plan and tile_tok.
+static int wp_table_dev(swt_wp_trie *t, const WpTableCall &call, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off,
+                        uint64_t n_sent, void *d_table, void *d_stats, void *stream) {
+  if (!t || !d_sent_off || !d_stats || (t->H.n_vocab && !d_table) || (n_bytes && !d_text)) return fail(SWT_ERR_INVALID, "null argument");
+  int rc;
+  if ((rc = wp_table_ready(t, call)) || (rc = call.upload(t))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const uint8_t *d_cls = nullptr;
   if ((rc = device_class_table(&d_cls))) return rc;
@@ -2464,69 +2375,46 @@ static int wp_marginal_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_byt
   if (n_tiles > 0x7FFFFFFFull)
     return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
   if ((rc = t->ws.plan.reserve((n_tiles + 1) * 8)) || (rc = t->ws.tile_tok.reserve((n_tiles + 1) * 4))) return rc;
-  if (t->H.n_vocab) SWT_HIP(hipMemsetAsync(d_counts, 0, (size_t)t->H.n_vocab * 8, st));
+  if (t->H.n_vocab) SWT_HIP(hipMemsetAsync(d_table, 0, (size_t)t->H.n_vocab * call.columns * 8, st));
   SWT_HIP(hipMemsetAsync(d_stats, 0, 3 * 8, st));
   if (n_sent == 0) return SWT_OK;
-  WpMarginalDev M;
-  M.T = WpDev{};
-  M.T.edges = t->d_edges;
-  M.T.edge_bits = t->edge_bits;
-  M.T.root_sharp = t->H.root_sharp;
-  M.tok = t->d_tok;
-  M.weight = t->d_weight;
-  M.max_chars = t->max_word_chars;
-  M.counts = reinterpret_cast<unsigned long long *>(d_counts);
-  M.stats = reinterpret_cast<unsigned long long *>(d_stats);
   prof_begin(st, 2);
   launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
   prof_begin(st);
-  hipLaunchKernelGGL(wp_marginal_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                     t->ws.plan.as<uint64_t>(), d_cls, M, t->ws.tile_tok.as<uint32_t>());
+  call.launch(t, (unsigned)n_tiles, st, d_text, n_bytes, d_sent_off, d_cls, static_cast<unsigned long long *>(d_table),
+              static_cast<unsigned long long *>(d_stats));
   prof_end(st);
   prof_end(st, 2);
   SWT_HIP(hipGetLastError());
   return SWT_OK;
 }
 
-// swt_wp_removal_losses_dev: wp_marginal_dev's route with wp_prune_kernel, under the scores
-static int wp_prune_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
-                        uint64_t *d_table, int64_t *d_stats, void *stream) {
-  if (!t || !d_sent_off || !d_stats || (t->H.n_vocab && !d_table) || (n_bytes && !d_text)) return fail(SWT_ERR_INVALID, "null argument");
-  if (t->H.n_vocab > kVitIdMask + 1)
-    return fail(SWT_ERR_UNSUPPORTED, "the removal losses take vocabularies of up to %u tokens", kVitIdMask + 1);
-  if (int rc = wp_scores_set(t)) return rc;
-  int rc = wp_upload_viterbi(t);
+// Host buffers: nothing of the host-call layer fits a call without ids, so the text and the offsets go up through the handle's
+// staging buffers, and the stats with the table behind them come back from one block of its out_off.  The weights or scores are
+// asked for before a device is.
+static int wp_table_host(swt_wp_trie *t, const WpTableCall &call, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent,
+                         void *table, void *stats) {
+  if (!t || !sent_off || !stats || (t->H.n_vocab && !table)) return fail(SWT_ERR_INVALID, "null argument");
+  if (int rc = wp_table_ready(t, call)) return rc;
+  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
+  for (uint64_t s = 0; s < n_sent; s++)
+    if (sent_off[s] > sent_off[s + 1])
+      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
+  const uint64_t n_bytes = sent_off[n_sent];
+  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
+  int rc = call.upload(t);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const uint8_t *d_cls = nullptr;
-  if ((rc = device_class_table(&d_cls))) return rc;
-  const uint64_t n_tiles = tile_count(n_bytes, kWpTile);
-  if (n_tiles > 0x7FFFFFFFull)
-    return fail(SWT_ERR_UNSUPPORTED, "text too large for one call (%llu bytes)", (unsigned long long)n_bytes);
-  if ((rc = t->ws.plan.reserve((n_tiles + 1) * 8)) || (rc = t->ws.tile_tok.reserve((n_tiles + 1) * 4))) return rc;
-  if (t->H.n_vocab) SWT_HIP(hipMemsetAsync(d_table, 0, (size_t)t->H.n_vocab * 3 * 8, st));
-  SWT_HIP(hipMemsetAsync(d_stats, 0, 3 * 8, st));
-  if (n_sent == 0) return SWT_OK;
-  WpPruneDev P;
-  P.V.T = WpDev{};
-  P.V.T.edges = t->d_edges;
-  P.V.T.edge_bits = t->edge_bits;
-  P.V.T.root_sharp = t->H.root_sharp;
-  P.V.tok = t->d_tok;
-  P.V.score = t->d_score;
-  P.V.unk_id = t->H.n_vocab + 1;
-  P.V.max_chars = t->max_word_chars;
-  P.table = reinterpret_cast<unsigned long long *>(d_table);
-  P.stats = reinterpret_cast<unsigned long long *>(d_stats);
-  P.n_vocab = t->H.n_vocab;
-  prof_begin(st, 2);
-  launch_plan(d_sent_off, n_sent, n_tiles, kWpTile, t->ws.plan.as<uint64_t>(), st);
-  prof_begin(st);
-  hipLaunchKernelGGL(wp_prune_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, d_text, n_bytes, d_sent_off,
-                     t->ws.plan.as<uint64_t>(), d_cls, P, t->ws.tile_tok.as<uint32_t>());
-  prof_end(st);
-  prof_end(st, 2);
-  SWT_HIP(hipGetLastError());
+  HostStage &hs = t->stage;
+  const size_t n_table = (size_t)call.columns * t->H.n_vocab;
+  if ((rc = hs.in_text.reserve(n_bytes + 64)) || (rc = hs.in_off.reserve((n_sent + 1) * 8)) || (rc = hs.out_off.reserve((3 + n_table) * 8)))
+    return rc;
+  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
+  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
+  uint64_t *d_out = hs.out_off.as<uint64_t>();
+  if ((rc = wp_table_dev(t, call, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, d_out + 3, d_out, nullptr))) return rc;
+  SWT_HIP(hipStreamSynchronize(nullptr));
+  SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
+  if (n_table) SWT_HIP(hipMemcpy(table, d_out + 3, n_table * 8, hipMemcpyDeviceToHost));
   return SWT_OK;
 }
 
@@ -2751,72 +2639,22 @@ int swt_wp_encode_sample(swt_wp_trie *t, const uint8_t *text, const uint64_t *se
 
 int swt_wp_expected_counts_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                                uint64_t *d_counts, uint64_t *d_stats, void *stream) try {
-  return wp_marginal_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_counts, d_stats, stream);
+  return wp_table_dev(t, kWpExpectedCounts, d_text, n_bytes, d_sent_off, n_sent, d_counts, d_stats, stream);
 } SWT_API_CATCH
 
-// Host buffers: nothing of the host-call layer fits a call without ids, so the text and the offsets go up through the handle's
-// staging buffers, and the stats with the table behind them come back from one block of its out_off.  The weights are asked for before a device is.
 int swt_wp_expected_counts(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *counts,
                            uint64_t *stats) try {
-  if (!t || !sent_off || !stats || (t->H.n_vocab && !counts)) return fail(SWT_ERR_INVALID, "null argument");
-  if (t->H.n_vocab > kVitIdMask + 1)
-    return fail(SWT_ERR_UNSUPPORTED, "the expected counts take vocabularies of up to %u tokens", kVitIdMask + 1);
-  if (int rc = wp_weights_set(t)) return rc;
-  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
-  for (uint64_t s = 0; s < n_sent; s++)
-    if (sent_off[s] > sent_off[s + 1])
-      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
-  const uint64_t n_bytes = sent_off[n_sent];
-  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
-  int rc = wp_upload_sample(t);
-  if (rc) return rc;
-  HostStage &hs = t->stage;
-  const size_t n_out = 3 + (size_t)t->H.n_vocab;
-  if ((rc = hs.in_text.reserve(n_bytes + 64)) || (rc = hs.in_off.reserve((n_sent + 1) * 8)) || (rc = hs.out_off.reserve(n_out * 8)))
-    return rc;
-  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
-  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  uint64_t *d_out = hs.out_off.as<uint64_t>();
-  if ((rc = wp_marginal_dev(t, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, d_out + 3, d_out, nullptr))) return rc;
-  SWT_HIP(hipStreamSynchronize(nullptr));
-  SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
-  if (t->H.n_vocab) SWT_HIP(hipMemcpy(counts, d_out + 3, (size_t)t->H.n_vocab * 8, hipMemcpyDeviceToHost));
-  return SWT_OK;
+  return wp_table_host(t, kWpExpectedCounts, text, sent_off, n_sent, counts, stats);
 } SWT_API_CATCH
 
 int swt_wp_removal_losses_dev(swt_wp_trie *t, const uint8_t *d_text, uint64_t n_bytes, const uint64_t *d_sent_off, uint64_t n_sent,
                               uint64_t *d_table, int64_t *d_stats, void *stream) try {
-  return wp_prune_dev(t, d_text, n_bytes, d_sent_off, n_sent, d_table, d_stats, stream);
+  return wp_table_dev(t, kWpRemovalLosses, d_text, n_bytes, d_sent_off, n_sent, d_table, d_stats, stream);
 } SWT_API_CATCH
 
-// Host buffers, as swt_wp_expected_counts: up through the handle's staging buffers, the stats and the table back from one block.
 int swt_wp_removal_losses(swt_wp_trie *t, const uint8_t *text, const uint64_t *sent_off, uint64_t n_sent, uint64_t *table,
                           int64_t *stats) try {
-  if (!t || !sent_off || !stats || (t->H.n_vocab && !table)) return fail(SWT_ERR_INVALID, "null argument");
-  if (t->H.n_vocab > kVitIdMask + 1)
-    return fail(SWT_ERR_UNSUPPORTED, "the removal losses take vocabularies of up to %u tokens", kVitIdMask + 1);
-  if (int rc = wp_scores_set(t)) return rc;
-  if (sent_off[0] != 0) return fail(SWT_ERR_INVALID, "sent_off[0] must be 0");
-  for (uint64_t s = 0; s < n_sent; s++)
-    if (sent_off[s] > sent_off[s + 1])
-      return fail(SWT_ERR_INVALID, "sentence offsets must be non-decreasing (at %llu)", (unsigned long long)s);
-  const uint64_t n_bytes = sent_off[n_sent];
-  if (n_bytes && !text) return fail(SWT_ERR_INVALID, "null text");
-  int rc = wp_upload_viterbi(t);
-  if (rc) return rc;
-  HostStage &hs = t->stage;
-  const size_t n_table = 3 * (size_t)t->H.n_vocab;
-  if ((rc = hs.in_text.reserve(n_bytes + 64)) || (rc = hs.in_off.reserve((n_sent + 1) * 8)) || (rc = hs.out_off.reserve((3 + n_table) * 8)))
-    return rc;
-  if (n_bytes) SWT_HIP(hipMemcpyAsync(hs.in_text.p, text, n_bytes, hipMemcpyHostToDevice, 0));
-  SWT_HIP(hipMemcpyAsync(hs.in_off.p, sent_off, (n_sent + 1) * 8, hipMemcpyHostToDevice, 0));
-  uint64_t *d_out = hs.out_off.as<uint64_t>();
-  if ((rc = wp_prune_dev(t, hs.in_text.as<uint8_t>(), n_bytes, hs.in_off.as<uint64_t>(), n_sent, d_out + 3, reinterpret_cast<int64_t *>(d_out), nullptr)))
-    return rc;
-  SWT_HIP(hipStreamSynchronize(nullptr));
-  SWT_HIP(hipMemcpy(stats, d_out, 3 * 8, hipMemcpyDeviceToHost));
-  if (n_table) SWT_HIP(hipMemcpy(table, d_out + 3, n_table * 8, hipMemcpyDeviceToHost));
-  return SWT_OK;
+  return wp_table_host(t, kWpRemovalLosses, text, sent_off, n_sent, table, stats);
 } SWT_API_CATCH
 
 }  // extern "C"

@@ -10,7 +10,8 @@ resident on the device.  Legs that alternate round after round in one process, H
   sample           swt_wp_encode_sample_dev
   hard             swt_wp_encode_viterbi_dev and swt_token_histogram_dev over its ids: the E-step of one hard iteration
   viterbi          swt_wp_encode_viterbi_dev
-  *_parent         the sampled and the Viterbi call into the parent commit's library (--parent-lib, loaded beside this tree's)
+  *_parent         the marginal, the sampled and the Viterbi call into the parent commit's library (--parent-lib, loaded beside
+                   this tree's)
 Before the timing the counts and stats of the first --check sentences are compared with the model of tests/marginal_cases.py.
 Then fit_scores(method="soft", iterations=--soft) on a fresh tokenizer, wall clock.  Prints one JSON line; --out FILE appends it."""
 import argparse
@@ -72,9 +73,10 @@ def main():
                 raise RuntimeError("%s: %s" % (entry, lib.swt_last_error().decode()))
         return call
 
-    def marginal(k=n_sent, d_off_k=d_off):
-        N.check(here.swt_wp_expected_counts_dev(trie._h, d_text.data_ptr(), int(off[k]), d_off_k.data_ptr(), k, d_counts[3:].data_ptr(),
-                                                d_counts.data_ptr(), stream))
+    def marginal(k=n_sent, d_off_k=d_off, lib=here, h=trie._h):
+        if lib.swt_wp_expected_counts_dev(h, d_text.data_ptr(), int(off[k]), d_off_k.data_ptr(), k, d_counts[3:].data_ptr(),
+                                          d_counts.data_ptr(), stream):
+            raise RuntimeError("swt_wp_expected_counts_dev: %s" % lib.swt_last_error().decode())
 
     viterbi = encode_of(here, "swt_wp_encode_viterbi_dev", trie._h)
     viterbi()
@@ -89,7 +91,7 @@ def main():
     if args.parent_lib:
         other = C.CDLL(os.path.abspath(args.parent_lib))
         for name in ("swt_init", "swt_last_error", "swt_wp_trie_create", "swt_wp_trie_set_scores", "swt_wp_trie_set_weights",
-                     "swt_wp_encode_viterbi_dev", "swt_wp_encode_sample_dev"):
+                     "swt_wp_encode_viterbi_dev", "swt_wp_encode_sample_dev", "swt_wp_expected_counts_dev"):
             fn = getattr(other, name)
             fn.restype, fn.argtypes = N.SIGNATURES[name]
         blob, voff = N.pack_utf32(tok._naive_tokens)
@@ -100,6 +102,7 @@ def main():
             raise RuntimeError("the parent's library: %s" % other.swt_last_error().decode())
         legs["sample_parent"] = encode_of(other, "swt_wp_encode_sample_dev", h, (SEED, EPOCH))
         legs["viterbi_parent"] = encode_of(other, "swt_wp_encode_viterbi_dev", h)
+        legs["marginal_parent"] = lambda: marginal(lib=other, h=h)
 
     # ---- the check: the first k sentences as a call of their own against the model
     k = min(args.check, n_sent)
@@ -136,7 +139,7 @@ def main():
     leg = out["legs"]
     for base in ("sample", "hard"):
         leg["marginal"]["ratio_to_" + base] = round(leg["marginal"]["median_ms"] / leg[base]["median_ms"], 3)
-    for name in ("sample", "viterbi"):
+    for name in ("marginal", "sample", "viterbi"):
         if name + "_parent" in leg:
             p = leg[name + "_parent"]
             out[name + "_against_parent"] = {"ratio": round(leg[name]["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], leg[name]["spread"]), 4)}

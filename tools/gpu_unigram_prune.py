@@ -6,7 +6,7 @@ S85k, the pretrained 20,000-token vocabulary, scores from fit_scores(S85k, itera
 device.  Legs that alternate round after round in one process, HIP events around enough back-to-back calls for 0.2 s each:
   prune            swt_wp_removal_losses_dev
   viterbi          swt_wp_encode_viterbi_dev
-  viterbi_parent   the Viterbi call into the parent commit's library (--parent-lib, loaded beside this tree's)
+  *_parent         both calls into the parent commit's library (--parent-lib, loaded beside this tree's)
 Before the timing the table and stats of the first --check sentences are compared with the model of tests/prune_cases.py.  Then
 train_unigram from the pretrained vocabulary as the seed down to --target on the first --train sentences, wall clock.  Prints one
 JSON line; --out FILE appends it."""
@@ -72,7 +72,8 @@ def main():
     legs = {"prune": prune, "viterbi": viterbi_of(here, trie._h)}
     if args.parent_lib:
         other = C.CDLL(os.path.abspath(args.parent_lib))
-        for name in ("swt_init", "swt_last_error", "swt_wp_trie_create", "swt_wp_trie_set_scores", "swt_wp_encode_viterbi_dev"):
+        for name in ("swt_init", "swt_last_error", "swt_wp_trie_create", "swt_wp_trie_set_scores", "swt_wp_encode_viterbi_dev",
+                     "swt_wp_removal_losses_dev"):
             fn = getattr(other, name)
             fn.restype, fn.argtypes = N.SIGNATURES[name]
         blob, voff = N.pack_utf32(tok._naive_tokens)
@@ -81,6 +82,12 @@ def main():
                 or other.swt_wp_trie_set_scores(h, N.ptr(scores, C.POINTER(C.c_float)), size)):
             raise RuntimeError("the parent's library: %s" % other.swt_last_error().decode())
         legs["viterbi_parent"] = viterbi_of(other, h)
+
+        def prune_parent():
+            if other.swt_wp_removal_losses_dev(h, d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_table[3:].data_ptr(),
+                                               d_table.data_ptr(), stream):
+                raise RuntimeError("swt_wp_removal_losses_dev: %s" % other.swt_last_error().decode())
+        legs["prune_parent"] = prune_parent
 
     # ---- the check: the first k sentences as a call of their own against the model
     k = min(args.check, n_sent)
@@ -119,9 +126,10 @@ def main():
         out["legs"][name] = {"ms": [round(x, 4) for x in v], "median_ms": round(med, 4), "spread": round((max(v) - min(v)) / med, 4)}
     leg = out["legs"]
     leg["prune"]["ratio_to_viterbi"] = round(leg["prune"]["median_ms"] / leg["viterbi"]["median_ms"], 3)
-    if "viterbi_parent" in leg:
-        p = leg["viterbi_parent"]
-        out["viterbi_against_parent"] = {"ratio": round(leg["viterbi"]["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], leg["viterbi"]["spread"]), 4)}
+    for name in ("prune", "viterbi"):
+        if name + "_parent" in leg:
+            p = leg[name + "_parent"]
+            out[name + "_against_parent"] = {"ratio": round(leg[name]["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], leg[name]["spread"]), 4)}
 
     # ---- the trainer, the pretrained vocabulary as its seed, on a tokenizer of its own
     fresh = S.UnigramWP()

@@ -6,8 +6,8 @@ S85k, the pretrained 20,000-token vocabulary, scores from fit_scores(S85k, itera
 resident on the device.  Legs that alternate round after round in one process, HIP events around enough back-to-back calls for
 0.2 s each:
   viterbi          swt_wp_encode_viterbi_dev, this tree
-  viterbi_parent   the same call into the parent commit's library (--parent-lib, loaded beside this tree's), when one is given
   sample           swt_wp_encode_sample_dev
+  *_parent         the same two calls into the parent commit's library (--parent-lib, loaded beside this tree's), when one is given
   sample@X         the same call into another build of the library (--variant-lib X=PATH, repeatable)
 Before the timing the sampled ids of the first --check sentences are compared with the model of tests/sample_cases.py.
 Prints one JSON line; --out FILE appends it."""
@@ -86,10 +86,13 @@ def main():
     legs = {"viterbi": call_of(here, "swt_wp_encode_viterbi_dev", trie._h),
             "sample": call_of(here, "swt_wp_encode_sample_dev", trie._h, (SEED, EPOCH))}
     if args.parent_lib:
-        other, h = another(args.parent_lib, ("swt_wp_trie_set_scores", "swt_wp_encode_viterbi_dev"))
-        if other.swt_wp_trie_set_scores(h, N.ptr(scores, C.POINTER(C.c_float)), int(scores.size)):
-            raise RuntimeError("scores: %s" % other.swt_last_error().decode())
+        other, h = another(args.parent_lib, ("swt_wp_trie_set_scores", "swt_wp_encode_viterbi_dev", "swt_wp_trie_set_weights",
+                                             "swt_wp_encode_sample_dev"))
+        if (other.swt_wp_trie_set_scores(h, N.ptr(scores, C.POINTER(C.c_float)), int(scores.size))
+                or other.swt_wp_trie_set_weights(h, N.ptr(weights, C.POINTER(C.c_float)), int(weights.size))):
+            raise RuntimeError("scores and weights: %s" % other.swt_last_error().decode())
         legs["viterbi_parent"] = call_of(other, "swt_wp_encode_viterbi_dev", h)
+        legs["sample_parent"] = call_of(other, "swt_wp_encode_sample_dev", h, (SEED, EPOCH))
     for v in args.variant_lib:
         other, h = another(v.partition("=")[2], ("swt_wp_trie_set_weights", "swt_wp_encode_sample_dev"))
         if other.swt_wp_trie_set_weights(h, N.ptr(weights, C.POINTER(C.c_float)), int(weights.size)):
@@ -137,9 +140,10 @@ def main():
     for name in legs:
         if name.startswith("sample"):
             out["legs"][name]["ratio_to_viterbi"] = round(out["legs"][name]["median_ms"] / base["median_ms"], 2)
-    if "viterbi_parent" in legs:
-        p = out["legs"]["viterbi_parent"]
-        out["viterbi_against_parent"] = {"ratio": round(base["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], base["spread"]), 4)}
+    for name in ("viterbi", "sample"):
+        if name + "_parent" in legs:
+            p, mine = out["legs"][name + "_parent"], out["legs"][name]
+            out[name + "_against_parent"] = {"ratio": round(mine["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], mine["spread"]), 4)}
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:

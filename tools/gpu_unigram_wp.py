@@ -5,9 +5,10 @@
 S85k, the pretrained 20,000-token vocabulary, scores from fit_scores(S85k, iterations=2), the lowercased text resident on the
 device.  Legs that alternate round after round in one process, HIP events around enough back-to-back calls for 0.2 s each:
   plain          swt_wp_encode_naive_dev, this tree
-  plain_parent   the same call into the parent commit's library (--parent-lib, loaded beside this tree's), when one is given
   plain@X        the same call into another build of the library (--variant-lib X=PATH, repeatable)
   viterbi        swt_wp_encode_viterbi_dev
+  dropout        swt_wp_encode_naive_dropout_dev at p = 0.1
+  *_parent       the same three calls into the parent commit's library (--parent-lib, loaded beside this tree's), when one is given
 Before the timing the Viterbi ids of the first --check sentences are compared with the model of tests/viterbi_cases.py.
 Prints one JSON line; --out FILE appends it."""
 import argparse
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 NEEDED = ("swt_init", "swt_last_error", "swt_wp_trie_create", "swt_wp_trie_destroy", "swt_wp_encode_naive_dev")
+DROPOUT = (round(0.1 * 2 ** 32), 0x5EED5EED5EED, 1)  # drop_below (p = 0.1), seed, epoch
 
 
 def main():
@@ -65,15 +67,17 @@ def main():
     d_status = torch.zeros(n_sent + 8, dtype=torch.uint8, device="cuda")
     here, trie = N.lib(), tok._ensure_scored_trie()
 
-    def call_of(lib, entry, h, n=n_bytes, k=n_sent):
+    def call_of(lib, entry, h, draw=()):
         def call():
-            if getattr(lib, entry)(h, d_text.data_ptr(), n, d_off.data_ptr(), k, d_ids.data_ptr(), d_tok_off.data_ptr(), d_status.data_ptr(),
-                                   d_ntok.data_ptr(), stream):
+            if getattr(lib, entry)(h, d_text.data_ptr(), n_bytes, d_off.data_ptr(), n_sent, d_ids.data_ptr(), d_tok_off.data_ptr(),
+                                   d_status.data_ptr(), d_ntok.data_ptr(), *draw, stream):
                 raise RuntimeError("%s: %s" % (entry, lib.swt_last_error().decode()))
         return call
 
-    legs = {"plain": call_of(here, "swt_wp_encode_naive_dev", trie._h), "viterbi": call_of(here, "swt_wp_encode_viterbi_dev", trie._h)}
+    legs = {"plain": call_of(here, "swt_wp_encode_naive_dev", trie._h), "viterbi": call_of(here, "swt_wp_encode_viterbi_dev", trie._h),
+            "dropout": call_of(here, "swt_wp_encode_naive_dropout_dev", trie._h, DROPOUT)}
     blob, voff = N.pack_utf32(tok._naive_tokens)
+    scores = np.array([tok.scores()[t] for t in tok._naive_tokens], dtype=np.float32)
     for leg, path in ([("plain_parent", args.parent_lib)] if args.parent_lib else []) + [("plain@" + v.partition("=")[0], v.partition("=")[2])
                                                                                          for v in args.variant_lib]:
         other = C.CDLL(os.path.abspath(path))
@@ -86,6 +90,14 @@ def main():
         if other.swt_wp_trie_create(N.ptr(blob, N.u32p), N.ptr(voff, N.u64p), len(tok._naive_tokens), C.byref(h_other)):
             raise RuntimeError("trie: %s" % other.swt_last_error().decode())
         legs[leg] = call_of(other, "swt_wp_encode_naive_dev", h_other)
+        if leg == "plain_parent":
+            for name in ("swt_wp_trie_set_scores", "swt_wp_encode_viterbi_dev", "swt_wp_encode_naive_dropout_dev"):
+                fn = getattr(other, name)
+                fn.restype, fn.argtypes = N.SIGNATURES[name]
+            if other.swt_wp_trie_set_scores(h_other, N.ptr(scores, C.POINTER(C.c_float)), int(scores.size)):
+                raise RuntimeError("scores: %s" % other.swt_last_error().decode())
+            legs["viterbi_parent"] = call_of(other, "swt_wp_encode_viterbi_dev", h_other)
+            legs["dropout_parent"] = call_of(other, "swt_wp_encode_naive_dropout_dev", h_other, DROPOUT)
 
     # ---- the check: the first k sentences as a call of their own against the model
     k = min(args.check, n_sent)
@@ -126,9 +138,10 @@ def main():
         out["legs"][name] = {"ms": [round(x, 4) for x in v], "median_ms": round(med, 4), "spread": round((max(v) - min(v)) / med, 4)}
     base = out["legs"]["plain"]
     out["legs"]["viterbi"]["ratio_to_plain"] = round(out["legs"]["viterbi"]["median_ms"] / base["median_ms"], 2)
-    if "plain_parent" in legs:
-        p = out["legs"]["plain_parent"]
-        out["plain_against_parent"] = {"ratio": round(base["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], base["spread"]), 4)}
+    for name in ("plain", "dropout", "viterbi"):
+        if name + "_parent" in legs:
+            p, mine = out["legs"][name + "_parent"], out["legs"][name]
+            out[name + "_against_parent"] = {"ratio": round(mine["median_ms"] / p["median_ms"], 4), "margin": round(max(p["spread"], mine["spread"]), 4)}
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:
