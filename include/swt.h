@@ -1242,7 +1242,21 @@ int swt_tag_capacity(uint32_t *cols_per_step, uint32_t *text_rows, uint32_t *sca
  * whatever the inputs hold.  They keep the workgroups' counts in a workspace of the process, and 1. scans in the workspace of
  * the plans: no two such calls at once on different streams.
  * swt_fill_capacity: the floats of a row one step of a wavefront covers (s above), the positions of one workgroup of 2., the
- * greatest k, and the cells of one scan group of 1. (csrc/swt_fill.hip). */
+ * greatest k, and the cells of one scan group of 1. (csrc/swt_fill.hip).
+ *
+ * 3. swt_mlm_predict16: 2. over logits of 16 bits -- IEEE half (dtype SWT_FILL_F16) or bfloat16 (SWT_FILL_BF16), given as their
+ * bits, uint16[rows, width, n_vocab], aligned to 2 bytes and no more -- which is what a model under autocast makes, read where
+ * it lies: no float32 copy of the logits is made.  THE RULE: every input value counts as its exact float32 widening (every half
+ * and every bfloat16 is a float32, subnormals included), and with that everything of 2. holds word for word: the order, the
+ * ranks, the ids and info are exact, out_top_logit and out_label_logit are float32 and hold the widening, out_lse is float32 and
+ * summed in float32 after the exact maximum.  The one thing that differs is the order of the additions: with s16 =
+ * values_per_step and a = log2(lane_sums) of swt_fill_capacity16 a term passes at most
+ *       chain16(V) = min(V - 1, ceil(V / s16) + a + 6)
+ * additions with another nonzero term -- ceil(V / s16) in its lane (a sum per column of the lane's eight values, one addition a
+ * step; the first sum starts from the lane's value of the peeled head or tail), a = 3 to add the lane's eight sums as a tree,
+ * 6 over the wavefront.  The remaining arguments, their checks, the "nothing" record, the zero-position success without a
+ * device, the workspace rule and info[5] are those of 2.; any other dtype is SWT_ERR_INVALID.  swt_fill_capacity16: the values
+ * of a row one step of a wavefront covers, and the sums a lane keeps. */
 #define SWT_FILL_EQUAL 0u
 #define SWT_FILL_NOT_EQUAL 1u
 #define SWT_FILL_IDS64 4u /* the value of SWT_BATCH_IDS64 */
@@ -1257,6 +1271,16 @@ int swt_mlm_predict_dev(const float *d_logits, uint64_t rows, uint32_t width, ui
                         const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id, float *d_out_top_logit,
                         int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info, void *stream);
 int swt_fill_capacity(uint32_t *floats_per_step, uint32_t *positions_per_workgroup, uint32_t *k_max, uint32_t *scan_cells);
+#define SWT_FILL_F16 1u
+#define SWT_FILL_BF16 2u
+int swt_mlm_predict16(const uint16_t *logits, uint32_t dtype, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *pos, uint64_t n_pos,
+                      const void *labels, uint32_t flags, uint32_t k, float *out_lse, int32_t *out_top_id, float *out_top_logit,
+                      int32_t *out_label_id, float *out_label_logit, int32_t *out_label_rank, uint64_t *info);
+int swt_mlm_predict16_dev(const uint16_t *d_logits, uint32_t dtype, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *d_pos,
+                          uint64_t n_pos, const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id,
+                          float *d_out_top_logit, int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info,
+                          void *stream);
+int swt_fill_capacity16(uint32_t *values_per_step, uint32_t *lane_sums);
 
 /* ------------------------------------------------------------------------------------------------
  * Added and special tokens written in the text ("[MASK]", "[SEP]", "<user>", a domain term kept whole): one stage in front of the

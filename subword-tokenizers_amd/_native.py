@@ -228,6 +228,11 @@ SIGNATURES = {
     "swt_mlm_predict_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                       C.c_uint32] + [C.c_void_p] * 8),
     "swt_fill_capacity": (C.c_int, [u32p, u32p, u32p, u32p]),
+    "swt_mlm_predict16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                    C.c_uint32] + [C.c_void_p] * 7),
+    "swt_mlm_predict16_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                        C.c_uint32] + [C.c_void_p] * 8),
+    "swt_fill_capacity16": (C.c_int, [u32p, u32p]),
     "swt_added_create": (C.c_int, [u8p, u64p, C.c_uint32, vpp]),
     "swt_added_destroy": (None, [C.c_void_p]),
     "swt_added_find": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u8p, u64p, u32p, u32p, C.c_uint64, u64p]),
@@ -1143,6 +1148,7 @@ def entity_spans(label, score, char_start, char_end, word_off, etype, begins, in
 
 
 FILL_EQUAL, FILL_NOT_EQUAL, FILL_IDS64 = 0, 1, 4  # the modes of swt_mlm_positions, the flag of both calls
+FILL_F16, FILL_BF16 = 1, 2  # the dtype of swt_mlm_predict16: IEEE half, bfloat16
 POSITION_COUNTS, FILL_COUNTS = 2, 5  # the entries of info of the two calls
 FILL_OUT = (("lse", np.float32, False), ("top_id", np.int32, True), ("top_logit", np.float32, True), ("label_id", np.int32, False),
             ("label_logit", np.float32, False), ("label_rank", np.int32, False))  # name, type, [n, k] instead of [n]
@@ -1155,6 +1161,14 @@ def fill_capacity():
     a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
     check(lib().swt_fill_capacity(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return a.value, b.value, c.value, d.value
+
+
+def fill_capacity16():
+    """-> (values_per_step, lane_sums): the 16-bit values of a row one step of a wavefront of swt_mlm_predict16 covers, the sums
+    a lane keeps (chain16 of include/swt.h is made of them)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib().swt_fill_capacity16(C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def _fill_ids(name, a):
@@ -1176,8 +1190,20 @@ def mlm_predict(logits, pos, labels=None, k=0, lse=True, info=True):
     """The scores of the rows logits[pos[p]] of float32 logits [rows, width, V] (swt_mlm_predict).  -> dict: lse float32[n] (or
     None), top_id int32, top_logit float32 [n, k] (None with k == 0), label_id, label_logit, label_rank [n] (None without labels),
     info uint64[5] (or None)"""
-    if not isinstance(logits, np.ndarray) or logits.dtype != np.float32 or logits.ndim != 3 or not logits.flags.c_contiguous:
-        raise TypeError("logits: a 3-D C-contiguous array of float32")
+    return _mlm_predict("swt_mlm_predict", np.float32, (), logits, pos, labels, k, lse, info)
+
+
+def mlm_predict16(bits, dtype, pos, labels=None, k=0, lse=True, info=True):
+    """mlm_predict over logits of 16 bits, given as their bits: uint16 [rows, width, V], dtype FILL_F16 or FILL_BF16
+    (swt_mlm_predict16; an np.float16 array goes in as a.view(np.uint16)).  Every value counts as its exact float32 widening, and
+    the outputs are those of mlm_predict, float32 included.  The host form is there for tests and small inputs: logits of 16
+    bits are born on the device, and fill_mask and mlm_scores read them there."""
+    return _mlm_predict("swt_mlm_predict16", np.uint16, (int(dtype),), bits, pos, labels, k, lse, info)
+
+
+def _mlm_predict(form, elem, extra, logits, pos, labels, k, lse, info):
+    if not isinstance(logits, np.ndarray) or logits.dtype != elem or logits.ndim != 3 or not logits.flags.c_contiguous:
+        raise TypeError("logits: a 3-D C-contiguous array of %s" % np.dtype(elem).name)
     rows, width, n_vocab = (int(x) for x in logits.shape)
     flags = 0
     if labels is not None:
@@ -1192,8 +1218,8 @@ def mlm_predict(logits, pos, labels=None, k=0, lse=True, info=True):
               "label_rank": labels is not None}
     out = {name: np.zeros((n, k) if per_k else n, dtype=t) if wanted[name] else None for name, t, per_k in FILL_OUT}
     out["info"] = np.zeros(FILL_COUNTS, dtype=np.uint64) if info else None
-    check(lib().swt_mlm_predict(_at(logits), rows, width, n_vocab, _at(pos), n, _at(labels), flags, k,
-                                *[_at(out[name]) for name, _, _ in FILL_OUT], _at(out["info"])))
+    check(getattr(lib(), form)(_at(logits), *extra, rows, width, n_vocab, _at(pos), n, _at(labels), flags, k,
+                               *[_at(out[name]) for name, _, _ in FILL_OUT], _at(out["info"])))
     return out
 
 

@@ -1126,7 +1126,9 @@ def entities(words, id2label, texts=None):
 def _fill_predict(ids, value, not_equal, logits, labels, top_k, what):
     """What fill_mask and mlm_scores share: the cells of `ids` that equal `value` (or do not) through swt_mlm_positions, the scores
     of their rows of logits through swt_mlm_predict -- NumPy arrays through the host forms, torch tensors on the GPU through the
-    `_dev` forms on the current device and stream, the position count and `info` the only read-backs.
+    `_dev` forms on the current device and stream, the position count and `info` the only read-backs.  A torch tensor of float16
+    or bfloat16 goes to swt_mlm_predict16_dev, which reads it where it lies (such logits are born on the device: NumPy logits are
+    float32); everything that comes back is float32 whatever the logits are.
     -> (dict: row, col, lse, top_id, top_logit, logprob, score, label_id, label_logit, label_rank; info)"""
     if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 64:
         raise ValueError("top_k lies in 1 .. 64")
@@ -1138,11 +1140,12 @@ def _fill_predict(ids, value, not_equal, logits, labels, top_k, what):
     else:
         import torch
         ok = isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype in (torch.int32, torch.int64) and ids.dim() == 2 and ids.is_contiguous()
-        logits_ok = isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32
+        half = {torch.float16: N.FILL_F16, torch.bfloat16: N.FILL_BF16}
+        logits_ok = isinstance(logits, torch.Tensor) and logits.is_cuda and (logits.dtype == torch.float32 or logits.dtype in half)
     if not ok:
         raise TypeError("%s: a 2-D C-contiguous NumPy array, or torch tensor on the GPU, of int32 or int64" % what)
     if not logits_ok:
-        raise TypeError("logits: float32, a NumPy array or a torch tensor on the GPU as %s is" % what)
+        raise TypeError("logits: a NumPy array of float32 or a torch tensor on the GPU of float32, float16 or bfloat16, as %s is" % what)
     rows, width = int(ids.shape[0]), int(ids.shape[1])
     if len(logits.shape) != 3 or tuple(logits.shape[:2]) != (rows, width) or int(logits.shape[2]) < 1:
         raise ValueError("logits has the shape [rows, width, V] over the rows of %s" % what)
@@ -1173,9 +1176,12 @@ def _fill_predict(ids, value, not_equal, logits, labels, top_k, what):
             wanted = [name for name, _, _ in N.FILL_OUT if labels is not None or not name.startswith("label")]
             out = {name: torch.empty((n, k) if per_k else n, dtype=types[t], device=dev) if name in wanted else None
                    for name, t, per_k in N.FILL_OUT}
-            N.check(N.lib().swt_mlm_predict_dev(p(logits), rows, width, int(logits.shape[2]), p(d_pos), n, p(labels),
-                                                N.FILL_IDS64 if ids64 else 0, k, *[p(out[name]) for name, _, _ in N.FILL_OUT],
-                                                d_info.data_ptr(), stream))
+            tail = (rows, width, int(logits.shape[2]), p(d_pos), n, p(labels), N.FILL_IDS64 if ids64 else 0, k,
+                    *[p(out[name]) for name, _, _ in N.FILL_OUT], d_info.data_ptr(), stream)
+            if logits.dtype in half:
+                N.check(N.lib().swt_mlm_predict16_dev(p(logits), half[logits.dtype], *tail))
+            else:
+                N.check(N.lib().swt_mlm_predict_dev(p(logits), *tail))
             info = d_info.cpu().numpy()
             cell = d_pos[:n]
             xp_exp = torch.exp

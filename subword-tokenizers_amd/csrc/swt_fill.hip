@@ -19,6 +19,8 @@
 //                        V = 8,192 and measured to come from L2 -- for the sum of expf(x - m): four sums a lane, one
 //                        per column of the quad, then (a0 + a1) + (a2 + a3) and a butterfly over the lanes, so that a term passes
 //                        ceil(V / 256) + 8 additions at most (swt.h states the formula the tolerance of the tests is made of).
+//   fill_predict16_kernel  the same over rows of IEEE half or bfloat16 (swt_mlm_predict16): eight values a 16-byte load, pass 1 on
+//                        16-bit keys with packed instructions, only pass 2 widens everything; described where it stands below.
 // Counts are stored per workgroup and summed by launch_counts_sum; there is no atomic and no scratch.
 #include <cmath>
 
@@ -80,8 +82,9 @@ __global__ __launch_bounds__(kLbThreads) void fill_scatter_kernel(PosArgs A) {
 
 // ---- one pass over each selected row of logits
 
-struct FillArgs {
-  const float *logits;
+template <class T>
+struct FillArgsT {
+  const T *logits;
   const unsigned long long *pos;
   const void *labels;  // null: no label outputs
   uint32_t labels64;
@@ -95,6 +98,7 @@ struct FillArgs {
   int32_t *label_rank;
   unsigned long long *part;  // kFlCounts per workgroup; null: nobody asked for info
 };
+using FillArgs = FillArgsT<float>;
 
 // (v, id) comes before (w, jd) in the order of the top-k and the rank: the greater logit, then the smaller id.  No NaN on either
 // side that is to come first: a NaN v is before nothing.
@@ -276,6 +280,264 @@ __global__ __launch_bounds__(kLbThreads) void fill_predict_kernel(FillArgs A) {
   if (threadIdx.x < kFlCounts) A.part[(uint64_t)blockIdx.x * kFlCounts + threadIdx.x] = sum;
 }
 
+// ---- the same over rows of 16-bit floats: IEEE half and bfloat16 (swt_mlm_predict16)
+//
+// A row is V values of 2 bytes at value offset pos * V, aligned to 2 bytes only: up to seven head values before the first 16-byte
+// boundary (lanes 0 .. 6 of the peel step) and up to seven tail values behind the last whole octet (lanes 8 .. 14), the octets
+// between are 16-byte loads, 64 octets -- 512 values -- a step.  PASS 1 STAYS IN 16 BITS.  fl16_key maps a value's bits to an
+// unsigned key whose order is the order of the values: b + 0x8000 for a cleared sign bit, 0 - b for a set one, so that both
+// zeros are 0x8000.  The keys of the NaNs lie outside [key(-inf), key(+inf)], below for a set sign bit and above for a cleared
+// one, so a lane's packed minimum and maximum of its keys tell at the end whether the row holds a NaN, and nothing in the loop
+// asks.  Two values share a register, and v_pk_max_u16, v_pk_min_u16 and the clamped v_pk_sub_u16 (nonzero exactly where a key
+// is above a threshold) make, two values an instruction, the maximum, the "does any of my eight beat the k-th best" test in
+// front of fill_offer, and the count of entries ahead of the label's.  The row is walked in ascending id -- head, octets, tail --
+// so an entry that ties with the k-th best never beats it and the test is a strict one on the keys alone; the count takes the
+// threshold key(label) - 1 for an octet before the label's and key(label) from the label's octet on, and the up to seven
+// entries before the label in its own octet that tie with it are counted after the loop.  Only an octet that the ballot lets
+// through is widened, for fill_offer, which then sees what the float32 kernel sees.  A key above key(+inf) counts as ahead of
+// the label although it is a NaN: a row whose extremes show one is read once more to count those (fill16_nans_above).
+// An octet beyond the row is loaded as eight -inf, which change none of the four.
+// PASS 2 widens every value (bfloat16 by a shift, half by v_cvt_f32_f16, both exact) and sums expf(x - m) as the float32
+// kernel does, eight sums a lane, one per column of the octet, folded as a tree of three levels, then the butterfly: a term
+// passes ceil(V / 512) + 3 + 6 additions at most.
+typedef uint16_t fl_u16x2 __attribute__((ext_vector_type(2)));
+typedef int16_t fl_i16x2 __attribute__((ext_vector_type(2)));
+
+constexpr uint32_t kFl16Oct = 8;                  // values of one 16-byte load
+constexpr uint32_t kFl16Step = 64 * kFl16Oct;     // values of a row one step of a wavefront covers
+constexpr uint32_t kFl16TailLane = 8;             // the peel step: lanes 0 .. 6 hold the head, lanes 8 .. 14 the tail
+constexpr uint32_t kFl16FlushSteps = 8192;        // a packed count grows by 4 a step at most: 4 * 8192 < 2^16
+
+// What the two formats differ in; BF: bfloat16, else IEEE half.
+template <bool BF>
+struct Fl16 {
+  static constexpr uint32_t kInfBits = BF ? 0x7F80u : 0x7C00u;  // |x| above this: a NaN
+  static constexpr uint32_t kNegInfBits = kInfBits | 0x8000u;
+  static constexpr uint32_t kKeyPosInf = kInfBits + 0x8000u, kKeyNegInf = 0x8000u - kInfBits;
+  static __device__ inline float widen(uint32_t b) {
+    if (BF) return __uint_as_float(b << 16);
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
+  }
+  // the bits of a float that widen() made
+  static __device__ inline uint32_t narrow(float v) {
+    if (BF) return __float_as_uint(v) >> 16;
+    return __builtin_bit_cast(uint16_t, (_Float16)v);
+  }
+  static __device__ inline void widen2(uint32_t w, float &lo, float &hi) {
+    if (BF) {
+      lo = __uint_as_float(w << 16);
+      hi = __uint_as_float(w & 0xFFFF0000u);
+    } else {
+      lo = widen(w & 0xFFFFu);
+      hi = widen(w >> 16);
+    }
+  }
+};
+
+__device__ inline uint32_t fl16_key(uint32_t b) { return (b & 0x8000u) ? (0u - b) & 0xFFFFu : b + 0x8000u; }
+__device__ inline uint32_t fl16_unkey(uint32_t key) { return (key & 0x8000u) ? key - 0x8000u : (0u - key) & 0xFFFFu; }
+
+// the keys of the two values of a register
+__device__ inline fl_u16x2 fl16_keys(uint32_t w) {
+  const fl_u16x2 b = __builtin_bit_cast(fl_u16x2, w);
+  const fl_u16x2 s = __builtin_bit_cast(fl_u16x2, __builtin_bit_cast(fl_i16x2, w) >> (fl_i16x2)(15));  // 0xFFFF under a set sign bit
+  return (b ^ (s | (fl_u16x2)(0x8000))) - s;
+}
+
+__device__ inline fl_u16x2 fl16_both(uint32_t key) { return __builtin_bit_cast(fl_u16x2, key * 0x10001u); }
+
+struct FillRow16 {
+  const uint16_t *x;
+  uint32_t head, octs, tail;
+};
+
+__device__ inline FillRow16 fill_row16(const uint16_t *x, uint32_t V) {
+  FillRow16 R;
+  R.x = x;
+  const uint32_t to_boundary = (uint32_t)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) / 2;
+  R.head = to_boundary < V ? to_boundary : V;
+  R.octs = (V - R.head) / kFl16Oct;
+  R.tail = (V - R.head) % kFl16Oct;
+  return R;
+}
+
+__device__ inline int32_t fill_peel_id16(const FillRow16 &R, uint32_t lane) {
+  if (lane < R.head) return (int32_t)lane;
+  if (lane >= kFl16TailLane && lane - kFl16TailLane < R.tail) return (int32_t)(R.head + R.octs * kFl16Oct + (lane - kFl16TailLane));
+  return -1;
+}
+
+template <bool BF>
+__device__ inline uint4 fill_oct(const FillRow16 &R, uint32_t q) {
+  constexpr uint32_t none = Fl16<BF>::kNegInfBits * 0x10001u;
+  return q < R.octs ? *reinterpret_cast<const uint4 *>(R.x + R.head + (uint64_t)q * kFl16Oct) : make_uint4(none, none, none, none);
+}
+
+// The entries of a row with a NaN whose key is above every number's: those with a cleared sign bit.
+template <bool BF>
+__device__ inline uint32_t fill16_nans_above(const FillRow16 &R, uint32_t V, uint32_t lane) {
+  uint32_t n = 0;
+  for (uint32_t i = lane; i < V; i += 64) {
+    const uint32_t b = R.x[i];
+    n += b < 0x8000u && b > Fl16<BF>::kInfBits;
+  }
+  for (int d = 32; d; d >>= 1) n += __shfl_xor(n, d, 64);
+  return n;
+}
+
+template <bool BF>
+__global__ __launch_bounds__(kLbThreads) void fill_predict16_kernel(FillArgsT<uint16_t> A) {
+  using F = Fl16<BF>;
+  __shared__ unsigned long long counts[kLbWaves][kFlCounts];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t p = (uint64_t)blockIdx.x * kFlPerBlock + wave;  // uniform over the wavefront
+  const uint32_t V = A.V, k = A.k;
+  uint32_t n[kFlCounts] = {0, 0, 0, 0, 0};
+  if (p < A.n) {
+    const unsigned long long cell = A.pos[p];
+    float lse = NAN, lab_v = NAN;
+    int32_t lab_id = -1, rank = -1;
+    FillList L{NAN, NAN, -1, -1};
+    if (cell < A.cells) {
+      const FillRow16 R = fill_row16(A.logits + cell * V, V);
+      bool range = true;
+      uint32_t lab_key = 0;
+      if (A.labels) {
+        const long long l = A.labels64 ? static_cast<const long long *>(A.labels)[cell] : (long long)static_cast<const int32_t *>(A.labels)[cell];
+        range = l >= 0 && l < (long long)V;
+        if (range) {
+          lab_id = (int32_t)l;
+          const uint32_t b = R.x[l];
+          lab_v = F::widen(b);
+          lab_key = fl16_key(b);
+        }
+      }
+      const bool have_label = lab_v == lab_v;  // and then kKeyNegInf <= lab_key <= kKeyPosInf
+      // the peel step: looked at here, its head offered before the octets and its tail behind them
+      const int32_t pid = fill_peel_id16(R, lane);
+      const uint32_t pbits = pid >= 0 ? R.x[pid] : F::kNegInfBits, pkey = fl16_key(pbits);
+      const float pv = F::widen(pbits);
+      fl_u16x2 hi = fl16_both(pkey), lo = hi;
+      uint32_t ahead = have_label && pid >= 0 && (pkey > lab_key || (pkey == lab_key && pid < lab_id));
+      if (k) fill_offer(L, k, lane, pv, pid, pid >= 0 && lane < kFl16TailLane && pv == pv);
+      fl_u16x2 thr = fl16_both(L.thr_id >= 0 ? fl16_key(F::narrow(L.thr_v)) : 0u);
+      // `one` goes through an empty asm so that the compiler takes it for a variable: it rewrites min(a -sat t, 1) with a constant
+      // into a compare and a select per half, six instructions a register where v_pk_sub_u16 clamp and v_pk_min_u16 are two
+      uint32_t one_bits = 0x00010001u;
+      asm("" : "+v"(one_bits));
+      const fl_u16x2 t_before = fl16_both(lab_key - 1), t_from = fl16_both(lab_key), one = __builtin_bit_cast(fl_u16x2, one_bits);
+      const int32_t lab_oct = lab_id - (int32_t)(kFl16Oct - 1);  // an octet that starts below it ends before the label
+      uint4 next = fill_oct<BF>(R, lane);
+      for (uint32_t q0 = 0; q0 < R.octs;) {  // uniform
+        const uint32_t q_end = R.octs - q0 > 64 * kFl16FlushSteps ? q0 + 64 * kFl16FlushSteps : R.octs;
+        fl_u16x2 acc = (fl_u16x2)(0);
+        for (; q0 < q_end; q0 += 64) {
+          const uint32_t q = q0 + lane;
+          const uint4 cur = next;
+          next = fill_oct<BF>(R, q + 64);
+          const int32_t id0 = (int32_t)(R.head + q * kFl16Oct);
+          const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+          fl_u16x2 key[4];
+#pragma unroll
+          for (uint32_t j = 0; j < 4; j++) {
+            key[j] = fl16_keys(w[j]);
+            hi = __builtin_elementwise_max(hi, key[j]);
+            lo = __builtin_elementwise_min(lo, key[j]);
+          }
+          if (have_label) {  // uniform
+            const fl_u16x2 t = id0 < lab_oct ? t_before : t_from;
+            fl_u16x2 c[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) c[j] = __builtin_elementwise_min(__builtin_elementwise_sub_sat(key[j], t), one);
+            acc += (c[0] + c[1]) + (c[2] + c[3]);
+          }
+          if (!k) continue;
+          bool hit = q < R.octs;
+          if (L.thr_id >= 0) {  // uniform: the list is full, and only a key above its last entry's gets in
+            fl_u16x2 over = __builtin_elementwise_sub_sat(key[0], thr);
+#pragma unroll
+            for (uint32_t j = 1; j < 4; j++) over |= __builtin_elementwise_sub_sat(key[j], thr);
+            hit = __builtin_bit_cast(uint32_t, over) != 0;
+          }
+          if (__ballot(hit)) {
+            const bool live = q < R.octs;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+              float v0, v1;
+              F::widen2(w[j], v0, v1);
+              fill_offer(L, k, lane, v0, id0 + (int32_t)(2 * j), live && v0 == v0);
+              fill_offer(L, k, lane, v1, id0 + (int32_t)(2 * j + 1), live && v1 == v1);
+            }
+            if (L.thr_id >= 0) thr = fl16_both(fl16_key(F::narrow(L.thr_v)));
+          }
+        }
+        ahead += (uint32_t)acc.x + (uint32_t)acc.y;
+      }
+      if (k) fill_offer(L, k, lane, pv, pid, pid >= 0 && lane >= kFl16TailLane && pv == pv);
+      const int32_t oct_end = (int32_t)(R.head + R.octs * kFl16Oct);
+      if (have_label && lab_id >= (int32_t)R.head && lab_id < oct_end) {  // uniform: the ties before the label in its own octet
+        const int32_t id = lab_id - (int32_t)((uint32_t)(lab_id - (int32_t)R.head) % kFl16Oct) + (int32_t)lane;
+        if (id < lab_id && fl16_key(R.x[id]) == lab_key) ahead++;
+      }
+      uint32_t top = hi.x > hi.y ? hi.x : hi.y, low = lo.x < lo.y ? lo.x : lo.y;
+      for (int d = 32; d; d >>= 1) {
+        const uint32_t ot = __shfl_xor(top, d, 64), ol = __shfl_xor(low, d, 64);
+        if (ot > top) top = ot;
+        if (ol < low) low = ol;
+        ahead += __shfl_xor(ahead, d, 64);
+      }
+      const bool any_nan = top > F::kKeyPosInf || low < F::kKeyNegInf;
+      if (have_label) rank = (int32_t)(ahead - (any_nan ? fill16_nans_above<BF>(R, V, lane) : 0u));
+      const float m = F::widen(fl16_unkey(top));
+      if (any_nan) lse = NAN;
+      else if (m == -INFINITY || m == INFINITY) lse = m;
+      else if (A.lse) {  // pass 2
+        float a[kFl16Oct] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (pid >= 0) a[0] = expf(__fsub_rn(pv, m));
+        uint4 nx = fill_oct<BF>(R, lane);
+        for (uint32_t q0 = 0; q0 < R.octs; q0 += 64) {
+          const uint32_t q = q0 + lane;
+          const uint4 cur = nx;
+          nx = fill_oct<BF>(R, q + 64);
+          if (q < R.octs) {
+            const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+              float v0, v1;
+              F::widen2(w[j], v0, v1);
+              a[2 * j] = __fadd_rn(a[2 * j], expf(__fsub_rn(v0, m)));
+              a[2 * j + 1] = __fadd_rn(a[2 * j + 1], expf(__fsub_rn(v1, m)));
+            }
+          }
+        }
+        float s = __fadd_rn(__fadd_rn(__fadd_rn(a[0], a[1]), __fadd_rn(a[2], a[3])), __fadd_rn(__fadd_rn(a[4], a[5]), __fadd_rn(a[6], a[7])));
+        for (int d = 32; d; d >>= 1) s = __fadd_rn(s, __shfl_xor(s, d, 64));
+        lse = __fadd_rn(m, logf(s));
+      }
+      if (!lane) {
+        n[1] = rank == 0;
+        n[2] = rank >= 0 && (uint32_t)rank < (k ? k : 1u);
+        n[3] = any_nan;
+        n[4] = !range;
+      }
+    }
+    if (!lane) {
+      n[0] = 1;
+      if (A.lse) A.lse[p] = lse;
+      if (A.label_id) A.label_id[p] = lab_id;
+      if (A.label_logit) A.label_logit[p] = lab_v;
+      if (A.label_rank) A.label_rank[p] = rank;
+    }
+    if (lane < k) {
+      if (A.top_id) A.top_id[p * k + lane] = L.id;
+      if (A.top_logit) A.top_logit[p * k + lane] = L.id >= 0 ? L.v : NAN;
+    }
+  }
+  if (!A.part) return;  // uniform over the launch
+  const unsigned long long sum = bt_fold_counts(n, counts);
+  if (threadIdx.x < kFlCounts) A.part[(uint64_t)blockIdx.x * kFlCounts + threadIdx.x] = sum;
+}
+
 // the workgroups' selected cells and counts between the launches of a call: grow-only and shared by all calls of the process, as
 // the workspace of the label calls and under the same rule
 static DevBuf g_fill_ws;
@@ -303,7 +565,7 @@ static int positions_check(const PositionsCall &c) {
 }
 
 struct FillCall {
-  const float *logits;
+  const void *logits;
   uint64_t rows;
   uint32_t width;
   uint64_t V;
@@ -318,6 +580,8 @@ struct FillCall {
   float *label_logit;
   int32_t *label_rank;
   uint64_t *info;
+  uint32_t dtype = 0;  // 0: float32 logits, else SWT_FILL_F16 or SWT_FILL_BF16
+  size_t elem() const { return dtype ? 2 : 4; }
 };
 
 static int fill_check(const FillCall &c) {
@@ -334,11 +598,73 @@ static int fill_check(const FillCall &c) {
   if (all_cells > ((1ull << 62) - 1) / c.V) return fail(SWT_ERR_INVALID, "logits: 2^62 elements or more");
   if (c.n >> 32) return fail(SWT_ERR_INVALID, "n_pos: 2^32 positions or more");
   const size_t cells = (size_t)all_cells, np = (size_t)c.n * 4, id_bytes = (c.flags & SWT_FILL_IDS64) ? 8 : 4;
-  return lb_check_layout({{"logits", c.logits, cells * c.V * 4, 4, true, false}, {"pos", c.pos, (size_t)c.n * 8, 8, true, false},
+  return lb_check_layout({{"logits", c.logits, cells * c.V * c.elem(), c.elem(), true, false}, {"pos", c.pos, (size_t)c.n * 8, 8, true, false},
                           {"labels", c.labels, cells * id_bytes, id_bytes, false, false}, {"out_lse", c.lse, np, 4, false, true},
                           {"out_top_id", c.top_id, np * c.k, 4, false, true}, {"out_top_logit", c.top_logit, np * c.k, 4, false, true},
                           {"out_label_id", c.label_id, np, 4, false, true}, {"out_label_logit", c.label_logit, np, 4, false, true},
                           {"out_label_rank", c.label_rank, np, 4, false, true}, {"info", c.info, kFlCounts * 8, 8, false, true}});
+}
+
+static int fill_check_dtype(uint32_t dtype) {
+  return dtype == SWT_FILL_F16 || dtype == SWT_FILL_BF16 ? SWT_OK : fail(SWT_ERR_INVALID, "dtype: SWT_FILL_F16 or SWT_FILL_BF16");
+}
+
+template <class T>
+static FillArgsT<T> fill_args(const FillCall &c, unsigned long long *part) {
+  return {static_cast<const T *>(c.logits), reinterpret_cast<const unsigned long long *>(c.pos), c.labels, (c.flags & SWT_FILL_IDS64) ? 1u : 0u, c.n,
+          c.rows * c.width, (uint32_t)c.V, c.k, c.lse, c.top_id, c.top_logit, c.label_id, c.label_logit, c.label_rank, part};
+}
+
+// The `_dev` form of every element type: c holds device pointers.
+static int predict_dev(const FillCall &c, hipStream_t st) {
+  int rc = fill_check(c);
+  if (rc) return rc;
+  if ((rc = ensure_device())) return rc;
+  if (c.info) SWT_HIP(hipMemsetAsync(c.info, 0, kFlCounts * 8, st));
+  if (!c.n) return SWT_OK;
+  const unsigned grid = fl_grid(c.n, kFlPerBlock);
+  unsigned long long *part = nullptr;
+  if (c.info) {
+    if ((rc = g_fill_ws.reserve((size_t)grid * kFlCounts * 8))) return rc;
+    part = g_fill_ws.as<unsigned long long>();
+  }
+  prof_begin(st);
+  if (c.dtype == SWT_FILL_BF16) hipLaunchKernelGGL(fill_predict16_kernel<true>, dim3(grid), dim3(kLbThreads), 0, st, fill_args<uint16_t>(c, part));
+  else if (c.dtype == SWT_FILL_F16) hipLaunchKernelGGL(fill_predict16_kernel<false>, dim3(grid), dim3(kLbThreads), 0, st, fill_args<uint16_t>(c, part));
+  else hipLaunchKernelGGL(fill_predict_kernel, dim3(grid), dim3(kLbThreads), 0, st, fill_args<float>(c, part));
+  prof_end(st);
+  if (c.info) launch_counts_sum(part, grid, kFlCounts, reinterpret_cast<unsigned long long *>(c.info), st);
+  SWT_HIP(hipGetLastError());
+  return SWT_OK;
+}
+
+// The host form of every element type: everything is checked before anything touches the device.
+static int predict_host(const FillCall &c) {
+  int rc = fill_check(c);
+  if (rc) return rc;
+  const size_t cells = (size_t)c.rows * c.width;
+  for (uint64_t p = 0; p < c.n; p++)
+    if (c.pos[p] >= cells) return fail(SWT_ERR_INVALID, "pos: position %llu is no cell of the rows", (unsigned long long)p);
+  if (c.info)
+    for (uint32_t i = 0; i < kFlCounts; i++) c.info[i] = 0;
+  if (!c.n) return SWT_OK;
+  if ((rc = ensure_device())) return rc;
+  const size_t np = (size_t)c.n * 4;
+  BatchStage s;
+  FillCall d = c;
+  d.logits = s.in(static_cast<const uint8_t *>(c.logits), cells * c.V * c.elem());
+  d.pos = s.in(c.pos, (size_t)c.n * 8);
+  d.labels = s.in(static_cast<const uint8_t *>(c.labels), cells * ((c.flags & SWT_FILL_IDS64) ? 8 : 4));
+  d.lse = s.out(c.lse, np);
+  d.top_id = s.out(c.top_id, np * c.k);
+  d.top_logit = s.out(c.top_logit, np * c.k);
+  d.label_id = s.out(c.label_id, np);
+  d.label_logit = s.out(c.label_logit, np);
+  d.label_rank = s.out(c.label_rank, np);
+  d.info = s.out(c.info, kFlCounts * 8);
+  if (s.rc) return s.rc;
+  if ((rc = predict_dev(d, nullptr))) return rc;
+  return s.fetch();
 }
 
 }  // namespace swt
@@ -400,54 +726,40 @@ int swt_mlm_positions(const void *ids, uint64_t rows, uint32_t width, int64_t va
 int swt_mlm_predict_dev(const float *d_logits, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *d_pos, uint64_t n_pos,
                         const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id, float *d_out_top_logit,
                         int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info, void *stream) try {
-  int rc = fill_check({d_logits, rows, width, n_vocab, d_pos, n_pos, d_labels, flags, k, d_out_lse, d_out_top_id, d_out_top_logit,
-                       d_out_label_id, d_out_label_logit, d_out_label_rank, d_info});
-  if (rc) return rc;
-  if ((rc = ensure_device())) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (d_info) SWT_HIP(hipMemsetAsync(d_info, 0, kFlCounts * 8, st));
-  if (!n_pos) return SWT_OK;
-  FillArgs A{d_logits, reinterpret_cast<const unsigned long long *>(d_pos), d_labels, (flags & SWT_FILL_IDS64) ? 1u : 0u, n_pos, rows * width,
-             (uint32_t)n_vocab, k, d_out_lse, d_out_top_id, d_out_top_logit, d_out_label_id, d_out_label_logit, d_out_label_rank, nullptr};
-  const unsigned grid = fl_grid(n_pos, kFlPerBlock);
-  if (d_info) {
-    if ((rc = g_fill_ws.reserve((size_t)grid * kFlCounts * 8))) return rc;
-    A.part = g_fill_ws.as<unsigned long long>();
-  }
-  prof_begin(st);
-  hipLaunchKernelGGL(fill_predict_kernel, dim3(grid), dim3(kLbThreads), 0, st, A);
-  prof_end(st);
-  if (d_info) launch_counts_sum(A.part, grid, kFlCounts, reinterpret_cast<unsigned long long *>(d_info), st);
-  SWT_HIP(hipGetLastError());
-  return SWT_OK;
+  return predict_dev({d_logits, rows, width, n_vocab, d_pos, n_pos, d_labels, flags, k, d_out_lse, d_out_top_id, d_out_top_logit, d_out_label_id,
+                      d_out_label_logit, d_out_label_rank, d_info},
+                     (hipStream_t)stream);
 } SWT_API_CATCH
 
 int swt_mlm_predict(const float *logits, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *pos, uint64_t n_pos, const void *labels,
                     uint32_t flags, uint32_t k, float *out_lse, int32_t *out_top_id, float *out_top_logit, int32_t *out_label_id,
                     float *out_label_logit, int32_t *out_label_rank, uint64_t *info) try {
-  int rc = fill_check({logits, rows, width, n_vocab, pos, n_pos, labels, flags, k, out_lse, out_top_id, out_top_logit, out_label_id,
+  return predict_host({logits, rows, width, n_vocab, pos, n_pos, labels, flags, k, out_lse, out_top_id, out_top_logit, out_label_id,
                        out_label_logit, out_label_rank, info});
-  if (rc) return rc;
-  const size_t cells = (size_t)rows * width;
-  for (uint64_t p = 0; p < n_pos; p++)
-    if (pos[p] >= cells) return fail(SWT_ERR_INVALID, "pos: position %llu is no cell of the rows", (unsigned long long)p);
-  if (info)
-    for (uint32_t i = 0; i < kFlCounts; i++) info[i] = 0;
-  if (!n_pos) return SWT_OK;
-  if ((rc = ensure_device())) return rc;
-  const size_t np = (size_t)n_pos * 4;
-  BatchStage s;
-  const float *d_logits = s.in(logits, cells * n_vocab * 4);
-  const uint64_t *d_pos = s.in(pos, (size_t)n_pos * 8);
-  const void *d_labels = s.in(static_cast<const uint8_t *>(labels), cells * ((flags & SWT_FILL_IDS64) ? 8 : 4));
-  float *d_lse = s.out(out_lse, np), *d_tl = s.out(out_top_logit, np * k), *d_ll = s.out(out_label_logit, np);
-  int32_t *d_ti = s.out(out_top_id, np * k), *d_li = s.out(out_label_id, np), *d_lr = s.out(out_label_rank, np);
-  uint64_t *d_info = s.out(info, kFlCounts * 8);
-  if (s.rc) return s.rc;
-  if ((rc = swt_mlm_predict_dev(d_logits, rows, width, n_vocab, d_pos, n_pos, d_labels, flags, k, d_lse, d_ti, d_tl, d_li, d_ll, d_lr, d_info,
-                                nullptr)))
-    return rc;
-  return s.fetch();
+} SWT_API_CATCH
+
+int swt_fill_capacity16(uint32_t *values_per_step, uint32_t *lane_sums) try {
+  if (values_per_step) *values_per_step = kFl16Step;
+  if (lane_sums) *lane_sums = kFl16Oct;
+  return SWT_OK;
+} SWT_API_CATCH
+
+int swt_mlm_predict16_dev(const uint16_t *d_logits, uint32_t dtype, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *d_pos,
+                          uint64_t n_pos, const void *d_labels, uint32_t flags, uint32_t k, float *d_out_lse, int32_t *d_out_top_id,
+                          float *d_out_top_logit, int32_t *d_out_label_id, float *d_out_label_logit, int32_t *d_out_label_rank, uint64_t *d_info,
+                          void *stream) try {
+  if (int rc = fill_check_dtype(dtype)) return rc;
+  return predict_dev({d_logits, rows, width, n_vocab, d_pos, n_pos, d_labels, flags, k, d_out_lse, d_out_top_id, d_out_top_logit, d_out_label_id,
+                      d_out_label_logit, d_out_label_rank, d_info, dtype},
+                     (hipStream_t)stream);
+} SWT_API_CATCH
+
+int swt_mlm_predict16(const uint16_t *logits, uint32_t dtype, uint64_t rows, uint32_t width, uint64_t n_vocab, const uint64_t *pos, uint64_t n_pos,
+                      const void *labels, uint32_t flags, uint32_t k, float *out_lse, int32_t *out_top_id, float *out_top_logit,
+                      int32_t *out_label_id, float *out_label_logit, int32_t *out_label_rank, uint64_t *info) try {
+  if (int rc = fill_check_dtype(dtype)) return rc;
+  return predict_host({logits, rows, width, n_vocab, pos, n_pos, labels, flags, k, out_lse, out_top_id, out_top_logit, out_label_id,
+                       out_label_logit, out_label_rank, info, dtype});
 } SWT_API_CATCH
 
 }  // extern "C"

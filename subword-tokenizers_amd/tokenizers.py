@@ -351,9 +351,12 @@ class SubwordTokenizer:
         """The top_k best tokens of every [MASK] column -- input_ids == mask_id() -- from a masked-LM's logits ([rows, width, V],
         float32), on the device (swt_mlm_positions, swt_mlm_predict), which reads the logits of those columns and of no other
         and makes no copy of them.  The order: the greater logit, then the smaller id; a NaN logit is no candidate.
+        A torch tensor on the GPU may also be float16 or bfloat16, as a model under autocast makes it: it is read as it lies
+        (swt_mlm_predict16, no logits.float()), every value counts as its exact float32 widening, and everything that comes back
+        is float32 as before.  Such logits are born on the device: a NumPy array is float32.
         input_ids: a 2-D C-contiguous int32 or int64 NumPy array, or such a torch tensor on the GPU, and C-contiguous logits of
         the same kind (then everything stays on the device and the current stream; the number of columns and the counts are
-        read back); logits that are not float32 or not of that kind raise TypeError; a shape other than [rows, width, V],
+        read back); logits of another type or not of that kind raise TypeError; a shape other than [rows, width, V],
         logits that are not contiguous or a top_k outside 1 .. 64 ValueError.
         -> per [MASK] column, in row-major order, {"row", "col", "token_ids" [n, top_k] (-1 where the row has fewer entries
         that are no NaN), "logit", "logprob" (logit - the row's log-sum-exp), "score" (exp(logprob)), "lse"}, "n_positions",
@@ -363,7 +366,8 @@ class SubwordTokenizer:
 
     def mlm_scores(self, logits, labels, top_k: int = 1) -> dict:
         """A masked-LM's logits ([rows, width, V], float32) scored against `labels` of encode_batch(..., mlm=...) or mask_tokens
-        at the columns with labels != -100, on the device (swt_mlm_positions, swt_mlm_predict).  Kinds, TypeError and
+        at the columns with labels != -100, on the device (swt_mlm_positions, swt_mlm_predict).  Kinds -- float16 and bfloat16
+        tensors on the GPU among them, with loss, perplexity and every log-probability float32 as before -- TypeError and
         ValueError as fill_mask.
         -> per such column {"row", "col", "label" (-1 for a label outside [0, V)), "label_logprob", "label_rank" (the entries
         that come before the label's: 0 for the argmax; -1 for a label out of range or with a NaN logit), "lse", and the top_k

@@ -12,7 +12,13 @@ round after round, HIP events around enough back-to-back calls for 0.2 s.
 
 Without --step this is the driver: every point is a process of its own under its own `timeout`, a failing point ends the run,
 and the points' JSON lines go to --out (profiles/fill_mask.txt).  `--step SHAPE:K --library-only` runs the library's calls
-alone, for a counter pass around it."""
+alone, for a counter pass around it.
+
+`--half SHAPE:K` is the point of the 16-bit form (swt_mlm_predict16_dev, profiles/fill_mask_16bit.txt): the same labels, the logits
+rounded to bfloat16 and to float16 on the device, and four legs -- the 16-bit kernel on each, fill_predict_kernel on the bfloat16
+values widened to float32 beforehand, and logits.float() followed by it, which is what a caller had to do -- with the peak of the
+device memory each leg allocates.  Before the timing the 16-bit outputs must equal the float32 kernel's on the widened values,
+the lse within the sum of the two tolerances.  With --library-only: each kernel three times, for a trace or a counter pass."""
 import argparse
 import json
 import os
@@ -44,16 +50,9 @@ def torch_leg(torch, logits, labels, k):
     return lse, top_v, top_i, lv[:, 0], rank
 
 
-def step(args):
-    import torch
-
-    from subword_tokenizers_amd import _native as N
+def point(shape):
+    """-> (rows, width, V, labels on the device) of a shape"""
     from subword_tokenizers_amd import synth, tokenizers
-    from tests import fill_cases as F
-
-    N.init(0)
-    shape, k = args.step.split(":")
-    k = int(k)
     if shape == "fastbpe_64":
         tok = tokenizers.FastBPE()
         tok.merges_list = list(synth.pretrained_merges()[:8000])
@@ -70,7 +69,41 @@ def step(args):
     V = tok.mask_id() + 1
     texts = synth.s85k_open(85000)[:rows]
     batch = tok.encode_batch(texts, max_length=width, padding="max_length", device=True, mlm={"probability": PROBABILITY, "seed": 7})
-    labels = batch["labels"].contiguous()
+    return rows, width, V, batch["labels"].contiguous()
+
+
+def timed(torch, fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record(); e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def rounds_of(torch, legs, args):
+    """the legs alternate inside a round, each timed over enough back-to-back calls for 0.2 s -> (per leg its summary, the calls)"""
+    reps = {name: max(1, int(np.ceil(200.0 / max(timed(torch, fn, 3), 1e-3)))) for name, fn in legs.items()}
+    ms = {name: [] for name in legs}
+    for r in range(args.warmup + args.rounds):
+        t = {name: timed(torch, fn, reps[name]) for name, fn in legs.items()}
+        if r >= args.warmup:
+            for name, v in t.items():
+                ms[name].append(v)
+    return {name: {"ms": [round(x, 4) for x in v], "median_ms": round(statistics.median(v), 4),
+                   "spread": round((max(v) - min(v)) / statistics.median(v), 4)} for name, v in ms.items()}, reps
+
+
+def step(args):
+    import torch
+
+    from subword_tokenizers_amd import _native as N
+    from tests import fill_cases as F
+
+    N.init(0)
+    shape, k = args.step.split(":")
+    k = int(k)
+    rows, width, V, labels = point(shape)
     gen = torch.Generator(device="cuda").manual_seed(11)
     logits = torch.randn((rows, width, V), device="cuda", generator=gen)
     lib, stream = N.lib(), torch.cuda.current_stream().cuda_stream
@@ -122,24 +155,8 @@ def step(args):
     worst = float((err / F.U).max())
     del x, exact, err, tol, lse, top_v, top_i, lv, rank
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record(); e1.synchronize()
-        return e0.elapsed_time(e1) / reps
-
     legs = {"library": library, "torch": lambda: torch_leg(torch, logits, labels, k), "mlm_positions_dev": positions, "mlm_predict_dev": predict}
-    reps = {name: max(1, int(np.ceil(200.0 / max(timed(fn, 3), 1e-3)))) for name, fn in legs.items()}
-    ms = {name: [] for name in legs}
-    for r in range(args.warmup + args.rounds):
-        t = {name: timed(fn, reps[name]) for name, fn in legs.items()}  # the legs alternate inside a round
-        if r >= args.warmup:
-            for name, v in t.items():
-                ms[name].append(v)
-    res = {name: {"ms": [round(x, 4) for x in v], "median_ms": round(statistics.median(v), 4),
-                  "spread": round((max(v) - min(v)) / statistics.median(v), 4)} for name, v in ms.items()}
+    res, reps = rounds_of(torch, legs, args)
     nbytes = n * V * 4
     for name in ("library", "mlm_predict_dev"):
         gbps = nbytes / res[name]["median_ms"] / 1e6
@@ -156,6 +173,91 @@ def step(args):
     return 0
 
 
+def step_half(args):
+    import torch
+
+    from subword_tokenizers_amd import _native as N
+    from tests import fill_cases as F
+
+    N.init(0)
+    shape, k = args.half.split(":")
+    k = int(k)
+    rows, width, V, labels = point(shape)
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    bf = torch.randn((rows, width, V), device="cuda", generator=gen).to(torch.bfloat16)
+    f16 = bf.float().mul_(1.0009765625).to(torch.float16)  # other bits than the bfloat16 values have: ten bits of fraction, not seven
+    wide = bf.float()
+    lib, stream = N.lib(), torch.cuda.current_stream().cuda_stream
+    p = lambda a: None if a is None else a.data_ptr()
+    d_pos = torch.empty(rows * width, dtype=torch.int64, device="cuda")
+    d_plan, d_info = torch.zeros(2, dtype=torch.int64, device="cuda"), torch.zeros(5, dtype=torch.int64, device="cuda")
+    N.check(lib.swt_mlm_positions_dev(p(labels), rows, width, -100, N.FILL_NOT_EQUAL, 0, p(d_pos), p(d_plan), stream))
+    n = int(d_plan[0])
+    types = {np.float32: torch.float32, np.int32: torch.int32}
+    out = {name: torch.empty((n, k) if per_k else n, dtype=types[t], device="cuda") for name, t, per_k in N.FILL_OUT}
+    tail = lambda: (rows, width, V, p(d_pos), n, p(labels), 0, k, *[p(out[name]) for name, _, _ in N.FILL_OUT], p(d_info), stream)
+    predict16 = lambda x, code: N.check(lib.swt_mlm_predict16_dev(p(x), code, *tail()))
+    predict32 = lambda x: N.check(lib.swt_mlm_predict_dev(p(x), *tail()))
+    legs = {"predict16_bf16": lambda: predict16(bf, N.FILL_BF16), "predict16_f16": lambda: predict16(f16, N.FILL_F16),
+            "predict_f32_of_widened": lambda: predict32(wide), "float_then_predict_f32": lambda: predict32(bf.float())}
+    if args.library_only:
+        for name in ("predict16_bf16", "predict16_f16", "predict_f32_of_widened"):
+            for _ in range(3):
+                legs[name]()
+        torch.cuda.synchronize()
+        print(json.dumps({"shape": shape, "V": V, "top_k": k, "positions": n, "values": n * V}), flush=True)
+        return 0
+    # ---- the 16-bit kernel gives what the float32 kernel gives on the widened values
+    snap = lambda: ({name: a.clone() for name, a in out.items()}, d_info.tolist())
+    tol16 = lambda lse: _lse_tol16(F, V, N.fill_capacity16(), lse)
+    for half, code in ((bf, N.FILL_BF16), (f16, N.FILL_F16)):
+        predict16(half, code)
+        got, info16 = snap()
+        predict32(half.float())
+        want, info32 = snap()
+        assert info16 == info32 and info16[0] == n
+        for name in got:
+            if name != "lse":
+                assert torch.equal(got[name], want[name]), name
+        exact = half[labels != -100].double().logsumexp(1)
+        err = (got["lse"].double() - exact).abs().cpu().numpy()
+        tol = np.array([tol16(float(v)) for v in exact.cpu()])
+        assert (err <= tol).all(), "lse: %.3f of the tolerance" % float((err / tol).max())
+        worst = float((err / F.U).max())
+    del got, want, exact
+    torch.cuda.synchronize()
+    peak = {}
+    for name, fn in legs.items():  # what a leg allocates on the device at its peak, beyond what is there before it
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        peak[name] = torch.cuda.max_memory_allocated() - before
+    res, reps = rounds_of(torch, legs, args)
+    for name in res:
+        nbytes = n * V * (2 if name.startswith("predict16") else 4)
+        gbps = nbytes / res[name]["median_ms"] / 1e6
+        res[name].update({"peak_bytes_allocated": peak[name], "selected_rows_bytes": nbytes})
+        if name != "float_then_predict_f32":
+            res[name].update({"rows_gb_s": round(gbps, 1), "share_of_hbm_peak": round(gbps / HBM_GBPS, 4)})
+    line = json.dumps({"shape": shape, "rows": rows, "width": width, "V": V, "top_k": k, "positions": n, "logits_bytes_16": rows * width * V * 2,
+                       "logits_bytes_32": rows * width * V * 4, "info": d_info.tolist(), "lse_largest_error_in_2^-24": round(worst, 3),
+                       "lse_tol16_in_2^-24_at_lse_0": round(tol16(0.0) / F.U, 1), "rounds": args.rounds, "calls_per_window": reps, "legs": res})
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a", encoding="utf-8") as f:
+            f.write(line + "\n")
+    return 0
+
+
+def _lse_tol16(F, V, cap, lse):
+    """fill_cases.lse_tol with chain16 of include/swt.h for its chain"""
+    import math
+    chain = min(V - 1, -(-V // cap[0]) + int(math.log2(cap[1])) + 6)
+    r = (1.0 + (1.0 + math.log(V)) * F.U) * (1.0 + F.U) ** (chain + 2) - 1.0
+    return r / (1.0 - r) + 2.0 * F.U * math.log(V) + F.U * abs(lse)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -163,7 +265,10 @@ def main():
     ap.add_argument("--step", default=None, help="SHAPE:TOP_K, one point in this process")
     ap.add_argument("--library-only", action="store_true", help="with --step: the library's calls a few times and nothing else")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fill_mask.txt"))
+    ap.add_argument("--half", default=None, help="SHAPE:TOP_K, the point of the 16-bit form in this process")
     args = ap.parse_args()
+    if args.half:
+        return step_half(args)
     if args.step:
         return step(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
