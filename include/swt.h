@@ -970,6 +970,79 @@ int swt_mlm_mask_dev(const void *d_ids, uint64_t rows, uint32_t width, const uin
 int swt_mlm_capacity(uint32_t *cols_per_step, uint32_t *rows_per_wave_max);
 
 /* ------------------------------------------------------------------------------------------------
+ * Span-corruption batches: over the same rows ids[rows, width] (int32, int64 with SWT_DENOISE_IDS64; C-contiguous), the span noise
+ * of three denoising objectives -- SpanBERT (spans masked in place), T5 (every span one sentinel in the row, the spans listed
+ * behind their sentinels in the labels) and BART text infilling (every span one [MASK]).  The reference has nothing of the sort;
+ * tests/denoise_cases.py holds these semantics in plain Python, and the kernel equals it bit for bit.
+ *
+ * UNITS.  cls_tab, the classes, eligibility and heads are exactly those of swt_mlm_mask (a '##' column whose left neighbour is
+ * class 2 or missing is a head); SWT_DENOISE_WHOLE_WORD plays the part of SWT_MLM_WHOLE_WORD: without it every eligible column
+ * is its own head.  The units of a row are its heads in column order, u = 0, 1, ...; a unit is the head and the eligible
+ * non-head columns that follow it.
+ *
+ * DRAWS.  The draw of a unit is Philox4x32-10 (as swt_mlm_mask) of the counter (head column, row, epoch, 1) under the key (seed's
+ * low word, seed's high word): word 3 of the counter is 1, so no draw is shared with swt_mlm_mask.  The unit STARTS A SPAN iff
+ * x0 < start_below, an integer in [0, 2^32]; the span's length in units is L = 1 + #{k < n_len : x1 >= len_below[k]}, len_below
+ * a non-decreasing table with entries in [0, 2^32] and n_len <= 31, so L lies in 1 .. 32 and P(L > k) = 1 - len_below[k - 1] /
+ * 2^32.  There is no floating point on the device.
+ *
+ * NOISE.  Unit u is noise iff some start s <= u has s + L(s) > u (a prefix maximum of s + L(s) over the starts: spans may
+ * overlap, and a span may run past the row's last unit).  A column is noise iff it is eligible and its unit is; class 2 columns
+ * never are.  A RUN is a maximal stretch of adjacent noise columns -- a class 2 column inside a span cuts it into two runs --,
+ * numbered k = 0, 1, ... from the left of the row.
+ *
+ * SWT_DENOISE_MASK (SpanBERT): out_ids[rows, width] holds mask_id on noise columns and the id elsewhere, out_labels[rows, width]
+ * the id on noise columns and -100 elsewhere.  out_mask, out_len and out_label_len are NULL.
+ * SWT_DENOISE_SENTINEL (T5), with sentinel_ids[n_sentinel], n_sentinel >= 2: a run with k >= n_sentinel - 1 is not noise after
+ * all -- its columns stay, and it is counted in info[3].  out_ids[rows, width]: the row's non-noise columns in order, every run
+ * replaced by the one id sentinel_ids[k]; the rest is pad_id.  out_mask[rows, width] (uint8; may be NULL): 1 where a sentinel
+ * stands or a kept column whose id is not pad_id, else 0.  out_len[rows] (may be NULL): the columns written before the fill.
+ * out_labels[rows, label_width]: for each run in order sentinel_ids[k], then the run's original ids; after the last run
+ * sentinel_ids[the number of runs] (a row with no run: sentinel_ids[0] alone); the rest is -100; what lies at label_width or
+ * beyond is cut.  out_label_len[rows] (may be NULL): the length before the cut, the closing sentinel included.
+ * SWT_DENOISE_INFILL (BART): as SENTINEL, but every run is replaced by mask_id, there is no cap on runs, and there is no label
+ * output (the labels are ids): out_labels and out_label_len are NULL.
+ *
+ * info[7]: eligible columns; noise columns (those of runs given back not among them); runs (those given back among them); runs
+ * given back for lack of sentinels; rows whose labels were cut (label length > label_width, SENTINEL mode); the greatest out_len
+ * (the width in MASK mode); the greatest label length (0 outside SENTINEL mode).  swt_denoise_plan makes info alone and reads
+ * neither sentinel_ids nor any output: called with the label_width a caller is ready to give (2^32 - 1: any), its info[6] is the
+ * label_width that cuts no row.  The result is a function of (seed, epoch, row, column) and the row's content alone -- not of the
+ * launch, of the other rows of the call or of the integer width.
+ *
+ * SWT_ERR_INVALID, swt_last_error naming the argument: NULL ids, cls_tab or spec, NULL info of a plan; NULL out_ids, NULL
+ * out_labels outside INFILL mode, NULL sentinel_ids in SENTINEL mode; an output the mode does not have; width == 0 with rows >
+ * 0; 2^32 rows or more; 2^31 columns or more; an unknown flag or mode; start_below above 2^32; n_len > 31; a len_below that
+ * decreases or exceeds 2^32; n_class == 0; n_sentinel < 2 in SENTINEL mode; an output that overlaps ids.  rows == 0 succeeds and
+ * zeroes info.  The spec is a host pointer in all forms; its `reserved` is not read.  The host forms check everything before
+ * anything touches the device.  The `_dev` forms take device pointers (aligned to their element type; 16 bytes get the wide
+ * loads and stores), enqueue on the stream and do not synchronise; they write every element of every output given and nothing
+ * outside it, whatever ids holds, and fill d_info[0..6] (zeroes for no row).  With d_info they keep the workgroups' counts
+ * between their two launches in a workspace of the process: no two such calls at once on different streams.
+ * swt_denoise_capacity: the columns of a row one step covers, the label ids one step stages, and the greatest n_len
+ * (csrc/swt_denoise.hip). */
+#define SWT_DENOISE_WHOLE_WORD 1u
+#define SWT_DENOISE_IDS64 4u /* the value of SWT_BATCH_IDS64 */
+#define SWT_DENOISE_MASK 0u
+#define SWT_DENOISE_SENTINEL 1u
+#define SWT_DENOISE_INFILL 2u
+typedef struct swt_denoise_spec {
+  uint64_t seed, start_below;
+  uint64_t len_below[31];
+  uint32_t n_len, epoch, flags, mode, mask_id, pad_id, n_class, n_sentinel, label_width, reserved;
+} swt_denoise_spec;
+int swt_denoise_plan(const void *ids, uint64_t rows, uint32_t width, const uint8_t *cls_tab, const swt_denoise_spec *spec, uint64_t *info);
+int swt_denoise_plan_dev(const void *d_ids, uint64_t rows, uint32_t width, const uint8_t *d_cls_tab, const swt_denoise_spec *spec,
+                         uint64_t *d_info, void *stream);
+int swt_denoise_rows(const void *ids, uint64_t rows, uint32_t width, const uint8_t *cls_tab, const uint32_t *sentinel_ids,
+                     const swt_denoise_spec *spec, void *out_ids, uint8_t *out_mask, uint32_t *out_len, void *out_labels,
+                     uint32_t *out_label_len, uint64_t *info);
+int swt_denoise_rows_dev(const void *d_ids, uint64_t rows, uint32_t width, const uint8_t *d_cls_tab, const uint32_t *d_sentinel_ids,
+                         const swt_denoise_spec *spec, void *d_out_ids, uint8_t *d_out_mask, uint32_t *d_out_len, void *d_out_labels,
+                         uint32_t *d_out_label_len, uint64_t *d_info, void *stream);
+int swt_denoise_capacity(uint32_t *cols_per_step, uint32_t *stage_labels, uint32_t *n_len_max);
+
+/* ------------------------------------------------------------------------------------------------
  * Decoding: finished rows ids[rows, width] of dense ids (int32, int64 with SWT_DECODE_IDS64; C-contiguous; any input_ids of the
  * batch calls above, a model's output) back to text, as the reference's recover_sentence (utils.py:141-154) spells the rows'
  * tokens.  tests/decode_cases.py holds these semantics, tests/golden/recover_sentence.json pins them to the reference's strings,

@@ -55,6 +55,19 @@ class MlmSpec(C.Structure):
 
 
 msp = C.POINTER(MlmSpec)
+DENOISE_WHOLE_WORD, DENOISE_IDS64 = 1, 4  # the flags of swt_denoise_spec
+DENOISE_MASK, DENOISE_SENTINEL, DENOISE_INFILL = 0, 1, 2  # its modes
+DENOISE_LEN_MAX = 31  # the entries of len_below at most
+
+
+class DenoiseSpec(C.Structure):
+    """swt_denoise_spec (include/swt.h): the draws, thresholds and ids of a span-corruption call"""
+    _fields_ = [("seed", C.c_uint64), ("start_below", C.c_uint64), ("len_below", C.c_uint64 * DENOISE_LEN_MAX)] + \
+               [(name, C.c_uint32) for name in ("n_len", "epoch", "flags", "mode", "mask_id", "pad_id", "n_class", "n_sentinel",
+                                                "label_width", "reserved")]
+
+
+dsp = C.POINTER(DenoiseSpec)
 
 # every symbol include/swt.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -191,6 +204,11 @@ SIGNATURES = {
     "swt_mlm_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u8p, u32p, C.c_uint32, msp, C.c_void_p, C.c_void_p, u8p, u64p]),
     "swt_mlm_mask_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, msp] + [C.c_void_p] * 5),
     "swt_mlm_capacity": (C.c_int, [u32p, u32p]),
+    "swt_denoise_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u8p, dsp, u64p]),
+    "swt_denoise_plan_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, dsp, C.c_void_p, C.c_void_p]),
+    "swt_denoise_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u8p, u32p, dsp, C.c_void_p, u8p, u32p, C.c_void_p, u32p, u64p]),
+    "swt_denoise_rows_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, dsp] + [C.c_void_p] * 7),
+    "swt_denoise_capacity": (C.c_int, [u32p, u32p, u32p]),
     "swt_decode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
     "swt_decode_plan_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] +
                             [C.c_void_p] * 4),
@@ -917,6 +935,77 @@ def mlm_mask(ids, cls_tab, rand_ids, spec, selected=True, info=True):
     check(lib().swt_mlm_mask(at(ids, C.c_void_p), rows, width, at(cls_tab, u8p), at(rand_ids, u32p), 0 if rand_ids is None else int(rand_ids.size),
                              C.byref(spec), at(out["input_ids"], C.c_void_p), at(out["labels"], C.c_void_p), at(out["selected"], u8p),
                              at(out["info"], u64p)))
+    return out
+
+
+def denoise_capacity():
+    """-> (cols_per_step, stage_labels, n_len_max): the columns of a row one step of the span-corruption kernel covers, the label
+    ids a step stages, and the entries of len_below at most (csrc/swt_denoise.hip)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().swt_denoise_capacity(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def denoise_spec(mode, n_class, mask_id, pad_id, start_below, len_below, n_sentinel=0, label_width=0, seed=0, epoch=0, whole_word=True,
+                 ids64=False):
+    """a DenoiseSpec; start_below and the entries of len_below are integers in [0, 2^32]"""
+    len_below = [int(x) for x in len_below]
+    if len(len_below) > DENOISE_LEN_MAX:
+        raise ValueError("len_below holds %d entries at most" % DENOISE_LEN_MAX)
+    table = (C.c_uint64 * DENOISE_LEN_MAX)(*len_below)
+    return DenoiseSpec(int(seed), int(start_below), table, len(len_below), int(epoch),
+                       (DENOISE_WHOLE_WORD if whole_word else 0) | (DENOISE_IDS64 if ids64 else 0), int(mode), int(mask_id), int(pad_id),
+                       int(n_class), int(n_sentinel), int(label_width), 0)
+
+
+def _denoise_ids(ids, spec):
+    want = np.int64 if spec.flags & DENOISE_IDS64 else np.int32
+    if not isinstance(ids, np.ndarray) or ids.dtype != want or ids.ndim != 2 or not ids.flags.c_contiguous:
+        raise TypeError("ids: a 2-D C-contiguous array of %s" % np.dtype(want).name)
+    return ids.shape
+
+
+_one = np.zeros(4, dtype=np.uint64)  # an array of no element still needs an address
+
+
+def _denoise_at(a, typ):
+    return None if a is None else C.cast(_vp(a) if a.size else _vp(_one), typ)
+
+
+def denoise_plan(ids, cls_tab, spec):
+    """info uint64[7] of a span-corruption call over rows of dense ids (swt_denoise_plan): eligible, noise columns, runs, runs
+    given back, rows cut at spec.label_width, the greatest length, the greatest label length"""
+    rows, width = _denoise_ids(ids, spec)
+    cls_tab = np.ascontiguousarray(cls_tab, dtype=np.uint8)
+    if cls_tab.size < spec.n_class:
+        raise ValueError("cls_tab holds n_class entries")
+    info = np.zeros(7, dtype=np.uint64)
+    check(lib().swt_denoise_plan(_denoise_at(ids, C.c_void_p), rows, width, _denoise_at(cls_tab, u8p), C.byref(spec), _denoise_at(info, u64p)))
+    return info
+
+
+def denoise_rows(ids, cls_tab, sentinel_ids, spec, info=True):
+    """The span-corrupted rows (swt_denoise_rows).  -> dict: input_ids; labels (None in INFILL mode); attention_mask uint8, length
+    uint32 (None in MASK mode); label_length uint32 (SENTINEL mode, else None); info uint64[7] (or None)"""
+    rows, width = _denoise_ids(ids, spec)
+    cls_tab = np.ascontiguousarray(cls_tab, dtype=np.uint8)
+    if cls_tab.size < spec.n_class:
+        raise ValueError("cls_tab holds n_class entries")
+    if sentinel_ids is not None:
+        sentinel_ids = np.ascontiguousarray(sentinel_ids, dtype=np.uint32)
+        if sentinel_ids.size < spec.n_sentinel:
+            raise ValueError("sentinel_ids holds n_sentinel entries")
+    sentinel, squeeze = spec.mode == DENOISE_SENTINEL, spec.mode != DENOISE_MASK
+    out = {"input_ids": np.zeros_like(ids),
+           "labels": np.zeros((rows, spec.label_width), dtype=ids.dtype) if sentinel else None if squeeze else np.zeros_like(ids),
+           "attention_mask": np.zeros(ids.shape, dtype=np.uint8) if squeeze else None,
+           "length": np.zeros(rows, dtype=np.uint32) if squeeze else None,
+           "label_length": np.zeros(rows, dtype=np.uint32) if sentinel else None,
+           "info": np.zeros(7, dtype=np.uint64) if info else None}
+    at = _denoise_at
+    check(lib().swt_denoise_rows(at(ids, C.c_void_p), rows, width, at(cls_tab, u8p), at(sentinel_ids, u32p), C.byref(spec),
+                                 at(out["input_ids"], C.c_void_p), at(out["attention_mask"], u8p), at(out["length"], u32p),
+                                 at(out["labels"], C.c_void_p), at(out["label_length"], u32p), at(out["info"], u64p)))
     return out
 
 

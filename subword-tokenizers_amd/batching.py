@@ -4,7 +4,8 @@ A tokenizer class gives its `Vocabulary` (`_batch_vocabulary`: specials and toke
 encoder's ids to dense ids) and its encode calls (`encode_ids_batch`, `_batch_encode_spans`, `_batch_encode_dev`); `encode_batch`
 pads, truncates or windows the rows on the device -- through the host forms of the C ABI into NumPy arrays, or with
 `device=True` on torch tensors without the ids ever leaving the device.  `mask_tokens` masks such rows for the masked-LM
-objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident.  `decode_batch`
+objective (swt_mlm_mask), from `encode_batch(..., mlm={...})` or on rows that stay resident; `corrupt_spans` gives
+them the span noise of SpanBERT, T5 and BART (swt_denoise_plan / swt_denoise_rows).  `decode_batch`
 spells rows of dense ids back as text (swt_decode_plan / swt_decode_rows).  `align_word_labels`,
 `answer_positions` and `best_answers` make the labels of token classification and extractive QA, and a QA model's best spans,
 from the rows of a batch (swt_label_words, swt_answer_positions, swt_answer_best)."""
@@ -761,6 +762,150 @@ def mask_tokens(tok, input_ids, probability=0.15, whole_word=True, seed=0, epoch
     if return_selected:
         res["selected"] = out["selected"]
     res.update((name, int(x)) for name, x in zip(MLM_COUNTS, info))
+    return res
+
+
+DENOISE_COUNTS = ("n_eligible", "n_noise", "n_runs", "n_runs_returned", "n_rows_cut", "max_length", "max_label_length")
+DENOISE_MODES = {"mask": N.DENOISE_MASK, "sentinel": N.DENOISE_SENTINEL, "infill": N.DENOISE_INFILL}
+DENOISE_SPAN_MAX = N.DENOISE_LEN_MAX + 1
+
+
+def _denoise_lengths(mean_span_length=3.0, lengths="geometric", max_span_length=10):
+    """-> (len_below, mean): the integer table of swt_denoise_spec -- len_below[k] = floor(P(L <= k + 1) * 2^32), one entry per
+    length but the last -- and the mean length of that very table, 1 + sum(1 - len_below[k] / 2^32).  "fixed": L =
+    mean_span_length, an integer; "geometric": P(L) ~ (1 - p)^(L - 1) with p = 1 / mean_span_length, "poisson": P(L) ~
+    mean_span_length^L / L!, both over 1 .. max_span_length; a list: P(L = 1), P(L = 2), ... itself."""
+    mean = float(mean_span_length)
+    if isinstance(lengths, str):
+        if lengths not in ("fixed", "geometric", "poisson"):
+            raise ValueError("lengths: 'geometric', 'poisson', 'fixed' or a list of probabilities")
+        if not 1.0 <= mean <= DENOISE_SPAN_MAX:  # (false for a NaN)
+            raise ValueError("mean_span_length lies in [1, %d]" % DENOISE_SPAN_MAX)
+        if int(max_span_length) != max_span_length or not 1 <= max_span_length <= DENOISE_SPAN_MAX:
+            raise ValueError("max_span_length: an integer in [1, %d]" % DENOISE_SPAN_MAX)
+        if lengths == "fixed":
+            if mean != int(mean):
+                raise ValueError("lengths='fixed': mean_span_length is an integer")
+            weights = [0.0] * (int(mean) - 1) + [1.0]
+        elif lengths == "geometric":
+            weights = [(1.0 - 1.0 / mean) ** k for k in range(int(max_span_length))]
+        else:
+            weights, w = [], 1.0
+            for k in range(1, int(max_span_length) + 1):
+                w *= mean / k
+                weights.append(w)
+    else:
+        weights = [float(p) for p in lengths]
+        if not 1 <= len(weights) <= DENOISE_SPAN_MAX or not all(p >= 0.0 for p in weights) or abs(sum(weights) - 1.0) > 1e-9:
+            raise ValueError("lengths: 1 to %d probabilities, none negative, that add up to 1" % DENOISE_SPAN_MAX)
+    total, below, acc = sum(weights), [], 0.0
+    for w in weights[:-1]:
+        acc += w
+        below.append(min(int(acc / total * 4294967296.0), 1 << 32))
+    return below, 1.0 + sum(1.0 - b / 4294967296.0 for b in below)
+
+
+def _denoise_thresholds(mode="sentinel", noise_density=0.15, mean_span_length=3.0, lengths="geometric", max_span_length=10, seed=0,
+                        epoch=0, target_length=None):
+    """-> (mode, start_below, len_below): the integers of swt_denoise_spec, or the ValueError for arguments that give none.
+    start_below = noise_density / (the table's own mean length), floored as _mlm_thresholds floors."""
+    if mode not in DENOISE_MODES:
+        raise ValueError("mode: 'sentinel', 'infill' or 'mask'")
+    if not 0.0 <= float(noise_density) <= 1.0:
+        raise ValueError("noise_density lies in [0, 1]")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed lies in [0, 2^64)")
+    if not 0 <= int(epoch) < 1 << 32:
+        raise ValueError("epoch lies in [0, 2^32)")
+    if target_length is not None and (int(target_length) != target_length or not 1 <= target_length < 1 << 31):
+        raise ValueError("target_length: None or an integer in [1, 2^31)")
+    len_below, mean = _denoise_lengths(mean_span_length, lengths, max_span_length)
+    return DENOISE_MODES[mode], int(float(noise_density) / mean * 4294967296.0), len_below
+
+
+def _denoise_sentinels(voc, sentinels):
+    """the dense ids of the sentinels: strings through the vocabulary's index, ids as they are; None: "<extra_id_0>", "<extra_id_1>",
+    ... as far as the vocabulary holds them"""
+    if sentinels is None:
+        sentinels = []
+        while "<extra_id_%d>" % len(sentinels) in voc.index:
+            sentinels.append("<extra_id_%d>" % len(sentinels))
+    elif isinstance(sentinels, str) or not isinstance(sentinels, (list, tuple)):
+        raise TypeError("sentinels: a list of token strings or of dense ids")
+    ids = []
+    for s in sentinels:
+        if isinstance(s, str):
+            if s not in voc.index:
+                raise ValueError("sentinel %r has no id: add_special_tokens gives it one" % s)
+            ids.append(voc.index[s])
+        elif isinstance(s, (int, np.integer)) and not isinstance(s, bool) and 0 <= int(s) < 1 << 31:
+            ids.append(int(s))
+        else:
+            raise ValueError("sentinel %r: a token string or a dense id" % (s,))
+    if len(ids) < 2:
+        raise ValueError("mode='sentinel' takes two sentinels or more (add_special_tokens([\"<extra_id_0>\", ...]))")
+    return np.array(ids, dtype=np.uint32)
+
+
+def corrupt_spans(tok, input_ids, mode="sentinel", noise_density=0.15, mean_span_length=3.0, lengths="geometric", max_span_length=10,
+                  sentinels=None, whole_word=True, seed=0, epoch=0, target_length=None):
+    """SubwordTokenizer.corrupt_spans: a NumPy array through swt_denoise_plan / swt_denoise_rows, a torch tensor on the GPU through
+    the `_dev` forms on the current device and stream, with `info` the only read-back -- the plan's in "sentinel" mode, where it
+    gives the width of the labels."""
+    m, start_below, len_below = _denoise_thresholds(mode, noise_density, mean_span_length, lengths, max_span_length, seed, epoch,
+                                                    target_length)
+    voc = tok._batch_vocabulary()
+    sentinel, squeeze = m == N.DENOISE_SENTINEL, m != N.DENOISE_MASK
+    sent = _denoise_sentinels(voc, sentinels) if sentinel else None
+    spec = lambda ids64, label_width: N.denoise_spec(m, voc.cls_tab.size, voc.mask_id, voc.special["pad"], start_below, len_below,
+                                                     sent.size if sentinel else 0, label_width, seed, epoch, whole_word, ids64)
+    any_width = (1 << 32) - 1 if target_length is None else int(target_length)
+    if isinstance(input_ids, np.ndarray):
+        if input_ids.dtype not in (np.int32, np.int64) or input_ids.ndim != 2 or not input_ids.flags.c_contiguous:
+            raise TypeError("input_ids: a 2-D C-contiguous array of int32 or int64")
+        ids64 = input_ids.dtype == np.int64
+        info = N.denoise_plan(input_ids, voc.cls_tab, spec(ids64, any_width)) if sentinel else None
+        label_width = 0 if not sentinel else int(info[6]) if target_length is None else int(target_length)
+        out = N.denoise_rows(input_ids, voc.cls_tab, sent, spec(ids64, label_width), info=not sentinel)
+        if not sentinel:
+            info = out["info"]
+    else:
+        import torch
+        if not isinstance(input_ids, torch.Tensor) or not input_ids.is_cuda or input_ids.dtype not in (torch.int32, torch.int64) \
+                or input_ids.dim() != 2 or not input_ids.is_contiguous():
+            raise TypeError("input_ids: a 2-D C-contiguous NumPy array, or torch tensor on the GPU, of int32 or int64")
+        dev, ids64 = input_ids.device, input_ids.dtype == torch.int64
+        rows, width = input_ids.shape
+        with torch.cuda.device(dev):
+            if voc.d_mlm is None or voc.d_mlm[0] != dev:
+                voc.d_mlm = (dev, torch.from_numpy(voc.cls_tab).to(dev), torch.from_numpy(voc.rand_ids.view(np.int32)).to(dev))
+            d_cls, stream = voc.d_mlm[1], torch.cuda.current_stream().cuda_stream
+            d_info = torch.empty(len(DENOISE_COUNTS), dtype=torch.int64, device=dev)
+            p = lambda t: None if t is None else t.data_ptr() or d_info.data_ptr()  # a tensor of no element still needs an address
+            info = None
+            if sentinel:
+                N.check(N.lib().swt_denoise_plan_dev(p(input_ids), rows, width, p(d_cls), C.byref(spec(ids64, any_width)), p(d_info), stream))
+                info = d_info.cpu().numpy()
+            label_width = 0 if not sentinel else int(info[6]) if target_length is None else int(target_length)
+            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+            out = {"input_ids": torch.empty_like(input_ids),
+                   "labels": new((rows, label_width), input_ids.dtype) if sentinel else None if squeeze else torch.empty_like(input_ids),
+                   "attention_mask": new((rows, width), torch.uint8) if squeeze else None,
+                   "length": new((rows,), torch.int32) if squeeze else None,
+                   "label_length": new((rows,), torch.int32) if sentinel else None}
+            d_sent = torch.from_numpy(sent.view(np.int32)).to(dev) if sentinel else None
+            N.check(N.lib().swt_denoise_rows_dev(p(input_ids), rows, width, p(d_cls), p(d_sent), C.byref(spec(ids64, label_width)),
+                                                 p(out["input_ids"]), p(out["attention_mask"]), p(out["length"]), p(out["labels"]),
+                                                 p(out["label_length"]), None if sentinel else p(d_info), stream))
+            if not sentinel:
+                info = d_info.cpu().numpy()
+    res = {"input_ids": out["input_ids"]}
+    if squeeze:
+        res.update(attention_mask=out["attention_mask"], length=out["length"])
+    res["labels"] = out["labels"] if m != N.DENOISE_INFILL else input_ids
+    if sentinel:
+        res["label_length"] = out["label_length"]
+    res.update((name, int(x)) for name, x in zip(DENOISE_COUNTS, info))
     return res
 
 

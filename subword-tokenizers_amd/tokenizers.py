@@ -269,6 +269,34 @@ class SubwordTokenizer:
         [0, 1], mask_share + random_share > 1, a seed outside [0, 2^64) or an epoch outside [0, 2^32)."""
         return batching.mask_tokens(self, input_ids, probability, whole_word, seed, epoch, mask_share, random_share, return_selected)
 
+    def corrupt_spans(self, input_ids, mode: str = "sentinel", noise_density: float = 0.15, mean_span_length: float = 3.0,
+                      lengths="geometric", max_span_length: int = 10, sentinels=None, whole_word: bool = True, seed: int = 0,
+                      epoch: int = 0, target_length: Optional[int] = None) -> dict:
+        """Rows of dense ids (any "input_ids" of encode_batch, packed ones included) with span noise for a denoising objective,
+        on the device (swt_denoise_plan, swt_denoise_rows).  A unit is a word -- a token and the '##' tokens
+        after it; with whole_word=False every token.  Every unit starts a span with probability noise_density / (the mean span
+        length); the span covers L units, L drawn from `lengths`: "geometric" (SpanBERT; p = 1 / mean_span_length) or "poisson"
+        (BART; lambda = mean_span_length), both cut to 1 .. max_span_length <= 32, "fixed" (L = mean_span_length), or a list
+        [P(L=1), P(L=2), ...].  Spans may overlap and end at the row's end, so the density reached is n_noise / n_eligible of
+        the result, not a promise.  [PAD], [UNK], [CLS], [SEP], [MASK] and special added tokens are never noise and cut a
+        span into two runs.  The draws are Philox4x32-10 by (seed, epoch, row, column) and shared with no other call.
+        mode "mask": noise columns become mask_id() in place -> "input_ids", "labels" (the id on noise columns, -100 elsewhere).
+        mode "sentinel" (T5): every run collapses to sentinels[k], k counting the row's runs -> "input_ids" (padded with
+        [PAD]), "attention_mask", "length", "labels" (sentinels[0], run 0, sentinels[1], run 1, ..., a closing sentinel, then
+        -100; as wide as the longest row of them, or target_length, which cuts) and "label_length" (before the cut).
+        `sentinels`: token strings (add_special_tokens gives them ids) or dense ids, two or more; None: "<extra_id_0>",
+        "<extra_id_1>", ... as far as the vocabulary holds them.  Runs beyond len(sentinels) - 1 stay as they were.
+        mode "infill" (BART): every run collapses to one mask_id() -> "input_ids", "attention_mask", "length", and "labels",
+        which are the rows given.
+        input_ids: a 2-D C-contiguous int32 or int64 NumPy array, or such a torch tensor on the GPU (the current stream; the ids
+        never leave the device, the seven counts are the one read-back); anything else raises TypeError.
+        Every mode adds "n_eligible", "n_noise", "n_runs", "n_runs_returned", "n_rows_cut", "max_length", "max_label_length".
+        ValueError: an unknown mode or lengths, a noise_density outside [0, 1], a mean_span_length outside [1, 32], a
+        max_span_length outside 1 .. 32, probabilities that are negative or do not add up to 1, a sentinel string without an id,
+        fewer than two sentinels, a seed outside [0, 2^64), an epoch outside [0, 2^32), a target_length below 1."""
+        return batching.corrupt_spans(self, input_ids, mode, noise_density, mean_span_length, lengths, max_span_length, sentinels,
+                                      whole_word, seed, epoch, target_length)
+
     # -- fine-tuning labels (not in the reference; batching.py, DESIGN.md 4.14).  They read a batch and no encoder state.
     def align_word_labels(self, batch: dict, word_labels, label_all_tokens: bool = False, inside=None, side: Optional[int] = None,
                           ignore_index: int = -100) -> dict:
